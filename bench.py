@@ -25,6 +25,9 @@ After the K timed steps the same step runs back to back for --sustain-s seconds 
 brought up beside it, proven with a 16-byte all-gather and used only if every rank saw it work -- otherwise the run
 finishes on gloo and says so in `collective_backend` (setup_collectives).
 
+--dump-outputs DIR writes what the last timed step computed to DIR/<name>.npy (dump_outputs): the inputs are fixed by
+the workload's seed, so two builds of the project can be compared output for output.
+
 With more than one rank the line also carries what SURVEY.md 8e lists beside the encrypt-only rate, all of it AFTER the
 timed steps and never part of `value`: `gather_ms` (the ciphertext all-gather: RCCL over xGMI, or -- when RCCL did not
 come up, e.g. the one-device dry run -- a gloo gather to rank 0), `encrypt_plus_gather_gib_s` (one step + the gather,
@@ -310,6 +313,49 @@ def cpu_baseline(workload, sample=None, all_cores=True):
     except Exception:
         pass
     return res
+
+
+def cpu_baseline_in_child(workload):
+    """cpu_baseline() in a fresh interpreter that never opens the GPU, so that its forked workers do not inherit this
+    process's device state.  Returns the same dict."""
+    import subprocess
+    code = ("import json, sys; sys.path.insert(0, %r); import bench; print(json.dumps(bench.cpu_baseline(%r)))"
+            % (ROOT, workload))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+    if r.returncode != 0:
+        raise RuntimeError("cpu_baseline child failed (rc %d): %s" % (r.returncode, r.stderr[-1000:]))
+    return json.loads(r.stdout.strip().splitlines()[-1])
+
+
+DUMP_BYTES = 8 << 20                 # --dump-outputs: bytes kept per array (32 MiB as float32)
+
+
+def dump_outputs(torch, out_dir, arrays, budget=DUMP_BYTES, seed=0):
+    """--dump-outputs: every tensor of `arrays` ({name: uint8 or int32 tensor}) as out_dir/<name>.npy, float32 (byte
+    values 0..255, or the integer).  An array longer than `budget` values is reduced to a fixed sample of 16-byte blocks -- numpy
+    default_rng(seed), the first and the last block always among them -- and out_dir/<name>_index.npy (float64) holds
+    the byte offset of each sampled block, in order; the last block of the array may be shorter than 16 bytes.
+    Returns {name: number of values written}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, t in arrays.items():
+        t = t.reshape(-1)
+        n = t.numel()
+        if n <= budget:
+            vals = t.cpu().numpy()
+        else:
+            nblk = (n + 15) // 16
+            pick = np.random.default_rng(seed).choice(nblk - 2, budget // 16 - 2, replace=False) + 1
+            starts = np.concatenate(([0], np.sort(pick), [nblk - 1])) * 16
+            pos = (starts[:, None] + np.arange(16)).reshape(-1)
+            pos = pos[pos < n]
+            vals = t[torch.from_numpy(pos).to(t.device)].cpu().numpy()
+            np.save(os.path.join(out_dir, name + "_index.npy"), starts.astype(np.float64))
+        np.save(os.path.join(out_dir, name + ".npy"), vals.astype(np.float32))
+        written[name] = int(vals.size)
+    return written
 
 
 def setup_collectives(a, torch, rank, world, local, dev):
@@ -612,11 +658,17 @@ def build_parser():
                          "the ciphertext all-gather, and the C host's uaes_mgpu_ctr_encrypt_gather sends its slice through "
                          "ncclSend / ncclRecv to itself (UAES_GATHER_FORCE_RCCL) -- so that a one-GPU box executes the "
                          "code an 8-GPU run depends on.  Says nothing about xGMI; never part of `value`.")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float32; outputs "
+                         "over %d MiB as a fixed sample of 16-byte blocks, offsets in DIR/<name>_index.npy; with more "
+                         "than one rank every rank writes <name>_rank<r>.npy)" % (DUMP_BYTES >> 20))
     return ap
 
 
 def main():
     a = build_parser().parse_args()
+    if a.steps < 1:
+        sys.exit("--steps must be at least 1")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(a.gpus)
@@ -750,6 +802,21 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     per_step_ms = [ev[i].elapsed_time(ev[i + 1]) for i in range(a.steps)]
+    dumped = None
+    if a.dump_outputs:
+        # what a caller of the timed path receives from its last step, before anything below writes to dst again
+        main_out = "plaintext" if a.workload in ("cbc-dec", "cfb-dec", "ocb-dec") else "ciphertext"
+        if a.workload == "cmac":
+            arrays = {"mac": torch.frombuffer(bytearray(mac16), dtype=torch.uint8)}
+        else:
+            arrays = {main_out: dst[:n]}
+        if a.workload in ("gcm", "ocb"):
+            arrays["tag"] = dst[n:n + 16]
+        if a.workload == "ocb-dec":
+            arrays["status"] = ocb_status
+        if world > 1:
+            arrays = {"%s_rank%d" % (k, rank): v for k, v in arrays.items()}
+        dumped = dump_outputs(torch, a.dump_outputs, arrays, budget=DUMP_BYTES // world)
     # Untimed for `value`, after the measured steps: the SUSTAINED rate.  K steps after 150 ms of settling are a
     # window of ~12 ms; the power manager keeps adjusting for longer than that (1605 GiB/s in the window,
     # 1512-1524 over 30 000 steps).  So the same step is queued back to back for >= --sustain-s seconds (HIP events on
@@ -980,6 +1047,8 @@ def main():
                                  "sclk_mhz": None if sclk_mhz is None else round(sclk_mhz, 0),
                                  "note": "the same step back to back after the K timed steps; not part of `value`"}
             line["roofline"]["frac_sustained"] = round(2.0 * n / (sustained["ms_per_step"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
+        if dumped is not None:
+            line["dump_outputs"] = {"dir": a.dump_outputs, "values": dumped}
         line.update(coll_info)
         line.update(gather_info)
         if c_gather is not None:
@@ -987,7 +1056,7 @@ def main():
         if world == 1 and a.workload == "ctr" and n == GIB and not a.no_other_configs:
             line["other_configs"] = other_configs(torch, uaes, dev, st)
         if not a.no_cpu and world == 1:
-            line["cpu_baseline"] = cpu_baseline(a.workload)
+            line["cpu_baseline"] = cpu_baseline_in_child(a.workload)
         print(json.dumps(line), file=_LINE_OUT, flush=True)
     if stuck_extra and not dist:
         sys.stdout.flush()

@@ -254,3 +254,22 @@ def test_bench_eight_ranks_flagless_dry_run_reports_everything_8e_lists():
     assert line["gathered_stream_digest_ok"] is True and "whole 8 GiB stream" in line["gathered_stream_check"]
     cg = line["c_gather"]
     assert cg.get("stream_digest_ok") is True and cg["shard0_equals_own_step"] is True and cg["ms"] > 0, cg
+
+
+def test_bench_three_ranks_flagless_dry_run_on_one_device():
+    """the same flagless multi-rank command on this box's one GPU (--single-device is the only addition) with three
+    ranks, so that no more than five processes hold the device (pytest, the launcher, the ranks): the line must hold the
+    gather, encrypt + gather, every gathered 1 GiB shard against the reference's digest of that shard of the C5 stream,
+    and the C host's own gather with the same digests -- RCCL refuses several ranks on one device, so the collective is
+    the labelled gloo stand-in here."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    env.update(UAES_BENCH_RCCL_WAIT_S="60")
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--steps", "3", "--warmup", "1", "--single-device"]
+    line = _one_json_line(subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1200))
+    assert line["n_gpus"] == 3 and line["verified"] is True and line["config"]["bytes_per_gpu"] == GIB
+    assert line["verified_shards"].startswith("every rank hashed its whole shard")
+    assert line["gather_ms"] > 0 and line["encrypt_plus_gather_gib_s"] > 0
+    assert line["gathered_stream_digest_ok"] is True
+    assert line["gathered_stream_check"].startswith("SHA-256 of each of the 3 gathered 1 GiB shards"), line["gathered_stream_check"]
+    cg = line["c_gather"]
+    assert cg.get("stream_digest_ok") is True and cg["shard0_equals_own_step"] is True and cg["ms"] > 0, cg

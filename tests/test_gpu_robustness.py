@@ -304,11 +304,11 @@ def test_single_process_multi_gpu_entry_points(orc):
 
 def test_single_process_multi_gpu_on_distinct_devices(orc):
     """the same on DISTINCT devices (per-device contexts, hipSetDevice per worker thread, no peer access
-    between them): every visible GPU once, and a list that visits them in reverse and device 0 twice"""
+    between them): every visible GPU once, and a list that visits them in reverse and device 0 twice -- [0] and
+    [0, 0] on a one-GPU box"""
     import torch
-    if torch.cuda.device_count() < 2:
-        pytest.skip("needs 2 GPUs: this box has %d" % torch.cuda.device_count())
-    for devlist in _mgpu_device_lists()[1:]:
+    n = torch.cuda.device_count()
+    for devlist in (list(range(n)), list(range(n - 1, -1, -1)) + [0]):
         _check_mgpu(orc, devlist)
 
 
@@ -807,8 +807,11 @@ def test_one_launch_gcm_under_oversubscription(orc):
                     st.synchronize()
                     assert bytes(d_out.cpu().numpy()) == want, (t, rep, n)
                     assert int(status.item()) == 0 and bytes(back.cpu().numpy()) == data, (t, rep, n)
-                    d_out[n // 2] ^= 1
-                    back.fill_(0xCC)
+                    # the forgery and the refill go on `st` too: on the default stream, which this thread shares with
+                    # the others, they could still be queued when the decryption on `st` reads the text
+                    with torch.cuda.stream(st):
+                        d_out[n // 2] ^= 1
+                        back.fill_(0xCC)
                     uaes.gcm_decrypt_dev(key, nonce, d_aad, d_out, n, back, status, stream=st)
                     st.synchronize()
                     assert int(status.item()) == 0x1A and int((back != 0xCC).sum()) == 0, (t, rep, n)
