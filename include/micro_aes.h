@@ -50,7 +50,9 @@
 #define EAXP     0
 #define SIV      0
 #define OCB      1          /* RFC 7253: block-parallel, offsets from the Gray code (uaes_ocb.hip) */
-#define POLY1305 0
+#ifndef POLY1305             /* micro_aes.h:52 -- Poly1305-AES (uaes_poly1305.hip); every library exports        */
+#define POLY1305 0          /* AES_Poly1305, a caller built with -DPOLY1305=1 sees its prototype (below)        */
+#endif
 #define MICRO_RJNDL 0
 
 #ifndef AES_PADDING          /* micro_aes.h:79 -- 0 zeros, 1 PKCS#7, 2 ISO/IEC 7816-4; a caller */
@@ -322,6 +324,12 @@ char GCM_SIV_decrypt(const uint8_t *key, const uint8_t *nonce,
 
 void AES_CMAC(const uint8_t *key,
               const void *data, const size_t dataSize, uint8_t mac[16]);
+
+#if POLY1305
+/* keys = k (AES_KEYLENGTH bytes) || r (16 bytes); mac = Poly1305-AES of data under nonce (micro_aes.h:444-450) */
+void AES_Poly1305(const uint8_t *keys, const uint8_t nonce[16],
+                  const void *data, const size_t dataSize, uint8_t mac[16]);
+#endif
 
 /* Not in the reference: what happens when a `void` function above cannot do its work
  * (no usable HIP device, an allocation or launch failure -- there is no CPU path).  The

@@ -271,6 +271,22 @@ int uaes_cbc_encrypt_batch(int keybits, const uint8_t *key, const uint8_t *ivs, 
 int uaes_cmac_batch(int keybits, const uint8_t *key, size_t nmsg, size_t msg_bytes,
                     const void *data, uint8_t *macs);
 
+/* Poly1305-AES (micro_aes.c:1955-1997): keys = k (keybits / 8 bytes) || r (16 bytes), mac = (h + AES_k(nonce)) mod
+ * 2^128 with h the Poly1305 polynomial in the clamped r.  Block-parallel on the VALU (uaes_poly1305.hip): one
+ * workgroup for a short message, chunk workgroups + a fold kernel beyond; AES_k(nonce) runs on the device too.
+ * data may be NULL when dataSize is 0 (mac = AES_k(nonce)).  uaes_poly1305 takes host or device data (device data
+ * produced on another stream: uaes_set_producer_stream) and follows the host policy; uaes_poly1305_dev enqueues on
+ * `stream` (a hipStream_t, NULL = default) and returns: d_data, d_mac device memory, keys and nonce host memory, the
+ * per-stream scratch goes back with uaes_stream_release, and the call can be captured into a graph.
+ * uaes_poly1305_batch: one key pair, nmsg nonces (16 bytes each) and nmsg messages of msg_bytes each back to back,
+ * one wave per message; nonces, data and macs host or device memory, macs = nmsg * 16 bytes. */
+int uaes_poly1305(int keybits, const uint8_t *keys, const uint8_t nonce[16],
+                  const void *data, size_t dataSize, uint8_t mac[16]);
+int uaes_poly1305_dev(int keybits, const uint8_t *keys, const uint8_t nonce[16],
+                      const void *d_data, size_t len, void *d_mac, void *stream);
+int uaes_poly1305_batch(int keybits, const uint8_t *keys, const uint8_t *nonces, size_t nmsg,
+                        size_t msg_bytes, const void *data, uint8_t *macs);
+
 /* ---- GCM-SIV: replaces GCM_SIV_encrypt / GCM_SIV_decrypt ---------------------
  * RFC 8452; micro_aes.c:1418-1516.  12-byte nonce, 16-byte tag appended.  Per-
  * nonce keys are derived with AES (GCM_SIVsetup), the tag is AES over POLYVAL
@@ -525,6 +541,10 @@ void uaes_debug_gather_stats(unsigned long out[5]);
 int uaes_debug_plan(int mode, int dir, size_t a, size_t b, unsigned flags, int out[4]);
 const char *uaes_debug_arrangement_name(int id);
 void uaes_debug_plan_disable(unsigned mask);
+/* Poly1305's planner (csrc/uaes_plan.h, its own rows): the arrangement name ("poly.small" / "poly.chunks" /
+ * "poly.batch") for one message of len bytes (nmsg <= 1) or a batch of nmsg >= 2 such messages; out (may be NULL)
+ * = launches, workgroups of the main kernel, blocks per thread.  Works without a device (a 256-CU MI355X). */
+const char *uaes_debug_plan_poly1305(size_t len, size_t nmsg, int out[3]);
 
 /* Test hooks of the one-launch GCM / GCM-SIV / streamed-piece arrangements (chunk workgroups + one preparing workgroup
  * in ONE launch; whoever of them arrives last on a counter word folds the chunk hashes and makes the tag -- nobody

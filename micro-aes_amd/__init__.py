@@ -42,6 +42,7 @@ EXPORTS = [
     "uaes_ocb_encrypt_ex", "uaes_ocb_decrypt_ex",
     "uaes_cmac", "uaes_ccm_encrypt", "uaes_ccm_decrypt", "uaes_gcmsiv_encrypt", "uaes_gcmsiv_decrypt",
     "uaes_ocb_encrypt", "uaes_ocb_decrypt", "uaes_ocb_dev",
+    "uaes_poly1305", "uaes_poly1305_dev", "uaes_poly1305_batch", "uaes_debug_plan_poly1305",
     "uaes_mgpu_ctr_xcrypt_at", "uaes_mgpu_xts_sectors", "uaes_mgpu_ctr_encrypt_gather", "uaes_debug_gather_stats", "uaes_debug_gcm_look", "uaes_debug_gcm_chunk_folds",
     "uaes_debug_plan", "uaes_debug_arrangement_name", "uaes_debug_plan_disable",
     "uaes_mgpu_ecb_encrypt", "uaes_mgpu_ecb_decrypt", "uaes_mgpu_gcm_encrypt", "uaes_mgpu_gcm_decrypt",
@@ -66,7 +67,7 @@ COMPAT_EXPORTS = [
     "AES_GCM_encrypt_ivlen", "AES_GCM_decrypt_ivlen", "AES_GCM_encrypt_lens", "AES_GCM_decrypt_lens",
     "AES_CCM_encrypt_lens", "AES_CCM_decrypt_lens", "AES_OCB_encrypt_lens", "AES_OCB_decrypt_lens",
     "AES_CCM_encrypt", "AES_CCM_decrypt", "AES_CMAC", "GCM_SIV_encrypt", "GCM_SIV_decrypt",
-    "AES_OCB_encrypt", "AES_OCB_decrypt",
+    "AES_OCB_encrypt", "AES_OCB_decrypt", "AES_Poly1305",
     "AES_CBC_encrypt", "AES_CBC_decrypt", "AES_CFB_encrypt", "AES_CFB_decrypt", "AES_OFB_encrypt", "AES_OFB_decrypt",
 ]
 
@@ -136,6 +137,11 @@ def engine():
         getattr(L, n).argtypes = [i, vp, vp, sz, sz, vp, sz, vp, sz, vp]
     L.uaes_ghash.argtypes = [vp, vp, sz, vp, sz, vp]
     L.uaes_cmac.argtypes = [i, vp, vp, sz, vp]
+    L.uaes_poly1305.argtypes = [i, vp, vp, vp, sz, vp]
+    L.uaes_poly1305_dev.argtypes = [i, vp, vp, vp, sz, vp, vp]
+    L.uaes_poly1305_batch.argtypes = [i, vp, vp, sz, sz, vp, vp]
+    L.uaes_debug_plan_poly1305.argtypes = [sz, sz, C.POINTER(C.c_int)]
+    L.uaes_debug_plan_poly1305.restype = C.c_char_p
     for n in ("uaes_cbc_encrypt", "uaes_cbc_decrypt", "uaes_cbc_decrypt_blocks", "uaes_cfb_encrypt", "uaes_cfb_decrypt", "uaes_ofb_xcrypt"):
         getattr(L, n).argtypes = [i, vp, vp, vp, sz, vp]
     for n in ("uaes_ccm_encrypt", "uaes_ccm_decrypt", "uaes_gcmsiv_encrypt", "uaes_gcmsiv_decrypt",
@@ -199,7 +205,7 @@ def engine():
         if n.startswith("uaes_debug_") and not hasattr(L, n):
             continue
         if n not in ("uaes_last_error", "uaes_version", "uaes_gcm_key_free", "uaes_gcm_stream_abort", "uaes_debug_gather_stats", "uaes_debug_gcm_look",
-                     "uaes_debug_arrangement_name", "uaes_debug_plan_disable"):
+                     "uaes_debug_arrangement_name", "uaes_debug_plan_disable", "uaes_debug_plan_poly1305"):
             getattr(L, n).restype = i
     _lib = L
     return L
@@ -427,6 +433,47 @@ def AES_CMAC(key, data):
     o = _out(16)
     _check(engine().uaes_cmac(_bits(key), _in(key), _in(data), len(data), o), "AES_CMAC")
     return bytes(o)
+
+
+def _poly_bits(keys):
+    bits = (len(keys) - 16) * 8
+    if bits not in (128, 192, 256):
+        raise ValueError("keys = k || r: 32, 40 or 48 bytes (got %d)" % len(keys))
+    return bits
+
+
+def AES_Poly1305(keys, nonce, data):
+    """micro_aes.c:1955.  keys = k || r (key size from len(keys) - 16); returns the 16-byte mac."""
+    o = _out(16)
+    _check(engine().uaes_poly1305(_poly_bits(keys), _in(keys), _fixed(nonce, 16, "nonce"), _in(data), len(data), o),
+           "AES_Poly1305")
+    return bytes(o)
+
+
+def poly1305_batch(keys, nonces, messages):
+    """One key pair, a nonce per message, equal-sized messages, one GPU wave each: == [AES_Poly1305(keys, n, m)]."""
+    n = len(messages)
+    if len(nonces) != n:
+        raise ValueError("one nonce per message")
+    if n == 0:
+        return []
+    size = len(messages[0])
+    if any(len(m) != size for m in messages):
+        raise ValueError("equal-sized messages")
+    if any(len(x) != 16 for x in nonces):
+        raise ValueError("16-byte nonces")
+    o = _out(n * 16)
+    _check(engine().uaes_poly1305_batch(_poly_bits(keys), _in(keys), _in(b"".join(nonces)), n, size,
+                                        _in(b"".join(messages)), o), "uaes_poly1305_batch")
+    raw = bytes(o)
+    return [raw[16 * i:16 * i + 16] for i in range(n)]
+
+
+def poly1305_plan(len, nmsg=1):
+    """What a Poly1305 call would run (uaes_debug_plan_poly1305): (arrangement, launches, workgroups, blocks per thread)."""
+    out = (C.c_int * 3)()
+    name = engine().uaes_debug_plan_poly1305(len, nmsg, out)
+    return name.decode(), out[0], out[1], out[2]
 
 
 def _ccm_nonce(nonce):
@@ -828,6 +875,12 @@ def ocb_dev(key, nonce, aad, src, nbytes, dst, decrypt=False, status=None, strea
     _check(engine().uaes_ocb_dev(_bits(key), _in(key), _fixed(nonce, 12, "nonce"), 1 if decrypt else 0, _ptr(aad),
                                  0 if aad is None else aad.numel(), _ptr(src), nbytes, _ptr(dst),
                                  _ptr(status), _stream(stream)), "uaes_ocb_dev")
+
+
+def poly1305_dev(keys, nonce, src, nbytes, mac, stream=None):
+    """Enqueue the Poly1305-AES mac of nbytes of the device tensor src into the 16-byte device tensor mac."""
+    _check(engine().uaes_poly1305_dev(_poly_bits(keys), _in(keys), _fixed(nonce, 16, "nonce"), _ptr(src), nbytes,
+                                      _ptr(mac), _stream(stream)), "uaes_poly1305_dev")
 
 
 def gcm_partial_dev(key, nonce, aad, total_aad_len, ct_shard, shard_len, shard_offset, total_len, partial,

@@ -6,6 +6,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#define POLY1305 1                  /* the libraries export AES_Poly1305 whatever a caller's switch says */
 #include "../../include/micro_aes.h"
 #include "../../include/uaes_hip.h"
 
@@ -205,6 +206,11 @@ char AES_CCM_decrypt(const uint8_t *key, const uint8_t *nonce,
 void AES_CMAC(const uint8_t *key, const void *data, const size_t dataSize, uint8_t mac[16])
 {
     must("AES_CMAC", uaes_cmac(KB, key, data, dataSize, mac));
+}
+
+void AES_Poly1305(const uint8_t *keys, const uint8_t nonce[16], const void *data, const size_t dataSize, uint8_t mac[16])
+{
+    must("AES_Poly1305", uaes_poly1305(KB, keys, nonce, data, dataSize, mac));
 }
 
 /* CTS (micro_aes.h:56) is the caller's compile-time choice too: with CTS 0 the reference's CBC pads its last

@@ -234,6 +234,16 @@ int uaesk_ticket(void *stream, void *pinned_flag, unsigned seq, const void *d_sr
  * { shader cycles, reference ticks } (two 64-bit words) to d_out16                               */
 int uaesk_clock_probe(void *stream, void *d_out16, unsigned long long ticks_100mhz);
 
+/* Poly1305-AES (uaes_poly1305.hip).  r16 = the r half of the key pair and nonce16 are HOST memory (clamped and
+ * passed as launch arguments); data, mac16 and scratch device memory.  scratch holds uaesk_poly1305_scratch_bytes(len)
+ * (0 for the one-workgroup arrangement: NULL is fine then); the call leaves it zeroed.  The batch form takes nmsg
+ * messages of msg_bytes each back to back, nonces (16 bytes each) and macs in device memory.                   */
+size_t uaesk_poly1305_scratch_bytes(size_t len);
+int uaesk_poly1305(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, const uint8_t *r16,
+                   const uint8_t *nonce16, const void *data, size_t len, void *mac16, void *scratch);
+int uaesk_poly1305_batch(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, const uint8_t *r16,
+                         const void *nonces, size_t nmsg, size_t msg_bytes, const void *data, void *macs);
+
 /* Device self-test of the primitives; writes a bitmask of failures.        */
 int uaesk_selftest(void *stream, const uaesk_tables *tb, const uaesk_rk *ek128,
                    const uaesk_rk *dk128, unsigned *d_result);

@@ -2608,6 +2608,94 @@ int uaes_cmac(int keybits, const uint8_t *key, const void *data, size_t dataSize
     DONE(L, rc);
 }
 
+/* ------------------------------------------------------------------------ */
+/* Poly1305-AES (micro_aes.c:1901-1997): keys = k (keybits / 8 bytes) || r (16) */
+/* ------------------------------------------------------------------------ */
+/* AES_k(nonce), the powers of r and the tag run in kernels (uaes_poly1305.hip); the host expands k, and the clamped r
+ * travels as a launch argument.  Every way out wipes the schedule; the chunk partials are zeroed by the fold kernel. */
+int uaes_poly1305(int keybits, const uint8_t *keys, const uint8_t nonce[16],
+                  const void *data, size_t dataSize, uint8_t mac[16])
+{
+    context *c;
+    lane *L;
+    keysched ks;
+    io_plan io;
+    int rc;
+    if (!keys || !nonce || !mac || (dataSize && !data)) return fail(UAES_E_ARG, "NULL pointer");
+    if ((rc = expand_key(&ks, keys, keybits)) != 0) return rc;
+    const uint8_t *r = keys + keybits / 8;
+    if (host_take(data, NULL, dataSize, 0)) {
+        const uaesh_key hk = host_key(&ks);
+        uaesh_poly1305(&hk, r, nonce, (const uint8_t *)data, dataSize, mac);
+        HOST_RET(ks, 0);
+    }
+    if ((rc = enter(&c, &L)) != 0) { burn(&ks, sizeof ks); return rc; }
+    do {
+        const size_t need = uaesk_poly1305_scratch_bytes(dataSize);
+        if ((rc = plan_io(L, data, dataSize, NULL, 0, &io)) != 0) break;
+        if (need && (rc = lane_scratch(L, need, SCRATCH_OTHER)) != 0) break;
+        int k = uaesk_poly1305(L->stream, &c->tb, ks.nr, &ks.ek, r, nonce, io.din, dataSize, L->d_status + 4,
+                               need ? L->scratch : NULL);
+        if (k) { rc = fail(UAES_E_HIP, "poly1305 launch: %s", hipGetErrorString((hipError_t)k)); break; }
+        rc = lane_fetch(L, mac, L->d_status + 4, 16);
+    } while (0);
+    burn(&ks, sizeof ks);
+    DONE(L, rc);
+}
+
+int uaes_poly1305_dev(int keybits, const uint8_t *keys, const uint8_t nonce[16],
+                      const void *d_data, size_t len, void *d_mac, void *stream)
+{
+    context *c;
+    keysched ks;
+    void *scr = NULL;
+    int rc, slot = -1;
+    if (!keys || !nonce || !d_mac || (len && !d_data)) return fail(UAES_E_ARG, "NULL pointer");
+    if ((rc = expand_key(&ks, keys, keybits)) != 0) return rc;
+    const size_t need = uaesk_poly1305_scratch_bytes(len);
+    if ((rc = get_context(&c)) != 0) { burn(&ks, sizeof ks); return rc; }
+    if (need) {
+        pthread_mutex_lock(&c->mu);
+        rc = scratch_pin(c, stream, need, &scr, &slot);
+        pthread_mutex_unlock(&c->mu);
+        if (rc) { burn(&ks, sizeof ks); return fail(UAES_E_HIP, "poly1305 scratch"); }
+    }
+    rc = uaesk_poly1305(stream, &c->tb, ks.nr, &ks.ek, keys + keybits / 8, nonce, d_data, len, d_mac, scr);
+    burn(&ks, sizeof ks);
+    KCHK_PINNED(c, slot, rc);
+    return 0;
+}
+
+int uaes_poly1305_batch(int keybits, const uint8_t *keys, const uint8_t *nonces, size_t nmsg,
+                        size_t msg_bytes, const void *data, uint8_t *macs)
+{
+    context *c;
+    lane *L;
+    keysched ks;
+    io_plan io;
+    const void *d_nonces = NULL;
+    int rc;
+    if (msg_bytes && nmsg > (size_t)-1 / msg_bytes) return fail(UAES_E_ARG, "batch size overflows");
+    if (!keys || (nmsg && (!nonces || !macs)) || (nmsg && msg_bytes && !data)) return fail(UAES_E_ARG, "NULL pointer");
+    if ((rc = expand_key(&ks, keys, keybits)) != 0) return rc;
+    if (nmsg == 0) { burn(&ks, sizeof ks); return 0; }
+    if ((rc = enter(&c, &L)) != 0) { burn(&ks, sizeof ks); return rc; }
+    do {
+        if ((rc = stage_aad(L, nonces, nmsg * 16, &d_nonces)) != 0) break;       /* host nonces -> device */
+        if ((rc = plan_io(L, data, nmsg * msg_bytes, macs, nmsg * 16, &io)) != 0) break;
+        if (io.dout == io.din && io.copy_back) {                  /* MACs must not overwrite unread messages */
+            if (grow_on(L->stream, &L->stage[1], &L->stage_cap[1], nmsg * 16 + 64)) { rc = UAES_E_HIP; break; }
+            io.dout = L->stage[1];
+        }
+        int k = uaesk_poly1305_batch(L->stream, &c->tb, ks.nr, &ks.ek, keys + keybits / 8, d_nonces, nmsg, msg_bytes,
+                                     io.din, io.dout);
+        if (k) { rc = fail(UAES_E_HIP, "poly1305 batch launch: %s", hipGetErrorString((hipError_t)k)); break; }
+        rc = finish_io(&io, nmsg * 16);
+    } while (0);
+    burn(&ks, sizeof ks);
+    DONE(L, rc);
+}
+
 static int ccm_lens_ok(size_t nonceLen, size_t tagLen)
 {
     if (nonceLen < 7 || nonceLen > 13) return fail(UAES_E_ARG, "CCM nonce length %zu (7..13)", nonceLen);
@@ -3759,6 +3847,14 @@ int uaes_debug_plan(int mode, int dir, size_t a, size_t b, unsigned flags, int o
     return 0;
 }
 const char *uaes_debug_arrangement_name(int id) { return uaesk_arrangement_name(id); }
+const char *uaes_debug_plan_poly1305(size_t len, size_t nmsg, int out[3])
+{
+    uaes_plan p;
+    memset(&p, 0, sizeof p);
+    (void)uaesk_plan_poly1305(len, nmsg, &p);
+    if (out) { out[0] = p.launches; out[1] = (int)p.grid; out[2] = (int)p.steps; }
+    return uaesk_poly1305_arrangement_name(p.arrangement);
+}
 void uaes_debug_plan_disable(unsigned mask) { uaesk_plan_disable(mask); }
 
 /* ---- test hooks of the one-launch GCM arrangements (include/uaes_hip.h) ---- */

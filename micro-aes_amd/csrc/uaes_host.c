@@ -761,3 +761,78 @@ int uaesh_ocb(const uaesh_key *k, int decrypt, const uint8_t *nonce, size_t nonc
     free(t);
     return rc;
 }
+
+/* ---- Poly1305-AES (AES_Poly1305, micro_aes.c:1955-1997): h = (h + c_i) r mod 2^130 - 5 in five 26-bit limbs ---- */
+static uint32_t load32le(const uint8_t *p)
+{
+    return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
+}
+static void store32le(uint8_t *p, uint32_t v)
+{
+    p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24);
+}
+
+static void poly_limbs(const uint8_t b[16], uint32_t hibit, uint32_t l[5])
+{
+    const uint32_t w0 = load32le(b), w1 = load32le(b + 4), w2 = load32le(b + 8), w3 = load32le(b + 12);
+    l[0] = w0 & 0x3ffffff;
+    l[1] = ((w0 >> 26) | (w1 << 6)) & 0x3ffffff;
+    l[2] = ((w1 >> 20) | (w2 << 12)) & 0x3ffffff;
+    l[3] = ((w2 >> 14) | (w3 << 18)) & 0x3ffffff;
+    l[4] = (w3 >> 8) | (hibit << 24);
+}
+
+void uaesh_poly1305(const uaesh_key *k, const uint8_t r16[16], const uint8_t nonce[16], const uint8_t *data, size_t len,
+                    uint8_t mac[16])
+{
+    uint8_t rb[16], blk[16];
+    uint32_t r[5], h[5] = { 0, 0, 0, 0, 0 }, c[5], g[5], s[4], mask;
+    uint64_t d[5], t;
+    int i, j;
+    uaesh_encrypt(k->ek, k->nr, nonce, blk);
+    if (!len) { memcpy(mac, blk, 16); memset(blk, 0, sizeof blk); return; }
+    for (i = 0; i < 4; ++i) s[i] = load32le(blk + 4 * i);
+    memcpy(rb, r16, 16);
+    rb[3] &= 15; rb[7] &= 15; rb[11] &= 15; rb[15] &= 15; rb[4] &= 252; rb[8] &= 252; rb[12] &= 252;
+    poly_limbs(rb, 0, r);
+    while (len) {
+        const size_t n = len < 16 ? len : 16;
+        memset(blk, 0, sizeof blk);
+        memcpy(blk, data, n);
+        if (n < 16) blk[n] = 1;
+        poly_limbs(blk, n == 16, c);
+        for (i = 0; i < 5; ++i) h[i] += c[i];
+        for (i = 0; i < 5; ++i) {                    /* d_i = sum_j h_j r_(i-j), the wrapped terms times 5 */
+            d[i] = 0;
+            for (j = 0; j < 5; ++j) d[i] += (uint64_t)h[j] * (j <= i ? r[i - j] : 5 * r[i - j + 5]);
+        }
+        for (i = 0; i < 4; ++i) { d[i + 1] += d[i] >> 26; h[i] = (uint32_t)d[i] & 0x3ffffff; }
+        h[4] = (uint32_t)d[4] & 0x3ffffff;
+        t = h[0] + (d[4] >> 26) * 5;
+        h[0] = (uint32_t)t & 0x3ffffff;
+        h[1] += (uint32_t)(t >> 26);
+        data += n;
+        len -= n;
+    }
+    for (j = 0; j < 2; ++j) {                        /* fully carried: h < 2^130 */
+        for (i = 0; i < 4; ++i) { h[i + 1] += h[i] >> 26; h[i] &= 0x3ffffff; }
+        t = h[4] >> 26; h[4] &= 0x3ffffff; h[0] += (uint32_t)t * 5;
+    }
+    h[1] += h[0] >> 26; h[0] &= 0x3ffffff;
+    g[0] = h[0] + 5;                                 /* h - p = h + 5 - 2^130, kept when it does not borrow */
+    for (i = 1; i < 5; ++i) { g[i] = h[i] + (g[i - 1] >> 26); g[i - 1] &= 0x3ffffff; }
+    g[4] -= 1u << 26;
+    mask = (g[4] >> 31) - 1u;
+    for (i = 0; i < 5; ++i) h[i] = (h[i] & ~mask) | (g[i] & mask);
+    t = (uint64_t)(h[0] | (h[1] << 26)) + s[0];                 store32le(mac, (uint32_t)t);
+    t = (t >> 32) + (uint32_t)((h[1] >> 6) | (h[2] << 20)) + s[1];  store32le(mac + 4, (uint32_t)t);
+    t = (t >> 32) + (uint32_t)((h[2] >> 12) | (h[3] << 14)) + s[2]; store32le(mac + 8, (uint32_t)t);
+    t = (t >> 32) + (uint32_t)((h[3] >> 18) | (h[4] << 8)) + s[3];  store32le(mac + 12, (uint32_t)t);
+    {                                                /* r, s and h do not outlive the call */
+        volatile uint32_t *v = r; for (i = 0; i < 5; ++i) v[i] = 0;
+        v = h; for (i = 0; i < 5; ++i) v[i] = 0;
+        v = s; for (i = 0; i < 4; ++i) v[i] = 0;
+        volatile uint8_t *vb = rb; for (i = 0; i < 16; ++i) vb[i] = 0;
+        vb = blk; for (i = 0; i < 16; ++i) vb[i] = 0;
+    }
+}

@@ -43,6 +43,10 @@ void uaesh_cmac(const uaesh_key *k, const uint8_t *data, size_t len, uint8_t mac
 int  uaesh_ccm(const uaesh_key *k, int decrypt, const uint8_t *nonce, size_t nonce_len, size_t tag_len,
                const uint8_t *aad, size_t aad_len, const uint8_t *in, size_t len, uint8_t *out);            /* :1226-1314 */
 
+/* r = the r half of the key pair (clamped here), AES_k(nonce) with k; len 0: mac = AES_k(nonce) */
+void uaesh_poly1305(const uaesh_key *k, const uint8_t r[16], const uint8_t nonce[16], const uint8_t *data, size_t len,
+                    uint8_t mac[16]);                                                                       /* :1955-1997 */
+
 /* expand = the engine's key schedule (uaes_expand_key): GCM-SIV derives its message key per nonce */
 int  uaesh_gcmsiv(const uaesh_key *master, int keybits, int decrypt, const uint8_t nonce[12],
                   const uint8_t *aad, size_t aad_len, const uint8_t *in, size_t len, uint8_t *out,

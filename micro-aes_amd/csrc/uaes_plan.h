@@ -28,6 +28,11 @@
  *   SIV   SIV_SMALL             k_siv_small                                         (1)    <= 2046 POLYVAL positions
  *         SIV_CHUNKS            k_siv_prep, hash-only k_gcm_chunks<FOLD>, k_ctr*    (3)    <= 512 MiB
  *         SIV_LEVELS            k_siv_prep, k_ghash_pass.., k_siv_tag, k_ctr*       (4-6)  beyond
+ *   POLY  poly.small            k_poly_small (one workgroup, AES_k(nonce) inside)   (1)    one message <= UAES_POLY_SMALL_MAX (128 KiB)
+ *         poly.chunks           k_poly_chunks, k_poly_fold (+ AES_k(nonce))         (2)    one message beyond
+ *         poly.batch            k_poly_batch (one wave per message)                 (1)    uaes_poly1305_batch
+ * The Poly1305 rows have a planner of their own (uaesk_plan_poly1305, uaes_poly1305.hip) and ids outside enum
+ * uaes_arrangement (uaes_debug_plan_poly1305 names them); a larger message never goes back to a smaller row.
  */
 #ifndef UAES_PLAN_H
 #define UAES_PLAN_H
@@ -87,6 +92,12 @@ unsigned uaesk_plan_disabled(void);
 int uaesk_plan(int mode, int dir, size_t a, size_t b, unsigned flags, uaes_plan *p);
 
 const char *uaesk_arrangement_name(int id);
+
+/* Poly1305-AES: len = bytes of one message; nmsg >= 2 = a batch of nmsg messages of len bytes each (nmsg 0 / 1: the
+ * one-message calls).  grid = workgroups of the main kernel, steps = blocks per thread (at most). */
+enum uaes_poly_arrangement { UAES_POLY_SMALL = 0, UAES_POLY_CHUNKS = 1, UAES_POLY_BATCH = 2 };
+int uaesk_plan_poly1305(size_t len, size_t nmsg, uaes_plan *p);
+const char *uaesk_poly1305_arrangement_name(int id);
 
 #ifdef __cplusplus
 }

@@ -67,3 +67,5 @@ for bits, key in ((128, key16), (256, key32)):
         nb = max(1, n // 65536)                              # (messages of 64 KiB: as many as the buffers hold)
         rate("cbc enc batch %d x 64 KiB" % nb, lambda: L.uaes_cbc_encrypt_batch(bits, key, ad, nb, 65536, a, b), nb * 65536)
         rate("cmac batch %d x 64 KiB" % nb, lambda: L.uaes_cmac_batch(bits, key, nb, 65536, a, b), nb * 65536)
+    pkeys = key + bytes(range(100, 116))                     # Poly1305-AES: k || r
+    rate("poly1305", lambda: L.uaes_poly1305(bits, pkeys, iv16, a, n, mac), n)

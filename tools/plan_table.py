@@ -50,3 +50,6 @@ walk("GCM decrypt, tag first (default, N7)", lambda n: uaes.plan("gcm", n, 0, 1)
 walk("GCM decrypt, one pass (uaes_set_gcm_one_pass_decrypt)", lambda n: uaes.plan("gcm", n, 0, 2), 0, 2048 * MIB)
 walk("OCB", lambda n: uaes.plan("ocb", n), 0, 64 * MIB)
 walk("GCM-SIV", lambda n: uaes.plan("siv", n), 0, 2048 * MIB)
+walk("Poly1305-AES, one message", lambda n: uaes.poly1305_plan(n)[:3] + (0,), 0, 2048 * MIB)
+walk("Poly1305-AES, batches of k messages of 1 KiB", lambda k: uaes.poly1305_plan(1024, max(k, 2))[:3] + (0,), 2, 1 << 20, 1,
+     lambda k: "%9d msgs (%9.3f MiB)" % (k, k * 1024 / MIB))
