@@ -537,8 +537,15 @@ void uaes_debug_gather_stats(unsigned long out[5]);
  *          [3] GHASH positions per thread (chunk arrangements)
  * Works without a device (answers for a 256-CU MI355X).  uaes_debug_plan_disable(mask): arrangements whose bit
  * (1u << id) is set are passed over wherever another one can take the call (measurement and tests; environment
- * UAES_PLAN_DISABLE gives the initial mask).  tests/test_gpu_plan.py derives its parity cases from this table. */
+ * UAES_PLAN_DISABLE gives the initial mask).  tests/test_gpu_plan.py derives its parity cases from this table.
+ * Under UAES_GCM_FOLD=0 the answer is the two-launch form the call then takes (GCM-SIV: the levels).
+ * uaes_debug_plan_at(): the same for a call whose keystream starts from counter16 -- the CTR call's first counter
+ * block, or the GCM call's J0 (GHASH of the nonce for a nonce that is not 12 bytes long).  The low byte of that
+ * counter decides where the text's groups of 256 counters and its stripes fall, and a text in which counter bits
+ * 40..47 move is not one striped launch (CTR: 2 launches; GCM: not gcm.striped).  counter16 = NULL is
+ * uaes_debug_plan(): a 12-byte CTR IV with start value 1, a 12-byte GCM nonce.  Other modes ignore it. */
 int uaes_debug_plan(int mode, int dir, size_t a, size_t b, unsigned flags, int out[4]);
+int uaes_debug_plan_at(int mode, int dir, size_t a, size_t b, unsigned flags, const uint8_t counter16[16], int out[4]);
 const char *uaes_debug_arrangement_name(int id);
 void uaes_debug_plan_disable(unsigned mask);
 /* Poly1305's planner (csrc/uaes_plan.h, its own rows): the arrangement name ("poly.small" / "poly.chunks" /

@@ -44,7 +44,7 @@ EXPORTS = [
     "uaes_ocb_encrypt", "uaes_ocb_decrypt", "uaes_ocb_dev",
     "uaes_poly1305", "uaes_poly1305_dev", "uaes_poly1305_batch", "uaes_debug_plan_poly1305",
     "uaes_mgpu_ctr_xcrypt_at", "uaes_mgpu_xts_sectors", "uaes_mgpu_ctr_encrypt_gather", "uaes_debug_gather_stats", "uaes_debug_gcm_look", "uaes_debug_gcm_chunk_folds",
-    "uaes_debug_plan", "uaes_debug_arrangement_name", "uaes_debug_plan_disable",
+    "uaes_debug_plan", "uaes_debug_plan_at", "uaes_debug_arrangement_name", "uaes_debug_plan_disable",
     "uaes_mgpu_ecb_encrypt", "uaes_mgpu_ecb_decrypt", "uaes_mgpu_gcm_encrypt", "uaes_mgpu_gcm_decrypt",
     "uaes_set_devices", "uaes_set_producer_stream", "uaes_set_host_policy", "uaes_get_host_policy",
     "uaes_gcm_key_new", "uaes_gcm_key_free", "uaes_gcm_key_encrypt", "uaes_gcm_key_decrypt",
@@ -162,6 +162,8 @@ def engine():
         L.uaes_debug_arrangement_name.restype = C.c_char_p
         L.uaes_debug_plan_disable.argtypes = [C.c_uint]
         L.uaes_debug_plan_disable.restype = None
+    if hasattr(L, "uaes_debug_plan_at"):
+        L.uaes_debug_plan_at.argtypes = [i, i, sz, sz, C.c_uint, vp, C.POINTER(C.c_int)]
     L.uaes_mgpu_ecb_encrypt.argtypes = [i, C.POINTER(C.c_int), i, vp, i, vp, sz, vp]
     L.uaes_mgpu_ecb_decrypt.argtypes = [i, C.POINTER(C.c_int), i, vp, vp, sz, vp]
     for n in ("uaes_mgpu_gcm_encrypt", "uaes_mgpu_gcm_decrypt"):
@@ -784,10 +786,16 @@ class GcmStream:
 MODES = {"ecb": 0, "ctr": 1, "xts": 2, "gcm": 3, "ocb": 4, "siv": 5}
 
 
-def plan(mode, a, b=0, direction=0, flags=0):
-    """What a call would run (uaes_debug_plan): (arrangement name, launches, workgroups, positions per thread)."""
+def plan(mode, a, b=0, direction=0, flags=0, counter=None):
+    """What a call would run (uaes_debug_plan): (arrangement name, launches, workgroups, positions per thread).
+    counter: the CTR call's first 16-byte counter block or the GCM call's J0 (uaes_debug_plan_at); None = a 12-byte
+    IV / nonce."""
     out = (C.c_int * 4)()
-    _check(engine().uaes_debug_plan(MODES[mode], direction, a, b, flags, out), "uaes_debug_plan")
+    if counter is None:
+        _check(engine().uaes_debug_plan(MODES[mode], direction, a, b, flags, out), "uaes_debug_plan")
+    else:
+        _check(engine().uaes_debug_plan_at(MODES[mode], direction, a, b, flags, _fixed(counter, 16, "counter"), out),
+               "uaes_debug_plan_at")
     return engine().uaes_debug_arrangement_name(out[0]).decode(), out[1], out[2], out[3]
 
 

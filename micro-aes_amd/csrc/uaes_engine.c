@@ -3836,15 +3836,19 @@ static int gather_fail_send(void)
 static struct { unsigned long sends, recvs, groups, inits, failures; } g_gather_stats;
 
 /* ---- the table of arrangements as data (csrc/uaes_plan.h; include/uaes_hip.h) ---- */
-int uaes_debug_plan(int mode, int dir, size_t a, size_t b, unsigned flags, int out[4])
+int uaes_debug_plan_at(int mode, int dir, size_t a, size_t b, unsigned flags, const uint8_t counter16[16], int out[4])
 {
     uaes_plan p;
     int e;
     if (!out) return fail(UAES_E_ARG, "NULL pointer");
     memset(&p, 0, sizeof p);
-    if ((e = uaesk_plan(mode, dir, a, b, flags, &p)) != 0) return fail(UAES_E_ARG, "no plan for mode %d, direction %d", mode, dir);
+    if ((e = uaesk_plan_at(mode, dir, a, b, flags, counter16, &p)) != 0) return fail(UAES_E_ARG, "no plan for mode %d, direction %d", mode, dir);
     out[0] = p.arrangement; out[1] = p.launches; out[2] = (int)p.grid; out[3] = (int)p.steps;
     return 0;
+}
+int uaes_debug_plan(int mode, int dir, size_t a, size_t b, unsigned flags, int out[4])
+{
+    return uaes_debug_plan_at(mode, dir, a, b, flags, NULL, out);
 }
 const char *uaes_debug_arrangement_name(int id) { return uaesk_arrangement_name(id); }
 const char *uaes_debug_plan_poly1305(size_t len, size_t nmsg, int out[3])

@@ -1387,13 +1387,15 @@ static void gcm_counter_from_j0(uaesk_ctr &c, const unsigned char j0b[16], u64 b
     c.v0 = (v + 1 + block_offset) & 0x00FFFFFFFFFFFFFFull;
 }
 
-int uaesk_plan_gcm(int dir, size_t len, size_t aad_len, unsigned flags, uaes_plan *p)
+/* j0: the call's J0, or NULL for a 12-byte nonce (J0 ends in 00000001); the stripes follow its counter as gcm_body's do */
+int uaesk_plan_gcm(int dir, size_t len, size_t aad_len, unsigned flags, const uint8_t *j0, uaes_plan *p)
 {
     if (dir < 0 || dir > 3) return (int)hipErrorInvalidValue;
-    unsigned char j0b[16] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1 };     /* a 12-byte nonce: J0 ends in 00000001 */
+    unsigned char j0b[16] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1 };
+    if (j0) memcpy(j0b, j0, 16);
     uaesk_ctr c;
     gcm_counter_from_j0(c, j0b, 0);
-    *p = gcm_plan(dir, len, aad_len, c, !((flags >> 2) & 1u)).p;
+    *p = gcm_plan(dir, len, aad_len, c, !((flags >> 2) & 1u) && uaesk_gcm_fold_on()).p;
     if (p->arrangement == UAES_ARR_GCM_LEVELS) {
         const u64 nv = ((aad_len + 15) >> 4) + ((len + 15) >> 4) + 1;
         const GPlan pl = plan_for(nv);
@@ -1424,7 +1426,7 @@ static uaes_plan siv_plan(u64 len, u64 aad_len, bool has_word, bool long_only = 
 int uaesk_plan_siv(int dir, size_t len, size_t aad_len, unsigned flags, uaes_plan *p)
 {
     if (dir < 0 || dir > 1) return (int)hipErrorInvalidValue;
-    *p = siv_plan(len, aad_len, !((flags >> 2) & 1u));
+    *p = siv_plan(len, aad_len, !((flags >> 2) & 1u) && uaesk_gcm_fold_on());
     return 0;
 }
 

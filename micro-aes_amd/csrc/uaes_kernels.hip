@@ -1261,14 +1261,19 @@ static thread_local int g_unused = 0;
  * tail of its scratch buffers) and arms one right before the call; a routine that can use it takes it at its entry. */
 static thread_local unsigned *g_done_word = nullptr;
 extern "C" void uaesk_done_word_arm(unsigned *w) { g_done_word = w; }
+/* UAES_GCM_FOLD=0: the one-launch arrangements of the GCM family (chunk workgroups + a fold inside the same launch)
+ * are off; every such call takes its multi-launch form (chunks, then k_gcm_combine).  The planners ask the same. */
+bool uaesk_gcm_fold_on()
+{
+    static const bool fold_on = [] { const char *e = getenv("UAES_GCM_FOLD"); return !(e && e[0] == '0'); }();
+    return fold_on;
+}
+
 unsigned *uaesk_done_word_take()
 {
-    /* UAES_GCM_FOLD=0: the one-launch arrangements of the GCM family (chunk workgroups + a fold inside the same
-     * launch) are off; every such call takes its multi-launch form (chunks, then k_gcm_combine) */
-    static const bool fold_on = [] { const char *e = getenv("UAES_GCM_FOLD"); return !(e && e[0] == '0'); }();
     unsigned *w = g_done_word;
     g_done_word = nullptr;
-    return fold_on ? w : nullptr;
+    return uaesk_gcm_fold_on() ? w : nullptr;
 }
 
 extern "C" int uaesk_ticket_disarm(void)
@@ -1343,11 +1348,16 @@ extern "C" int uaesk_selftest(void *stream, const uaesk_tables *tb, const uaesk_
 /* ------------------------------------------------------------------------ */
 /* the table as data (uaes_plan.h)                                             */
 /* ------------------------------------------------------------------------ */
-int uaesk_plan_gcm(int dir, size_t len, size_t aad_len, unsigned flags, uaes_plan *p);     /* uaes_gcm.hip */
+int uaesk_plan_gcm(int dir, size_t len, size_t aad_len, unsigned flags, const uint8_t *j0, uaes_plan *p);  /* uaes_gcm.hip */
 int uaesk_plan_siv(int dir, size_t len, size_t aad_len, unsigned flags, uaes_plan *p);     /* uaes_gcm.hip */
 int uaesk_plan_ocb(int dir, size_t len, size_t aad_len, uaes_plan *p);                     /* uaes_ocb.hip */
 
 extern "C" int uaesk_plan(int mode, int dir, size_t a, size_t b, unsigned flags, uaes_plan *p)
+{
+    return uaesk_plan_at(mode, dir, a, b, flags, nullptr, p);
+}
+
+extern "C" int uaesk_plan_at(int mode, int dir, size_t a, size_t b, unsigned flags, const uint8_t *counter16, uaes_plan *p)
 {
     if (!p) return (int)hipErrorInvalidValue;
     if (uaesk_device_info(nullptr, nullptr) != 0) g_cus = 0;    /* no device: the table of a 256-CU MI355X (grid_for, plan_cus) */
@@ -1358,7 +1368,14 @@ extern "C" int uaesk_plan(int mode, int dir, size_t a, size_t b, unsigned flags,
     case UAES_PLAN_CTR: {
         uaesk_ctr c;
         memset(&c, 0, sizeof c);
-        c.v0 = 1;                                   /* CTR_START_VALUE; the planner looks at the low byte only */
+        if (counter16) {                            /* the block-to-counter arithmetic of the CTR launcher (make_ctr) */
+            memcpy(&c.w0, counter16, 4);
+            memcpy(&c.w1, counter16 + 4, 4);
+            c.b8 = counter16[8];
+            for (int i = 9; i < 16; ++i) c.v0 = (c.v0 << 8) | counter16[i];
+        } else {
+            c.v0 = 1;                               /* CTR_START_VALUE behind a 12-byte IV */
+        }
         c.le32 = (flags >> 3) & 1u;
         *p = plan_ctr(&c, a, nullptr, nullptr);
         return 0;
@@ -1367,7 +1384,7 @@ extern "C" int uaesk_plan(int mode, int dir, size_t a, size_t b, unsigned flags,
         if (a < 16 || b == 0) return (int)hipErrorInvalidValue;
         *p = plan_xts(a, b, (flags >> 1) & 1u);
         return 0;
-    case UAES_PLAN_GCM: return uaesk_plan_gcm(dir, a, b, flags, p);
+    case UAES_PLAN_GCM: return uaesk_plan_gcm(dir, a, b, flags, counter16, p);
     case UAES_PLAN_SIV: return uaesk_plan_siv(dir, a, b, flags, p);
     case UAES_PLAN_OCB: return uaesk_plan_ocb(dir, a, b, p);
     default: return (int)hipErrorInvalidValue;

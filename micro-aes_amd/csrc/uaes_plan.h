@@ -5,7 +5,10 @@
  * (include/uaes_hip.h) returns the same answer as data, and tests/test_gpu_plan.py derives its parity cases from it:
  * it walks the sizes, finds every boundary b at which the answer changes and checks b - 16, b, b + 16 in both
  * directions (and a forged tag) against the oracle.  There is no other place where a size threshold decides what
- * runs, and no threshold is read from the environment.
+ * runs, and no size threshold is read from the environment.  Three switches are: UAES_PLAN_DISABLE (the initial mask of
+ * uaesk_plan_disable below), UAES_GCM_FOLD=0 (no counter word reaches the kernels, so the one-launch GCM forms become
+ * their two-launch forms and GCM-SIV takes the levels; the planners answer the same) and UAES_GCM_LOOK_TICKS (how long
+ * the one-launch GCM kernel's preparing workgroup looks at the arrival counter; it does not change the arrangement).
  *
  *   mode  arrangement           kernels (launches)                                         reached when
  *   ----  --------------------  ---------------------------------------------------------  ---------------------------------
@@ -90,6 +93,12 @@ unsigned uaesk_plan_disabled(void);
  * The number of CUs decides most boundaries; without a device the answer is the one for a 256-CU MI355X.  Returns 0
  * and fills *p, or a HIP error code for arguments that make no sense. */
 int uaesk_plan(int mode, int dir, size_t a, size_t b, unsigned flags, uaes_plan *p);
+/* the same for a call whose keystream starts from a given counter: counter16 = the CTR call's first counter block
+ * (ctr0 at block offset 0) or the GCM call's J0 (the keystream starts at J0 + 1).  Where a CTR or GCM text's groups of
+ * 256 counters and its stripes fall depends on the counter's low byte, and a text in which counter bits 40..47 move
+ * cannot be one striped launch (CTR: two launches; GCM: not gcm.striped).  NULL = uaesk_plan (CTR: a 12-byte IV and
+ * start value 1; GCM: a 12-byte nonce).  Other modes ignore it. */
+int uaesk_plan_at(int mode, int dir, size_t a, size_t b, unsigned flags, const uint8_t *counter16, uaes_plan *p);
 
 const char *uaesk_arrangement_name(int id);
 

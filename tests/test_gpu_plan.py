@@ -307,6 +307,11 @@ import micro_aes_amd as uaes
 from oracle.pyoracle import Oracle
 orc = Oracle()
 key, n12 = bytes(range(16)), bytes(range(12))
+# the table reports the forms that run: two-launch chunks / twophase, GCM-SIV by the levels
+assert uaes.plan("gcm", (1 << 20) + 5, 0, 0) == (uaes.plan("gcm", (1 << 20) + 5, 0, 0, 4)), uaes.plan("gcm", (1 << 20) + 5)
+assert uaes.plan("gcm", (1 << 20) + 5)[:2] == ("gcm.chunks", 2), uaes.plan("gcm", (1 << 20) + 5)
+assert uaes.plan("gcm", (20 << 20) + 3)[:2] == ("gcm.twophase", 3), uaes.plan("gcm", (20 << 20) + 3)
+assert uaes.plan("siv", (1 << 20) + 5)[0] == "siv.levels", uaes.plan("siv", (1 << 20) + 5)
 for n, aad in ((40000, b"abc"), ((1 << 20) + 5, b""), ((6 << 20) + 16, bytes(100)), ((20 << 20) + 3, b"x")):
     d = orc.splitmix(n + 1, n)
     want = orc.gcm_encrypt(key, n12, aad, d)

@@ -791,7 +791,8 @@ def test_one_launch_gcm_under_oversubscription(orc):
     def worker(t):
         try:
             st = torch.cuda.Stream(device=dev)
-            status = torch.full((1,), -1, dtype=torch.int32, device=dev)
+            with torch.cuda.stream(st):                 # (on the default stream this fill could land after the first
+                status = torch.full((1,), -1, dtype=torch.int32, device=dev)     # decryption on `st` wrote the status)
             for rep in range(2):
                 for n in sizes[t % 2:] + sizes[:t % 2]:
                     data, aad, want = cases[n]
