@@ -12,29 +12,35 @@ the optional ciphertext all-gather is timed separately and never part of
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \\
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0.  `roofline` prices the dominant kernel against
-the 8 TB/s HBM peak with ALGORITHMIC bytes (32 B per 16-byte block: read the
-plaintext, write the ciphertext); `cpu_baseline` times the
-compiled REFERENCE (oracle/_ref, or the oracle restatement if that did not
-travel) on this box's host cores on a bounded sample of the same workload.
-Other workloads (--workload ecb|xts|gcm|ocb|...) are for profiling, not the bench line; `cbc-enc` / `cmac` time ONE
-serial chain with the reference's CPU loop beside it.
+Prints ONE JSON line on rank 0.  A plain run does only what `value` needs: it sets up, warms up, times the K steps,
+writes --dump-outputs if asked and prints the line.  `roofline.achieved` / `frac` price the mean step time against the
+8 TB/s HBM peak with ALGORITHMIC bytes (32 B per 16-byte block: read the plaintext, write the ciphertext; DESIGN.md
+section 4); `roofline.traffic` is then the figure recorded under profiles/, labelled as such.
 
-After the K timed steps the same step runs back to back for --sustain-s seconds (default 2): `sustained` and
-`roofline.frac_sustained` ride next to `value`, never inside it.  With --gpus N the control plane is gloo; RCCL is
-brought up beside it, proven with a 16-byte all-gather and used only if every rank saw it work -- otherwise the run
-finishes on gloo and says so in `collective_backend` (setup_collectives).
+--full adds everything else the line can carry, all of it AFTER the timed steps and never part of `value`
+(resolve_extras): `verified` (the output against the reference's digest or the oracle), `roofline.traffic` measured by
+rocprofv3 PMC passes over a child run, the stream-copy ceiling, `other_configs` (GCM C4 and XTS C3, 1-GPU CTR 1 GiB
+line), `cpu_baseline` (the compiled REFERENCE, oracle/_ref, or the oracle restatement if that did not travel, on this
+box's host cores on a bounded sample of the same workload), the sustained run and the gathers below.  Each --no-*
+switch turns one of them back off.
+Other workloads (--workload ecb|xts|gcm|ocb|...) are for profiling, not the bench line; `cbc-enc` / `cmac` time ONE
+serial chain with the reference's CPU loop beside it under --full.
+
+After the K timed steps the same step runs back to back for --sustain-s seconds (default 2 under --full, else 0):
+`sustained` and `roofline.frac_sustained` ride next to `value`, never inside it.  With --gpus N the control plane is
+gloo; RCCL is brought up beside it, proven with a 16-byte all-gather and used only if every rank saw it work --
+otherwise the run finishes on gloo and says so in `collective_backend` (setup_collectives).
 
 --dump-outputs DIR writes what the last timed step computed to DIR/<name>.npy (dump_outputs): the inputs are fixed by
 the workload's seed, so two builds of the project can be compared output for output.
 
-With more than one rank the line also carries what SURVEY.md 8e lists beside the encrypt-only rate, all of it AFTER the
-timed steps and never part of `value`: `gather_ms` (the ciphertext all-gather: RCCL over xGMI, or -- when RCCL did not
-come up, e.g. the one-device dry run -- a gloo gather to rank 0), `encrypt_plus_gather_gib_s` (one step + the gather,
-end to end), `gathered_stream_digest_ok` (the concatenated stream against the reference's digests: every 1 GiB shard,
-and the whole 8 GiB C5 stream at N = 8) and `c_gather` (rank 0 alone runs the C host's uaes_mgpu_ctr_encrypt_gather
-over all N devices in ONE process).  Each runs under its own bounded wait and try/except: none of them can cost the
-line.  --no-gather / --no-c-gather switch them off.
+With more than one rank, --full also carries what SURVEY.md 8e lists beside the encrypt-only rate: `gather_ms` (the
+ciphertext all-gather: RCCL over xGMI, or -- when RCCL did not come up, e.g. the one-device dry run -- a gloo gather to
+rank 0), `encrypt_plus_gather_gib_s` (one step + the gather, end to end), `gathered_stream_digest_ok` (the concatenated
+stream against the reference's digests: every 1 GiB shard, and the whole 8 GiB C5 stream at N = 8) and `c_gather`
+(rank 0 alone runs the C host's uaes_mgpu_ctr_encrypt_gather over all N devices in ONE process).  Each runs under its
+own bounded wait and try/except: none of them can cost the line.  --gather / --c-gather ask for them without --full;
+--no-gather / --no-c-gather switch them off.
 """
 import argparse
 import ctypes
@@ -412,11 +418,23 @@ def setup_collectives(a, torch, rank, world, local, dev):
     return dist, None, torch.device("cpu"), info
 
 
+def resolve_extras(a):
+    """What runs beside `value`, decided once after parsing.  A plain run does what the headline needs and nothing
+    else; --full switches on verification, the PMC passes behind roofline.traffic, other_configs, cpu_baseline and a
+    2 s sustained run (the copy ceiling and the gathers follow a.full where they run), and each --no-* switch turns one
+    of them back off.  An explicit --sustain-s is honoured either way."""
+    if a.sustain_s is None:
+        a.sustain_s = 2.0 if a.full else 0.0
+    if not a.full:
+        a.no_verify = a.no_traffic = a.no_other_configs = a.no_cpu = True
+    return a
+
+
 def resolve_gather_flags(a, world, force=False):
-    """--gather / --c-gather default ON as soon as there is more than one rank (SURVEY.md 8e "what to report":
-    encrypt-only, encrypt + gather, bit-exactness of the concatenated stream) or --force-collective asks for the
-    one-rank run of the same code, OFF for the plain one-GPU line"""
-    many = world > 1 or force
+    """--gather / --c-gather default ON under --full as soon as there is more than one rank (SURVEY.md 8e "what to
+    report": encrypt-only, encrypt + gather, bit-exactness of the concatenated stream) or --force-collective asks for
+    the one-rank run of the same code; OFF for a plain run and for the one-GPU line"""
+    many = (world > 1 or force) and a.full
     gather = many if a.gather is None else bool(a.gather)
     c_gather = (many and gather) if a.c_gather is None else bool(a.c_gather)
     return gather, c_gather and gather
@@ -630,22 +648,28 @@ def build_parser():
     ap.add_argument("--bytes", type=int, default=GIB, help="bytes per GPU")
     ap.add_argument("--settle-ms", type=float, default=150.0,
                     help="extra untimed warm-up until the clocks have settled (0 = only --warmup steps)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, everything beside the headline as well: verification against the "
+                         "reference, the PMC passes behind roofline.traffic, the copy ceiling, `other_configs`, "
+                         "`cpu_baseline`, the sustained run and, with more than one rank, the gathers (each --no-* "
+                         "switch below turns one back off); a plain run does only what `value` needs")
     ap.add_argument("--no-verify", action="store_true")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-traffic", action="store_true", help="skip the two rocprofv3 PMC passes behind roofline.traffic")
     ap.add_argument("--no-clock-probe", action="store_true",
                     help="skip the shader-clock sample behind roofline.lds_ceiling (taken in the middle of the sustained run)")
-    ap.add_argument("--sustain-s", type=float, default=2.0,
+    ap.add_argument("--sustain-s", type=float, default=None,
                     help="after the K timed steps, seconds of the same step back to back (untimed for `value`) behind "
-                         "`sustained` and roofline.frac_sustained; 0 = skip")
+                         "`sustained` and roofline.frac_sustained (default: 2 with --full, else 0); 0 = skip")
     ap.add_argument("--gather", dest="gather", action="store_true", default=None,
                     help="after the timed steps: the ciphertext gather, encrypt + gather end to end and the digest of the "
-                         "concatenated stream (default: ON with more than one rank)")
+                         "concatenated stream (default: ON with --full and more than one rank)")
     ap.add_argument("--no-gather", dest="gather", action="store_false")
     ap.add_argument("--c-gather", dest="c_gather", action="store_true", default=None,
                     help="with the gather: rank 0 also runs uaes_mgpu_ctr_encrypt_gather -- the C host's own encrypt + RCCL "
                          "gather over all N devices in ONE process (include/uaes_hip.h) -- while the other ranks wait "
-                         "(default: ON with more than one rank)")
+                         "(default: ON with --full and more than one rank; with --full the one-GPU CTR line runs it "
+                         "once through RCCL to itself)")
     ap.add_argument("--no-c-gather", dest="c_gather", action="store_false")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo + --single-device: dry-run the multi-rank code path on a 1-GPU box")
@@ -666,7 +690,7 @@ def build_parser():
 
 
 def main():
-    a = build_parser().parse_args()
+    a = resolve_extras(build_parser().parse_args())
     if a.steps < 1:
         sys.exit("--steps must be at least 1")
 
@@ -861,10 +885,11 @@ def main():
         if cg is not None and not still_rccl and "gather" in gather_info:
             cg, cdev = None, torch.device("cpu")                # RCCL misbehaved: the remaining reductions go over gloo
             coll_info["collective_backend"] += "; gloo after the gather failed"
-    rccl_self = (world == 1 and not force and a.workload == "ctr" and a.c_gather is not False and a.gather is not False)
+    rccl_self = (world == 1 and not force and a.workload == "ctr" and a.gather is not False
+                 and (a.full if a.c_gather is None else a.c_gather))
     if rccl_self:
-        # The plain one-GPU line: no process group at all, but the C host's gather still runs once through RCCL
-        # (ncclSend / ncclRecv to itself, UAES_GATHER_FORCE_RCCL) so that every driver run executes the code that
+        # The one-GPU line under --full: no process group at all, but the C host's gather still runs once through RCCL
+        # (ncclSend / ncclRecv to itself, UAES_GATHER_FORCE_RCCL) so that a --full run executes the code that
         # configs[4] depends on and checks its stream against the reference.  After the timed steps; bounded.
         os.environ["UAES_GATHER_FORCE_RCCL"] = "1"
         res, err, stuck = bounded(lambda: c_gather_phase(a, torch, uaes, rank, world, n, dev, src, dst, seed),
@@ -882,9 +907,9 @@ def main():
         if dist:
             dist.barrier()                                      # gloo (the default group)
 
-    # measured HBM stream-copy ceiling on this GPU (read n + write n), for context next to the 8 TB/s spec
+    # measured HBM stream-copy ceiling on this GPU (read n + write n), for context next to the 8 TB/s spec (--full)
     copy_gbs = None
-    if world == 1:
+    if world == 1 and a.full:
         tmp = torch.empty(n, dtype=torch.uint8, device=dev)
         for _ in range(3):
             tmp.copy_(src)
@@ -1038,8 +1063,9 @@ def main():
             line["roofline"]["per_gpu_frac"] = [round(x / HBM_PEAK_GBS, 4) for x in per_gpu]
             line["roofline"]["aggregate"] = {"achieved": round(sum(per_gpu), 1), "peak": HBM_PEAK_GBS * world,
                                              "frac": round(sum(per_gpu) / (HBM_PEAK_GBS * world), 4)}
-            line["verified_shards"] = "every rank hashed its whole shard against the reference's digest" \
-                if (a.workload == "ctr" and n == GIB and not a.no_verify) else "head of every shard against the oracle"
+            if not a.no_verify:
+                line["verified_shards"] = "every rank hashed its whole shard against the reference's digest" \
+                    if (a.workload == "ctr" and n == GIB) else "head of every shard against the oracle"
         if sustained:
             # whole-job sustained rate = the sum of the ranks' own back-to-back rates (no collective inside the run)
             line["sustained"] = {"value": round(sum(sus_all), 2), "unit": "GiB/s", "seconds": round(sustained["seconds"], 3),

@@ -36,3 +36,19 @@ def test_traffic_from_the_two_counter_passes():
     t, src = bench.traffic_of({"FETCH_SIZE": 527966.0, "WRITE_SIZE": 1059605.0})
     assert t == int((2 * 527966 + 1059605) * 1024) and src.startswith("measured in this run")
     assert bench.traffic_of({"FETCH_SIZE": 1.0}) == (None, None)
+
+
+def test_a_plain_run_does_only_what_value_needs_and_full_adds_the_rest():
+    ap = bench.build_parser()
+    plain = bench.resolve_extras(ap.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "3"]))
+    assert not plain.full and plain.sustain_s == 0.0
+    assert plain.no_verify and plain.no_traffic and plain.no_other_configs and plain.no_cpu
+    assert bench.resolve_gather_flags(plain, 1) == (False, False) and bench.resolve_gather_flags(plain, 8) == (False, False)
+    full = bench.resolve_extras(ap.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "3", "--full"]))
+    assert full.sustain_s == 2.0
+    assert not (full.no_verify or full.no_traffic or full.no_other_configs or full.no_cpu)
+    assert bench.resolve_gather_flags(full, 8) == (True, True) and bench.resolve_gather_flags(full, 1, force=True) == (True, True)
+    # under --full a --no-* switch still turns its part off; an explicit --sustain-s holds with or without --full
+    some = bench.resolve_extras(ap.parse_args(["--full", "--no-cpu", "--sustain-s", "0"]))
+    assert some.no_cpu and not some.no_verify and some.sustain_s == 0.0
+    assert bench.resolve_extras(ap.parse_args(["--sustain-s", "0.5"])).sustain_s == 0.5

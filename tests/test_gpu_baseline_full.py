@@ -95,7 +95,7 @@ def test_bench_two_rank_dry_run(workload):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full",
            "--backend", "gloo", "--single-device", "--bytes", str(64 << 20), "--settle-ms", "0", "--sustain-s", "0.2",
            "--workload", workload]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
@@ -124,7 +124,7 @@ def test_bench_self_launch_verifies_every_shard():
     --single-device) at the full 1 GiB per rank, so that EVERY rank hashes its whole shard against the
     reference's digest of that shard of the C5 stream (PRESET_COUNTER build of the reference)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full",
            "--backend", "gloo", "--single-device", "--settle-ms", "0", "--sustain-s", "0.5"]
     line = _one_json_line(subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900))
     assert line["n_gpus"] == 2 and line["verified"] is True
@@ -135,12 +135,12 @@ def test_bench_self_launch_verifies_every_shard():
 
 
 def test_bench_line_measures_its_own_traffic_and_clock():
-    """the N = 1 line as the driver reads it: `roofline.traffic` from the two rocprofv3 PMC passes the run makes over a
+    """the N = 1 line with --full: `roofline.traffic` from the two rocprofv3 PMC passes the run makes over a
     child of itself -- the algorithmic bytes plus no more than a few per cent (it once counted the clock sample's
     extra steps) -- and `roofline.lds_ceiling` from the shader clock sampled under the load"""
     import shutil
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--no-cpu"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--full", "--no-cpu"]
     line = _one_json_line(subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900))
     roof = line["roofline"]
     assert line["n_gpus"] == 1 and line["verified"] is True and roof["algorithmic_bytes"] == 2 << 30
@@ -176,6 +176,31 @@ def test_bench_line_measures_its_own_traffic_and_clock():
     assert sus["sclk_mhz"] == lc["sclk_mhz_under_load"]
 
 
+def test_bench_plain_line_times_the_headline_only(orc, tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: the headline and what --dump-outputs writes, none of
+    what --full adds -- and the dumped ciphertext blocks are the oracle's at their offsets"""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+           "--dump-outputs", str(tmp_path)]
+    line = _one_json_line(subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300))
+    assert line["metric"] == "GiB/s encrypted (AES-128-CTR, 1 GiB buffer per GPU)" and line["unit"] == "GiB/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "u8" and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["verified"] is None
+    for k in ("cpu_baseline", "other_configs", "sustained", "c_gather", "gather_ms"):
+        assert k not in line, k
+    roof = line["roofline"]
+    assert roof["measured_copy_ceiling_gbs"] is None and roof["lds_ceiling"] is None and roof["pipes"] is None
+    ct = np.load(tmp_path / "ciphertext.npy").astype(np.uint8)
+    starts = np.load(tmp_path / "ciphertext_index.npy").astype(np.int64)
+    assert ct.size == 16 * starts.size and starts[0] == 0 and starts[-1] == GIB - 16
+    key, ctr0 = bytes(range(16)), bytes(range(0xF0, 0xFC)) + b"\0\0\0\1"
+    for i in list(range(32)) + [starts.size - 1]:
+        blk = int(starts[i]) // 16
+        want = orc.ctr_xcrypt_at(key, ctr0, blk, orc.splitmix(2, 16, word0=2 * blk))
+        assert ct[16 * i:16 * i + 16].tobytes() == want, blk
+
+
 def test_bench_two_ranks_rccl():
     """the real thing on a multi-GPU box: two ranks, two devices, RCCL (nccl backend with device_id), the
     ciphertext all-gather included"""
@@ -183,7 +208,7 @@ def test_bench_two_ranks_rccl():
     if torch.cuda.device_count() < 2:
         pytest.skip("needs 2 GPUs: this box has %d" % torch.cuda.device_count())
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--gather"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--gather"]
     line = _one_json_line(subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900))
     assert line["n_gpus"] == 2 and line["verified"] is True and line["gather_ms"] > 0
 
@@ -195,7 +220,7 @@ def test_bench_one_rank_force_collective_runs_rccl_on_one_gpu():
     The gathered stream (1 GiB, = C2) must match the reference's digest through BOTH gathers."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT",
                                                             "UAES_GATHER_FORCE_RCCL", "UAES_GATHER_FAIL_SEND")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--force-collective",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--force-collective",
            "--sustain-s", "0.2", "--no-traffic", "--no-cpu"]
     line = _one_json_line(subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900))
     assert line["n_gpus"] == 1 and line["verified"] is True and line["value"] > 0
@@ -214,8 +239,8 @@ def test_bench_two_ranks_survive_an_rccl_failure():
     plane, still time and verify both shards, and say what happened in `collective_backend`."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(UAES_BENCH_FORCE_NCCL_FAIL="1", UAES_BENCH_RCCL_WAIT_S="30")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--single-device", "--bytes", str(64 << 20), "--settle-ms", "0", "--sustain-s", "0.2"]      # gather + C gather: defaults
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full",
+           "--single-device", "--bytes", str(64 << 20), "--settle-ms", "0", "--sustain-s", "0.2"]      # gather + C gather: --full's defaults
     line = _one_json_line(subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900))
     assert line["n_gpus"] == 2 and line["verified"] is True and line["value"] > 0
     assert line["collective_backend"].startswith("gloo (nccl init failed: RuntimeError: forced by"), line["collective_backend"]
@@ -233,7 +258,7 @@ def test_bench_two_ranks_real_rccl_bring_up_on_one_device():
     with that (it refuses duplicate devices), the bench line must come out verified, on RCCL or on the gloo fallback."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(UAES_BENCH_RCCL_WAIT_S="60")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full",
            "--single-device", "--bytes", str(64 << 20), "--settle-ms", "0", "--sustain-s", "0.2"]
     line = _one_json_line(subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900))
     assert line["n_gpus"] == 2 and line["verified"] is True
@@ -241,13 +266,14 @@ def test_bench_two_ranks_real_rccl_bring_up_on_one_device():
 
 
 def test_bench_eight_ranks_flagless_dry_run_reports_everything_8e_lists():
-    """the driver's multi-GPU command carries no flag but --gpus/--steps/--warmup.  Eight ranks on this
-    box's one GPU (--single-device is the only addition): the line must hold the gather, encrypt + gather, the digest of
-    the concatenated 8 GiB stream against the reference's C5 digest, and the C host's own gather with the same digest --
-    RCCL refuses eight ranks on one device, so the collective is the labelled gloo stand-in here."""
+    """the multi-GPU command carries no flag but --gpus/--steps/--warmup, and --full for what rides
+    beside the headline.  Eight ranks on this box's one GPU (--single-device is the only addition): the line must hold
+    the gather, encrypt + gather, the digest of the concatenated 8 GiB stream against the reference's C5 digest, and the
+    C host's own gather with the same digest -- RCCL refuses eight ranks on one device, so the collective is the
+    labelled gloo stand-in here."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(UAES_BENCH_RCCL_WAIT_S="60")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1", "--single-device"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1", "--full", "--single-device"]
     line = _one_json_line(subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1200))
     assert line["n_gpus"] == 8 and line["verified"] is True and line["config"]["bytes_per_gpu"] == GIB
     assert line["gather_ms"] > 0 and line["encrypt_plus_gather_gib_s"] > 0
@@ -257,14 +283,14 @@ def test_bench_eight_ranks_flagless_dry_run_reports_everything_8e_lists():
 
 
 def test_bench_three_ranks_flagless_dry_run_on_one_device():
-    """the same flagless multi-rank command on this box's one GPU (--single-device is the only addition) with three
+    """the same multi-rank --full command on this box's one GPU (--single-device is the only addition) with three
     ranks, so that no more than five processes hold the device (pytest, the launcher, the ranks): the line must hold the
     gather, encrypt + gather, every gathered 1 GiB shard against the reference's digest of that shard of the C5 stream,
     and the C host's own gather with the same digests -- RCCL refuses several ranks on one device, so the collective is
     the labelled gloo stand-in here."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(UAES_BENCH_RCCL_WAIT_S="60")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--steps", "3", "--warmup", "1", "--single-device"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--steps", "3", "--warmup", "1", "--full", "--single-device"]
     line = _one_json_line(subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1200))
     assert line["n_gpus"] == 3 and line["verified"] is True and line["config"]["bytes_per_gpu"] == GIB
     assert line["verified_shards"].startswith("every rank hashed its whole shard")

@@ -312,19 +312,22 @@ def test_bench_self_launch_command(monkeypatch):
 
 
 def test_bench_reports_the_gather_by_default_with_more_than_one_rank():
-    """the driver's command is `bench.py --gpus N --steps K --warmup W` and nothing else -- with N > 1
-    that alone must produce everything SURVEY.md 8e lists (gather, encrypt + gather, the digest of the concatenated
-    stream, the C host's own gather); the one-GPU line stays as it is; --no-gather / --no-c-gather opt out"""
+    """`bench.py --gpus N --steps K --warmup W --full` and nothing else -- with N > 1 that alone must
+    produce everything SURVEY.md 8e lists (gather, encrypt + gather, the digest of the concatenated stream, the C host's
+    own gather); the one-GPU line stays as it is; --no-gather / --no-c-gather opt out.  A plain run (no --full) times
+    the headline only; --gather / --c-gather ask for the gathers without --full."""
     import bench
     ap = bench.build_parser()
-    a = ap.parse_args(["--gpus", "8", "--steps", "20", "--warmup", "3"])
+    a = ap.parse_args(["--gpus", "8", "--steps", "20", "--warmup", "3", "--full"])
     assert a.gather is None and a.c_gather is None
     assert bench.resolve_gather_flags(a, 8) == (True, True)
     assert bench.resolve_gather_flags(a, 2) == (True, True)
-    assert bench.resolve_gather_flags(ap.parse_args([]), 1) == (False, False)
-    assert bench.resolve_gather_flags(ap.parse_args(["--gpus", "8", "--no-gather"]), 8) == (False, False)
-    assert bench.resolve_gather_flags(ap.parse_args(["--gpus", "8", "--no-c-gather"]), 8) == (True, False)
+    assert bench.resolve_gather_flags(ap.parse_args(["--full"]), 1) == (False, False)
+    assert bench.resolve_gather_flags(ap.parse_args(["--gpus", "8", "--full", "--no-gather"]), 8) == (False, False)
+    assert bench.resolve_gather_flags(ap.parse_args(["--gpus", "8", "--full", "--no-c-gather"]), 8) == (True, False)
     assert bench.resolve_gather_flags(ap.parse_args(["--gather", "--c-gather"]), 1) == (True, True)
+    assert bench.resolve_gather_flags(ap.parse_args(["--gpus", "8", "--steps", "20", "--warmup", "3"]), 8) == (False, False)
+    assert bench.resolve_gather_flags(ap.parse_args(["--gpus", "8", "--gather"]), 8) == (True, False)
 
 
 def test_bench_bounded_wait_returns_an_answer_whatever_happens():
