@@ -46,9 +46,13 @@
 #endif
 #define KWA      0
 #define FPE      0
-#define EAX      0
+#ifndef EAX                  /* micro_aes.h:43 -- EAX (uaes_eax_siv.hip); every library exports AES_EAX_*, a caller */
+#define EAX      0          /* built with -DEAX=1 sees the prototypes (below)                                       */
+#endif
 #define EAXP     0
-#define SIV      0
+#ifndef SIV                  /* micro_aes.h:44 -- SIV, RFC 5297 (uaes_eax_siv.hip); every library exports AES_SIV_*, */
+#define SIV      0          /* a caller built with -DSIV=1 sees the prototypes (below)                              */
+#endif
 #define OCB      1          /* RFC 7253: block-parallel, offsets from the Gray code (uaes_ocb.hip) */
 #ifndef POLY1305             /* micro_aes.h:52 -- Poly1305-AES (uaes_poly1305.hip); every library exports        */
 #define POLY1305 0          /* AES_Poly1305, a caller built with -DPOLY1305=1 sees its prototype (below)        */
@@ -95,6 +99,14 @@ enum constant_parameters_of_modes
 #endif
     SIVGCM_NONCE_LEN = 12,
     SIVGCM_TAG_LEN  = 16,
+#if EAX
+#ifndef EAX_NONCE_LEN      /* micro_aes.h:120-121; -DEAX_NONCE_LEN=n (any, 0 too) / -DEAX_TAG_LEN=n (1..16) bind */
+    EAX_NONCE_LEN   = 16,  /* AES_EAX_* to the general entry points below                                        */
+#endif
+#ifndef EAX_TAG_LEN
+    EAX_TAG_LEN     = 16,
+#endif
+#endif
 #if AES___ == 256 || AES___ == 192
     AES_KEYLENGTH   = AES___ / 8
 #else
@@ -324,6 +336,52 @@ char GCM_SIV_decrypt(const uint8_t *key, const uint8_t *nonce,
 
 void AES_CMAC(const uint8_t *key,
               const void *data, const size_t dataSize, uint8_t mac[16]);
+
+#if EAX
+/* EAX (micro_aes.c:1560-1648): tag = N ^ H ^ C, EAX_TAG_LEN bytes appended at crtxt + ptextLen; decrypt checks the tag
+ * before it writes (a forgery returns M_AUTHENTICATION_ERROR and leaves pntxt as it was) */
+void AES_EAX_encrypt(const uint8_t *key, const uint8_t *nonce,
+                     const void *aData, const size_t aDataLen,
+                     const void *pntxt, const size_t ptextLen, void *crtxt);
+char AES_EAX_decrypt(const uint8_t *key, const uint8_t *nonce,
+                     const void *aData, const size_t aDataLen,
+                     const void *crtxt, const size_t crtxtLen, void *pntxt);
+void AES_EAX_encrypt_lens(const size_t nonceLen, const size_t tagLen, const uint8_t *key, const uint8_t *nonce,
+                          const void *aData, const size_t aDataLen,
+                          const void *pntxt, const size_t ptextLen, void *crtxt);
+char AES_EAX_decrypt_lens(const size_t nonceLen, const size_t tagLen, const uint8_t *key, const uint8_t *nonce,
+                          const void *aData, const size_t aDataLen,
+                          const void *crtxt, const size_t crtxtLen, void *pntxt);
+#if defined(EAX_NONCE_LEN) || defined(EAX_TAG_LEN)
+typedef char uaes_eax_lengths_ok[(EAX_TAG_LEN >= 1 && EAX_TAG_LEN <= 16) ? 1 : -1];
+UAES_STATIC_INLINE void AES_EAX_encrypt_nl(const uint8_t *key, const uint8_t *nonce,
+                                           const void *aData, const size_t aDataLen,
+                                           const void *pntxt, const size_t ptextLen, void *crtxt)
+{
+    AES_EAX_encrypt_lens(EAX_NONCE_LEN, EAX_TAG_LEN, key, nonce, aData, aDataLen, pntxt, ptextLen, crtxt);
+}
+UAES_STATIC_INLINE char AES_EAX_decrypt_nl(const uint8_t *key, const uint8_t *nonce,
+                                           const void *aData, const size_t aDataLen,
+                                           const void *crtxt, const size_t crtxtLen, void *pntxt)
+{
+    return AES_EAX_decrypt_lens(EAX_NONCE_LEN, EAX_TAG_LEN, key, nonce, aData, aDataLen, crtxt, crtxtLen, pntxt);
+}
+#define AES_EAX_encrypt AES_EAX_encrypt_nl
+#define AES_EAX_decrypt AES_EAX_decrypt_nl
+#endif
+#endif
+
+#if SIV
+/* SIV, RFC 5297 (micro_aes.c:1323-1411): keys = K_s2v || K_ctr (AES_KEYLENGTH bytes each), iv = the synthesized IV;
+ * decrypt returns M_AUTHENTICATION_ERROR on a mismatch */
+void AES_SIV_encrypt(const uint8_t *keys,
+                     const void *aData, const size_t aDataLen,
+                     const void *pntxt, const size_t ptextLen,
+                     uint8_t iv[16], void *crtxt);
+char AES_SIV_decrypt(const uint8_t *keys, const uint8_t iv[16],
+                     const void *aData, const size_t aDataLen,
+                     const void *crtxt, const size_t crtxtLen, void *pntxt);
+#endif
 
 #if POLY1305
 /* keys = k (AES_KEYLENGTH bytes) || r (16 bytes); mac = Poly1305-AES of data under nonce (micro_aes.h:444-450) */

@@ -232,6 +232,42 @@ int uaes_ccm_decrypt_ex(int keybits, const uint8_t *key, const uint8_t *nonce, s
                         const void *aData, size_t aDataLen,
                         const void *crtxt, size_t crtxtLen, void *pntxt);
 
+/* ---- EAX and SIV (RFC 5297): replace AES_EAX_* / AES_SIV_* ----------------
+ * micro_aes.c:1560-1648 (EAX) and :1323-1411 (SIV).  Host or device pointers, as CCM; the host policy applies.
+ * EAX: nonce of any length (0 included; the reference's EAX_NONCE_LEN), tagLen = 1..16 (EAX_TAG_LEN) bytes of
+ * N ^ H ^ C appended at crtxt + ptextLen.  Decrypt checks the tag BEFORE it writes: on a mismatch it returns
+ * UAES_E_AUTHENTICATION and pntxt is untouched (the wipe switch does not apply).
+ * SIV: keys = K_s2v || K_ctr (keybits / 8 bytes each), iv = the 16-byte synthesized IV (out / in); an empty AAD is
+ * no header unit.  Decrypt runs CTR first and authenticates the result: on a mismatch it returns
+ * UAES_E_AUTHENTICATION and leaves the text in pntxt unless uaes_set_wipe_on_auth_failure(1).
+ * in == out works for both.  A text of at most 16 KiB is one kernel launch; a longer one runs its independent CMAC
+ * chains at the same time (one launch), reads the counter block back and runs CTR -- the call takes about as long
+ * as its longest chain (~0.42 us per AES-128 block).                                                           */
+int uaes_eax_encrypt(int keybits, const uint8_t *key, const uint8_t *nonce, size_t nonceLen, size_t tagLen,
+                     const void *aData, size_t aDataLen, const void *pntxt, size_t ptextLen, void *crtxt);
+int uaes_eax_decrypt(int keybits, const uint8_t *key, const uint8_t *nonce, size_t nonceLen, size_t tagLen,
+                     const void *aData, size_t aDataLen, const void *crtxt, size_t crtxtLen, void *pntxt);
+int uaes_siv_encrypt(int keybits, const uint8_t *keys, const void *aData, size_t aDataLen,
+                     const void *pntxt, size_t ptextLen, uint8_t iv[16], void *crtxt);
+int uaes_siv_decrypt(int keybits, const uint8_t *keys, const uint8_t iv[16], const void *aData, size_t aDataLen,
+                     const void *crtxt, size_t crtxtLen, void *pntxt);
+/* Batches under one key: nmsg records of msg_bytes each back to back (record m at m * msg_bytes), sixteen GPU lanes
+ * per record.  EAX: nonces = nmsg * nonce_len bytes, tags = nmsg * 16 (the whole tag); SIV: ivs = nmsg * 16.
+ * aData = nmsg * aad_bytes (aad_bytes 0: no AAD).  Decrypt writes verdicts[m] = 1 (authentic) / 0 and returns 0 when
+ * every record is authentic, else UAES_E_AUTHENTICATION; EAX leaves a forged record's plaintext untouched, SIV
+ * follows the wipe switch per record.  Every array host or device memory.                                      */
+int uaes_eax_encrypt_batch(int keybits, const uint8_t *key, size_t nmsg, size_t msg_bytes,
+                           const uint8_t *nonces, size_t nonce_len, const void *aData, size_t aad_bytes,
+                           const void *pntxt, void *crtxt, uint8_t *tags);
+int uaes_eax_decrypt_batch(int keybits, const uint8_t *key, size_t nmsg, size_t msg_bytes,
+                           const uint8_t *nonces, size_t nonce_len, const void *aData, size_t aad_bytes,
+                           const void *crtxt, const uint8_t *tags, void *pntxt, uint8_t *verdicts);
+int uaes_siv_encrypt_batch(int keybits, const uint8_t *keys, size_t nmsg, size_t msg_bytes,
+                           const void *aData, size_t aad_bytes, const void *pntxt, uint8_t *ivs, void *crtxt);
+int uaes_siv_decrypt_batch(int keybits, const uint8_t *keys, size_t nmsg, size_t msg_bytes,
+                           const void *aData, size_t aad_bytes, const uint8_t *ivs, const void *crtxt, void *pntxt,
+                           uint8_t *verdicts);
+
 /* ---- CBC / CFB / OFB: replace AES_CBC_*, AES_CFB_*, AES_OFB_* -------------
  * micro_aes.c:697-782 (CBC with CS3 ciphertext stealing, CTS 1: the last two
  * blocks are always swapped, len < 16 -> UAES_E_DATALENGTH), :799-845 (CFB),
@@ -552,6 +588,11 @@ void uaes_debug_plan_disable(unsigned mask);
  * "poly.batch") for one message of len bytes (nmsg <= 1) or a batch of nmsg >= 2 such messages; out (may be NULL)
  * = launches, workgroups of the main kernel, blocks per thread.  Works without a device (a 256-CU MI355X). */
 const char *uaes_debug_plan_poly1305(size_t len, size_t nmsg, int out[3]);
+/* EAX / SIV's planner (csrc/uaes_plan.h, its own rows): "eax.small" / "eax.long" / "eax.batch" (siv = 0) or
+ * "s2v.small" / "s2v.long" / "s2v.batch" (siv = 1) for one text of len bytes (nmsg <= 1) or a batch of nmsg >= 2,
+ * dir 0 encrypt / 1 decrypt; out (may be NULL) = launches, workgroups of the main kernel, UAES_EAX_SIV_SMALL_MAX
+ * (the longest text of the small arrangement).  NULL for arguments that make no sense. */
+const char *uaes_debug_plan_eax_siv(int siv, int dir, size_t len, size_t nmsg, int out[3]);
 
 /* Test hooks of the one-launch GCM / GCM-SIV / streamed-piece arrangements (chunk workgroups + one preparing workgroup
  * in ONE launch; whoever of them arrives last on a counter word folds the chunk hashes and makes the tag -- nobody

@@ -43,6 +43,9 @@ EXPORTS = [
     "uaes_cmac", "uaes_ccm_encrypt", "uaes_ccm_decrypt", "uaes_gcmsiv_encrypt", "uaes_gcmsiv_decrypt",
     "uaes_ocb_encrypt", "uaes_ocb_decrypt", "uaes_ocb_dev",
     "uaes_poly1305", "uaes_poly1305_dev", "uaes_poly1305_batch", "uaes_debug_plan_poly1305",
+    "uaes_eax_encrypt", "uaes_eax_decrypt", "uaes_siv_encrypt", "uaes_siv_decrypt",
+    "uaes_eax_encrypt_batch", "uaes_eax_decrypt_batch", "uaes_siv_encrypt_batch", "uaes_siv_decrypt_batch",
+    "uaes_debug_plan_eax_siv",
     "uaes_mgpu_ctr_xcrypt_at", "uaes_mgpu_xts_sectors", "uaes_mgpu_ctr_encrypt_gather", "uaes_debug_gather_stats", "uaes_debug_gcm_look", "uaes_debug_gcm_chunk_folds",
     "uaes_debug_plan", "uaes_debug_plan_at", "uaes_debug_arrangement_name", "uaes_debug_plan_disable",
     "uaes_mgpu_ecb_encrypt", "uaes_mgpu_ecb_decrypt", "uaes_mgpu_gcm_encrypt", "uaes_mgpu_gcm_decrypt",
@@ -68,6 +71,7 @@ COMPAT_EXPORTS = [
     "AES_CCM_encrypt_lens", "AES_CCM_decrypt_lens", "AES_OCB_encrypt_lens", "AES_OCB_decrypt_lens",
     "AES_CCM_encrypt", "AES_CCM_decrypt", "AES_CMAC", "GCM_SIV_encrypt", "GCM_SIV_decrypt",
     "AES_OCB_encrypt", "AES_OCB_decrypt", "AES_Poly1305",
+    "AES_EAX_encrypt", "AES_EAX_decrypt", "AES_EAX_encrypt_lens", "AES_EAX_decrypt_lens", "AES_SIV_encrypt", "AES_SIV_decrypt",
     "AES_CBC_encrypt", "AES_CBC_decrypt", "AES_CFB_encrypt", "AES_CFB_decrypt", "AES_OFB_encrypt", "AES_OFB_decrypt",
 ]
 
@@ -141,6 +145,16 @@ def engine():
     L.uaes_poly1305_dev.argtypes = [i, vp, vp, vp, sz, vp, vp]
     L.uaes_poly1305_batch.argtypes = [i, vp, vp, sz, sz, vp, vp]
     L.uaes_debug_plan_poly1305.argtypes = [sz, sz, C.POINTER(C.c_int)]
+    L.uaes_eax_encrypt.argtypes = [i, vp, vp, sz, sz, vp, sz, vp, sz, vp]
+    L.uaes_eax_decrypt.argtypes = [i, vp, vp, sz, sz, vp, sz, vp, sz, vp]
+    L.uaes_siv_encrypt.argtypes = [i, vp, vp, sz, vp, sz, vp, vp]
+    L.uaes_siv_decrypt.argtypes = [i, vp, vp, vp, sz, vp, sz, vp]
+    L.uaes_eax_encrypt_batch.argtypes = [i, vp, sz, sz, vp, sz, vp, sz, vp, vp, vp]
+    L.uaes_eax_decrypt_batch.argtypes = [i, vp, sz, sz, vp, sz, vp, sz, vp, vp, vp, vp]
+    L.uaes_siv_encrypt_batch.argtypes = [i, vp, sz, sz, vp, sz, vp, vp, vp]
+    L.uaes_siv_decrypt_batch.argtypes = [i, vp, sz, sz, vp, sz, vp, vp, vp, vp]
+    L.uaes_debug_plan_eax_siv.argtypes = [i, i, sz, sz, C.POINTER(C.c_int)]
+    L.uaes_debug_plan_eax_siv.restype = C.c_char_p
     L.uaes_debug_plan_poly1305.restype = C.c_char_p
     for n in ("uaes_cbc_encrypt", "uaes_cbc_decrypt", "uaes_cbc_decrypt_blocks", "uaes_cfb_encrypt", "uaes_cfb_decrypt", "uaes_ofb_xcrypt"):
         getattr(L, n).argtypes = [i, vp, vp, vp, sz, vp]
@@ -207,7 +221,8 @@ def engine():
         if n.startswith("uaes_debug_") and not hasattr(L, n):
             continue
         if n not in ("uaes_last_error", "uaes_version", "uaes_gcm_key_free", "uaes_gcm_stream_abort", "uaes_debug_gather_stats", "uaes_debug_gcm_look",
-                     "uaes_debug_arrangement_name", "uaes_debug_plan_disable", "uaes_debug_plan_poly1305"):
+                     "uaes_debug_arrangement_name", "uaes_debug_plan_disable", "uaes_debug_plan_poly1305",
+                     "uaes_debug_plan_eax_siv"):
             getattr(L, n).restype = i
     _lib = L
     return L
@@ -475,6 +490,115 @@ def poly1305_plan(len, nmsg=1):
     """What a Poly1305 call would run (uaes_debug_plan_poly1305): (arrangement, launches, workgroups, blocks per thread)."""
     out = (C.c_int * 3)()
     name = engine().uaes_debug_plan_poly1305(len, nmsg, out)
+    return name.decode(), out[0], out[1], out[2]
+
+
+def AES_EAX_encrypt(key, nonce, aData, pntxt, tag_len=16):
+    """micro_aes.c:1560.  Any nonce length (the reference's EAX_NONCE_LEN, 16 by default), tag_len = EAX_TAG_LEN
+    (1..16); returns ciphertext || tag."""
+    _taglen(tag_len, 1, 16, False, "EAX")
+    o = _out(len(pntxt) + 16)
+    _check(engine().uaes_eax_encrypt(_bits(key), _in(key), _in(nonce), len(nonce), tag_len, _in(aData), len(aData),
+                                     _in(pntxt), len(pntxt), o), "AES_EAX_encrypt")
+    return bytes(o)[: len(pntxt) + tag_len]
+
+
+def AES_EAX_decrypt(key, nonce, aData, crtxt_and_tag, prefill=0, tag_len=16):
+    """micro_aes.c:1613.  Returns (code, text); the tag is checked first, so on 0x1A the text is the untouched
+    prefill."""
+    _taglen(tag_len, 1, 16, False, "EAX")
+    n = len(crtxt_and_tag) - tag_len
+    if n < 0:
+        raise ValueError("shorter than the tag")
+    o = _out(n, prefill)
+    rc = _check(engine().uaes_eax_decrypt(_bits(key), _in(key), _in(nonce), len(nonce), tag_len, _in(aData), len(aData),
+                                          _in(crtxt_and_tag), n, o), "AES_EAX_decrypt")
+    return rc, bytes(o)[:n]
+
+
+def AES_SIV_encrypt(keys, aData, pntxt):
+    """micro_aes.c:1373 (RFC 5297).  keys = K_s2v || K_ctr (32, 48 or 64 bytes); returns (iv, ciphertext)."""
+    iv, o = _out(16), _out(len(pntxt))
+    _check(engine().uaes_siv_encrypt(_bits(keys, 2), _in(keys), _in(aData), len(aData), _in(pntxt), len(pntxt), iv, o),
+           "AES_SIV_encrypt")
+    return bytes(iv), bytes(o)[: len(pntxt)]
+
+
+def AES_SIV_decrypt(keys, iv, aData, crtxt, prefill=0):
+    """micro_aes.c:1394.  Returns (code, text); on 0x1A the text is the decryption (zeros under the wipe switch)."""
+    o = _out(len(crtxt), prefill)
+    rc = _check(engine().uaes_siv_decrypt(_bits(keys, 2), _in(keys), _fixed(iv, 16, "iv"), _in(aData), len(aData),
+                                          _in(crtxt), len(crtxt), o), "AES_SIV_decrypt")
+    return rc, bytes(o)[: len(crtxt)]
+
+
+def _records(items, what):
+    n = len(items)
+    size = len(items[0]) if n else 0
+    if any(len(x) != size for x in items):
+        raise ValueError("equal-sized %s" % what)
+    return size, b"".join(bytes(x) for x in items)
+
+
+def eax_batch(key, nonces, aads, texts, decrypt=False, tags=None, prefill=0):
+    """EAX of many records under one key (uaes_eax_*_batch): equal-sized nonces, AADs (or None) and texts.
+    encrypt: returns (ciphertexts, 16-byte tags); decrypt (tags given): returns (code, plaintexts, verdicts), a
+    forged record's plaintext stays the prefill."""
+    n = len(texts)
+    aads = aads if aads is not None else [b""] * n
+    if len(nonces) != n or len(aads) != n or (decrypt and (tags is None or len(tags) != n)):
+        raise ValueError("one nonce, AAD (and tag) per record")
+    if n == 0:
+        return (0, [], []) if decrypt else ([], [])
+    nl, nb = _records(nonces, "nonces")
+    al, ab = _records(aads, "AADs")
+    ml, mb = _records(texts, "texts")
+    L = engine()
+    o = _out(n * ml, prefill)
+    if not decrypt:
+        t = _out(n * 16)
+        _check(L.uaes_eax_encrypt_batch(_bits(key), _in(key), n, ml, _in(nb), nl, _in(ab), al, _in(mb), o, t),
+               "uaes_eax_encrypt_batch")
+        raw, tr = bytes(o), bytes(t)
+        return [raw[i * ml:(i + 1) * ml] for i in range(n)], [tr[16 * i:16 * i + 16] for i in range(n)]
+    v = _out(n)
+    rc = _check(L.uaes_eax_decrypt_batch(_bits(key), _in(key), n, ml, _in(nb), nl, _in(ab), al, _in(mb),
+                                         _in(b"".join(tags)), o, v), "uaes_eax_decrypt_batch")
+    raw = bytes(o)
+    return rc, [raw[i * ml:(i + 1) * ml] for i in range(n)], list(bytes(v)[:n])
+
+
+def siv_batch(keys, aads, texts, decrypt=False, ivs=None, prefill=0):
+    """SIV (RFC 5297) of many records under one key pair (uaes_siv_*_batch): equal-sized AADs (or None) and texts.
+    encrypt: returns (ivs, ciphertexts); decrypt (ivs given): returns (code, plaintexts, verdicts)."""
+    n = len(texts)
+    aads = aads if aads is not None else [b""] * n
+    if len(aads) != n or (decrypt and (ivs is None or len(ivs) != n)):
+        raise ValueError("one AAD (and IV) per record")
+    if n == 0:
+        return (0, [], []) if decrypt else ([], [])
+    al, ab = _records(aads, "AADs")
+    ml, mb = _records(texts, "texts")
+    L = engine()
+    o = _out(n * ml, prefill)
+    if not decrypt:
+        t = _out(n * 16)
+        _check(L.uaes_siv_encrypt_batch(_bits(keys, 2), _in(keys), n, ml, _in(ab), al, _in(mb), t, o),
+               "uaes_siv_encrypt_batch")
+        raw, tr = bytes(o), bytes(t)
+        return [tr[16 * i:16 * i + 16] for i in range(n)], [raw[i * ml:(i + 1) * ml] for i in range(n)]
+    v = _out(n)
+    rc = _check(L.uaes_siv_decrypt_batch(_bits(keys, 2), _in(keys), n, ml, _in(ab), al, _in(b"".join(ivs)), _in(mb), o, v),
+                "uaes_siv_decrypt_batch")
+    raw = bytes(o)
+    return rc, [raw[i * ml:(i + 1) * ml] for i in range(n)], list(bytes(v)[:n])
+
+
+def eax_siv_plan(siv, length, nmsg=1, decrypt=False):
+    """What an EAX (siv=False) / SIV call would run (uaes_debug_plan_eax_siv): (arrangement, launches, workgroups,
+    longest text of the small arrangement)."""
+    out = (C.c_int * 3)()
+    name = engine().uaes_debug_plan_eax_siv(int(bool(siv)), int(bool(decrypt)), length, nmsg, out)
     return name.decode(), out[0], out[1], out[2]
 
 

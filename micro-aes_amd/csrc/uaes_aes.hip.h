@@ -660,7 +660,7 @@ __device__ __forceinline__ void row_fill_tables(const u32 *__restrict__ te0, con
 }
 
 template <int NR>
-__device__ __forceinline__ RowLane<NR> row_lane()
+__device__ __forceinline__ RowLane<NR> row_lane(u32 key_at = 65536u)   /* key_at: LDS byte address of the round keys */
 {
     RowLane<NR> L;
     const u32 i = threadIdx.x & 15u, r = i & 3u;
@@ -670,7 +670,7 @@ __device__ __forceinline__ RowLane<NR> row_lane()
     L.sel = 0x0c020000u | ((4u + r) << 8);
     L.lsel = (0x0c0c0c0cu & ~(0xffu << (8u * r))) | ((4u + r) << (8u * r));
 #pragma unroll
-    for (int j = 0; j <= NR; ++j) L.kc[j] = lds_word(65536u + 16u * (u32)j + 4u * L.c);
+    for (int j = 0; j <= NR; ++j) L.kc[j] = lds_word(key_at + 16u * (u32)j + 4u * L.c);
     return L;
 }
 
@@ -706,7 +706,7 @@ __device__ __forceinline__ void row4_fill_tables(const u32 *__restrict__ te0, co
 }
 
 template <int NR>
-__device__ __forceinline__ RowLane<NR> row4_lane()
+__device__ __forceinline__ RowLane<NR> row4_lane(u32 key_at = 131072u)
 {
     RowLane<NR> L;
     const u32 i = threadIdx.x & 15u, r = i & 3u, q = (threadIdx.x >> 4) & 3u;
@@ -716,7 +716,7 @@ __device__ __forceinline__ RowLane<NR> row4_lane()
     L.sel = 0x0c020000u | ((4u + r) << 8);
     L.lsel = (0x0c0c0c0cu & ~(0xffu << (8u * r))) | ((4u + r) << (8u * r));
 #pragma unroll
-    for (int j = 0; j <= NR; ++j) L.kc[j] = lds_word(131072u + 16u * (u32)j + 4u * L.c);
+    for (int j = 0; j <= NR; ++j) L.kc[j] = lds_word(key_at + 16u * (u32)j + 4u * L.c);
     return L;
 }
 

@@ -6,7 +6,9 @@
 #include <stdio.h>
 #include <stdlib.h>
 
-#define POLY1305 1                  /* the libraries export AES_Poly1305 whatever a caller's switch says */
+#define POLY1305 1                  /* the libraries export AES_Poly1305, AES_EAX_* and AES_SIV_* whatever a */
+#define EAX      1                  /* caller's switches say                                                 */
+#define SIV      1
 #include "../../include/micro_aes.h"
 #include "../../include/uaes_hip.h"
 
@@ -322,5 +324,47 @@ char AES_OCB_decrypt(const uint8_t *key, const uint8_t *nonce,
                      const void *crtxt, const size_t crtxtLen, void *pntxt)
 {
     return soft("AES_OCB_decrypt", uaes_ocb_decrypt(KB, key, nonce, aData, aDataLen, crtxt, crtxtLen, pntxt),
+                M_DECRYPTION_ERROR);
+}
+
+void AES_EAX_encrypt_lens(const size_t nonceLen, const size_t tagLen, const uint8_t *key, const uint8_t *nonce,
+                          const void *aData, const size_t aDataLen,
+                          const void *pntxt, const size_t ptextLen, void *crtxt)
+{
+    must("AES_EAX_encrypt", uaes_eax_encrypt(KB, key, nonce, nonceLen, tagLen, aData, aDataLen, pntxt, ptextLen, crtxt));
+}
+
+char AES_EAX_decrypt_lens(const size_t nonceLen, const size_t tagLen, const uint8_t *key, const uint8_t *nonce,
+                          const void *aData, const size_t aDataLen,
+                          const void *crtxt, const size_t crtxtLen, void *pntxt)
+{
+    return soft("AES_EAX_decrypt", uaes_eax_decrypt(KB, key, nonce, nonceLen, tagLen, aData, aDataLen, crtxt, crtxtLen, pntxt),
+                M_DECRYPTION_ERROR);
+}
+
+void AES_EAX_encrypt(const uint8_t *key, const uint8_t *nonce,
+                     const void *aData, const size_t aDataLen,
+                     const void *pntxt, const size_t ptextLen, void *crtxt)
+{
+    AES_EAX_encrypt_lens(16, 16, key, nonce, aData, aDataLen, pntxt, ptextLen, crtxt);
+}
+
+char AES_EAX_decrypt(const uint8_t *key, const uint8_t *nonce,
+                     const void *aData, const size_t aDataLen,
+                     const void *crtxt, const size_t crtxtLen, void *pntxt)
+{
+    return AES_EAX_decrypt_lens(16, 16, key, nonce, aData, aDataLen, crtxt, crtxtLen, pntxt);
+}
+
+void AES_SIV_encrypt(const uint8_t *keys, const void *aData, const size_t aDataLen,
+                     const void *pntxt, const size_t ptextLen, uint8_t iv[16], void *crtxt)
+{
+    must("AES_SIV_encrypt", uaes_siv_encrypt(KB, keys, aData, aDataLen, pntxt, ptextLen, iv, crtxt));
+}
+
+char AES_SIV_decrypt(const uint8_t *keys, const uint8_t iv[16], const void *aData, const size_t aDataLen,
+                     const void *crtxt, const size_t crtxtLen, void *pntxt)
+{
+    return soft("AES_SIV_decrypt", uaes_siv_decrypt(KB, keys, iv, aData, aDataLen, crtxt, crtxtLen, pntxt),
                 M_DECRYPTION_ERROR);
 }

@@ -244,6 +244,33 @@ int uaesk_poly1305(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk 
 int uaesk_poly1305_batch(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, const uint8_t *r16,
                          const void *nonces, size_t nmsg, size_t msg_bytes, const void *data, void *macs);
 
+/* EAX and SIV, RFC 5297 (uaes_eax_siv.hip); every pointer device memory unless noted.
+ * uaesk_eax_small: a text of <= UAES_EAX_SIV_SMALL_MAX bytes in one launch; encrypt writes tag_len (1..16) bytes of
+ * tag to tag_io, decrypt compares them with tag_io, writes *status = 0 / 0x1A and writes `out` only when authentic.
+ * uaesk_eax_macs: mode 0 = N || H into res48 (N at +16, N ^ H at +32); 1 = N || H || C, the tag compared with tag_io
+ * (status at +0, N at +16); 2 = C only over ct, the tag (C ^ N ^ H from res48) to tag_io.
+ * uaesk_s2v_small: iv16 (host; decrypt only) = the IV to check; encrypt writes V to iv_out (16 bytes).
+ * uaesk_s2v_macs: S2V over text (the plaintext) into res48 (+16; encrypt) or its status against iv16 (+0; decrypt).
+ * Batches: record m's text at in / out + m msg_bytes, nonce at nonces + m nonce_len, AAD at aad + m aad_bytes, tag / V
+ * at tags / ivs + 16 m; decrypt writes verdicts[m] (1 = authentic) and ORs 1 into *bad for a forgery.            */
+int uaesk_eax_small(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, int decrypt,
+                    const void *nonce, size_t nonce_len, const void *aad, size_t aad_len,
+                    const void *in, size_t len, void *out, void *tag_io, unsigned tag_len, int *status);
+int uaesk_eax_macs(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, int mode,
+                   const void *nonce, size_t nonce_len, const void *aad, size_t aad_len,
+                   const void *ct, size_t len, void *tag_io, unsigned tag_len, void *res48);
+int uaesk_s2v_small(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek_s2v, const uaesk_rk *ek_ctr,
+                    int decrypt, const uint8_t *iv16, const void *aad, size_t aad_len,
+                    const void *in, size_t len, void *out, void *iv_out, int *status);
+int uaesk_s2v_macs(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek_s2v, int decrypt,
+                   const uint8_t *iv16, const void *aad, size_t aad_len, const void *text, size_t len, void *res48);
+int uaesk_eax_batch(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, int decrypt,
+                    const void *nonces, size_t nonce_len, const void *aad, size_t aad_bytes,
+                    size_t nmsg, size_t msg_bytes, const void *in, void *out, void *tags, void *verdicts, int *bad);
+int uaesk_s2v_batch(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek_s2v, const uaesk_rk *ek_ctr,
+                    int decrypt, int wipe, const void *aad, size_t aad_bytes,
+                    size_t nmsg, size_t msg_bytes, const void *in, void *out, void *ivs, void *verdicts, int *bad);
+
 /* Device self-test of the primitives; writes a bitmask of failures.        */
 int uaesk_selftest(void *stream, const uaesk_tables *tb, const uaesk_rk *ek128,
                    const uaesk_rk *dk128, unsigned *d_result);

@@ -2786,6 +2786,328 @@ int uaes_ccm_decrypt(int keybits, const uint8_t *key, const uint8_t *nonce,
 }
 
 /* ------------------------------------------------------------------------ */
+/* EAX and SIV, RFC 5297 (AES_EAX_* micro_aes.c:1560-1648, AES_SIV_* :1373-1411) */
+/* ------------------------------------------------------------------------ */
+/* Kernels in uaes_eax_siv.hip.  A text of at most UAES_EAX_SIV_SMALL_MAX bytes is one launch; a longer one runs its
+ * independent chains in one launch, reads the counter block (and the verdict) back in one fetch and hands it to the
+ * positioned CTR kernels.  Side arrays (nonce, AAD) in host memory travel through the lane's scratch.             */
+#define SIDE(n) (((n) + 15) & ~(size_t)15)
+
+static int side_in(lane *L, size_t *off, const void *src, size_t n, const void **d)
+{
+    *d = NULL;
+    if (!n) return 0;
+    if (is_device_ptr(src)) { *d = src; return wait_for_callers_device_work(); }
+    *d = (char *)L->scratch + *off;
+    *off += SIDE(n);
+    HIPCHK(hipMemcpyAsync((void *)*d, src, n, hipMemcpyHostToDevice, (hipStream_t)L->stream));
+    return 0;
+}
+
+/* 16 bytes (an IV) from host or device memory to host memory, or back */
+static int iv_read(uint8_t out[16], const uint8_t *iv)
+{
+    if (is_device_ptr(iv)) { HIPCHK(hipMemcpy(out, iv, 16, hipMemcpyDeviceToHost)); }
+    else memcpy(out, iv, 16);
+    return 0;
+}
+static int iv_write(uint8_t *iv, const uint8_t v[16])
+{
+    if (is_device_ptr(iv)) { HIPCHK(hipMemcpy(iv, v, 16, hipMemcpyHostToDevice)); }
+    else memcpy(iv, v, 16);
+    return 0;
+}
+
+#define HIPCHK_GOTO(call)                                                                            \
+    do {                                                                                              \
+        const hipError_t e_ = (call);                                                                 \
+        if (e_ != hipSuccess) { rc = fail(UAES_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); goto out; } \
+    } while (0)
+#define ES_KCHK(what, call)                                                                           \
+    do {                                                                                              \
+        const int k_ = (call);                                                                        \
+        if (k_) { rc = fail(UAES_E_HIP, what " launch: %s", hipGetErrorString((hipError_t)k_)); goto out; } \
+    } while (0)
+
+static int eax_common(int keybits, const uint8_t *key, int decrypt, const uint8_t *nonce, size_t nonceLen, size_t tagLen,
+                      const void *aData, size_t aDataLen, const void *in, size_t len, void *outp)
+{
+    context *c;
+    lane *L;
+    keysched ks;
+    io_plan io;
+    const void *d_nonce, *d_aad;
+    size_t off = 0;
+    int rc, status = 0;
+    uint8_t res[32];
+    if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
+    if (!in || (len && !outp) || (nonceLen && !nonce)) return fail(UAES_E_ARG, "NULL pointer");
+    if (!decrypt && !outp) return fail(UAES_E_ARG, "NULL pointer");
+    if (tagLen < 1 || tagLen > 16) return fail(UAES_E_ARG, "EAX tag length %zu (1..16)", tagLen);
+    if (aDataLen && !aData) return fail(UAES_E_ARG, "NULL aData with aDataLen != 0");
+    if (host_take(in, outp, len, 1) && !is_device_ptr(aData) && !is_device_ptr(nonce)) {
+        const uaesh_key hk = host_key(&ks);
+        HOST_RET(ks, uaesh_eax(&hk, decrypt, nonce, nonceLen, tagLen, (const uint8_t *)aData, aDataLen,
+                               (const uint8_t *)in, len, (uint8_t *)outp));
+    }
+    if ((rc = enter(&c, &L)) != 0) { burn(&ks, sizeof ks); return rc; }
+    if ((rc = lane_scratch(L, SIDE(nonceLen) + SIDE(aDataLen), SCRATCH_OTHER)) != 0) goto out;
+    if ((rc = side_in(L, &off, nonce, nonceLen, &d_nonce)) != 0) goto out;
+    if ((rc = side_in(L, &off, aData, aDataLen, &d_aad)) != 0) goto out;
+    if (decrypt) rc = plan_io(L, in, len + tagLen, outp, len, &io);
+    else rc = plan_io(L, in, len, outp, len + tagLen, &io);
+    if (rc) goto out;
+    {
+        unsigned char *tag = decrypt ? (unsigned char *)io.din + len : (unsigned char *)io.dout + len;
+        const unsigned tl = (unsigned)tagLen;
+        if (len <= UAES_EAX_SIV_SMALL_MAX) {             /* eax.small: one launch */
+            ES_KCHK("eax", uaesk_eax_small(L->stream, &c->tb, ks.nr, &ks.ek, decrypt, d_nonce, nonceLen, d_aad, aDataLen,
+                                           io.din, len, io.dout, tag, tl, decrypt ? L->d_status : NULL));
+            if (decrypt) {
+                if ((rc = lane_fetch(L, &status, L->d_status, sizeof status)) != 0) goto out;
+                io.drained = 1;
+            }
+        } else {                                          /* eax.long: the chains, one fetch, then CTR */
+            uaesk_ctr ctr;
+            ES_KCHK("eax", uaesk_eax_macs(L->stream, &c->tb, ks.nr, &ks.ek, decrypt ? 1 : 0, d_nonce, nonceLen,
+                                          d_aad, aDataLen, decrypt ? io.din : NULL, decrypt ? len : 0, tag, tl, L->d_status));
+            if ((rc = lane_fetch(L, res, L->d_status, sizeof res)) != 0) goto out;
+            memcpy(&status, res, sizeof status);
+            if (decrypt && status) {
+                io.drained = 1;
+            } else {
+                make_ctr(&ctr, res + 16, 0);
+                ES_KCHK("eax ctr", uaesk_ctr_xcrypt(L->stream, &c->tb, ks.nr, &ks.ek, &ctr, io.din, io.dout, len, NULL));
+                if (!decrypt)
+                    ES_KCHK("eax", uaesk_eax_macs(L->stream, &c->tb, ks.nr, &ks.ek, 2, NULL, 0, NULL, 0, io.dout, len,
+                                                  tag, tl, L->d_status));
+            }
+        }
+    }
+    /* the tag is checked before anything is written (:1638-1645): a forgery leaves pntxt as it was */
+    if (decrypt && status) rc = UAES_E_AUTHENTICATION;
+    else rc = finish_io(&io, decrypt ? len : len + tagLen);
+out:
+    burn(&ks, sizeof ks);
+    memset(res, 0, sizeof res);
+    DONE(L, rc);
+}
+
+int uaes_eax_encrypt(int keybits, const uint8_t *key, const uint8_t *nonce, size_t nonceLen, size_t tagLen,
+                     const void *aData, size_t aDataLen, const void *pntxt, size_t ptextLen, void *crtxt)
+{
+    if (!pntxt && !ptextLen) pntxt = crtxt;                       /* (nothing is read) */
+    return eax_common(keybits, key, 0, nonce, nonceLen, tagLen, aData, aDataLen, pntxt, ptextLen, crtxt);
+}
+
+int uaes_eax_decrypt(int keybits, const uint8_t *key, const uint8_t *nonce, size_t nonceLen, size_t tagLen,
+                     const void *aData, size_t aDataLen, const void *crtxt, size_t crtxtLen, void *pntxt)
+{
+    return eax_common(keybits, key, 1, nonce, nonceLen, tagLen, aData, aDataLen, crtxt, crtxtLen, pntxt);
+}
+
+static int siv_keys(keysched *k1, keysched *k2, const uint8_t *keys, int keybits)
+{
+    int rc;
+    if (!keys) return fail(UAES_E_ARG, "NULL keys");
+    if ((rc = expand_key(k1, keys, keybits)) != 0) return rc;
+    return expand_key(k2, keys + keybits / 8, keybits);
+}
+
+static int siv_common(int keybits, const uint8_t *keys, int decrypt, uint8_t *iv, const void *aData, size_t aDataLen,
+                      const void *in, size_t len, void *outp)
+{
+    context *c;
+    lane *L;
+    keysched k1, k2;
+    io_plan io;
+    const void *d_aad;
+    size_t off = 0;
+    int rc, status = 0;
+    uint8_t v[16], res[32];
+    if ((rc = siv_keys(&k1, &k2, keys, keybits)) != 0) return rc;
+    if (!iv || (len && (!in || !outp))) return fail(UAES_E_ARG, "NULL pointer");
+    if (aDataLen && !aData) return fail(UAES_E_ARG, "NULL aData with aDataLen != 0");
+    if (decrypt && (rc = iv_read(v, iv)) != 0) return rc;
+    if (host_take(in, outp, len, 1) && !is_device_ptr(aData) && !is_device_ptr(iv)) {
+        const uaesh_key h1 = host_key(&k1), h2 = host_key(&k2);
+        rc = uaesh_siv(&h1, &h2, decrypt, v, (const uint8_t *)aData, aDataLen, (const uint8_t *)in, len, (uint8_t *)outp);
+        burn(&k1, sizeof k1);
+        burn(&k2, sizeof k2);
+        if (!decrypt) memcpy(iv, v, 16);
+        if (rc && len && wipe_on_auth_failure()) memset(outp, 0, len);       /* (the default leaves the text, as the reference does) */
+        return host_result(rc);
+    }
+    if ((rc = enter(&c, &L)) != 0) { burn(&k1, sizeof k1); burn(&k2, sizeof k2); return rc; }
+    if ((rc = lane_scratch(L, SIDE(aDataLen), SCRATCH_OTHER)) != 0) goto out;
+    if ((rc = side_in(L, &off, aData, aDataLen, &d_aad)) != 0) goto out;
+    if ((rc = plan_io(L, len ? in : NULL, len, len ? outp : NULL, len, &io)) != 0) goto out;
+    if (len <= UAES_EAX_SIV_SMALL_MAX) {                  /* s2v.small: one launch */
+        ES_KCHK("siv", uaesk_s2v_small(L->stream, &c->tb, k1.nr, &k1.ek, &k2.ek, decrypt, decrypt ? v : NULL, d_aad,
+                                       aDataLen, io.din, len, io.dout, (char *)L->d_status + 16,
+                                       decrypt ? L->d_status : NULL));
+        if ((rc = lane_fetch(L, res, L->d_status, sizeof res)) != 0) goto out;
+        io.drained = 1;
+    } else if (!decrypt) {                                /* s2v.long: the chains, one fetch, then CTR(V') */
+        uaesk_ctr ctr;
+        ES_KCHK("siv", uaesk_s2v_macs(L->stream, &c->tb, k1.nr, &k1.ek, 0, NULL, d_aad, aDataLen, io.din, len, L->d_status));
+        if ((rc = lane_fetch(L, res, L->d_status, sizeof res)) != 0) goto out;
+        memcpy(v, res + 16, 16);
+        v[8] &= 0x7F;
+        v[12] &= 0x7F;
+        make_ctr(&ctr, v, 0);
+        ES_KCHK("siv ctr", uaesk_ctr_xcrypt(L->stream, &c->tb, k2.nr, &k2.ek, &ctr, io.din, io.dout, len, NULL));
+    } else {                                              /* decrypt: CTR(iv') first, S2V over what it wrote, one fetch */
+        uaesk_ctr ctr;
+        uint8_t cv[16];
+        memcpy(cv, v, 16);
+        cv[8] &= 0x7F;
+        cv[12] &= 0x7F;
+        make_ctr(&ctr, cv, 0);
+        ES_KCHK("siv ctr", uaesk_ctr_xcrypt(L->stream, &c->tb, k2.nr, &k2.ek, &ctr, io.din, io.dout, len, NULL));
+        ES_KCHK("siv", uaesk_s2v_macs(L->stream, &c->tb, k1.nr, &k1.ek, 1, v, d_aad, aDataLen, io.dout, len, L->d_status));
+        if ((rc = lane_fetch(L, res, L->d_status, sizeof res)) != 0) goto out;
+        io.drained = 1;
+    }
+    if (decrypt) {
+        memcpy(&status, res, sizeof status);
+        /* like the reference: the text is written before it is authenticated; SABOTAGE = uaes_set_wipe_on_auth_failure */
+        if ((rc = status ? finish_io_unauthenticated(&io, len) : finish_io(&io, len)) == 0 && status) rc = UAES_E_AUTHENTICATION;
+    } else {
+        memcpy(v, res + 16, 16);
+        if ((rc = finish_io(&io, len)) == 0) rc = iv_write(iv, v);
+    }
+out:
+    burn(&k1, sizeof k1);
+    burn(&k2, sizeof k2);
+    DONE(L, rc);
+}
+
+int uaes_siv_encrypt(int keybits, const uint8_t *keys, const void *aData, size_t aDataLen,
+                     const void *pntxt, size_t ptextLen, uint8_t iv[16], void *crtxt)
+{
+    return siv_common(keybits, keys, 0, iv, aData, aDataLen, pntxt, ptextLen, crtxt);
+}
+
+int uaes_siv_decrypt(int keybits, const uint8_t *keys, const uint8_t iv[16], const void *aData, size_t aDataLen,
+                     const void *crtxt, size_t crtxtLen, void *pntxt)
+{
+    return siv_common(keybits, keys, 1, (uint8_t *)iv, aData, aDataLen, crtxt, crtxtLen, pntxt);
+}
+
+/* Batches: nmsg records of msg_bytes each under one key, sixteen lanes per record.  Every array may be host or
+ * device memory; host arrays travel through the lane's staging buffers and scratch.  An EAX decryption writes only
+ * authentic records: the output buffer starts as the caller's (host memory is copied in first).                   */
+static int stage_text(lane *L, int k, const void *user, size_t n, int prefill, void **d)
+{
+    if (!n) { *d = NULL; return 0; }
+    if (is_device_ptr(user)) { *d = (void *)user; return wait_for_callers_device_work(); }
+    if (grow_on(L->stream, &L->stage[k], &L->stage_cap[k], n + 64)) return UAES_E_HIP;
+    *d = L->stage[k];
+    if (prefill) HIPCHK(hipMemcpyAsync(*d, user, n, hipMemcpyHostToDevice, (hipStream_t)L->stream));
+    return 0;
+}
+
+static int side_out(lane *L, size_t *off, void *user, size_t n, void **d)
+{
+    if (is_device_ptr(user)) { *d = user; return 0; }
+    *d = (char *)L->scratch + *off;
+    *off += SIDE(n);
+    return 0;
+}
+
+static int copy_out(lane *L, void *user, const void *d, size_t n)
+{
+    if (!n || d == user) return 0;
+    HIPCHK(hipMemcpyAsync(user, d, n, hipMemcpyDeviceToHost, (hipStream_t)L->stream));
+    return 0;
+}
+
+static int aead_batch(int siv, int decrypt, int keybits, const uint8_t *key, size_t nmsg, size_t msg_bytes,
+                      const uint8_t *nonces, size_t nonce_len, const void *aData, size_t aad_bytes,
+                      const void *in, void *outp, uint8_t *tags, uint8_t *verdicts)
+{
+    context *c;
+    lane *L;
+    keysched k1, k2;
+    const void *d_nonces = NULL, *d_aad = NULL, *d_tags_in = NULL;
+    void *d_in = NULL, *d_out = NULL, *d_tags = NULL, *d_verdicts = NULL;
+    size_t off = 0;
+    int rc, bad = 0;
+    if ((msg_bytes && nmsg > (size_t)-1 / msg_bytes) || (nonce_len && nmsg > (size_t)-1 / nonce_len) ||
+        (aad_bytes && nmsg > (size_t)-1 / aad_bytes) || nmsg > (size_t)-1 / 16)
+        return fail(UAES_E_ARG, "batch size overflows");
+    if ((rc = siv ? siv_keys(&k1, &k2, key, keybits) : expand_key(&k1, key, keybits)) != 0) return rc;
+    if (nmsg == 0) { burn(&k1, sizeof k1); burn(&k2, sizeof k2); return 0; }
+    {
+        const size_t total = nmsg * msg_bytes;
+        if ((total && (!in || !outp)) || !tags || (decrypt && !verdicts) || (!siv && nonce_len && !nonces) ||
+            (aad_bytes && !aData)) {
+            burn(&k1, sizeof k1); burn(&k2, sizeof k2);
+            return fail(UAES_E_ARG, "NULL pointer");
+        }
+        if ((rc = enter(&c, &L)) != 0) { burn(&k1, sizeof k1); burn(&k2, sizeof k2); return rc; }
+        if ((rc = lane_scratch(L, SIDE(nmsg * nonce_len) + SIDE(nmsg * aad_bytes) + SIDE(nmsg * 16) + SIDE(nmsg),
+                               SCRATCH_OTHER)) != 0) goto out;
+        if (!siv && (rc = side_in(L, &off, nonces, nmsg * nonce_len, &d_nonces)) != 0) goto out;
+        if ((rc = side_in(L, &off, aData, nmsg * aad_bytes, &d_aad)) != 0) goto out;
+        if (decrypt) {
+            if ((rc = side_in(L, &off, tags, nmsg * 16, &d_tags_in)) != 0) goto out;
+            d_tags = (void *)d_tags_in;
+            if ((rc = side_out(L, &off, verdicts, nmsg, &d_verdicts)) != 0) goto out;
+        } else if ((rc = side_out(L, &off, tags, nmsg * 16, &d_tags)) != 0) goto out;
+        if ((rc = stage_text(L, 0, in, total, 1, &d_in)) != 0) goto out;
+        if ((rc = stage_text(L, 1, outp, total, decrypt && !siv, &d_out)) != 0) goto out;
+        if (decrypt) HIPCHK_GOTO(hipMemsetAsync(L->d_status, 0, sizeof(int), (hipStream_t)L->stream));
+        if (siv)
+            ES_KCHK("siv batch", uaesk_s2v_batch(L->stream, &c->tb, k1.nr, &k1.ek, &k2.ek, decrypt, wipe_on_auth_failure(),
+                                                 d_aad, aad_bytes, nmsg, msg_bytes, d_in, d_out, d_tags, d_verdicts,
+                                                 L->d_status));
+        else
+            ES_KCHK("eax batch", uaesk_eax_batch(L->stream, &c->tb, k1.nr, &k1.ek, decrypt, d_nonces, nonce_len, d_aad,
+                                                 aad_bytes, nmsg, msg_bytes, d_in, d_out, d_tags, d_verdicts, L->d_status));
+        if ((rc = copy_out(L, outp, d_out, total)) != 0) goto out;
+        if ((rc = decrypt ? copy_out(L, verdicts, d_verdicts, nmsg) : copy_out(L, tags, d_tags, nmsg * 16)) != 0) goto out;
+        if (decrypt) HIPCHK_GOTO(hipMemcpyAsync(&bad, L->d_status, sizeof bad, hipMemcpyDeviceToHost, (hipStream_t)L->stream));
+        HIPCHK_GOTO(hipStreamSynchronize((hipStream_t)L->stream));
+        rc = bad ? UAES_E_AUTHENTICATION : 0;
+    }
+out:
+    burn(&k1, sizeof k1);
+    burn(&k2, sizeof k2);
+    DONE(L, rc);
+}
+
+int uaes_eax_encrypt_batch(int keybits, const uint8_t *key, size_t nmsg, size_t msg_bytes,
+                           const uint8_t *nonces, size_t nonce_len, const void *aData, size_t aad_bytes,
+                           const void *pntxt, void *crtxt, uint8_t *tags)
+{
+    return aead_batch(0, 0, keybits, key, nmsg, msg_bytes, nonces, nonce_len, aData, aad_bytes, pntxt, crtxt, tags, NULL);
+}
+
+int uaes_eax_decrypt_batch(int keybits, const uint8_t *key, size_t nmsg, size_t msg_bytes,
+                           const uint8_t *nonces, size_t nonce_len, const void *aData, size_t aad_bytes,
+                           const void *crtxt, const uint8_t *tags, void *pntxt, uint8_t *verdicts)
+{
+    return aead_batch(0, 1, keybits, key, nmsg, msg_bytes, nonces, nonce_len, aData, aad_bytes, crtxt, pntxt,
+                      (uint8_t *)tags, verdicts);
+}
+
+int uaes_siv_encrypt_batch(int keybits, const uint8_t *keys, size_t nmsg, size_t msg_bytes,
+                           const void *aData, size_t aad_bytes, const void *pntxt, uint8_t *ivs, void *crtxt)
+{
+    return aead_batch(1, 0, keybits, keys, nmsg, msg_bytes, NULL, 0, aData, aad_bytes, pntxt, crtxt, ivs, NULL);
+}
+
+int uaes_siv_decrypt_batch(int keybits, const uint8_t *keys, size_t nmsg, size_t msg_bytes,
+                           const void *aData, size_t aad_bytes, const uint8_t *ivs, const void *crtxt, void *pntxt,
+                           uint8_t *verdicts)
+{
+    return aead_batch(1, 1, keybits, keys, nmsg, msg_bytes, NULL, 0, aData, aad_bytes, crtxt, pntxt, (uint8_t *)ivs,
+                      verdicts);
+}
+
+/* ------------------------------------------------------------------------ */
 /* CBC / CFB / OFB                                   */
 /* ------------------------------------------------------------------------ */
 /* mode: 0 CBC enc, 1 CBC dec, 2 CFB enc, 3 CFB dec, 4 OFB; the CBC of a reference build with CTS 0 (micro_aes.h:56):
@@ -3858,6 +4180,14 @@ const char *uaes_debug_plan_poly1305(size_t len, size_t nmsg, int out[3])
     (void)uaesk_plan_poly1305(len, nmsg, &p);
     if (out) { out[0] = p.launches; out[1] = (int)p.grid; out[2] = (int)p.steps; }
     return uaesk_poly1305_arrangement_name(p.arrangement);
+}
+const char *uaes_debug_plan_eax_siv(int siv, int dir, size_t len, size_t nmsg, int out[3])
+{
+    uaes_plan p;
+    memset(&p, 0, sizeof p);
+    if (uaesk_plan_eax_siv(siv, dir, len, nmsg, &p)) return NULL;
+    if (out) { out[0] = p.launches; out[1] = (int)p.grid; out[2] = (int)UAES_EAX_SIV_SMALL_MAX; }
+    return uaesk_eax_siv_arrangement_name(p.arrangement);
 }
 void uaes_debug_plan_disable(unsigned mask) { uaesk_plan_disable(mask); }
 

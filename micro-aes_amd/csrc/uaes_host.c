@@ -554,6 +554,138 @@ int uaesh_ccm(const uaesh_key *k, int decrypt, const uint8_t *nonce, size_t nonc
     return differ(tag, given, tag_len) ? 0x1A : 0;
 }
 
+/* ---- EAX (AES_EAX_encrypt / _decrypt micro_aes.c:1560-1648, oMac :1531-1548) and SIV, RFC 5297 (S2V :1323-1361,
+ *      AES_SIV_encrypt / _decrypt :1373-1411) ------------------------------------------------------------------------ */
+typedef struct { uint8_t k1[16], k2[16]; } cmac_keys;
+
+static void cmac_keys_of(const uaesh_key *k, cmac_keys *s)
+{
+    memset(s->k1, 0, 16);
+    uaesh_encrypt(k->ek, k->nr, s->k1, s->k1);
+    cmac_double(s->k1);
+    memcpy(s->k2, s->k1, 16);
+    cmac_double(s->k2);
+}
+
+/* the CMAC chain m continued over len >= 1 bytes: whole blocks, then the last one with K1, or 10* padding and K2 */
+static void cmac_continue(const uaesh_key *k, const cmac_keys *s, uint8_t m[16], const uint8_t *x, size_t len)
+{
+    const size_t last = (len - 1) % 16 + 1;
+    size_t i;
+    cbcmac_absorb(k, m, x, len - last);
+    x += len - last;
+    for (i = 0; i < 16; ++i) m[i] ^= (i < last ? x[i] : i == last ? 0x80 : 0) ^ (last < 16 ? s->k2[i] : s->k1[i]);
+    uaesh_encrypt(k->ek, k->nr, m, m);
+}
+
+/* OMAC^t(x) = CMAC([t]_16 || x) */
+static void eax_omac(const uaesh_key *k, const cmac_keys *s, unsigned t, const uint8_t *x, size_t len, uint8_t out[16])
+{
+    memset(out, 0, 16);
+    out[15] = (uint8_t)t;
+    if (!len) {
+        xor16(out, out, s->k1);
+        uaesh_encrypt(k->ek, k->nr, out, out);
+        return;
+    }
+    uaesh_encrypt(k->ek, k->nr, out, out);
+    cmac_continue(k, s, out, x, len);
+}
+
+/* decrypt: in = ct || tag; the tag is checked first and `out` stays untouched on 0x1A */
+int uaesh_eax(const uaesh_key *k, int decrypt, const uint8_t *nonce, size_t nonce_len, size_t tag_len,
+              const uint8_t *aad, size_t aad_len, const uint8_t *in, size_t len, uint8_t *out)
+{
+    cmac_keys s;
+    uint8_t n[16], h[16], c[16], tag[16];
+    int rc = 0;
+    cmac_keys_of(k, &s);
+    eax_omac(k, &s, 0, nonce, nonce_len, n);
+    eax_omac(k, &s, 1, aad, aad_len, h);
+    if (decrypt) {
+        eax_omac(k, &s, 2, in, len, c);
+        xor16(tag, n, h);
+        xor16(tag, tag, c);
+        if (differ(tag, in + len, tag_len)) rc = 0x1A;
+        else uaesh_ctr(k, n, 0, in, len, out);
+    } else {
+        uaesh_ctr(k, n, 0, in, len, out);
+        eax_omac(k, &s, 2, out, len, c);
+        xor16(tag, n, h);
+        xor16(tag, tag, c);
+        memcpy(out + len, tag, tag_len);
+    }
+    memset(&s, 0, sizeof s);
+    return rc;
+}
+
+/* V = S2V(aad, p): an empty AAD is no header unit at all; Y is XORed into the last 16 bytes of a text of 16 bytes or
+ * more, a shorter one gets dbl(Y) ^ pad(p) */
+static void s2v(const uaesh_key *k, const uint8_t *aad, size_t aad_len, const uint8_t *p, size_t len, uint8_t v[16])
+{
+    cmac_keys s;
+    uint8_t y[16] = { 0 }, d[16], t[16];
+    size_t i;
+    cmac_keys_of(k, &s);
+    xor16(y, y, s.k1);
+    uaesh_encrypt(k->ek, k->nr, y, y);                                  /* CMAC(0^128) */
+    if (aad_len) {
+        memset(d, 0, 16);
+        cmac_continue(k, &s, d, aad, aad_len);
+        cmac_double(y);
+        xor16(y, y, d);
+    }
+    memset(v, 0, 16);
+    if (len < 16) {
+        cmac_double(y);
+        for (i = 0; i < 16; ++i) t[i] = y[i] ^ (i < len ? p[i] : i == len ? 0x80 : 0) ^ s.k1[i];
+        uaesh_encrypt(k->ek, k->nr, t, v);
+    } else {
+        const size_t last = (len - 1) % 16 + 1, head = len - 16;       /* Y covers bytes head .. len-1 */
+        cbcmac_absorb(k, v, p, len - last - (last < 16 ? 16 : 0));
+        for (i = len - last - (last < 16 ? 16 : 0); i < len; i += 16) {
+            const size_t n = len - i < 16 ? len - i : 16;
+            size_t j;
+            for (j = 0; j < 16; ++j) {
+                const size_t at = i + j;
+                uint8_t b = j < n ? p[at] : j == n ? 0x80 : 0;
+                if (j < n && at >= head) b ^= y[at - head];
+                if (i + 16 >= len) b ^= n < 16 ? s.k2[j] : s.k1[j];
+                v[j] ^= b;
+            }
+            uaesh_encrypt(k->ek, k->nr, v, v);
+        }
+    }
+    memset(&s, 0, sizeof s);
+    memset(y, 0, 16);
+}
+
+static void s2v_ctr(const uaesh_key *k, const uint8_t v[16], const uint8_t *in, size_t len, uint8_t *out)
+{
+    uint8_t c[16];
+    memcpy(c, v, 16);
+    c[8] &= 0x7F;
+    c[12] &= 0x7F;
+    uaesh_ctr(k, c, 0, in, len, out);
+}
+
+/* k = K_s2v, kc = K_ctr; decrypt: CTR first, then S2V over the plaintext, 0x1A on a mismatch (the text stays) */
+int uaesh_siv(const uaesh_key *k, const uaesh_key *kc, int decrypt, uint8_t iv[16], const uint8_t *aad, size_t aad_len,
+              const uint8_t *in, size_t len, uint8_t *out)
+{
+    uint8_t v[16];
+    if (!decrypt) {
+        s2v(k, aad, aad_len, in, len, v);
+        s2v_ctr(kc, v, in, len, out);
+        memcpy(iv, v, 16);
+        return 0;
+    }
+    memcpy(v, iv, 16);
+    s2v_ctr(kc, v, in, len, out);
+    s2v(k, aad, aad_len, out, len, v);
+    return differ(v, iv, 16) ? 0x1A : 0;
+}
+
 /* ---- GCM-SIV (RFC 8452; GCM_SIVsetup micro_aes.c:1434-1449, polyval :1421-1432, GCM_SIVtag :1452-1459,
  *      GCM_SIV_encrypt :1473-1485, _decrypt :1494-1515; CTR flavour SIVGCM_CTR :935-938) --------------------------------
  * POLYVAL runs through the GHASH tables above: POLYVAL(H, X_1..X_n) = ByteReverse(GHASH(mulX(ByteReverse(H)),

@@ -34,8 +34,16 @@
  *   POLY  poly.small            k_poly_small (one workgroup, AES_k(nonce) inside)   (1)    one message <= UAES_POLY_SMALL_MAX (128 KiB)
  *         poly.chunks           k_poly_chunks, k_poly_fold (+ AES_k(nonce))         (2)    one message beyond
  *         poly.batch            k_poly_batch (one wave per message)                 (1)    uaes_poly1305_batch
+ *   EAX   eax.small             k_eax_small (N || H, CTR, C; decrypt: N || H || C, CTR)  (1)  text <= UAES_EAX_SIV_SMALL_MAX
+ *         eax.long              k_eax_macs, CTR (k_ctr*) [, k_eax_macs C]           (3)    beyond (the counter block and the
+ *                                                                                          verdict come back to the host)
+ *         eax.batch             k_eax_batch (sixteen lanes per record)              (1)    uaes_eax_*_batch
+ *   S2V   s2v.small             k_s2v_small (Y || lead blocks, then CTR)            (1)    text <= UAES_EAX_SIV_SMALL_MAX
+ *         s2v.long              k_s2v_macs and CTR (k_ctr*), in either order        (2)    beyond
+ *         s2v.batch             k_s2v_batch (sixteen lanes per record)              (1)    uaes_siv_*_batch
  * The Poly1305 rows have a planner of their own (uaesk_plan_poly1305, uaes_poly1305.hip) and ids outside enum
  * uaes_arrangement (uaes_debug_plan_poly1305 names them); a larger message never goes back to a smaller row.
+ * So do the EAX and SIV (RFC 5297) rows (uaesk_plan_eax_siv, uaes_eax_siv.hip; uaes_debug_plan_eax_siv).
  */
 #ifndef UAES_PLAN_H
 #define UAES_PLAN_H
@@ -107,6 +115,15 @@ const char *uaesk_arrangement_name(int id);
 enum uaes_poly_arrangement { UAES_POLY_SMALL = 0, UAES_POLY_CHUNKS = 1, UAES_POLY_BATCH = 2 };
 int uaesk_plan_poly1305(size_t len, size_t nmsg, uaes_plan *p);
 const char *uaesk_poly1305_arrangement_name(int id);
+
+/* EAX and SIV (RFC 5297): a text of at most UAES_EAX_SIV_SMALL_MAX bytes is one launch of one workgroup; a longer one
+ * runs its independent CMAC chains in one launch, fetches the counter block and the verdict in one round trip and
+ * then runs the positioned CTR kernels.  siv: 0 = EAX, 1 = SIV; dir: 0 encrypt, 1 decrypt; nmsg >= 2 = a batch.
+ * launches = kernels the call enqueues; grid = workgroups of the main kernel. */
+#define UAES_EAX_SIV_SMALL_MAX ((size_t)16384)
+enum uaes_eax_siv_arrangement { UAES_EAX_SMALL = 0, UAES_EAX_LONG, UAES_EAX_BATCH, UAES_S2V_SMALL, UAES_S2V_LONG, UAES_S2V_BATCH };
+int uaesk_plan_eax_siv(int siv, int dir, size_t len, size_t nmsg, uaes_plan *p);
+const char *uaesk_eax_siv_arrangement_name(int id);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Bulk rate of EVERY mode through the synchronous C ABI with device pointers (GiB/s, one call = the whole text):
 a sweep for holes -- shapes that run far below the rate their arithmetic allows.  The serial chains (CBC/CFB encrypt,
-OFB, CMAC, CCM's MAC) are latency-bound by construction and get a short text.  [MiB] default 256."""
+OFB, CMAC, CCM's MAC, EAX, SIV) are latency-bound by construction and get a short text.  [MiB] default 256."""
 import ctypes as C
 import os
 import sys
@@ -67,5 +67,19 @@ for bits, key in ((128, key16), (256, key32)):
         nb = max(1, n // 65536)                              # (messages of 64 KiB: as many as the buffers hold)
         rate("cbc enc batch %d x 64 KiB" % nb, lambda: L.uaes_cbc_encrypt_batch(bits, key, ad, nb, 65536, a, b), nb * 65536)
         rate("cmac batch %d x 64 KiB" % nb, lambda: L.uaes_cmac_batch(bits, key, nb, 65536, a, b), nb * 65536)
+        # EAX / SIV (RFC 5297): the chains of a call run at the same time, so a call costs about one CMAC chain
+        kk, ivb = key + key, (C.c_uint8 * 16)()
+        dn = C.c_void_p(aad_t.data_ptr() + (16 << 20))      # nonces / tags / IVs of the batches: the AAD buffer's upper half
+        dt = C.c_void_p(aad_t.data_ptr() + (24 << 20))
+        rate("eax enc (1 MiB: chains)", lambda: L.uaes_eax_encrypt(bits, key, iv16, 16, 16, None, 0, a, small, b), small, reps=2)
+        rate("eax dec (1 MiB: chains)", lambda: L.uaes_eax_decrypt(bits, key, iv16, 16, 16, None, 0, b, small, ad), small,
+             prep=lambda: L.uaes_eax_encrypt(bits, key, iv16, 16, 16, None, 0, a, small, b), reps=2)
+        rate("siv enc (1 MiB: chains)", lambda: L.uaes_siv_encrypt(bits, kk, None, 0, a, small, ivb, b), small, reps=2)
+        rate("siv dec (1 MiB: chains)", lambda: L.uaes_siv_decrypt(bits, kk, ivb, None, 0, b, small, ad), small,
+             prep=lambda: L.uaes_siv_encrypt(bits, kk, None, 0, a, small, ivb, b), reps=2)
+        rate("eax enc batch %d x 64 KiB" % nb, lambda: L.uaes_eax_encrypt_batch(bits, key, nb, 65536, dn, 16, None, 0, a, b, dt),
+             nb * 65536)
+        rate("siv enc batch %d x 64 KiB" % nb, lambda: L.uaes_siv_encrypt_batch(bits, kk, nb, 65536, None, 0, a, dt, b),
+             nb * 65536)
     pkeys = key + bytes(range(100, 116))                     # Poly1305-AES: k || r
     rate("poly1305", lambda: L.uaes_poly1305(bits, pkeys, iv16, a, n, mac), n)

@@ -53,3 +53,7 @@ walk("GCM-SIV", lambda n: uaes.plan("siv", n), 0, 2048 * MIB)
 walk("Poly1305-AES, one message", lambda n: uaes.poly1305_plan(n)[:3] + (0,), 0, 2048 * MIB)
 walk("Poly1305-AES, batches of k messages of 1 KiB", lambda k: uaes.poly1305_plan(1024, max(k, 2))[:3] + (0,), 2, 1 << 20, 1,
      lambda k: "%9d msgs (%9.3f MiB)" % (k, k * 1024 / MIB))
+print("EAX / SIV (RFC 5297): one launch up to UAES_EAX_SIV_SMALL_MAX = %d bytes of text" % uaes.eax_siv_plan(False, 0)[3])
+walk("EAX encrypt", lambda n: uaes.eax_siv_plan(False, n)[:2] + (0, 0), 0, 64 * MIB)
+walk("EAX decrypt", lambda n: uaes.eax_siv_plan(False, n, decrypt=True)[:2] + (0, 0), 0, 64 * MIB)
+walk("SIV (RFC 5297)", lambda n: uaes.eax_siv_plan(True, n)[:2] + (0, 0), 0, 64 * MIB)
