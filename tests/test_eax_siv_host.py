@@ -14,19 +14,7 @@ from tests import eax_siv_ref as R
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def eax_vectors(golden_dir):
-    cases, cur = [], {}
-    with open(os.path.join(golden_dir, "EAX_AES128.tv")) as f:
-        for line in f:
-            line = line.strip()
-            if not line or line.startswith("#"):
-                continue
-            name, _, value = line.partition(":")
-            cur[name.strip()] = bytes.fromhex(value.strip())
-            if name.strip() == "CIPHER":
-                cases.append(cur)
-                cur = {}
-    return cases
+eax_vectors = R.eax_vectors
 
 
 @pytest.fixture
@@ -85,6 +73,74 @@ def flip(b, i):
     b = bytearray(b)
     b[i % len(b)] ^= 1 << (i % 8)
     return bytes(b)
+
+
+def test_reference_builds_with_other_eax_lengths():
+    """the three EAX_NONCE_LEN / EAX_TAG_LEN builds agree with the composition from the reference's CMAC and block
+    cipher (which stands in for them at every other length), and their decryption accepts their own output"""
+    rng = random.Random(21)
+    for (bits, nl, tl) in R.EAX_LENS:
+        for n in (0, 1, 16, 17, 300, 20000):
+            key, nonce, aad, pt = rng.randbytes(bits // 8), rng.randbytes(nl), rng.randbytes(n % 41), rng.randbytes(n)
+            ct = R.eax_encrypt_lens(bits, nl, tl, key, nonce, aad, pt)
+            assert len(ct) == n + tl and ct == R.eax_composed(key, nonce, aad, pt, tl, bits), (bits, nl, tl, n)
+            assert R.eax_decrypt_lens(bits, nl, tl, key, nonce, aad, ct) == (0, pt), (bits, nl, tl, n)
+            assert R.eax_decrypt_lens(bits, nl, tl, key, nonce, aad, flip(ct, 8 * n + 3), 0x5C) == (0x1A, b"\x5c" * n)
+    key, nonce, aad, pt = rng.randbytes(16), rng.randbytes(16), rng.randbytes(9), rng.randbytes(100)
+    for bits in (128, 192, 256):                               # the composition at 16 / 16 against the default builds
+        key = rng.randbytes(bits // 8)
+        assert R.eax_composed(key, nonce, aad, pt, 16, bits) == R.eax_encrypt(bits, key, nonce, aad, pt)
+
+
+@pytest.mark.parametrize("bits", [128, 192, 256])
+def test_eax_length_matrix(host_forced, bits):
+    """every nonce length x tag length of the matrix x texts on both sides of the small / long boundary: the pair
+    this key size has a reference build for against that build, the rest against the composition; a truncated tag is
+    accepted, a flip of each of its bytes rejected with the output untouched"""
+    rng = random.Random(1000 + bits)
+    small = uaes.eax_siv_plan(False, 0)[3]
+    for nl in R.NONCE_LENS:
+        for tl in R.TAG_LENS:
+            key, nonce = rng.randbytes(bits // 8), rng.randbytes(nl)
+            for n in (0, 1, 16, 17, 300 + nl % 16, small, small + 1):
+                aad, pt = rng.randbytes((n + tl) % 50), rng.randbytes(n)
+                info = (bits, nl, tl, n)
+                want = R.eax_expected(bits, key, nonce, aad, pt, tl)
+                assert uaes.AES_EAX_encrypt(key, nonce, aad, pt, tag_len=tl) == want, info
+                assert uaes.AES_EAX_decrypt(key, nonce, aad, want, tag_len=tl) == (0, pt), info
+                for i in range(tl if n in (0, 17, small + 1) else 0):
+                    bad = bytearray(want)
+                    bad[n + i] ^= 1 << rng.randrange(8)
+                    assert uaes.AES_EAX_decrypt(key, nonce, aad, bytes(bad), prefill=0x5C, tag_len=tl) == \
+                        (0x1A, b"\x5c" * n), info + (i,)
+    done = [k for k in R.EAX_LENS if k[0] == bits]
+    assert len(done) == 1 and done[0][1] in R.NONCE_LENS and done[0][2] in R.TAG_LENS     # the build's pair was in the loop
+
+
+@pytest.mark.parametrize("bits", [128, 192, 256])
+def test_long_associated_data(host_forced, bits):
+    rng = random.Random(2000 + bits)
+    small = uaes.eax_siv_plan(False, 0)[3]
+    (nl, tl), = [k[1:] for k in R.EAX_LENS if k[0] == bits]
+    key, keys = rng.randbytes(bits // 8), rng.randbytes(bits // 4)
+    for alen in R.AAD_LENS:
+        aad = rng.randbytes(alen)
+        for n in (0, 5, small, small + 1, alen):
+            pt = rng.randbytes(n)
+            for nlen, tlen in ((nl, tl), (16, 16)):
+                nonce = rng.randbytes(nlen)
+                want = R.eax_encrypt_lens(bits, nlen, tlen, key, nonce, aad, pt)
+                assert uaes.AES_EAX_encrypt(key, nonce, aad, pt, tag_len=tlen) == want, (bits, alen, n, nlen)
+                assert uaes.AES_EAX_decrypt(key, nonce, aad, want, tag_len=tlen) == (0, pt), (bits, alen, n, nlen)
+                other = flip(aad, 8 * alen - 1)
+                rc = R.eax_verdict(bits, key, nonce, other, want, tlen)            # (a one-byte tag can match by chance)
+                assert rc == 0x1A or tlen < 3
+                assert uaes.AES_EAX_decrypt(key, nonce, other, want, prefill=0x5C, tag_len=tlen) == \
+                    (rc, b"\x5c" * n if rc else pt), (bits, alen, n, nlen)
+            iv, sct = uaes.AES_SIV_encrypt(keys, aad, pt)
+            assert (iv, sct) == R.siv_encrypt(bits, keys, aad, pt), (bits, alen, n)
+            assert uaes.AES_SIV_decrypt(keys, iv, aad, sct) == (0, pt), (bits, alen, n)
+            assert uaes.AES_SIV_decrypt(keys, iv, flip(aad, 8 * alen - 1), sct)[0] == 0x1A, (bits, alen, n)
 
 
 def test_forgeries(host_forced):

@@ -1,7 +1,8 @@
 """Seeded differential fuzzing of the C ABI against the CPU oracle: random key sizes,
 sizes drawn around the kernels' internal boundaries (16 B blocks, 256-block chunks, 16-chunk
 runs, 256 KiB CTR chunks and whole rounds of them, GHASH level plans), host or device
-pointers, aligned or not, in place or not.  Every case is reproducible from its printed tuple."""
+pointers, aligned or not, in place or not; EAX and SIV (RFC 5297) against the compiled reference.  Every case is
+reproducible from its printed tuple."""
 import ctypes as C
 import os
 import random
@@ -9,6 +10,7 @@ import random
 import pytest
 
 import micro_aes_amd as uaes
+from tests import eax_siv_ref as R
 
 pytestmark = pytest.mark.gpu
 
@@ -198,6 +200,99 @@ def test_fuzz_aead(orc):
             assert all(x == b.guard for x in b.result()[0]), info
 
     run_cases(303, 160, body)
+
+
+def side_array(rnd, data):
+    """a side array (AAD, nonce, IV) as the call gets it: the bytes themselves (host memory), or -- four times in ten
+    -- device memory at an offset that is odd more often than not; returns (argument, tensor or None)"""
+    if not data or rnd.random() >= 0.4:
+        return bytes(data), None
+    import torch
+    off = rnd.choice([0, 1, 3, 7])
+    t = torch.full((len(data) + 32,), 0xA5, dtype=torch.uint8, device="cuda:0")
+    t[off:off + len(data)] = torch.frombuffer(bytearray(data), dtype=torch.uint8).to("cuda:0")
+    return C.c_void_p(t.data_ptr() + off), t
+
+
+def test_fuzz_eax_siv():
+    """EAX and SIV (RFC 5297) against the compiled reference (tests/eax_siv_ref.py): random key size, text size, nonce
+    and tag length; text, AAD, nonce and IV independently in host or device memory at odd offsets, in place or not.
+    Encrypt equals the reference, decrypt returns the text, a forgery is rejected (EAX: the guard pattern stays; SIV:
+    what the reference leaves), and the 16 bytes behind the output -- behind a truncated tag in particular -- stay."""
+    import torch
+    L = uaes.engine()
+
+    def body(rnd, i):
+        bits = rnd.choice([128, 192, 256])
+        n = pick_size(rnd, 1 << 20)
+        data = rnd.randbytes(n)
+        aad = rnd.randbytes(rnd.choice([0, 0, 1, 15, 16, 17, 100, 255, 256, 257, 4099, 70000]))
+        aad_arg, _ta = side_array(rnd, aad)
+        if rnd.random() < 0.55:
+            key = rnd.randbytes(bits // 8)
+            nl, tl = rnd.choice([0, 1, 7, 12, 15, 16, 16, 17, 32, 37, 100, 1000]), rnd.randrange(1, 17)
+            if rnd.random() < 0.25:                          # the lengths this key size has a reference build for
+                (nl, tl), = [k[1:] for k in R.EAX_LENS if k[0] == bits]
+            nonce = rnd.randbytes(nl)
+            nonce_arg, _tn = side_array(rnd, nonce)
+            want = R.eax_expected(bits, key, nonce, aad, data, tl)
+            b = Buffers(rnd, data, n + tl)
+            info = ("eax", i, bits, n, nl, tl, len(aad), not isinstance(aad_arg, bytes), not isinstance(nonce_arg, bytes), b.describe())
+            assert L.uaes_eax_encrypt(bits, key, nonce_arg, nl, tl, aad_arg, len(aad), b.pin, n, b.pout) == 0, info
+            got, guard_ok = b.result()
+            assert got == want and guard_ok, info
+            b = Buffers(rnd, want, n)                        # (behind a truncated tag: the guard value, not the tag's bytes)
+            info = info[:-1] + (b.describe(),)
+            assert L.uaes_eax_decrypt(bits, key, nonce_arg, nl, tl, aad_arg, len(aad), b.pin, n, b.pout) == 0, info
+            got, guard_ok = b.result()
+            assert got == data and guard_ok, info
+            bad = bytearray(want)
+            where = rnd.choice([rnd.randrange(len(bad)), n + rnd.randrange(tl)])
+            bad[where] ^= 1 << rnd.randrange(8)
+            b = Buffers(rnd, bytes(bad), n)
+            info = info[:-1] + (b.describe(), where)
+            verdict = R.eax_verdict(bits, key, nonce, aad, bytes(bad), tl)    # (a changed text under a short tag can pass)
+            assert verdict == 0x1A or (where < n and tl < 3), info
+            assert L.uaes_eax_decrypt(bits, key, nonce_arg, nl, tl, aad_arg, len(aad), b.pin, n, b.pout) == verdict, info
+            got, guard_ok = b.result()
+            if verdict:
+                assert guard_ok and (b.alias or all(x == b.guard for x in got)), info
+                if b.alias:
+                    assert got == bytes(bad)[:n], info       # in place: the ciphertext stays
+        else:
+            keys = rnd.randbytes(bits // 4)
+            want_iv, want = R.siv_encrypt(bits, keys, aad, data)
+            iv_dev = rnd.random() < 0.4
+            iv_off = rnd.choice([0, 1, 5])
+            tiv = torch.full((48,), 0xA5, dtype=torch.uint8, device="cuda:0") if iv_dev else None
+            hiv = (C.c_uint8 * 48)(*([0xA5] * 48))
+            iv_arg = C.c_void_p((tiv.data_ptr() if iv_dev else C.addressof(hiv)) + iv_off)
+            b = Buffers(rnd, data, n)
+            info = ("siv", i, bits, n, len(aad), not isinstance(aad_arg, bytes), iv_dev, iv_off, b.describe())
+            assert L.uaes_siv_encrypt(bits, keys, aad_arg, len(aad), b.pin, n, iv_arg, b.pout) == 0, info
+            got, guard_ok = b.result()
+            raw_iv = bytes(tiv.cpu().numpy()) if iv_dev else bytes(hiv)
+            assert got == want and guard_ok and raw_iv[iv_off:iv_off + 16] == want_iv, info
+            assert set(raw_iv[:iv_off] + raw_iv[iv_off + 16:]) == {0xA5}, info
+            b = Buffers(rnd, want, n)
+            info = info[:-1] + (b.describe(),)
+            assert L.uaes_siv_decrypt(bits, keys, iv_arg, aad_arg, len(aad), b.pin, n, b.pout) == 0, info
+            got, guard_ok = b.result()
+            assert got == data and guard_ok, info
+            bad_iv, bad = bytearray(want_iv), bytearray(want)
+            where = rnd.randrange(16 + n)
+            if where < 16:
+                bad_iv[where] ^= 1 << rnd.randrange(8)
+            else:
+                bad[where - 16] ^= 1 << rnd.randrange(8)
+            biv_arg, _tv = side_array(rnd, bytes(bad_iv))
+            b = Buffers(rnd, bytes(bad), n)
+            info = info[:-1] + (b.describe(), where)
+            assert L.uaes_siv_decrypt(bits, keys, biv_arg, aad_arg, len(aad), b.pin, n, b.pout) == 0x1A, info
+            got, guard_ok = b.result()
+            assert got == R.siv_decrypt_rc(bits, keys, bytes(bad_iv), aad, bytes(bad))[1] and guard_ok, info
+
+    run_cases(1111, 100, body)
 
 
 def test_fuzz_feedback_and_macs(orc):
@@ -651,6 +746,23 @@ def test_fuzz_kernels_against_the_host_path(orc):
             assert g == h and g[1] == orc.cbc(key, iv, data[:20000 + n % 16], True)[1], ("cbc",) + info
             g, h = both(lambda: uaes.AES_CBC_decrypt(key, iv, g[1]))
             assert g == h == (0, data[:20000 + n % 16])
+        # EAX and SIV (RFC 5297): the serial chains cap the text; nonce and tag lengths of the reference's other builds too
+        nl, tl = rnd.choice([(16, 16), (16, 16), (0, 1), (12, 8), (37, 13), (5, 15), (1000, 2)])
+        en, text = rnd.randbytes(nl), data[:60000]
+        g, h = both(lambda: uaes.AES_EAX_encrypt(key, en, aad, text, tag_len=tl))
+        assert g == h == R.eax_expected(bits, key, en, aad, text, tl), ("eax", nl, tl) + info
+        g2, h2 = both(lambda: uaes.AES_EAX_decrypt(key, en, aad, g, tag_len=tl))
+        assert g2 == h2 == (0, text), ("eax", nl, tl) + info
+        g2, h2 = both(lambda: uaes.AES_EAX_decrypt(key, en, aad, g[:-1] + bytes([g[-1] ^ 4]), prefill=0x3C, tag_len=tl))
+        assert g2 == h2 == (0x1A, b"\x3c" * len(text)), ("eax", nl, tl) + info
+        keys2 = rnd.randbytes(bits // 4)
+        g, h = both(lambda: uaes.AES_SIV_encrypt(keys2, aad, text))
+        assert g == h == R.siv_encrypt(bits, keys2, aad, text), ("siv",) + info
+        g2, h2 = both(lambda: uaes.AES_SIV_decrypt(keys2, g[0], aad, g[1]))
+        assert g2 == h2 == (0, text), ("siv",) + info
+        fiv = bytes([g[0][0] ^ 1]) + g[0][1:]
+        g2, h2 = both(lambda: uaes.AES_SIV_decrypt(keys2, fiv, aad, g[1]))
+        assert g2 == h2 == R.siv_decrypt_rc(bits, keys2, fiv, aad, g[1]), ("siv",) + info
 
     run_cases(909, 40, body)
     # device pointers stay on the GPU even with the host path switched on: a host routine would fault on them

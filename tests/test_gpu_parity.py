@@ -581,6 +581,14 @@ def test_gcm_lane_key_cache(orc):
         bad[-1] ^= 2
         assert uaes.AES_GCM_decrypt(key, nonce, aad, bytes(bad), tag_len=tag_len)[0] == 0x1A
 
+    def eax_siv(aad, n):
+        from tests import eax_siv_ref as R
+        nonce, pt = rnd.randbytes(16), orc.splitmix(n + 1, n)
+        want = R.eax_encrypt(256, kb, nonce, aad, pt)
+        assert uaes.AES_EAX_encrypt(kb, nonce, aad, pt) == want and uaes.AES_EAX_decrypt(kb, nonce, aad, want) == (0, pt)
+        want = R.siv_encrypt(128, kb, aad, pt)
+        assert uaes.AES_SIV_encrypt(kb, aad, pt) == want and uaes.AES_SIV_decrypt(kb, want[0], aad, want[1]) == (0, pt)
+
     for i in range(14):                                       # 28 calls in a row under ka: the tables come at the eighth
         check(ka, sizes[i % len(sizes)])
     disturbances = [
@@ -591,6 +599,9 @@ def test_gcm_lane_key_cache(orc):
         lambda: check(kb, 100, nonce_len=8),                  # ... whose J0 is a GHASH on the lane's scratch
         lambda: check(kb, 4096, tag_len=12),                  # ... the truncated-tag order (tag first, then CTR)
         lambda: uaes.GCM_SIV_encrypt(ka, bytes(12), b"", orc.splitmix(4, 30000)),
+        lambda: eax_siv(b"aad", 300),                         # EAX and SIV (RFC 5297): a host nonce and AAD travel in the scratch
+        lambda: eax_siv(orc.splitmix(5, 70000), 20000),       # ... an AAD longer than the key's tables, eax.long / s2v.long
+        lambda: eax_siv(orc.splitmix(6, (1 << 20) + 7), 5),   # ... and one that makes the scratch grow
     ]
     for d in disturbances:
         d()
