@@ -1,5 +1,5 @@
 /*
- * uaes_device.h -- interface between the C host layer (uaes_engine.c) and the
+ * uaes_device.h -- interface between the C host layer (uaes_engine*.c) and the
  * HIP kernels (uaes_kernels.hip).  Plain C types only; every entry point is a
  * thin launcher that enqueues gfx950 kernels on the given stream and returns
  * the hipError_t value (0 = success).  Nothing here touches host data.

@@ -1,0 +1,1042 @@
+/*
+ * uaes_engine_modes.c -- entry points of the modes other than GCM: ECB, CTR, XTS, CMAC, Poly1305, CCM, EAX, SIV,
+ * CBC / CFB / OFB, the chain batches and OCB.  They mirror the reference's mode drivers (AES_ECB_*, AES_CTR_*,
+ * AES_XTS_* ...; micro_aes.c:636-680, :962-990, :1066-1093): argument checking, the reference's error behaviour
+ * and buffer plumbing on top of the core (uaes_engine.c, through uaes_engine.h).
+ */
+#include "uaes_engine.h"
+
+/* ------------------------------------------------------------------------ */
+/* ECB                                                                        */
+/* ------------------------------------------------------------------------ */
+typedef struct { context *c; keysched *ks; int decrypt, padding; size_t total; } ecb_pipe_arg;
+
+static int ecb_pipe_launch(void *arg, int worker, void *stream, const void *d_in, void *d_out, size_t off, size_t len)
+{
+    ecb_pipe_arg *a = (ecb_pipe_arg *)arg;
+    (void)worker;
+    const int last = off + len == a->total;
+    return uaesk_ecb(stream, &a->c->tb, a->ks->nr, a->decrypt ? &a->ks->dk : &a->ks->ek, a->decrypt, d_in, d_out,
+                     len / 16, (a->decrypt || !last) ? 0 : (unsigned)(len % 16), (last && !a->decrypt) ? (unsigned)a->padding : 0);
+}
+
+static int ecb_common(int keybits, const uint8_t *key, int decrypt, int padding,
+                      const void *in, size_t len, void *out)
+{
+    context *c;
+    lane *L;
+    keysched ks;
+    io_plan io;
+    int rc;
+    const size_t rem = len % 16, nfull = len / 16;
+    const size_t out_len = decrypt ? len : (padding ? (len / 16 + 1) * 16 : (len + 15) / 16 * 16);
+    if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
+    if (padding < 0 || padding > 2) return fail(UAES_E_ARG, "padding must be 0 (zeros), 1 (PKCS#7) or 2 (ISO/IEC 7816-4)");
+    if (out_len == 0) return 0;
+    if ((len && !in) || !out) return fail(UAES_E_ARG, "NULL data pointer");
+    if (host_take(in, out, len, 0)) {
+        const uaesh_key hk = host_key(&ks);
+        if (!decrypt) { uaesh_ecb_encrypt(&hk, padding, (const uint8_t *)in, len, (uint8_t *)out); HOST_RET(ks, 0); }
+        uaesh_ecb_decrypt(&hk, (const uint8_t *)in, len, (uint8_t *)out);
+        HOST_RET(ks, rem ? UAES_E_DECRYPTION : 0);
+    }
+    {
+        int devs[MAX_DEVICES];
+        const int nd = auto_devices(in, out, len, devs);
+        if (nd) return decrypt ? uaes_mgpu_ecb_decrypt(nd, devs, keybits, key, in, len, out)
+                               : uaes_mgpu_ecb_encrypt(nd, devs, keybits, key, padding, in, len, out);
+    }
+    if ((rc = enter(&c, &L)) != 0) return rc;
+    do {
+        ecb_pipe_arg pa;
+        pa.c = c; pa.ks = &ks; pa.decrypt = decrypt; pa.padding = padding; pa.total = len;
+        if (!(decrypt && rem) && run_pipelined(c, in, out, len, 16, out_len - len, ecb_pipe_launch, &pa, &rc)) return rc;
+        if ((rc = plan_io(L, in, len, out, out_len, &io)) != 0) break;
+        if (decrypt && rem && io.dout != io.din) {
+            /* ragged decrypt: the reference copies the tail through (:664) */
+            if (hipMemcpyAsync((char *)io.dout + nfull * 16, (const char *)io.din + nfull * 16, rem,
+                               hipMemcpyDeviceToDevice, (hipStream_t)L->stream) != hipSuccess) {
+                rc = fail(UAES_E_HIP, "tail copy failed");
+                break;
+            }
+        }
+        ticket_arm(L, len);
+        int k = uaesk_ecb(L->stream, &c->tb, ks.nr, decrypt ? &ks.dk : &ks.ek, decrypt,
+                          io.din, io.dout, nfull, decrypt ? 0 : (unsigned)rem, decrypt ? 0 : (unsigned)padding);
+        ticket_armed_launch_done(L);
+        if (k) { rc = fail(UAES_E_HIP, "ecb launch: %s", hipGetErrorString((hipError_t)k)); break; }
+        if ((rc = finish_io(&io, out_len)) != 0) break;
+        rc = (decrypt && rem) ? UAES_E_DECRYPTION : 0;           /* :679 */
+    } while (0);
+    DONE(L, rc);
+}
+
+int uaes_ecb_encrypt(int keybits, const uint8_t *key, const void *pntxt, size_t ptextLen, void *crtxt)
+{
+    return ecb_common(keybits, key, 0, 0, pntxt, ptextLen, crtxt);
+}
+
+int uaes_ecb_encrypt_padded(int keybits, const uint8_t *key, int padding,
+                            const void *pntxt, size_t ptextLen, void *crtxt)
+{
+    return ecb_common(keybits, key, 0, padding, pntxt, ptextLen, crtxt);
+}
+
+int uaes_ecb_decrypt(int keybits, const uint8_t *key, const void *crtxt, size_t crtxtLen, void *pntxt)
+{
+    return ecb_common(keybits, key, 1, 0, crtxt, crtxtLen, pntxt);
+}
+
+int uaes_ecb_dev(int keybits, const uint8_t *key, int decrypt,
+                 const void *d_in, size_t len, void *d_out, void *stream)
+{
+    context *c;
+    keysched ks;
+    int rc;
+    if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
+    if ((rc = dev_ptrs_ok(d_in, d_out, len)) != 0) return rc;
+    if ((rc = get_context(&c)) != 0) return rc;
+    if (decrypt && len % 16) return fail(UAES_E_ARG, "uaes_ecb_dev: ragged decrypt length");
+    KCHK(uaesk_ecb(stream, &c->tb, ks.nr, decrypt ? &ks.dk : &ks.ek, decrypt, d_in, d_out,
+                   len / 16, (unsigned)(len % 16), 0));
+    return 0;
+}
+
+/* ------------------------------------------------------------------------ */
+/* CTR                                                                        */
+/* ------------------------------------------------------------------------ */
+int uaes_ctr_xcrypt_at_dev(int keybits, const uint8_t *key, const uint8_t ctr0[16],
+                           uint64_t block_offset,
+                           const void *d_in, size_t len, void *d_out, void *stream)
+{
+    context *c;
+    keysched ks;
+    uaesk_ctr ctr;
+    int rc;
+    if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
+    if ((rc = dev_ptrs_ok(d_in, d_out, len)) != 0) return rc;
+    if (!ctr0) return fail(UAES_E_ARG, "NULL counter block");
+    if ((rc = get_context(&c)) != 0) return rc;
+    make_ctr(&ctr, ctr0, block_offset);
+    KCHK(uaesk_ctr_xcrypt(stream, &c->tb, ks.nr, &ks.ek, &ctr, d_in, d_out, len, NULL));
+    return 0;
+}
+
+typedef struct { context *c; keysched *ks; uaesk_ctr *ctr; } ctr_pipe_arg;
+
+static int ctr_pipe_launch(void *arg, int worker, void *stream, const void *d_in, void *d_out, size_t off, size_t len)
+{
+    ctr_pipe_arg *a = (ctr_pipe_arg *)arg;
+    (void)worker;
+    uaesk_ctr sl = *a->ctr;
+    sl.v0 = (a->ctr->v0 + off / 16) & 0x00FFFFFFFFFFFFFFull;     /* the slice's counter: the 56-bit add of incBlock */
+    return uaesk_ctr_xcrypt(stream, &a->c->tb, a->ks->nr, &a->ks->ek, &sl, d_in, d_out, len, NULL);
+}
+
+int uaes_ctr_xcrypt_at(int keybits, const uint8_t *key, const uint8_t ctr0[16],
+                       uint64_t block_offset, const void *in, size_t len, void *out)
+{
+    context *c;
+    lane *L;
+    keysched ks;
+    uaesk_ctr ctr;
+    io_plan io;
+    int rc;
+    if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
+    if (!ctr0) return fail(UAES_E_ARG, "NULL counter block");
+    if (len == 0) return 0;
+    if (!in || !out) return fail(UAES_E_ARG, "NULL data pointer");
+    if (host_take(in, out, len, 0)) {
+        const uaesh_key hk = host_key(&ks);
+        uaesh_ctr(&hk, ctr0, block_offset, (const uint8_t *)in, len, (uint8_t *)out);
+        HOST_RET(ks, 0);
+    }
+    {
+        int devs[MAX_DEVICES];
+        const int nd = auto_devices(in, out, len, devs);
+        if (nd) return uaes_mgpu_ctr_xcrypt_at(nd, devs, keybits, key, ctr0, block_offset, in, len, out);
+    }
+    if ((rc = enter(&c, &L)) != 0) return rc;
+    make_ctr(&ctr, ctr0, block_offset);
+    do {
+        ctr_pipe_arg pa;
+        pa.c = c; pa.ks = &ks; pa.ctr = &ctr;
+        if (run_pipelined(c, in, out, len, 16, 0, ctr_pipe_launch, &pa, &rc)) return rc;
+        if ((rc = plan_io(L, in, len, out, len, &io)) != 0) break;
+        ticket_arm(L, len);
+        int k = uaesk_ctr_xcrypt(L->stream, &c->tb, ks.nr, &ks.ek, &ctr, io.din, io.dout, len, NULL);
+        ticket_armed_launch_done(L);
+        if (k) { rc = fail(UAES_E_HIP, "ctr launch: %s", hipGetErrorString((hipError_t)k)); break; }
+        rc = finish_io(&io, len);
+    } while (0);
+    DONE(L, rc);
+}
+
+/* ivLen / startValue = the reference's compile-time CTR_IV_LENGTH / CTR_START_VALUE (micro_aes.h:98-99): the counter
+ * block is the IV's first ivLen bytes with zeros behind them, and the start value XORed in as a big-endian integer
+ * that ends at byte 15 (micro_aes.c:968-971, xorBEint :410-415)                                                   */
+int uaes_ctr_xcrypt_iv(int keybits, const uint8_t *key, const uint8_t *iv, size_t ivLen, uint64_t startValue,
+                       const void *in, size_t len, void *out)
+{
+    uint8_t ctr0[16] = { 0 };
+    int pos = 15;
+    if (!iv && ivLen) return fail(UAES_E_ARG, "NULL iv");
+    if (ivLen > 16) return fail(UAES_E_ARG, "CTR IV length %zu (at most 16)", ivLen);
+    if (ivLen) memcpy(ctr0, iv, ivLen);
+    do ctr0[pos--] ^= (uint8_t)startValue; while ((startValue >>= 8) != 0);
+    return uaes_ctr_xcrypt_at(keybits, key, ctr0, 0, in, len, out);
+}
+
+int uaes_ctr_xcrypt(int keybits, const uint8_t *key, const uint8_t *iv,
+                    const void *in, size_t len, void *out)
+{
+    if (!iv) return fail(UAES_E_ARG, "NULL iv");
+    return uaes_ctr_xcrypt_iv(keybits, key, iv, 12, 1, in, len, out);      /* CTR_IV_LENGTH 12, CTR_START_VALUE 1 */
+}
+
+/* ------------------------------------------------------------------------ */
+/* XTS                                                                        */
+/* ------------------------------------------------------------------------ */
+static int xts_keys(keysched *k1, keysched *k2, const uint8_t *keys, int keybits)
+{
+    int rc;
+    if (!keys) return fail(UAES_E_ARG, "NULL key pair");
+    if ((rc = expand_key(k1, keys, keybits)) != 0) return rc;
+    return expand_key(k2, keys + keybits / 8, keybits);          /* :1026-1029 */
+}
+
+/* scratch == NULL: the *_dev path -- take (and pin) the slot of the caller's stream */
+static int xts_run(context *c, void *stream, keysched *k1, keysched *k2, int encrypt,
+                   const uint8_t *tweak16, uint64_t first_sector,
+                   size_t sector_bytes, size_t nsectors, const void *din, void *dout, void *scratch)
+{
+    int slot = -1, k;
+    if (!scratch) {
+        pthread_mutex_lock(&c->mu);
+        const int g = scratch_pin(c, stream, uaesk_xts_scratch_bytes(sector_bytes, nsectors), &scratch, &slot);
+        pthread_mutex_unlock(&c->mu);
+        if (g) return UAES_E_HIP;
+    }
+    k = uaesk_xts(stream, &c->tb, k1->nr, encrypt ? &k1->ek : &k1->dk, &k2->ek, !encrypt,
+                  tweak16, first_sector, sector_bytes, nsectors, din, dout, scratch);
+    if (slot >= 0) scratch_unpin(c, slot);
+    if (k) return fail(UAES_E_HIP, "xts launch: %s", hipGetErrorString((hipError_t)k));
+    return 0;
+}
+
+typedef struct { context *c; keysched *k1, *k2; int encrypt; uint64_t first_sector; size_t sector_bytes; } xts_pipe_arg;
+
+/* a pipeline worker keeps its own chunk-tweak scratch next to its device slice: it never takes one of
+ * the per-stream slots of the *_dev API (which it used to occupy for the life of the process)       */
+static int xts_pipe_launch(void *arg, int worker, void *stream, const void *d_in, void *d_out, size_t off, size_t len)
+{
+    xts_pipe_arg *a = (xts_pipe_arg *)arg;
+    context *c = a->c;
+    const size_t ns = len / a->sector_bytes;
+    if (grow_on(stream, &c->pipe[worker].xscratch, &c->pipe[worker].xscratch_cap,
+                uaesk_xts_scratch_bytes(a->sector_bytes, ns)))
+        return -1;
+    return xts_run(c, stream, a->k1, a->k2, a->encrypt, NULL, a->first_sector + off / a->sector_bytes,
+                   a->sector_bytes, ns, d_in, d_out, c->pipe[worker].xscratch) ? -1 : 0;
+}
+
+static int xts_common(int keybits, const uint8_t *keys, const uint8_t *tweak, int raw_tweak,
+                      uint64_t first_sector, size_t sector_bytes, size_t nsectors,
+                      const void *in, void *out, int encrypt)
+{
+    context *c;
+    lane *L;
+    keysched k1, k2;
+    io_plan io;
+    uint8_t zero[16] = { 0 };
+    int rc;
+    const size_t total = sector_bytes * nsectors;
+    if ((rc = xts_keys(&k1, &k2, keys, keybits)) != 0) return rc;
+    if (sector_bytes < 16) return UAES_E_DATALENGTH;             /* :1069, untouched */
+    if (nsectors == 0) return 0;
+    if (!in || !out) return fail(UAES_E_ARG, "NULL data pointer");
+    if (host_take(in, out, total, 0)) {
+        const uaesh_key h1 = host_key(&k1), h2 = host_key(&k2);
+        if (raw_tweak) uaesh_xts_unit(&h1, &h2, encrypt, tweak ? tweak : zero, (const uint8_t *)in, sector_bytes, (uint8_t *)out);
+        else uaesh_xts_sectors(&h1, &h2, encrypt, first_sector, sector_bytes, nsectors, (const uint8_t *)in, (uint8_t *)out);
+        do { burn(&k2, sizeof k2); HOST_RET(k1, 0); } while (0);
+    }
+    if (!raw_tweak && nsectors > 1) {
+        int devs[MAX_DEVICES];
+        const int nd = auto_devices(in, out, total, devs);
+        if (nd) return uaes_mgpu_xts_sectors(nd, devs, keybits, keys, first_sector, sector_bytes, nsectors, in, out, encrypt);
+    }
+    if ((rc = enter(&c, &L)) != 0) return rc;
+    do {
+        xts_pipe_arg pa;
+        pa.c = c; pa.k1 = &k1; pa.k2 = &k2; pa.encrypt = encrypt; pa.first_sector = first_sector; pa.sector_bytes = sector_bytes;
+        if (!raw_tweak && nsectors > 1 && run_pipelined(c, in, out, total, sector_bytes, 0, xts_pipe_launch, &pa, &rc)) return rc;
+        if ((rc = lane_scratch(L, uaesk_xts_scratch_bytes(sector_bytes, nsectors), SCRATCH_OTHER)) != 0) break;
+        if ((rc = plan_io(L, in, total, out, total, &io)) != 0) break;
+        ticket_arm(L, total);
+        rc = xts_run(c, L->stream, &k1, &k2, encrypt, raw_tweak ? (tweak ? tweak : zero) : NULL,
+                     first_sector, sector_bytes, nsectors, io.din, io.dout, L->scratch);
+        ticket_armed_launch_done(L);
+        if (rc) break;
+        rc = finish_io(&io, total);
+    } while (0);
+    DONE(L, rc);
+}
+
+int uaes_xts_encrypt(int keybits, const uint8_t *keys, const uint8_t *tweak,
+                     const void *pntxt, size_t ptextLen, void *crtxt)
+{
+    return xts_common(keybits, keys, tweak, 1, 0, ptextLen, 1, pntxt, crtxt, 1);
+}
+
+int uaes_xts_decrypt(int keybits, const uint8_t *keys, const uint8_t *tweak,
+                     const void *crtxt, size_t crtxtLen, void *pntxt)
+{
+    return xts_common(keybits, keys, tweak, 1, 0, crtxtLen, 1, crtxt, pntxt, 0);
+}
+
+int uaes_xts_sectors(int keybits, const uint8_t *keys, uint64_t first_sector,
+                     size_t sector_bytes, size_t nsectors, const void *in, void *out, int encrypt)
+{
+    return xts_common(keybits, keys, NULL, 0, first_sector, sector_bytes, nsectors, in, out, encrypt);
+}
+
+int uaes_xts_sectors_dev(int keybits, const uint8_t *keys, uint64_t first_sector,
+                         size_t sector_bytes, size_t nsectors,
+                         const void *d_in, void *d_out, int encrypt, void *stream)
+{
+    context *c;
+    keysched k1, k2;
+    int rc;
+    if ((rc = xts_keys(&k1, &k2, keys, keybits)) != 0) return rc;
+    if ((rc = dev_ptrs_ok(d_in, d_out, sector_bytes * nsectors)) != 0) return rc;
+    if (sector_bytes < 16) return UAES_E_DATALENGTH;
+    if ((rc = get_context(&c)) != 0) return rc;
+    return xts_run(c, stream, &k1, &k2, encrypt, NULL, first_sector, sector_bytes, nsectors, d_in, d_out, NULL);
+}
+
+/* ------------------------------------------------------------------------ */
+/* CMAC and CCM: serial CBC-MAC chains, one GPU lane */
+/* ------------------------------------------------------------------------ */
+int uaes_cmac(int keybits, const uint8_t *key, const void *data, size_t dataSize, uint8_t mac[16])
+{
+    context *c;
+    lane *L;
+    keysched ks;
+    io_plan io;
+    int rc;
+    if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
+    if (!mac || (dataSize && !data)) return fail(UAES_E_ARG, "NULL pointer");
+    if (host_take(data, NULL, dataSize, 1)) {
+        const uaesh_key hk = host_key(&ks);
+        uaesh_cmac(&hk, (const uint8_t *)data, dataSize, mac);
+        HOST_RET(ks, 0);
+    }
+    if ((rc = enter(&c, &L)) != 0) return rc;
+    do {
+        if ((rc = plan_io(L, data, dataSize, NULL, 0, &io)) != 0) break;
+        int k = uaesk_cmac(L->stream, &c->tb, ks.nr, &ks.ek, io.din, dataSize, L->d_status + 4);
+        if (k) { rc = fail(UAES_E_HIP, "cmac launch: %s", hipGetErrorString((hipError_t)k)); break; }
+        rc = lane_fetch(L, mac, L->d_status + 4, 16);
+    } while (0);
+    DONE(L, rc);
+}
+
+/* ------------------------------------------------------------------------ */
+/* Poly1305-AES (micro_aes.c:1901-1997): keys = k (keybits / 8 bytes) || r (16) */
+/* ------------------------------------------------------------------------ */
+/* AES_k(nonce), the powers of r and the tag run in kernels (uaes_poly1305.hip); the host expands k, and the clamped r
+ * travels as a launch argument.  Every way out wipes the schedule; the chunk partials are zeroed by the fold kernel. */
+int uaes_poly1305(int keybits, const uint8_t *keys, const uint8_t nonce[16],
+                  const void *data, size_t dataSize, uint8_t mac[16])
+{
+    context *c;
+    lane *L;
+    keysched ks;
+    io_plan io;
+    int rc;
+    if (!keys || !nonce || !mac || (dataSize && !data)) return fail(UAES_E_ARG, "NULL pointer");
+    if ((rc = expand_key(&ks, keys, keybits)) != 0) return rc;
+    const uint8_t *r = keys + keybits / 8;
+    if (host_take(data, NULL, dataSize, 0)) {
+        const uaesh_key hk = host_key(&ks);
+        uaesh_poly1305(&hk, r, nonce, (const uint8_t *)data, dataSize, mac);
+        HOST_RET(ks, 0);
+    }
+    if ((rc = enter(&c, &L)) != 0) { burn(&ks, sizeof ks); return rc; }
+    do {
+        const size_t need = uaesk_poly1305_scratch_bytes(dataSize);
+        if ((rc = plan_io(L, data, dataSize, NULL, 0, &io)) != 0) break;
+        if (need && (rc = lane_scratch(L, need, SCRATCH_OTHER)) != 0) break;
+        int k = uaesk_poly1305(L->stream, &c->tb, ks.nr, &ks.ek, r, nonce, io.din, dataSize, L->d_status + 4,
+                               need ? L->scratch : NULL);
+        if (k) { rc = fail(UAES_E_HIP, "poly1305 launch: %s", hipGetErrorString((hipError_t)k)); break; }
+        rc = lane_fetch(L, mac, L->d_status + 4, 16);
+    } while (0);
+    burn(&ks, sizeof ks);
+    DONE(L, rc);
+}
+
+int uaes_poly1305_dev(int keybits, const uint8_t *keys, const uint8_t nonce[16],
+                      const void *d_data, size_t len, void *d_mac, void *stream)
+{
+    context *c;
+    keysched ks;
+    void *scr = NULL;
+    int rc, slot = -1;
+    if (!keys || !nonce || !d_mac || (len && !d_data)) return fail(UAES_E_ARG, "NULL pointer");
+    if ((rc = expand_key(&ks, keys, keybits)) != 0) return rc;
+    const size_t need = uaesk_poly1305_scratch_bytes(len);
+    if ((rc = get_context(&c)) != 0) { burn(&ks, sizeof ks); return rc; }
+    if (need) {
+        pthread_mutex_lock(&c->mu);
+        rc = scratch_pin(c, stream, need, &scr, &slot);
+        pthread_mutex_unlock(&c->mu);
+        if (rc) { burn(&ks, sizeof ks); return fail(UAES_E_HIP, "poly1305 scratch"); }
+    }
+    rc = uaesk_poly1305(stream, &c->tb, ks.nr, &ks.ek, keys + keybits / 8, nonce, d_data, len, d_mac, scr);
+    burn(&ks, sizeof ks);
+    KCHK_PINNED(c, slot, rc);
+    return 0;
+}
+
+int uaes_poly1305_batch(int keybits, const uint8_t *keys, const uint8_t *nonces, size_t nmsg,
+                        size_t msg_bytes, const void *data, uint8_t *macs)
+{
+    context *c;
+    lane *L;
+    keysched ks;
+    io_plan io;
+    const void *d_nonces = NULL;
+    int rc;
+    if (msg_bytes && nmsg > (size_t)-1 / msg_bytes) return fail(UAES_E_ARG, "batch size overflows");
+    if (!keys || (nmsg && (!nonces || !macs)) || (nmsg && msg_bytes && !data)) return fail(UAES_E_ARG, "NULL pointer");
+    if ((rc = expand_key(&ks, keys, keybits)) != 0) return rc;
+    if (nmsg == 0) { burn(&ks, sizeof ks); return 0; }
+    if ((rc = enter(&c, &L)) != 0) { burn(&ks, sizeof ks); return rc; }
+    do {
+        if ((rc = stage_aad(L, nonces, nmsg * 16, &d_nonces)) != 0) break;       /* host nonces -> device */
+        if ((rc = plan_io(L, data, nmsg * msg_bytes, macs, nmsg * 16, &io)) != 0) break;
+        if (io.dout == io.din && io.copy_back) {                  /* MACs must not overwrite unread messages */
+            if (grow_on(L->stream, &L->stage[1], &L->stage_cap[1], nmsg * 16 + 64)) { rc = UAES_E_HIP; break; }
+            io.dout = L->stage[1];
+        }
+        int k = uaesk_poly1305_batch(L->stream, &c->tb, ks.nr, &ks.ek, keys + keybits / 8, d_nonces, nmsg, msg_bytes,
+                                     io.din, io.dout);
+        if (k) { rc = fail(UAES_E_HIP, "poly1305 batch launch: %s", hipGetErrorString((hipError_t)k)); break; }
+        rc = finish_io(&io, nmsg * 16);
+    } while (0);
+    burn(&ks, sizeof ks);
+    DONE(L, rc);
+}
+
+static int ccm_lens_ok(size_t nonceLen, size_t tagLen)
+{
+    if (nonceLen < 7 || nonceLen > 13) return fail(UAES_E_ARG, "CCM nonce length %zu (7..13)", nonceLen);
+    if (tagLen < 4 || tagLen > 16 || (tagLen & 1)) return fail(UAES_E_ARG, "CCM tag length %zu (even, 4..16)", tagLen);
+    return 0;
+}
+
+/* nonceLen / tagLen = the reference's compile-time CCM_NONCE_LEN / CCM_TAG_LEN (micro_aes.h:103-104) */
+int uaes_ccm_encrypt_ex(int keybits, const uint8_t *key, const uint8_t *nonce, size_t nonceLen, size_t tagLen,
+                        const void *aData, size_t aDataLen,
+                        const void *pntxt, size_t ptextLen, void *crtxt)
+{
+    context *c;
+    lane *L;
+    keysched ks;
+    io_plan io;
+    const void *d_aad;
+    int rc;
+    if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
+    if (!nonce || !crtxt || (ptextLen && !pntxt)) return fail(UAES_E_ARG, "NULL pointer");
+    if ((rc = ccm_lens_ok(nonceLen, tagLen)) != 0) return rc;
+    if (aDataLen && !aData) return fail(UAES_E_ARG, "NULL aData with aDataLen != 0");
+    if (host_take(pntxt, crtxt, ptextLen, 1) && !is_device_ptr(aData)) {
+        const uaesh_key hk = host_key(&ks);
+        HOST_RET(ks, uaesh_ccm(&hk, 0, nonce, nonceLen, tagLen, (const uint8_t *)aData, aDataLen, (const uint8_t *)pntxt, ptextLen, (uint8_t *)crtxt));
+    }
+    if ((rc = enter(&c, &L)) != 0) return rc;
+    do {
+        if ((rc = stage_aad(L, aData, aDataLen, &d_aad)) != 0) break;
+        if ((rc = plan_io(L, pntxt, ptextLen, crtxt, ptextLen + tagLen, &io)) != 0) break;
+        int k = uaesk_ccm(L->stream, &c->tb, ks.nr, &ks.ek, 0, nonce, nonceLen, tagLen, d_aad, aDataLen,
+                          io.din, ptextLen, io.dout, NULL);
+        if (k) { rc = fail(UAES_E_HIP, "ccm launch: %s", hipGetErrorString((hipError_t)k)); break; }
+        rc = finish_io(&io, ptextLen + tagLen);
+    } while (0);
+    DONE(L, rc);
+}
+
+int uaes_ccm_encrypt(int keybits, const uint8_t *key, const uint8_t *nonce,
+                     const void *aData, size_t aDataLen,
+                     const void *pntxt, size_t ptextLen, void *crtxt)
+{
+    return uaes_ccm_encrypt_ex(keybits, key, nonce, 11, 16, aData, aDataLen, pntxt, ptextLen, crtxt);
+}
+
+int uaes_ccm_decrypt_ex(int keybits, const uint8_t *key, const uint8_t *nonce, size_t nonceLen, size_t tagLen,
+                        const void *aData, size_t aDataLen,
+                        const void *crtxt, size_t crtxtLen, void *pntxt)
+{
+    context *c;
+    lane *L;
+    keysched ks;
+    io_plan io;
+    const void *d_aad;
+    int rc, status = -1;
+    if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
+    if (!nonce || !crtxt || (crtxtLen && !pntxt)) return fail(UAES_E_ARG, "NULL pointer");
+    if ((rc = ccm_lens_ok(nonceLen, tagLen)) != 0) return rc;
+    if (aDataLen && !aData) return fail(UAES_E_ARG, "NULL aData with aDataLen != 0");
+    if (host_take(crtxt, pntxt, crtxtLen, 1) && !is_device_ptr(aData)) {
+        const uaesh_key hk = host_key(&ks);
+        rc = uaesh_ccm(&hk, 1, nonce, nonceLen, tagLen, (const uint8_t *)aData, aDataLen, (const uint8_t *)crtxt, crtxtLen, (uint8_t *)pntxt);
+        if (rc && wipe_on_auth_failure()) memset(pntxt, 0, crtxtLen);       /* (the default leaves the text, as the reference does) */
+        HOST_RET(ks, rc);
+    }
+    if ((rc = enter(&c, &L)) != 0) return rc;
+    do {
+        if ((rc = stage_aad(L, aData, aDataLen, &d_aad)) != 0) break;
+        if ((rc = plan_io(L, crtxt, crtxtLen + tagLen, pntxt, crtxtLen, &io)) != 0) break;
+        int k = uaesk_ccm(L->stream, &c->tb, ks.nr, &ks.ek, 1, nonce, nonceLen, tagLen, d_aad, aDataLen,
+                          io.din, crtxtLen, io.dout, L->d_status);
+        if (k) { rc = fail(UAES_E_HIP, "ccm launch: %s", hipGetErrorString((hipError_t)k)); break; }
+        if ((rc = lane_fetch(L, &status, L->d_status, sizeof status)) != 0) break;
+        io.drained = 1;                              /* (a second wait costs another ticket kernel) */
+        /* the reference decrypts before it authenticates and (SABOTAGE being a
+         * no-op in its default build) leaves the text in place on a mismatch   */
+        if ((rc = status ? finish_io_unauthenticated(&io, crtxtLen) : finish_io(&io, crtxtLen)) != 0) break;
+        rc = status ? UAES_E_AUTHENTICATION : 0;
+    } while (0);
+    DONE(L, rc);
+}
+
+int uaes_ccm_decrypt(int keybits, const uint8_t *key, const uint8_t *nonce,
+                     const void *aData, size_t aDataLen,
+                     const void *crtxt, size_t crtxtLen, void *pntxt)
+{
+    return uaes_ccm_decrypt_ex(keybits, key, nonce, 11, 16, aData, aDataLen, crtxt, crtxtLen, pntxt);
+}
+
+/* ------------------------------------------------------------------------ */
+/* EAX and SIV, RFC 5297 (AES_EAX_* micro_aes.c:1560-1648, AES_SIV_* :1373-1411) */
+/* ------------------------------------------------------------------------ */
+/* Kernels in uaes_eax_siv.hip.  A text of at most UAES_EAX_SIV_SMALL_MAX bytes is one launch; a longer one runs its
+ * independent chains in one launch, reads the counter block (and the verdict) back in one fetch and hands it to the
+ * positioned CTR kernels.  Side arrays (nonce, AAD) in host memory travel through the lane's scratch.             */
+
+#define HIPCHK_GOTO(call)                                                                            \
+    do {                                                                                              \
+        const hipError_t e_ = (call);                                                                 \
+        if (e_ != hipSuccess) { rc = fail(UAES_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); goto out; } \
+    } while (0)
+#define ES_KCHK(what, call)                                                                           \
+    do {                                                                                              \
+        const int k_ = (call);                                                                        \
+        if (k_) { rc = fail(UAES_E_HIP, what " launch: %s", hipGetErrorString((hipError_t)k_)); goto out; } \
+    } while (0)
+
+static int eax_common(int keybits, const uint8_t *key, int decrypt, const uint8_t *nonce, size_t nonceLen, size_t tagLen,
+                      const void *aData, size_t aDataLen, const void *in, size_t len, void *outp)
+{
+    context *c;
+    lane *L;
+    keysched ks;
+    io_plan io;
+    const void *d_nonce, *d_aad;
+    size_t off = 0;
+    int rc, status = 0;
+    uint8_t res[32];
+    if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
+    if (!in || (len && !outp) || (nonceLen && !nonce)) return fail(UAES_E_ARG, "NULL pointer");
+    if (!decrypt && !outp) return fail(UAES_E_ARG, "NULL pointer");
+    if (tagLen < 1 || tagLen > 16) return fail(UAES_E_ARG, "EAX tag length %zu (1..16)", tagLen);
+    if (aDataLen && !aData) return fail(UAES_E_ARG, "NULL aData with aDataLen != 0");
+    if (host_take(in, outp, len, 1) && !is_device_ptr(aData) && !is_device_ptr(nonce)) {
+        const uaesh_key hk = host_key(&ks);
+        HOST_RET(ks, uaesh_eax(&hk, decrypt, nonce, nonceLen, tagLen, (const uint8_t *)aData, aDataLen,
+                               (const uint8_t *)in, len, (uint8_t *)outp));
+    }
+    if ((rc = enter(&c, &L)) != 0) { burn(&ks, sizeof ks); return rc; }
+    if ((rc = lane_scratch(L, SIDE(nonceLen) + SIDE(aDataLen), SCRATCH_OTHER)) != 0) goto out;
+    if ((rc = side_in(L, &off, nonce, nonceLen, &d_nonce)) != 0) goto out;
+    if ((rc = side_in(L, &off, aData, aDataLen, &d_aad)) != 0) goto out;
+    if (decrypt) rc = plan_io(L, in, len + tagLen, outp, len, &io);
+    else rc = plan_io(L, in, len, outp, len + tagLen, &io);
+    if (rc) goto out;
+    {
+        unsigned char *tag = decrypt ? (unsigned char *)io.din + len : (unsigned char *)io.dout + len;
+        const unsigned tl = (unsigned)tagLen;
+        if (len <= UAES_EAX_SIV_SMALL_MAX) {             /* eax.small: one launch */
+            ES_KCHK("eax", uaesk_eax_small(L->stream, &c->tb, ks.nr, &ks.ek, decrypt, d_nonce, nonceLen, d_aad, aDataLen,
+                                           io.din, len, io.dout, tag, tl, decrypt ? L->d_status : NULL));
+            if (decrypt) {
+                if ((rc = lane_fetch(L, &status, L->d_status, sizeof status)) != 0) goto out;
+                io.drained = 1;
+            }
+        } else {                                          /* eax.long: the chains, one fetch, then CTR */
+            uaesk_ctr ctr;
+            ES_KCHK("eax", uaesk_eax_macs(L->stream, &c->tb, ks.nr, &ks.ek, decrypt ? 1 : 0, d_nonce, nonceLen,
+                                          d_aad, aDataLen, decrypt ? io.din : NULL, decrypt ? len : 0, tag, tl, L->d_status));
+            if ((rc = lane_fetch(L, res, L->d_status, sizeof res)) != 0) goto out;
+            memcpy(&status, res, sizeof status);
+            if (decrypt && status) {
+                io.drained = 1;
+            } else {
+                make_ctr(&ctr, res + 16, 0);
+                ES_KCHK("eax ctr", uaesk_ctr_xcrypt(L->stream, &c->tb, ks.nr, &ks.ek, &ctr, io.din, io.dout, len, NULL));
+                if (!decrypt)
+                    ES_KCHK("eax", uaesk_eax_macs(L->stream, &c->tb, ks.nr, &ks.ek, 2, NULL, 0, NULL, 0, io.dout, len,
+                                                  tag, tl, L->d_status));
+            }
+        }
+    }
+    /* the tag is checked before anything is written (:1638-1645): a forgery leaves pntxt as it was */
+    if (decrypt && status) rc = UAES_E_AUTHENTICATION;
+    else rc = finish_io(&io, decrypt ? len : len + tagLen);
+out:
+    burn(&ks, sizeof ks);
+    memset(res, 0, sizeof res);
+    DONE(L, rc);
+}
+
+int uaes_eax_encrypt(int keybits, const uint8_t *key, const uint8_t *nonce, size_t nonceLen, size_t tagLen,
+                     const void *aData, size_t aDataLen, const void *pntxt, size_t ptextLen, void *crtxt)
+{
+    if (!pntxt && !ptextLen) pntxt = crtxt;                       /* (nothing is read) */
+    return eax_common(keybits, key, 0, nonce, nonceLen, tagLen, aData, aDataLen, pntxt, ptextLen, crtxt);
+}
+
+int uaes_eax_decrypt(int keybits, const uint8_t *key, const uint8_t *nonce, size_t nonceLen, size_t tagLen,
+                     const void *aData, size_t aDataLen, const void *crtxt, size_t crtxtLen, void *pntxt)
+{
+    return eax_common(keybits, key, 1, nonce, nonceLen, tagLen, aData, aDataLen, crtxt, crtxtLen, pntxt);
+}
+
+static int siv_keys(keysched *k1, keysched *k2, const uint8_t *keys, int keybits)
+{
+    int rc;
+    if (!keys) return fail(UAES_E_ARG, "NULL keys");
+    if ((rc = expand_key(k1, keys, keybits)) != 0) return rc;
+    return expand_key(k2, keys + keybits / 8, keybits);
+}
+
+static int siv_common(int keybits, const uint8_t *keys, int decrypt, uint8_t *iv, const void *aData, size_t aDataLen,
+                      const void *in, size_t len, void *outp)
+{
+    context *c;
+    lane *L;
+    keysched k1, k2;
+    io_plan io;
+    const void *d_aad;
+    size_t off = 0;
+    int rc, status = 0;
+    uint8_t v[16], res[32];
+    if ((rc = siv_keys(&k1, &k2, keys, keybits)) != 0) return rc;
+    if (!iv || (len && (!in || !outp))) return fail(UAES_E_ARG, "NULL pointer");
+    if (aDataLen && !aData) return fail(UAES_E_ARG, "NULL aData with aDataLen != 0");
+    if (decrypt && (rc = iv_read(v, iv)) != 0) return rc;
+    if (host_take(in, outp, len, 1) && !is_device_ptr(aData) && !is_device_ptr(iv)) {
+        const uaesh_key h1 = host_key(&k1), h2 = host_key(&k2);
+        rc = uaesh_siv(&h1, &h2, decrypt, v, (const uint8_t *)aData, aDataLen, (const uint8_t *)in, len, (uint8_t *)outp);
+        burn(&k1, sizeof k1);
+        burn(&k2, sizeof k2);
+        if (!decrypt) memcpy(iv, v, 16);
+        if (rc && len && wipe_on_auth_failure()) memset(outp, 0, len);       /* (the default leaves the text, as the reference does) */
+        return host_result(rc);
+    }
+    if ((rc = enter(&c, &L)) != 0) { burn(&k1, sizeof k1); burn(&k2, sizeof k2); return rc; }
+    if ((rc = lane_scratch(L, SIDE(aDataLen), SCRATCH_OTHER)) != 0) goto out;
+    if ((rc = side_in(L, &off, aData, aDataLen, &d_aad)) != 0) goto out;
+    if ((rc = plan_io(L, len ? in : NULL, len, len ? outp : NULL, len, &io)) != 0) goto out;
+    if (len <= UAES_EAX_SIV_SMALL_MAX) {                  /* s2v.small: one launch */
+        ES_KCHK("siv", uaesk_s2v_small(L->stream, &c->tb, k1.nr, &k1.ek, &k2.ek, decrypt, decrypt ? v : NULL, d_aad,
+                                       aDataLen, io.din, len, io.dout, (char *)L->d_status + 16,
+                                       decrypt ? L->d_status : NULL));
+        if ((rc = lane_fetch(L, res, L->d_status, sizeof res)) != 0) goto out;
+        io.drained = 1;
+    } else if (!decrypt) {                                /* s2v.long: the chains, one fetch, then CTR(V') */
+        uaesk_ctr ctr;
+        ES_KCHK("siv", uaesk_s2v_macs(L->stream, &c->tb, k1.nr, &k1.ek, 0, NULL, d_aad, aDataLen, io.din, len, L->d_status));
+        if ((rc = lane_fetch(L, res, L->d_status, sizeof res)) != 0) goto out;
+        memcpy(v, res + 16, 16);
+        v[8] &= 0x7F;
+        v[12] &= 0x7F;
+        make_ctr(&ctr, v, 0);
+        ES_KCHK("siv ctr", uaesk_ctr_xcrypt(L->stream, &c->tb, k2.nr, &k2.ek, &ctr, io.din, io.dout, len, NULL));
+    } else {                                              /* decrypt: CTR(iv') first, S2V over what it wrote, one fetch */
+        uaesk_ctr ctr;
+        uint8_t cv[16];
+        memcpy(cv, v, 16);
+        cv[8] &= 0x7F;
+        cv[12] &= 0x7F;
+        make_ctr(&ctr, cv, 0);
+        ES_KCHK("siv ctr", uaesk_ctr_xcrypt(L->stream, &c->tb, k2.nr, &k2.ek, &ctr, io.din, io.dout, len, NULL));
+        ES_KCHK("siv", uaesk_s2v_macs(L->stream, &c->tb, k1.nr, &k1.ek, 1, v, d_aad, aDataLen, io.dout, len, L->d_status));
+        if ((rc = lane_fetch(L, res, L->d_status, sizeof res)) != 0) goto out;
+        io.drained = 1;
+    }
+    if (decrypt) {
+        memcpy(&status, res, sizeof status);
+        /* like the reference: the text is written before it is authenticated; SABOTAGE = uaes_set_wipe_on_auth_failure */
+        if ((rc = status ? finish_io_unauthenticated(&io, len) : finish_io(&io, len)) == 0 && status) rc = UAES_E_AUTHENTICATION;
+    } else {
+        memcpy(v, res + 16, 16);
+        if ((rc = finish_io(&io, len)) == 0) rc = iv_write(iv, v);
+    }
+out:
+    burn(&k1, sizeof k1);
+    burn(&k2, sizeof k2);
+    DONE(L, rc);
+}
+
+int uaes_siv_encrypt(int keybits, const uint8_t *keys, const void *aData, size_t aDataLen,
+                     const void *pntxt, size_t ptextLen, uint8_t iv[16], void *crtxt)
+{
+    return siv_common(keybits, keys, 0, iv, aData, aDataLen, pntxt, ptextLen, crtxt);
+}
+
+int uaes_siv_decrypt(int keybits, const uint8_t *keys, const uint8_t iv[16], const void *aData, size_t aDataLen,
+                     const void *crtxt, size_t crtxtLen, void *pntxt)
+{
+    return siv_common(keybits, keys, 1, (uint8_t *)iv, aData, aDataLen, crtxt, crtxtLen, pntxt);
+}
+
+/* Batches: nmsg records of msg_bytes each under one key, sixteen lanes per record.  Every array may be host or
+ * device memory; host arrays travel through the lane's staging buffers and scratch.  An EAX decryption writes only
+ * authentic records: the output buffer starts as the caller's (host memory is copied in first).                   */
+static int aead_batch(int siv, int decrypt, int keybits, const uint8_t *key, size_t nmsg, size_t msg_bytes,
+                      const uint8_t *nonces, size_t nonce_len, const void *aData, size_t aad_bytes,
+                      const void *in, void *outp, uint8_t *tags, uint8_t *verdicts)
+{
+    context *c;
+    lane *L;
+    keysched k1, k2;
+    const void *d_nonces = NULL, *d_aad = NULL, *d_tags_in = NULL;
+    void *d_in = NULL, *d_out = NULL, *d_tags = NULL, *d_verdicts = NULL;
+    size_t off = 0;
+    int rc, bad = 0;
+    if ((msg_bytes && nmsg > (size_t)-1 / msg_bytes) || (nonce_len && nmsg > (size_t)-1 / nonce_len) ||
+        (aad_bytes && nmsg > (size_t)-1 / aad_bytes) || nmsg > (size_t)-1 / 16)
+        return fail(UAES_E_ARG, "batch size overflows");
+    if ((rc = siv ? siv_keys(&k1, &k2, key, keybits) : expand_key(&k1, key, keybits)) != 0) return rc;
+    if (nmsg == 0) { burn(&k1, sizeof k1); burn(&k2, sizeof k2); return 0; }
+    {
+        const size_t total = nmsg * msg_bytes;
+        if ((total && (!in || !outp)) || !tags || (decrypt && !verdicts) || (!siv && nonce_len && !nonces) ||
+            (aad_bytes && !aData)) {
+            burn(&k1, sizeof k1); burn(&k2, sizeof k2);
+            return fail(UAES_E_ARG, "NULL pointer");
+        }
+        if ((rc = enter(&c, &L)) != 0) { burn(&k1, sizeof k1); burn(&k2, sizeof k2); return rc; }
+        if ((rc = lane_scratch(L, SIDE(nmsg * nonce_len) + SIDE(nmsg * aad_bytes) + SIDE(nmsg * 16) + SIDE(nmsg),
+                               SCRATCH_OTHER)) != 0) goto out;
+        if (!siv && (rc = side_in(L, &off, nonces, nmsg * nonce_len, &d_nonces)) != 0) goto out;
+        if ((rc = side_in(L, &off, aData, nmsg * aad_bytes, &d_aad)) != 0) goto out;
+        if (decrypt) {
+            if ((rc = side_in(L, &off, tags, nmsg * 16, &d_tags_in)) != 0) goto out;
+            d_tags = (void *)d_tags_in;
+            if ((rc = side_out(L, &off, verdicts, nmsg, &d_verdicts)) != 0) goto out;
+        } else if ((rc = side_out(L, &off, tags, nmsg * 16, &d_tags)) != 0) goto out;
+        if ((rc = stage_text(L, 0, in, total, 1, &d_in)) != 0) goto out;
+        if ((rc = stage_text(L, 1, outp, total, decrypt && !siv, &d_out)) != 0) goto out;
+        if (decrypt) HIPCHK_GOTO(hipMemsetAsync(L->d_status, 0, sizeof(int), (hipStream_t)L->stream));
+        if (siv)
+            ES_KCHK("siv batch", uaesk_s2v_batch(L->stream, &c->tb, k1.nr, &k1.ek, &k2.ek, decrypt, wipe_on_auth_failure(),
+                                                 d_aad, aad_bytes, nmsg, msg_bytes, d_in, d_out, d_tags, d_verdicts,
+                                                 L->d_status));
+        else
+            ES_KCHK("eax batch", uaesk_eax_batch(L->stream, &c->tb, k1.nr, &k1.ek, decrypt, d_nonces, nonce_len, d_aad,
+                                                 aad_bytes, nmsg, msg_bytes, d_in, d_out, d_tags, d_verdicts, L->d_status));
+        if ((rc = copy_out(L, outp, d_out, total)) != 0) goto out;
+        if ((rc = decrypt ? copy_out(L, verdicts, d_verdicts, nmsg) : copy_out(L, tags, d_tags, nmsg * 16)) != 0) goto out;
+        if (decrypt) HIPCHK_GOTO(hipMemcpyAsync(&bad, L->d_status, sizeof bad, hipMemcpyDeviceToHost, (hipStream_t)L->stream));
+        HIPCHK_GOTO(hipStreamSynchronize((hipStream_t)L->stream));
+        rc = bad ? UAES_E_AUTHENTICATION : 0;
+    }
+out:
+    burn(&k1, sizeof k1);
+    burn(&k2, sizeof k2);
+    DONE(L, rc);
+}
+
+int uaes_eax_encrypt_batch(int keybits, const uint8_t *key, size_t nmsg, size_t msg_bytes,
+                           const uint8_t *nonces, size_t nonce_len, const void *aData, size_t aad_bytes,
+                           const void *pntxt, void *crtxt, uint8_t *tags)
+{
+    return aead_batch(0, 0, keybits, key, nmsg, msg_bytes, nonces, nonce_len, aData, aad_bytes, pntxt, crtxt, tags, NULL);
+}
+
+int uaes_eax_decrypt_batch(int keybits, const uint8_t *key, size_t nmsg, size_t msg_bytes,
+                           const uint8_t *nonces, size_t nonce_len, const void *aData, size_t aad_bytes,
+                           const void *crtxt, const uint8_t *tags, void *pntxt, uint8_t *verdicts)
+{
+    return aead_batch(0, 1, keybits, key, nmsg, msg_bytes, nonces, nonce_len, aData, aad_bytes, crtxt, pntxt,
+                      (uint8_t *)tags, verdicts);
+}
+
+int uaes_siv_encrypt_batch(int keybits, const uint8_t *keys, size_t nmsg, size_t msg_bytes,
+                           const void *aData, size_t aad_bytes, const void *pntxt, uint8_t *ivs, void *crtxt)
+{
+    return aead_batch(1, 0, keybits, keys, nmsg, msg_bytes, NULL, 0, aData, aad_bytes, pntxt, crtxt, ivs, NULL);
+}
+
+int uaes_siv_decrypt_batch(int keybits, const uint8_t *keys, size_t nmsg, size_t msg_bytes,
+                           const void *aData, size_t aad_bytes, const uint8_t *ivs, const void *crtxt, void *pntxt,
+                           uint8_t *verdicts)
+{
+    return aead_batch(1, 1, keybits, keys, nmsg, msg_bytes, NULL, 0, aData, aad_bytes, crtxt, pntxt, (uint8_t *)ivs,
+                      verdicts);
+}
+
+/* ------------------------------------------------------------------------ */
+/* CBC / CFB / OFB                                   */
+/* ------------------------------------------------------------------------ */
+/* mode: 0 CBC enc, 1 CBC dec, 2 CFB enc, 3 CFB dec, 4 OFB; the CBC of a reference build with CTS 0 (micro_aes.h:56):
+ * 5 + p CBC enc that pads its last chunk with AES_PADDING p (micro_aes.c:727-733), 8 CBC dec of whole blocks (:761) */
+static int feedback_common(int keybits, const uint8_t *key, const uint8_t *iVec, int mode,
+                           const void *in, size_t len, void *out)
+{
+    context *c;
+    lane *L;
+    keysched ks;
+    io_plan io;
+    int rc;
+    size_t out_len = len;
+    if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
+    if (!iVec) return fail(UAES_E_ARG, "NULL iVec");
+    if (mode <= 1 && len < 16) return UAES_E_DATALENGTH;          /* CTS: data size >= BLOCKSIZE (:708, :758) */
+    if (mode == 8 && len % 16) return UAES_E_DATALENGTH;          /* no CTS: whole blocks (:761)              */
+    if (mode >= 5 && mode <= 7) {
+        if (len > (size_t)-1 - 16) return fail(UAES_E_ARG, "length overflows");
+        out_len = len - len % 16 + ((len % 16 || mode > 5) ? 16 : 0);       /* padBlock (:610-621)            */
+    }
+    if (out_len == 0) return 0;
+    if ((len && !in) || !out) return fail(UAES_E_ARG, "NULL data pointer");
+    /* the encrypting directions and OFB are ONE serial chain; the decrypting directions of CBC and CFB are block-parallel */
+    if (host_take(in, out, len, !(mode == 1 || mode == 3 || mode == 8))) {
+        const uaesh_key hk = host_key(&ks);
+        const uint8_t *x = (const uint8_t *)in;
+        uint8_t *y = (uint8_t *)out;
+        switch (mode) {
+        case 0: HOST_RET(ks, uaesh_cbc_encrypt(&hk, iVec, 1, 0, x, len, y));
+        case 1: HOST_RET(ks, uaesh_cbc_decrypt(&hk, iVec, 1, x, len, y));
+        case 2: uaesh_cfb(&hk, iVec, 1, x, len, y); HOST_RET(ks, 0);
+        case 3: uaesh_cfb(&hk, iVec, 0, x, len, y); HOST_RET(ks, 0);
+        case 4: uaesh_ofb(&hk, iVec, x, len, y); HOST_RET(ks, 0);
+        case 8: HOST_RET(ks, uaesh_cbc_decrypt(&hk, iVec, 0, x, len, y));
+        default: HOST_RET(ks, uaesh_cbc_encrypt(&hk, iVec, 0, mode - 5, x, len, y));
+        }
+    }
+    if ((rc = enter(&c, &L)) != 0) return rc;
+    do {
+        if ((rc = plan_io(L, in, len, out, out_len, &io)) != 0) break;
+        if ((mode == 1 || mode == 3 || mode == 8) && io.din == io.dout) {
+            /* the parallel directions read C_{i-1} from the input: give them a private copy */
+            if (grow_on(L->stream, &L->stage[1], &L->stage_cap[1], len + 64)) { rc = UAES_E_HIP; break; }
+            if (hipMemcpyAsync(L->stage[1], io.din, len, hipMemcpyDeviceToDevice, (hipStream_t)L->stream) != hipSuccess) {
+                rc = fail(UAES_E_HIP, "input copy failed");
+                break;
+            }
+            io.din = L->stage[1];
+        }
+        int k = uaesk_feedback(L->stream, &c->tb, ks.nr, &ks.ek, &ks.dk, mode, iVec, io.din, len, io.dout);
+        if (k) { rc = fail(UAES_E_HIP, "feedback-mode launch: %s", hipGetErrorString((hipError_t)k)); break; }
+        rc = finish_io(&io, out_len);
+    } while (0);
+    DONE(L, rc);
+}
+
+/* CBC as a reference build with CTS 0 does it (micro_aes.h:56, micro_aes.c:704-733, :753-761): no ciphertext stealing
+ * and no minimum length; the last chunk is padded like ECB's (padding = AES_PADDING: 0 zeros behind a partial chunk,
+ * 1 PKCS#7 / 2 ISO 7816-4 always append), so crtxt receives 16 * (ptextLen / 16 + (ptextLen % 16 || padding)) bytes;
+ * decryption wants whole blocks (else UAES_E_DATALENGTH) and leaves the padding in place                         */
+int uaes_cbc_encrypt_padded(int keybits, const uint8_t *key, const uint8_t *iVec, int padding,
+                            const void *pntxt, size_t ptextLen, void *crtxt)
+{
+    if (padding < 0 || padding > 2) return fail(UAES_E_ARG, "padding %d (0 zeros, 1 PKCS#7, 2 ISO/IEC 7816-4)", padding);
+    return feedback_common(keybits, key, iVec, 5 + padding, pntxt, ptextLen, crtxt);
+}
+
+int uaes_cbc_decrypt_blocks(int keybits, const uint8_t *key, const uint8_t *iVec,
+                            const void *crtxt, size_t crtxtLen, void *pntxt)
+{
+    return feedback_common(keybits, key, iVec, 8, crtxt, crtxtLen, pntxt);
+}
+
+int uaes_cbc_encrypt(int keybits, const uint8_t *key, const uint8_t *iVec,
+                     const void *pntxt, size_t ptextLen, void *crtxt)
+{
+    return feedback_common(keybits, key, iVec, 0, pntxt, ptextLen, crtxt);
+}
+
+int uaes_cbc_decrypt(int keybits, const uint8_t *key, const uint8_t *iVec,
+                     const void *crtxt, size_t crtxtLen, void *pntxt)
+{
+    return feedback_common(keybits, key, iVec, 1, crtxt, crtxtLen, pntxt);
+}
+
+int uaes_cfb_encrypt(int keybits, const uint8_t *key, const uint8_t *iVec,
+                     const void *pntxt, size_t ptextLen, void *crtxt)
+{
+    return feedback_common(keybits, key, iVec, 2, pntxt, ptextLen, crtxt);
+}
+
+int uaes_cfb_decrypt(int keybits, const uint8_t *key, const uint8_t *iVec,
+                     const void *crtxt, size_t crtxtLen, void *pntxt)
+{
+    return feedback_common(keybits, key, iVec, 3, crtxt, crtxtLen, pntxt);
+}
+
+int uaes_ofb_xcrypt(int keybits, const uint8_t *key, const uint8_t *iVec,
+                    const void *in, size_t len, void *out)
+{
+    return feedback_common(keybits, key, iVec, 4, in, len, out);
+}
+
+/* ------------------------------------------------------------------------ */
+/* batches of independent chains (one GPU lane per message)                     */
+/* ------------------------------------------------------------------------ */
+static int batch_common(int keybits, const uint8_t *key, int mac, const uint8_t *ivs, size_t nmsg,
+                        size_t msg_bytes, const void *in, void *out)
+{
+    context *c;
+    lane *L;
+    keysched ks;
+    io_plan io;
+    const void *d_ivs = NULL;
+    int rc;
+    const size_t total = nmsg * msg_bytes, out_len = mac ? nmsg * 16 : total;
+    if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
+    if (!mac && (msg_bytes < 16 || msg_bytes % 16))
+        return fail(UAES_E_ARG, "batched CBC: every message must be a whole number of blocks (got %zu bytes)", msg_bytes);
+    if (msg_bytes && nmsg > (size_t)-1 / msg_bytes) return fail(UAES_E_ARG, "batch size overflows");
+    if (nmsg == 0) return 0;
+    if ((total && !in) || !out || (!mac && !ivs)) return fail(UAES_E_ARG, "NULL pointer");
+    if ((rc = enter(&c, &L)) != 0) return rc;
+    do {
+        if (!mac && (rc = stage_aad(L, ivs, nmsg * 16, &d_ivs)) != 0) break;     /* host IVs -> device */
+        if (!mac && (((uintptr_t)d_ivs) & 15u)) { rc = fail(UAES_E_ARG, "device IV array must be 16-byte aligned"); break; }
+        if ((rc = plan_io(L, in, total, out, out_len, &io)) != 0) break;
+        if (mac && io.dout == io.din && io.copy_back) {          /* MACs must not overwrite unread messages */
+            if (grow_on(L->stream, &L->stage[1], &L->stage_cap[1], out_len + 64)) { rc = UAES_E_HIP; break; }
+            io.dout = L->stage[1];
+        }
+        int k = uaesk_chain_batch(L->stream, &c->tb, ks.nr, &ks.ek, mac, d_ivs, nmsg, msg_bytes, io.din, io.dout);
+        if (k) { rc = fail(UAES_E_HIP, "batch launch: %s", hipGetErrorString((hipError_t)k)); break; }
+        rc = finish_io(&io, out_len);
+    } while (0);
+    DONE(L, rc);
+}
+
+int uaes_cbc_encrypt_batch(int keybits, const uint8_t *key, const uint8_t *ivs, size_t nmsg,
+                           size_t msg_bytes, const void *pntxt, void *crtxt)
+{
+    return batch_common(keybits, key, 0, ivs, nmsg, msg_bytes, pntxt, crtxt);
+}
+
+int uaes_cmac_batch(int keybits, const uint8_t *key, size_t nmsg, size_t msg_bytes,
+                    const void *data, uint8_t *macs)
+{
+    return batch_common(keybits, key, 1, NULL, nmsg, msg_bytes, data, macs);
+}
+
+/* ------------------------------------------------------------------------ */
+/* OCB (RFC 7253; AES_OCB_encrypt / AES_OCB_decrypt, micro_aes.c:1774-1811)     */
+/* ------------------------------------------------------------------------ */
+/* nonceLen / tagLen = the reference's compile-time OCB_NONCE_LEN (1..15) / OCB_TAG_LEN (1..16), micro_aes.h:115-116 */
+static int ocb_common(int keybits, const uint8_t *key, const uint8_t *nonce, size_t nonceLen, size_t tagLen, int decrypt,
+                      const void *aData, size_t aDataLen, const void *in, size_t len, void *out)
+{
+    context *c;
+    lane *L;
+    keysched ks;
+    io_plan io;
+    const void *d_aad;
+    int rc, status = -1;
+    if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
+    if (!nonce || (!decrypt && !out) || (len && (!in || !out)) || (decrypt && !in))
+        return fail(UAES_E_ARG, "NULL pointer");
+    if (nonceLen < 1 || nonceLen > 15) return fail(UAES_E_ARG, "OCB nonce length %zu (1..15)", nonceLen);
+    if (tagLen < 1 || tagLen > 16) return fail(UAES_E_ARG, "OCB tag length %zu (1..16)", tagLen);
+    if (aDataLen && !aData) return fail(UAES_E_ARG, "NULL aData with aDataLen != 0");
+    if (host_take(in, out, len, 0) && !is_device_ptr(aData)) {
+        const uaesh_key hk = host_key(&ks);
+        rc = uaesh_ocb(&hk, decrypt, nonce, nonceLen, tagLen, (const uint8_t *)aData, aDataLen, (const uint8_t *)in, len, (uint8_t *)out);
+        if (rc < 0) return fail(UAES_E_HIP, "out of host memory");
+        if (rc == UAES_E_AUTHENTICATION && wipe_on_auth_failure()) memset(out, 0, len);
+        HOST_RET(ks, rc);
+    }
+    if ((rc = enter(&c, &L)) != 0) return rc;
+    do {
+        if ((rc = gcm_scratch(L, SCRATCH_OTHER)) != 0) break;        /* >= uaesk_ocb_scratch_bytes() */
+        if ((rc = stage_aad(L, aData, aDataLen, &d_aad)) != 0) break;
+        if ((rc = plan_io(L, in, len + (decrypt ? tagLen : 0), out, len + (decrypt ? 0 : tagLen), &io)) != 0) break;
+        int *st_where = lane_status(L);
+        if (!decrypt || st_where != L->d_status) {            /* a one-launch call may carry the completion ticket */
+            if (decrypt) *(volatile int *)st_where = -1;
+            ticket_arm(L, len);
+        }
+        int k = uaesk_ocb(L->stream, &c->tb, ks.nr, &ks.ek, &ks.dk, decrypt, nonce, nonceLen, tagLen, d_aad, aDataLen,
+                          io.din, len, io.dout, L->scratch, scratch_done_word(L->scratch, L->scratch_cap), st_where);
+        ticket_armed_launch_done(L);
+        if (k) { rc = fail(UAES_E_HIP, "ocb launch: %s", hipGetErrorString((hipError_t)k)); break; }
+        if (decrypt) {
+            if ((rc = lane_read_status(L, st_where, &status)) != 0) break;
+            io.drained = 1;
+        }
+        /* decrypt: the text stays on a bad tag, as in the reference, unless wiping is switched on */
+        if ((rc = (decrypt && status != 0) ? finish_io_unauthenticated(&io, len)
+                                           : finish_io(&io, len + (decrypt ? 0 : tagLen))) != 0) break;
+        if (decrypt && status != 0) rc = UAES_E_AUTHENTICATION;
+    } while (0);
+    DONE(L, rc);
+}
+
+int uaes_ocb_encrypt(int keybits, const uint8_t *key, const uint8_t *nonce,
+                     const void *aData, size_t aDataLen,
+                     const void *pntxt, size_t ptextLen, void *crtxt)
+{
+    return ocb_common(keybits, key, nonce, 12, 16, 0, aData, aDataLen, pntxt, ptextLen, crtxt);
+}
+
+int uaes_ocb_encrypt_ex(int keybits, const uint8_t *key, const uint8_t *nonce, size_t nonceLen, size_t tagLen,
+                        const void *aData, size_t aDataLen,
+                        const void *pntxt, size_t ptextLen, void *crtxt)
+{
+    return ocb_common(keybits, key, nonce, nonceLen, tagLen, 0, aData, aDataLen, pntxt, ptextLen, crtxt);
+}
+
+int uaes_ocb_decrypt_ex(int keybits, const uint8_t *key, const uint8_t *nonce, size_t nonceLen, size_t tagLen,
+                        const void *aData, size_t aDataLen,
+                        const void *crtxt, size_t crtxtLen, void *pntxt)
+{
+    return ocb_common(keybits, key, nonce, nonceLen, tagLen, 1, aData, aDataLen, crtxt, crtxtLen, pntxt);
+}
+
+int uaes_ocb_decrypt(int keybits, const uint8_t *key, const uint8_t *nonce,
+                     const void *aData, size_t aDataLen,
+                     const void *crtxt, size_t crtxtLen, void *pntxt)
+{
+    return ocb_common(keybits, key, nonce, 12, 16, 1, aData, aDataLen, crtxt, crtxtLen, pntxt);
+}
+
+int uaes_ocb_dev(int keybits, const uint8_t *key, const uint8_t *nonce, int decrypt,
+                 const void *d_aad, size_t aad_len,
+                 const void *d_in, size_t len, void *d_out, int *d_status, void *stream)
+{
+    context *c;
+    keysched ks;
+    void *scr;
+    int rc, slot;
+    if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
+    if (!nonce || (decrypt ? !d_in : !d_out)) return fail(UAES_E_ARG, "NULL pointer");
+    if ((rc = dev_ptrs_ok(d_in, d_out, len)) != 0) return rc;
+    if (decrypt && !d_status) return fail(UAES_E_ARG, "NULL d_status");
+    if ((rc = get_context(&c)) != 0) return rc;
+    if ((rc = gcm_scratch_locked(c, stream, &scr, &slot)) != 0) return rc;
+    KCHK_PINNED(c, slot, uaesk_ocb(stream, &c->tb, ks.nr, &ks.ek, &ks.dk, decrypt, nonce, 12, 16, d_aad, aad_len, d_in, len,
+                                   d_out, scr, scratch_done_word(scr, c->slot[slot].cap), d_status));
+    return 0;
+}

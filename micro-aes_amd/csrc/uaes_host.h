@@ -1,5 +1,5 @@
 /*
- * uaes_host.h -- the engine's own host data path (uaes_host.c): what uaes_engine.c calls when the deployer has
+ * uaes_host.h -- the engine's own host data path (uaes_host.c): what the entry points in uaes_engine_*.c call when the deployer has
  * switched it on (uaes_set_host_policy, include/uaes_hip.h).  Plain C, host memory only, re-entrant; key schedules are
  * the engine's (little-endian words of the FIPS-197 byte stream: ek = encryption round keys, dk = the equivalent
  * inverse cipher's).  Every function states the reference function it follows (paths relative to the reference).

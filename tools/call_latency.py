@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """Per-call latency of the drop-in boundary for small buffers (BASELINE config C1 is a
-4 KiB ECB call): host pointers (staged through device memory) and device pointers."""
+4 KiB ECB call): host pointers (staged through device memory) and device pointers.
+
+    python tools/call_latency.py [libuaes_hip_A.so [reps]]   # another build kept in micro-aes_amd/lib/ (tools/ab_libs.py);
+                                                             # reps: timed calls per cell (300)"""
 import ctypes as C
 import os
 import sys
@@ -11,12 +14,17 @@ import numpy as np
 import torch
 import micro_aes_amd as uaes
 
+if len(sys.argv) > 1:
+    uaes.lib_path.__defaults__ = (sys.argv[1],)
 L = uaes.engine()
 key, iv, nonce = bytes(range(16)), bytes(range(0xF0, 0xFC)), bytes(range(12))
 keys2 = bytes(range(32))
 
 
-def bench(name, fn, reps=300):
+REPS = int(sys.argv[2]) if len(sys.argv) > 2 else 300
+
+
+def bench(name, fn, reps=REPS):
     for _ in range(10):
         fn()
     t0 = time.perf_counter()
@@ -41,4 +49,4 @@ for n in (16, 4096, 65536, 1 << 20):
             "gcm": bench("gcm", lambda: L.uaes_gcm_encrypt(128, key, nonce, None, 0, x, n, y)),
             "ocb": bench("ocb", lambda: L.uaes_ocb_encrypt(128, key, nonce, None, 0, x, n, y)),
         }
-        print("%8d B  %s pointers, us per call: " % (n, tag) + "  ".join("%s %7.1f" % kv for kv in r.items()))
+        print("%8d B  %s pointers, us per call: " % (n, tag) + "  ".join("%s %7.2f" % kv for kv in r.items()))
