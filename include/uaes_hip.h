@@ -593,6 +593,17 @@ const char *uaes_debug_plan_poly1305(size_t len, size_t nmsg, int out[3]);
  * dir 0 encrypt / 1 decrypt; out (may be NULL) = launches, workgroups of the main kernel, UAES_EAX_SIV_SMALL_MAX
  * (the longest text of the small arrangement).  NULL for arguments that make no sense. */
 const char *uaes_debug_plan_eax_siv(int siv, int dir, size_t len, size_t nmsg, int out[3]);
+/* The planners of the feedback modes, the CBC-MAC modes and the batches of chains (csrc/uaes_plan.h, their own rows):
+ *   what   0 CBC with CS3 stealing, 1 CFB, 2 OFB, 3 CMAC, 4 CCM, 5 uaes_cbc_encrypt_batch, 6 uaes_cmac_batch,
+ *          7 CBC without stealing (uaes_cbc_encrypt_padded / uaes_cbc_decrypt_blocks)
+ *   dir    0 encrypt (or the MAC), 1 decrypt
+ *   a, b   bytes of text (batches: bytes per message), messages of a batch (ignored otherwise)
+ *   out    (may be NULL) launches, workgroups of the main kernel, its threads per workgroup
+ * Returns "chain.serial" (one wave walks the chain), "fbdec.single" / "fbdec.tiled" (the block-parallel decrypt with
+ * one / four blocks per lane), "ccm.fused" / "ccm.split", "batch.row" / "batch.lane" (sixteen lanes / one lane per
+ * message), or NULL for arguments that make no sense.  Works without a device (a 256-CU MI355X).
+ * tests/test_gpu_chains.py derives its sizes and message counts from this. */
+const char *uaes_debug_plan_chain(int what, int dir, size_t a, size_t b, int out[3]);
 
 /* Test hooks of the one-launch GCM / GCM-SIV / streamed-piece arrangements (chunk workgroups + one preparing workgroup
  * in ONE launch; whoever of them arrives last on a counter word folds the chunk hashes and makes the tag -- nobody

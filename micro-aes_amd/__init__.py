@@ -45,7 +45,7 @@ EXPORTS = [
     "uaes_poly1305", "uaes_poly1305_dev", "uaes_poly1305_batch", "uaes_debug_plan_poly1305",
     "uaes_eax_encrypt", "uaes_eax_decrypt", "uaes_siv_encrypt", "uaes_siv_decrypt",
     "uaes_eax_encrypt_batch", "uaes_eax_decrypt_batch", "uaes_siv_encrypt_batch", "uaes_siv_decrypt_batch",
-    "uaes_debug_plan_eax_siv",
+    "uaes_debug_plan_eax_siv", "uaes_debug_plan_chain",
     "uaes_mgpu_ctr_xcrypt_at", "uaes_mgpu_xts_sectors", "uaes_mgpu_ctr_encrypt_gather", "uaes_debug_gather_stats", "uaes_debug_gcm_look", "uaes_debug_gcm_chunk_folds",
     "uaes_debug_plan", "uaes_debug_plan_at", "uaes_debug_arrangement_name", "uaes_debug_plan_disable",
     "uaes_mgpu_ecb_encrypt", "uaes_mgpu_ecb_decrypt", "uaes_mgpu_gcm_encrypt", "uaes_mgpu_gcm_decrypt",
@@ -156,6 +156,8 @@ def engine():
     L.uaes_debug_plan_eax_siv.argtypes = [i, i, sz, sz, C.POINTER(C.c_int)]
     L.uaes_debug_plan_eax_siv.restype = C.c_char_p
     L.uaes_debug_plan_poly1305.restype = C.c_char_p
+    L.uaes_debug_plan_chain.argtypes = [i, i, sz, sz, C.POINTER(C.c_int)]
+    L.uaes_debug_plan_chain.restype = C.c_char_p
     for n in ("uaes_cbc_encrypt", "uaes_cbc_decrypt", "uaes_cbc_decrypt_blocks", "uaes_cfb_encrypt", "uaes_cfb_decrypt", "uaes_ofb_xcrypt"):
         getattr(L, n).argtypes = [i, vp, vp, vp, sz, vp]
     for n in ("uaes_ccm_encrypt", "uaes_ccm_decrypt", "uaes_gcmsiv_encrypt", "uaes_gcmsiv_decrypt",
@@ -222,7 +224,7 @@ def engine():
             continue
         if n not in ("uaes_last_error", "uaes_version", "uaes_gcm_key_free", "uaes_gcm_stream_abort", "uaes_debug_gather_stats", "uaes_debug_gcm_look",
                      "uaes_debug_arrangement_name", "uaes_debug_plan_disable", "uaes_debug_plan_poly1305",
-                     "uaes_debug_plan_eax_siv"):
+                     "uaes_debug_plan_eax_siv", "uaes_debug_plan_chain"):
             getattr(L, n).restype = i
     _lib = L
     return L
@@ -599,6 +601,20 @@ def eax_siv_plan(siv, length, nmsg=1, decrypt=False):
     longest text of the small arrangement)."""
     out = (C.c_int * 3)()
     name = engine().uaes_debug_plan_eax_siv(int(bool(siv)), int(bool(decrypt)), length, nmsg, out)
+    return name.decode(), out[0], out[1], out[2]
+
+
+CHAIN_WHAT = {"cbc": 0, "cfb": 1, "ofb": 2, "cmac": 3, "ccm": 4, "cbc_batch": 5, "cmac_batch": 6, "cbc_nocts": 7}
+
+
+def chain_plan(what, a, b=0, decrypt=False):
+    """What a CBC / CFB / OFB / CMAC / CCM call or a batch of chains would run (uaes_debug_plan_chain): (arrangement,
+    launches, workgroups of the main kernel, its threads per workgroup).  a = bytes of text (batches: bytes per
+    message), b = messages of a batch."""
+    out = (C.c_int * 3)()
+    name = engine().uaes_debug_plan_chain(CHAIN_WHAT[what], int(bool(decrypt)), a, b, out)
+    if name is None:
+        raise ValueError("no plan for %s of %d bytes (%d messages, decrypt=%s)" % (what, a, b, bool(decrypt)))
     return name.decode(), out[0], out[1], out[2]
 
 

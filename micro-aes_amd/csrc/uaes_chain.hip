@@ -9,8 +9,8 @@
  *                           workgroups, 4 blocks per lane, 1 KiB wave accesses).
  *   k_chain_serial          the inherently serial directions -- CBC encrypt
  *                           (:697-744), CFB encrypt (:799-817, mode 1), OFB
- *                           (:861-893) -- and the CTS pair of CBC decrypt: one
- *                           lane walks the chain (north_star: "CBC/CFB/OFB stay
+ *                           (:861-893): one wave
+ *                           walks the chain (north_star: "CBC/CFB/OFB stay
  *                           single-GPU because the chain is serial").
  *
  * The parallel kernels read C_{i-1} from the INPUT buffer, so they must not run
@@ -23,6 +23,7 @@
 #include <stdlib.h>
 #include "uaes_aes.hip.h"
 #include "uaes_device.h"
+#include "uaes_plan.h"
 
 #define UAES_U 4
 static inline hipStream_t S(void *s) { return (hipStream_t)s; }
@@ -188,13 +189,11 @@ __global__ __launch_bounds__(UAES_WG) void k_fb_dec(uaesk_rk rk, uaesk_tables tb
     }
 }
 
-enum { CH_CBC_ENC = 0, CH_CFB_ENC = 1, CH_OFB = 2, CH_CBC_DEC_CTS = 3, CH_CBC_ENC_PAD = 4 };
+enum { CH_CBC_ENC = 0, CH_CFB_ENC = 1, CH_OFB = 2, CH_CBC_ENC_PAD = 4 };
 
 /* OP = CH_CBC_ENC     whole message, CS3 ciphertext stealing (AES_CBC_encrypt :697-744); len >= 16
  *      CH_CFB_ENC     whole message (:799-817 mode 1)
  *      CH_OFB         whole message (:861-886)
- *      CH_CBC_DEC_CTS the last two blocks {X full, Z r bytes} of AES_CBC_decrypt (:770-778):
- *                     in/out point at X; iv = the block before X (or the IV)
  *      CH_CBC_ENC_PAD whole message of a build with CTS 0 (:704-733): no stealing, the last chunk padded by
  *                     padBlock (:610-621) with aux = AES_PADDING (0: zeros behind a partial chunk only; 1 PKCS#7 and
  *                     2 ISO 7816-4 always append); any len, writes 16 * (len / 16 + (len % 16 || aux)) bytes       */
@@ -206,17 +205,8 @@ __global__ __launch_bounds__(UAES_WG) void k_chain_serial(uaesk_rk rk, uaesk_tab
 {
     /* encrypt-direction chains: ONE wave; the sixteen lanes of a DPP row share each block encryption
      * (row_encrypt, uaes_aes.hip.h: one state byte and one lookup per lane and round), the four rows run
-     * redundantly, the chain value stays a column word per lane and lanes 0/4/8/12 store.  The two-block CTS
-     * decrypt keeps the one-lane inverse cipher on the full tables (launched with 1024 threads to fill them). */
-    if (OP == CH_CBC_DEC_CTS) {
-        fill_dec_tables(tb.td0);
-        if (threadIdx.x != 0) return;
-        const LaneConst lc = make_lane_const();
-        if (iv_dev) iv4 = *iv_dev;
-        const Blk iv = { { iv4.x, iv4.y, iv4.z, iv4.w } };
-        cbc_dec_cts_pair<NR>(rk, lc, iv, in, out, (u32)len);      /* rk = decryption keys */
-        return;
-    }
+     * redundantly, the chain value stays a column word per lane and lanes 0/4/8/12 store.  (The stolen pair of CBC
+     * decrypt is one lane's work in k_fb_dec.) */
     row_fill_tables(tb.te0, rk);
     const RowLane<NR> L = row_lane<NR>();
     if (iv_dev) iv4 = *iv_dev;
@@ -478,74 +468,167 @@ static unsigned cu_count()
     return cus > 0 ? (unsigned)cus : 256u;
 }
 
+/* ---- the plan (uaes_plan.h): every size threshold of this file ---------------------------------------------------- */
+/* the parallel decrypt of n blocks: short texts take one block per lane so that up to four times as many CUs take
+ * part; the grid is capped at the CU count and the kernel strides beyond it */
+static void plan_fb_dec(u64 n, uaes_plan *p)
+{
+    const u64 wgs4 = (n + (u64)UAES_WG * UAES_U - 1) / ((u64)UAES_WG * UAES_U);
+    const unsigned u = wgs4 * 2 <= cu_count() ? 1u : (unsigned)UAES_U;
+    u64 want = (n + (u64)UAES_WG * u - 1) / ((u64)UAES_WG * u);
+    if (!want) want = 1;
+    p->arrangement = u == 1 ? UAES_FBDEC_SINGLE : UAES_FBDEC_TILED;
+    p->launches = 1;
+    p->grid = (unsigned)(want < cu_count() ? want : cu_count());
+    p->steps = UAES_WG;
+}
+
+/* sixteen lanes per message up to UAES_BATCH_ROW_MAX messages, a lane per message beyond (where the two arrangements
+ * cross: profiles/HISTORY.md, profiles/r05_batch_rate_after.log).  Row kernel: 64 messages per 16-wave workgroup; few messages: 4-wave workgroups,
+ * so that they spread over the CUs.  Either grid is capped at the CU count and the kernels stride beyond it. */
+static void plan_batch(u64 nmsg, uaes_plan *p)
+{
+    p->launches = 1;
+    if (nmsg <= (u64)UAES_BATCH_ROW_MAX) {
+        const unsigned wg = (nmsg + 63) / 64 * 2 <= cu_count() ? 256u : UAES_WG;
+        const u64 want = (nmsg + wg / 16 - 1) / (wg / 16);
+        p->arrangement = UAES_BATCH_ROW;
+        p->grid = (unsigned)(want < cu_count() ? (want ? want : 1) : cu_count());
+        p->steps = wg;
+        return;
+    }
+    const u64 want = (nmsg + UAES_WG - 1) / UAES_WG;
+    p->arrangement = UAES_BATCH_LANE;
+    p->grid = (unsigned)(want < cu_count() ? want : cu_count());
+    p->steps = UAES_WG;
+}
+
+/* CBC decrypt with stealing: n parallel blocks in front of the held-back pair {full block, r bytes} (r = 0: none) */
+static void cbc_cts_split(u64 len, u64 *n, u32 *r)
+{
+    *n = len / 16;
+    *r = (u32)(len % 16);
+    if (*n > 1 && !*r) { --*n; *r = 16; }                 /* CS3 (:756) */
+    if (*r) --*n;                                         /* hold the last two blocks (:764) */
+}
+
+/* the encrypting directions and OFB: one wave walks the chain, whatever the length */
+static void plan_serial(uaes_plan *p)
+{
+    p->arrangement = UAES_CHAIN_SERIAL;
+    p->launches = 1;
+    p->grid = 1;
+    p->steps = 64;
+}
+
+extern "C" int uaesk_plan_chain(int what, int dir, size_t a, size_t b, uaes_plan *p)
+{
+    memset(p, 0, sizeof *p);
+    if (dir != 0 && dir != 1) return (int)hipErrorInvalidValue;
+    switch (what) {
+    case UAES_WHAT_CBC_BATCH:
+        if (a < 16 || a % 16) return (int)hipErrorInvalidValue;
+        /* fall through */
+    case UAES_WHAT_CMAC_BATCH:
+        if (dir) return (int)hipErrorInvalidValue;
+        plan_batch(b, p);
+        return 0;
+    case UAES_WHAT_CBC:
+        if (a < 16) return (int)hipErrorInvalidValue;
+        if (dir) {
+            u64 n;
+            u32 r;
+            cbc_cts_split(a, &n, &r);
+            plan_fb_dec(n, p);
+            return 0;
+        }
+        break;
+    case UAES_WHAT_CBC_NOCTS:
+        if (dir) {
+            if (a % 16) return (int)hipErrorInvalidValue;
+            plan_fb_dec(a / 16, p);
+            return 0;
+        }
+        break;
+    case UAES_WHAT_CFB:
+        if (dir) { plan_fb_dec(a / 16, p); return 0; }
+        break;
+    case UAES_WHAT_OFB:
+        break;
+    default:
+        return (int)hipErrorInvalidValue;
+    }
+    plan_serial(p);
+    return 0;
+}
+
+extern "C" const char *uaesk_chain_arrangement_name(int id)
+{
+    static const char *const names[] = { "chain.serial", "fbdec.single", "fbdec.tiled", "ccm.fused", "ccm.split",
+                                         "batch.row", "batch.lane" };
+    return id >= 0 && id < 7 ? names[id] : "?";
+}
+
 template <int NR, bool CFB, int U>
 static int launch_fb_dec_u(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *k, uint4 iv,
-                           const void *in, void *out, u64 n, u32 rem, u32 cts_r)
+                           const void *in, void *out, u64 n, u32 rem, u32 cts_r, unsigned grid)
 {
     const unsigned lds = CFB ? UAES_LDS_ENC : UAES_LDS_DEC;
     hipError_t e = uaesk_want_lds((const void *)k_fb_dec<NR, CFB, U>, (unsigned)(lds));
     if (e != hipSuccess) return (int)e;
-    u64 want = (n + (u64)UAES_WG * U - 1) / ((u64)UAES_WG * U);
-    if (!want) want = 1;
-    const unsigned grid = (unsigned)(want < cu_count() ? want : cu_count());
     hipLaunchKernelGGL((k_fb_dec<NR, CFB, U>), dim3(grid), dim3(UAES_WG), lds, st, *k, *tb, iv,
                        (const uint4 *)in, (uint4 *)out, n, rem, cts_r);
     return (int)hipGetLastError();
 }
 
-/* short texts take one block per lane so that up to four times as many CUs take part */
 template <int NR, bool CFB>
 static int launch_fb_dec(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *k, uint4 iv,
                          const void *in, void *out, u64 n, u32 rem, u32 cts_r = 0)
 {
-    const u64 wgs4 = (n + (u64)UAES_WG * UAES_U - 1) / ((u64)UAES_WG * UAES_U);
-    if (wgs4 * 2 <= cu_count()) return launch_fb_dec_u<NR, CFB, 1>(st, tb, k, iv, in, out, n, rem, cts_r);
-    return launch_fb_dec_u<NR, CFB, UAES_U>(st, tb, k, iv, in, out, n, rem, cts_r);
+    uaes_plan p;
+    plan_fb_dec(n, &p);
+    if (p.arrangement == UAES_FBDEC_SINGLE) return launch_fb_dec_u<NR, CFB, 1>(st, tb, k, iv, in, out, n, rem, cts_r, p.grid);
+    return launch_fb_dec_u<NR, CFB, UAES_U>(st, tb, k, iv, in, out, n, rem, cts_r, p.grid);
 }
 
 template <int NR, int OP>
 static int launch_serial(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *k, uint4 iv,
                          const void *in, void *out, u64 len, const uint4 *iv_dev = nullptr, u32 aux = 0)
 {
-    const unsigned lds = OP == CH_CBC_DEC_CTS ? UAES_LDS_DEC : UAES_LDS_ROW;
-    const unsigned threads = OP == CH_CBC_DEC_CTS ? UAES_WG : 64u;
+    const unsigned lds = UAES_LDS_ROW;
+    uaes_plan p;
+    plan_serial(&p);
     hipError_t e = uaesk_want_lds((const void *)k_chain_serial<NR, OP>, (unsigned)(lds));
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((k_chain_serial<NR, OP>), dim3(1), dim3(threads), lds, st, *k, *tb, iv, iv_dev,
+    hipLaunchKernelGGL((k_chain_serial<NR, OP>), dim3(p.grid), dim3(p.steps), lds, st, *k, *tb, iv, iv_dev,
                        (const unsigned char *)in, (unsigned char *)out, len, aux);
     return (int)hipGetLastError();
 }
 
-/* a lane per message from 81 920 messages on (where the two arrangements cross), sixteen lanes below:
- * tools/batch_rate.py, profiles/r05_batch_rate.log; UAES_BATCH_ROW_MAX moves the switch */
+/* the arrangement, the workgroup shape and the grid are plan_batch's */
 template <int NR, bool MAC>
 static int launch_batch(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *k, const void *ivs,
                         u64 nmsg, u64 msg_bytes, const void *in, void *out)
 {
-    const int row_max = 81919;
-    if (nmsg <= (u64)row_max) {
+    uaes_plan p;
+    plan_batch(nmsg, &p);
+    if (p.arrangement == UAES_BATCH_ROW) {
         const bool a4 = ((((uintptr_t)in) | ((uintptr_t)out)) & 3u) == 0 && msg_bytes % 4 == 0;
-        /* 64 messages per 16-wave workgroup; few messages: 4-wave workgroups, so that they spread over the CUs */
-        const unsigned wg = (nmsg + 63) / 64 * 2 <= cu_count() ? 256u : UAES_WG;
-        const u64 want = (nmsg + wg / 16 - 1) / (wg / 16);
-        const unsigned grid = (unsigned)(want < cu_count() ? want : cu_count());
         hipError_t e;
         if (a4) {
             if ((e = uaesk_want_lds((const void *)k_chain_batch_row<NR, MAC, true>, (unsigned)(UAES_LDS_ROW4))) != hipSuccess) return (int)e;
-            hipLaunchKernelGGL((k_chain_batch_row<NR, MAC, true>), dim3(grid), dim3(wg), UAES_LDS_ROW4, st, *k, *tb,
+            hipLaunchKernelGGL((k_chain_batch_row<NR, MAC, true>), dim3(p.grid), dim3(p.steps), UAES_LDS_ROW4, st, *k, *tb,
                                (const uint4 *)ivs, nmsg, msg_bytes, (const unsigned char *)in, (unsigned char *)out);
         } else {
             if ((e = uaesk_want_lds((const void *)k_chain_batch_row<NR, MAC, false>, (unsigned)(UAES_LDS_ROW4))) != hipSuccess) return (int)e;
-            hipLaunchKernelGGL((k_chain_batch_row<NR, MAC, false>), dim3(grid), dim3(wg), UAES_LDS_ROW4, st, *k, *tb,
+            hipLaunchKernelGGL((k_chain_batch_row<NR, MAC, false>), dim3(p.grid), dim3(p.steps), UAES_LDS_ROW4, st, *k, *tb,
                                (const uint4 *)ivs, nmsg, msg_bytes, (const unsigned char *)in, (unsigned char *)out);
         }
         return (int)hipGetLastError();
     }
     hipError_t e = uaesk_want_lds((const void *)k_chain_batch<NR, MAC>, (unsigned)(UAES_LDS_ENC));
     if (e != hipSuccess) return (int)e;
-    u64 want = (nmsg + UAES_WG - 1) / UAES_WG;
-    const unsigned grid = (unsigned)(want < cu_count() ? (want ? want : 1) : cu_count());
-    hipLaunchKernelGGL((k_chain_batch<NR, MAC>), dim3(grid), dim3(UAES_WG), UAES_LDS_ENC, st, *k, *tb,
+    hipLaunchKernelGGL((k_chain_batch<NR, MAC>), dim3(p.grid), dim3(p.steps), UAES_LDS_ENC, st, *k, *tb,
                        (const uint4 *)ivs, nmsg, msg_bytes, (const unsigned char *)in, (unsigned char *)out);
     return (int)hipGetLastError();
 }
@@ -585,10 +668,9 @@ extern "C" int uaesk_feedback(void *stream, const uaesk_tables *tb, int nr,
     case 4: DISPATCH_NR(nr, return (launch_serial<NR, CH_OFB>(st, tb, ek, iv, in, out, len))); break;
     case 3: DISPATCH_NR(nr, return (launch_fb_dec<NR, true>(st, tb, ek, iv, in, out, len / 16, (u32)(len % 16)))); break;
     case 1: {
-        u64 n = len / 16;
-        u32 r = (u32)(len % 16);
-        if (n > 1 && !r) { --n; r = 16; }                 /* CS3 (:756) */
-        if (r) --n;                                       /* hold the last two blocks (:764) */
+        u64 n;
+        u32 r;
+        cbc_cts_split(len, &n, &r);
         /* the n parallel blocks and the stolen pair behind them in ONE launch (k_fb_dec: one lane takes the pair) */
         DISPATCH_NR(nr, return (launch_fb_dec<NR, false>(st, tb, dk, iv, in, out, n, 0, r)));
     } break;

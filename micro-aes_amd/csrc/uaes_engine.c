@@ -1406,6 +1406,15 @@ const char *uaes_debug_plan_eax_siv(int siv, int dir, size_t len, size_t nmsg, i
     if (out) { out[0] = p.launches; out[1] = (int)p.grid; out[2] = (int)UAES_EAX_SIV_SMALL_MAX; }
     return uaesk_eax_siv_arrangement_name(p.arrangement);
 }
+const char *uaes_debug_plan_chain(int what, int dir, size_t a, size_t b, int out[3])
+{
+    uaes_plan p;
+    memset(&p, 0, sizeof p);
+    if (what == UAES_WHAT_CMAC || what == UAES_WHAT_CCM ? uaesk_plan_mac(what, dir, a, &p) : uaesk_plan_chain(what, dir, a, b, &p))
+        return NULL;
+    if (out) { out[0] = p.launches; out[1] = (int)p.grid; out[2] = (int)p.steps; }
+    return uaesk_chain_arrangement_name(p.arrangement);
+}
 void uaes_debug_plan_disable(unsigned mask) { uaesk_plan_disable(mask); }
 
 /* ---- test hooks of the one-launch GCM arrangements (include/uaes_hip.h) ---- */

@@ -16,6 +16,7 @@
 #include <string.h>
 #include "uaes_ctr.hip.h"
 #include "uaes_device.h"
+#include "uaes_plan.h"
 
 static inline hipStream_t S(void *s) { return (hipStream_t)s; }
 
@@ -302,13 +303,43 @@ __global__ __launch_bounds__(64) void k_ccm(uaesk_rk rk, uaesk_tables tb, uint4 
     default: return (int)hipErrorInvalidValue;        \
     }
 
+/* ---- the plan (uaes_plan.h) ---------------------------------------------------------------------------------------
+ * CMAC is one wave whatever the length.  CCM: a short message (CCM's usual diet) is ONE launch, the MAC chain and the
+ * counter blocks share the wave (ccm_text); its chain step is a third longer than the plain MAC's, so texts beyond
+ * UAES_CCM_FUSED_MAX keep the two kernels.  plan_mac is what the launchers switch on and take their launch shape
+ * from; it costs them nothing (the CTR kernels' share of ccm.split's launches is added for the hook alone). */
+static void plan_mac(int what, size_t a, uaes_plan *p)
+{
+    memset(p, 0, sizeof *p);
+    p->arrangement = what == UAES_WHAT_CMAC ? UAES_CHAIN_SERIAL : a <= UAES_CCM_FUSED_MAX ? UAES_CCM_FUSED : UAES_CCM_SPLIT;
+    p->launches = 1;
+    p->grid = 1;                                 /* one wave: sixteen lanes per block, four rows */
+    p->steps = 64;
+}
+
+extern "C" int uaesk_plan_mac(int what, int dir, size_t a, uaes_plan *p)
+{
+    memset(p, 0, sizeof *p);
+    if ((what != UAES_WHAT_CMAC && what != UAES_WHAT_CCM) || (dir != 0 && dir != 1) || (what == UAES_WHAT_CMAC && dir))
+        return (int)hipErrorInvalidValue;
+    plan_mac(what, a, p);
+    if (p->arrangement == UAES_CCM_SPLIT) {
+        uaes_plan ctr;
+        if (uaesk_plan(UAES_PLAN_CTR, 0, a, 0, 0, &ctr)) return (int)hipErrorInvalidValue;
+        p->launches += ctr.launches;
+    }
+    return 0;
+}
+
 template <int NR>
 static int launch_cmac(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *ek,
                        const void *data, size_t len, void *mac)
 {
+    uaes_plan p;
+    plan_mac(UAES_WHAT_CMAC, len, &p);
     hipError_t e = uaesk_want_lds((const void *)k_cmac<NR>, (unsigned)(UAES_LDS_ROW));
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((k_cmac<NR>), dim3(1), dim3(64), UAES_LDS_ROW, st, *ek, *tb,
+    hipLaunchKernelGGL((k_cmac<NR>), dim3(p.grid), dim3(p.steps), UAES_LDS_ROW, st, *ek, *tb,
                        (const unsigned char *)data, (u64)len, (unsigned char *)mac);
     return (int)hipGetLastError();
 }
@@ -320,22 +351,20 @@ extern "C" int uaesk_cmac(void *stream, const uaesk_tables *tb, int nr, const ua
     return 0;
 }
 
-#define CCM_FUSED_MAX 256u
-
 template <int NR>
-static int launch_ccm_tag(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *ek, uint4 iv,
+static int launch_ccm_tag(hipStream_t st, const uaes_plan &p, const uaesk_tables *tb, const uaesk_rk *ek, uint4 iv,
                           const void *aad, size_t aad_len, const void *pt, size_t pt_len,
                           int mode, void *tag_io, int *status, u32 tag_len)
 {
     hipError_t e = uaesk_want_lds((const void *)k_ccm_tag<NR>, (unsigned)(UAES_LDS_ROW));
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((k_ccm_tag<NR>), dim3(1), dim3(64), UAES_LDS_ROW, st, *ek, *tb, iv,
+    hipLaunchKernelGGL((k_ccm_tag<NR>), dim3(p.grid), dim3(p.steps), UAES_LDS_ROW, st, *ek, *tb, iv,
                        (const unsigned char *)aad, (u64)aad_len, (const unsigned char *)pt, (u64)pt_len,
                        mode, (unsigned char *)tag_io, status, tag_len);
     return (int)hipGetLastError();
 }
 template <int NR>
-static int launch_ccm(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *ek, uint4 iv, const uaesk_ctr &c, int decrypt,
+static int launch_ccm(hipStream_t st, const uaes_plan &p, const uaesk_tables *tb, const uaesk_rk *ek, uint4 iv, const uaesk_ctr &c, int decrypt,
                       const void *aad, size_t aad_len, const void *in, size_t len, void *out,
                       void *tag_io, int *status, u32 tag_len)
 {
@@ -343,13 +372,13 @@ static int launch_ccm(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *ek
     if (decrypt) {
         e = uaesk_want_lds((const void *)k_ccm<NR, true>, (unsigned)(UAES_LDS_ROW));
         if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL((k_ccm<NR, true>), dim3(1), dim3(64), UAES_LDS_ROW, st, *ek, *tb, iv, c,
+        hipLaunchKernelGGL((k_ccm<NR, true>), dim3(p.grid), dim3(p.steps), UAES_LDS_ROW, st, *ek, *tb, iv, c,
                            (const unsigned char *)aad, (u64)aad_len, (const unsigned char *)in, (u64)len,
                            (unsigned char *)out, (unsigned char *)tag_io, status, tag_len);
     } else {
         e = uaesk_want_lds((const void *)k_ccm<NR, false>, (unsigned)(UAES_LDS_ROW));
         if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL((k_ccm<NR, false>), dim3(1), dim3(64), UAES_LDS_ROW, st, *ek, *tb, iv, c,
+        hipLaunchKernelGGL((k_ccm<NR, false>), dim3(p.grid), dim3(p.steps), UAES_LDS_ROW, st, *ek, *tb, iv, c,
                            (const unsigned char *)aad, (u64)aad_len, (const unsigned char *)in, (u64)len,
                            (unsigned char *)out, (unsigned char *)tag_io, status, tag_len);
     }
@@ -386,23 +415,23 @@ extern "C" int uaesk_ccm(void *stream, const uaesk_tables *tb, int nr, const uae
     }
     const u32 tl = (u32)tag_len;
     int rc;
-    if (len <= CCM_FUSED_MAX) {
-        /* a short message (CCM's usual diet): ONE launch, the MAC chain and the counter blocks share the wave
-         * (ccm_text); its chain step is a third longer than the plain MAC's, so longer texts keep the two kernels */
-        DISPATCH_NR(nr, rc = (launch_ccm<NR>(S(stream), tb, ek, iv, c, decrypt, aad, aad_len, in, len, out,
+    uaes_plan p;
+    plan_mac(UAES_WHAT_CCM, len, &p);
+    if (p.arrangement == UAES_CCM_FUSED) {
+        DISPATCH_NR(nr, rc = (launch_ccm<NR>(S(stream), p, tb, ek, iv, c, decrypt, aad, aad_len, in, len, out,
                                              decrypt ? (void *)((unsigned char *)in + len) : (void *)((unsigned char *)out + len),
                                              status, tl)));
         return rc;
     }
     if (!decrypt) {
-        DISPATCH_NR(nr, rc = (launch_ccm_tag<NR>(S(stream), tb, ek, iv, aad, aad_len, in, len, 0,
+        DISPATCH_NR(nr, rc = (launch_ccm_tag<NR>(S(stream), p, tb, ek, iv, aad, aad_len, in, len, 0,
                                                  (unsigned char *)out + len, nullptr, tl)));
         if (rc) return rc;
         return uaesk_ctr_xcrypt(stream, tb, nr, ek, &c, in, out, len, nullptr);
     }
     rc = uaesk_ctr_xcrypt(stream, tb, nr, ek, &c, in, out, len, nullptr);
     if (rc) return rc;
-    DISPATCH_NR(nr, rc = (launch_ccm_tag<NR>(S(stream), tb, ek, iv, aad, aad_len, out, len, 1,
+    DISPATCH_NR(nr, rc = (launch_ccm_tag<NR>(S(stream), p, tb, ek, iv, aad, aad_len, out, len, 1,
                                              (unsigned char *)in + len, status, tl)));
     return rc;
 }

@@ -41,9 +41,21 @@
  *   S2V   s2v.small             k_s2v_small (Y || lead blocks, then CTR)            (1)    text <= UAES_EAX_SIV_SMALL_MAX
  *         s2v.long              k_s2v_macs and CTR (k_ctr*), in either order        (2)    beyond
  *         s2v.batch             k_s2v_batch (sixteen lanes per record)              (1)    uaes_siv_*_batch
+ *   CBC   chain.serial          k_chain_serial (one wave walks the chain)           (1)    CBC encrypt, CFB encrypt, OFB: any length
+ *   CFB   fbdec.single          k_fb_dec<U=1> (the CS3 pair / CFB tail: one lane)   (1)    CBC / CFB decrypt, < half the CUs' worth of
+ *   OFB                                                                                    4-block tiles (<= 8 MiB on 256 CUs)
+ *         fbdec.tiled           k_fb_dec<U=4>                                       (1)    CBC / CFB decrypt beyond
+ *   CMAC  chain.serial          k_cmac (one wave)                                   (1)    any length
+ *   CCM   ccm.fused             k_ccm (MAC rows and keystream rows share the wave)  (1)    text <= UAES_CCM_FUSED_MAX (256 B)
+ *         ccm.split             k_ccm_tag and CTR (k_ctr*), decrypt: CTR first      (2+)   beyond
+ *   batch batch.row             k_chain_batch_row (sixteen lanes per message;       (1)    uaes_cbc_encrypt_batch / uaes_cmac_batch,
+ *                               256-thread workgroups while they fill <= half the CUs)     <= UAES_BATCH_ROW_MAX messages (81 919)
+ *         batch.lane            k_chain_batch (one lane per message)                (1)    more messages
  * The Poly1305 rows have a planner of their own (uaesk_plan_poly1305, uaes_poly1305.hip) and ids outside enum
  * uaes_arrangement (uaes_debug_plan_poly1305 names them); a larger message never goes back to a smaller row.
- * So do the EAX and SIV (RFC 5297) rows (uaesk_plan_eax_siv, uaes_eax_siv.hip; uaes_debug_plan_eax_siv).
+ * So do the EAX and SIV (RFC 5297) rows (uaesk_plan_eax_siv, uaes_eax_siv.hip; uaes_debug_plan_eax_siv), and the
+ * CBC / CFB / OFB / CMAC / CCM / batch rows (uaesk_plan_chain, uaes_chain.hip, and uaesk_plan_mac, uaes_mac.hip;
+ * uaes_debug_plan_chain); tests/test_gpu_chains.py derives its sizes and message counts from them.
  */
 #ifndef UAES_PLAN_H
 #define UAES_PLAN_H
@@ -124,6 +136,24 @@ const char *uaesk_poly1305_arrangement_name(int id);
 enum uaes_eax_siv_arrangement { UAES_EAX_SMALL = 0, UAES_EAX_LONG, UAES_EAX_BATCH, UAES_S2V_SMALL, UAES_S2V_LONG, UAES_S2V_BATCH };
 int uaesk_plan_eax_siv(int siv, int dir, size_t len, size_t nmsg, uaes_plan *p);
 const char *uaesk_eax_siv_arrangement_name(int id);
+
+/* The feedback modes, the CBC-MAC modes and the batches of chains.  what = enum uaes_chain_what; dir: 0 encrypt (or
+ * the MAC), 1 decrypt; a = bytes of text (batches: bytes per message), b = messages of a batch (other rows ignore it).
+ * launches = kernels the call enqueues (ccm.split: k_ccm_tag plus what the CTR planner answers for a text of a bytes
+ * whose counter does not carry into bits 40..47); grid = workgroups of the main kernel, steps = its threads per
+ * workgroup; every launcher of the two files takes its launch shape from these answers.  uaesk_plan_chain
+ * (uaes_chain.hip) answers for CBC / CFB / OFB and the two batches, uaesk_plan_mac (uaes_mac.hip) for CMAC and CCM
+ * (the launchers use its static core, which does not ask the CTR planner); either returns a HIP error code for a `what` of the other's or arguments that make
+ * no sense (CBC with stealing below 16 bytes, a batched CBC message that is not whole blocks). */
+#define UAES_CCM_FUSED_MAX ((size_t)256)
+#define UAES_BATCH_ROW_MAX ((size_t)81919)
+enum uaes_chain_what { UAES_WHAT_CBC = 0, UAES_WHAT_CFB, UAES_WHAT_OFB, UAES_WHAT_CMAC, UAES_WHAT_CCM, UAES_WHAT_CBC_BATCH,
+                       UAES_WHAT_CMAC_BATCH, UAES_WHAT_CBC_NOCTS, UAES_WHAT_COUNT };
+enum uaes_chain_arrangement { UAES_CHAIN_SERIAL = 0, UAES_FBDEC_SINGLE, UAES_FBDEC_TILED, UAES_CCM_FUSED, UAES_CCM_SPLIT,
+                              UAES_BATCH_ROW, UAES_BATCH_LANE };
+int uaesk_plan_chain(int what, int dir, size_t a, size_t b, uaes_plan *p);
+int uaesk_plan_mac(int what, int dir, size_t a, uaes_plan *p);
+const char *uaesk_chain_arrangement_name(int id);
 
 #ifdef __cplusplus
 }

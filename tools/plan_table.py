@@ -57,3 +57,11 @@ print("EAX / SIV (RFC 5297): one launch up to UAES_EAX_SIV_SMALL_MAX = %d bytes 
 walk("EAX encrypt", lambda n: uaes.eax_siv_plan(False, n)[:2] + (0, 0), 0, 64 * MIB)
 walk("EAX decrypt", lambda n: uaes.eax_siv_plan(False, n, decrypt=True)[:2] + (0, 0), 0, 64 * MIB)
 walk("SIV (RFC 5297)", lambda n: uaes.eax_siv_plan(True, n)[:2] + (0, 0), 0, 64 * MIB)
+for what in ("cbc", "cfb", "cbc_nocts"):
+    walk("%s decrypt" % what.upper(), lambda n: uaes.chain_plan(what, max(n, 16), decrypt=True)[:2] + (0, 0), 16, 64 * MIB)
+walk("CBC / CFB encrypt, OFB, CMAC", lambda n: uaes.chain_plan("cbc", max(n, 16))[:2] + (0, 0), 16, 64 * MIB)
+walk("CCM", lambda n: uaes.chain_plan("ccm", n)[:2] + (0, 0), 0, 64 * MIB, 1)
+for what in ("cbc_batch", "cmac_batch"):
+    walk("%s, k messages of 1 KiB (positions/thread: threads per workgroup)" % what,
+         lambda k: uaes.chain_plan(what, 1024, max(k, 1))[:2] + (0, uaes.chain_plan(what, 1024, max(k, 1))[3]), 1, 1 << 20, 1,
+         lambda k: "%9d msgs (%9.3f MiB)" % (k, k * 1024 / MIB))
