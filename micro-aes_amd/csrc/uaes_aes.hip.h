@@ -30,6 +30,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "uaes_device.h"
+#include "uaes_launch.hip.h"
 
 typedef uint32_t u32;
 typedef uint64_t u64;
@@ -52,27 +53,10 @@ __device__ __forceinline__ u32 lds_word(u32 byte_addr)
     return *(lds_cu32 *)(uintptr_t)byte_addr;
 }
 
-/* ---- completion ticket riding on a kernel (uaes_device.h: uaesk_done) ----------------------------------------
+/* ---- completion ticket riding on a kernel (uaes_device.h: uaesk_done; host side: uaes_launch.hip.h) ------------
  * EVERY thread of EVERY workgroup must call this as its last action: the workgroup meets, thread 0 releases the
  * workgroup's stores to system scope and counts the workgroup in, and the last one to arrive releases the ticket
  * number to the pinned host word (the classic last-block pattern; one workgroup: no counting).               */
-uaesk_done uaesk_ticket_take();                     /* the calling host thread's armed ticket (cleared), uaes_kernels.hip */
-void uaesk_ticket_unused();
-unsigned *uaesk_done_word_take();                    /* the armed zero-between-calls word (cleared), uaes_kernels.hip */
-bool uaesk_gcm_fold_on();                             /* UAES_GCM_FOLD is not 0 (uaes_kernels.hip) */
-hipError_t uaesk_want_lds(const void *kern, unsigned bytes);   /* dynamic-LDS attribute, set once per (kernel, device) */
-
-/* a multi-launch routine takes the ticket at its entry, so that the single-launch building blocks it calls do not
- * pick it up in the middle of the sequence, and hands it to the one path that is a single launch (use()); if no
- * such path was taken the host layer is told so (uaesk_ticket_disarm() = 1) and sends k_ticket itself          */
-struct TicketScope {
-    uaesk_done d;
-    bool used;
-    TicketScope() : d(uaesk_ticket_take()), used(false) {}
-    ~TicketScope() { if (d.flag && !used) uaesk_ticket_unused(); }
-    const uaesk_done &use() { used = true; return d; }
-};
-
 __device__ __forceinline__ void ticket_release(const uaesk_done &d)
 {
     if (!d.flag) return;                             /* kernel argument: uniform */

@@ -26,7 +26,6 @@
 #include "uaes_plan.h"
 
 #define UAES_U 4
-static inline hipStream_t S(void *s) { return (hipStream_t)s; }
 
 /* ------------------------------------------------------------------------ */
 /* serial directions: one wave, a quad of lanes per block encryption          */
@@ -453,33 +452,19 @@ __global__ __launch_bounds__(UAES_WG) void k_chain_batch_row(uaesk_rk rk, uaesk_
 /* ------------------------------------------------------------------------ */
 /* launchers                                                                  */
 /* ------------------------------------------------------------------------ */
-#define DISPATCH_NR(nr, CALL)                         \
-    switch (nr) {                                     \
-    case 10: { constexpr int NR = 10; CALL; } break;  \
-    case 12: { constexpr int NR = 12; CALL; } break;  \
-    case 14: { constexpr int NR = 14; CALL; } break;  \
-    default: return (int)hipErrorInvalidValue;        \
-    }
-
-static unsigned cu_count()
-{
-    static int cus = 0;
-    if (!cus) uaesk_device_info(&cus, nullptr);
-    return cus > 0 ? (unsigned)cus : 256u;
-}
-
 /* ---- the plan (uaes_plan.h): every size threshold of this file ---------------------------------------------------- */
 /* the parallel decrypt of n blocks: short texts take one block per lane so that up to four times as many CUs take
  * part; the grid is capped at the CU count and the kernel strides beyond it */
 static void plan_fb_dec(u64 n, uaes_plan *p)
 {
+    const unsigned cus = uaesk_cus_or_256();
     const u64 wgs4 = (n + (u64)UAES_WG * UAES_U - 1) / ((u64)UAES_WG * UAES_U);
-    const unsigned u = wgs4 * 2 <= cu_count() ? 1u : (unsigned)UAES_U;
+    const unsigned u = wgs4 * 2 <= cus ? 1u : (unsigned)UAES_U;
     u64 want = (n + (u64)UAES_WG * u - 1) / ((u64)UAES_WG * u);
     if (!want) want = 1;
     p->arrangement = u == 1 ? UAES_FBDEC_SINGLE : UAES_FBDEC_TILED;
     p->launches = 1;
-    p->grid = (unsigned)(want < cu_count() ? want : cu_count());
+    p->grid = (unsigned)(want < cus ? want : cus);
     p->steps = UAES_WG;
 }
 
@@ -488,18 +473,19 @@ static void plan_fb_dec(u64 n, uaes_plan *p)
  * so that they spread over the CUs.  Either grid is capped at the CU count and the kernels stride beyond it. */
 static void plan_batch(u64 nmsg, uaes_plan *p)
 {
+    const unsigned cus = uaesk_cus_or_256();
     p->launches = 1;
     if (nmsg <= (u64)UAES_BATCH_ROW_MAX) {
-        const unsigned wg = (nmsg + 63) / 64 * 2 <= cu_count() ? 256u : UAES_WG;
+        const unsigned wg = (nmsg + 63) / 64 * 2 <= cus ? 256u : UAES_WG;
         const u64 want = (nmsg + wg / 16 - 1) / (wg / 16);
         p->arrangement = UAES_BATCH_ROW;
-        p->grid = (unsigned)(want < cu_count() ? (want ? want : 1) : cu_count());
+        p->grid = (unsigned)(want < cus ? (want ? want : 1) : cus);
         p->steps = wg;
         return;
     }
     const u64 want = (nmsg + UAES_WG - 1) / UAES_WG;
     p->arrangement = UAES_BATCH_LANE;
-    p->grid = (unsigned)(want < cu_count() ? want : cu_count());
+    p->grid = (unsigned)(want < cus ? want : cus);
     p->steps = UAES_WG;
 }
 
@@ -573,12 +559,7 @@ template <int NR, bool CFB, int U>
 static int launch_fb_dec_u(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *k, uint4 iv,
                            const void *in, void *out, u64 n, u32 rem, u32 cts_r, unsigned grid)
 {
-    const unsigned lds = CFB ? UAES_LDS_ENC : UAES_LDS_DEC;
-    hipError_t e = uaesk_want_lds((const void *)k_fb_dec<NR, CFB, U>, (unsigned)(lds));
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((k_fb_dec<NR, CFB, U>), dim3(grid), dim3(UAES_WG), lds, st, *k, *tb, iv,
-                       (const uint4 *)in, (uint4 *)out, n, rem, cts_r);
-    return (int)hipGetLastError();
+    return uaesk_launch(k_fb_dec<NR, CFB, U>, grid, UAES_WG, CFB ? UAES_LDS_ENC : UAES_LDS_DEC, st, *k, *tb, iv, in, out, n, rem, cts_r);
 }
 
 template <int NR, bool CFB>
@@ -595,14 +576,9 @@ template <int NR, int OP>
 static int launch_serial(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *k, uint4 iv,
                          const void *in, void *out, u64 len, const uint4 *iv_dev = nullptr, u32 aux = 0)
 {
-    const unsigned lds = UAES_LDS_ROW;
     uaes_plan p;
     plan_serial(&p);
-    hipError_t e = uaesk_want_lds((const void *)k_chain_serial<NR, OP>, (unsigned)(lds));
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((k_chain_serial<NR, OP>), dim3(p.grid), dim3(p.steps), lds, st, *k, *tb, iv, iv_dev,
-                       (const unsigned char *)in, (unsigned char *)out, len, aux);
-    return (int)hipGetLastError();
+    return uaesk_launch(k_chain_serial<NR, OP>, p.grid, p.steps, UAES_LDS_ROW, st, *k, *tb, iv, iv_dev, in, out, len, aux);
 }
 
 /* the arrangement, the workgroup shape and the grid are plan_batch's */
@@ -614,23 +590,11 @@ static int launch_batch(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *
     plan_batch(nmsg, &p);
     if (p.arrangement == UAES_BATCH_ROW) {
         const bool a4 = ((((uintptr_t)in) | ((uintptr_t)out)) & 3u) == 0 && msg_bytes % 4 == 0;
-        hipError_t e;
-        if (a4) {
-            if ((e = uaesk_want_lds((const void *)k_chain_batch_row<NR, MAC, true>, (unsigned)(UAES_LDS_ROW4))) != hipSuccess) return (int)e;
-            hipLaunchKernelGGL((k_chain_batch_row<NR, MAC, true>), dim3(p.grid), dim3(p.steps), UAES_LDS_ROW4, st, *k, *tb,
-                               (const uint4 *)ivs, nmsg, msg_bytes, (const unsigned char *)in, (unsigned char *)out);
-        } else {
-            if ((e = uaesk_want_lds((const void *)k_chain_batch_row<NR, MAC, false>, (unsigned)(UAES_LDS_ROW4))) != hipSuccess) return (int)e;
-            hipLaunchKernelGGL((k_chain_batch_row<NR, MAC, false>), dim3(p.grid), dim3(p.steps), UAES_LDS_ROW4, st, *k, *tb,
-                               (const uint4 *)ivs, nmsg, msg_bytes, (const unsigned char *)in, (unsigned char *)out);
-        }
-        return (int)hipGetLastError();
+        return with_bool(a4, [&](auto A4) {
+            return uaesk_launch(k_chain_batch_row<NR, MAC, decltype(A4)::value>, p.grid, p.steps, UAES_LDS_ROW4, st, *k, *tb, ivs,
+                                nmsg, msg_bytes, in, out); });
     }
-    hipError_t e = uaesk_want_lds((const void *)k_chain_batch<NR, MAC>, (unsigned)(UAES_LDS_ENC));
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((k_chain_batch<NR, MAC>), dim3(p.grid), dim3(p.steps), UAES_LDS_ENC, st, *k, *tb,
-                       (const uint4 *)ivs, nmsg, msg_bytes, (const unsigned char *)in, (unsigned char *)out);
-    return (int)hipGetLastError();
+    return uaesk_launch(k_chain_batch<NR, MAC>, p.grid, p.steps, UAES_LDS_ENC, st, *k, *tb, ivs, nmsg, msg_bytes, in, out);
 }
 
 /* mac == 0: CBC encrypt of nmsg messages of msg_bytes (a multiple of 16, >= 16) each, IVs at ivs (device);
@@ -640,8 +604,9 @@ extern "C" int uaesk_chain_batch(void *stream, const uaesk_tables *tb, int nr, c
 {
     if (nmsg == 0) return 0;
     if (!mac && (msg_bytes < 16 || msg_bytes % 16)) return (int)hipErrorInvalidValue;
-    if (mac) { DISPATCH_NR(nr, return (launch_batch<NR, true>(S(stream), tb, ek, nullptr, nmsg, msg_bytes, in, out))); }
-    else     { DISPATCH_NR(nr, return (launch_batch<NR, false>(S(stream), tb, ek, ivs, nmsg, msg_bytes, in, out))); }
+    if (mac) ivs = nullptr;
+    DISPATCH_NR(nr, return with_bool(mac, [&](auto MAC) {
+        return launch_batch<NR, decltype(MAC)::value>(S(stream), tb, ek, ivs, nmsg, msg_bytes, in, out); }));
     return 0;
 }
 

@@ -256,9 +256,7 @@ __device__ __forceinline__ void ctr_shared_loop(const uaesk_rk &rk, const uaesk_
              * registers of the second store: ~1 % of the blocks came out as the selects' zeros, different ones every run,
              * profiles/r04_buffer_store_hazard.log).  The ISA manuals list that hazard -- store data of more than 64 bits,
              * then a VALU write of the data registers: 1 wait state -- with the exception "not if SOFFSET is an SGPR",
-             * and the compiler's hazard recogniser follows them; for global_store it always inserts the wait state.
-             * (The store path that reproduces it, and the timing-only builds without loads / stores, are a patch for the
-             * measuring tools: tools/experiments/ctr_measurement_switches.patch.)                                      */
+             * and the compiler's hazard recogniser follows them; for global_store it always inserts the wait state.   */
             (out + (((g0 + 4u * u) << 8) - c0))[lane_blk] = ct[u];
         }
         if (FOLD::of_input) fold(d_cur[0], d_cur[1]); else fold(ct[0], ct[1]);

@@ -44,8 +44,6 @@ typedef struct {
     uint32_t le32, w2, w3;
 } uaesk_ctr;
 
-int uaesk_device_info(int *cu_count, int *lds_bytes);
-
 /* ECB: nfull whole blocks, plus (enc only) one padded tail block built from the
  * `rem` trailing bytes (reference N1, micro_aes.c:648-651).  padding = the
  * reference's AES_PADDING (padBlock, micro_aes.c:610-621): 0 zeros and only when

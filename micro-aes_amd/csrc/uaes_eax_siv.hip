@@ -28,8 +28,6 @@
 #include "uaes_device.h"
 #include "uaes_plan.h"
 
-static inline hipStream_t S(void *s) { return (hipStream_t)s; }
-
 /* LDS behind the row tables (row_fill_tables: keys at 64 KiB; row4_fill_tables: keys at 128 KiB): a second key
  * schedule (SIV's K_ctr) and four exchange blocks between the waves */
 #define ER_KEY2   (65536u + 256u)
@@ -605,21 +603,6 @@ __global__ __launch_bounds__(UAES_WG) void k_s2v_batch(uaesk_rk rk, uaesk_rk rk2
 }
 
 /* ---- launchers ---------------------------------------------------------------------------------------------------- */
-#define DISPATCH_NR(nr, CALL)                         \
-    switch (nr) {                                     \
-    case 10: { constexpr int NR = 10; CALL; } break;  \
-    case 12: { constexpr int NR = 12; CALL; } break;  \
-    case 14: { constexpr int NR = 14; CALL; } break;  \
-    default: return (int)hipErrorInvalidValue;        \
-    }
-
-static unsigned cu_count()
-{
-    static int cus = 0;
-    if (!cus) uaesk_device_info(&cus, nullptr);
-    return cus > 0 ? (unsigned)cus : 256u;
-}
-
 static uint4 uint4_of(const uint8_t *b)
 {
     uint4 v = make_uint4(0, 0, 0, 0);
@@ -632,18 +615,9 @@ static int launch_eax_small(hipStream_t st, const uaesk_tables *tb, const uaesk_
                             const void *nonce, size_t nonce_len, const void *aad, size_t aad_len,
                             const void *in, size_t len, void *out, void *tag_io, unsigned tag_len, int *status)
 {
-    const void *k = decrypt ? (const void *)k_eax_small<NR, true> : (const void *)k_eax_small<NR, false>;
-    hipError_t e = uaesk_want_lds(k, E4_LDS);
-    if (e != hipSuccess) return (int)e;
-    if (decrypt)
-        hipLaunchKernelGGL((k_eax_small<NR, true>), dim3(1), dim3(SMALL_WG), E4_LDS, st, *ek, *tb,
-                           (const unsigned char *)nonce, (u64)nonce_len, (const unsigned char *)aad, (u64)aad_len,
-                           (const unsigned char *)in, (u64)len, (unsigned char *)out, (unsigned char *)tag_io, tag_len, status);
-    else
-        hipLaunchKernelGGL((k_eax_small<NR, false>), dim3(1), dim3(SMALL_WG), E4_LDS, st, *ek, *tb,
-                           (const unsigned char *)nonce, (u64)nonce_len, (const unsigned char *)aad, (u64)aad_len,
-                           (const unsigned char *)in, (u64)len, (unsigned char *)out, (unsigned char *)tag_io, tag_len, status);
-    return (int)hipGetLastError();
+    return with_bool(decrypt, [&](auto DEC) {
+        return uaesk_launch(k_eax_small<NR, decltype(DEC)::value>, 1, SMALL_WG, E4_LDS, st, *ek, *tb, nonce, nonce_len, aad, aad_len,
+                            in, len, out, tag_io, tag_len, status); });
 }
 
 extern "C" int uaesk_eax_small(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, int decrypt,
@@ -661,13 +635,9 @@ static int launch_eax_macs(hipStream_t st, const uaesk_tables *tb, const uaesk_r
                            const void *nonce, size_t nonce_len, const void *aad, size_t aad_len,
                            const void *ct, size_t len, void *tag_io, unsigned tag_len, void *res)
 {
-    hipError_t e = uaesk_want_lds((const void *)k_eax_macs<NR>, ER_LDS);
-    if (e != hipSuccess) return (int)e;
     const unsigned waves = mode == 0 ? 2u : mode == 1 ? 3u : 1u;
-    hipLaunchKernelGGL((k_eax_macs<NR>), dim3(1), dim3(64 * waves), ER_LDS, st, *ek, *tb, mode,
-                       (const unsigned char *)nonce, (u64)nonce_len, (const unsigned char *)aad, (u64)aad_len,
-                       (const unsigned char *)ct, (u64)len, (unsigned char *)tag_io, tag_len, (unsigned char *)res);
-    return (int)hipGetLastError();
+    return uaesk_launch(k_eax_macs<NR>, 1, 64 * waves, ER_LDS, st, *ek, *tb, mode, nonce, nonce_len, aad, aad_len, ct, len, tag_io,
+                        tag_len, res);
 }
 
 extern "C" int uaesk_eax_macs(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, int mode,
@@ -685,18 +655,9 @@ static int launch_s2v_small(hipStream_t st, const uaesk_tables *tb, const uaesk_
                             uint4 iv, const void *aad, size_t aad_len, const void *in, size_t len, void *out,
                             void *iv_out, int *status)
 {
-    const void *k = decrypt ? (const void *)k_s2v_small<NR, true> : (const void *)k_s2v_small<NR, false>;
-    hipError_t e = uaesk_want_lds(k, E4_LDS);
-    if (e != hipSuccess) return (int)e;
-    if (decrypt)
-        hipLaunchKernelGGL((k_s2v_small<NR, true>), dim3(1), dim3(SMALL_WG), E4_LDS, st, *ek, *ek2, *tb, iv,
-                           (const unsigned char *)aad, (u64)aad_len, (const unsigned char *)in, (u64)len,
-                           (unsigned char *)out, (unsigned char *)iv_out, status);
-    else
-        hipLaunchKernelGGL((k_s2v_small<NR, false>), dim3(1), dim3(SMALL_WG), E4_LDS, st, *ek, *ek2, *tb, iv,
-                           (const unsigned char *)aad, (u64)aad_len, (const unsigned char *)in, (u64)len,
-                           (unsigned char *)out, (unsigned char *)iv_out, status);
-    return (int)hipGetLastError();
+    return with_bool(decrypt, [&](auto DEC) {
+        return uaesk_launch(k_s2v_small<NR, decltype(DEC)::value>, 1, SMALL_WG, E4_LDS, st, *ek, *ek2, *tb, iv, aad, aad_len, in, len,
+                            out, iv_out, status); });
 }
 
 extern "C" int uaesk_s2v_small(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek_s2v,
@@ -713,16 +674,8 @@ template <int NR>
 static int launch_s2v_macs(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *ek, int decrypt, uint4 iv,
                            const void *aad, size_t aad_len, const void *text, size_t len, void *res)
 {
-    const void *k = decrypt ? (const void *)k_s2v_macs<NR, true> : (const void *)k_s2v_macs<NR, false>;
-    hipError_t e = uaesk_want_lds(k, ER_LDS);
-    if (e != hipSuccess) return (int)e;
-    if (decrypt)
-        hipLaunchKernelGGL((k_s2v_macs<NR, true>), dim3(1), dim3(128), ER_LDS, st, *ek, *tb, iv,
-                           (const unsigned char *)aad, (u64)aad_len, (const unsigned char *)text, (u64)len, (unsigned char *)res);
-    else
-        hipLaunchKernelGGL((k_s2v_macs<NR, false>), dim3(1), dim3(128), ER_LDS, st, *ek, *tb, iv,
-                           (const unsigned char *)aad, (u64)aad_len, (const unsigned char *)text, (u64)len, (unsigned char *)res);
-    return (int)hipGetLastError();
+    return with_bool(decrypt, [&](auto DEC) {
+        return uaesk_launch(k_s2v_macs<NR, decltype(DEC)::value>, 1, 128, ER_LDS, st, *ek, *tb, iv, aad, aad_len, text, len, res); });
 }
 
 extern "C" int uaesk_s2v_macs(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek_s2v, int decrypt,
@@ -736,25 +689,10 @@ extern "C" int uaesk_s2v_macs(void *stream, const uaesk_tables *tb, int nr, cons
 /* as launch_batch (uaes_chain.hip): 64 records per 16-wave workgroup, 4-wave workgroups for few records */
 static void batch_shape(u64 nmsg, unsigned *grid, unsigned *wg)
 {
-    *wg = (nmsg + 63) / 64 * 2 <= cu_count() ? 256u : UAES_WG;
+    const unsigned cus = uaesk_cus_or_256();
+    *wg = (nmsg + 63) / 64 * 2 <= cus ? 256u : UAES_WG;
     const u64 want = (nmsg + *wg / 16 - 1) / (*wg / 16);
-    *grid = (unsigned)(want < cu_count() ? want : cu_count());
-}
-
-template <int NR, bool DEC, bool A4>
-static int launch_eax_batch_t(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *ek, const void *nonces,
-                              size_t nonce_len, const void *aad, size_t aad_bytes, size_t nmsg, size_t msg_bytes,
-                              const void *in, void *out, void *tags, void *verdicts, int *bad)
-{
-    hipError_t e = uaesk_want_lds((const void *)k_eax_batch<NR, DEC, A4>, E4_LDS);
-    if (e != hipSuccess) return (int)e;
-    unsigned grid, wg;
-    batch_shape(nmsg, &grid, &wg);
-    hipLaunchKernelGGL((k_eax_batch<NR, DEC, A4>), dim3(grid), dim3(wg), E4_LDS, st, *ek, *tb,
-                       (const unsigned char *)nonces, (u64)nonce_len, (const unsigned char *)aad, (u64)aad_bytes,
-                       (u64)nmsg, (u64)msg_bytes, (const unsigned char *)in, (unsigned char *)out,
-                       (unsigned char *)tags, (unsigned char *)verdicts, bad);
-    return (int)hipGetLastError();
+    *grid = (unsigned)(want < cus ? want : cus);
 }
 
 template <int NR>
@@ -763,12 +701,11 @@ static int launch_eax_batch(hipStream_t st, const uaesk_tables *tb, const uaesk_
                             const void *in, void *out, void *tags, void *verdicts, int *bad)
 {
     const bool a4 = ((((uintptr_t)in) | ((uintptr_t)out)) & 3u) == 0 && msg_bytes % 4 == 0;
-#define EAXB(D, A) return launch_eax_batch_t<NR, D, A>(st, tb, ek, nonces, nonce_len, aad, aad_bytes, nmsg, msg_bytes, \
-                                                       in, out, tags, verdicts, bad)
-    if (decrypt) { if (a4) EAXB(true, true); EAXB(true, false); }
-    if (a4) EAXB(false, true);
-    EAXB(false, false);
-#undef EAXB
+    unsigned grid, wg;
+    batch_shape(nmsg, &grid, &wg);
+    return with_bool(decrypt, [&](auto DEC) { return with_bool(a4, [&](auto A4) {
+        return uaesk_launch(k_eax_batch<NR, decltype(DEC)::value, decltype(A4)::value>, grid, wg, E4_LDS, st, *ek, *tb, nonces,
+                            nonce_len, aad, aad_bytes, nmsg, msg_bytes, in, out, tags, verdicts, bad); }); });
 }
 
 extern "C" int uaesk_eax_batch(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, int decrypt,
@@ -781,33 +718,17 @@ extern "C" int uaesk_eax_batch(void *stream, const uaesk_tables *tb, int nr, con
     return 0;
 }
 
-template <int NR, bool DEC, bool A4>
-static int launch_s2v_batch_t(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *ek, const uaesk_rk *ek2, int wipe,
-                              const void *aad, size_t aad_bytes, size_t nmsg, size_t msg_bytes,
-                              const void *in, void *out, void *ivs, void *verdicts, int *bad)
-{
-    hipError_t e = uaesk_want_lds((const void *)k_s2v_batch<NR, DEC, A4>, E4_LDS);
-    if (e != hipSuccess) return (int)e;
-    unsigned grid, wg;
-    batch_shape(nmsg, &grid, &wg);
-    hipLaunchKernelGGL((k_s2v_batch<NR, DEC, A4>), dim3(grid), dim3(wg), E4_LDS, st, *ek, *ek2, *tb, wipe,
-                       (const unsigned char *)aad, (u64)aad_bytes, (u64)nmsg, (u64)msg_bytes,
-                       (const unsigned char *)in, (unsigned char *)out, (unsigned char *)ivs, (unsigned char *)verdicts, bad);
-    return (int)hipGetLastError();
-}
-
 template <int NR>
 static int launch_s2v_batch(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *ek, const uaesk_rk *ek2, int decrypt,
                             int wipe, const void *aad, size_t aad_bytes, size_t nmsg, size_t msg_bytes,
                             const void *in, void *out, void *ivs, void *verdicts, int *bad)
 {
     const bool a4 = ((((uintptr_t)in) | ((uintptr_t)out)) & 3u) == 0 && msg_bytes % 4 == 0;
-#define S2VB(D, A) return launch_s2v_batch_t<NR, D, A>(st, tb, ek, ek2, wipe, aad, aad_bytes, nmsg, msg_bytes, \
-                                                       in, out, ivs, verdicts, bad)
-    if (decrypt) { if (a4) S2VB(true, true); S2VB(true, false); }
-    if (a4) S2VB(false, true);
-    S2VB(false, false);
-#undef S2VB
+    unsigned grid, wg;
+    batch_shape(nmsg, &grid, &wg);
+    return with_bool(decrypt, [&](auto DEC) { return with_bool(a4, [&](auto A4) {
+        return uaesk_launch(k_s2v_batch<NR, decltype(DEC)::value, decltype(A4)::value>, grid, wg, E4_LDS, st, *ek, *ek2, *tb, wipe,
+                            aad, aad_bytes, nmsg, msg_bytes, in, out, ivs, verdicts, bad); }); });
 }
 
 extern "C" int uaesk_s2v_batch(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek_s2v,

@@ -271,7 +271,6 @@ int get_context(context **out)
                 pthread_cond_init(&c->cv, NULL);
                 c->sync_made = 1;
             }
-            uaesk_device_info(NULL, NULL);
             __atomic_store_n(&c->ready, 1, __ATOMIC_RELEASE);
         }
         pthread_mutex_unlock(&g_init_mu);

@@ -474,29 +474,14 @@ __global__ __launch_bounds__(UAES_WG) void k_gcm_fused(uaesk_rk rk, uaesk_tables
     }
 }
 
-template <int NR, bool DEC>
-static int launch_fused(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *ek, const uaesk_ctr *c,
+static int launch_fused(int nr, bool decrypt, hipStream_t st, const uaesk_tables *tb, const uaesk_rk *ek, const uaesk_ctr *c,
                         const void *in, void *out, unsigned grid, u64 g_lo, u64 stripes, u64 h1, u64 nfull, u32 rem,
                         const GSrc &front, u64 nfront, unsigned char *sc)
 {
-    hipError_t e = uaesk_want_lds((const void *)k_gcm_fused<NR, DEC>, (unsigned)(GF_LDS_TOTAL));
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((k_gcm_fused<NR, DEC>), dim3(grid), dim3(UAES_WG), GF_LDS_TOTAL, st, *ek, *tb, *c,
-                       (const uint4 *)in, (uint4 *)out, g_lo, stripes, h1, nfull, rem, front, nfront, sc);
-    return (int)hipGetLastError();
-}
-
-template <bool DEC>
-static int launch_fused_nr(int nr, hipStream_t st, const uaesk_tables *tb, const uaesk_rk *ek, const uaesk_ctr *c,
-                           const void *in, void *out, unsigned grid, u64 g_lo, u64 stripes, u64 h1, u64 nfull, u32 rem,
-                           const GSrc &front, u64 nfront, unsigned char *sc)
-{
-    switch (nr) {
-    case 10: return launch_fused<10, DEC>(st, tb, ek, c, in, out, grid, g_lo, stripes, h1, nfull, rem, front, nfront, sc);
-    case 12: return launch_fused<12, DEC>(st, tb, ek, c, in, out, grid, g_lo, stripes, h1, nfull, rem, front, nfront, sc);
-    case 14: return launch_fused<14, DEC>(st, tb, ek, c, in, out, grid, g_lo, stripes, h1, nfull, rem, front, nfront, sc);
-    default: return (int)hipErrorInvalidValue;
-    }
+    DISPATCH_NR(nr, return with_bool(decrypt, [&](auto DEC) {
+        return uaesk_launch(k_gcm_fused<NR, decltype(DEC)::value>, grid, UAES_WG, GF_LDS_TOTAL, st, *ek, *tb, *c, in, out, g_lo,
+                            stripes, h1, nfull, rem, front, nfront, sc); }));
+    return 0;
 }
 
 /* one-pass decrypt, failed authentication: the plaintext written before the tag was known is zeroed */
@@ -534,10 +519,7 @@ __global__ __launch_bounds__(64) void k_gcm_ej0(uaesk_rk ek, uaesk_tables tb, ui
 template <int NR>
 static int launch_ej0(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *ek, uint4 j0, unsigned char *sc)
 {
-    hipError_t e = uaesk_want_lds((const void *)k_gcm_ej0<NR>, (unsigned)(UAES_LDS_QUAD));
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((k_gcm_ej0<NR>), dim3(1), dim3(64), UAES_LDS_QUAD, st, *ek, *tb, j0, sc);
-    return (int)hipGetLastError();
+    return uaesk_launch(k_gcm_ej0<NR>, 1, 64, UAES_LDS_QUAD, st, *ek, *tb, j0, sc);
 }
 
 
@@ -680,29 +662,14 @@ __global__ __launch_bounds__(GH_T) void k_gcm_small(uaesk_rk rk, uaesk_tables tb
     ticket_release(done);
 }
 
-template <int NR, bool DEC>
-static int launch_small(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *ek, const uaesk_ctr *c, uint4 j0,
-                        const GSrc &src, const void *in, void *out, const unsigned char *sc,
+static int launch_small(int nr, bool decrypt, hipStream_t st, const uaesk_tables *tb, const uaesk_rk *ek, const uaesk_ctr *c,
+                        uint4 j0, const GSrc &src, const void *in, void *out, const unsigned char *sc,
                         unsigned char *tag_io, int *status, u32 build, const uaesk_done &done)
 {
-    hipError_t e = uaesk_want_lds((const void *)k_gcm_small<NR, DEC>, (unsigned)(GSM_LDS_TOTAL));
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((k_gcm_small<NR, DEC>), dim3(1), dim3(GH_T), GSM_LDS_TOTAL, st, *ek, *tb, *c, j0, src,
-                       (const uint4 *)in, (uint4 *)out, sc, tag_io, status, build, done);
-    return (int)hipGetLastError();
-}
-
-template <bool DEC>
-static int launch_small_nr(int nr, hipStream_t st, const uaesk_tables *tb, const uaesk_rk *ek, const uaesk_ctr *c,
-                           uint4 j0, const GSrc &src, const void *in, void *out, const unsigned char *sc,
-                           unsigned char *tag_io, int *status, u32 build, const uaesk_done &done)
-{
-    switch (nr) {
-    case 10: return launch_small<10, DEC>(st, tb, ek, c, j0, src, in, out, sc, tag_io, status, build, done);
-    case 12: return launch_small<12, DEC>(st, tb, ek, c, j0, src, in, out, sc, tag_io, status, build, done);
-    case 14: return launch_small<14, DEC>(st, tb, ek, c, j0, src, in, out, sc, tag_io, status, build, done);
-    default: return (int)hipErrorInvalidValue;
-    }
+    DISPATCH_NR(nr, return with_bool(decrypt, [&](auto DEC) {
+        return uaesk_launch(k_gcm_small<NR, decltype(DEC)::value>, 1, GH_T, GSM_LDS_TOTAL, st, *ek, *tb, *c, j0, src, in, out, sc,
+                            tag_io, status, build, done); }));
+    return 0;
 }
 
 
@@ -1142,39 +1109,28 @@ static int launch_medium(hipStream_t st, const uaesk_tables *tb, const uaesk_rk 
 {
     /* hash_only: an encryption without text (GMAC): the hash-only chunk workgroups, the tag written by the finisher */
     uint4 *partial = (uint4 *)(sc + GS_ACC1);
-    hipError_t e;
     GmcFin fin;
     memset(&fin, 0, sizeof fin);
     /* with a counter word from the host layer, encryption and the hash-only pass of a decryption are ONE launch */
     /* (as long as the chunk workgroups are one round; see medium_steps about W = the number of CUs) */
-    int cus_f = 0;
-    if (uaesk_device_info(&cus_f, nullptr) != 0) cus_f = 0;
-    const bool fold = done_word != nullptr && decrypt != 2 && (int)W <= cus_f;
+    const bool fold = done_word != nullptr && decrypt != 2 && (int)W <= uaesk_cus();
     if (fold) {
         fin.j0 = j0; fin.done_word = done_word; fin.look_ticks = gcm_look_ticks(); fin.tag_io = tag_io; fin.status = status; fin.mode = decrypt ? 1 : 0;
         fin.ylog = 10u + log2_u32(steps);
         fin.len_aad = src.len_aad; fin.len_ct = src.len_ct;
         if (!decrypt) fin.done = ticket.use();
     }
-#define GMC_LAUNCH(M, F)                                                                                            \
-    do {                                                                                                            \
-        e = uaesk_want_lds((const void *)k_gcm_chunks<NR, M, F>, (unsigned)(GSM_LDS_TOTAL)); \
-        if (e != hipSuccess) return (int)e;                                                                         \
-        hipLaunchKernelGGL((k_gcm_chunks<NR, M, F>), dim3(W + (F ? 1u : 0u)), dim3(GH_T), GSM_LDS_TOTAL, st, *ek, *tb, *c, src, \
-                           (const uint4 *)in, (uint4 *)out, (const unsigned char *)sc, partial, build, steps, fin);  \
-    } while (0)
-    if (fold) {
-        if (decrypt == 0 && !hash_only) GMC_LAUNCH(0, true); else GMC_LAUNCH(1, true);
-        return (int)hipGetLastError();
-    }
-    if (decrypt == 0 && !hash_only) GMC_LAUNCH(0, false); else if (decrypt == 1 || hash_only) GMC_LAUNCH(1, false); else GMC_LAUNCH(2, false);
-#undef GMC_LAUNCH
-    e = uaesk_want_lds((const void *)k_gcm_combine<NR>, (unsigned)(GHFB_LDS));
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((k_gcm_combine<NR>), dim3(1), dim3(GH_T), GHFB_LDS, st, *ek, *tb, j0, (const uint4 *)partial, W,
-                       (const unsigned char *)sc, build, decrypt ? 1 : 0, tag_io, status, 10u + log2_u32(steps),
-                       decrypt == 2 ? (unsigned char *)out : nullptr, (u64)src.ct_len, (u64)src.len_aad, (u64)src.len_ct);
-    return (int)hipGetLastError();
+    /* MODE (k_gcm_chunks) 0: encrypt; 1: hash only; 2: decrypt while hashing.  FOLD: one more workgroup, the finisher */
+    const int mode = decrypt == 0 && !hash_only ? 0 : decrypt == 1 || hash_only ? 1 : 2;
+    auto chunks = [&](auto kern, u32 wgs) {
+        return uaesk_launch(kern, wgs, GH_T, GSM_LDS_TOTAL, st, *ek, *tb, *c, src, in, out, sc, partial, build, steps, fin);
+    };
+    if (fold) return mode == 0 ? chunks(k_gcm_chunks<NR, 0, true>, W + 1u) : chunks(k_gcm_chunks<NR, 1, true>, W + 1u);
+    const int rc = mode == 0 ? chunks(k_gcm_chunks<NR, 0, false>, W) : mode == 1 ? chunks(k_gcm_chunks<NR, 1, false>, W)
+                                                                               : chunks(k_gcm_chunks<NR, 2, false>, W);
+    if (rc) return rc;
+    return uaesk_launch(k_gcm_combine<NR>, 1, GH_T, GHFB_LDS, st, *ek, *tb, j0, partial, W, sc, build, decrypt ? 1 : 0, tag_io, status,
+                        10u + log2_u32(steps), decrypt == 2 ? (unsigned char *)out : nullptr, src.ct_len, src.len_aad, src.len_ct);
 }
 
 
@@ -1204,29 +1160,25 @@ static int run_ghash_levels(hipStream_t st, const GSrc &msg, u64 nv, const GPlan
 {
     GSrc cur = msg;
     u64 n = nv;
-    hipError_t e;
+    int rc;
     if (pl.logA) {
-        e = uaesk_want_lds((const void *)k_ghash_pass, (unsigned)(65536));
-        if (e != hipSuccess) return (int)e;
         const u64 sA = (u64)1 << pl.logA;
-        hipLaunchKernelGGL(k_ghash_pass, dim3((unsigned)(sA / GH_PT)), dim3(GH_PT), 65536, st,
-                           cur, n, (const uint4 *)(scratch + GS_TAB8_A), (uint4 *)(scratch + GS_ACC1));
+        rc = uaesk_launch(k_ghash_pass, (unsigned)(sA / GH_PT), GH_PT, 65536, st, cur, n, (const uint4 *)(scratch + GS_TAB8_A),
+                          (uint4 *)(scratch + GS_ACC1));
+        if (rc) return rc;
         cur.aad = nullptr; cur.aad_len = 0; cur.ct = scratch + GS_ACC1; cur.ct_len = sA * 16; cur.has_len = 0;
         cur.rev = 0;
         n = sA;
         if (pl.needB) {
             const u64 sB = (u64)1 << GH_LOGB;
-            hipLaunchKernelGGL(k_ghash_pass, dim3((unsigned)(sB / GH_PT)), dim3(GH_PT), 65536, st,
-                               cur, n, (const uint4 *)(scratch + GS_TAB8_B), (uint4 *)(scratch + GS_ACC2));
+            rc = uaesk_launch(k_ghash_pass, (unsigned)(sB / GH_PT), GH_PT, 65536, st, cur, n, (const uint4 *)(scratch + GS_TAB8_B),
+                              (uint4 *)(scratch + GS_ACC2));
+            if (rc) return rc;
             cur.ct = scratch + GS_ACC2; cur.ct_len = sB * 16;
             n = sB;
         }
     }
-    e = uaesk_want_lds((const void *)k_ghash_final, (unsigned)(GHF_LDS));
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(k_ghash_final, dim3(1), dim3(GH_T), GHF_LDS, st,
-                       cur, n, (const unsigned char *)scratch, mode, tag_io, status);
-    return (int)hipGetLastError();
+    return uaesk_launch(k_ghash_final, 1, GH_T, GHF_LDS, st, cur, n, scratch, mode, tag_io, status);
 }
 
 extern "C" size_t uaesk_gcm_scratch_bytes(void) { return GS_TOTAL; }
@@ -1237,8 +1189,6 @@ static int launch_setup(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *
                         unsigned char *scratch, const GPlan &pl, u32 h_given, uint4 hval, u32 want_pow64 = 0,
                         u32 logF = 0)
 {
-    hipError_t e = uaesk_want_lds((const void *)k_gcm_setup<NR>, (unsigned)(SETUP_LDS));
-    if (e != hipSuccess) return (int)e;
     /* powers actually needed: the bulk tables, and of the last-levels tables H^1024 / H^64 / H^4 / H
      * only those a message of nv blocks reaches (k_ghash_final skips the empty levels)       */
     u32 maxlog = pl.nv > 1024 ? 10u : pl.nv > 256 ? 8u : pl.nv > 64 ? 6u : pl.nv > 16 ? 4u : pl.nv > 4 ? 2u : 0u;
@@ -1246,9 +1196,8 @@ static int launch_setup(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *
     if (pl.needB && GH_LOGB > maxlog) maxlog = GH_LOGB;
     if (logF > maxlog) maxlog = logF;
     /* with the fused kernel's weights to make: a second workgroup for them (k_gcm_setup: tables_wg / weights_wg) */
-    hipLaunchKernelGGL((k_gcm_setup<NR>), dim3(logF ? 2u : 1u), dim3(UAES_WG), SETUP_LDS, st, *ek, *tb, j0, scratch,
-                       pl.logA, pl.needB, h_given, hval, want_pow64, logF, maxlog);
-    return (int)hipGetLastError();
+    return uaesk_launch(k_gcm_setup<NR>, logF ? 2u : 1u, UAES_WG, SETUP_LDS, st, *ek, *tb, j0, scratch, pl.logA, pl.needB, h_given,
+                        hval, want_pow64, logF, maxlog);
 }
 
 /* J0 of a nonce whose length is not 12 bytes (GCMsetup's first branch, micro_aes.c:1145-1149):
@@ -1291,15 +1240,6 @@ extern "C" int uaesk_gcm_j0(void *stream, const uaesk_tables *tb, int nr, const 
 #define GMC_ONEPASS_MAX_NV  ((u64)1 << 20)
 #define GMC_TWOPHASE_MAX_NV ((u64)1 << 23)
 
-bool uaesk_arr_on(int id);                                       /* uaes_kernels.hip: the switch of uaes_plan.h */
-
-static int plan_cus(void)
-{
-    int cus = 0;
-    if (uaesk_device_info(&cus, nullptr) != 0 || cus <= 0) cus = 256;      /* (no device: planned for an MI355X) */
-    return cus;
-}
-
 static u32 medium_steps(u64 nv, int cus)
 {
     if (cus < 2) return 0;
@@ -1314,7 +1254,7 @@ struct GcmStripes { bool ok; u32 logF; u64 h0, g_lo, n8, h1; int cus; };
 static GcmStripes gcm_stripes(const uaesk_ctr &c, u64 len, u64 ablk)
 {
     GcmStripes g;
-    g.cus = plan_cus();
+    g.cus = (int)uaesk_cus_or_256();
     const u64 Sl = 2048ull * (u64)g.cus;
     g.logF = 0;
     while (((u64)1 << g.logF) < Sl) ++g.logF;
@@ -1412,7 +1352,7 @@ static uaes_plan siv_plan(u64 len, u64 aad_len, bool has_word, bool long_only = 
     uaes_plan p = { UAES_ARR_SIV_LEVELS, 0, 0, 0 };
     const u64 nvh = ((aad_len + 15) >> 4) + ((len + 15) >> 4);
     if (!long_only && nvh + 1 <= GSM_MAXNV && uaesk_arr_on(UAES_ARR_SIV_SMALL)) { p.arrangement = UAES_ARR_SIV_SMALL; p.launches = 1; p.grid = 1; return p; }
-    const u32 steps = medium_steps(nvh, plan_cus());
+    const u32 steps = medium_steps(nvh, (int)uaesk_cus_or_256());
     if (has_word && steps && uaesk_arr_on(UAES_ARR_SIV_CHUNKS)) {
         p.arrangement = UAES_ARR_SIV_CHUNKS; p.launches = 3; p.steps = steps;
         p.grid = (unsigned)((nvh + 1024ull * steps - 1) / (1024ull * steps));
@@ -1477,8 +1417,8 @@ static int gcm_body(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk
         GSrc sm = msg;
         sm.ct = (const unsigned char *)in;     /* the kernel reads the text itself */
         if (decrypt)                               /* (the host layer arms a ticket only with a host-visible status word) */
-            return launch_small_nr<true>(nr, st, tb, ek, &c, j0, sm, in, out, sc, (unsigned char *)in + len, status, build, ticket.use());
-        return launch_small_nr<false>(nr, st, tb, ek, &c, j0, sm, in, out, sc, (unsigned char *)out + len, nullptr, build, ticket.use());
+            return launch_small(nr, true, st, tb, ek, &c, j0, sm, in, out, sc, (unsigned char *)in + len, status, build, ticket.use());
+        return launch_small(nr, false, st, tb, ek, &c, j0, sm, in, out, sc, (unsigned char *)out + len, nullptr, build, ticket.use());
     }
     case UAES_ARR_GCM_CHUNKS:
     case UAES_ARR_GCM_TWOPHASE: {
@@ -1509,9 +1449,7 @@ static int gcm_body(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk
         if (dmode == 1) {
             rc = uaesk_ctr_xcrypt(stream, tb, nr, ek, &c, in, out, len, status);
             if (!rc && two && decrypt == 2) {                    /* the one-pass contract: zeroed on a forgery */
-                hipLaunchKernelGGL(k_wipe_if_failed, dim3((unsigned)sp.cus * 2u), dim3(1024), 0, st, status,
-                                   (unsigned char *)out, (u64)len);
-                rc = (int)hipGetLastError();
+                rc = uaesk_launch(k_wipe_if_failed, (unsigned)sp.cus * 2u, 1024, 0, st, status, out, len);
             }
         }
         return rc;                             /* mode 2: the combine kernel takes a forgery's plaintext back itself */
@@ -1534,13 +1472,13 @@ static int gcm_body(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk
         else       { GCM_NR((launch_setup<NR>(st, tb, ek, j0, sc, plf, 0, z, 0, sp.logF))); }
         if (rc) return rc;
         if (!decrypt) {
-            rc = launch_fused_nr<false>(nr, st, tb, ek, &c, in, out, (unsigned)sp.cus, sp.g_lo, sp.n8, sp.h1, nfull,
+            rc = launch_fused(nr, false, st, tb, ek, &c, in, out, (unsigned)sp.cus, sp.g_lo, sp.n8, sp.h1, nfull,
                                         (u32)(len % 16), front, ablk + sp.h0, sc);
             if (rc) return rc;
             return run_ghash_levels(st, fin, nvf, plf, sc, 0, (unsigned char *)out + len, nullptr);
         }
         /* the fused kernel leaves the tail alone (h1 = nfull, no ragged bytes) */
-        rc = launch_fused_nr<true>(nr, st, tb, ek, &c, in, out, (unsigned)sp.cus, sp.g_lo, sp.n8, nfull, nfull, 0,
+        rc = launch_fused(nr, true, st, tb, ek, &c, in, out, (unsigned)sp.cus, sp.g_lo, sp.n8, nfull, nfull, 0,
                                    front, ablk + sp.h0, sc);
         if (rc) return rc;                          /* nothing has been written yet */
         /* from here on `out` holds plaintext nobody has authenticated: if anything below cannot be
@@ -1553,9 +1491,7 @@ static int gcm_body(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk
                                   (unsigned char *)out + sp.h1 * 16, len - sp.h1 * 16, status);
         }
         if (!rc) {
-            hipLaunchKernelGGL(k_wipe_if_failed, dim3((unsigned)sp.cus * 2u), dim3(1024), 0, st, status,
-                               (unsigned char *)out, (u64)len);
-            rc = (int)hipGetLastError();
+            rc = uaesk_launch(k_wipe_if_failed, (unsigned)sp.cus * 2u, 1024, 0, st, status, out, len);
         }
         if (rc) (void)hipMemsetAsync(out, 0, len, st);
         return rc;
@@ -1631,9 +1567,8 @@ extern "C" int uaesk_gcm_key_tables(void *stream, const uaesk_tables *tb, int nr
     hipStream_t st = S(stream);
     unsigned char *sc = (unsigned char *)key_scratch;
     GPlan pl = plan_for(2048);                 /* no bulk table; the nibble tables of all four last levels */
-    int cus = 0;
     u32 logF = 0;
-    if (uaesk_device_info(&cus, nullptr) == 0 && cus > 0) {
+    if (const int cus = uaesk_cus()) {
         const u64 Sl = 2048ull * (u64)cus;
         while (((u64)1 << logF) < Sl) ++logF;
         if (((u64)1 << logF) != Sl || logF > GF_MAXLOG) logF = 0;
@@ -1642,10 +1577,7 @@ extern "C" int uaesk_gcm_key_tables(void *stream, const uaesk_tables *tb, int nr
     int rc;
     GCM_NR((launch_setup<NR>(st, tb, ek, z, sc, pl, 0, z, 1, logF)));
     if (rc) return rc;
-    hipError_t e = uaesk_want_lds((const void *)k_gcm_ytables, (unsigned)GHF_LDS);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(k_gcm_ytables, dim3(GS_YTAB_SETS), dim3(GH_T), GHF_LDS, st, *tb, sc);
-    return (int)hipGetLastError();
+    return uaesk_launch(k_gcm_ytables, GS_YTAB_SETS, GH_T, GHF_LDS, st, *tb, sc);
 }
 
 extern "C" int uaesk_ghash(void *stream, const uaesk_tables *tb, const uint8_t *H_host,
@@ -1773,13 +1705,13 @@ extern "C" int uaesk_gcm_shard(void *stream, const uaesk_tables *tb, int nr, con
             GCM_NR((launch_setup<NR>(st, tb, ek, j0, sc, plf, 0, z, 1, logF)));
             if (rc) return rc;
             if (mode == 0) {
-                rc = launch_fused_nr<false>(nr, st, tb, ek, &c, in, out, (unsigned)cus, g_lo, n8, h1, nfull,
+                rc = launch_fused(nr, false, st, tb, ek, &c, in, out, (unsigned)cus, g_lo, n8, h1, nfull,
                                             (u32)(shard_len % 16), front, ablk + h0, sc);
                 if (rc) return rc;
                 rc = run_ghash_levels(st, fin, nvf, plf, sc, 2, sc + GS_PART, nullptr);
             } else {
                 /* the fused kernel leaves the tail alone: it is hashed as ciphertext first (in may be out) */
-                rc = launch_fused_nr<true>(nr, st, tb, ek, &c, in, out, (unsigned)cus, g_lo, n8, nfull, nfull, 0,
+                rc = launch_fused(nr, true, st, tb, ek, &c, in, out, (unsigned)cus, g_lo, n8, nfull, nfull, 0,
                                            front, ablk + h0, sc);
                 if (rc) return rc;
                 rc = run_ghash_levels(st, fin, nvf, plf, sc, 2, sc + GS_PART, nullptr);
@@ -1791,9 +1723,7 @@ extern "C" int uaesk_gcm_shard(void *stream, const uaesk_tables *tb, int nr, con
                 }
             }
             if (rc) return rc;
-            hipLaunchKernelGGL(k_gcm_weight, dim3(1), dim3(64), 0, st, (const unsigned char *)sc, m_total - hi,
-                               (u32)first, 0u, (unsigned char *)partial16);
-            return (int)hipGetLastError();
+            return uaesk_launch(k_gcm_weight, 1, 64, 0, st, sc, m_total - hi, first, 0u, partial16);
         }
     }
 
@@ -1808,9 +1738,7 @@ extern "C" int uaesk_gcm_shard(void *stream, const uaesk_tables *tb, int nr, con
         rc = run_ghash_levels(st, msg, nv, pl, sc, 2, sc + GS_PART, nullptr);
         if (rc) return rc;
     }
-    hipLaunchKernelGGL(k_gcm_weight, dim3(1), dim3(64), 0, st, (const unsigned char *)sc, m_total - hi,
-                       (u32)first, (u32)(nv == 0), (unsigned char *)partial16);
-    rc = (int)hipGetLastError();
+    rc = uaesk_launch(k_gcm_weight, 1, 64, 0, st, sc, m_total - hi, first, nv == 0, partial16);
     if (!rc && mode == 2 && shard_len)          /* behind the hash: the ciphertext may be overwritten now */
         rc = uaesk_ctr_xcrypt(stream, tb, nr, ek, &c, in, out, shard_len, nullptr);
     return rc;
@@ -1909,8 +1837,7 @@ extern "C" int uaesk_gcm_stream_absorb(void *stream, const uaesk_tables *tb, int
         rc = run_ghash_levels(st, msg, nv, pl, sc, 2, sc + GS_PART, nullptr);
         if (rc) return rc;
     }
-    hipLaunchKernelGGL(k_gcm_fold, dim3(1), dim3(64), 0, st, sc, nv, (u32)(kind == 0));
-    return (int)hipGetLastError();
+    return uaesk_launch(k_gcm_fold, 1, 64, 0, st, sc, nv, kind == 0);
 }
 
 /* One piece of a streamed message, CTR and GHASH in ONE pass when the piece is long enough for the striped kernel
@@ -1925,22 +1852,11 @@ static int launch_stream_chunks(hipStream_t st, const uaesk_tables *tb, const ua
                                 const void *in, void *out, unsigned char *sc, u32 W, u32 steps, int decrypt, const GmcFin &fin,
                                 bool hash_only = false)
 {
-    hipError_t e;
-    uint4 *partial = (uint4 *)(sc + GS_ACC1);
-    if (hash_only) {                                          /* `in` = the piece's CIPHERTEXT; nothing is written */
-        if ((e = uaesk_want_lds((const void *)k_gcm_chunks<NR, 1, true>, (unsigned)(GSM_LDS_TOTAL))) != hipSuccess) return (int)e;
-        hipLaunchKernelGGL((k_gcm_chunks<NR, 1, true>), dim3(W + 1u), dim3(GH_T), GSM_LDS_TOTAL, st, *ek, *tb, *c, src,
-                           (const uint4 *)in, (uint4 *)out, (const unsigned char *)sc, partial, 0u, steps, fin);
-    } else if (decrypt) {
-        if ((e = uaesk_want_lds((const void *)k_gcm_chunks<NR, 2, true>, (unsigned)(GSM_LDS_TOTAL))) != hipSuccess) return (int)e;
-        hipLaunchKernelGGL((k_gcm_chunks<NR, 2, true>), dim3(W + 1u), dim3(GH_T), GSM_LDS_TOTAL, st, *ek, *tb, *c, src,
-                           (const uint4 *)in, (uint4 *)out, (const unsigned char *)sc, partial, 0u, steps, fin);
-    } else {
-        if ((e = uaesk_want_lds((const void *)k_gcm_chunks<NR, 0, true>, (unsigned)(GSM_LDS_TOTAL))) != hipSuccess) return (int)e;
-        hipLaunchKernelGGL((k_gcm_chunks<NR, 0, true>), dim3(W + 1u), dim3(GH_T), GSM_LDS_TOTAL, st, *ek, *tb, *c, src,
-                           (const uint4 *)in, (uint4 *)out, (const unsigned char *)sc, partial, 0u, steps, fin);
-    }
-    return (int)hipGetLastError();
+    auto chunks = [&](auto kern) {
+        return uaesk_launch(kern, W + 1u, GH_T, GSM_LDS_TOTAL, st, *ek, *tb, *c, src, in, out, sc, (uint4 *)(sc + GS_ACC1), 0u, steps, fin);
+    };
+    /* hash_only: `in` = the piece's CIPHERTEXT; nothing is written */
+    return hash_only ? chunks(k_gcm_chunks<NR, 1, true>) : decrypt ? chunks(k_gcm_chunks<NR, 2, true>) : chunks(k_gcm_chunks<NR, 0, true>);
 }
 
 /* ... and a piece of 16 KiB .. 8 MiB is ONE launch: the chunk workgroups of the medium-sized one-shot call (k_gcm_chunks,
@@ -2014,12 +1930,12 @@ extern "C" int uaesk_gcm_stream_piece(void *stream, const uaesk_tables *tb, int 
     }
     if (rc) return rc;
     if (!decrypt) {
-        rc = launch_fused_nr<false>(nr, st, tb, ek, &c, in, out, (unsigned)cus, g_lo, n8, h1, nfull, (u32)(len % 16),
+        rc = launch_fused(nr, false, st, tb, ek, &c, in, out, (unsigned)cus, g_lo, n8, h1, nfull, (u32)(len % 16),
                                     front, h0, sc);
         if (!rc) rc = run_ghash_levels(st, fin, nvf, plf, sc, 2, sc + GS_PART, nullptr);
     } else {
         /* the fused kernel leaves the tail alone: it is hashed as ciphertext first (in may be out) */
-        rc = launch_fused_nr<true>(nr, st, tb, ek, &c, in, out, (unsigned)cus, g_lo, n8, nfull, nfull, 0, front, h0, sc);
+        rc = launch_fused(nr, true, st, tb, ek, &c, in, out, (unsigned)cus, g_lo, n8, nfull, nfull, 0, front, h0, sc);
         if (!rc) rc = run_ghash_levels(st, fin, nvf, plf, sc, 2, sc + GS_PART, nullptr);
         if (!rc && len > h1 * 16) {
             uaesk_ctr ct = c;
@@ -2029,15 +1945,12 @@ extern "C" int uaesk_gcm_stream_piece(void *stream, const uaesk_tables *tb, int 
         }
     }
     if (rc) return rc;
-    hipLaunchKernelGGL(k_gcm_fold, dim3(1), dim3(64), 0, st, sc, (u64)((len + 15) >> 4), 0u);
-    return (int)hipGetLastError();
+    return uaesk_launch(k_gcm_fold, 1, 64, 0, st, sc, (len + 15) >> 4, 0u);
 }
 
 extern "C" int uaesk_gcm_stream_tag(void *stream, void *scratch, int compare, void *tag_io, int *status)
 {
-    hipLaunchKernelGGL(k_gcm_stream_tag, dim3(1), dim3(64), 0, S(stream), (const unsigned char *)scratch,
-                       compare ? 1 : 0, (unsigned char *)tag_io, status);
-    return (int)hipGetLastError();
+    return uaesk_launch(k_gcm_stream_tag, 1, 64, 0, S(stream), scratch, compare ? 1 : 0, tag_io, status);
 }
 
 
@@ -2140,8 +2053,7 @@ static int siv_long_nr(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *m
                        unsigned *done_word)
 {
     const unsigned char *tag_in = decrypt ? (const unsigned char *)in + len : nullptr;
-    hipLaunchKernelGGL((k_siv_prep<NR>), dim3(1), dim3(64), 1024 + 64, st, *mk, *tb, nn, tag_in, sc);
-    int rc = (int)hipGetLastError();
+    int rc = uaesk_launch(k_siv_prep<NR>, 1, 64, 1024 + 64, st, *mk, *tb, nn, tag_in, sc);
     if (rc) return rc;
     const uaesk_rk *d_rk = (const uaesk_rk *)(sc + GS_SIV_RK);
     const uaesk_ctr *d_ctr = (const uaesk_ctr *)(sc + GS_SIV_CTR);
@@ -2170,11 +2082,9 @@ static int siv_long_nr(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *m
         uaesk_ctr cdummy;
         memset(&dummy, 0, sizeof dummy);
         memset(&cdummy, 0, sizeof cdummy);
-        hipError_t e = uaesk_want_lds((const void *)k_gcm_chunks<NR, 1, true>, (unsigned)(GSM_LDS_TOTAL));
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL((k_gcm_chunks<NR, 1, true>), dim3(W + 1u), dim3(GH_T), GSM_LDS_TOTAL, st, dummy, *tb, cdummy, sm,
-                           (const uint4 *)msg.ct, (uint4 *)nullptr, (const unsigned char *)sc, (uint4 *)(sc + GS_ACC1), 1u, steps, fin);
-        if ((rc = (int)hipGetLastError()) != 0) return rc;
+        rc = uaesk_launch(k_gcm_chunks<NR, 1, true>, W + 1u, GH_T, GSM_LDS_TOTAL, st, dummy, *tb, cdummy, sm, (const uint4 *)msg.ct, nullptr, sc,
+                          (uint4 *)(sc + GS_ACC1), 1u, steps, fin);
+        if (rc) return rc;
         if (!decrypt) rc = uaesk_ctr_xcrypt_ind(st, tb, NR, d_rk, d_ctr, in, out, len);
         return rc;
     }
@@ -2183,9 +2093,10 @@ static int siv_long_nr(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *m
     memset(&dummy_rk, 0, sizeof dummy_rk);
     if ((rc = launch_setup<10>(st, tb, &dummy_rk, make_uint4(0, 0, 0, 0), sc, pl, 2, make_uint4(0, 0, 0, 0))) != 0) return rc;
     if ((rc = run_ghash_levels(st, msg, nv, pl, sc, 2, sc + GS_SIV_PV, nullptr)) != 0) return rc;
-    if (decrypt) hipLaunchKernelGGL((k_siv_tag<NR, true>), dim3(1), dim3(64), 1024, st, *tb, nn, sc, (unsigned char *)in + len, status);
-    else         hipLaunchKernelGGL((k_siv_tag<NR, false>), dim3(1), dim3(64), 1024, st, *tb, nn, sc, (unsigned char *)out + len, nullptr);
-    if ((rc = (int)hipGetLastError()) != 0) return rc;
+    rc = with_bool(decrypt, [&](auto DEC) {
+        return uaesk_launch(k_siv_tag<NR, decltype(DEC)::value>, 1, 64, 1024, st, *tb, nn, sc,
+                            DEC ? (unsigned char *)in + len : (unsigned char *)out + len, DEC ? status : nullptr); });
+    if (rc) return rc;
     if (!decrypt) rc = uaesk_ctr_xcrypt_ind(st, tb, NR, d_rk, d_ctr, in, out, len);
     return rc;
 }
@@ -2202,10 +2113,6 @@ extern "C" int uaesk_gcmsiv_long(void *stream, const uaesk_tables *tb, int nr, c
     memcpy(&nn, nonce12, 12);
     unsigned char *sc = (unsigned char *)scratch;
     unsigned *done_word = uaesk_done_word_take();               /* armed by the host layer: a word that is zero between calls */
-    switch (nr) {
-    case 10: return siv_long_nr<10>(S(stream), tb, mk, decrypt, nn, aad, aad_len, in, len, out, sc, status, done_word);
-    case 12: return siv_long_nr<12>(S(stream), tb, mk, decrypt, nn, aad, aad_len, in, len, out, sc, status, done_word);
-    case 14: return siv_long_nr<14>(S(stream), tb, mk, decrypt, nn, aad, aad_len, in, len, out, sc, status, done_word);
-    default: return (int)hipErrorInvalidValue;
-    }
+    DISPATCH_NR(nr, return siv_long_nr<NR>(S(stream), tb, mk, decrypt, nn, aad, aad_len, in, len, out, sc, status, done_word));
+    return 0;
 }

@@ -251,30 +251,14 @@ static int launch_records(hipStream_t st, const uaesk_tables *tb, const uaesk_rk
                           size_t in_stride, void *out, size_t out_stride, size_t nrec, const void *sc,
                           unsigned char *verdicts, int *status, const void *lens)
 {
-    int cus = 0;
-    uaesk_device_info(&cus, nullptr);
     const u64 nv = (aad_len + 15) / 16 + (rec_len + 15) / 16 + 1;
     const u32 lg = nv + 1 <= 128 ? 3u : nv + 1 <= 512 ? 4u : 5u;   /* one or two positions per thread */
     const u64 turns = (nrec + (GH_T >> (2 * lg)) - 1) / (GH_T >> (2 * lg));
-    const u64 cap = cus > 0 ? (u64)cus : 256u;
+    const u64 cap = uaesk_cus_or_256();
     const unsigned grid = (unsigned)(turns < cap ? turns : cap);
-    hipError_t e;
-    if (decrypt) {
-        e = uaesk_want_lds((const void *)k_gcm_records<NR, true>, (unsigned)GREC_LDS_TOTAL);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL((k_gcm_records<NR, true>), dim3(grid), dim3(GH_T), GREC_LDS_TOTAL, st, *ek, *tb,
-                           (const unsigned char *)nonces, (const unsigned char *)aad, (u64)aad_len, (u64)aad_stride,
-                           (const unsigned char *)in, (u64)rec_len, (u64)in_stride, (unsigned char *)out, (u64)out_stride,
-                           (u64)nrec, lg, (const u32 *)lens, (const unsigned char *)sc, verdicts, status);
-    } else {
-        e = uaesk_want_lds((const void *)k_gcm_records<NR, false>, (unsigned)GREC_LDS_TOTAL);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL((k_gcm_records<NR, false>), dim3(grid), dim3(GH_T), GREC_LDS_TOTAL, st, *ek, *tb,
-                           (const unsigned char *)nonces, (const unsigned char *)aad, (u64)aad_len, (u64)aad_stride,
-                           (const unsigned char *)in, (u64)rec_len, (u64)in_stride, (unsigned char *)out, (u64)out_stride,
-                           (u64)nrec, lg, (const u32 *)lens, (const unsigned char *)sc, verdicts, status);
-    }
-    return (int)hipGetLastError();
+    return with_bool(decrypt, [&](auto DEC) {
+        return uaesk_launch(k_gcm_records<NR, decltype(DEC)::value>, grid, GH_T, GREC_LDS_TOTAL, st, *ek, *tb, nonces, aad, aad_len,
+                            aad_stride, in, rec_len, in_stride, out, out_stride, nrec, lg, lens, sc, verdicts, status); });
 }
 
 /* records of up to uaesk_gcm_record_max(aad_len) bytes; texts and strides 16-byte aligned; decrypt: *status must be
@@ -296,13 +280,7 @@ extern "C" int uaesk_gcm_records(void *stream, const uaesk_tables *tb, int nr, c
     if ((((uintptr_t)in | (uintptr_t)out | in_stride | out_stride) & 15u) != 0) return (int)hipErrorInvalidValue;
     if (decrypt && !status) return (int)hipErrorInvalidValue;
     if (((uintptr_t)lens) & 3u) return (int)hipErrorInvalidValue;
-    switch (nr) {
-    case 10: return launch_records<10>(S(stream), tb, ek, decrypt, nonces12, aad, aad_len, aad_stride, in, rec_len, in_stride,
-                                       out, out_stride, nrec, key_scratch, verdicts, status, lens);
-    case 12: return launch_records<12>(S(stream), tb, ek, decrypt, nonces12, aad, aad_len, aad_stride, in, rec_len, in_stride,
-                                       out, out_stride, nrec, key_scratch, verdicts, status, lens);
-    case 14: return launch_records<14>(S(stream), tb, ek, decrypt, nonces12, aad, aad_len, aad_stride, in, rec_len, in_stride,
-                                       out, out_stride, nrec, key_scratch, verdicts, status, lens);
-    default: return (int)hipErrorInvalidValue;
-    }
+    DISPATCH_NR(nr, return launch_records<NR>(S(stream), tb, ek, decrypt, nonces12, aad, aad_len, aad_stride, in, rec_len, in_stride,
+                                              out, out_stride, nrec, key_scratch, verdicts, status, lens));
+    return 0;
 }

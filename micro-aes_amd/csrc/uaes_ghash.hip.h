@@ -53,8 +53,6 @@
 #define GS_SIV_CTR  (GS_SIV + 288u)                 /*   the keystream's counter description (uaesk_ctr)         */
 #define GS_TOTAL    (GS_SIV + 512u)
 
-static inline hipStream_t S(void *s) { return (hipStream_t)s; }
-
 /* the sequence of GHASH input blocks: AAD blocks, CT blocks, length block */
 struct GSrc {
     const unsigned char *aad;
@@ -419,12 +417,6 @@ __device__ __forceinline__ void gcm_build_nibble_tables(uint4 *TC, uint4 *buf, c
 #define GSM_LDS_TAB    65536u
 #define GSM_LDS_TOTAL  (GSM_LDS_TAB + (GT_NTAB * 512u + GT_BUF) * 16u)
 
-#define GCM_NR(CALL)                                              \
-    switch (nr) {                                                 \
-    case 10: { constexpr int NR = 10; rc = CALL; } break;         \
-    case 12: { constexpr int NR = 12; rc = CALL; } break;         \
-    case 14: { constexpr int NR = 14; rc = CALL; } break;         \
-    default: return (int)hipErrorInvalidValue;                    \
-    }
+#define GCM_NR(CALL) DISPATCH_NR(nr, rc = CALL)       /* in a function that has `nr` and `rc` */
 
 #endif /* UAES_GHASH_HIP_H_ */

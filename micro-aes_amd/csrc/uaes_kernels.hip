@@ -27,8 +27,6 @@
 
 #define UAES_U 4            /* blocks per lane per iteration */
 
-static inline hipStream_t S(void *s) { return (hipStream_t)s; }
-
 /* ------------------------------------------------------------------------ */
 /* ECB                                                                        */
 /* ------------------------------------------------------------------------ */
@@ -795,28 +793,27 @@ __global__ __launch_bounds__(UAES_WG) void k_selftest(uaesk_rk ek, uaesk_rk dk, 
 /* ------------------------------------------------------------------------ */
 /* launchers                                                                  */
 /* ------------------------------------------------------------------------ */
-static int g_cus = 0;
-
-extern "C" int uaesk_device_info(int *cu_count, int *lds_bytes)
+/* the current device's CU count, asked once per device ordinal (the table of uaesk_want_lds): a racing first call
+ * merely asks twice, an ordinal outside the table asks every time, and a failure (0: no device to ask) is not kept */
+int uaesk_cus()
 {
+    static volatile int seen[16];
     int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return (int)e;
     hipDeviceProp_t p;
-    e = hipGetDeviceProperties(&p, dev);
-    if (e != hipSuccess) return (int)e;
-    g_cus = p.multiProcessorCount;
-    if (cu_count) *cu_count = p.multiProcessorCount;
-    if (lds_bytes) *lds_bytes = (int)p.maxSharedMemoryPerMultiProcessor;
-    return 0;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return 0; }   /* (the error is not left behind) */
+    const bool kept = dev >= 0 && dev < 16;
+    if (kept && seen[dev]) return seen[dev];
+    if (hipGetDeviceProperties(&p, dev) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    if (kept) seen[dev] = p.multiProcessorCount;
+    return p.multiProcessorCount;
 }
 
-static unsigned grid_for(u64 work_items, u64 per_wg)
+/* (a routine that sizes several grids asks for the CU count once and hands it in) */
+static unsigned grid_for(u64 work_items, u64 per_wg, unsigned cus = uaesk_cus_or_256())
 {
-    if (g_cus <= 0) uaesk_device_info(nullptr, nullptr);
     u64 want = (work_items + per_wg - 1) / per_wg;
     if (want < 1) want = 1;
-    const u64 cap = (u64)(g_cus > 0 ? g_cus : 256);
+    const u64 cap = cus;
     return (unsigned)(want < cap ? want : cap);
 }
 
@@ -843,20 +840,6 @@ hipError_t uaesk_want_lds(const void *kern, unsigned bytes)
     if (e == hipSuccess && free_slot >= 0) seen[dev][free_slot] = kern;
     return e;
 }
-
-template <typename K>
-static hipError_t set_lds(K kern, unsigned bytes)
-{
-    return uaesk_want_lds((const void *)kern, bytes);
-}
-
-#define DISPATCH_NR(nr, CALL)                         \
-    switch (nr) {                                     \
-    case 10: { constexpr int NR = 10; CALL; } break;  \
-    case 12: { constexpr int NR = 12; CALL; } break;  \
-    case 14: { constexpr int NR = 14; CALL; } break;  \
-    default: return (int)hipErrorInvalidValue;        \
-    }
 
 /* ------------------------------------------------------------------------ */
 /* the table of arrangements (uaes_plan.h): switch, names, ECB / CTR / XTS planners */
@@ -885,16 +868,17 @@ extern "C" const char *uaesk_arrangement_name(int id)
 }
 
 /* short texts: one block per lane, so that up to four times as many CUs take part */
-static bool short_text(u64 nblocks)
+static bool short_text(u64 nblocks, unsigned cus = uaesk_cus_or_256())
 {
-    return grid_for(nblocks, (u64)UAES_WG * UAES_U) * 2 <= grid_for(~0ull, 1);
+    return grid_for(nblocks, (u64)UAES_WG * UAES_U, cus) * 2 <= cus;
 }
 
 static uaes_plan plan_ecb(u64 items)
 {
     uaes_plan p = { UAES_ARR_ECB_TILED, 1, 0, 0 };
-    if (short_text(items) && uaesk_arr_on(UAES_ARR_ECB_SINGLE)) { p.arrangement = UAES_ARR_ECB_SINGLE; p.grid = grid_for(items, UAES_WG); }
-    else p.grid = grid_for(items, (u64)UAES_WG * UAES_U);
+    const unsigned cus = uaesk_cus_or_256();
+    if (short_text(items, cus) && uaesk_arr_on(UAES_ARR_ECB_SINGLE)) { p.arrangement = UAES_ARR_ECB_SINGLE; p.grid = grid_for(items, UAES_WG, cus); }
+    else p.grid = grid_for(items, (u64)UAES_WG * UAES_U, cus);
     return p;
 }
 
@@ -909,7 +893,7 @@ static uaes_plan plan_ctr(const uaesk_ctr *ctr, size_t len, u64 *g_lo_out, u64 *
 {
     const u64 nfull = len / 16, nblocks = (len + 15) / 16;
     uaes_plan p = { UAES_ARR_CTR_QUAD, 1, 0, 0 };
-    const unsigned grid = grid_for(~0ull, 1);
+    const unsigned grid = uaesk_cus_or_256();                    /* one workgroup per CU */
     if (!ctr->le32 && uaesk_arr_on(UAES_ARR_CTR_STRIPED)) {      /* (the shared rounds assume the 56-bit big-endian counter) */
         const u32 c0 = (u32)ctr->v0 & 0xffu;
         const u64 g_lo = c0 ? 1 : 0, groups = (c0 + nfull) / 256;
@@ -925,8 +909,8 @@ static uaes_plan plan_ctr(const uaesk_ctr *ctr, size_t len, u64 *g_lo_out, u64 *
             return p;
         }
     }
-    if (short_text(nblocks) && uaesk_arr_on(UAES_ARR_CTR_SINGLE)) { p.arrangement = UAES_ARR_CTR_SINGLE; p.grid = grid_for(nblocks, UAES_WG); }
-    else p.grid = grid_for(nblocks, (u64)UAES_WG * UAES_U);
+    if (short_text(nblocks, grid) && uaesk_arr_on(UAES_ARR_CTR_SINGLE)) { p.arrangement = UAES_ARR_CTR_SINGLE; p.grid = grid_for(nblocks, UAES_WG, grid); }
+    else p.grid = grid_for(nblocks, (u64)UAES_WG * UAES_U, grid);
     return p;
 }
 
@@ -935,25 +919,16 @@ static int launch_ecb(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *ke
                       const void *in, void *out, size_t nfull, unsigned rem, unsigned padding)
 {
     const unsigned lds = DEC ? UAES_LDS_DEC : UAES_LDS_ENC;
-    hipError_t e = set_lds(k_ecb<NR, DEC, UAES_U>, lds);
-    if (e == hipSuccess) e = set_lds(k_ecb<NR, DEC, 1>, lds);
-    if (e != hipSuccess) return (int)e;
     const u64 items = nfull + ((rem || padding) ? 1 : 0);
     const uaesk_done done = uaesk_ticket_take();              /* the call's only kernel: it carries the ticket */
     const uaes_plan pl = plan_ecb(items);
-    if (pl.arrangement == UAES_ARR_ECB_SINGLE) {
-        hipLaunchKernelGGL((k_ecb<NR, DEC, 1>), dim3(pl.grid), dim3(UAES_WG), lds, st, *keys, *tb,
-                           (const uint4 *)in, (uint4 *)out, (u64)nfull, (u32)rem, (u32)padding, done, (u64)nfull);
-    } else {
-        const unsigned grid = pl.grid;
-        const u64 tile = (u64)UAES_WG * UAES_U, per_round = tile * grid;
-        const u64 rounds = (u64)nfull / per_round, left = (u64)nfull - rounds * per_round;
-        /* the remainder of the last round as single blocks when it covers less than 80 % of the grid */
-        const u64 tail_from = (rounds && left && left * 100 < per_round * 80) ? rounds * per_round : (u64)nfull;
-        hipLaunchKernelGGL((k_ecb<NR, DEC, UAES_U>), dim3(grid), dim3(UAES_WG), lds, st,
-                           *keys, *tb, (const uint4 *)in, (uint4 *)out, (u64)nfull, (u32)rem, (u32)padding, done, tail_from);
-    }
-    return (int)hipGetLastError();
+    if (pl.arrangement == UAES_ARR_ECB_SINGLE)
+        return uaesk_launch(k_ecb<NR, DEC, 1>, pl.grid, UAES_WG, lds, st, *keys, *tb, in, out, nfull, rem, padding, done, nfull);
+    const u64 tile = (u64)UAES_WG * UAES_U, per_round = tile * pl.grid;
+    const u64 rounds = (u64)nfull / per_round, left = (u64)nfull - rounds * per_round;
+    /* the remainder of the last round as single blocks when it covers less than 80 % of the grid */
+    const u64 tail_from = (rounds && left && left * 100 < per_round * 80) ? rounds * per_round : (u64)nfull;
+    return uaesk_launch(k_ecb<NR, DEC, UAES_U>, pl.grid, UAES_WG, lds, st, *keys, *tb, in, out, nfull, rem, padding, done, tail_from);
 }
 
 extern "C" int uaesk_ecb(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *keys,
@@ -962,8 +937,9 @@ extern "C" int uaesk_ecb(void *stream, const uaesk_tables *tb, int nr, const uae
     if (decrypt) padding = 0;
     if (nfull == 0 && rem == 0 && padding == 0) return 0;
     if (padding > 2) return (int)hipErrorInvalidValue;
-    if (decrypt) { DISPATCH_NR(nr, return (launch_ecb<NR, true>(S(stream), tb, keys, in, out, nfull, 0, 0))); }
-    else         { DISPATCH_NR(nr, return (launch_ecb<NR, false>(S(stream), tb, keys, in, out, nfull, rem, padding))); }
+    if (decrypt) rem = 0;
+    DISPATCH_NR(nr, return with_bool(decrypt, [&](auto D) {
+        return launch_ecb<NR, decltype(D)::value>(S(stream), tb, keys, in, out, nfull, rem, padding); }));
     return 0;
 }
 
@@ -971,9 +947,6 @@ template <int NR, int U>
 static int launch_ctr_u(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *ek, const uaesk_ctr *ctr,
                         const void *in, void *out, size_t len, const int *gate)
 {
-    const unsigned lds = UAES_LDS_ENC;
-    hipError_t e = set_lds(k_ctr<NR, U>, lds);
-    if (e != hipSuccess) return (int)e;
     const u64 nfull = len / 16;
     const u32 rem = (u32)(len % 16);
     const unsigned grid = grid_for(nfull + (rem ? 1 : 0), (u64)UAES_WG * U);
@@ -981,9 +954,7 @@ static int launch_ctr_u(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *
      * which never arms) */
     uaesk_done done = { nullptr, nullptr, 0 };
     if (!gate) done = uaesk_ticket_take();
-    hipLaunchKernelGGL((k_ctr<NR, U>), dim3(grid), dim3(UAES_WG), lds, st, *ek, *tb, *ctr,
-                       (const uint4 *)in, (uint4 *)out, nfull, rem, gate, done);
-    return (int)hipGetLastError();
+    return uaesk_launch(k_ctr<NR, U>, grid, UAES_WG, UAES_LDS_ENC, st, *ek, *tb, *ctr, in, out, nfull, rem, gate, done);
 }
 
 /* one launch of the striped kernel over a text whose stripes do not cross a 2^40-block boundary */
@@ -991,11 +962,8 @@ template <int NR>
 static int launch_ctr_striped(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *ek, const uaesk_ctr *ctr,
                               const void *in, void *out, size_t len, const int *gate, unsigned grid, u64 g_lo, u64 n8)
 {
-    hipError_t e = set_lds(k_ctr_shared2<NR>, UAES_LDS_CTRS);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((k_ctr_shared2<NR>), dim3(grid), dim3(UAES_WG), UAES_LDS_CTRS, st, *ek, *tb, *ctr,
-                       (const uint4 *)in, (uint4 *)out, g_lo, n8, (u64)(len / 16), (u32)(len % 16), gate);
-    return (int)hipGetLastError();
+    return uaesk_launch(k_ctr_shared2<NR>, grid, UAES_WG, UAES_LDS_CTRS, st, *ek, *tb, *ctr, in, out, g_lo, n8, len / 16,
+                        len % 16, gate);
 }
 
 template <int NR>
@@ -1025,15 +993,10 @@ template <int NR, int U>
 static int launch_ctr_ind_u(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *d_rk, const uaesk_ctr *d_ctr,
                             const void *in, void *out, size_t len)
 {
-    const unsigned lds = UAES_LDS_ENC;
-    hipError_t e = set_lds(k_ctr_ind<NR, U>, lds);
-    if (e != hipSuccess) return (int)e;
     const u64 nfull = len / 16;
     const u32 rem = (u32)(len % 16);
     const unsigned grid = grid_for(nfull + (rem ? 1 : 0), (u64)UAES_WG * U);
-    hipLaunchKernelGGL((k_ctr_ind<NR, U>), dim3(grid), dim3(UAES_WG), lds, st, d_rk, *tb, d_ctr,
-                       (const uint4 *)in, (uint4 *)out, nfull, rem);
-    return (int)hipGetLastError();
+    return uaesk_launch(k_ctr_ind<NR, U>, grid, UAES_WG, UAES_LDS_ENC, st, d_rk, *tb, d_ctr, in, out, nfull, rem);
 }
 
 /* the generic CTR kernel with key schedule and counter description read from device memory (k_ctr_ind) */
@@ -1131,99 +1094,74 @@ static int launch_xts(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *k1
     u64 mb, cps; u32 r;
     xts_geometry(sector_bytes, &mb, &r, &cps);
     const unsigned lds = DEC ? UAES_LDS_DEC : UAES_LDS_ENC;
-    hipError_t e = set_lds(k_xts_tweaks<NR>, UAES_LDS_ENC);
-    if (e == hipSuccess) e = set_lds(k_xts<NR, DEC, true>, lds);
-    if (e == hipSuccess) e = set_lds(k_xts<NR, DEC, false>, lds);
-    if (e == hipSuccess) e = set_lds(k_xts_cts<NR, DEC>, lds);
-    if (e != hipSuccess) return (int)e;
+    const u32 explicit_tweak = tweak16 != nullptr;
+    int rc;
 
     uint4 raw = make_uint4(0, 0, 0, 0);
     if (tweak16) memcpy(&raw, tweak16, 16);
     const uaes_plan pl = plan_xts(sector_bytes, nsectors, tweak16 != nullptr);
-    const bool few_units = pl.arrangement == UAES_ARR_XTS_SMALL && nsectors > 1;     /* (one unit, or several whole-block ones) */
     if (pl.arrangement == UAES_ARR_XTS_SMALL) {
-        e = few_units ? set_lds((k_xts_small<NR, DEC, true>), XTS_SMALL_LDS) : set_lds((k_xts_small<NR, DEC, false>), XTS_SMALL_LDS);
-        if (e != hipSuccess) return (int)e;
         uaesk_done done = { nullptr, nullptr, 0 };
         if (!r) done = uaesk_ticket_take();                   /* no stealing kernel behind it: it carries the ticket */
         /* a workgroup per 1024 blocks (one per lane), as many as half the CUs: a 64 KiB unit runs on four CUs at the
-         * latency of one block */
-        const unsigned sgrid = pl.grid;
-        if (few_units)
-            hipLaunchKernelGGL((k_xts_small<NR, DEC, true>), dim3(sgrid), dim3(UAES_WG), XTS_SMALL_LDS, st, *k1, *k2, *tb, raw,
-                               0u, first_sector, (uint4 *)scratch, cps, mb,
-                               (const unsigned char *)in, (unsigned char *)out, done, *xts_pow_table(), (u64)nsectors,
-                               (u64)sector_bytes);
-        else
-            hipLaunchKernelGGL((k_xts_small<NR, DEC, false>), dim3(sgrid), dim3(UAES_WG), XTS_SMALL_LDS, st, *k1, *k2, *tb, raw,
-                               (u32)(tweak16 != nullptr), first_sector, (uint4 *)scratch, cps, mb,
-                               (const unsigned char *)in, (unsigned char *)out, done, *xts_pow_table(), (u64)1,
-                               (u64)sector_bytes);
-        if (r)
-            hipLaunchKernelGGL((k_xts_cts<NR, DEC>), dim3(1), dim3(UAES_WG), lds, st,
-                               *k1, *tb, (const uint4 *)scratch, (u64)1, cps, mb, r, (u64)sector_bytes,
-                               (const unsigned char *)in, (unsigned char *)out);
-        return (int)hipGetLastError();
+         * latency of one block.  FEW: several whole-block units numbered from first_sector, never with an explicit
+         * tweak (plan_xts); else one unit */
+        rc = with_bool(nsectors > 1, [&](auto FEW) {
+            return uaesk_launch(k_xts_small<NR, DEC, decltype(FEW)::value>, pl.grid, UAES_WG, XTS_SMALL_LDS, st, *k1, *k2, *tb, raw,
+                                explicit_tweak, first_sector, scratch, cps, mb, in, out, done, *xts_pow_table(), nsectors,
+                                sector_bytes); });
+        if (rc || !r) return rc;
+        return uaesk_launch(k_xts_cts<NR, DEC>, 1, UAES_WG, lds, st, *k1, *tb, scratch, 1, cps, mb, r, sector_bytes, in, out);
     }
     const bool serial = cps <= XTS_SERIAL_CPS;
+    const unsigned cus = uaesk_cus_or_256();
     if (!serial && ((cps + 63) / 64) >> XTS_POW_N) return (int)hipErrorInvalidValue;
-    if (nsectors <= 65536) {                 /* few units: one-wave workgroups on a plain table (k_xts_tweaks) */
-        if ((e = set_lds((k_xts_tweaks<NR, true>), 1024u)) != hipSuccess) return (int)e;
-        hipLaunchKernelGGL((k_xts_tweaks<NR, true>), dim3((unsigned)((nsectors + 63) / 64)), dim3(64), 1024u, st,
-                           *k2, *tb, raw, (u32)(tweak16 != nullptr), first_sector, (u64)nsectors, cps, (u32)serial,
-                           (uint4 *)scratch);
-    } else {
-        hipLaunchKernelGGL((k_xts_tweaks<NR>), dim3(grid_for(nsectors, UAES_WG)), dim3(UAES_WG), UAES_LDS_ENC, st,
-                           *k2, *tb, raw, (u32)(tweak16 != nullptr), first_sector, (u64)nsectors, cps, (u32)serial,
-                           (uint4 *)scratch);
+    if (nsectors <= 65536)                   /* few units: one-wave workgroups on a plain table (k_xts_tweaks) */
+        rc = uaesk_launch(k_xts_tweaks<NR, true>, (unsigned)((nsectors + 63) / 64), 64, 1024u, st, *k2, *tb, raw, explicit_tweak,
+                          first_sector, nsectors, cps, serial, scratch);
+    else
+        rc = uaesk_launch(k_xts_tweaks<NR>, grid_for(nsectors, UAES_WG, cus), UAES_WG, UAES_LDS_ENC, st, *k2, *tb, raw, explicit_tweak,
+                          first_sector, nsectors, cps, serial, scratch);
+    if (rc) return rc;
+    if (!serial) {
+        rc = uaesk_launch(k_xts_expand, grid_for((u64)nsectors * ((cps + 63) / 64), UAES_WG / 64, cus), UAES_WG, 0, st, *xts_pow_table(),
+                          nsectors, cps, scratch);
+        if (rc) return rc;
     }
-    if (!serial)
-        hipLaunchKernelGGL(k_xts_expand, dim3(grid_for((u64)nsectors * ((cps + 63) / 64), UAES_WG / 64)),
-                           dim3(UAES_WG), 0, st, *xts_pow_table(), (u64)nsectors, cps, (uint4 *)scratch);
     /* units shorter than a chunk (whole blocks, a multiple of four): the flat, packed arrangement (k_xts) */
     if (pl.arrangement == UAES_ARR_XTS_PACKED) {
-        if ((e = set_lds((k_xts<NR, DEC, true, true>), lds)) != hipSuccess) return (int)e;
         const u64 total = (u64)nsectors * mb, nchunks = (total + XTS_CHUNK - 1) / XTS_CHUNK;
-        const unsigned wg = grid_for(nchunks, UAES_WG / 64) * 2 <= grid_for(~0ull, 1) ? 256u : UAES_WG;
-        const unsigned xgrid = grid_for(nchunks, wg / 64);
+        const unsigned wg = grid_for(nchunks, UAES_WG / 64, cus) * 2 <= cus ? 256u : UAES_WG;
+        const unsigned xgrid = grid_for(nchunks, wg / 64, cus);
         const u64 adv = (u64)xgrid * (wg / 64) * XTS_CHUNK;
-        hipLaunchKernelGGL((k_xts<NR, DEC, true, true>), dim3(xgrid), dim3(wg), lds, st,
-                           *k1, *tb, (const uint4 *)scratch, (u64)nsectors, mb, total, (u64)sector_bytes, adv / mb, adv % mb,
-                           (const unsigned char *)in, (unsigned char *)out, nchunks, (u32)(((1u << 24) + mb - 1) / mb));
-        return (int)hipGetLastError();
+        return uaesk_launch(k_xts<NR, DEC, true, true>, xgrid, wg, lds, st, *k1, *tb, scratch, nsectors, mb, total, sector_bytes,
+                            adv / mb, adv % mb, in, out, nchunks, ((1u << 24) + mb - 1) / mb);
     }
     if (mb > 0) {
         const u64 nchunks = (u64)nsectors * ((mb + XTS_CHUNK - 1) / XTS_CHUNK);
         /* one wave per 256-block chunk: a short text on 16-wave workgroups would sit on a few CUs,
          * so below half a GPU's worth of chunks the workgroups shrink to 4 waves              */
-        const unsigned wg = grid_for(nchunks, UAES_WG / 64) * 2 <= grid_for(~0ull, 1) ? 256u : UAES_WG;
-        /* every block address is a multiple of 16 unless units of ragged size follow one another */
-        const unsigned xgrid = grid_for(nchunks, wg / 64);
+        const unsigned wg = grid_for(nchunks, UAES_WG / 64, cus) * 2 <= cus ? 256u : UAES_WG;
+        const unsigned xgrid = grid_for(nchunks, wg / 64, cus);
         const u64 nwaves = (u64)xgrid * (wg / 64), step_q = nwaves / cps, step_r = nwaves % cps;
         /* the remainder of the last round by quarter chunks when it covers less than 80 % of the waves (k_xts) */
         const u64 pct = 80;                                   /* (as CTR_TAIL_PCT) */
         const u64 rounds = nchunks / nwaves, left = nchunks % nwaves;
         const u64 nmain = (rounds && left && left * 100 < nwaves * pct) ? rounds * nwaves : nchunks;
-        if ((sector_bytes % 16 == 0 || nsectors == 1) && mb % XTS_CHUNK == 0) {        /* every chunk whole: k_xts<.., ALLFULL> */
-            if ((e = set_lds((k_xts<NR, DEC, true, false, true>), lds)) != hipSuccess) return (int)e;
-            hipLaunchKernelGGL((k_xts<NR, DEC, true, false, true>), dim3(xgrid), dim3(wg), lds, st,
-                               *k1, *tb, (const uint4 *)scratch, (u64)nsectors, cps, mb, (u64)sector_bytes, step_q, step_r,
-                               (const unsigned char *)in, (unsigned char *)out, nmain, 0u);
-        } else if (sector_bytes % 16 == 0 || nsectors == 1)
-            hipLaunchKernelGGL((k_xts<NR, DEC, true>), dim3(xgrid), dim3(wg), lds, st,
-                               *k1, *tb, (const uint4 *)scratch, (u64)nsectors, cps, mb, (u64)sector_bytes, step_q, step_r,
-                               (const unsigned char *)in, (unsigned char *)out, nmain, 0u);
-        else
-            hipLaunchKernelGGL((k_xts<NR, DEC, false>), dim3(xgrid), dim3(wg), lds, st,
-                               *k1, *tb, (const uint4 *)scratch, (u64)nsectors, cps, mb, (u64)sector_bytes, step_q, step_r,
-                               (const unsigned char *)in, (unsigned char *)out, nmain, 0u);
+        /* every block address is a multiple of 16 unless units of ragged size follow one another */
+        const bool aligned = sector_bytes % 16 == 0 || nsectors == 1;
+        auto bulk = [&](auto kern) {
+            return uaesk_launch(kern, xgrid, wg, lds, st, *k1, *tb, scratch, nsectors, cps, mb, sector_bytes, step_q, step_r,
+                                in, out, nmain, 0u);
+        };
+        rc = aligned && mb % XTS_CHUNK == 0 ? bulk(k_xts<NR, DEC, true, false, true>)       /* every chunk whole: ALLFULL */
+             : aligned ? bulk(k_xts<NR, DEC, true>) : bulk(k_xts<NR, DEC, false>);
+        if (rc) return rc;
     }
-    if (r) {
-        hipLaunchKernelGGL((k_xts_cts<NR, DEC>), dim3(grid_for(nsectors, UAES_WG)), dim3(UAES_WG), lds, st,
-                           *k1, *tb, (const uint4 *)scratch, (u64)nsectors, cps, mb, r, (u64)sector_bytes,
-                           (const unsigned char *)in, (unsigned char *)out);
-    }
-    return (int)hipGetLastError();
+    if (r)
+        return uaesk_launch(k_xts_cts<NR, DEC>, grid_for(nsectors, UAES_WG, cus), UAES_WG, lds, st, *k1, *tb, scratch, nsectors, cps, mb, r,
+                            sector_bytes, in, out);
+    return 0;
 }
 
 extern "C" int uaesk_xts(void *stream, const uaesk_tables *tb, int nr,
@@ -1234,8 +1172,8 @@ extern "C" int uaesk_xts(void *stream, const uaesk_tables *tb, int nr,
 {
     if (nsectors == 0) return 0;
     if (sector_bytes < 16) return (int)hipErrorInvalidValue;
-    if (decrypt) { DISPATCH_NR(nr, return (launch_xts<NR, true>(S(stream), tb, k1, k2_enc, tweak16, first_sector, sector_bytes, nsectors, in, out, scratch))); }
-    else         { DISPATCH_NR(nr, return (launch_xts<NR, false>(S(stream), tb, k1, k2_enc, tweak16, first_sector, sector_bytes, nsectors, in, out, scratch))); }
+    DISPATCH_NR(nr, return with_bool(decrypt, [&](auto D) {
+        return launch_xts<NR, decltype(D)::value>(S(stream), tb, k1, k2_enc, tweak16, first_sector, sector_bytes, nsectors, in, out, scratch); }));
     return 0;
 }
 
@@ -1305,9 +1243,7 @@ __global__ __launch_bounds__(64) void k_ticket(unsigned *flag, unsigned seq, con
 extern "C" int uaesk_ticket(void *stream, void *pinned_flag, unsigned seq, const void *d_src, void *pinned_dst, unsigned nbytes)
 {
     if (nbytes > 64u || (nbytes & 3u)) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_ticket, dim3(1), dim3(64), 0, S(stream), (unsigned *)pinned_flag, seq, (const unsigned *)d_src,
-                       (unsigned *)pinned_dst, nbytes / 4u);
-    return (int)hipGetLastError();
+    return uaesk_launch(k_ticket, 1, 64, 0, S(stream), pinned_flag, seq, d_src, pinned_dst, nbytes / 4u);
 }
 
 /* ------------------------------------------------------------------------ */
@@ -1332,17 +1268,13 @@ __global__ __launch_bounds__(64) void k_clock_probe(unsigned long long *out, uns
 
 extern "C" int uaesk_clock_probe(void *stream, void *d_out16, unsigned long long ticks_100mhz)
 {
-    hipLaunchKernelGGL(k_clock_probe, dim3(1), dim3(64), 0, S(stream), (unsigned long long *)d_out16, ticks_100mhz);
-    return (int)hipGetLastError();
+    return uaesk_launch(k_clock_probe, 1, 64, 0, S(stream), d_out16, ticks_100mhz);
 }
 
 extern "C" int uaesk_selftest(void *stream, const uaesk_tables *tb, const uaesk_rk *ek128,
                               const uaesk_rk *dk128, unsigned *d_result)
 {
-    hipError_t e = set_lds(k_selftest, UAES_LDS_ENC);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(k_selftest, dim3(2), dim3(UAES_WG), UAES_LDS_ENC, S(stream), *ek128, *dk128, *tb, d_result);
-    return (int)hipGetLastError();
+    return uaesk_launch(k_selftest, 2, UAES_WG, UAES_LDS_ENC, S(stream), *ek128, *dk128, *tb, d_result);
 }
 
 /* ------------------------------------------------------------------------ */
@@ -1360,7 +1292,6 @@ extern "C" int uaesk_plan(int mode, int dir, size_t a, size_t b, unsigned flags,
 extern "C" int uaesk_plan_at(int mode, int dir, size_t a, size_t b, unsigned flags, const uint8_t *counter16, uaes_plan *p)
 {
     if (!p) return (int)hipErrorInvalidValue;
-    if (uaesk_device_info(nullptr, nullptr) != 0) g_cus = 0;    /* no device: the table of a 256-CU MI355X (grid_for, plan_cus) */
     switch (mode) {
     case UAES_PLAN_ECB:
         *p = plan_ecb((u64)((a + 15) / 16));

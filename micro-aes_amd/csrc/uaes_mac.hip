@@ -18,8 +18,6 @@
 #include "uaes_device.h"
 #include "uaes_plan.h"
 
-static inline hipStream_t S(void *s) { return (hipStream_t)s; }
-
 struct Blk {
     u32 w[4];
 };
@@ -295,14 +293,6 @@ __global__ __launch_bounds__(64) void k_ccm(uaesk_rk rk, uaesk_tables tb, uint4 
     }
 }
 
-#define DISPATCH_NR(nr, CALL)                         \
-    switch (nr) {                                     \
-    case 10: { constexpr int NR = 10; CALL; } break;  \
-    case 12: { constexpr int NR = 12; CALL; } break;  \
-    case 14: { constexpr int NR = 14; CALL; } break;  \
-    default: return (int)hipErrorInvalidValue;        \
-    }
-
 /* ---- the plan (uaes_plan.h) ---------------------------------------------------------------------------------------
  * CMAC is one wave whatever the length.  CCM: a short message (CCM's usual diet) is ONE launch, the MAC chain and the
  * counter blocks share the wave (ccm_text); its chain step is a third longer than the plain MAC's, so texts beyond
@@ -337,11 +327,7 @@ static int launch_cmac(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *e
 {
     uaes_plan p;
     plan_mac(UAES_WHAT_CMAC, len, &p);
-    hipError_t e = uaesk_want_lds((const void *)k_cmac<NR>, (unsigned)(UAES_LDS_ROW));
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((k_cmac<NR>), dim3(p.grid), dim3(p.steps), UAES_LDS_ROW, st, *ek, *tb,
-                       (const unsigned char *)data, (u64)len, (unsigned char *)mac);
-    return (int)hipGetLastError();
+    return uaesk_launch(k_cmac<NR>, p.grid, p.steps, UAES_LDS_ROW, st, *ek, *tb, data, len, mac);
 }
 
 extern "C" int uaesk_cmac(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek,
@@ -356,33 +342,17 @@ static int launch_ccm_tag(hipStream_t st, const uaes_plan &p, const uaesk_tables
                           const void *aad, size_t aad_len, const void *pt, size_t pt_len,
                           int mode, void *tag_io, int *status, u32 tag_len)
 {
-    hipError_t e = uaesk_want_lds((const void *)k_ccm_tag<NR>, (unsigned)(UAES_LDS_ROW));
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((k_ccm_tag<NR>), dim3(p.grid), dim3(p.steps), UAES_LDS_ROW, st, *ek, *tb, iv,
-                       (const unsigned char *)aad, (u64)aad_len, (const unsigned char *)pt, (u64)pt_len,
-                       mode, (unsigned char *)tag_io, status, tag_len);
-    return (int)hipGetLastError();
+    return uaesk_launch(k_ccm_tag<NR>, p.grid, p.steps, UAES_LDS_ROW, st, *ek, *tb, iv, aad, aad_len, pt, pt_len, mode, tag_io,
+                        status, tag_len);
 }
 template <int NR>
 static int launch_ccm(hipStream_t st, const uaes_plan &p, const uaesk_tables *tb, const uaesk_rk *ek, uint4 iv, const uaesk_ctr &c, int decrypt,
                       const void *aad, size_t aad_len, const void *in, size_t len, void *out,
                       void *tag_io, int *status, u32 tag_len)
 {
-    hipError_t e;
-    if (decrypt) {
-        e = uaesk_want_lds((const void *)k_ccm<NR, true>, (unsigned)(UAES_LDS_ROW));
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL((k_ccm<NR, true>), dim3(p.grid), dim3(p.steps), UAES_LDS_ROW, st, *ek, *tb, iv, c,
-                           (const unsigned char *)aad, (u64)aad_len, (const unsigned char *)in, (u64)len,
-                           (unsigned char *)out, (unsigned char *)tag_io, status, tag_len);
-    } else {
-        e = uaesk_want_lds((const void *)k_ccm<NR, false>, (unsigned)(UAES_LDS_ROW));
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL((k_ccm<NR, false>), dim3(p.grid), dim3(p.steps), UAES_LDS_ROW, st, *ek, *tb, iv, c,
-                           (const unsigned char *)aad, (u64)aad_len, (const unsigned char *)in, (u64)len,
-                           (unsigned char *)out, (unsigned char *)tag_io, status, tag_len);
-    }
-    return (int)hipGetLastError();
+    return with_bool(decrypt, [&](auto DEC) {
+        return uaesk_launch(k_ccm<NR, decltype(DEC)::value>, p.grid, p.steps, UAES_LDS_ROW, st, *ek, *tb, iv, c, aad, aad_len, in, len,
+                            out, tag_io, status, tag_len); });
 }
 
 /* nonce is a host pointer; everything else device memory.  encrypt: tag over

@@ -30,8 +30,6 @@
 #include "uaes_device.h"
 #include "uaes_plan.h"
 
-static inline hipStream_t S(void *s) { return (hipStream_t)s; }
-
 #define OCB_NL       64u                      /* table rows: 0 L_*, 1 L_$, 2+j L_j      */
 #define OCB_LDS_L    (128u * 1024u)           /* L table in LDS, after the cipher tables */
 #define OCB_LDS_ACC  (OCB_LDS_L + OCB_NL * 16u)
@@ -665,22 +663,9 @@ __global__ __launch_bounds__(UAES_WG) void k_ocb_small(uaesk_rk ek, uaesk_rk dk,
 /* ------------------------------------------------------------------------ */
 /* launcher                                                                    */
 /* ------------------------------------------------------------------------ */
-static unsigned cu_count()
-{
-    static int cus = 0;
-    if (!cus) uaesk_device_info(&cus, nullptr);
-    return cus > 0 ? (unsigned)cus : 256u;
-}
-
-static hipError_t want_lds(const void *kern)
-{
-    return uaesk_want_lds(kern, (unsigned)(OCB_LDS));
-}
-
 /* OCB's rows of the table of arrangements (uaes_plan.h): one workgroup for a short message with short associated data,
  * else runs of chunks over as many workgroups as there are CUs -- both ONE launch, the last workgroup to arrive makes
  * the tag */
-bool uaesk_arr_on(int id);                                       /* uaes_kernels.hip */
 static uaes_plan plan_ocb(u64 len, u64 aad_len)
 {
     uaes_plan p = { UAES_ARR_OCB_RUNS, 1, 0, 0 };
@@ -699,25 +684,16 @@ static int launch_ocb(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *ek
                       int decrypt, uint4 nb, u32 bottom, u32 tag_len, const void *aad, size_t aad_len,
                       const void *in, size_t len, void *out, void *scratch, unsigned *done_word, int *status)
 {
-    uint4 *scr = (uint4 *)scratch;
-    hipError_t e;
+    const uaesk_rk &k2 = decrypt ? *dk : *ek;
+    const unsigned cus = uaesk_cus_or_256();
     /* one launch either way, which can carry the call's completion ticket (a decryption's status word must then
      * be host-visible: the host layer arms a ticket only when it passes a pinned status pointer) */
     const uaesk_done done = uaesk_ticket_take();
     if (plan_ocb(len, aad_len).arrangement == UAES_ARR_OCB_SMALL) {         /* short message: one workgroup */
-        const void *ks = decrypt ? (const void *)k_ocb_small<NR, true> : (const void *)k_ocb_small<NR, false>;
-        if ((e = uaesk_want_lds(ks, (unsigned)OCB_SMALL_LDS)) != hipSuccess) return (int)e;
-        if (decrypt)
-            hipLaunchKernelGGL((k_ocb_small<NR, true>), dim3(1), dim3(UAES_WG), OCB_SMALL_LDS, st, *ek, *dk, *tb, nb, bottom,
-                               (const unsigned char *)aad, (u64)aad_len, (const unsigned char *)in,
-                               (unsigned char *)out, (u64)len, status, tag_len, done);
-        else
-            hipLaunchKernelGGL((k_ocb_small<NR, false>), dim3(1), dim3(UAES_WG), OCB_SMALL_LDS, st, *ek, *ek, *tb, nb, bottom,
-                               (const unsigned char *)aad, (u64)aad_len, (const unsigned char *)in,
-                               (unsigned char *)out, (u64)len, status, tag_len, done);
-        return (int)hipGetLastError();
+        return with_bool(decrypt, [&](auto DEC) {
+            return uaesk_launch(k_ocb_small<NR, decltype(DEC)::value>, 1, UAES_WG, OCB_SMALL_LDS, st, *ek, k2, *tb, nb, bottom, aad,
+                                aad_len, in, out, len, status, tag_len, done); });
     }
-    if ((e = want_lds(decrypt ? (const void *)k_ocb<NR, true> : (const void *)k_ocb<NR, false>)) != hipSuccess) return (int)e;
     const u64 nblocks = len >> 4;
     /* long associated data (whole blocks, 16-byte aligned) is hashed by all workgroups as a second walk */
     const u64 hblocks = ((u64)(aad_len >> 4) >= OCB_HASH_SPREAD && ((uintptr_t)aad & 15u) == 0) ? (u64)(aad_len >> 4) : 0;
@@ -730,10 +706,10 @@ static int launch_ocb(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *ek
         const u64 nchunks = (walk[w] >> 8) + 1;
         /* at least 8 runs per wave, so that an uneven split costs at most 1/8 */
         u32 run = OCB_RUN_MAX;
-        while (run > 1 && nchunks / run < 8ull * cu_count() * (UAES_WG / 64)) run >>= 1;
+        while (run > 1 && nchunks / run < 8ull * cus * (UAES_WG / 64)) run >>= 1;
         const u64 runs = (nchunks + run - 1) / run;
         /* short texts: 4-wave workgroups, so that the few chunks spread over more CUs */
-        const unsigned wgw = (runs + UAES_WG / 64 - 1) / (UAES_WG / 64) * 2 <= cu_count() ? 256u : UAES_WG;
+        const unsigned wgw = (runs + UAES_WG / 64 - 1) / (UAES_WG / 64) * 2 <= cus ? 256u : UAES_WG;
         runs_of[w] = run;
         if (wgw > wg) wg = wgw;
     }
@@ -743,18 +719,17 @@ static int launch_ocb(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *ek
         u64 g = (runs + wg / 64 - 1) / (wg / 64);
         if (g > grid) grid = g;
     }
-    if (grid > cu_count()) grid = cu_count();
+    if (grid > cus) grid = cus;
     if (grid > OCB_MAX_WGS) grid = OCB_MAX_WGS;
     const u32 run = runs_of[0];
     OcbArgs ka;
-    ka.ek = *ek; ka.dk = decrypt ? *dk : *ek; ka.tb = *tb; ka.nonce_block = nb; ka.scr = scr; ka.done_word = done_word;
+    ka.ek = *ek; ka.dk = k2; ka.tb = *tb; ka.nonce_block = nb; ka.scr = (uint4 *)scratch; ka.done_word = done_word;
     ka.nblocks = nblocks; ka.aad_len = aad_len; ka.len = len; ka.aad = (const unsigned char *)aad;
     ka.hash_blocks = hblocks; ka.run_aad = runs_of[1];
     ka.in = (const unsigned char *)in; ka.out = (unsigned char *)out; ka.status = status;
     ka.bottom = bottom; ka.run = run; ka.tag_len = tag_len; ka.done = done;
-    if (decrypt) hipLaunchKernelGGL((k_ocb<NR, true>), dim3((unsigned)grid), dim3(wg), OCB_LDS, st, ka);
-    else hipLaunchKernelGGL((k_ocb<NR, false>), dim3((unsigned)grid), dim3(wg), OCB_LDS, st, ka);
-    return (int)hipGetLastError();
+    return with_bool(decrypt, [&](auto DEC) {
+        return uaesk_launch(k_ocb<NR, decltype(DEC)::value>, (unsigned)grid, wg, OCB_LDS, st, ka); });
 }
 
 extern "C" size_t uaesk_ocb_scratch_bytes(void) { return 16u * (OCB_ROW_HASH + OCB_MAX_WGS); }
@@ -781,10 +756,6 @@ extern "C" int uaesk_ocb(void *stream, const uaesk_tables *tb, int nr,
     uint4 nb;
     memcpy(&nb, kt, 16);
     const u32 tl = (u32)tag_len;
-    switch (nr) {
-    case 10: return launch_ocb<10>(S(stream), tb, ek, dk, decrypt, nb, bottom, tl, aad, aad_len, in, len, out, scratch, done_word, status);
-    case 12: return launch_ocb<12>(S(stream), tb, ek, dk, decrypt, nb, bottom, tl, aad, aad_len, in, len, out, scratch, done_word, status);
-    case 14: return launch_ocb<14>(S(stream), tb, ek, dk, decrypt, nb, bottom, tl, aad, aad_len, in, len, out, scratch, done_word, status);
-    default: return (int)hipErrorInvalidValue;
-    }
+    DISPATCH_NR(nr, return launch_ocb<NR>(S(stream), tb, ek, dk, decrypt, nb, bottom, tl, aad, aad_len, in, len, out, scratch, done_word, status));
+    return 0;
 }

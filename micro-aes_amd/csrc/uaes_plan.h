@@ -5,8 +5,8 @@
  * (include/uaes_hip.h) returns the same answer as data, and tests/test_gpu_plan.py derives its parity cases from it:
  * it walks the sizes, finds every boundary b at which the answer changes and checks b - 16, b, b + 16 in both
  * directions (and a forged tag) against the oracle.  There is no other place where a size threshold decides what
- * runs, and no size threshold is read from the environment.  Three switches are: UAES_PLAN_DISABLE (the initial mask of
- * uaesk_plan_disable below), UAES_GCM_FOLD=0 (no counter word reaches the kernels, so the one-launch GCM forms become
+ * runs.  Three switches are read from the environment, and none of them moves a threshold: UAES_PLAN_DISABLE (the
+ * initial mask of uaesk_plan_disable below), UAES_GCM_FOLD=0 (no counter word reaches the kernels, so the one-launch GCM forms become
  * their two-launch forms and GCM-SIV takes the levels; the planners answer the same) and UAES_GCM_LOOK_TICKS (how long
  * the one-launch GCM kernel's preparing workgroup looks at the arrival counter; it does not change the arrangement).
  *

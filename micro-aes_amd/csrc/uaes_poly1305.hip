@@ -34,8 +34,6 @@
 #define POLY_MIN_STEPS  8u                        /* poly.chunks: blocks per lane at least, before the grid grows */
 #define POLY_WG_PER_CU  8u                        /* ... and at most this many workgroups per CU                 */
 
-static inline hipStream_t S(void *s) { return (hipStream_t)s; }
-
 /* a value mod p in five 26-bit limbs, least significant first */
 struct P5 {
     u32 v[5];
@@ -382,22 +380,12 @@ __global__ __launch_bounds__(PT) void k_poly_batch(uaesk_rk rk, const u32 *__res
 /* ---------------------------------------------------------------------------------------------------------------- */
 /* planning and launching                                                                                             */
 /* ---------------------------------------------------------------------------------------------------------------- */
-static int poly_cus(void)
-{
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) {
-        (void)hipGetLastError();
-        cus = 256;                                /* (no device: planned for an MI355X) */
-    }
-    return cus;
-}
-
 extern "C" int uaesk_plan_poly1305(size_t len, size_t nmsg, uaes_plan *p)
 {
     const u64 q = ((u64)len + 15) >> 4;
     memset(p, 0, sizeof *p);
     if (nmsg > 1) {
-        const u64 cap = (u64)poly_cus() * POLY_WG_PER_CU;
+        const u64 cap = (u64)uaesk_cus_or_256() * POLY_WG_PER_CU;
         const u64 want = ((u64)nmsg + PT / 64u - 1) / (PT / 64u);          /* a wave per message */
         p->arrangement = UAES_POLY_BATCH;
         p->launches = 1;
@@ -412,7 +400,7 @@ extern "C" int uaesk_plan_poly1305(size_t len, size_t nmsg, uaes_plan *p)
         p->steps = (unsigned)((q + PT - 1) / PT);
         return 0;
     }
-    const u64 cap = (u64)poly_cus() * POLY_WG_PER_CU;
+    const u64 cap = (u64)uaesk_cus_or_256() * POLY_WG_PER_CU;
     u64 want = (q + (u64)PT * POLY_MIN_STEPS - 1) / ((u64)PT * POLY_MIN_STEPS);
     if (want > cap) want = cap;
     if (want < 2) want = 2;
@@ -464,30 +452,18 @@ static void wipe_r(PolyR *r)
     for (int i = 0; i < 5; ++i) v[i] = 0;
 }
 
-#define DISPATCH_NR(nr, CALL)                         \
-    switch (nr) {                                     \
-    case 10: { constexpr int NR = 10; CALL; } break;  \
-    case 12: { constexpr int NR = 12; CALL; } break;  \
-    case 14: { constexpr int NR = 14; CALL; } break;  \
-    default: return (int)hipErrorInvalidValue;        \
-    }
-
 template <int NR>
 static int launch_one(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *ek, const PolyR &r, uint4 nonce,
                       const unsigned char *data, u64 len, unsigned char *mac, u32 *partial, const uaes_plan &p)
 {
     const bool a16 = (((uintptr_t)data) & 15u) == 0;
-    if (p.arrangement == UAES_POLY_SMALL) {
-        if (a16) hipLaunchKernelGGL((k_poly_small<NR, true>), dim3(1), dim3(PT), 0, st, *ek, tb->te0, r, nonce, data, len, mac);
-        else     hipLaunchKernelGGL((k_poly_small<NR, false>), dim3(1), dim3(PT), 0, st, *ek, tb->te0, r, nonce, data, len, mac);
-        return (int)hipGetLastError();
-    }
-    if (a16) hipLaunchKernelGGL((k_poly_chunks<true>), dim3(p.grid), dim3(PT), 0, st, r, data, len, partial);
-    else     hipLaunchKernelGGL((k_poly_chunks<false>), dim3(p.grid), dim3(PT), 0, st, r, data, len, partial);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((k_poly_fold<NR>), dim3(1), dim3(PT), 0, st, *ek, tb->te0, r, nonce, partial, (u32)p.grid, mac);
-    return (int)hipGetLastError();
+    if (p.arrangement == UAES_POLY_SMALL)
+        return with_bool(a16, [&](auto A16) {
+            return uaesk_launch(k_poly_small<NR, decltype(A16)::value>, 1, PT, 0, st, *ek, tb->te0, r, nonce, data, len, mac); });
+    const int rc = with_bool(a16, [&](auto A16) {
+        return uaesk_launch(k_poly_chunks<decltype(A16)::value>, p.grid, PT, 0, st, r, data, len, partial); });
+    if (rc) return rc;
+    return uaesk_launch(k_poly_fold<NR>, 1, PT, 0, st, *ek, tb->te0, r, nonce, partial, p.grid, mac);
 }
 
 /* one message: data / mac16 / scratch device memory (scratch: uaesk_poly1305_scratch_bytes(len), may be NULL when
@@ -513,9 +489,8 @@ static int launch_batch(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *
                         u64 nmsg, u64 msg_bytes, const unsigned char *data, unsigned char *macs, unsigned grid)
 {
     const bool a16 = ((((uintptr_t)data) | msg_bytes) & 15u) == 0;
-    if (a16) hipLaunchKernelGGL((k_poly_batch<NR, true>), dim3(grid), dim3(PT), 0, st, *ek, tb->te0, r, nonces, nmsg, msg_bytes, data, macs);
-    else     hipLaunchKernelGGL((k_poly_batch<NR, false>), dim3(grid), dim3(PT), 0, st, *ek, tb->te0, r, nonces, nmsg, msg_bytes, data, macs);
-    return (int)hipGetLastError();
+    return with_bool(a16, [&](auto A16) {
+        return uaesk_launch(k_poly_batch<NR, decltype(A16)::value>, grid, PT, 0, st, *ek, tb->te0, r, nonces, nmsg, msg_bytes, data, macs); });
 }
 
 /* nmsg messages of msg_bytes each, back to back; nonces (16 bytes each), data and macs device memory */

@@ -197,22 +197,8 @@ extern "C" int uaesk_gcmsiv_small(void *stream, const uaesk_tables *tb, int nr, 
     src.has_len = 1; src.len_aad = aad_len; src.len_ct = len; src.rev = 1;
     uint4 nn = make_uint4(0, 0, 0, 0);
     memcpy(&nn, nonce12, 12);
-    hipStream_t st = S(stream);
-    hipError_t e;
-#define SIV_LAUNCH(NRV, D)                                                                                          \
-    do {                                                                                                            \
-        e = uaesk_want_lds((const void *)k_siv_small<NRV, D>, (unsigned)(SIV_LDS_TOTAL));                           \
-        if (e != hipSuccess) return (int)e;                                                                         \
-        hipLaunchKernelGGL((k_siv_small<NRV, D>), dim3(1), dim3(GH_T), SIV_LDS_TOTAL, st, *mk, *tb, nn, src,        \
-                           (const uint4 *)in, (uint4 *)out,                                                         \
-                           (D) ? (unsigned char *)in + len : (unsigned char *)out + len, status);                   \
-    } while (0)
-    switch (nr) {
-    case 10: if (decrypt) SIV_LAUNCH(10, true); else SIV_LAUNCH(10, false); break;
-    case 12: if (decrypt) SIV_LAUNCH(12, true); else SIV_LAUNCH(12, false); break;
-    case 14: if (decrypt) SIV_LAUNCH(14, true); else SIV_LAUNCH(14, false); break;
-    default: return (int)hipErrorInvalidValue;
-    }
-#undef SIV_LAUNCH
-    return (int)hipGetLastError();
+    DISPATCH_NR(nr, return with_bool(decrypt, [&](auto DEC) {
+        return uaesk_launch(k_siv_small<NR, decltype(DEC)::value>, 1, GH_T, SIV_LDS_TOTAL, S(stream), *mk, *tb, nn, src, in, out,
+                            DEC ? (unsigned char *)in + len : (unsigned char *)out + len, status); }));
+    return 0;
 }

@@ -79,6 +79,52 @@ def test_the_table_has_the_boundaries_the_design_names():
     assert [r[2][0] for r in boundaries(lambda n: regime("ocb", n), 0, 64 * MIB)] == ["ocb.runs"]
 
 
+def test_every_planner_sees_this_devices_cu_count():
+    """Plan only (no kernel runs): every planner family, asked for a call large enough to fill the device, reports the
+    workgroup count that follows from ONE CU count -- the device's own, read here through torch.  The kernel files
+    used to count the CUs in five places of their own (a process-wide variable, three per-file statics, a query per
+    call); they now share uaesk_cus() (csrc/uaes_launch.hip.h), and this shows that the planners which report a workgroup
+    count agree with each other and with the device.  Expected values are the parent code's functions of the CU count: the count itself for
+    the grids capped at one workgroup per CU, eight per CU for Poly1305, one round of chunk workgroups for the
+    tag-first GCM decryption and GCM-SIV (medium_steps, csrc/uaes_gcm.hip), tests/counters.py stripe_geometry for the
+    striped GCM.  XTS's bulk row and OCB's row report no workgroup count (0): only their launchers use it,
+    so OCB's use of the count and the bulk XTS launcher's are NOT shown here (the OCB tests that compare against the
+    oracle run those launchers)."""
+    import torch
+    from tests.counters import stripe_geometry
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    gib, many = 1 << 30, 1 << 24
+    # csrc/uaes_kernels.hip (grid_for): ECB, CTR, one XTS unit on one block per lane
+    assert uaes.plan("ecb", gib) == ("ecb.tiled", 1, cus, 0) and uaes.plan("ecb", gib, 0, 1) == ("ecb.tiled", 1, cus, 0)
+    assert uaes.plan("ctr", gib) == ("ctr.striped", 1, cus, 0)
+    assert uaes.plan("xts", gib, 1) == ("xts.bulk", 3, 0, 0)
+    assert uaes.plan("xts", 8 * MIB, 1) == ("xts.small", 1, min(8 * MIB // 16 // 1024, cus), 0)
+    # csrc/uaes_gcm.hip: the striped pass needs a stripe per workgroup of a grid of one workgroup per CU ...
+    _h0, _g_lo, n8, _h1 = stripe_geometry(2, gib // 16, cus)                   # (12-byte nonce: the first counter is 2)
+    assert n8 >= cus and uaes.plan("gcm", gib) == ("gcm.striped", 3, cus, 0)
+    # ... and the chunk workgroups are one round: the fewest positions per thread (a power of two) with which they fit
+    nvh = 256 * MIB // 16
+    steps = next(1 << lg for lg in range(8) if -(-nvh // (1024 << lg)) <= cus)
+    assert uaes.plan("gcm", 256 * MIB, 0, 1) == ("gcm.chunks", 2, -(-nvh // (1024 * steps)), steps)
+    assert uaes.plan("siv", 256 * MIB) == ("siv.chunks", 3, -(-nvh // (1024 * steps)), steps)
+    assert -(-nvh // (1024 * steps)) > cus // 2
+    # csrc/uaes_ocb.hip
+    assert uaes.plan("ocb", gib) == ("ocb.runs", 1, 0, 0)
+    # csrc/uaes_chain.hip: the parallel decryptions and the batches of chains
+    for mode in ("cbc", "cfb", "cbc_nocts"):
+        assert uaes.chain_plan(mode, gib, decrypt=True) == ("fbdec.tiled", 1, cus, 1024), mode
+    for what in ("cbc_batch", "cmac_batch"):
+        assert uaes.chain_plan(what, 16, many) == ("batch.lane", 1, cus, 1024), what
+    # csrc/uaes_eax_siv.hip: the batches of records
+    for siv, name in ((False, "eax.batch"), (True, "s2v.batch")):
+        for dec in (False, True):
+            assert uaes.eax_siv_plan(siv, 64, many, decrypt=dec)[:3] == (name, 1, cus), (siv, dec)
+    # csrc/uaes_poly1305.hip: eight workgroups per CU
+    q = gib // 16
+    assert uaes.poly1305_plan(gib) == ("poly.chunks", 2, 8 * cus, -(-q // (8 * cus * 256)))
+    assert uaes.poly1305_plan(64, many)[:3] == ("poly.batch", 1, 8 * cus)
+
+
 def test_ecb_and_ctr_at_every_boundary(orc):
     rnd = random.Random(601)
     for bits in (128, 256):
