@@ -44,7 +44,9 @@
 #ifndef CTS                  /* micro_aes.h:56 -- CBC ciphertext stealing (CS3).  A caller built with -DCTS=0 gets   */
 #define CTS      1          /* the reference's other CBC: last chunk padded (AES_PADDING), whole-block decrypt   */
 #endif
-#define KWA      0
+#ifndef KWA                  /* micro_aes.h:50 -- key wrap, RFC 3394 (uaes_kw.hip); every library exports AES_KEY_wrap /  */
+#define KWA      0          /* AES_KEY_unwrap, a caller built with -DKWA=1 sees the prototypes (below)                */
+#endif
 #define FPE      0
 #ifndef EAX                  /* micro_aes.h:43 -- EAX (uaes_eax_siv.hip); every library exports AES_EAX_*, a caller */
 #define EAX      0          /* built with -DEAX=1 sees the prototypes (below)                                       */
@@ -381,6 +383,17 @@ void AES_SIV_encrypt(const uint8_t *keys,
 char AES_SIV_decrypt(const uint8_t *keys, const uint8_t iv[16],
                      const void *aData, const size_t aDataLen,
                      const void *crtxt, const size_t crtxtLen, void *pntxt);
+#endif
+
+#if KWA
+/* RFC 3394 (micro_aes.c:1829-1894): wrapped = secretLen + 8 bytes; M_DATALENGTH_ERROR unless secretLen is a multiple of 8
+ * and at least 16 (unwrap: wrapLen at least 24), nothing written then.  unwrap returns M_AUTHENTICATION_ERROR when the
+ * integrity value is not A6 x 8 and, like the reference, leaves what it computed in secret.  An engine failure makes
+ * wrap return M_ENCRYPTION_ERROR and unwrap M_DECRYPTION_ERROR. */
+char AES_KEY_wrap(const uint8_t *kek,
+                  const void *secret, const size_t secretLen, void *wrapped);
+char AES_KEY_unwrap(const uint8_t *kek,
+                    const void *wrapped, const size_t wrapLen, void *secret);
 #endif
 
 #if POLY1305

@@ -99,12 +99,12 @@ int         uaes_stream_release(void *stream);
  * GPU and fails loudly without one.  Three independent, process-wide switches for the cases a GPU serves badly:
  *   max_bytes  calls whose data pointers are HOST memory and whose text is at most this long run on the host: a
  *              launch costs 12-20 us whatever the size, one host core needs that long for ~1 KiB (GCM ~200 B);
- *   chains     ONE serial chain in host memory -- CBC / CFB encryption, OFB, CMAC, CCM -- runs on the host whatever
+ *   chains     ONE serial chain in host memory -- CBC / CFB encryption, OFB, CMAC, CCM, key wrap -- runs on the host whatever
  *              its length (a chain is a latency-bound single wave on the GPU: 36 MiB/s; uaes_*_batch are the GPU's form);
  *   fallback   with NO usable HIP device the calls below run on the host instead of returning UAES_E_HIP -- the
  *              reference's `void` functions cannot report an error.
  * Covered: every synchronous one-message call of this header -- ECB, CTR, XTS (unit and sectors), GCM (any nonce / tag
- * length), CBC (CTS and CTS-0 forms), CFB, OFB, CMAC, CCM, GCM-SIV, OCB.  Not covered (always GPU): the *_dev / *_batch
+ * length), CBC (CTS and CTS-0 forms), CFB, OFB, CMAC, CCM, GCM-SIV, OCB, KW.  Not covered (always GPU): the *_dev / *_batch
  * / record / key-context / stream / mgpu calls, uaes_ghash, and any call that is handed a device pointer.
  * Environment, read at first use: UAES_HOST_MAX=<bytes>, UAES_HOST_CHAINS=1, UAES_HOST_FALLBACK=1; or
  * UAES_HOST_POLICY=recommended = (4096, 1, 1), the measured crossover on the builder's hosts (profiles/r05_host_policy.md),
@@ -306,6 +306,31 @@ int uaes_cbc_encrypt_batch(int keybits, const uint8_t *key, const uint8_t *ivs, 
                            size_t msg_bytes, const void *pntxt, void *crtxt);
 int uaes_cmac_batch(int keybits, const uint8_t *key, size_t nmsg, size_t msg_bytes,
                     const void *data, uint8_t *macs);
+
+/* ---- KW: replaces AES_KEY_wrap / AES_KEY_unwrap (RFC 3394, SP 800-38F KW) ------
+ * micro_aes.c:1829-1894.  kek = the key-encryption key (host memory).  wrap writes secretLen + 8 bytes: A || R_1..R_n
+ * after 6 n chained block encryptions over the n = secretLen / 8 semiblocks; secretLen % 8 != 0 or n < 2 ->
+ * UAES_E_DATALENGTH, wrapped untouched.  unwrap runs the chain backwards with the inverse cipher and writes
+ * wrapLen - 8 bytes; wrapLen % 8 != 0 or wrapLen / 8 < 3 -> UAES_E_DATALENGTH, secret untouched; if A does not come
+ * out as A6 x 8 it returns UAES_E_AUTHENTICATION and, like the reference, leaves what the chain made in secret (zeros
+ * under uaes_set_wipe_on_auth_failure(1)).  Data pointers host or device memory at any byte offset; the buffers are
+ * disjoint, or the secret sits 8 bytes into the wrapped buffer (secret == (uint8_t *)wrapped + 8, the reference's own
+ * in-place form); any other overlap is undefined.  The host policy applies (one serial chain: `chains`).
+ * One wave walks the chain, sixteen lanes per block: a secret of up to 4 KiB keeps its semiblocks in LDS, a longer one
+ * is worked on in place in device memory with its loads issued a chunk of steps ahead.  No rate is stated: none has
+ * been measured yet (tools/kw_rate.py times one call, the batches and a chain step in both directions on the GPU and
+ * writes profiles/kw_rate.md, which does not exist yet).
+ * Batches: nkeys records of one length under one kek, back to back -- secret m at m * secret_bytes, wrapped record m at
+ * m * (secret_bytes + 8) -- sixteen GPU lanes per record, always on the GPU; a record holds at most 256 bytes of secret
+ * (UAES_E_ARG beyond; a 2048-bit secret fits), lengths as above (UAES_E_DATALENGTH).  unwrap_batch sets verdicts[m] =
+ * 1 (authentic) / 0 for every record, returns UAES_E_AUTHENTICATION if any record failed and follows the wipe switch
+ * per record, as uaes_siv_decrypt_batch does.  Arrays host or device memory; the batches have no in-place form.      */
+int uaes_kw_wrap(int keybits, const uint8_t *kek, const void *secret, size_t secretLen, void *wrapped);
+int uaes_kw_unwrap(int keybits, const uint8_t *kek, const void *wrapped, size_t wrapLen, void *secret);
+int uaes_kw_wrap_batch(int keybits, const uint8_t *kek, size_t nkeys, size_t secret_bytes,
+                       const void *secrets, void *wrapped);
+int uaes_kw_unwrap_batch(int keybits, const uint8_t *kek, size_t nkeys, size_t wrapped_bytes,
+                         const void *wrapped, void *secrets, uint8_t *verdicts);
 
 /* Poly1305-AES (micro_aes.c:1955-1997): keys = k (keybits / 8 bytes) || r (16 bytes), mac = (h + AES_k(nonce)) mod
  * 2^128 with h the Poly1305 polynomial in the clamped r.  Block-parallel on the VALU (uaes_poly1305.hip): one
@@ -604,6 +629,13 @@ const char *uaes_debug_plan_eax_siv(int siv, int dir, size_t len, size_t nmsg, i
  * message), or NULL for arguments that make no sense.  Works without a device (a 256-CU MI355X).
  * tests/test_gpu_chains.py derives its sizes and message counts from this. */
 const char *uaes_debug_plan_chain(int what, int dir, size_t a, size_t b, int out[3]);
+/* The planner of key wrap (csrc/uaes_plan.h, its own rows): dir 0 wrap / 1 unwrap; len = bytes of the SECRET in either
+ * direction; nkeys 0 = uaes_kw_wrap / uaes_kw_unwrap, nkeys >= 1 = a batch of that many records.  out (may be NULL)
+ * receives { launches, workgroups, threads per workgroup } (a batch: sixteen threads per record).  Returns "kw.lds"
+ * (the semiblocks in LDS), "kw.global" (in place in the output buffer) or "kw.batch", or NULL for arguments that make
+ * no sense: a length that is no multiple of 8 or below 16, a batch record above the limit.  Works without a device (a
+ * 256-CU MI355X).  tests/test_gpu_kw.py finds the two boundaries by walking this. */
+const char *uaes_debug_plan_kw(int dir, size_t len, size_t nkeys, int out[3]);
 
 /* Test hooks of the one-launch GCM / GCM-SIV / streamed-piece arrangements (chunk workgroups + one preparing workgroup
  * in ONE launch; whoever of them arrives last on a counter word folds the chunk hashes and makes the tag -- nobody

@@ -46,6 +46,7 @@ EXPORTS = [
     "uaes_eax_encrypt", "uaes_eax_decrypt", "uaes_siv_encrypt", "uaes_siv_decrypt",
     "uaes_eax_encrypt_batch", "uaes_eax_decrypt_batch", "uaes_siv_encrypt_batch", "uaes_siv_decrypt_batch",
     "uaes_debug_plan_eax_siv", "uaes_debug_plan_chain",
+    "uaes_kw_wrap", "uaes_kw_unwrap", "uaes_kw_wrap_batch", "uaes_kw_unwrap_batch", "uaes_debug_plan_kw",
     "uaes_mgpu_ctr_xcrypt_at", "uaes_mgpu_xts_sectors", "uaes_mgpu_ctr_encrypt_gather", "uaes_debug_gather_stats", "uaes_debug_gcm_look", "uaes_debug_gcm_chunk_folds",
     "uaes_debug_plan", "uaes_debug_plan_at", "uaes_debug_arrangement_name", "uaes_debug_plan_disable",
     "uaes_mgpu_ecb_encrypt", "uaes_mgpu_ecb_decrypt", "uaes_mgpu_gcm_encrypt", "uaes_mgpu_gcm_decrypt",
@@ -70,7 +71,7 @@ COMPAT_EXPORTS = [
     "AES_GCM_encrypt_ivlen", "AES_GCM_decrypt_ivlen", "AES_GCM_encrypt_lens", "AES_GCM_decrypt_lens",
     "AES_CCM_encrypt_lens", "AES_CCM_decrypt_lens", "AES_OCB_encrypt_lens", "AES_OCB_decrypt_lens",
     "AES_CCM_encrypt", "AES_CCM_decrypt", "AES_CMAC", "GCM_SIV_encrypt", "GCM_SIV_decrypt",
-    "AES_OCB_encrypt", "AES_OCB_decrypt", "AES_Poly1305",
+    "AES_OCB_encrypt", "AES_OCB_decrypt", "AES_Poly1305", "AES_KEY_wrap", "AES_KEY_unwrap",
     "AES_EAX_encrypt", "AES_EAX_decrypt", "AES_EAX_encrypt_lens", "AES_EAX_decrypt_lens", "AES_SIV_encrypt", "AES_SIV_decrypt",
     "AES_CBC_encrypt", "AES_CBC_decrypt", "AES_CFB_encrypt", "AES_CFB_decrypt", "AES_OFB_encrypt", "AES_OFB_decrypt",
 ]
@@ -158,6 +159,12 @@ def engine():
     L.uaes_debug_plan_poly1305.restype = C.c_char_p
     L.uaes_debug_plan_chain.argtypes = [i, i, sz, sz, C.POINTER(C.c_int)]
     L.uaes_debug_plan_chain.restype = C.c_char_p
+    L.uaes_kw_wrap.argtypes = [i, vp, vp, sz, vp]
+    L.uaes_kw_unwrap.argtypes = [i, vp, vp, sz, vp]
+    L.uaes_kw_wrap_batch.argtypes = [i, vp, sz, sz, vp, vp]
+    L.uaes_kw_unwrap_batch.argtypes = [i, vp, sz, sz, vp, vp, vp]
+    L.uaes_debug_plan_kw.argtypes = [i, sz, sz, C.POINTER(C.c_int)]
+    L.uaes_debug_plan_kw.restype = C.c_char_p
     for n in ("uaes_cbc_encrypt", "uaes_cbc_decrypt", "uaes_cbc_decrypt_blocks", "uaes_cfb_encrypt", "uaes_cfb_decrypt", "uaes_ofb_xcrypt"):
         getattr(L, n).argtypes = [i, vp, vp, vp, sz, vp]
     for n in ("uaes_ccm_encrypt", "uaes_ccm_decrypt", "uaes_gcmsiv_encrypt", "uaes_gcmsiv_decrypt",
@@ -224,7 +231,7 @@ def engine():
             continue
         if n not in ("uaes_last_error", "uaes_version", "uaes_gcm_key_free", "uaes_gcm_stream_abort", "uaes_debug_gather_stats", "uaes_debug_gcm_look",
                      "uaes_debug_arrangement_name", "uaes_debug_plan_disable", "uaes_debug_plan_poly1305",
-                     "uaes_debug_plan_eax_siv", "uaes_debug_plan_chain"):
+                     "uaes_debug_plan_eax_siv", "uaes_debug_plan_chain", "uaes_debug_plan_kw"):
             getattr(L, n).restype = i
     _lib = L
     return L
@@ -616,6 +623,69 @@ def chain_plan(what, a, b=0, decrypt=False):
     if name is None:
         raise ValueError("no plan for %s of %d bytes (%d messages, decrypt=%s)" % (what, a, b, bool(decrypt)))
     return name.decode(), out[0], out[1], out[2]
+
+
+def AES_KEY_wrap(kek, secret, prefill=0):
+    """micro_aes.c:1829 (RFC 3394).  Returns (code, output buffer of len(secret) + 8 bytes): code 1 for a secret that is
+    no multiple of 8 bytes or shorter than 16, the buffer untouched then."""
+    n = len(secret) + 8
+    o = _out(n, prefill)
+    rc = _check(engine().uaes_kw_wrap(_bits(kek), _in(kek), _in(secret), len(secret), o), "AES_KEY_wrap")
+    return rc, bytes(o)[:n]
+
+
+def AES_KEY_unwrap(kek, wrapped, prefill=0):
+    """micro_aes.c:1865.  Returns (code, output buffer of len(wrapped) - 8 bytes); like the reference the unwrapped
+    bytes are returned even when the code is 0x1A (zeros under the wipe switch)."""
+    n = max(len(wrapped) - 8, 0)
+    o = _out(n, prefill)
+    rc = _check(engine().uaes_kw_unwrap(_bits(kek), _in(kek), _in(wrapped), len(wrapped), o), "AES_KEY_unwrap")
+    return rc, bytes(o)[:n]
+
+
+def kw_batch(kek, records, unwrap=False, prefill=0):
+    """Key wrap of many equal-sized records under one key-encryption key (uaes_kw_*_batch).  wrap: returns (code, wrapped
+    records); unwrap: returns (code, secrets, verdicts)."""
+    n = len(records)
+    if n == 0:
+        return (0, [], []) if unwrap else (0, [])
+    rl, rb = _records(records, "records")
+    ol = rl - 8 if unwrap else rl + 8
+    o = _out(n * max(ol, 0), prefill)
+    L = engine()
+    if not unwrap:
+        rc = _check(L.uaes_kw_wrap_batch(_bits(kek), _in(kek), n, rl, _in(rb), o), "uaes_kw_wrap_batch")
+        raw = bytes(o)
+        return rc, [raw[i * ol:(i + 1) * ol] for i in range(n)]
+    v = _out(n)
+    rc = _check(L.uaes_kw_unwrap_batch(_bits(kek), _in(kek), n, rl, _in(rb), o, v), "uaes_kw_unwrap_batch")
+    raw = bytes(o)
+    return rc, [raw[i * ol:(i + 1) * ol] for i in range(n)], list(bytes(v)[:n])
+
+
+def kw_plan(length, nkeys=0, unwrap=False):
+    """What a key wrap of a secret of `length` bytes would run (uaes_debug_plan_kw; nkeys 0: the one-secret calls, else a
+    batch): (arrangement, launches, workgroups, threads per workgroup), or None for arguments that make no sense."""
+    out = (C.c_int * 3)()
+    name = engine().uaes_debug_plan_kw(int(bool(unwrap)), length, nkeys, out)
+    return None if name is None else (name.decode(), out[0], out[1], out[2])
+
+
+_compat = {}
+
+
+def compat(bits):
+    """libmicro_aes_hip_<bits>.so (the reference's compile-time API, include/micro_aes.h) with the prototypes of the
+    key-wrap pair attached: char AES_KEY_wrap(kek, secret, secretLen, wrapped), char AES_KEY_unwrap(kek, wrapped,
+    wrapLen, secret)."""
+    if bits not in _compat:
+        engine()
+        lib = C.CDLL(lib_path("libmicro_aes_hip_%d.so" % bits))
+        for n in ("AES_KEY_wrap", "AES_KEY_unwrap"):
+            getattr(lib, n).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+            getattr(lib, n).restype = C.c_char
+        _compat[bits] = lib
+    return _compat[bits]
 
 
 def _ccm_nonce(nonce):

@@ -817,4 +817,87 @@ __device__ __forceinline__ void row_walk(const unsigned char *p, u64 nblk, u32 c
     }
 }
 
+/* ---- the INVERSE cipher, sixteen lanes per block (key unwrap, uaes_kw.hip: the one chain of AES^-1 in the tree) ----
+ * row_encrypt's arrangement with the equivalent inverse cipher (FIPS-197 sec. 5.3.5): lane i = (column i / 4, row
+ * i % 4) looks byte r of its column word up in Td_r = rotl(Td0, 8 r).  InvShiftRows moves row r of column c to column
+ * c + r, so output column c' takes row r from column c' - r: lane 4 (c' - r) + r = 4 c' - 3 r, i.e. lanes
+ * i, i + 13, i + 10, i + 7 (mod 16) where encryption takes i, i + 5, i + 10, i + 15:
+ *     y = t ^ row_ror:3(t)      t[i] ^ t[i + 13]
+ *     z = y ^ row_ror:6(y)      t[i] ^ t[i + 13] ^ t[i + 10] ^ t[i + 7]     (13 + 10 = 7 mod 16)
+ * and quad_perm:[0,0,0,0] hands the sum of lane 4 c' to the quad.  The last round has no InvMixColumns: its table
+ * holds Si[x] in every byte and lsel keeps byte r, as in row_encrypt; Si[x] is the XOR of the four bytes of Td0[x]
+ * (uaes_device.h), built while the tables are filled.  Same LDS layouts as the encrypting fills, filled from Td0 and
+ * the dk round keys, so row_lane / row4_lane serve both directions.                                                */
+__device__ __forceinline__ u32 row_si_word(u32 td)
+{
+    const u32 g = td ^ (td >> 16), s = (g ^ (g >> 8)) & 0xffu;
+    return s * 0x01010101u;
+}
+
+__device__ __forceinline__ void row_fill_tables_dec(const u32 *__restrict__ td0, const uaesk_rk &dk)
+{
+    for (u32 j0 = threadIdx.x; j0 < 2048u; j0 += 16u * blockDim.x) {       /* as row_fill_tables: sixteen words at a time */
+        u32 t[16];
+#pragma unroll
+        for (u32 k = 0; k < 16; ++k) {
+            const u32 j = j0 + k * blockDim.x;
+            t[k] = td0[(j < 2048u ? j : 0u) >> 3];
+        }
+#pragma unroll
+        for (u32 k = 0; k < 16; ++k) {
+            const u32 j = j0 + k * blockDim.x;
+            if (j < 2048u) {
+                const u32 q = j & 7u, x = j >> 3;
+                const u32 t0 = t[k], t1 = rotl32(t0, 8), t2 = rotl32(t0, 16), t3 = rotl32(t0, 24), si = row_si_word(t0);
+                *(uint4 *)(uaes_lds + x * 256u + 16u * q) = q < 4u ? make_uint4(t0, t1, t2, t3) : make_uint4(si, si, si, si);
+            }
+        }
+    }
+    for (u32 i = threadIdx.x; i < 60u; i += blockDim.x) ((u32 *)(uaes_lds + 65536u))[i] = dk.w[i];
+    __syncthreads();
+}
+
+__device__ __forceinline__ void row4_fill_tables_dec(const u32 *__restrict__ td0, const uaesk_rk &dk)
+{
+    for (u32 j0 = threadIdx.x; j0 < 8192u; j0 += 8u * blockDim.x) {      /* as row4_fill_tables */
+        u32 t[8];
+#pragma unroll
+        for (u32 k = 0; k < 8; ++k) {
+            const u32 j = j0 + k * blockDim.x;
+            t[k] = td0[(j < 8192u ? j : 0u) >> 5];
+        }
+#pragma unroll
+        for (u32 k = 0; k < 8; ++k) {
+            const u32 j = j0 + k * blockDim.x;
+            if (j < 8192u) {
+                const u32 q = j & 31u, x = j >> 5;
+                const u32 t0 = t[k], t1 = rotl32(t0, 8), t2 = rotl32(t0, 16), t3 = rotl32(t0, 24), si = row_si_word(t0);
+                *(uint4 *)(uaes_lds + (q >> 4) * 65536u + x * 256u + 16u * (q & 15u)) =
+                    q < 16u ? make_uint4(t0, t1, t2, t3) : make_uint4(si, si, si, si);
+            }
+        }
+    }
+    for (u32 i = threadIdx.x; i < 60u; i += blockDim.x) ((u32 *)(uaes_lds + 131072u))[i] = dk.w[i];
+    __syncthreads();
+}
+
+/* w = this lane's column word of the block (no round key applied) -> the same of its decryption; L from row_lane /
+ * row4_lane over tables filled by row_fill_tables_dec / row4_fill_tables_dec                                        */
+template <int NR>
+__device__ __forceinline__ u32 row_decrypt(u32 w, const RowLane<NR> &L)
+{
+    w ^= L.kc[0];
+    u32 addr = __builtin_amdgcn_perm(w, L.tmain, L.sel);
+#pragma unroll
+    for (int r = 1; r <= NR; ++r) {
+        u32 t = lds_word(addr);
+        if (r == NR) t = __builtin_amdgcn_perm(t, 0u, L.lsel);
+        const u32 y = t ^ row_dpp<0x123>(t);          /* row_ror:3 = take lane i+13 */
+        const u32 z = y ^ row_dpp<0x126>(y);          /* row_ror:6 = take lane i+10 */
+        w = L.kc[r] ^ row_dpp<0x00>(z);               /* quad_perm:[0,0,0,0]        */
+        if (r < NR) addr = __builtin_amdgcn_perm(w, r + 1 < NR ? L.tmain : L.tlast, L.sel);
+    }
+    return w;
+}
+
 #endif

@@ -6,9 +6,10 @@
 #include <stdio.h>
 #include <stdlib.h>
 
-#define POLY1305 1                  /* the libraries export AES_Poly1305, AES_EAX_* and AES_SIV_* whatever a */
+#define POLY1305 1                  /* the libraries export AES_Poly1305, AES_EAX_*, AES_SIV_* and AES_KEY_* whatever a */
 #define EAX      1                  /* caller's switches say                                                 */
 #define SIV      1
+#define KWA      1
 #include "../../include/micro_aes.h"
 #include "../../include/uaes_hip.h"
 
@@ -213,6 +214,16 @@ void AES_CMAC(const uint8_t *key, const void *data, const size_t dataSize, uint8
 void AES_Poly1305(const uint8_t *keys, const uint8_t nonce[16], const void *data, const size_t dataSize, uint8_t mac[16])
 {
     must("AES_Poly1305", uaes_poly1305(KB, keys, nonce, data, dataSize, mac));
+}
+
+char AES_KEY_wrap(const uint8_t *kek, const void *secret, const size_t secretLen, void *wrapped)
+{
+    return soft("AES_KEY_wrap", uaes_kw_wrap(KB, kek, secret, secretLen, wrapped), M_ENCRYPTION_ERROR);
+}
+
+char AES_KEY_unwrap(const uint8_t *kek, const void *wrapped, const size_t wrapLen, void *secret)
+{
+    return soft("AES_KEY_unwrap", uaes_kw_unwrap(KB, kek, wrapped, wrapLen, secret), M_DECRYPTION_ERROR);
 }
 
 /* CTS (micro_aes.h:56) is the caller's compile-time choice too: with CTS 0 the reference's CBC pads its last

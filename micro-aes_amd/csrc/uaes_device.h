@@ -269,6 +269,19 @@ int uaesk_s2v_batch(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk
                     int decrypt, int wipe, const void *aad, size_t aad_bytes,
                     size_t nmsg, size_t msg_bytes, const void *in, void *out, void *ivs, void *verdicts, int *bad);
 
+/* AES key wrap, RFC 3394 (uaes_kw.hip; AES_KEY_wrap / AES_KEY_unwrap, micro_aes.c:1829-1894); device pointers at any
+ * byte offset.  secret_len = bytes of the secret (a multiple of 8, >= 16) in both directions.  wrap: in = the secret,
+ * out receives secret_len + 8 bytes; unwrap: in = the wrapped form (secret_len + 8 bytes), out receives the secret
+ * whatever the verdict and *status = 0 / 0x1A.  in and out are disjoint, or the secret sits 8 bytes into the wrapped
+ * buffer.  ek / dk: encryption / equivalent-inverse keys (wrap reads ek, unwrap dk).
+ * Batch: nkeys records of secret_bytes (<= UAES_KW_BATCH_MAX) back to back, wrapped record m at m (secret_bytes + 8);
+ * unwrap writes verdicts[m] (1 = authentic), ORs 1 into *bad for a forgery and zeroes a forged record when wipe. */
+int uaesk_kw(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, const uaesk_rk *dk, int unwrap,
+             const void *in, size_t secret_len, void *out, int *status);
+int uaesk_kw_batch(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, const uaesk_rk *dk,
+                   int unwrap, int wipe, size_t nkeys, size_t secret_bytes, const void *in, void *out,
+                   void *verdicts, int *bad);
+
 /* Device self-test of the primitives; writes a bitmask of failures.        */
 int uaesk_selftest(void *stream, const uaesk_tables *tb, const uaesk_rk *ek128,
                    const uaesk_rk *dk128, unsigned *d_result);

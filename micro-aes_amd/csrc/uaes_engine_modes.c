@@ -943,6 +943,149 @@ int uaes_cmac_batch(int keybits, const uint8_t *key, size_t nmsg, size_t msg_byt
 }
 
 /* ------------------------------------------------------------------------ */
+/* key wrap, RFC 3394 (AES_KEY_wrap / AES_KEY_unwrap, micro_aes.c:1829-1894)    */
+/* ------------------------------------------------------------------------ */
+/* One serial chain of 6 n block operations, one wave (uaes_kw.hip).  A secret of at most UAES_KW_LDS_MAX bytes in host
+ * memory travels like any short text (plan_io: the mapped pinned buffers); the kernel reads all of it before it writes,
+ * so plan_io's one staging buffer for both directions is fine.  A longer one is worked on in place in the output
+ * buffer, which therefore is device memory of its own -- never the mapped host window, and never the input's staging
+ * buffer (the secret sits 8 bytes into the wrapped form).  Device buffers go to the kernels as they are, at any byte
+ * offset, the in-place form secret == wrapped + 8 included. */
+static int kw_io(lane *L, const void *in, size_t in_len, void *out, size_t out_len, size_t secret_len, io_plan *io)
+{
+    void *d_in, *d_out;
+    int rc;
+    if (secret_len <= UAES_KW_LDS_MAX && !(is_device_ptr(in) && is_device_ptr(out)))
+        return plan_io(L, in, in_len, out, out_len, io);
+    memset(io, 0, sizeof *io);
+    if ((rc = stage_text(L, 0, in, in_len, 1, &d_in)) != 0) return rc;
+    if ((rc = stage_text(L, 1, out, out_len, 0, &d_out)) != 0) return rc;
+    io->din = d_in;
+    io->dout = d_out;
+    io->user_out = out;
+    io->L = L;
+    io->out_is_host = !is_device_ptr(out);
+    io->copy_back = io->out_is_host;
+    return 0;
+}
+
+int uaes_kw_wrap(int keybits, const uint8_t *kek, const void *secret, size_t secretLen, void *wrapped)
+{
+    context *c;
+    lane *L;
+    keysched ks;
+    io_plan io;
+    int rc;
+    if ((rc = expand_key(&ks, kek, keybits)) != 0) return rc;
+    if (secretLen % 8 || secretLen / 8 < 2) { burn(&ks, sizeof ks); return UAES_E_DATALENGTH; }     /* (:1837) */
+    if (!secret || !wrapped) { burn(&ks, sizeof ks); return fail(UAES_E_ARG, "NULL pointer"); }
+    if (secretLen > (size_t)-1 - 8) { burn(&ks, sizeof ks); return fail(UAES_E_ARG, "length overflows"); }
+    if (host_take(secret, wrapped, secretLen, 1)) {
+        const uaesh_key hk = host_key(&ks);
+        HOST_RET(ks, uaesh_kw_wrap(&hk, (const uint8_t *)secret, secretLen, (uint8_t *)wrapped));
+    }
+    if ((rc = enter(&c, &L)) != 0) { burn(&ks, sizeof ks); return rc; }
+    do {
+        if ((rc = kw_io(L, secret, secretLen, wrapped, secretLen + 8, secretLen, &io)) != 0) break;
+        int k = uaesk_kw(L->stream, &c->tb, ks.nr, &ks.ek, &ks.dk, 0, io.din, secretLen, io.dout, NULL);
+        if (k) { rc = fail(UAES_E_HIP, "key wrap launch: %s", hipGetErrorString((hipError_t)k)); break; }
+        rc = finish_io(&io, secretLen + 8);
+    } while (0);
+    burn(&ks, sizeof ks);
+    DONE(L, rc);
+}
+
+int uaes_kw_unwrap(int keybits, const uint8_t *kek, const void *wrapped, size_t wrapLen, void *secret)
+{
+    context *c;
+    lane *L;
+    keysched ks;
+    io_plan io;
+    int rc, status = 0;
+    size_t len;
+    if ((rc = expand_key(&ks, kek, keybits)) != 0) return rc;
+    if (wrapLen % 8 || wrapLen / 8 < 3) { burn(&ks, sizeof ks); return UAES_E_DATALENGTH; }        /* (:1873) */
+    len = wrapLen - 8;
+    if (!secret || !wrapped) { burn(&ks, sizeof ks); return fail(UAES_E_ARG, "NULL pointer"); }
+    if (host_take(wrapped, secret, wrapLen, 1)) {
+        const uaesh_key hk = host_key(&ks);
+        rc = uaesh_kw_unwrap(&hk, (const uint8_t *)wrapped, wrapLen, (uint8_t *)secret);
+        burn(&ks, sizeof ks);
+        if (rc == UAES_E_AUTHENTICATION && wipe_on_auth_failure()) memset(secret, 0, len);   /* (the default leaves it, as the reference does) */
+        return host_result(rc);
+    }
+    if ((rc = enter(&c, &L)) != 0) { burn(&ks, sizeof ks); return rc; }
+    do {
+        if ((rc = kw_io(L, wrapped, wrapLen, secret, len, len, &io)) != 0) break;
+        int k = uaesk_kw(L->stream, &c->tb, ks.nr, &ks.ek, &ks.dk, 1, io.din, len, io.dout, L->d_status);
+        if (k) { rc = fail(UAES_E_HIP, "key unwrap launch: %s", hipGetErrorString((hipError_t)k)); break; }
+        if ((rc = lane_fetch(L, &status, L->d_status, sizeof status)) != 0) break;
+        io.drained = 1;
+        /* like the reference: the secret is written before A is checked; SABOTAGE = uaes_set_wipe_on_auth_failure */
+        if ((rc = status ? finish_io_unauthenticated(&io, len) : finish_io(&io, len)) == 0 && status) rc = UAES_E_AUTHENTICATION;
+    } while (0);
+    burn(&ks, sizeof ks);
+    DONE(L, rc);
+}
+
+/* Batches: nkeys records of one length under one key-encryption key, sixteen lanes per record, always on the GPU.
+ * Either array may be host or device memory; host arrays travel through the lane's staging buffers. */
+static int kw_batch(int unwrap, int keybits, const uint8_t *kek, size_t nkeys, size_t secret_bytes,
+                    const void *in, void *outp, uint8_t *verdicts)
+{
+    context *c;
+    lane *L;
+    keysched ks;
+    void *d_in = NULL, *d_out = NULL, *d_verdicts = NULL;
+    size_t off = 0;
+    int rc, bad = 0;
+    const size_t in_rec = unwrap ? secret_bytes + 8 : secret_bytes, out_rec = unwrap ? secret_bytes : secret_bytes + 8;
+    if ((rc = expand_key(&ks, kek, keybits)) != 0) return rc;
+    if (secret_bytes > UAES_KW_BATCH_MAX) {
+        burn(&ks, sizeof ks);
+        return fail(UAES_E_ARG, "batched key wrap: a record holds at most %zu bytes of secret (got %zu)",
+                    (size_t)UAES_KW_BATCH_MAX, secret_bytes);
+    }
+    if (nkeys > (size_t)-1 / (secret_bytes + 8)) { burn(&ks, sizeof ks); return fail(UAES_E_ARG, "batch size overflows"); }
+    if (nkeys == 0) { burn(&ks, sizeof ks); return 0; }
+    if (!in || !outp || (unwrap && !verdicts)) { burn(&ks, sizeof ks); return fail(UAES_E_ARG, "NULL pointer"); }
+    if ((rc = enter(&c, &L)) != 0) { burn(&ks, sizeof ks); return rc; }
+    if (unwrap) {
+        if ((rc = lane_scratch(L, SIDE(nkeys), SCRATCH_OTHER)) != 0) goto out;
+        if ((rc = side_out(L, &off, verdicts, nkeys, &d_verdicts)) != 0) goto out;
+        if (is_device_ptr(verdicts) && (rc = wait_for_callers_device_work()) != 0) goto out;
+    }
+    if ((rc = stage_text(L, 0, in, nkeys * in_rec, 1, &d_in)) != 0) goto out;
+    if ((rc = stage_text(L, 1, outp, nkeys * out_rec, 0, &d_out)) != 0) goto out;
+    if (unwrap) HIPCHK_GOTO(hipMemsetAsync(L->d_status, 0, sizeof(int), (hipStream_t)L->stream));
+    ES_KCHK("key wrap batch", uaesk_kw_batch(L->stream, &c->tb, ks.nr, &ks.ek, &ks.dk, unwrap, wipe_on_auth_failure(), nkeys,
+                                             secret_bytes, d_in, d_out, d_verdicts, L->d_status));
+    if ((rc = copy_out(L, outp, d_out, nkeys * out_rec)) != 0) goto out;
+    if (unwrap) {
+        if ((rc = copy_out(L, verdicts, d_verdicts, nkeys)) != 0) goto out;
+        HIPCHK_GOTO(hipMemcpyAsync(&bad, L->d_status, sizeof bad, hipMemcpyDeviceToHost, (hipStream_t)L->stream));
+    }
+    HIPCHK_GOTO(hipStreamSynchronize((hipStream_t)L->stream));
+    rc = bad ? UAES_E_AUTHENTICATION : 0;
+out:
+    burn(&ks, sizeof ks);
+    DONE(L, rc);
+}
+
+int uaes_kw_wrap_batch(int keybits, const uint8_t *kek, size_t nkeys, size_t secret_bytes, const void *secrets, void *wrapped)
+{
+    if (secret_bytes % 8 || secret_bytes / 8 < 2) return UAES_E_DATALENGTH;
+    return kw_batch(0, keybits, kek, nkeys, secret_bytes, secrets, wrapped, NULL);
+}
+
+int uaes_kw_unwrap_batch(int keybits, const uint8_t *kek, size_t nkeys, size_t wrapped_bytes, const void *wrapped,
+                         void *secrets, uint8_t *verdicts)
+{
+    if (wrapped_bytes % 8 || wrapped_bytes / 8 < 3) return UAES_E_DATALENGTH;
+    return kw_batch(1, keybits, kek, nkeys, wrapped_bytes - 8, wrapped, secrets, verdicts);
+}
+
+/* ------------------------------------------------------------------------ */
 /* OCB (RFC 7253; AES_OCB_encrypt / AES_OCB_decrypt, micro_aes.c:1774-1811)     */
 /* ------------------------------------------------------------------------ */
 /* nonceLen / tagLen = the reference's compile-time OCB_NONCE_LEN (1..15) / OCB_TAG_LEN (1..16), micro_aes.h:115-116 */

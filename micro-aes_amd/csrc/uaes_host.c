@@ -5,7 +5,7 @@
  * without one unless the deployer has switched this path on (uaes_set_host_policy / UAES_HOST_MAX, UAES_HOST_CHAINS,
  * UAES_HOST_FALLBACK; include/uaes_hip.h).  It exists for the three places where a GPU cannot serve a caller of the
  * reference well (SURVEY.md 8b "Errors"): host-pointer calls too short to amortise a launch, ONE serial
- * chain (CBC / CFB encryption, OFB, CMAC, CCM's CBC-MAC: a latency-bound single wave on the GPU), and a `void` function
+ * chain (CBC / CFB encryption, OFB, CMAC, CCM's CBC-MAC, key wrap: a latency-bound single wave on the GPU), and a `void` function
  * of the drop-in API on a box whose GPU has gone away.
  *
  * Product code, parity-tested like a kernel (tests/test_host_path.py runs the reference-held vectors and the golden
@@ -967,4 +967,56 @@ void uaesh_poly1305(const uaesh_key *k, const uint8_t r16[16], const uint8_t non
         volatile uint8_t *vb = rb; for (i = 0; i < 16; ++i) vb[i] = 0;
         vb = blk; for (i = 0; i < 16; ++i) vb[i] = 0;
     }
+}
+
+/* ---- key wrap, RFC 3394 (AES_KEY_wrap micro_aes.c:1829-1855, AES_KEY_unwrap :1865-1894; xorBEint with MIDST) ------- */
+/* the step counter, big-endian, ending at byte 7 of A */
+static void kw_xor_step(uint8_t a[16], uint64_t t)
+{
+    int i;
+    for (i = 7; i >= 0 && t; --i, t >>= 8) a[i] ^= (uint8_t)t;
+}
+
+/* secret and wrapped are disjoint, or secret == wrapped + 8 (the reference's own in-place form) */
+int uaesh_kw_wrap(const uaesh_key *k, const uint8_t *secret, size_t len, uint8_t *wrapped)
+{
+    const size_t n = len / 8;
+    uint8_t a[16], *r = wrapped + 8;
+    uint64_t t;
+    if (n < 2 || len % 8) return 1;                     /* M_DATALENGTH_ERROR */
+    memset(a, 0xA6, 8);
+    memmove(r, secret, len);
+    for (t = 1; t <= 6 * (uint64_t)n; ++t) {
+        memcpy(a + 8, r, 8);
+        uaesh_encrypt(k->ek, k->nr, a, a);
+        memcpy(r, a + 8, 8);
+        kw_xor_step(a, t);
+        r = (r == wrapped + len ? wrapped : r) + 8;
+    }
+    memcpy(wrapped, a, 8);
+    memset(a, 0, sizeof a);
+    return 0;
+}
+
+/* the secret is written whatever the verdict, like the reference; 0x1A = M_AUTHENTICATION_ERROR */
+int uaesh_kw_unwrap(const uaesh_key *k, const uint8_t *wrapped, size_t wrap_len, uint8_t *secret)
+{
+    const size_t n = wrap_len / 8;
+    uint8_t a[16], *r = secret, *end, bad = 0;
+    uint64_t t;
+    int i;
+    if (n < 3 || wrap_len % 8) return 1;
+    end = secret + wrap_len - 8;
+    memcpy(a, wrapped, 8);
+    memmove(secret, wrapped + 8, wrap_len - 8);
+    for (t = 6 * (uint64_t)(n - 1); t; --t) {
+        r = (r == secret ? end : r) - 8;
+        kw_xor_step(a, t);
+        memcpy(a + 8, r, 8);
+        uaesh_decrypt(k->dk, k->nr, a, a);
+        memcpy(r, a + 8, 8);
+    }
+    for (i = 0; i < 8; ++i) bad |= a[i] ^ 0xA6;
+    memset(a, 0, sizeof a);
+    return bad ? 0x1A : 0;
 }

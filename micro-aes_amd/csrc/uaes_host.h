@@ -60,4 +60,9 @@ int  uaesh_gcmsiv(const uaesh_key *master, int keybits, int decrypt, const uint8
 int  uaesh_ocb(const uaesh_key *k, int decrypt, const uint8_t *nonce, size_t nonce_len, size_t tag_len,
                const uint8_t *aad, size_t aad_len, const uint8_t *in, size_t len, uint8_t *out);            /* :1693-1811 */
 
+/* RFC 3394 key wrap: 0, 1 (M_DATALENGTH_ERROR: no multiple of 8 bytes, or fewer than two semiblocks of secret; nothing
+ * written) or, from unwrap, 0x1A (the secret is written all the same); secret == wrapped + 8 works in place */
+int  uaesh_kw_wrap(const uaesh_key *k, const uint8_t *secret, size_t len, uint8_t *wrapped);                  /* :1829-1855 */
+int  uaesh_kw_unwrap(const uaesh_key *k, const uint8_t *wrapped, size_t wrap_len, uint8_t *secret);           /* :1865-1894 */
+
 #endif

@@ -51,11 +51,15 @@
  *   batch batch.row             k_chain_batch_row (sixteen lanes per message;       (1)    uaes_cbc_encrypt_batch / uaes_cmac_batch,
  *                               256-thread workgroups while they fill <= half the CUs)     <= UAES_BATCH_ROW_MAX messages (81 919)
  *         batch.lane            k_chain_batch (one lane per message)                (1)    more messages
+ *   KW    kw.lds                k_kw<LDS> (one wave; the semiblocks in LDS)         (1)    secret <= UAES_KW_LDS_MAX (4 KiB)
+ *         kw.global             k_kw<in place> (one wave; loads a chunk ahead)      (1)    beyond
+ *         kw.batch              k_kw_batch (sixteen lanes per record)               (1)    uaes_kw_*_batch, <= UAES_KW_BATCH_MAX (256 B)
  * The Poly1305 rows have a planner of their own (uaesk_plan_poly1305, uaes_poly1305.hip) and ids outside enum
  * uaes_arrangement (uaes_debug_plan_poly1305 names them); a larger message never goes back to a smaller row.
  * So do the EAX and SIV (RFC 5297) rows (uaesk_plan_eax_siv, uaes_eax_siv.hip; uaes_debug_plan_eax_siv), and the
  * CBC / CFB / OFB / CMAC / CCM / batch rows (uaesk_plan_chain, uaes_chain.hip, and uaesk_plan_mac, uaes_mac.hip;
- * uaes_debug_plan_chain); tests/test_gpu_chains.py derives its sizes and message counts from them.
+ * uaes_debug_plan_chain); tests/test_gpu_chains.py derives its sizes and message counts from them.  Key wrap has
+ * uaesk_plan_kw (uaes_kw.hip; uaes_debug_plan_kw), and tests/test_gpu_kw.py finds its two boundaries by walking it.
  */
 #ifndef UAES_PLAN_H
 #define UAES_PLAN_H
@@ -154,6 +158,21 @@ enum uaes_chain_arrangement { UAES_CHAIN_SERIAL = 0, UAES_FBDEC_SINGLE, UAES_FBD
 int uaesk_plan_chain(int what, int dir, size_t a, size_t b, uaes_plan *p);
 int uaesk_plan_mac(int what, int dir, size_t a, uaes_plan *p);
 const char *uaesk_chain_arrangement_name(int id);
+
+/* AES key wrap (RFC 3394; uaes_kw.hip).  dir: 0 wrap, 1 unwrap; len = bytes of the SECRET in either direction (the
+ * wrapped form is 8 bytes longer); nkeys 0 = the one-secret calls, nkeys >= 1 = a batch of nkeys records of len bytes.
+ * One secret is one wave: up to UAES_KW_LDS_MAX bytes its semiblocks live in LDS behind the row tables, a longer one
+ * is worked on in place in the output buffer (a semiblock is next touched n - 1 chain steps after it was stored, far
+ * longer than a store and a load take, so its load is requested a chunk of steps ahead and never sits on the chain;
+ * below the boundary that distance would be too short, and 4 KiB of LDS cost nothing).  A batch record is at most
+ * UAES_KW_BATCH_MAX bytes: 64 records of a workgroup keep their semiblocks in the 31 KiB of LDS the row4 tables leave
+ * (a 2048-bit secret still fits).  grid = workgroups, steps = threads per workgroup (batch: sixteen per record).
+ * Returns a HIP error code for a length that is no multiple of 8 or below 16, or a batch record above the limit. */
+#define UAES_KW_LDS_MAX   ((size_t)4096)
+#define UAES_KW_BATCH_MAX ((size_t)256)
+enum uaes_kw_arrangement { UAES_KW_LDS = 0, UAES_KW_GLOBAL, UAES_KW_BATCH };
+int uaesk_plan_kw(int dir, size_t len, size_t nkeys, uaes_plan *p);
+const char *uaesk_kw_arrangement_name(int id);
 
 #ifdef __cplusplus
 }

@@ -65,3 +65,11 @@ for what in ("cbc_batch", "cmac_batch"):
     walk("%s, k messages of 1 KiB (positions/thread: threads per workgroup)" % what,
          lambda k: uaes.chain_plan(what, 1024, max(k, 1))[:2] + (0, uaes.chain_plan(what, 1024, max(k, 1))[3]), 1, 1 << 20, 1,
          lambda k: "%9d msgs (%9.3f MiB)" % (k, k * 1024 / MIB))
+for dec in (False, True):
+    walk("KW %s, one secret of n bytes" % ("unwrap" if dec else "wrap"),
+         lambda n: uaes.kw_plan(max(n, 16), unwrap=dec)[:2] + (0, 0), 16, 64 * MIB, 8)
+top = max(n for n in range(16, 1 << 13, 8) if uaes.kw_plan(n, 2) is not None)
+print("KW batches: a record holds at most UAES_KW_BATCH_MAX = %d bytes of secret" % top)
+walk("KW batch, k secrets of 32 bytes (positions/thread: threads per workgroup)",
+     lambda k: uaes.kw_plan(32, max(k, 1))[:2] + (0, uaes.kw_plan(32, max(k, 1))[3]), 1, 1 << 20, 1,
+     lambda k: "%9d keys (%9.3f MiB)" % (k, k * 32 / MIB))
