@@ -387,6 +387,8 @@ struct GhFold {
     static constexpr bool expand2 = false;     /* the loop body once per trip: twice would spill (128 VGPRs are all in use) */
     static constexpr bool text_ahead = false;  /* one text buffer, loaded at the head of its own iteration: no second buffer,
                                                   no eight v_mov per trip to rotate it (profiles/r05_gcm_text_ab.log) */
+    static constexpr bool aligned = false;     /* lanes pinned to the counter: the GHASH geometry hangs on g_lo */
+    static constexpr bool write_through = false;
     uint4 acc[2];
     GhLane gl;
     __device__ __forceinline__ void operator()(const uint4 &c0, const uint4 &c1)

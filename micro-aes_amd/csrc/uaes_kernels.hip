@@ -222,34 +222,37 @@ __global__ __launch_bounds__(UAES_WG, 4) void k_ctr_ind(const uaesk_rk *__restri
     ctr_generic_body<NR, U>(rk, tb, ctr, in, out, nfull, rem, nullptr, none);
 }
 
-#define CTRS_BUF   (UAES_LDS_ENC)            /* 2 x 64 x 32 B after the tables */
-#define UAES_LDS_CTRS (UAES_LDS_ENC + 2u * CTRS_CHUNK * 32u)
+#define CTRS_BUF   (UAES_LDS_ENC)            /* 2 x 72 x 32 B after the tables */
+#define UAES_LDS_CTRS (UAES_LDS_ENC + 2u * CTRS_SLOTS(CtrNoFold::aligned) * 32u)
 
-/* The shared-round CTR kernel (uaes_ctr.hip.h): the hot loop handles only whole 8-group
- * stripes (2048 blocks, 32 KiB) that lie completely inside the stream, so it has no bounds
- * checks; the blocks before and after them (up to block nfull) and a byte tail run in the
- * prologue.  The stripes are dealt round-robin over the workgroups, so every workgroup gets
- * floor or ceil of stripes/grid and the kernel's time follows the text size in 32 KiB steps
- * (round 1 dealt 256 KiB chunks: 80 MiB ran 10 % slower than 64 MiB,
- * profiles/HISTORY.md).  A lock-step four-block version
- * measured 4 % slower (profiles/HISTORY.md).                            */
+/* The shared-round CTR kernel (uaes_ctr.hip.h): the hot loop handles only whole stripes
+ * (2048 blocks, 32 KiB), counted from block 0 of the text, so it has no bounds checks and
+ * every wave access lies on the text's own 128-byte lines; the blocks behind them (up to
+ * block nfull) and a byte tail go one per thread through the plain rounds.  The stripes are
+ * dealt round-robin over the workgroups, so every workgroup gets floor or ceil of
+ * stripes/grid and the kernel's time follows the text size in 32 KiB steps (round 1 dealt
+ * 256 KiB chunks: 80 MiB ran 10 % slower than 64 MiB, profiles/HISTORY.md).  A lock-step
+ * four-block version measured 4 % slower (profiles/HISTORY.md).
+ * Order: the first stripe's text is requested before the tables are made, and the edge blocks
+ * come after the stripes: wave 0 reaches its first U-buffer refill -- where the other fifteen
+ * waves wait for it -- with no text round trip and no latency-bound chain of rounds in front. */
 template <int NR>
 __global__ __launch_bounds__(UAES_WG, 4) void k_ctr_shared2(uaesk_rk rk, uaesk_tables tb, uaesk_ctr ctr,
                                                            const uint4 *in, uint4 *out,
-                                                           u64 g_lo, u64 stripes, u64 nfull, u32 rem,
+                                                           u64 stripes, u64 nfull, u32 rem,
                                                            const int *__restrict__ gate)
 {
     if (gate && *gate != 0) return;
+    CtrGeo geo;
+    geo.first = 0;
+    geo.iters = stripes / gridDim.x + (blockIdx.x < stripes % gridDim.x ? 1 : 0);
+    uint4 d0[2];
+    ctr_first_text<CtrNoFold>(ctr, in, geo, d0);
     fill_enc_tables(tb.te0);
     const LaneConst lc = make_lane_const();
-    const u32 c0 = (u32)ctr.v0 & 0xffu;
-    CtrGeo geo;
-    geo.first = g_lo;
-    geo.iters = stripes / gridDim.x + (blockIdx.x < stripes % gridDim.x ? 1 : 0);
-    ctr_edge_blocks<NR>(rk, ctr, in, out, g_lo * 256 - (g_lo ? c0 : 0),              /* blocks [0, pre_end) */
-                        (g_lo + 8 * stripes) * 256 - c0, nfull, rem, lc);           /* blocks [suf, nfull) */
     CtrNoFold nofold;
-    ctr_shared_loop<NR>(rk, ctr, in, out, geo, CTRS_BUF, lc, nofold);
+    ctr_shared_loop<NR>(rk, ctr, in, out, geo, CTRS_BUF, lc, nofold, d0);
+    ctr_edge_blocks<NR>(rk, ctr, in, out, 0, 2048 * stripes, nfull, rem, lc);       /* blocks [2048 stripes, nfull) */
 }
 
 /* ------------------------------------------------------------------------ */
@@ -882,14 +885,16 @@ static uaes_plan plan_ecb(u64 items)
     return p;
 }
 
-/* CTR.  The striped kernel (k_ctr_shared2: rounds 1-2 shared by the 256 counters of a group, eight groups per stripe)
+/* CTR.  The striped kernel (k_ctr_shared2: rounds 1-2 shared by the 256 counters of a group, 2048 blocks per stripe)
  * from ONE grid of stripes on: below that the generic kernel's one- or four-block work items spread better over the
- * CUs (8 MiB on 256 CUs; profiles/HISTORY.md "CTR size sweep").  A last round of stripes that covers less than
- * CTR_TAIL_PCT % of the grid is handed to the kernel's edge path -- one block per thread through the plain rounds,
- * spread over ALL workgroups (20 MiB = 640 stripes on 256 workgroups: 2.5 rounds would cost 3).  g_lo / n8: the
- * stripes' first group and their number (uaes_ctr.hip.h). */
+ * CUs (8 MiB on 256 CUs; profiles/HISTORY.md "CTR size sweep").  Where that threshold lies is still told in whole
+ * groups of the counter behind the first one (c0 = the first counter's byte 15, g_lo = 1 unless c0 == 0), as it was
+ * measured; the kernel's stripes have since moved to block 0 of the text, which never leaves it fewer stripes than
+ * that count.  A last round of stripes that covers less than CTR_TAIL_PCT % of the grid is handed to the kernel's
+ * edge path -- one block per thread through the plain rounds, spread over ALL workgroups (20 MiB = 640 stripes on
+ * 256 workgroups: 2.5 rounds would cost 3).  n8: the number of stripes, from block 0 (uaes_ctr.hip.h). */
 #define CTR_TAIL_PCT 80u
-static uaes_plan plan_ctr(const uaesk_ctr *ctr, size_t len, u64 *g_lo_out, u64 *n8_out)
+static uaes_plan plan_ctr(const uaesk_ctr *ctr, size_t len, u64 *n8_out)
 {
     const u64 nfull = len / 16, nblocks = (len + 15) / 16;
     uaes_plan p = { UAES_ARR_CTR_QUAD, 1, 0, 0 };
@@ -897,14 +902,13 @@ static uaes_plan plan_ctr(const uaesk_ctr *ctr, size_t len, u64 *g_lo_out, u64 *
     if (!ctr->le32 && uaesk_arr_on(UAES_ARR_CTR_STRIPED)) {      /* (the shared rounds assume the 56-bit big-endian counter) */
         const u32 c0 = (u32)ctr->v0 & 0xffu;
         const u64 g_lo = c0 ? 1 : 0, groups = (c0 + nfull) / 256;
-        u64 n8 = groups > g_lo ? (groups - g_lo) / 8 : 0;
-        if (n8 >= (u64)grid) {
+        if (groups >= g_lo + 8 * (u64)grid) {
+            u64 n8 = nfull / 2048;
             const u64 r = n8 % grid;
             if (r && n8 > grid && r * 100 < (u64)grid * CTR_TAIL_PCT) n8 -= r;
             p.arrangement = UAES_ARR_CTR_STRIPED; p.grid = grid;
             /* a text in which counter bits 40..47 move -- once in 2^40 blocks -- is cut there into two launches */
-            if (ctr_stripes_cross_a(ctr, g_lo, n8)) p.launches = 2;
-            if (g_lo_out) *g_lo_out = g_lo;
+            if (ctr_blocks_cross_a(ctr, 0, 2048 * n8)) p.launches = 2;
             if (n8_out) *n8_out = n8;
             return p;
         }
@@ -960,9 +964,9 @@ static int launch_ctr_u(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *
 /* one launch of the striped kernel over a text whose stripes do not cross a 2^40-block boundary */
 template <int NR>
 static int launch_ctr_striped(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *ek, const uaesk_ctr *ctr,
-                              const void *in, void *out, size_t len, const int *gate, unsigned grid, u64 g_lo, u64 n8)
+                              const void *in, void *out, size_t len, const int *gate, unsigned grid, u64 n8)
 {
-    return uaesk_launch(k_ctr_shared2<NR>, grid, UAES_WG, UAES_LDS_CTRS, st, *ek, *tb, *ctr, in, out, g_lo, n8, len / 16,
+    return uaesk_launch(k_ctr_shared2<NR>, grid, UAES_WG, UAES_LDS_CTRS, st, *ek, *tb, *ctr, in, out, n8, len / 16,
                         len % 16, gate);
 }
 
@@ -970,8 +974,8 @@ template <int NR>
 static int launch_ctr(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *ek, const uaesk_ctr *ctr,
                       const void *in, void *out, size_t len, const int *gate)
 {
-    u64 g_lo = 0, n8 = 0;
-    const uaes_plan pl = plan_ctr(ctr, len, &g_lo, &n8);
+    u64 n8 = 0;
+    const uaes_plan pl = plan_ctr(ctr, len, &n8);
     if (pl.arrangement == UAES_ARR_CTR_SINGLE) return launch_ctr_u<NR, 1>(st, tb, ek, ctr, in, out, len, gate);
     if (pl.arrangement == UAES_ARR_CTR_QUAD) return launch_ctr_u<NR, UAES_U>(st, tb, ek, ctr, in, out, len, gate);
     if (pl.launches == 2) {
@@ -986,7 +990,7 @@ static int launch_ctr(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *ek
         return launch_ctr<NR>(st, tb, ek, &second, (const unsigned char *)in + nb * 16, (unsigned char *)out + nb * 16,
                               len - (size_t)(nb * 16), gate);
     }
-    return launch_ctr_striped<NR>(st, tb, ek, ctr, in, out, len, gate, pl.grid, g_lo, n8);
+    return launch_ctr_striped<NR>(st, tb, ek, ctr, in, out, len, gate, pl.grid, n8);
 }
 
 template <int NR, int U>
@@ -1308,7 +1312,7 @@ extern "C" int uaesk_plan_at(int mode, int dir, size_t a, size_t b, unsigned fla
             c.v0 = 1;                               /* CTR_START_VALUE behind a 12-byte IV */
         }
         c.le32 = (flags >> 3) & 1u;
-        *p = plan_ctr(&c, a, nullptr, nullptr);
+        *p = plan_ctr(&c, a, nullptr);
         return 0;
     }
     case UAES_PLAN_XTS:
