@@ -47,7 +47,23 @@
 #ifndef KWA                  /* micro_aes.h:50 -- key wrap, RFC 3394 (uaes_kw.hip); every library exports AES_KEY_wrap /  */
 #define KWA      0          /* AES_KEY_unwrap, a caller built with -DKWA=1 sees the prototypes (below)                */
 #endif
-#define FPE      0
+#ifndef FPE                  /* micro_aes.h:51 -- FF1 format-preserving encryption (uaes_ff1.hip); every library exports */
+#define FPE      0          /* AES_FPE_*, a caller built with -DFPE=1 sees the prototypes (below)                   */
+#endif
+#if FPE
+#ifndef CUSTOM_ALPHABET      /* micro_aes.h:87 -- 0: the digits 0..9; 1..9: ALPHABET and RADIX of the caller's micro_fpe.h */
+#define CUSTOM_ALPHABET 0
+#endif
+#ifndef FF_X                 /* micro_aes.h:88 -- 1: FF1, the only method served */
+#define FF_X            1
+#endif
+#if FF_X != 1
+#error "FF_X: only FF1 (FF_X 1) is served; FF3-1 is not"
+#endif
+#if CUSTOM_ALPHABET >= 10 || CUSTOM_ALPHABET < 0
+#error "CUSTOM_ALPHABET: wide-character alphabets (10 and above) are not served"
+#endif
+#endif
 #ifndef EAX                  /* micro_aes.h:43 -- EAX (uaes_eax_siv.hip); every library exports AES_EAX_*, a caller */
 #define EAX      0          /* built with -DEAX=1 sees the prototypes (below)                                       */
 #endif
@@ -394,6 +410,39 @@ char AES_KEY_wrap(const uint8_t *kek,
                   const void *secret, const size_t secretLen, void *wrapped);
 char AES_KEY_unwrap(const uint8_t *kek,
                     const void *wrapped, const size_t wrapLen, void *secret);
+#endif
+
+#if FPE
+/* FF1, SP 800-38G (micro_aes.c:2267-2347): a string of ptextLen characters of the alphabet to another such string, a NUL
+ * behind it (crtxt holds ptextLen + 1 bytes).  Any failure -- a string shorter than the radix's minimum (6 for decimal)
+ * or longer than 4096 characters (the reference takes any length), a character outside the alphabet, an engine failure
+ * -- returns M_ENCRYPTION_ERROR / M_DECRYPTION_ERROR and leaves the output as it was. */
+char AES_FPE_encrypt(const uint8_t *key, const uint8_t *tweak, const size_t tweakLen,
+                     const void *pntxt, const size_t ptextLen, void *crtxt);
+char AES_FPE_decrypt(const uint8_t *key, const uint8_t *tweak, const size_t tweakLen,
+                     const void *crtxt, const size_t crtxtLen, void *pntxt);
+/* the alphabet is a compile-time choice of the CALLER's build in the reference; every library exports the general
+ * entry points (alphabet = radix distinct characters, radix 2..256) and a caller built with -DCUSTOM_ALPHABET=n (1..9)
+ * is bound to them with the ALPHABET and RADIX of its own micro_fpe.h, the file the reference's micro_aes.c includes */
+char AES_FPE_encrypt_alpha(const char *alphabet, const size_t radix, const uint8_t *key, const uint8_t *tweak,
+                           const size_t tweakLen, const void *pntxt, const size_t ptextLen, void *crtxt);
+char AES_FPE_decrypt_alpha(const char *alphabet, const size_t radix, const uint8_t *key, const uint8_t *tweak,
+                           const size_t tweakLen, const void *crtxt, const size_t crtxtLen, void *pntxt);
+#if CUSTOM_ALPHABET
+#include "micro_fpe.h"
+UAES_STATIC_INLINE char AES_FPE_encrypt_ca(const uint8_t *key, const uint8_t *tweak, const size_t tweakLen,
+                                           const void *pntxt, const size_t ptextLen, void *crtxt)
+{
+    return AES_FPE_encrypt_alpha(ALPHABET, RADIX, key, tweak, tweakLen, pntxt, ptextLen, crtxt);
+}
+UAES_STATIC_INLINE char AES_FPE_decrypt_ca(const uint8_t *key, const uint8_t *tweak, const size_t tweakLen,
+                                           const void *crtxt, const size_t crtxtLen, void *pntxt)
+{
+    return AES_FPE_decrypt_alpha(ALPHABET, RADIX, key, tweak, tweakLen, crtxt, crtxtLen, pntxt);
+}
+#define AES_FPE_encrypt AES_FPE_encrypt_ca
+#define AES_FPE_decrypt AES_FPE_decrypt_ca
+#endif
 #endif
 
 #if POLY1305

@@ -99,12 +99,12 @@ int         uaes_stream_release(void *stream);
  * GPU and fails loudly without one.  Three independent, process-wide switches for the cases a GPU serves badly:
  *   max_bytes  calls whose data pointers are HOST memory and whose text is at most this long run on the host: a
  *              launch costs 12-20 us whatever the size, one host core needs that long for ~1 KiB (GCM ~200 B);
- *   chains     ONE serial chain in host memory -- CBC / CFB encryption, OFB, CMAC, CCM, key wrap -- runs on the host whatever
+ *   chains     ONE serial chain in host memory -- CBC / CFB encryption, OFB, CMAC, CCM, key wrap, FF1 -- runs on the host whatever
  *              its length (a chain is a latency-bound single wave on the GPU: 36 MiB/s; uaes_*_batch are the GPU's form);
  *   fallback   with NO usable HIP device the calls below run on the host instead of returning UAES_E_HIP -- the
  *              reference's `void` functions cannot report an error.
  * Covered: every synchronous one-message call of this header -- ECB, CTR, XTS (unit and sectors), GCM (any nonce / tag
- * length), CBC (CTS and CTS-0 forms), CFB, OFB, CMAC, CCM, GCM-SIV, OCB, KW.  Not covered (always GPU): the *_dev / *_batch
+ * length), CBC (CTS and CTS-0 forms), CFB, OFB, CMAC, CCM, GCM-SIV, OCB, KW, FF1.  Not covered (always GPU): the *_dev / *_batch
  * / record / key-context / stream / mgpu calls, uaes_ghash, and any call that is handed a device pointer.
  * Environment, read at first use: UAES_HOST_MAX=<bytes>, UAES_HOST_CHAINS=1, UAES_HOST_FALLBACK=1; or
  * UAES_HOST_POLICY=recommended = (4096, 1, 1), the measured crossover on the builder's hosts (profiles/r05_host_policy.md),
@@ -331,6 +331,46 @@ int uaes_kw_wrap_batch(int keybits, const uint8_t *kek, size_t nkeys, size_t sec
                        const void *secrets, void *wrapped);
 int uaes_kw_unwrap_batch(int keybits, const uint8_t *kek, size_t nkeys, size_t wrapped_bytes,
                          const void *wrapped, void *secrets, uint8_t *verdicts);
+
+/* ---- FF1: replaces AES_FPE_encrypt / AES_FPE_decrypt (SP 800-38G, FF_X 1) ------
+ * micro_aes.c:2091-2147, :2267-2347.  Format-preserving encryption of len numerals, ONE BYTE PER NUMERAL.  radix =
+ * 2..256; alphabet = radix distinct bytes (input bytes are looked up in it, output digits mapped through it), or NULL:
+ * the bytes are the digit values 0..radix-1 themselves.  key, alphabet: host memory; tweak, in, out: host or device
+ * memory at any byte offset; out == in works (every numeral is looked up before anything is written).  No NUL is
+ * appended at this level.
+ *   lengths   len at least the smallest n with radix^n >= 1 000 000 (6 for decimal; the reference's MINLEN for every
+ *             radix), at most UAES_FF1_MAX = 4096, tweakLen below 2^32; otherwise UAES_E_DATALENGTH, out untouched.
+ *             The cap departs from the reference, which takes any length: the radix conversions are quadratic in the
+ *             length (the reference needs 43 s for 100 000 digits on one host core).
+ *   errors    radix outside 2..256 or a byte twice in the alphabet: UAES_E_ARG.  A byte of `in` that is no numeral:
+ *             UAES_E_ENCRYPTION from encrypt, UAES_E_DECRYPTION from decrypt, out untouched (the reference's 'C',
+ *             micro_aes.c:2294-2300).
+ * b = ceil(bits(radix^v - 1) / 8) is computed with exact integers, as SP 800-38G states it.  The reference's
+ * floating-point form agrees for radix 10 at every length this call takes; where v log2(radix) is a multiple of 8 at 136
+ * bits or more (radix 2 from v = 128, radix 64 from v = 24, radix 256 from v = 16; v = len - len / 2) it is one too
+ * large, and the engine follows the specification there.
+ * Ten Feistel rounds, each a CBC-MAC of one to a few blocks and two radix conversions: a chain like key wrap, so the
+ * host policy applies (`chains`), and the GPU's form is the batch: nrec records of len numerals back to back under
+ * one key, sixteen GPU lanes per record, always on the GPU.  tweak_stride 0: one tweak for all records; otherwise
+ * record m's tweak is at tweaks + m * tweak_stride.  A record holds at most UAES_FF1_BATCH_MAX = 128 numerals
+ * (UAES_E_DATALENGTH beyond).  A record with a byte that is no numeral is left unwritten and gets verdicts[m] = 0,
+ * the others 1 (verdicts may be NULL, host or device memory); the call completes every good record and then returns
+ * the encryption / decryption error if any record was bad.  nrec == 0 returns 0.  A single call of up to
+ * UAES_FF1_BATCH_MAX numerals runs as a batch of one, a longer one on a wave of its own.
+ * Rates (profiles/ff1_rate.md: tools/ff1_rate.py on an MI355X, AES-128, 16-digit decimal records, device-resident):
+ * 2^20 records 5.02 ms = 2.09e8 records/s, 2^16 records 0.34 ms, 2^10 records 0.10 ms, shared or per-record tweaks,
+ * either direction; one 16-digit call 105 us; one 4096-digit call 20 ms.  One host core: the reference 2.62e5
+ * records/s, the engine's host path 4.13e5.                                                                       */
+int uaes_ff1_encrypt(int keybits, const uint8_t *key, unsigned radix, const uint8_t *alphabet,
+                     const uint8_t *tweak, size_t tweakLen, const void *in, size_t len, void *out);
+int uaes_ff1_decrypt(int keybits, const uint8_t *key, unsigned radix, const uint8_t *alphabet,
+                     const uint8_t *tweak, size_t tweakLen, const void *in, size_t len, void *out);
+int uaes_ff1_encrypt_batch(int keybits, const uint8_t *key, unsigned radix, const uint8_t *alphabet,
+                           const uint8_t *tweaks, size_t tweakLen, size_t tweak_stride,
+                           size_t nrec, size_t len, const void *in, void *out, uint8_t *verdicts);
+int uaes_ff1_decrypt_batch(int keybits, const uint8_t *key, unsigned radix, const uint8_t *alphabet,
+                           const uint8_t *tweaks, size_t tweakLen, size_t tweak_stride,
+                           size_t nrec, size_t len, const void *in, void *out, uint8_t *verdicts);
 
 /* Poly1305-AES (micro_aes.c:1955-1997): keys = k (keybits / 8 bytes) || r (16 bytes), mac = (h + AES_k(nonce)) mod
  * 2^128 with h the Poly1305 polynomial in the clamped r.  Block-parallel on the VALU (uaes_poly1305.hip): one
@@ -636,6 +676,13 @@ const char *uaes_debug_plan_chain(int what, int dir, size_t a, size_t b, int out
  * no sense: a length that is no multiple of 8 or below 16, a batch record above the limit.  Works without a device (a
  * 256-CU MI355X).  tests/test_gpu_kw.py finds the two boundaries by walking this. */
 const char *uaes_debug_plan_kw(int dir, size_t len, size_t nkeys, int out[3]);
+/* The planner of FF1 (csrc/uaes_plan.h, its own rows): dir 0 encrypt / 1 decrypt; len = numerals of one text; nrec 0 =
+ * uaes_ff1_encrypt / uaes_ff1_decrypt, nrec >= 1 = a batch of that many records.  out (may be NULL) receives
+ * { launches, workgroups, threads per workgroup } (a batch: sixteen threads per record).  Returns "ff1.batch" (sixteen
+ * lanes per record; one text within the batch limit is a batch of one), "ff1.wave" (one text on a wave of its own), or
+ * NULL for arguments that make no sense: a radix outside 2..256, a length below the radix's minimum or above the
+ * limit.  Works without a device (a 256-CU MI355X).  tests/test_gpu_ff1.py finds the boundary by walking this. */
+const char *uaes_debug_plan_ff1(int dir, unsigned radix, size_t len, size_t nrec, int out[3]);
 
 /* Test hooks of the one-launch GCM / GCM-SIV / streamed-piece arrangements (chunk workgroups + one preparing workgroup
  * in ONE launch; whoever of them arrives last on a counter word folds the chunk hashes and makes the tag -- nobody

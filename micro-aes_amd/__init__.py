@@ -47,6 +47,7 @@ EXPORTS = [
     "uaes_eax_encrypt_batch", "uaes_eax_decrypt_batch", "uaes_siv_encrypt_batch", "uaes_siv_decrypt_batch",
     "uaes_debug_plan_eax_siv", "uaes_debug_plan_chain",
     "uaes_kw_wrap", "uaes_kw_unwrap", "uaes_kw_wrap_batch", "uaes_kw_unwrap_batch", "uaes_debug_plan_kw",
+    "uaes_ff1_encrypt", "uaes_ff1_decrypt", "uaes_ff1_encrypt_batch", "uaes_ff1_decrypt_batch", "uaes_debug_plan_ff1",
     "uaes_mgpu_ctr_xcrypt_at", "uaes_mgpu_xts_sectors", "uaes_mgpu_ctr_encrypt_gather", "uaes_debug_gather_stats", "uaes_debug_gcm_look", "uaes_debug_gcm_chunk_folds",
     "uaes_debug_plan", "uaes_debug_plan_at", "uaes_debug_arrangement_name", "uaes_debug_plan_disable",
     "uaes_mgpu_ecb_encrypt", "uaes_mgpu_ecb_decrypt", "uaes_mgpu_gcm_encrypt", "uaes_mgpu_gcm_decrypt",
@@ -72,6 +73,7 @@ COMPAT_EXPORTS = [
     "AES_CCM_encrypt_lens", "AES_CCM_decrypt_lens", "AES_OCB_encrypt_lens", "AES_OCB_decrypt_lens",
     "AES_CCM_encrypt", "AES_CCM_decrypt", "AES_CMAC", "GCM_SIV_encrypt", "GCM_SIV_decrypt",
     "AES_OCB_encrypt", "AES_OCB_decrypt", "AES_Poly1305", "AES_KEY_wrap", "AES_KEY_unwrap",
+    "AES_FPE_encrypt", "AES_FPE_decrypt", "AES_FPE_encrypt_alpha", "AES_FPE_decrypt_alpha",
     "AES_EAX_encrypt", "AES_EAX_decrypt", "AES_EAX_encrypt_lens", "AES_EAX_decrypt_lens", "AES_SIV_encrypt", "AES_SIV_decrypt",
     "AES_CBC_encrypt", "AES_CBC_decrypt", "AES_CFB_encrypt", "AES_CFB_decrypt", "AES_OFB_encrypt", "AES_OFB_decrypt",
 ]
@@ -165,6 +167,12 @@ def engine():
     L.uaes_kw_unwrap_batch.argtypes = [i, vp, sz, sz, vp, vp, vp]
     L.uaes_debug_plan_kw.argtypes = [i, sz, sz, C.POINTER(C.c_int)]
     L.uaes_debug_plan_kw.restype = C.c_char_p
+    for n in ("uaes_ff1_encrypt", "uaes_ff1_decrypt"):
+        getattr(L, n).argtypes = [i, vp, C.c_uint, vp, vp, sz, vp, sz, vp]
+    for n in ("uaes_ff1_encrypt_batch", "uaes_ff1_decrypt_batch"):
+        getattr(L, n).argtypes = [i, vp, C.c_uint, vp, vp, sz, sz, sz, sz, vp, vp, vp]
+    L.uaes_debug_plan_ff1.argtypes = [i, C.c_uint, sz, sz, C.POINTER(C.c_int)]
+    L.uaes_debug_plan_ff1.restype = C.c_char_p
     for n in ("uaes_cbc_encrypt", "uaes_cbc_decrypt", "uaes_cbc_decrypt_blocks", "uaes_cfb_encrypt", "uaes_cfb_decrypt", "uaes_ofb_xcrypt"):
         getattr(L, n).argtypes = [i, vp, vp, vp, sz, vp]
     for n in ("uaes_ccm_encrypt", "uaes_ccm_decrypt", "uaes_gcmsiv_encrypt", "uaes_gcmsiv_decrypt",
@@ -231,7 +239,7 @@ def engine():
             continue
         if n not in ("uaes_last_error", "uaes_version", "uaes_gcm_key_free", "uaes_gcm_stream_abort", "uaes_debug_gather_stats", "uaes_debug_gcm_look",
                      "uaes_debug_arrangement_name", "uaes_debug_plan_disable", "uaes_debug_plan_poly1305",
-                     "uaes_debug_plan_eax_siv", "uaes_debug_plan_chain", "uaes_debug_plan_kw"):
+                     "uaes_debug_plan_eax_siv", "uaes_debug_plan_chain", "uaes_debug_plan_kw", "uaes_debug_plan_ff1"):
             getattr(L, n).restype = i
     _lib = L
     return L
@@ -671,18 +679,92 @@ def kw_plan(length, nkeys=0, unwrap=False):
     return None if name is None else (name.decode(), out[0], out[1], out[2])
 
 
+def _ff1_alpha(alphabet, radix):
+    """(radix, alphabet argument): alphabet = the bytes of the numerals, or None with radix = raw digit values"""
+    if alphabet is None:
+        if radix is None:
+            raise ValueError("an alphabet or a radix")
+        return radix, None
+    alphabet = bytes(alphabet)
+    return len(alphabet), _in(alphabet)
+
+
+def _ff1(decrypt, key, tweak, text, alphabet, radix, prefill):
+    radix, a = _ff1_alpha(alphabet, radix)
+    o = _out(len(text), prefill)
+    L = engine()
+    fn = L.uaes_ff1_decrypt if decrypt else L.uaes_ff1_encrypt
+    rc = fn(_bits(key), _in(key), radix, a, _in(tweak), len(tweak), _in(text), len(text), o)
+    if rc < 0 and rc != -2:
+        _check(rc, "AES_FPE_decrypt" if decrypt else "AES_FPE_encrypt")
+    return rc, bytes(o)[:len(text)]
+
+
+def AES_FPE_encrypt(key, tweak, text, alphabet=b"0123456789", radix=None, prefill=0):
+    """micro_aes.c:2326 (FF1, SP 800-38G).  text = numerals, one byte each, out of `alphabet` (alphabet=None: raw digit
+    values below `radix`).  Returns (code, output): 0; 1 for a text shorter than the radix's minimum or longer than
+    4096; -2 for a radix outside 2..256 or a repeated alphabet byte; 0x1E for a byte that is no numeral; the output is
+    the prefill unless the code is 0."""
+    return _ff1(False, key, tweak, text, alphabet, radix, prefill)
+
+
+def AES_FPE_decrypt(key, tweak, text, alphabet=b"0123456789", radix=None, prefill=0):
+    """micro_aes.c:2343.  As AES_FPE_encrypt; 0x1D for a byte that is no numeral."""
+    return _ff1(True, key, tweak, text, alphabet, radix, prefill)
+
+
+def ff1_batch(key, tweaks, records, alphabet=b"0123456789", radix=None, decrypt=False, prefill=0, verdicts=True):
+    """FF1 of many equal-sized records under one key (uaes_ff1_*_batch).  tweaks = one tweak (bytes) for all records or a
+    list of equal-sized tweaks, one per record.  Returns (code, outputs, verdicts): a record with a byte that is no
+    numeral keeps the prefill and has verdict 0."""
+    n = len(records)
+    radix, a = _ff1_alpha(alphabet, radix)
+    if isinstance(tweaks, (bytes, bytearray)):
+        tl, stride, tb = len(tweaks), 0, bytes(tweaks)
+    else:
+        if len(tweaks) != n:
+            raise ValueError("one tweak per record")
+        tl, tb = _records(tweaks, "tweaks")
+        stride = tl
+    rl, rb = _records(records, "records")
+    o = _out(n * rl, prefill)
+    v = _out(n)
+    L = engine()
+    fn = L.uaes_ff1_decrypt_batch if decrypt else L.uaes_ff1_encrypt_batch
+    rc = fn(_bits(key), _in(key), radix, a, _in(tb), tl, stride, n, rl, _in(rb), o, v if verdicts else None)
+    if rc < 0 and rc != -2:
+        _check(rc, "uaes_ff1_batch")
+    raw = bytes(o)
+    return rc, [raw[k * rl:(k + 1) * rl] for k in range(n)], list(bytes(v)[:n])
+
+
+def ff1_plan(length, nrec=0, radix=10, decrypt=False):
+    """What FF1 over a text of `length` numerals would run (uaes_debug_plan_ff1; nrec 0: the one-text calls, else a
+    batch): (arrangement, launches, workgroups, threads per workgroup), or None for arguments that make no sense."""
+    out = (C.c_int * 3)()
+    name = engine().uaes_debug_plan_ff1(int(bool(decrypt)), radix, length, nrec, out)
+    return None if name is None else (name.decode(), out[0], out[1], out[2])
+
+
 _compat = {}
 
 
 def compat(bits):
     """libmicro_aes_hip_<bits>.so (the reference's compile-time API, include/micro_aes.h) with the prototypes of the
     key-wrap pair attached: char AES_KEY_wrap(kek, secret, secretLen, wrapped), char AES_KEY_unwrap(kek, wrapped,
-    wrapLen, secret)."""
+    wrapLen, secret), and of the FF1 pairs: char AES_FPE_encrypt(key, tweak, tweakLen, in, len, out) and
+    AES_FPE_encrypt_alpha(alphabet, radix, key, ...)."""
     if bits not in _compat:
         engine()
         lib = C.CDLL(lib_path("libmicro_aes_hip_%d.so" % bits))
         for n in ("AES_KEY_wrap", "AES_KEY_unwrap"):
             getattr(lib, n).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+            getattr(lib, n).restype = C.c_char
+        for n in ("AES_FPE_encrypt", "AES_FPE_decrypt"):
+            getattr(lib, n).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
+            getattr(lib, n).restype = C.c_char
+        for n in ("AES_FPE_encrypt_alpha", "AES_FPE_decrypt_alpha"):
+            getattr(lib, n).argtypes = [C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
             getattr(lib, n).restype = C.c_char
         _compat[bits] = lib
     return _compat[bits]

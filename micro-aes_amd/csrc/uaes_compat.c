@@ -6,10 +6,11 @@
 #include <stdio.h>
 #include <stdlib.h>
 
-#define POLY1305 1                  /* the libraries export AES_Poly1305, AES_EAX_*, AES_SIV_* and AES_KEY_* whatever a */
+#define POLY1305 1                  /* the libraries export AES_Poly1305, AES_EAX_*, AES_SIV_*, AES_KEY_* and AES_FPE_* whatever a */
 #define EAX      1                  /* caller's switches say                                                 */
 #define SIV      1
 #define KWA      1
+#define FPE      1
 #include "../../include/micro_aes.h"
 #include "../../include/uaes_hip.h"
 
@@ -224,6 +225,49 @@ char AES_KEY_wrap(const uint8_t *kek, const void *secret, const size_t secretLen
 char AES_KEY_unwrap(const uint8_t *kek, const void *wrapped, const size_t wrapLen, void *secret)
 {
     return soft("AES_KEY_unwrap", uaes_kw_unwrap(KB, kek, wrapped, wrapLen, secret), M_DECRYPTION_ERROR);
+}
+
+/* FF1 (micro_aes.c:2267-2347): the alphabet is a compile-time choice of the CALLER's build in the reference
+ * (CUSTOM_ALPHABET, micro_fpe.h); every library exports the decimal pair and the pair that takes the alphabet, and
+ * include/micro_aes.h binds AES_FPE_* to the caller's.  Any failure is the reference's one code per direction, with the
+ * output as it was; on success the NUL of :2308 follows the text. */
+static char fpe(const char *fn, int decrypt, const char *alphabet, size_t radix, const uint8_t *key, const uint8_t *tweak,
+                size_t tweakLen, const void *in, size_t len, void *out)
+{
+    const char bad = decrypt ? M_DECRYPTION_ERROR : M_ENCRYPTION_ERROR;
+    int rc;
+    if (radix < 2 || radix > 256) return bad;
+    rc = decrypt ? uaes_ff1_decrypt(KB, key, (unsigned)radix, (const uint8_t *)alphabet, tweak, tweakLen, in, len, out)
+                 : uaes_ff1_encrypt(KB, key, (unsigned)radix, (const uint8_t *)alphabet, tweak, tweakLen, in, len, out);
+    if (rc == 0) { ((char *)out)[len] = 0; return M_RESULT_SUCCESS; }
+    if (rc < 0) fprintf(stderr, "uaes-hip: %s failed (%d): %s\n", fn, rc, uaes_last_error());
+    return bad;
+}
+
+#undef AES_FPE_encrypt
+#undef AES_FPE_decrypt
+char AES_FPE_encrypt(const uint8_t *key, const uint8_t *tweak, const size_t tweakLen,
+                     const void *pntxt, const size_t ptextLen, void *crtxt)
+{
+    return fpe("AES_FPE_encrypt", 0, "0123456789", 10, key, tweak, tweakLen, pntxt, ptextLen, crtxt);
+}
+
+char AES_FPE_decrypt(const uint8_t *key, const uint8_t *tweak, const size_t tweakLen,
+                     const void *crtxt, const size_t crtxtLen, void *pntxt)
+{
+    return fpe("AES_FPE_decrypt", 1, "0123456789", 10, key, tweak, tweakLen, crtxt, crtxtLen, pntxt);
+}
+
+char AES_FPE_encrypt_alpha(const char *alphabet, const size_t radix, const uint8_t *key, const uint8_t *tweak,
+                           const size_t tweakLen, const void *pntxt, const size_t ptextLen, void *crtxt)
+{
+    return fpe("AES_FPE_encrypt", 0, alphabet, radix, key, tweak, tweakLen, pntxt, ptextLen, crtxt);
+}
+
+char AES_FPE_decrypt_alpha(const char *alphabet, const size_t radix, const uint8_t *key, const uint8_t *tweak,
+                           const size_t tweakLen, const void *crtxt, const size_t crtxtLen, void *pntxt)
+{
+    return fpe("AES_FPE_decrypt", 1, alphabet, radix, key, tweak, tweakLen, crtxt, crtxtLen, pntxt);
 }
 
 /* CTS (micro_aes.h:56) is the caller's compile-time choice too: with CTS 0 the reference's CBC pads its last

@@ -282,6 +282,22 @@ int uaesk_kw_batch(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk 
                    int unwrap, int wipe, size_t nkeys, size_t secret_bytes, const void *in, void *out,
                    void *verdicts, int *bad);
 
+/* FF1, SP 800-38G (uaes_ff1.hip; AES_FPE_encrypt / AES_FPE_decrypt with FF_X 1, micro_aes.c:2091-2147, :2267-2314).
+ * What depends on (radix, len, tweak length, alphabet) alone is made once on the host: b and d with exact integers,
+ * the P block as four little-endian column words, inv = byte -> digit value (0xFF: no numeral; every byte is one at
+ * radix 256) and fwd = digit value -> byte.  nrec 0: one text of q->len numerals (a batch of one up to
+ * UAES_FF1_BATCH_MAX, a wave of its own beyond); nrec >= 1: records back to back, record m's tweak at tweaks +
+ * m * tweak_stride (0: one tweak for all).  Device pointers at any byte offset; in == out is fine.  verdicts (may be
+ * NULL) receives 1 / 0 per record; a record with a byte that is no numeral is left unwritten and ORs 1 into *bad. */
+typedef struct {
+    unsigned           radix, len, b, d;
+    unsigned long long tweak_len, tweak_stride;
+    unsigned           p[4];
+    unsigned char      inv[256], fwd[256];
+} uaesk_ff1;
+int uaesk_ff1_run(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, int decrypt, const uaesk_ff1 *q,
+                  const void *tweaks, size_t nrec, const void *in, void *out, void *verdicts, int *bad);
+
 /* Device self-test of the primitives; writes a bitmask of failures.        */
 int uaesk_selftest(void *stream, const uaesk_tables *tb, const uaesk_rk *ek128,
                    const uaesk_rk *dk128, unsigned *d_result);

@@ -1086,6 +1086,145 @@ int uaes_kw_unwrap_batch(int keybits, const uint8_t *kek, size_t nkeys, size_t w
 }
 
 /* ------------------------------------------------------------------------ */
+/* FF1, SP 800-38G (AES_FPE_encrypt / AES_FPE_decrypt, micro_aes.c:2091-2147, :2267-2347) */
+/* ------------------------------------------------------------------------ */
+/* Kernels in uaes_ff1.hip.  What depends on (radix, alphabet, len, tweak length) alone is made here, once per call: the
+ * two alphabet tables, b and d with exact integers (uaesh_ff1_b -- not the reference's floating-point LOGRDX form,
+ * DESIGN.md), the P block.  cap = the longest text this call takes. */
+static int ff1_setup(unsigned radix, const uint8_t *alphabet, size_t tweakLen, size_t tweak_stride, size_t len, size_t cap,
+                     uaesk_ff1 *q)
+{
+    uint8_t seen[256], p[16];
+    size_t v;
+    unsigned i;
+    if (radix < 2 || radix > 256) return fail(UAES_E_ARG, "FF1: radix %u (2..256)", radix);
+    memset(q, 0, sizeof *q);
+    memset(seen, 0, sizeof seen);
+    memset(q->inv, 0xFF, sizeof q->inv);
+    for (i = 0; i < radix; ++i) {
+        const uint8_t a = alphabet ? alphabet[i] : (uint8_t)i;
+        if (seen[a]) return fail(UAES_E_ARG, "FF1: byte 0x%02x occurs twice in the alphabet", a);
+        seen[a] = 1;
+        q->inv[a] = (uint8_t)i;
+        q->fwd[i] = a;
+    }
+    if (len < uaesh_ff1_minlen(radix) || len > cap || (uint64_t)tweakLen >> 32) return UAES_E_DATALENGTH;
+    v = len - len / 2;
+    q->radix = radix;
+    q->len = (unsigned)len;
+    q->b = (unsigned)uaesh_ff1_b(radix, v);
+    q->d = 4 * ((q->b + 3) / 4) + 4;
+    q->tweak_len = tweakLen;
+    q->tweak_stride = tweak_stride;
+    p[0] = 1; p[1] = 2; p[2] = 1; p[3] = (uint8_t)(radix >> 16); p[4] = (uint8_t)(radix >> 8); p[5] = (uint8_t)radix;
+    p[6] = 10; p[7] = (uint8_t)(len / 2);
+    for (i = 0; i < 4; ++i) { p[8 + i] = (uint8_t)(len >> (24 - 8 * i)); p[12 + i] = (uint8_t)(tweakLen >> (24 - 8 * i)); }
+    for (i = 0; i < 4; ++i) q->p[i] = (unsigned)p[4 * i] | (unsigned)p[4 * i + 1] << 8 | (unsigned)p[4 * i + 2] << 16 | (unsigned)p[4 * i + 3] << 24;
+    return 0;
+}
+
+/* nrec 0: one text.  Host arrays travel through the lane's staging buffers; the output's buffer starts as a copy of
+ * the caller's, so that a record the kernel leaves unwritten comes back as it was. */
+static int ff1_gpu(const keysched *ks, int decrypt, const uaesk_ff1 *q, const uint8_t *tweaks, size_t tweak_bytes,
+                   size_t nrec, const void *in, void *outp, uint8_t *verdicts)
+{
+    context *c;
+    lane *L;
+    void *d_in = NULL, *d_out = NULL, *d_verdicts = NULL;
+    const void *d_tweaks = NULL;
+    const size_t n = nrec ? nrec : 1, total = n * q->len;
+    size_t off = 0;
+    int rc, bad = 0;
+    if ((rc = enter(&c, &L)) != 0) return rc;
+    if (verdicts) {
+        if ((rc = lane_scratch(L, SIDE(n), SCRATCH_OTHER)) != 0) goto out;
+        if ((rc = side_out(L, &off, verdicts, n, &d_verdicts)) != 0) goto out;
+        if (is_device_ptr(verdicts) && (rc = wait_for_callers_device_work()) != 0) goto out;
+    }
+    if ((rc = stage_aad(L, tweaks, tweak_bytes, &d_tweaks)) != 0) goto out;
+    if ((rc = stage_text(L, 0, in, total, 1, &d_in)) != 0) goto out;
+    if ((rc = stage_text(L, 1, outp, total, 1, &d_out)) != 0) goto out;
+    HIPCHK_GOTO(hipMemsetAsync(L->d_status, 0, sizeof(int), (hipStream_t)L->stream));
+    ES_KCHK("FF1", uaesk_ff1_run(L->stream, &c->tb, ks->nr, &ks->ek, decrypt, q, d_tweaks, nrec, d_in, d_out, d_verdicts,
+                                 L->d_status));
+    if ((rc = copy_out(L, outp, d_out, total)) != 0) goto out;
+    if (verdicts && (rc = copy_out(L, verdicts, d_verdicts, n)) != 0) goto out;
+    HIPCHK_GOTO(hipMemcpyAsync(&bad, L->d_status, sizeof bad, hipMemcpyDeviceToHost, (hipStream_t)L->stream));
+    HIPCHK_GOTO(hipStreamSynchronize((hipStream_t)L->stream));
+    rc = bad ? (decrypt ? UAES_E_DECRYPTION : UAES_E_ENCRYPTION) : 0;
+out:
+    DONE(L, rc);
+}
+
+static int ff1_one(int decrypt, int keybits, const uint8_t *key, unsigned radix, const uint8_t *alphabet,
+                   const uint8_t *tweak, size_t tweakLen, const void *in, size_t len, void *out)
+{
+    keysched ks;
+    uaesk_ff1 q;
+    int rc;
+    if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
+    if ((rc = ff1_setup(radix, alphabet, tweakLen, 0, len, UAES_FF1_MAX, &q)) != 0) { burn(&ks, sizeof ks); return rc; }
+    if (!in || !out || (tweakLen && !tweak)) { burn(&ks, sizeof ks); return fail(UAES_E_ARG, "NULL pointer"); }
+    if (host_take(in, out, len, 1) && !(tweakLen && is_device_ptr(tweak))) {
+        const uaesh_key hk = host_key(&ks);
+        rc = uaesh_ff1(&hk, decrypt, radix, alphabet, tweak, tweakLen, (const uint8_t *)in, len, (uint8_t *)out);
+        burn(&ks, sizeof ks);
+        return rc == UAES_E_ENCRYPTION || rc == UAES_E_DECRYPTION ? rc : host_result(rc);
+    }
+    rc = ff1_gpu(&ks, decrypt, &q, tweak, tweakLen, 0, in, out, NULL);
+    burn(&ks, sizeof ks);
+    return rc;
+}
+
+int uaes_ff1_encrypt(int keybits, const uint8_t *key, unsigned radix, const uint8_t *alphabet,
+                     const uint8_t *tweak, size_t tweakLen, const void *in, size_t len, void *out)
+{
+    return ff1_one(0, keybits, key, radix, alphabet, tweak, tweakLen, in, len, out);
+}
+
+int uaes_ff1_decrypt(int keybits, const uint8_t *key, unsigned radix, const uint8_t *alphabet,
+                     const uint8_t *tweak, size_t tweakLen, const void *in, size_t len, void *out)
+{
+    return ff1_one(1, keybits, key, radix, alphabet, tweak, tweakLen, in, len, out);
+}
+
+static int ff1_batch(int decrypt, int keybits, const uint8_t *key, unsigned radix, const uint8_t *alphabet,
+                     const uint8_t *tweaks, size_t tweakLen, size_t tweak_stride, size_t nrec, size_t len,
+                     const void *in, void *out, uint8_t *verdicts)
+{
+    keysched ks;
+    uaesk_ff1 q;
+    size_t tweak_bytes;
+    int rc;
+    if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
+    if ((rc = ff1_setup(radix, alphabet, tweakLen, tweak_stride, len, UAES_FF1_BATCH_MAX, &q)) != 0) { burn(&ks, sizeof ks); return rc; }
+    if (nrec == 0) { burn(&ks, sizeof ks); return 0; }
+    if (nrec > (size_t)-1 / len || (tweak_stride && nrec - 1 > ((size_t)-1 - tweakLen) / tweak_stride)) {
+        burn(&ks, sizeof ks);
+        return fail(UAES_E_ARG, "batch size overflows");
+    }
+    if (!in || !out || (tweakLen && !tweaks)) { burn(&ks, sizeof ks); return fail(UAES_E_ARG, "NULL pointer"); }
+    tweak_bytes = tweakLen ? (nrec - 1) * tweak_stride + tweakLen : 0;
+    rc = ff1_gpu(&ks, decrypt, &q, tweaks, tweak_bytes, nrec, in, out, verdicts);
+    burn(&ks, sizeof ks);
+    return rc;
+}
+
+int uaes_ff1_encrypt_batch(int keybits, const uint8_t *key, unsigned radix, const uint8_t *alphabet,
+                           const uint8_t *tweaks, size_t tweakLen, size_t tweak_stride,
+                           size_t nrec, size_t len, const void *in, void *out, uint8_t *verdicts)
+{
+    return ff1_batch(0, keybits, key, radix, alphabet, tweaks, tweakLen, tweak_stride, nrec, len, in, out, verdicts);
+}
+
+int uaes_ff1_decrypt_batch(int keybits, const uint8_t *key, unsigned radix, const uint8_t *alphabet,
+                           const uint8_t *tweaks, size_t tweakLen, size_t tweak_stride,
+                           size_t nrec, size_t len, const void *in, void *out, uint8_t *verdicts)
+{
+    return ff1_batch(1, keybits, key, radix, alphabet, tweaks, tweakLen, tweak_stride, nrec, len, in, out, verdicts);
+}
+
+/* ------------------------------------------------------------------------ */
 /* OCB (RFC 7253; AES_OCB_encrypt / AES_OCB_decrypt, micro_aes.c:1774-1811)     */
 /* ------------------------------------------------------------------------ */
 /* nonceLen / tagLen = the reference's compile-time OCB_NONCE_LEN (1..15) / OCB_TAG_LEN (1..16), micro_aes.h:115-116 */

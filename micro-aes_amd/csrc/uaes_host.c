@@ -5,7 +5,7 @@
  * without one unless the deployer has switched this path on (uaes_set_host_policy / UAES_HOST_MAX, UAES_HOST_CHAINS,
  * UAES_HOST_FALLBACK; include/uaes_hip.h).  It exists for the three places where a GPU cannot serve a caller of the
  * reference well (SURVEY.md 8b "Errors"): host-pointer calls too short to amortise a launch, ONE serial
- * chain (CBC / CFB encryption, OFB, CMAC, CCM's CBC-MAC, key wrap: a latency-bound single wave on the GPU), and a `void` function
+ * chain (CBC / CFB encryption, OFB, CMAC, CCM's CBC-MAC, key wrap, FF1: a latency-bound single wave on the GPU), and a `void` function
  * of the drop-in API on a box whose GPU has gone away.
  *
  * Product code, parity-tested like a kernel (tests/test_host_path.py runs the reference-held vectors and the golden
@@ -1019,4 +1019,139 @@ int uaesh_kw_unwrap(const uaesh_key *k, const uint8_t *wrapped, size_t wrap_len,
     for (i = 0; i < 8; ++i) bad |= a[i] ^ 0xA6;
     memset(a, 0, sizeof a);
     return bad ? 0x1A : 0;
+}
+
+/* ---- FF1, SP 800-38G (FF1_cipher micro_aes.c:2091-2147, FPE_cipher :2267-2314) ---------------------------------------- */
+/* the smallest n with radix^n >= 1 000 000 (the reference's MINLEN for every radix 2..256); 0 for a radix out of range */
+unsigned uaesh_ff1_minlen(unsigned radix)
+{
+    unsigned n = 0;
+    uint64_t p = 1;
+    if (radix < 2 || radix > 256) return 0;
+    while (p < 1000000u) { p *= radix; ++n; }
+    return n;
+}
+
+/* b = ceil(bits(radix^v - 1) / 8), exactly: a power of two has v log2(radix) bits in radix^v - 1, any other radix as
+ * many as radix^v itself, which is multiplied out in 32-bit limbs (v <= UAES_FF1_MAX / 2: at most 512 of them) */
+size_t uaesh_ff1_b(unsigned radix, size_t v)
+{
+    uint32_t w[516];
+    size_t n = 1, i, j, bits;
+    if (radix < 2 || radix > 256 || v == 0 || v > 2048) return 0;
+    if ((radix & (radix - 1)) == 0) {
+        unsigned lg = 0;
+        while ((1u << lg) < radix) ++lg;
+        return (v * lg + 7) / 8;
+    }
+    w[0] = 1;
+    for (i = 0; i < v; ++i) {
+        uint64_t c = 0;
+        for (j = 0; j < n; ++j) { c += (uint64_t)w[j] * radix; w[j] = (uint32_t)c; c >>= 32; }
+        if (c) w[n++] = (uint32_t)c;
+    }
+    bits = 32 * (n - 1);
+    while (w[n - 1]) { ++bits; w[n - 1] >>= 1; }
+    return (bits + 7) / 8;
+}
+
+#define FF1_MAX   4096u
+#define FF1_HALF  (FF1_MAX / 2)
+
+/* NUM_radix of n digits, most significant first, as nl 32-bit limbs, least significant first */
+static void ff1_num(const uint8_t *s, size_t n, unsigned radix, uint32_t *limb, size_t nl)
+{
+    size_t i, j, top = 0;
+    memset(limb, 0, nl * sizeof *limb);
+    for (i = 0; i < n; ++i) {
+        uint64_t c = s[i];
+        for (j = 0; j < top; ++j) { c += (uint64_t)limb[j] * radix; limb[j] = (uint32_t)c; c >>= 32; }
+        if (c && top < nl) limb[top++] = (uint32_t)c;
+    }
+}
+
+/* the d bytes of S (a multiple of 4), a big-endian number, to m digits: what strRadix does a byte at a time, four at
+ * a time; a longer number is cut to S mod radix^m, which is all FF1 wants of it */
+static void ff1_str(const uint8_t *num, size_t d, unsigned radix, uint8_t *s, size_t m)
+{
+    size_t k, i;
+    memset(s, 0, m);
+    for (k = 0; k < d; k += 4) {
+        uint64_t x = (uint64_t)num[k] << 24 | (uint64_t)num[k + 1] << 16 | (uint64_t)num[k + 2] << 8 | num[k + 3];
+        for (i = m; i--; x /= radix) {
+            x += (uint64_t)s[i] << 32;
+            s[i] = (uint8_t)(x % radix);
+        }
+    }
+}
+
+int uaesh_ff1(const uaesh_key *k, int decrypt, unsigned radix, const uint8_t *alphabet,
+              const uint8_t *tweak, size_t tweak_len, const uint8_t *in, size_t len, uint8_t *out)
+{
+    uint8_t x[FF1_MAX], y[FF1_HALF], q[FF1_HALF + 64], inv[256], seen[256], p[16], r[16], blk[16];
+    uint32_t limb[FF1_HALF / 4 + 1];
+    const size_t u = len / 2, v = len - u, tfull = tweak_len & ~(size_t)15, trem = tweak_len & 15;
+    size_t b, d, z, i, j, tail;
+    int round, step;
+    if (radix < 2 || radix > 256) return -2;
+    if (len < uaesh_ff1_minlen(radix) || len > FF1_MAX || (uint64_t)tweak_len >> 32) return 1;
+    memset(seen, 0, sizeof seen);
+    memset(inv, 0, sizeof inv);
+    for (i = 0; i < radix; ++i) {
+        const uint8_t a = alphabet ? alphabet[i] : (uint8_t)i;
+        if (seen[a]) return -2;
+        seen[a] = 1;
+        inv[a] = (uint8_t)i;
+    }
+    for (i = 0; i < len; ++i) {                               /* every numeral is looked up before anything is written */
+        if (!seen[in[i]]) return decrypt ? 0x1D : 0x1E;
+        x[i] = inv[in[i]];
+    }
+    b = uaesh_ff1_b(radix, v);
+    d = 4 * ((b + 3) / 4) + 4;
+    z = (16 - (tweak_len + b + 1) % 16) % 16;
+    tail = trem + z + 1 + b;                                  /* a multiple of 16 */
+    p[0] = 1; p[1] = 2; p[2] = 1; p[3] = (uint8_t)(radix >> 16); p[4] = (uint8_t)(radix >> 8); p[5] = (uint8_t)radix;
+    p[6] = 10; p[7] = (uint8_t)u;
+    for (i = 0; i < 4; ++i) { p[8 + i] = (uint8_t)(len >> (24 - 8 * i)); p[12 + i] = (uint8_t)(tweak_len >> (24 - 8 * i)); }
+    uaesh_encrypt(k->ek, k->nr, p, p);                         /* the PRF over P and the tweak's full blocks: once */
+    for (i = 0; i < tfull; i += 16) {
+        for (j = 0; j < 16; ++j) p[j] ^= tweak[i + j];
+        uaesh_encrypt(k->ek, k->nr, p, p);
+    }
+    memset(q, 0, trem + z);
+    if (trem) memcpy(q, tweak + tfull, trem);
+    for (step = 0; step < 10; ++step) {
+        const size_t nl = (b + 3) / 4;
+        round = decrypt ? 9 - step : step;
+        {   /* even rounds: the first u numerals take F(the last v); odd rounds the other way round */
+            uint8_t *a = round & 1 ? x + u : x;
+            const uint8_t *bb = round & 1 ? x : x + u;
+            const size_t m = round & 1 ? v : u, n = round & 1 ? u : v;
+            unsigned c;
+            ff1_num(bb, n, radix, limb, nl);
+            q[trem + z] = (uint8_t)round;
+            for (i = 0; i < b; ++i) q[trem + z + 1 + i] = (uint8_t)(limb[(b - 1 - i) / 4] >> (8 * ((b - 1 - i) % 4)));
+            memcpy(r, p, 16);
+            for (i = 0; i < tail; i += 16) {
+                for (j = 0; j < 16; ++j) r[j] ^= q[i + j];
+                uaesh_encrypt(k->ek, k->nr, r, r);
+            }
+            memcpy(q + trem + z, r, 16);                      /* S = R | E(R ^ [1]) | ... behind the tweak's tail */
+            for (i = 1; 16 * i < d; ++i) {
+                memcpy(blk, r, 16);
+                blk[15] ^= (uint8_t)i; blk[14] ^= (uint8_t)(i >> 8);
+                uaesh_encrypt(k->ek, k->nr, blk, q + trem + z + 16 * i);
+            }
+            ff1_str(q + trem + z, d, radix, y, m);
+            if (!decrypt)
+                for (i = m, c = 0; i--; c /= radix) { c += (unsigned)a[i] + y[i]; a[i] = (uint8_t)(c % radix); }
+            else
+                for (i = m, c = 1; i--; c /= radix) { c += radix - 1 + a[i] - y[i]; a[i] = (uint8_t)(c % radix); }
+        }
+    }
+    for (i = 0; i < len; ++i) out[i] = alphabet ? alphabet[x[i]] : x[i];
+    memset(x, 0, sizeof x); memset(y, 0, sizeof y); memset(q, 0, sizeof q);
+    memset(limb, 0, sizeof limb); memset(p, 0, sizeof p); memset(r, 0, sizeof r);
+    return 0;
 }

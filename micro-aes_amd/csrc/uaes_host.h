@@ -65,4 +65,13 @@ int  uaesh_ocb(const uaesh_key *k, int decrypt, const uint8_t *nonce, size_t non
 int  uaesh_kw_wrap(const uaesh_key *k, const uint8_t *secret, size_t len, uint8_t *wrapped);                  /* :1829-1855 */
 int  uaesh_kw_unwrap(const uaesh_key *k, const uint8_t *wrapped, size_t wrap_len, uint8_t *secret);           /* :1865-1894 */
 
+/* FF1, SP 800-38G: len numerals of one byte each (digit values, or bytes of `alphabet` = radix distinct bytes), in
+ * place allowed.  0; 1 (len below uaesh_ff1_minlen(radix), above 4096, or a tweak of 2^32 bytes or more); -2 (radix
+ * outside 2..256, a repeated alphabet byte); 0x1E / 0x1D (encrypt / decrypt: a byte that is no numeral).  Nothing is
+ * written unless it returns 0.  uaesh_ff1_b = the b of the specification for a half of v numerals, exact integers. */
+unsigned uaesh_ff1_minlen(unsigned radix);
+size_t   uaesh_ff1_b(unsigned radix, size_t v);
+int  uaesh_ff1(const uaesh_key *k, int decrypt, unsigned radix, const uint8_t *alphabet, const uint8_t *tweak,
+               size_t tweak_len, const uint8_t *in, size_t len, uint8_t *out);                               /* :2091-2147, :2267-2314 */
+
 #endif

@@ -54,12 +54,15 @@
  *   KW    kw.lds                k_kw<LDS> (one wave; the semiblocks in LDS)         (1)    secret <= UAES_KW_LDS_MAX (4 KiB)
  *         kw.global             k_kw<in place> (one wave; loads a chunk ahead)      (1)    beyond
  *         kw.batch              k_kw_batch (sixteen lanes per record)               (1)    uaes_kw_*_batch, <= UAES_KW_BATCH_MAX (256 B)
+ *   FF1   ff1.batch             k_ff1<16> (sixteen lanes per record, four per wave) (1)    uaes_ff1_*_batch; one text of <= UAES_FF1_BATCH_MAX (128) numerals
+ *         ff1.wave              k_ff1<64> (one wave per text)                       (1)    one longer text, <= UAES_FF1_MAX (4096) numerals
  * The Poly1305 rows have a planner of their own (uaesk_plan_poly1305, uaes_poly1305.hip) and ids outside enum
  * uaes_arrangement (uaes_debug_plan_poly1305 names them); a larger message never goes back to a smaller row.
  * So do the EAX and SIV (RFC 5297) rows (uaesk_plan_eax_siv, uaes_eax_siv.hip; uaes_debug_plan_eax_siv), and the
  * CBC / CFB / OFB / CMAC / CCM / batch rows (uaesk_plan_chain, uaes_chain.hip, and uaesk_plan_mac, uaes_mac.hip;
  * uaes_debug_plan_chain); tests/test_gpu_chains.py derives its sizes and message counts from them.  Key wrap has
  * uaesk_plan_kw (uaes_kw.hip; uaes_debug_plan_kw), and tests/test_gpu_kw.py finds its two boundaries by walking it.
+ * FF1 has uaesk_plan_ff1 (uaes_ff1.hip; uaes_debug_plan_ff1); tests/test_gpu_ff1.py walks it likewise.
  */
 #ifndef UAES_PLAN_H
 #define UAES_PLAN_H
@@ -173,6 +176,20 @@ const char *uaesk_chain_arrangement_name(int id);
 enum uaes_kw_arrangement { UAES_KW_LDS = 0, UAES_KW_GLOBAL, UAES_KW_BATCH };
 int uaesk_plan_kw(int dir, size_t len, size_t nkeys, uaes_plan *p);
 const char *uaesk_kw_arrangement_name(int id);
+
+/* FF1, SP 800-38G (uaes_ff1.hip).  dir: 0 encrypt, 1 decrypt; len = numerals of one text (one byte each); nrec 0 = the
+ * one-text calls, nrec >= 1 = a batch of nrec records of len numerals.  A text is at most UAES_FF1_MAX numerals: the
+ * reference takes any length, but the radix conversions are quadratic in it.  A record of a batch is at most
+ * UAES_FF1_BATCH_MAX numerals: the largest power of two at which the 64 records of a workgroup keep their numerals,
+ * the number NUM(B) / the bytes of S and the digits of S in the 31 KiB of LDS the row4 tables leave (uaes_ff1.hip
+ * asserts it).  One text within that limit runs as a batch of one, a longer one on a whole wave.  grid = workgroups,
+ * steps = threads per workgroup.  Returns a HIP error code for a radix outside 2..256, a length below the radix's
+ * minimum (radix^len >= 1 000 000) or above the limit. */
+#define UAES_FF1_MAX       ((size_t)4096)
+#define UAES_FF1_BATCH_MAX ((size_t)128)
+enum uaes_ff1_arrangement { UAES_FF1_BATCH = 0, UAES_FF1_WAVE };
+int uaesk_plan_ff1(int dir, unsigned radix, size_t len, size_t nrec, uaes_plan *p);
+const char *uaesk_ff1_arrangement_name(int id);
 
 #ifdef __cplusplus
 }

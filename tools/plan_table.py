@@ -73,3 +73,12 @@ print("KW batches: a record holds at most UAES_KW_BATCH_MAX = %d bytes of secret
 walk("KW batch, k secrets of 32 bytes (positions/thread: threads per workgroup)",
      lambda k: uaes.kw_plan(32, max(k, 1))[:2] + (0, uaes.kw_plan(32, max(k, 1))[3]), 1, 1 << 20, 1,
      lambda k: "%9d keys (%9.3f MiB)" % (k, k * 32 / MIB))
+for dec in (False, True):
+    walk("FF1 %s, one decimal text of n numerals" % ("decrypt" if dec else "encrypt"),
+         lambda n: uaes.ff1_plan(max(n, 6), decrypt=dec)[:2] + (0, 0), 6, 4096, 1, lambda n: "%11d numerals" % n)
+top = max(n for n in range(6, 8200) if uaes.ff1_plan(n) is not None)
+btop = max(n for n in range(6, 8200) if uaes.ff1_plan(n, 2) is not None)
+print("FF1: a text holds at most UAES_FF1_MAX = %d numerals, a batch record at most UAES_FF1_BATCH_MAX = %d" % (top, btop))
+walk("FF1 batch, k decimal records of 16 numerals (positions/thread: threads per workgroup)",
+     lambda k: uaes.ff1_plan(16, max(k, 1))[:2] + (0, uaes.ff1_plan(16, max(k, 1))[3]), 1, 1 << 20, 1,
+     lambda k: "%9d records (%9.3f MiB)" % (k, k * 16 / MIB))
