@@ -39,6 +39,7 @@ EXPORTS = [
     "uaes_xts_encrypt", "uaes_xts_decrypt", "uaes_xts_sectors",
     "uaes_gcm_encrypt", "uaes_gcm_decrypt", "uaes_gcm_encrypt_iv", "uaes_gcm_decrypt_iv", "uaes_ghash",
     "uaes_gcm_encrypt_ex", "uaes_gcm_decrypt_ex", "uaes_ccm_encrypt_ex", "uaes_ccm_decrypt_ex",
+    "uaes_ccm_encrypt_batch", "uaes_ccm_decrypt_batch",
     "uaes_ocb_encrypt_ex", "uaes_ocb_decrypt_ex",
     "uaes_cmac", "uaes_ccm_encrypt", "uaes_ccm_decrypt", "uaes_gcmsiv_encrypt", "uaes_gcmsiv_decrypt",
     "uaes_ocb_encrypt", "uaes_ocb_decrypt", "uaes_ocb_dev",
@@ -154,6 +155,8 @@ def engine():
     L.uaes_siv_decrypt.argtypes = [i, vp, vp, vp, sz, vp, sz, vp]
     L.uaes_eax_encrypt_batch.argtypes = [i, vp, sz, sz, vp, sz, vp, sz, vp, vp, vp]
     L.uaes_eax_decrypt_batch.argtypes = [i, vp, sz, sz, vp, sz, vp, sz, vp, vp, vp, vp]
+    L.uaes_ccm_encrypt_batch.argtypes = [i, vp, sz, sz, sz, sz, vp, vp, vp, sz, vp, vp, vp]
+    L.uaes_ccm_decrypt_batch.argtypes = [i, vp, sz, sz, sz, sz, vp, vp, vp, sz, vp, vp, vp, vp]
     L.uaes_siv_encrypt_batch.argtypes = [i, vp, sz, sz, vp, sz, vp, vp, vp]
     L.uaes_siv_decrypt_batch.argtypes = [i, vp, sz, sz, vp, sz, vp, vp, vp, vp]
     L.uaes_debug_plan_eax_siv.argtypes = [i, i, sz, sz, C.POINTER(C.c_int)]
@@ -585,6 +588,39 @@ def eax_batch(key, nonces, aads, texts, decrypt=False, tags=None, prefill=0):
     return rc, [raw[i * ml:(i + 1) * ml] for i in range(n)], list(bytes(v)[:n])
 
 
+def ccm_batch(key, nonces, aads, texts, tag_len=16, decrypt=False, tags=None, prefill=0, lens=None):
+    """CCM of many records under one key (uaes_ccm_*_batch): equal-sized nonces (7..13 bytes), AADs (or None) and
+    texts.  encrypt: returns (ciphertexts, tag_len-byte tags); decrypt (tags given): returns (code, plaintexts,
+    verdicts); like the reference's CCM a forged record's plaintext is what CTR made of it (zeros under
+    wipe_on_auth_failure).  lens (optional, one per record): record m is the first lens[m] bytes of its text, and the
+    rest of its output slot stays the prefill."""
+    n = len(texts)
+    aads = aads if aads is not None else [b""] * n
+    if len(nonces) != n or len(aads) != n or (decrypt and (tags is None or len(tags) != n)) or (lens is not None and len(lens) != n):
+        raise ValueError("one nonce, AAD (tag and length) per record")
+    if n == 0:
+        return (0, [], []) if decrypt else ([], [])
+    nl, nb = _records(nonces, "nonces")
+    al, ab = _records(aads, "AADs")
+    ml, mb = _records(texts, "texts")
+    lv = (C.c_uint32 * n)(*lens) if lens is not None else None
+    L = engine()
+    o = _out(n * ml, prefill)
+    if not decrypt:
+        t = _out(n * tag_len)
+        _check(L.uaes_ccm_encrypt_batch(_bits(key), _in(key), nl, tag_len, n, ml, lv, _in(nb), _in(ab), al, _in(mb), o, t),
+               "uaes_ccm_encrypt_batch")
+        raw, tr = bytes(o), bytes(t)
+        return [raw[i * ml:(i + 1) * ml] for i in range(n)], [tr[tag_len * i:tag_len * (i + 1)] for i in range(n)]
+    if any(len(x) != tag_len for x in tags):
+        raise ValueError("tags of tag_len bytes")
+    v = _out(n)
+    rc = _check(L.uaes_ccm_decrypt_batch(_bits(key), _in(key), nl, tag_len, n, ml, lv, _in(nb), _in(ab), al, _in(mb),
+                                         _in(b"".join(tags)), o, v), "uaes_ccm_decrypt_batch")
+    raw = bytes(o)
+    return rc, [raw[i * ml:(i + 1) * ml] for i in range(n)], list(bytes(v)[:n])
+
+
 def siv_batch(keys, aads, texts, decrypt=False, ivs=None, prefill=0):
     """SIV (RFC 5297) of many records under one key pair (uaes_siv_*_batch): equal-sized AADs (or None) and texts.
     encrypt: returns (ivs, ciphertexts); decrypt (ivs given): returns (code, plaintexts, verdicts)."""
@@ -619,7 +655,8 @@ def eax_siv_plan(siv, length, nmsg=1, decrypt=False):
     return name.decode(), out[0], out[1], out[2]
 
 
-CHAIN_WHAT = {"cbc": 0, "cfb": 1, "ofb": 2, "cmac": 3, "ccm": 4, "cbc_batch": 5, "cmac_batch": 6, "cbc_nocts": 7}
+CHAIN_WHAT = {"cbc": 0, "cfb": 1, "ofb": 2, "cmac": 3, "ccm": 4, "cbc_batch": 5, "cmac_batch": 6, "cbc_nocts": 7,
+              "ccm_batch": 9}
 
 
 def chain_plan(what, a, b=0, decrypt=False):

@@ -551,8 +551,8 @@ extern "C" int uaesk_plan_chain(int what, int dir, size_t a, size_t b, uaes_plan
 extern "C" const char *uaesk_chain_arrangement_name(int id)
 {
     static const char *const names[] = { "chain.serial", "fbdec.single", "fbdec.tiled", "ccm.fused", "ccm.split",
-                                         "batch.row", "batch.lane" };
-    return id >= 0 && id < 7 ? names[id] : "?";
+                                         "batch.row", "batch.lane", "ccm.batch" };
+    return id >= 0 && id < 8 ? names[id] : "?";
 }
 
 template <int NR, bool CFB, int U>

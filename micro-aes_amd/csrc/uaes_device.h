@@ -178,6 +178,14 @@ int uaesk_ccm(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek,
               int decrypt, const uint8_t *nonce, size_t nonce_len, size_t tag_len,
               const void *aad, size_t aad_len,
               const void *in, size_t len, void *out, int *status);
+/* Batch: nmsg records under one key, sixteen lanes per record (k_ccm_batch); all device pointers.  Record m: text at
+ * in / out + m msg_bytes (msg_bytes <= UAES_CCM_BATCH_MAX), its first lens[m] bytes (lens NULL: msg_bytes), nonce at
+ * nonces + m nonce_len, AAD at aad + m aad_bytes (<= 0xFEFF), tag at tags + m tag_len.  decrypt writes verdicts[m]
+ * (1 = authentic) and ORs 1 into *bad for a forgery, whose output stays as decrypted or is zeroed when wipe != 0. */
+int uaesk_ccm_batch(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, int decrypt, int wipe,
+                    const void *nonces, size_t nonce_len, size_t tag_len, const void *aad, size_t aad_bytes,
+                    size_t nmsg, size_t msg_bytes, const void *lens, const void *in, void *out, void *tags,
+                    void *verdicts, int *bad);
 
 /* Feedback modes (micro_aes.c:697-893).  mode: 0 CBC encrypt (CS3 stealing),
  * 1 CBC decrypt, 2 CFB encrypt, 3 CFB decrypt, 4 OFB.  iv16 is a host pointer.

@@ -103,29 +103,6 @@ __device__ __forceinline__ void row_put(unsigned char *p, u32 w, u32 n, u32 c)
         if (4u * c + k < n) p[4u * c + k] = (unsigned char)(w >> (8u * k));
 }
 
-/* two independent blocks, round by round (the second chain hides in the first one's LDS latency);
- * La / Lb may hold different keys over the same tables */
-template <int NR>
-__device__ __forceinline__ void row_encrypt2(u32 &a, u32 &b, const RowLane<NR> &La, const RowLane<NR> &Lb)
-{
-    a ^= La.kc[0];
-    b ^= Lb.kc[0];
-    u32 pa = __builtin_amdgcn_perm(a, La.tmain, La.sel), pb = __builtin_amdgcn_perm(b, Lb.tmain, Lb.sel);
-#pragma unroll
-    for (int r = 1; r <= NR; ++r) {
-        u32 ta = lds_word(pa), tb = lds_word(pb);
-        if (r == NR) { ta = __builtin_amdgcn_perm(ta, 0u, La.lsel); tb = __builtin_amdgcn_perm(tb, 0u, Lb.lsel); }
-        const u32 ya = ta ^ row_dpp<0x12B>(ta), yb = tb ^ row_dpp<0x12B>(tb);
-        const u32 za = ya ^ row_dpp<0x126>(ya), zb = yb ^ row_dpp<0x126>(yb);
-        a = La.kc[r] ^ row_dpp<0x00>(za);
-        b = Lb.kc[r] ^ row_dpp<0x00>(zb);
-        if (r < NR) {
-            pa = __builtin_amdgcn_perm(a, r + 1 < NR ? La.tmain : La.tlast, La.sel);
-            pb = __builtin_amdgcn_perm(b, r + 1 < NR ? Lb.tmain : Lb.tlast, Lb.sel);
-        }
-    }
-}
-
 /* K1 = 2 Enc(0), K2 = 4 Enc(0) (getSubkeys :593-605): this lane's columns */
 template <int NR>
 __device__ __forceinline__ void cmac_subkeys(const RowLane<NR> &L, u32 &k1c, u32 &k2c)

@@ -1409,7 +1409,8 @@ const char *uaes_debug_plan_chain(int what, int dir, size_t a, size_t b, int out
 {
     uaes_plan p;
     memset(&p, 0, sizeof p);
-    if (what == UAES_WHAT_CMAC || what == UAES_WHAT_CCM ? uaesk_plan_mac(what, dir, a, &p) : uaesk_plan_chain(what, dir, a, b, &p))
+    if (what == UAES_WHAT_CCM_BATCH ? uaesk_plan_ccm_batch(dir, a, b, &p)
+        : what == UAES_WHAT_CMAC || what == UAES_WHAT_CCM ? uaesk_plan_mac(what, dir, a, &p) : uaesk_plan_chain(what, dir, a, b, &p))
         return NULL;
     if (out) { out[0] = p.launches; out[1] = (int)p.grid; out[2] = (int)p.steps; }
     return uaesk_chain_arrangement_name(p.arrangement);

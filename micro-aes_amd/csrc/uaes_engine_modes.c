@@ -790,6 +790,81 @@ int uaes_siv_decrypt_batch(int keybits, const uint8_t *keys, size_t nmsg, size_t
                       verdicts);
 }
 
+/* CCM batches (k_ccm_batch, uaes_mac.hip): as aead_batch, with the nonce and tag lengths, packed tags of tagLen bytes
+ * and optional per-record lengths.  Like the reference's CCM a decryption writes the text before it knows the tag, so
+ * the output buffer need not start as the caller's -- except with `lens`, where the remainder of a slot is not written
+ * and a host buffer is copied in first.  Every argument is checked before the device is touched.                   */
+static int ccm_batch(int decrypt, int keybits, const uint8_t *key, size_t nonceLen, size_t tagLen, size_t nmsg,
+                     size_t msg_bytes, const uint32_t *lens, const uint8_t *nonces, const void *aData, size_t aad_bytes,
+                     const void *in, void *outp, uint8_t *tags, uint8_t *verdicts)
+{
+    context *c;
+    lane *L;
+    keysched ks;
+    const void *d_nonces = NULL, *d_aad = NULL, *d_tags_in = NULL, *d_lens = NULL;
+    void *d_in = NULL, *d_out = NULL, *d_tags = NULL, *d_verdicts = NULL;
+    const size_t lim = (size_t)-1 / 8;               /* five side arrays and their padding still add up */
+    size_t off = 0;
+    int rc, bad = 0;
+    if ((rc = ccm_lens_ok(nonceLen, tagLen)) != 0) return rc;
+    if (msg_bytes > UAES_CCM_BATCH_MAX)
+        return fail(UAES_E_ARG, "a CCM batch record holds at most %zu bytes (got %zu)", (size_t)UAES_CCM_BATCH_MAX, msg_bytes);
+    if (aad_bytes > 0xFEFF) return fail(UAES_E_ARG, "a CCM batch record takes at most 65279 bytes of AAD (got %zu)", aad_bytes);
+    if (nmsg > lim / (msg_bytes > 16 ? msg_bytes : 16) || (aad_bytes && nmsg > lim / aad_bytes))
+        return fail(UAES_E_ARG, "batch size overflows");
+    if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
+    if (nmsg == 0) { burn(&ks, sizeof ks); return 0; }
+    {
+        const size_t total = nmsg * msg_bytes;
+        if ((total && (!in || !outp)) || !nonces || !tags || (decrypt && !verdicts) || (aad_bytes && !aData)) {
+            burn(&ks, sizeof ks);
+            return fail(UAES_E_ARG, "NULL pointer");
+        }
+        if ((rc = enter(&c, &L)) != 0) { burn(&ks, sizeof ks); return rc; }
+        if ((rc = lane_scratch(L, SIDE(nmsg * nonceLen) + SIDE(nmsg * aad_bytes) + SIDE(nmsg * tagLen) + SIDE(nmsg) +
+                               SIDE(nmsg * sizeof *lens), SCRATCH_OTHER)) != 0) goto out;
+        if ((rc = side_in(L, &off, nonces, nmsg * nonceLen, &d_nonces)) != 0) goto out;
+        if ((rc = side_in(L, &off, aData, nmsg * aad_bytes, &d_aad)) != 0) goto out;
+        if (lens && (rc = side_in(L, &off, lens, nmsg * sizeof *lens, &d_lens)) != 0) goto out;
+        if (decrypt) {
+            if ((rc = side_in(L, &off, tags, nmsg * tagLen, &d_tags_in)) != 0) goto out;
+            d_tags = (void *)d_tags_in;
+            if ((rc = side_out(L, &off, verdicts, nmsg, &d_verdicts)) != 0) goto out;
+        } else if ((rc = side_out(L, &off, tags, nmsg * tagLen, &d_tags)) != 0) goto out;
+        if ((rc = stage_text(L, 0, in, total, 1, &d_in)) != 0) goto out;
+        if ((rc = stage_text(L, 1, outp, total, lens != NULL, &d_out)) != 0) goto out;
+        if (decrypt) HIPCHK_GOTO(hipMemsetAsync(L->d_status, 0, sizeof(int), (hipStream_t)L->stream));
+        ES_KCHK("ccm batch", uaesk_ccm_batch(L->stream, &c->tb, ks.nr, &ks.ek, decrypt, wipe_on_auth_failure(), d_nonces,
+                                             nonceLen, tagLen, d_aad, aad_bytes, nmsg, msg_bytes, d_lens, d_in, d_out,
+                                             d_tags, d_verdicts, L->d_status));
+        if ((rc = copy_out(L, outp, d_out, total)) != 0) goto out;
+        if ((rc = decrypt ? copy_out(L, verdicts, d_verdicts, nmsg) : copy_out(L, tags, d_tags, nmsg * tagLen)) != 0) goto out;
+        if (decrypt) HIPCHK_GOTO(hipMemcpyAsync(&bad, L->d_status, sizeof bad, hipMemcpyDeviceToHost, (hipStream_t)L->stream));
+        HIPCHK_GOTO(hipStreamSynchronize((hipStream_t)L->stream));
+        rc = bad ? UAES_E_AUTHENTICATION : 0;
+    }
+out:
+    burn(&ks, sizeof ks);
+    DONE(L, rc);
+}
+
+int uaes_ccm_encrypt_batch(int keybits, const uint8_t *key, size_t nonceLen, size_t tagLen,
+                           size_t nmsg, size_t msg_bytes, const uint32_t *lens,
+                           const uint8_t *nonces, const void *aData, size_t aad_bytes,
+                           const void *pntxt, void *crtxt, uint8_t *tags)
+{
+    return ccm_batch(0, keybits, key, nonceLen, tagLen, nmsg, msg_bytes, lens, nonces, aData, aad_bytes, pntxt, crtxt, tags, NULL);
+}
+
+int uaes_ccm_decrypt_batch(int keybits, const uint8_t *key, size_t nonceLen, size_t tagLen,
+                           size_t nmsg, size_t msg_bytes, const uint32_t *lens,
+                           const uint8_t *nonces, const void *aData, size_t aad_bytes,
+                           const void *crtxt, const uint8_t *tags, void *pntxt, uint8_t *verdicts)
+{
+    return ccm_batch(1, keybits, key, nonceLen, tagLen, nmsg, msg_bytes, lens, nonces, aData, aad_bytes, crtxt, pntxt,
+                     (uint8_t *)tags, verdicts);
+}
+
 /* ------------------------------------------------------------------------ */
 /* CBC / CFB / OFB                                   */
 /* ------------------------------------------------------------------------ */

@@ -6,6 +6,8 @@
  *                 doubleBblock :434-444
  *   k_ccm_tag  <- CCMtag :1222-1256 (used by AES_CCM_encrypt/decrypt :1268-1314;
  *                 the CTR half is k_ctr with the CCM/GCM pre-increment)
+ *   k_ccm        <- AES_CCM_encrypt/decrypt of a short text in one launch of one wave
+ *   k_ccm_batch  <- the same for many records under one key, a DPP row per record
  *
  * A CBC-MAC is a strictly serial chain (M <- Enc(M ^ X_i)): what counts is the latency
  * of one block.  One wave walks the message; the sixteen lanes of a DPP row share each block
@@ -293,6 +295,116 @@ __global__ __launch_bounds__(64) void k_ccm(uaesk_rk rk, uaesk_tables tb, uint4 
     }
 }
 
+/* ---- batches: nmsg CCM records under one key, sixteen lanes per record, four records per wave ---------------------- */
+
+/* bytes of column c below n */
+__device__ __forceinline__ u32 ccm_keep(u32 n, u32 c)
+{
+    return n >= 4u * c + 4u ? 0xffffffffu : n <= 4u * c ? 0u : (1u << (8u * (n - 4u * c))) - 1u;
+}
+
+/* the first n bytes of the block whose column words the row holds -> p (one lane per column of the row stores) */
+__device__ __forceinline__ void ccm_put(unsigned char *p, u32 w, u32 n, u32 c)
+{
+    if (threadIdx.x & 3u) return;
+    if (n >= 16 && (((uintptr_t)p) & 3u) == 0) { ((u32 *)p)[c] = w; return; }
+#pragma unroll
+    for (u32 k = 0; k < 4; ++k)
+        if (4u * c + k < n) p[4u * c + k] = (unsigned char)(w >> (8u * k));
+}
+
+/* this lane's column of A_j: A0 with the counter j in bytes 14..15 (a text of at most UAES_CCM_BATCH_MAX bytes has at
+ * most 4096 blocks, so the reference's 56-bit increment of bytes 9..15 never leaves them, whatever the nonce length) */
+__device__ __forceinline__ u32 ccm_a_col(u32 a0c, u32 j, u32 c)
+{
+    return c == 3u ? a0c | (j & 0xff00u) << 8 | (j & 0xffu) << 24 : a0c;
+}
+
+/* Record m: text at in / out + m msg_bytes (its first lens[m] <= msg_bytes bytes; lens == NULL: all of it), nonce at
+ * nonces + m nonce_len, AAD at aad + m aad_bytes (<= 0xFEFF: the two-byte length header), tag at tags + m tag_len.
+ * One row step is a MAC block and a counter block in the same instructions (row_encrypt2); the keystream runs one
+ * block ahead of the chain in BOTH directions, so that the block is stored before the step and the loop is the same:
+ *   Enc(B0) || KS_0,  the AAD blocks,  then per text block  out_i = in_i ^ KS_i,  Enc(m ^ P_i) || KS_(i+1),
+ * and the last step carries Enc(A0) for the tag in place of a keystream block nobody needs (no text: B0's does):
+ * 1 + ceil((2 + aad) / 16) + ceil(len / 16) steps per record.  A row never reads a lane of another record.
+ * Decrypt follows the reference per record (AES_CCM_decrypt :1296-1314): the text is written before the tag is
+ * known; verdicts[m] = 1 if authentic, else 0 and bad[0] |= 1 (a vector atomic), the output left as decrypted or
+ * zeroed when `wipe`.  in == out works: a block is loaded before it is stored.  A4: text 4-byte aligned. */
+template <int NR, bool DEC, bool A4>
+__global__ __launch_bounds__(UAES_WG) void k_ccm_batch(uaesk_rk rk, uaesk_tables tb, int wipe,
+                                                       const unsigned char *nonces, u32 nonce_len, u32 tag_len,
+                                                       const unsigned char *aad, u32 aad_bytes,
+                                                       u64 nmsg, u32 msg_bytes, const u32 *lens,
+                                                       const unsigned char *in, unsigned char *out,
+                                                       unsigned char *tags, unsigned char *verdicts, int *bad)
+{
+    row4_fill_tables(tb.te0, rk);
+    const RowLane<NR> L = row4_lane<NR>();
+    const u32 c = L.c;
+    const u64 rows = blockDim.x >> 4;
+    for (u64 m = (u64)blockIdx.x * rows + (threadIdx.x >> 4); m < nmsg; m += (u64)gridDim.x * rows) {
+        u32 len = msg_bytes;
+        if (lens) { len = lens[m]; if (len > msg_bytes) len = msg_bytes; }
+        const unsigned char *np = nonces + m * nonce_len;
+        const unsigned char *src = in + m * msg_bytes;
+        unsigned char *dst = out + m * msg_bytes;
+        unsigned char *tg = tags + m * tag_len;
+        /* A0 = { 14 - nonce_len, nonce, 0... } (:1273), B0 = A0 with the tag length, the AAD bit and the text length (:1229-1233) */
+        u32 a0c = c == 0u ? 14u - nonce_len : 0u;
+#pragma unroll
+        for (u32 k = 0; k < 4; ++k) {
+            const u32 i = 4u * c + k;
+            if (i >= 1u && i <= nonce_len) a0c |= (u32)np[i - 1u] << (8u * k);
+        }
+        const u32 full = len >> 4, rem = len & 15u, nblk = full + (rem ? 1u : 0u);
+        u32 mc = a0c;
+        if (c == 0u) mc |= ((tag_len - 2u) << 2) | (aad_bytes ? 0x40u : 0u);
+        if (c == 3u) mc |= (len & 0xff00u) << 8 | (len & 0xffu) << 24;
+        u32 ks = nblk ? ccm_a_col(a0c, 1u, c) : a0c;
+        row_encrypt2<NR>(mc, ks, L, L);
+        if (aad_bytes) {
+            const unsigned char *ap = aad + m * aad_bytes;
+            u32 h = c == 0u ? (aad_bytes >> 8) | (aad_bytes & 0xffu) << 8 : 0u;       /* the length in front, big-endian */
+#pragma unroll
+            for (u32 k = 0; k < 4; ++k) {
+                const u32 i = 4u * c + k;
+                if (i >= 2u && i - 2u < aad_bytes) h |= (u32)ap[i - 2u] << (8u * k);
+            }
+            mc = row_encrypt<NR>(mc ^ h, L);
+            if (aad_bytes > 14u) cbcmac_absorb<NR>(mc, ap + 14, aad_bytes - 14u, L);
+        }
+        row_walk<A4>(src, full, c, [&](u64 i, u32 x) {
+            const u32 y = x ^ ks;
+            row_store_full<A4>(dst + 16 * i, y, c);
+            mc ^= DEC ? y : x;
+            ks = (u32)i + 1u < nblk ? ccm_a_col(a0c, (u32)i + 2u, c) : a0c;
+            row_encrypt2<NR>(mc, ks, L, L);
+        });
+        if (rem) {                                     /* the partial last block: zero padded into the MAC, cut in the output */
+            const u32 x = row_load(src + 16 * (u64)full, rem, c);
+            const u32 y = (x ^ ks) & ccm_keep(rem, c);
+            ccm_put(dst + 16 * (u64)full, y, rem, c);
+            mc ^= DEC ? y : x;
+            ks = a0c;
+            row_encrypt2<NR>(mc, ks, L, L);
+        }
+        const u32 t = mc ^ ks;                         /* tag = CBC-MAC ^ Enc(A0) */
+        if (!DEC) {
+            ccm_put(tg, t, tag_len, c);
+        } else {
+            const u32 d = (t ^ row_load(tg, tag_len, c)) & ccm_keep(tag_len, c);
+            const u64 b = __ballot(d != 0u);
+            const bool forged = ((b >> (threadIdx.x & 48u)) & 0xffffull) != 0;      /* this row's sixteen lanes */
+            if ((threadIdx.x & 15u) == 0) {
+                verdicts[m] = forged ? 0 : 1;
+                if (forged) atomicOr(bad, 1);
+            }
+            if (forged && wipe)
+                for (u32 i = 0; i < len; i += 16) ccm_put(dst + i, 0u, len - i < 16u ? len - i : 16u, c);
+        }
+    }
+}
+
 /* ---- the plan (uaes_plan.h) ---------------------------------------------------------------------------------------
  * CMAC is one wave whatever the length.  CCM: a short message (CCM's usual diet) is ONE launch, the MAC chain and the
  * counter blocks share the wave (ccm_text); its chain step is a third longer than the plain MAC's, so texts beyond
@@ -318,6 +430,58 @@ extern "C" int uaesk_plan_mac(int what, int dir, size_t a, uaes_plan *p)
         if (uaesk_plan(UAES_PLAN_CTR, 0, a, 0, 0, &ctr)) return (int)hipErrorInvalidValue;
         p->launches += ctr.launches;
     }
+    return 0;
+}
+
+/* ccm.batch: the launch shape of the other row batches (batch_shape in uaes_eax_siv.hip, plan_batch in uaes_chain.hip):
+ * 64 records per 16-wave workgroup; few records: 4-wave workgroups, so that they spread over the CUs; the grid is
+ * capped at the CU count and the kernel strides beyond it */
+static void plan_ccm_batch(u64 nmsg, uaes_plan *p)
+{
+    const unsigned cus = uaesk_cus_or_256();
+    const unsigned wg = (nmsg + 63) / 64 * 2 <= cus ? 256u : UAES_WG;
+    const u64 want = (nmsg + wg / 16 - 1) / (wg / 16);
+    memset(p, 0, sizeof *p);
+    p->arrangement = UAES_CCM_BATCH;
+    p->launches = 1;
+    p->grid = (unsigned)(want < cus ? (want ? want : 1) : cus);
+    p->steps = wg;
+}
+
+extern "C" int uaesk_plan_ccm_batch(int dir, size_t len, size_t nmsg, uaes_plan *p)
+{
+    memset(p, 0, sizeof *p);
+    if ((dir != 0 && dir != 1) || len > UAES_CCM_BATCH_MAX) return (int)hipErrorInvalidValue;
+    plan_ccm_batch(nmsg, p);
+    return 0;
+}
+
+template <int NR>
+static int launch_ccm_batch(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *ek, int decrypt, int wipe,
+                            const void *nonces, size_t nonce_len, size_t tag_len, const void *aad, size_t aad_bytes,
+                            size_t nmsg, size_t msg_bytes, const void *lens, const void *in, void *out, void *tags,
+                            void *verdicts, int *bad)
+{
+    const bool a4 = ((((uintptr_t)in) | ((uintptr_t)out)) & 3u) == 0 && msg_bytes % 4 == 0;
+    uaes_plan p;
+    plan_ccm_batch(nmsg, &p);
+    return with_bool(decrypt, [&](auto DEC) { return with_bool(a4, [&](auto A4) {
+        return uaesk_launch(k_ccm_batch<NR, decltype(DEC)::value, decltype(A4)::value>, p.grid, p.steps, UAES_LDS_ROW4, st, *ek, *tb,
+                            wipe, nonces, nonce_len, tag_len, aad, aad_bytes, nmsg, msg_bytes, lens, in, out, tags, verdicts,
+                            bad); }); });
+}
+
+extern "C" int uaesk_ccm_batch(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, int decrypt, int wipe,
+                               const void *nonces, size_t nonce_len, size_t tag_len, const void *aad, size_t aad_bytes,
+                               size_t nmsg, size_t msg_bytes, const void *lens, const void *in, void *out, void *tags,
+                               void *verdicts, int *bad)
+{
+    if (nonce_len < 7 || nonce_len > 13 || tag_len < 4 || tag_len > 16 || (tag_len & 1) || aad_bytes > 0xFEFF ||
+        msg_bytes > UAES_CCM_BATCH_MAX)
+        return (int)hipErrorInvalidValue;
+    if (nmsg == 0) return 0;
+    DISPATCH_NR(nr, return (launch_ccm_batch<NR>(S(stream), tb, ek, decrypt, wipe, nonces, nonce_len, tag_len, aad, aad_bytes,
+                                                 nmsg, msg_bytes, lens, in, out, tags, verdicts, bad)));
     return 0;
 }
 

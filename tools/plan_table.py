@@ -65,6 +65,18 @@ for what in ("cbc_batch", "cmac_batch"):
     walk("%s, k messages of 1 KiB (positions/thread: threads per workgroup)" % what,
          lambda k: uaes.chain_plan(what, 1024, max(k, 1))[:2] + (0, uaes.chain_plan(what, 1024, max(k, 1))[3]), 1, 1 << 20, 1,
          lambda k: "%9d msgs (%9.3f MiB)" % (k, k * 1024 / MIB))
+def ccm_batch_plan(k, n=64):
+    try:
+        return uaes.chain_plan("ccm_batch", n, max(k, 1))
+    except ValueError:
+        return None
+
+
+top = max(n for n in range(65000, 66000) if ccm_batch_plan(2, n) is not None)
+print("CCM batches: a record holds at most UAES_CCM_BATCH_MAX = %d bytes of text" % top)
+walk("CCM batch, k records of 64 bytes (positions/thread: threads per workgroup)",
+     lambda k: ccm_batch_plan(k)[:2] + (0, ccm_batch_plan(k)[3]), 1, 1 << 20, 1,
+     lambda k: "%9d records (%9.3f MiB)" % (k, k * 64 / MIB))
 for dec in (False, True):
     walk("KW %s, one secret of n bytes" % ("unwrap" if dec else "wrap"),
          lambda n: uaes.kw_plan(max(n, 16), unwrap=dec)[:2] + (0, 0), 16, 64 * MIB, 8)
