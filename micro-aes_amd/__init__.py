@@ -281,6 +281,11 @@ def _out(n, fill=0):
     return buf
 
 
+def _split(buf, size, n):
+    """the n records of `size` bytes a batch call left back to back in buf"""
+    return [buf[i * size:(i + 1) * size] for i in range(n)]
+
+
 def _bits(key, mult=1):
     bits = len(key) * 8 // mult
     if bits not in (128, 192, 256):
@@ -430,7 +435,7 @@ def cbc_encrypt_batch(key, ivs, messages):
     _check(engine().uaes_cbc_encrypt_batch(_bits(key), _in(key), _in(b"".join(ivs)), n, size,
                                            _in(b"".join(messages)), o), "uaes_cbc_encrypt_batch")
     raw = bytes(o)
-    return [raw[i * size:(i + 1) * size] for i in range(n)]
+    return _split(raw, size, n)
 
 
 def cmac_batch(key, messages):
@@ -444,7 +449,7 @@ def cmac_batch(key, messages):
     o = _out(n * 16)
     _check(engine().uaes_cmac_batch(_bits(key), _in(key), n, size, _in(b"".join(messages)), o), "uaes_cmac_batch")
     raw = bytes(o)
-    return [raw[16 * i:16 * i + 16] for i in range(n)]
+    return _split(raw, 16, n)
 
 
 def AES_CFB_encrypt(key, iVec, pntxt):
@@ -503,7 +508,7 @@ def poly1305_batch(keys, nonces, messages):
     _check(engine().uaes_poly1305_batch(_poly_bits(keys), _in(keys), _in(b"".join(nonces)), n, size,
                                         _in(b"".join(messages)), o), "uaes_poly1305_batch")
     raw = bytes(o)
-    return [raw[16 * i:16 * i + 16] for i in range(n)]
+    return _split(raw, 16, n)
 
 
 def poly1305_plan(len, nmsg=1):
@@ -580,12 +585,12 @@ def eax_batch(key, nonces, aads, texts, decrypt=False, tags=None, prefill=0):
         _check(L.uaes_eax_encrypt_batch(_bits(key), _in(key), n, ml, _in(nb), nl, _in(ab), al, _in(mb), o, t),
                "uaes_eax_encrypt_batch")
         raw, tr = bytes(o), bytes(t)
-        return [raw[i * ml:(i + 1) * ml] for i in range(n)], [tr[16 * i:16 * i + 16] for i in range(n)]
+        return _split(raw, ml, n), _split(tr, 16, n)
     v = _out(n)
     rc = _check(L.uaes_eax_decrypt_batch(_bits(key), _in(key), n, ml, _in(nb), nl, _in(ab), al, _in(mb),
                                          _in(b"".join(tags)), o, v), "uaes_eax_decrypt_batch")
     raw = bytes(o)
-    return rc, [raw[i * ml:(i + 1) * ml] for i in range(n)], list(bytes(v)[:n])
+    return rc, _split(raw, ml, n), list(bytes(v)[:n])
 
 
 def ccm_batch(key, nonces, aads, texts, tag_len=16, decrypt=False, tags=None, prefill=0, lens=None):
@@ -611,14 +616,14 @@ def ccm_batch(key, nonces, aads, texts, tag_len=16, decrypt=False, tags=None, pr
         _check(L.uaes_ccm_encrypt_batch(_bits(key), _in(key), nl, tag_len, n, ml, lv, _in(nb), _in(ab), al, _in(mb), o, t),
                "uaes_ccm_encrypt_batch")
         raw, tr = bytes(o), bytes(t)
-        return [raw[i * ml:(i + 1) * ml] for i in range(n)], [tr[tag_len * i:tag_len * (i + 1)] for i in range(n)]
+        return _split(raw, ml, n), _split(tr, tag_len, n)
     if any(len(x) != tag_len for x in tags):
         raise ValueError("tags of tag_len bytes")
     v = _out(n)
     rc = _check(L.uaes_ccm_decrypt_batch(_bits(key), _in(key), nl, tag_len, n, ml, lv, _in(nb), _in(ab), al, _in(mb),
                                          _in(b"".join(tags)), o, v), "uaes_ccm_decrypt_batch")
     raw = bytes(o)
-    return rc, [raw[i * ml:(i + 1) * ml] for i in range(n)], list(bytes(v)[:n])
+    return rc, _split(raw, ml, n), list(bytes(v)[:n])
 
 
 def siv_batch(keys, aads, texts, decrypt=False, ivs=None, prefill=0):
@@ -639,12 +644,12 @@ def siv_batch(keys, aads, texts, decrypt=False, ivs=None, prefill=0):
         _check(L.uaes_siv_encrypt_batch(_bits(keys, 2), _in(keys), n, ml, _in(ab), al, _in(mb), t, o),
                "uaes_siv_encrypt_batch")
         raw, tr = bytes(o), bytes(t)
-        return [tr[16 * i:16 * i + 16] for i in range(n)], [raw[i * ml:(i + 1) * ml] for i in range(n)]
+        return _split(tr, 16, n), _split(raw, ml, n)
     v = _out(n)
     rc = _check(L.uaes_siv_decrypt_batch(_bits(keys, 2), _in(keys), n, ml, _in(ab), al, _in(b"".join(ivs)), _in(mb), o, v),
                 "uaes_siv_decrypt_batch")
     raw = bytes(o)
-    return rc, [raw[i * ml:(i + 1) * ml] for i in range(n)], list(bytes(v)[:n])
+    return rc, _split(raw, ml, n), list(bytes(v)[:n])
 
 
 def eax_siv_plan(siv, length, nmsg=1, decrypt=False):
@@ -701,11 +706,11 @@ def kw_batch(kek, records, unwrap=False, prefill=0):
     if not unwrap:
         rc = _check(L.uaes_kw_wrap_batch(_bits(kek), _in(kek), n, rl, _in(rb), o), "uaes_kw_wrap_batch")
         raw = bytes(o)
-        return rc, [raw[i * ol:(i + 1) * ol] for i in range(n)]
+        return rc, _split(raw, ol, n)
     v = _out(n)
     rc = _check(L.uaes_kw_unwrap_batch(_bits(kek), _in(kek), n, rl, _in(rb), o, v), "uaes_kw_unwrap_batch")
     raw = bytes(o)
-    return rc, [raw[i * ol:(i + 1) * ol] for i in range(n)], list(bytes(v)[:n])
+    return rc, _split(raw, ol, n), list(bytes(v)[:n])
 
 
 def kw_plan(length, nkeys=0, unwrap=False):
@@ -772,7 +777,7 @@ def ff1_batch(key, tweaks, records, alphabet=b"0123456789", radix=None, decrypt=
     if rc < 0 and rc != -2:
         _check(rc, "uaes_ff1_batch")
     raw = bytes(o)
-    return rc, [raw[k * rl:(k + 1) * rl] for k in range(n)], list(bytes(v)[:n])
+    return rc, _split(raw, rl, n), list(bytes(v)[:n])
 
 
 def ff1_plan(length, nrec=0, radix=10, decrypt=False):

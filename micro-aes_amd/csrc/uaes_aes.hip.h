@@ -36,6 +36,7 @@ typedef uint32_t u32;
 typedef uint64_t u64;
 
 #define UAES_WG        1024u              /* threads per workgroup (16 waves)  */
+static_assert(UAES_WG == UAESK_ROW_WG, "uaesk_row_shape's 16-wave workgroup is the kernels' launch bound");
 #define UAES_LDS_ENC   (128u * 1024u)
 #define UAES_LDS_DEC   (128u * 1024u)
 
@@ -838,6 +839,24 @@ __device__ __forceinline__ void row_walk(const unsigned char *p, u64 nblk, u32 c
 #pragma unroll
         for (u32 j = 0; j < ROW_CH; ++j) cur[j] = nxt[j];
     }
+}
+
+/* ---- a record's verdict in the row batches (four records per wave: row4_lane) ----
+ * does any of this row's sixteen lanes say x */
+__device__ __forceinline__ bool row_any(bool x)
+{
+    return ((__ballot(x) >> (threadIdx.x & 48u)) & 0xffffull) != 0;
+}
+
+/* record m's first lane (`first`) writes verdicts[m] = 1 for a good record, 0 for a bad one, and for a bad one
+ * bad[0] |= 1: a vector atomic, and what the host turns into the call's return code.  OPTIONAL: verdicts may be NULL
+ * (a kernel whose callers always pass the array does not pay for the test) */
+template <bool OPTIONAL = false>
+__device__ __forceinline__ void row_verdict(bool first, unsigned char *verdicts, u64 m, bool ok, int *bad)
+{
+    if (!first) return;
+    if (!OPTIONAL || verdicts) verdicts[m] = ok ? 1 : 0;
+    if (!ok) atomicOr(bad, 1);
 }
 
 /* ---- the INVERSE cipher, sixteen lanes per block (key unwrap, uaes_kw.hip: the one chain of AES^-1 in the tree) ----

@@ -469,20 +469,19 @@ static void plan_fb_dec(u64 n, uaes_plan *p)
 }
 
 /* sixteen lanes per message up to UAES_BATCH_ROW_MAX messages, a lane per message beyond (where the two arrangements
- * cross: profiles/HISTORY.md, profiles/r05_batch_rate_after.log).  Row kernel: 64 messages per 16-wave workgroup; few messages: 4-wave workgroups,
- * so that they spread over the CUs.  Either grid is capped at the CU count and the kernels stride beyond it. */
+ * cross: profiles/HISTORY.md, profiles/r05_batch_rate_after.log).  The row kernel's shape is every row batch's
+ * (uaesk_row_shape); the lane kernel's grid is capped at the CU count and the kernel strides beyond it. */
 static void plan_batch(u64 nmsg, uaes_plan *p)
 {
-    const unsigned cus = uaesk_cus_or_256();
     p->launches = 1;
     if (nmsg <= (u64)UAES_BATCH_ROW_MAX) {
-        const unsigned wg = (nmsg + 63) / 64 * 2 <= cus ? 256u : UAES_WG;
-        const u64 want = (nmsg + wg / 16 - 1) / (wg / 16);
+        const RowShape s = uaesk_row_shape(nmsg);
         p->arrangement = UAES_BATCH_ROW;
-        p->grid = (unsigned)(want < cus ? (want ? want : 1) : cus);
-        p->steps = wg;
+        p->grid = s.grid;
+        p->steps = s.wg;
         return;
     }
+    const unsigned cus = uaesk_cus_or_256();
     const u64 want = (nmsg + UAES_WG - 1) / UAES_WG;
     p->arrangement = UAES_BATCH_LANE;
     p->grid = (unsigned)(want < cus ? want : cus);
@@ -589,8 +588,7 @@ static int launch_batch(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *
     uaes_plan p;
     plan_batch(nmsg, &p);
     if (p.arrangement == UAES_BATCH_ROW) {
-        const bool a4 = ((((uintptr_t)in) | ((uintptr_t)out)) & 3u) == 0 && msg_bytes % 4 == 0;
-        return with_bool(a4, [&](auto A4) {
+        return with_bool(uaesk_rows_a4(in, out, msg_bytes), [&](auto A4) {
             return uaesk_launch(k_chain_batch_row<NR, MAC, decltype(A4)::value>, p.grid, p.steps, UAES_LDS_ROW4, st, *k, *tb, ivs,
                                 nmsg, msg_bytes, in, out); });
     }

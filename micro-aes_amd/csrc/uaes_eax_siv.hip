@@ -525,10 +525,7 @@ __global__ __launch_bounds__(UAES_WG) void k_eax_batch(uaesk_rk rk, uaesk_tables
             u32 d[4];
             row_gather(n ^ h ^ c ^ row_load(tg, 16, L.c), d);
             const bool ok = (d[0] | d[1] | d[2] | d[3]) == 0;
-            if ((threadIdx.x & 15u) == 0) {
-                verdicts[m] = ok ? 1 : 0;
-                if (!ok) atomicOr(bad, 1);
-            }
+            row_verdict((threadIdx.x & 15u) == 0, verdicts, m, ok, bad);
             if (ok) ctr_row<NR, A4>(ctr, src, dst, msg_bytes, L);
         }
     }
@@ -569,10 +566,7 @@ __global__ __launch_bounds__(UAES_WG) void k_s2v_batch(uaesk_rk rk, uaesk_rk rk2
             u32 d[4];
             row_gather(v ^ iv, d);
             const bool ok = (d[0] | d[1] | d[2] | d[3]) == 0;
-            if ((threadIdx.x & 15u) == 0) {
-                verdicts[m] = ok ? 1 : 0;
-                if (!ok) atomicOr(bad, 1);
-            }
+            row_verdict((threadIdx.x & 15u) == 0, verdicts, m, ok, bad);
             if (!ok && wipe)
                 for (u64 i = 0; i < msg_bytes; i += 16) row_put(dst + i, 0u, msg_bytes - i < 16 ? (u32)(msg_bytes - i) : 16u, L.c);
         }
@@ -663,25 +657,14 @@ extern "C" int uaesk_s2v_macs(void *stream, const uaesk_tables *tb, int nr, cons
     return 0;
 }
 
-/* as launch_batch (uaes_chain.hip): 64 records per 16-wave workgroup, 4-wave workgroups for few records */
-static void batch_shape(u64 nmsg, unsigned *grid, unsigned *wg)
-{
-    const unsigned cus = uaesk_cus_or_256();
-    *wg = (nmsg + 63) / 64 * 2 <= cus ? 256u : UAES_WG;
-    const u64 want = (nmsg + *wg / 16 - 1) / (*wg / 16);
-    *grid = (unsigned)(want < cus ? want : cus);
-}
-
 template <int NR>
 static int launch_eax_batch(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *ek, int decrypt, const void *nonces,
                             size_t nonce_len, const void *aad, size_t aad_bytes, size_t nmsg, size_t msg_bytes,
                             const void *in, void *out, void *tags, void *verdicts, int *bad)
 {
-    const bool a4 = ((((uintptr_t)in) | ((uintptr_t)out)) & 3u) == 0 && msg_bytes % 4 == 0;
-    unsigned grid, wg;
-    batch_shape(nmsg, &grid, &wg);
-    return with_bool(decrypt, [&](auto DEC) { return with_bool(a4, [&](auto A4) {
-        return uaesk_launch(k_eax_batch<NR, decltype(DEC)::value, decltype(A4)::value>, grid, wg, E4_LDS, st, *ek, *tb, nonces,
+    const RowShape s = uaesk_row_shape(nmsg);
+    return with_bool(decrypt, [&](auto DEC) { return with_bool(uaesk_rows_a4(in, out, msg_bytes), [&](auto A4) {
+        return uaesk_launch(k_eax_batch<NR, decltype(DEC)::value, decltype(A4)::value>, s.grid, s.wg, E4_LDS, st, *ek, *tb, nonces,
                             nonce_len, aad, aad_bytes, nmsg, msg_bytes, in, out, tags, verdicts, bad); }); });
 }
 
@@ -700,11 +683,9 @@ static int launch_s2v_batch(hipStream_t st, const uaesk_tables *tb, const uaesk_
                             int wipe, const void *aad, size_t aad_bytes, size_t nmsg, size_t msg_bytes,
                             const void *in, void *out, void *ivs, void *verdicts, int *bad)
 {
-    const bool a4 = ((((uintptr_t)in) | ((uintptr_t)out)) & 3u) == 0 && msg_bytes % 4 == 0;
-    unsigned grid, wg;
-    batch_shape(nmsg, &grid, &wg);
-    return with_bool(decrypt, [&](auto DEC) { return with_bool(a4, [&](auto A4) {
-        return uaesk_launch(k_s2v_batch<NR, decltype(DEC)::value, decltype(A4)::value>, grid, wg, E4_LDS, st, *ek, *ek2, *tb, wipe,
+    const RowShape s = uaesk_row_shape(nmsg);
+    return with_bool(decrypt, [&](auto DEC) { return with_bool(uaesk_rows_a4(in, out, msg_bytes), [&](auto A4) {
+        return uaesk_launch(k_s2v_batch<NR, decltype(DEC)::value, decltype(A4)::value>, s.grid, s.wg, E4_LDS, st, *ek, *ek2, *tb, wipe,
                             aad, aad_bytes, nmsg, msg_bytes, in, out, ivs, verdicts, bad); }); });
 }
 
@@ -724,11 +705,9 @@ extern "C" int uaesk_plan_eax_siv(int siv, int dir, size_t len, size_t nmsg, uae
     memset(p, 0, sizeof *p);
     if ((siv != 0 && siv != 1) || (dir != 0 && dir != 1)) return (int)hipErrorInvalidValue;
     if (nmsg > 1) {
-        unsigned grid, wg;
-        batch_shape(nmsg, &grid, &wg);
         p->arrangement = siv ? UAES_S2V_BATCH : UAES_EAX_BATCH;
         p->launches = 1;
-        p->grid = grid;
+        p->grid = uaesk_row_shape(nmsg).grid;
         return 0;
     }
     p->grid = 1;

@@ -1340,18 +1340,54 @@ int stage_text(lane *L, int k, const void *user, size_t n, int prefill, void **d
     return 0;
 }
 
-int side_out(lane *L, size_t *off, void *user, size_t n, void **d)
+/* ---- a row batch's arrays (uaes_engine_modes.c: the EAX / SIV, CCM, key-wrap and FF1 batches) ----
+ * The caller lists its side arrays (row_array, uaes_engine.h) and its two texts (row_text) and calls row_stage,
+ * row_texts, its launcher and row_finish, in this order.  A device array goes to the kernel as it is; host arrays
+ * share the lane's scratch, SIDE(bytes) each.  The offsets and the size asked of lane_scratch come from the one list,
+ * so no array can lie past the end.  row_stage waits for the caller's device work, once for the whole list, if any
+ * listed array, read or written, is device memory (row_texts waits again for each text that is: stage_text);
+ * status != 0: the kernel reports through L->d_status[0], cleared here. */
+int row_stage(lane *L, row_array *a, int n, int status)
 {
-    if (is_device_ptr(user)) { *d = user; return 0; }
-    *d = (char *)L->scratch + *off;
-    *off += SIDE(n);
+    size_t need = 0, off = 0;
+    int i, rc, dev = 0;
+    for (i = 0; i < n; ++i) {
+        a[i].d = NULL;
+        if (!a[i].bytes) continue;
+        if (is_device_ptr(a[i].user)) { a[i].d = (void *)a[i].user; dev = 1; }
+        else need += SIDE(a[i].bytes);
+    }
+    if (need && (rc = lane_scratch(L, need, SCRATCH_OTHER)) != 0) return rc;
+    for (i = 0; i < n; ++i) {
+        if (!a[i].bytes || a[i].d) continue;
+        a[i].d = (char *)L->scratch + off;
+        off += SIDE(a[i].bytes);
+        if (!a[i].out) HIPCHK(hipMemcpyAsync(a[i].d, a[i].user, a[i].bytes, hipMemcpyHostToDevice, (hipStream_t)L->stream));
+    }
+    if (dev && (rc = wait_for_callers_device_work()) != 0) return rc;
+    if (status) HIPCHK(hipMemsetAsync(L->d_status, 0, sizeof(int), (hipStream_t)L->stream));
     return 0;
 }
 
-int copy_out(lane *L, void *user, const void *d, size_t n)
+int row_texts(lane *L, row_text *t)
 {
-    if (!n || d == user) return 0;
-    HIPCHK(hipMemcpyAsync(user, d, n, hipMemcpyDeviceToHost, (hipStream_t)L->stream));
+    const int rc = stage_text(L, 0, t->in, t->in_bytes, 1, &t->d_in);
+    return rc ? rc : stage_text(L, 1, t->out, t->out_bytes, t->prefill, &t->d_out);
+}
+
+/* everything the kernel wrote into staging goes back to the caller, with the status word if the call has one
+ * (else *bad = 0): one synchronise, one round trip */
+int row_finish(lane *L, const row_text *t, const row_array *a, int n, int status, int *bad)
+{
+    hipStream_t st = (hipStream_t)L->stream;
+    int i;
+    *bad = 0;
+    if (t->out_bytes && t->d_out != t->out) HIPCHK(hipMemcpyAsync(t->out, t->d_out, t->out_bytes, hipMemcpyDeviceToHost, st));
+    for (i = 0; i < n; ++i)
+        if (a[i].out && a[i].bytes && a[i].d != a[i].user)
+            HIPCHK(hipMemcpyAsync((void *)a[i].user, a[i].d, a[i].bytes, hipMemcpyDeviceToHost, st));
+    if (status) HIPCHK(hipMemcpyAsync(bad, L->d_status, sizeof *bad, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     return 0;
 }
 

@@ -158,6 +158,23 @@ typedef int (*pipe_launch_fn)(void *arg, int worker, void *stream, const void *d
 
 #define SIDE(n) (((n) + 15) & ~(size_t)15)
 
+/* a row batch's side arrays and texts, as its host function lists them (row_stage, uaes_engine.c) */
+typedef struct {
+    const void *user;               /* the caller's array, host or device memory (const for the inputs' sake:
+                                     * row_stage and row_finish cast it back for an array with out = 1)       */
+    size_t      bytes;              /* 0: this call has no such array, and d stays NULL                        */
+    int         out;                /* 0: the kernel reads it; 1: it writes it and row_finish brings it back  */
+    void       *d;                  /* row_stage's answer: where the kernel finds it                           */
+} row_array;
+typedef struct {
+    const void *in;
+    void       *out;
+    size_t      in_bytes, out_bytes;
+    int         prefill;            /* the output's staging starts as a copy of the caller's buffer: the kernel
+                                     * leaves part of it unwritten                                             */
+    void       *d_in, *d_out;       /* row_texts' answer */
+} row_text;
+
 /* ---- uaes_engine.c ---- */
 int fail(int code, const char *fmt, ...);
 int wipe_on_auth_failure(void);
@@ -206,8 +223,9 @@ int side_in(lane *L, size_t *off, const void *src, size_t n, const void **d);
 int iv_read(uint8_t out[16], const uint8_t *iv);
 int iv_write(uint8_t *iv, const uint8_t v[16]);
 int stage_text(lane *L, int k, const void *user, size_t n, int prefill, void **d);
-int side_out(lane *L, size_t *off, void *user, size_t n, void **d);
-int copy_out(lane *L, void *user, const void *d, size_t n);
+int row_stage(lane *L, row_array *a, int n, int status);
+int row_texts(lane *L, row_text *t);
+int row_finish(lane *L, const row_text *t, const row_array *a, int n, int status, int *bad);
 int tag_store(void *dst, const uint8_t tag[16]);
 int tag_load(uint8_t tag[16], const void *src);
 

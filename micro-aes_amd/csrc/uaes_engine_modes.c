@@ -526,11 +526,6 @@ int uaes_ccm_decrypt(int keybits, const uint8_t *key, const uint8_t *nonce,
  * independent chains in one launch, reads the counter block (and the verdict) back in one fetch and hands it to the
  * positioned CTR kernels.  Side arrays (nonce, AAD) in host memory travel through the lane's scratch.             */
 
-#define HIPCHK_GOTO(call)                                                                            \
-    do {                                                                                              \
-        const hipError_t e_ = (call);                                                                 \
-        if (e_ != hipSuccess) { rc = fail(UAES_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); goto out; } \
-    } while (0)
 #define ES_KCHK(what, call)                                                                           \
     do {                                                                                              \
         const int k_ = (call);                                                                        \
@@ -713,10 +708,7 @@ static int aead_batch(int siv, int decrypt, int keybits, const uint8_t *key, siz
     context *c;
     lane *L;
     keysched k1, k2;
-    const void *d_nonces = NULL, *d_aad = NULL, *d_tags_in = NULL;
-    void *d_in = NULL, *d_out = NULL, *d_tags = NULL, *d_verdicts = NULL;
-    size_t off = 0;
-    int rc, bad = 0;
+    int rc, bad;
     if ((msg_bytes && nmsg > (size_t)-1 / msg_bytes) || (nonce_len && nmsg > (size_t)-1 / nonce_len) ||
         (aad_bytes && nmsg > (size_t)-1 / aad_bytes) || nmsg > (size_t)-1 / 16)
         return fail(UAES_E_ARG, "batch size overflows");
@@ -730,29 +722,21 @@ static int aead_batch(int siv, int decrypt, int keybits, const uint8_t *key, siz
             return fail(UAES_E_ARG, "NULL pointer");
         }
         if ((rc = enter(&c, &L)) != 0) { burn(&k1, sizeof k1); burn(&k2, sizeof k2); return rc; }
-        if ((rc = lane_scratch(L, SIDE(nmsg * nonce_len) + SIDE(nmsg * aad_bytes) + SIDE(nmsg * 16) + SIDE(nmsg),
-                               SCRATCH_OTHER)) != 0) goto out;
-        if (!siv && (rc = side_in(L, &off, nonces, nmsg * nonce_len, &d_nonces)) != 0) goto out;
-        if ((rc = side_in(L, &off, aData, nmsg * aad_bytes, &d_aad)) != 0) goto out;
-        if (decrypt) {
-            if ((rc = side_in(L, &off, tags, nmsg * 16, &d_tags_in)) != 0) goto out;
-            d_tags = (void *)d_tags_in;
-            if ((rc = side_out(L, &off, verdicts, nmsg, &d_verdicts)) != 0) goto out;
-        } else if ((rc = side_out(L, &off, tags, nmsg * 16, &d_tags)) != 0) goto out;
-        if ((rc = stage_text(L, 0, in, total, 1, &d_in)) != 0) goto out;
-        if ((rc = stage_text(L, 1, outp, total, decrypt && !siv, &d_out)) != 0) goto out;
-        if (decrypt) HIPCHK_GOTO(hipMemsetAsync(L->d_status, 0, sizeof(int), (hipStream_t)L->stream));
+        enum { NONCES, AAD, TAGS, VERDICTS, NSIDE };
+        row_array a[NSIDE] = { { nonces, siv ? 0 : nmsg * nonce_len, 0, NULL }, { aData, nmsg * aad_bytes, 0, NULL },
+                               { tags, nmsg * 16, !decrypt, NULL }, { verdicts, decrypt ? nmsg : 0, 1, NULL } };
+        row_text t = { in, outp, total, total, decrypt && !siv, NULL, NULL };
+        if ((rc = row_stage(L, a, NSIDE, decrypt)) != 0) goto out;
+        if ((rc = row_texts(L, &t)) != 0) goto out;
         if (siv)
             ES_KCHK("siv batch", uaesk_s2v_batch(L->stream, &c->tb, k1.nr, &k1.ek, &k2.ek, decrypt, wipe_on_auth_failure(),
-                                                 d_aad, aad_bytes, nmsg, msg_bytes, d_in, d_out, d_tags, d_verdicts,
-                                                 L->d_status));
+                                                 a[AAD].d, aad_bytes, nmsg, msg_bytes, t.d_in, t.d_out, a[TAGS].d,
+                                                 a[VERDICTS].d, L->d_status));
         else
-            ES_KCHK("eax batch", uaesk_eax_batch(L->stream, &c->tb, k1.nr, &k1.ek, decrypt, d_nonces, nonce_len, d_aad,
-                                                 aad_bytes, nmsg, msg_bytes, d_in, d_out, d_tags, d_verdicts, L->d_status));
-        if ((rc = copy_out(L, outp, d_out, total)) != 0) goto out;
-        if ((rc = decrypt ? copy_out(L, verdicts, d_verdicts, nmsg) : copy_out(L, tags, d_tags, nmsg * 16)) != 0) goto out;
-        if (decrypt) HIPCHK_GOTO(hipMemcpyAsync(&bad, L->d_status, sizeof bad, hipMemcpyDeviceToHost, (hipStream_t)L->stream));
-        HIPCHK_GOTO(hipStreamSynchronize((hipStream_t)L->stream));
+            ES_KCHK("eax batch", uaesk_eax_batch(L->stream, &c->tb, k1.nr, &k1.ek, decrypt, a[NONCES].d, nonce_len, a[AAD].d,
+                                                 aad_bytes, nmsg, msg_bytes, t.d_in, t.d_out, a[TAGS].d, a[VERDICTS].d,
+                                                 L->d_status));
+        if ((rc = row_finish(L, &t, a, NSIDE, decrypt, &bad)) != 0) goto out;
         rc = bad ? UAES_E_AUTHENTICATION : 0;
     }
 out:
@@ -801,11 +785,8 @@ static int ccm_batch(int decrypt, int keybits, const uint8_t *key, size_t nonceL
     context *c;
     lane *L;
     keysched ks;
-    const void *d_nonces = NULL, *d_aad = NULL, *d_tags_in = NULL, *d_lens = NULL;
-    void *d_in = NULL, *d_out = NULL, *d_tags = NULL, *d_verdicts = NULL;
     const size_t lim = (size_t)-1 / 8;               /* five side arrays and their padding still add up */
-    size_t off = 0;
-    int rc, bad = 0;
+    int rc, bad;
     if ((rc = ccm_lens_ok(nonceLen, tagLen)) != 0) return rc;
     if (msg_bytes > UAES_CCM_BATCH_MAX)
         return fail(UAES_E_ARG, "a CCM batch record holds at most %zu bytes (got %zu)", (size_t)UAES_CCM_BATCH_MAX, msg_bytes);
@@ -821,26 +802,17 @@ static int ccm_batch(int decrypt, int keybits, const uint8_t *key, size_t nonceL
             return fail(UAES_E_ARG, "NULL pointer");
         }
         if ((rc = enter(&c, &L)) != 0) { burn(&ks, sizeof ks); return rc; }
-        if ((rc = lane_scratch(L, SIDE(nmsg * nonceLen) + SIDE(nmsg * aad_bytes) + SIDE(nmsg * tagLen) + SIDE(nmsg) +
-                               SIDE(nmsg * sizeof *lens), SCRATCH_OTHER)) != 0) goto out;
-        if ((rc = side_in(L, &off, nonces, nmsg * nonceLen, &d_nonces)) != 0) goto out;
-        if ((rc = side_in(L, &off, aData, nmsg * aad_bytes, &d_aad)) != 0) goto out;
-        if (lens && (rc = side_in(L, &off, lens, nmsg * sizeof *lens, &d_lens)) != 0) goto out;
-        if (decrypt) {
-            if ((rc = side_in(L, &off, tags, nmsg * tagLen, &d_tags_in)) != 0) goto out;
-            d_tags = (void *)d_tags_in;
-            if ((rc = side_out(L, &off, verdicts, nmsg, &d_verdicts)) != 0) goto out;
-        } else if ((rc = side_out(L, &off, tags, nmsg * tagLen, &d_tags)) != 0) goto out;
-        if ((rc = stage_text(L, 0, in, total, 1, &d_in)) != 0) goto out;
-        if ((rc = stage_text(L, 1, outp, total, lens != NULL, &d_out)) != 0) goto out;
-        if (decrypt) HIPCHK_GOTO(hipMemsetAsync(L->d_status, 0, sizeof(int), (hipStream_t)L->stream));
-        ES_KCHK("ccm batch", uaesk_ccm_batch(L->stream, &c->tb, ks.nr, &ks.ek, decrypt, wipe_on_auth_failure(), d_nonces,
-                                             nonceLen, tagLen, d_aad, aad_bytes, nmsg, msg_bytes, d_lens, d_in, d_out,
-                                             d_tags, d_verdicts, L->d_status));
-        if ((rc = copy_out(L, outp, d_out, total)) != 0) goto out;
-        if ((rc = decrypt ? copy_out(L, verdicts, d_verdicts, nmsg) : copy_out(L, tags, d_tags, nmsg * tagLen)) != 0) goto out;
-        if (decrypt) HIPCHK_GOTO(hipMemcpyAsync(&bad, L->d_status, sizeof bad, hipMemcpyDeviceToHost, (hipStream_t)L->stream));
-        HIPCHK_GOTO(hipStreamSynchronize((hipStream_t)L->stream));
+        enum { NONCES, AAD, LENS, TAGS, VERDICTS, NSIDE };
+        row_array a[NSIDE] = { { nonces, nmsg * nonceLen, 0, NULL }, { aData, nmsg * aad_bytes, 0, NULL },
+                               { lens, lens ? nmsg * sizeof *lens : 0, 0, NULL }, { tags, nmsg * tagLen, !decrypt, NULL },
+                               { verdicts, decrypt ? nmsg : 0, 1, NULL } };
+        row_text t = { in, outp, total, total, lens != NULL, NULL, NULL };
+        if ((rc = row_stage(L, a, NSIDE, decrypt)) != 0) goto out;
+        if ((rc = row_texts(L, &t)) != 0) goto out;
+        ES_KCHK("ccm batch", uaesk_ccm_batch(L->stream, &c->tb, ks.nr, &ks.ek, decrypt, wipe_on_auth_failure(), a[NONCES].d,
+                                             nonceLen, tagLen, a[AAD].d, aad_bytes, nmsg, msg_bytes, a[LENS].d, t.d_in, t.d_out,
+                                             a[TAGS].d, a[VERDICTS].d, L->d_status));
+        if ((rc = row_finish(L, &t, a, NSIDE, decrypt, &bad)) != 0) goto out;
         rc = bad ? UAES_E_AUTHENTICATION : 0;
     }
 out:
@@ -984,12 +956,14 @@ static int batch_common(int keybits, const uint8_t *key, int mac, const uint8_t 
     int rc;
     const size_t total = nmsg * msg_bytes, out_len = mac ? nmsg * 16 : total;
     if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
-    if (!mac && (msg_bytes < 16 || msg_bytes % 16))
+    if (!mac && (msg_bytes < 16 || msg_bytes % 16)) {
+        burn(&ks, sizeof ks);
         return fail(UAES_E_ARG, "batched CBC: every message must be a whole number of blocks (got %zu bytes)", msg_bytes);
-    if (msg_bytes && nmsg > (size_t)-1 / msg_bytes) return fail(UAES_E_ARG, "batch size overflows");
-    if (nmsg == 0) return 0;
-    if ((total && !in) || !out || (!mac && !ivs)) return fail(UAES_E_ARG, "NULL pointer");
-    if ((rc = enter(&c, &L)) != 0) return rc;
+    }
+    if (msg_bytes && nmsg > (size_t)-1 / msg_bytes) { burn(&ks, sizeof ks); return fail(UAES_E_ARG, "batch size overflows"); }
+    if (nmsg == 0) { burn(&ks, sizeof ks); return 0; }
+    if ((total && !in) || !out || (!mac && !ivs)) { burn(&ks, sizeof ks); return fail(UAES_E_ARG, "NULL pointer"); }
+    if ((rc = enter(&c, &L)) != 0) { burn(&ks, sizeof ks); return rc; }
     do {
         if (!mac && (rc = stage_aad(L, ivs, nmsg * 16, &d_ivs)) != 0) break;     /* host IVs -> device */
         if (!mac && (((uintptr_t)d_ivs) & 15u)) { rc = fail(UAES_E_ARG, "device IV array must be 16-byte aligned"); break; }
@@ -1002,6 +976,7 @@ static int batch_common(int keybits, const uint8_t *key, int mac, const uint8_t 
         if (k) { rc = fail(UAES_E_HIP, "batch launch: %s", hipGetErrorString((hipError_t)k)); break; }
         rc = finish_io(&io, out_len);
     } while (0);
+    burn(&ks, sizeof ks);
     DONE(L, rc);
 }
 
@@ -1111,9 +1086,7 @@ static int kw_batch(int unwrap, int keybits, const uint8_t *kek, size_t nkeys, s
     context *c;
     lane *L;
     keysched ks;
-    void *d_in = NULL, *d_out = NULL, *d_verdicts = NULL;
-    size_t off = 0;
-    int rc, bad = 0;
+    int rc, bad;
     const size_t in_rec = unwrap ? secret_bytes + 8 : secret_bytes, out_rec = unwrap ? secret_bytes : secret_bytes + 8;
     if ((rc = expand_key(&ks, kek, keybits)) != 0) return rc;
     if (secret_bytes > UAES_KW_BATCH_MAX) {
@@ -1125,22 +1098,13 @@ static int kw_batch(int unwrap, int keybits, const uint8_t *kek, size_t nkeys, s
     if (nkeys == 0) { burn(&ks, sizeof ks); return 0; }
     if (!in || !outp || (unwrap && !verdicts)) { burn(&ks, sizeof ks); return fail(UAES_E_ARG, "NULL pointer"); }
     if ((rc = enter(&c, &L)) != 0) { burn(&ks, sizeof ks); return rc; }
-    if (unwrap) {
-        if ((rc = lane_scratch(L, SIDE(nkeys), SCRATCH_OTHER)) != 0) goto out;
-        if ((rc = side_out(L, &off, verdicts, nkeys, &d_verdicts)) != 0) goto out;
-        if (is_device_ptr(verdicts) && (rc = wait_for_callers_device_work()) != 0) goto out;
-    }
-    if ((rc = stage_text(L, 0, in, nkeys * in_rec, 1, &d_in)) != 0) goto out;
-    if ((rc = stage_text(L, 1, outp, nkeys * out_rec, 0, &d_out)) != 0) goto out;
-    if (unwrap) HIPCHK_GOTO(hipMemsetAsync(L->d_status, 0, sizeof(int), (hipStream_t)L->stream));
+    row_array a[1] = { { verdicts, unwrap ? nkeys : 0, 1, NULL } };
+    row_text t = { in, outp, nkeys * in_rec, nkeys * out_rec, 0, NULL, NULL };
+    if ((rc = row_stage(L, a, 1, unwrap)) != 0) goto out;
+    if ((rc = row_texts(L, &t)) != 0) goto out;
     ES_KCHK("key wrap batch", uaesk_kw_batch(L->stream, &c->tb, ks.nr, &ks.ek, &ks.dk, unwrap, wipe_on_auth_failure(), nkeys,
-                                             secret_bytes, d_in, d_out, d_verdicts, L->d_status));
-    if ((rc = copy_out(L, outp, d_out, nkeys * out_rec)) != 0) goto out;
-    if (unwrap) {
-        if ((rc = copy_out(L, verdicts, d_verdicts, nkeys)) != 0) goto out;
-        HIPCHK_GOTO(hipMemcpyAsync(&bad, L->d_status, sizeof bad, hipMemcpyDeviceToHost, (hipStream_t)L->stream));
-    }
-    HIPCHK_GOTO(hipStreamSynchronize((hipStream_t)L->stream));
+                                             secret_bytes, t.d_in, t.d_out, a[0].d, L->d_status));
+    if ((rc = row_finish(L, &t, a, 1, unwrap, &bad)) != 0) goto out;
     rc = bad ? UAES_E_AUTHENTICATION : 0;
 out:
     burn(&ks, sizeof ks);
@@ -1205,27 +1169,18 @@ static int ff1_gpu(const keysched *ks, int decrypt, const uaesk_ff1 *q, const ui
 {
     context *c;
     lane *L;
-    void *d_in = NULL, *d_out = NULL, *d_verdicts = NULL;
     const void *d_tweaks = NULL;
     const size_t n = nrec ? nrec : 1, total = n * q->len;
-    size_t off = 0;
-    int rc, bad = 0;
+    int rc, bad;
     if ((rc = enter(&c, &L)) != 0) return rc;
-    if (verdicts) {
-        if ((rc = lane_scratch(L, SIDE(n), SCRATCH_OTHER)) != 0) goto out;
-        if ((rc = side_out(L, &off, verdicts, n, &d_verdicts)) != 0) goto out;
-        if (is_device_ptr(verdicts) && (rc = wait_for_callers_device_work()) != 0) goto out;
-    }
+    row_array a[1] = { { verdicts, verdicts ? n : 0, 1, NULL } };
+    row_text t = { in, outp, total, total, 1, NULL, NULL };
+    if ((rc = row_stage(L, a, 1, 1)) != 0) goto out;
     if ((rc = stage_aad(L, tweaks, tweak_bytes, &d_tweaks)) != 0) goto out;
-    if ((rc = stage_text(L, 0, in, total, 1, &d_in)) != 0) goto out;
-    if ((rc = stage_text(L, 1, outp, total, 1, &d_out)) != 0) goto out;
-    HIPCHK_GOTO(hipMemsetAsync(L->d_status, 0, sizeof(int), (hipStream_t)L->stream));
-    ES_KCHK("FF1", uaesk_ff1_run(L->stream, &c->tb, ks->nr, &ks->ek, decrypt, q, d_tweaks, nrec, d_in, d_out, d_verdicts,
+    if ((rc = row_texts(L, &t)) != 0) goto out;
+    ES_KCHK("FF1", uaesk_ff1_run(L->stream, &c->tb, ks->nr, &ks->ek, decrypt, q, d_tweaks, nrec, t.d_in, t.d_out, a[0].d,
                                  L->d_status));
-    if ((rc = copy_out(L, outp, d_out, total)) != 0) goto out;
-    if (verdicts && (rc = copy_out(L, verdicts, d_verdicts, n)) != 0) goto out;
-    HIPCHK_GOTO(hipMemcpyAsync(&bad, L->d_status, sizeof bad, hipMemcpyDeviceToHost, (hipStream_t)L->stream));
-    HIPCHK_GOTO(hipStreamSynchronize((hipStream_t)L->stream));
+    if ((rc = row_finish(L, &t, a, 1, 1, &bad)) != 0) goto out;
     rc = bad ? (decrypt ? UAES_E_DECRYPTION : UAES_E_ENCRYPTION) : 0;
 out:
     DONE(L, rc);

@@ -158,8 +158,7 @@ __global__ __launch_bounds__(W == 16u ? UAES_WG : 64u) void k_ff1(uaesk_rk rk, u
             foreign |= dg >= radix;
             ff1_st8(xat + i, dg);
         }
-        const u64 vote = __ballot(foreign);
-        const bool good = W == 16u ? ((vote >> (threadIdx.x & 48u)) & 0xffffull) == 0 : vote == 0;
+        const bool good = W == 16u ? !row_any(foreign) : __ballot(foreign) == 0;
         FF1_PHASE();
 
         u32 y = row_encrypt<NR>(row_pick(q.p, L.c), L);     /* E(P), then the tweak's full blocks */
@@ -198,10 +197,7 @@ __global__ __launch_bounds__(W == 16u ? UAES_WG : 64u) void k_ff1(uaesk_rk rk, u
             unsigned char *dst = out + rec * len;
             for (u32 i = li; i < len; i += W) dst[i] = (unsigned char)ff1_ld8(AT + 256u + ff1_ld8(xat + i));
         }
-        if (live && li == 0) {
-            if (verdicts) verdicts[rec] = good ? 1 : 0;
-            if (!good) atomicOr(bad, 1);
-        }
+        row_verdict<true>(live && li == 0, verdicts, rec, good, bad);
         FF1_PHASE();
     }
 }
@@ -220,14 +216,10 @@ static int plan_ff1(int dir, unsigned radix, size_t len, size_t nrec, uaes_plan 
         return 0;
     }
     if (len > UAES_FF1_BATCH_MAX) return (int)hipErrorInvalidValue;
-    /* as plan_kw: 64 records per 16-wave workgroup; few records: 4-wave workgroups, so that they spread over the CUs;
-     * the grid is capped at the CU count and the kernel strides */
-    const unsigned cus = uaesk_cus_or_256();
-    const unsigned wg = ((u64)nrec + 63) / 64 * 2 <= cus ? 256u : UAES_WG;
-    const u64 want = ((u64)nrec + wg / 16 - 1) / (wg / 16);
+    const RowShape s = uaesk_row_shape(nrec);
     p->arrangement = UAES_FF1_BATCH;
-    p->grid = (unsigned)(want < cus ? want : cus);
-    p->steps = wg;
+    p->grid = s.grid;
+    p->steps = s.wg;
     return 0;
 }
 

@@ -204,12 +204,8 @@ __global__ __launch_bounds__(UAES_WG) void k_kw_batch(uaesk_rk rk, uaesk_tables 
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         bool zero = false;
         if (DEC) {
-            const u64 b = __ballot(L.c < 2u && a != KW_IV);
-            const bool forged = ((b >> (threadIdx.x & 48u)) & 0xffffull) != 0;      /* this row's sixteen lanes */
-            if (li == 0) {
-                verdicts[m] = forged ? 0 : 1;
-                if (forged) atomicOr(bad, 1);
-            }
+            const bool forged = row_any(L.c < 2u && a != KW_IV);
+            row_verdict(li == 0, verdicts, m, !forged, bad);
             zero = forged && wipe;
         } else if (li < 8u && (li & 3u) == 0) {
             kw_st<A4>(dst + half, a);
@@ -232,14 +228,10 @@ static int plan_kw(int dir, size_t len, size_t nkeys, uaes_plan *p)
         return 0;
     }
     if (len > UAES_KW_BATCH_MAX) return (int)hipErrorInvalidValue;
-    /* as the batches of chains (uaes_chain.hip, plan_batch): 64 records per 16-wave workgroup; few records: 4-wave
-     * workgroups, so that they spread over the CUs; the grid is capped at the CU count and the kernel strides */
-    const unsigned cus = uaesk_cus_or_256();
-    const unsigned wg = ((u64)nkeys + 63) / 64 * 2 <= cus ? 256u : UAES_WG;
-    const u64 want = ((u64)nkeys + wg / 16 - 1) / (wg / 16);
+    const RowShape s = uaesk_row_shape(nkeys);
     p->arrangement = UAES_KW_BATCH;
-    p->grid = (unsigned)(want < cus ? want : cus);
-    p->steps = wg;
+    p->grid = s.grid;
+    p->steps = s.wg;
     return 0;
 }
 
@@ -262,10 +254,9 @@ static int launch_kw(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *k, 
     uaes_plan p;
     const int e = plan_kw(dec, len, 0, &p);
     if (e) return e;
-    const bool a4 = ((((uintptr_t)in) | ((uintptr_t)out)) & 3u) == 0;
     return with_bool(dec, [&](auto DEC) {
         return with_bool(p.arrangement == UAES_KW_GLOBAL, [&](auto G) {
-            return with_bool(a4, [&](auto A4) {
+            return with_bool(uaesk_rows_a4(in, out, len), [&](auto A4) {
                 return uaesk_launch(k_kw<NR, decltype(DEC)::value, decltype(G)::value, decltype(A4)::value>, p.grid, p.steps,
                                     KW_LDS, st, *k, *tb, in, out, len / 8, status); }); }); });
 }
@@ -277,9 +268,8 @@ static int launch_kw_batch(hipStream_t st, const uaesk_tables *tb, const uaesk_r
     uaes_plan p;
     const int e = plan_kw(dec, len, nkeys, &p);
     if (e) return e;
-    const bool a4 = ((((uintptr_t)in) | ((uintptr_t)out)) & 3u) == 0;
     return with_bool(dec, [&](auto DEC) {
-        return with_bool(a4, [&](auto A4) {
+        return with_bool(uaesk_rows_a4(in, out, len), [&](auto A4) {
             return uaesk_launch(k_kw_batch<NR, decltype(DEC)::value, decltype(A4)::value>, p.grid, p.steps, KW_BATCH_LDS, st,
                                 *k, *tb, nkeys, len / 8, in, out, verdicts, bad, wipe); }); });
 }

@@ -39,6 +39,28 @@ static inline unsigned uaesk_cus_or_256()
     return cus ? (unsigned)cus : 256u;
 }
 
+/* The launch shape of every row batch (sixteen lanes per record, four records per wave, a grid-stride loop over the
+ * records): 64 records per 16-wave workgroup.  Few records -- while such workgroups would fill at most half the CUs --
+ * run in 4-wave workgroups instead, so that they spread over four times as many CUs: every record is a serial chain
+ * that its row walks alone, so a batch is only as fast as the number of SIMDs it reaches (profiles/HISTORY.md,
+ * "sixteen lanes per message", has the measurements).  The grid is capped at the CU count and the kernels stride
+ * beyond it; no records still is a grid of 1. */
+struct RowShape { unsigned grid, wg; };
+constexpr unsigned UAESK_ROW_WG = 1024u;             /* = UAES_WG, the row kernels' launch bound (uaes_aes.hip.h asserts it) */
+static inline RowShape uaesk_row_shape(unsigned long long nrec)
+{
+    const unsigned cus = uaesk_cus_or_256();
+    const unsigned wg = (nrec + 63) / 64 * 2 <= cus ? 256u : UAESK_ROW_WG;
+    const unsigned long long want = (nrec + wg / 16 - 1) / (wg / 16);
+    return RowShape{ (unsigned)(want < cus ? (want ? want : 1) : cus), wg };
+}
+
+/* the row kernels' A4: both texts and the record size are 4-byte aligned, so every record is */
+static inline bool uaesk_rows_a4(const void *in, const void *out, size_t rec_bytes)
+{
+    return ((((uintptr_t)in) | ((uintptr_t)out)) & 3u) == 0 && rec_bytes % 4 == 0;
+}
+
 #define DISPATCH_NR(nr, CALL)                         \
     switch (nr) {                                     \
     case 10: { constexpr int NR = 10; CALL; } break;  \

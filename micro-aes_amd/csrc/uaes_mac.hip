@@ -393,12 +393,8 @@ __global__ __launch_bounds__(UAES_WG) void k_ccm_batch(uaesk_rk rk, uaesk_tables
             ccm_put(tg, t, tag_len, c);
         } else {
             const u32 d = (t ^ row_load(tg, tag_len, c)) & ccm_keep(tag_len, c);
-            const u64 b = __ballot(d != 0u);
-            const bool forged = ((b >> (threadIdx.x & 48u)) & 0xffffull) != 0;      /* this row's sixteen lanes */
-            if ((threadIdx.x & 15u) == 0) {
-                verdicts[m] = forged ? 0 : 1;
-                if (forged) atomicOr(bad, 1);
-            }
+            const bool forged = row_any(d != 0u);
+            row_verdict((threadIdx.x & 15u) == 0, verdicts, m, !forged, bad);
             if (forged && wipe)
                 for (u32 i = 0; i < len; i += 16) ccm_put(dst + i, 0u, len - i < 16u ? len - i : 16u, c);
         }
@@ -433,19 +429,15 @@ extern "C" int uaesk_plan_mac(int what, int dir, size_t a, uaes_plan *p)
     return 0;
 }
 
-/* ccm.batch: the launch shape of the other row batches (batch_shape in uaes_eax_siv.hip, plan_batch in uaes_chain.hip):
- * 64 records per 16-wave workgroup; few records: 4-wave workgroups, so that they spread over the CUs; the grid is
- * capped at the CU count and the kernel strides beyond it */
+/* ccm.batch: a row batch at any number of records (uaesk_row_shape) */
 static void plan_ccm_batch(u64 nmsg, uaes_plan *p)
 {
-    const unsigned cus = uaesk_cus_or_256();
-    const unsigned wg = (nmsg + 63) / 64 * 2 <= cus ? 256u : UAES_WG;
-    const u64 want = (nmsg + wg / 16 - 1) / (wg / 16);
+    const RowShape s = uaesk_row_shape(nmsg);
     memset(p, 0, sizeof *p);
     p->arrangement = UAES_CCM_BATCH;
     p->launches = 1;
-    p->grid = (unsigned)(want < cus ? (want ? want : 1) : cus);
-    p->steps = wg;
+    p->grid = s.grid;
+    p->steps = s.wg;
 }
 
 extern "C" int uaesk_plan_ccm_batch(int dir, size_t len, size_t nmsg, uaes_plan *p)
@@ -462,10 +454,9 @@ static int launch_ccm_batch(hipStream_t st, const uaesk_tables *tb, const uaesk_
                             size_t nmsg, size_t msg_bytes, const void *lens, const void *in, void *out, void *tags,
                             void *verdicts, int *bad)
 {
-    const bool a4 = ((((uintptr_t)in) | ((uintptr_t)out)) & 3u) == 0 && msg_bytes % 4 == 0;
     uaes_plan p;
     plan_ccm_batch(nmsg, &p);
-    return with_bool(decrypt, [&](auto DEC) { return with_bool(a4, [&](auto A4) {
+    return with_bool(decrypt, [&](auto DEC) { return with_bool(uaesk_rows_a4(in, out, msg_bytes), [&](auto A4) {
         return uaesk_launch(k_ccm_batch<NR, decltype(DEC)::value, decltype(A4)::value>, p.grid, p.steps, UAES_LDS_ROW4, st, *ek, *tb,
                             wipe, nonces, nonce_len, tag_len, aad, aad_bytes, nmsg, msg_bytes, lens, in, out, tags, verdicts,
                             bad); }); });

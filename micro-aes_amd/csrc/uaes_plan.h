@@ -49,8 +49,8 @@
  *   CCM   ccm.fused             k_ccm (MAC rows and keystream rows share the wave)  (1)    text <= UAES_CCM_FUSED_MAX (256 B)
  *         ccm.split             k_ccm_tag and CTR (k_ctr*), decrypt: CTR first      (2+)   beyond
  *         ccm.batch             k_ccm_batch (sixteen lanes per record, four per wave) (1)  uaes_ccm_*_batch, records <= UAES_CCM_BATCH_MAX (65535 B)
- *   batch batch.row             k_chain_batch_row (sixteen lanes per message;       (1)    uaes_cbc_encrypt_batch / uaes_cmac_batch,
- *                               256-thread workgroups while they fill <= half the CUs)     <= UAES_BATCH_ROW_MAX messages (81 919)
+ *   batch batch.row             k_chain_batch_row (sixteen lanes per message)       (1)    uaes_cbc_encrypt_batch / uaes_cmac_batch,
+ *                                                                                          <= UAES_BATCH_ROW_MAX messages (81 919)
  *         batch.lane            k_chain_batch (one lane per message)                (1)    more messages
  *   KW    kw.lds                k_kw<LDS> (one wave; the semiblocks in LDS)         (1)    secret <= UAES_KW_LDS_MAX (4 KiB)
  *         kw.global             k_kw<in place> (one wave; loads a chunk ahead)      (1)    beyond
@@ -64,6 +64,9 @@
  * uaes_mac.hip; uaes_debug_plan_chain); tests/test_gpu_chains.py derives its sizes and message counts from them.  Key wrap has
  * uaesk_plan_kw (uaes_kw.hip; uaes_debug_plan_kw), and tests/test_gpu_kw.py finds its two boundaries by walking it.
  * FF1 has uaesk_plan_ff1 (uaes_ff1.hip; uaes_debug_plan_ff1); tests/test_gpu_ff1.py walks it likewise.
+ * The rows that say "sixteen lanes per record / message" -- eax.batch, s2v.batch, ccm.batch, batch.row, kw.batch,
+ * ff1.batch -- are the row batches: grid and threads per workgroup are uaesk_row_shape's (uaes_launch.hip.h), the same
+ * for the same number of records in every one of them.
  */
 #ifndef UAES_PLAN_H
 #define UAES_PLAN_H
@@ -154,7 +157,7 @@ const char *uaesk_eax_siv_arrangement_name(int id);
  * (the launchers use its static core, which does not ask the CTR planner); either returns a HIP error code for a `what` of the other's or arguments that make
  * no sense (CBC with stealing below 16 bytes, a batched CBC message that is not whole blocks).
  * uaesk_plan_ccm_batch (uaes_mac.hip) answers for the batches of CCM records (UAES_WHAT_CCM_BATCH): len = bytes per
- * record, nmsg = records; the launch shape of batch.row at any number of records.  A record is at most
+ * record, nmsg = records; a row batch at any number of records.  A record is at most
  * UAES_CCM_BATCH_MAX bytes: the longest text whose length every nonce length 7..13 can still encode in B0 (two bytes
  * are left behind a 13-byte nonce), so that no record's counter can leave its field.
  * UAES_WHAT_CCM_BATCH is 9, not 8: 8 was UAES_WHAT_COUNT, the one value past the end that the plan test keeps asking

@@ -68,3 +68,24 @@ def test_batch_samples_cover_the_ends_and_every_pass():
         for k in range(1, nmsg // per_pass + 1):
             assert {k * per_pass - 1, k * per_pass, k * per_pass + 1} & set(range(nmsg)) <= set(s), (nmsg, k)
     assert K.batch_samples(100, uaes.chain_plan("cbc_batch", 16, 100)) == list(range(100))
+
+
+def test_every_row_batch_takes_one_launch_shape():
+    """the row batches (CBC / CMAC up to 81 919 messages, CCM, key wrap, FF1, EAX / SIV) answer with the same grid
+    and, where the hook reports them, the same threads per workgroup, at every number of records; the values are
+    those for 256 CUs"""
+    pinned = {1: (1, 256), 64: (4, 256), 65: (5, 256), 4096: (256, 256), 8192: (256, 256), 8193: (129, 1024),
+              16384: (256, 1024), 81919: (256, 1024), 1 << 24: (256, 1024)}
+    for n in (1, 2, 63, 64, 65, 4096, 4097, 8192, 8193, 16384, 16385, 81919, 81920, 1 << 20, 1 << 24):
+        shapes = {("ccm_batch", d): uaes.chain_plan("ccm_batch", 16, n, decrypt=d)[2:] for d in (False, True)}
+        shapes.update({("kw", d): uaes.kw_plan(16, n, unwrap=d)[2:] for d in (False, True)})
+        shapes["ff1"] = uaes.ff1_plan(6, n)[2:]
+        if n <= 81919:
+            shapes.update({what: uaes.chain_plan(what, 16, n)[2:] for what in ("cbc_batch", "cmac_batch")})
+        assert len(set(shapes.values())) == 1, (n, shapes)
+        shape = shapes["ff1"]
+        if n >= 2:
+            for siv in (False, True):
+                assert uaes.eax_siv_plan(siv, 16, n)[2] == shape[0], (n, siv)
+        if n in pinned:
+            assert shape == pinned[n], n

@@ -501,7 +501,7 @@ def test_lane_scratch_shared_with_the_gcm_key_cache():
 # ---- batches ----------------------------------------------------------------------------------------------------------
 
 def predicted_shape(nmsg, cus):
-    """uaes_eax_siv.hip's batch_shape: 256-thread workgroups (16 records each) while ceil(nmsg / 64) * 2 <= CUs, else
+    """uaes_launch.hip.h's uaesk_row_shape: 256-thread workgroups (16 records each) while ceil(nmsg / 64) * 2 <= CUs, else
     1024-thread ones (64 records); as many workgroups as there are records to fill, at most one per CU"""
     wg = 256 if (nmsg + 63) // 64 * 2 <= cus else 1024
     rows = wg // 16
@@ -524,7 +524,7 @@ SHAPE_COUNTS = ("16C", "16C+1", "32C", "32C+1", "64C", "64C+1", "192C+5")
 def test_batch_shapes_from_the_device(which, ml):
     """record counts on both sides of the first second pass of a 256-thread grid, of the switch to 1024-thread
     workgroups and of the first second pass of those; the plan must report the workgroup count this reading of
-    batch_shape predicts; EVERY record against the reference, forged records in first, last and middle rows"""
+    uaesk_row_shape predicts; EVERY record against the reference, forged records in first, last and middle rows"""
     import torch
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     counts = (16 * cus, 16 * cus + 1, 32 * cus, 32 * cus + 1, 64 * cus, 64 * cus + 1, 3 * 64 * cus + 5)
