@@ -47,18 +47,18 @@
 #ifndef KWA                  /* micro_aes.h:50 -- key wrap, RFC 3394 (uaes_kw.hip); every library exports AES_KEY_wrap /  */
 #define KWA      0          /* AES_KEY_unwrap, a caller built with -DKWA=1 sees the prototypes (below)                */
 #endif
-#ifndef FPE                  /* micro_aes.h:51 -- FF1 format-preserving encryption (uaes_ff1.hip); every library exports */
-#define FPE      0          /* AES_FPE_*, a caller built with -DFPE=1 sees the prototypes (below)                   */
+#ifndef FPE                  /* micro_aes.h:51 -- FF1 / FF3-1 format-preserving encryption (uaes_ff1.hip, uaes_ff3.hip); every library exports */
+#define FPE      0          /* AES_FPE_* and AES_FF3_*, a caller built with -DFPE=1 sees the prototypes (below)    */
 #endif
 #if FPE
 #ifndef CUSTOM_ALPHABET      /* micro_aes.h:87 -- 0: the digits 0..9; 1..9: ALPHABET and RADIX of the caller's micro_fpe.h */
 #define CUSTOM_ALPHABET 0
 #endif
-#ifndef FF_X                 /* micro_aes.h:88 -- 1: FF1, the only method served */
+#ifndef FF_X                 /* micro_aes.h:88 -- 1: FF1, the only method AES_FPE_* is bound to (FF3-1: AES_FF3_*) */
 #define FF_X            1
 #endif
 #if FF_X != 1
-#error "FF_X: only FF1 (FF_X 1) is served; FF3-1 is not"
+#error "FF_X: AES_FPE_* is bound to FF1 (FF_X 1) only; FF3-1 is served through AES_FF3_encrypt / AES_FF3_decrypt"
 #endif
 #if CUSTOM_ALPHABET >= 10 || CUSTOM_ALPHABET < 0
 #error "CUSTOM_ALPHABET: wide-character alphabets (10 and above) are not served"
@@ -443,6 +443,20 @@ UAES_STATIC_INLINE char AES_FPE_decrypt_ca(const uint8_t *key, const uint8_t *tw
 #define AES_FPE_encrypt AES_FPE_encrypt_ca
 #define AES_FPE_decrypt AES_FPE_decrypt_ca
 #endif
+/* FF3-1, SP 800-38G revision 1 (micro_aes.c:2150-2248): what the reference's AES_FPE_* are when it is built with FF_X 3,
+ * under names of their own -- the same parameter list (no tweakLen: the tweak is FF3_TWEAK_LEN bytes), the decimal
+ * alphabet, a NUL behind the output.  Any failure -- a string shorter than 6 or longer than 56 characters, a character
+ * that is no digit, an engine failure -- returns M_ENCRYPTION_ERROR / M_DECRYPTION_ERROR and leaves the output as it
+ * was.  The _alpha pair takes the alphabet (radix distinct characters, radix 2..256; the length limits follow it). */
+enum { FF3_TWEAK_LEN = 7 };
+char AES_FF3_encrypt(const uint8_t *key, const uint8_t *tweak,
+                     const void *pntxt, const size_t ptextLen, void *crtxt);
+char AES_FF3_decrypt(const uint8_t *key, const uint8_t *tweak,
+                     const void *crtxt, const size_t crtxtLen, void *pntxt);
+char AES_FF3_encrypt_alpha(const char *alphabet, const size_t radix, const uint8_t *key, const uint8_t *tweak,
+                           const void *pntxt, const size_t ptextLen, void *crtxt);
+char AES_FF3_decrypt_alpha(const char *alphabet, const size_t radix, const uint8_t *key, const uint8_t *tweak,
+                           const void *crtxt, const size_t crtxtLen, void *pntxt);
 #endif
 
 #if POLY1305

@@ -99,12 +99,12 @@ int         uaes_stream_release(void *stream);
  * GPU and fails loudly without one.  Three independent, process-wide switches for the cases a GPU serves badly:
  *   max_bytes  calls whose data pointers are HOST memory and whose text is at most this long run on the host: a
  *              launch costs 12-20 us whatever the size, one host core needs that long for ~1 KiB (GCM ~200 B);
- *   chains     ONE serial chain in host memory -- CBC / CFB encryption, OFB, CMAC, CCM, key wrap, FF1 -- runs on the host whatever
+ *   chains     ONE serial chain in host memory -- CBC / CFB encryption, OFB, CMAC, CCM, key wrap, FF1, FF3-1 -- runs on the host whatever
  *              its length (a chain is a latency-bound single wave on the GPU: 36 MiB/s; uaes_*_batch are the GPU's form);
  *   fallback   with NO usable HIP device the calls below run on the host instead of returning UAES_E_HIP -- the
  *              reference's `void` functions cannot report an error.
  * Covered: every synchronous one-message call of this header -- ECB, CTR, XTS (unit and sectors), GCM (any nonce / tag
- * length), CBC (CTS and CTS-0 forms), CFB, OFB, CMAC, CCM, GCM-SIV, OCB, KW, FF1.  Not covered (always GPU): the *_dev / *_batch
+ * length), CBC (CTS and CTS-0 forms), CFB, OFB, CMAC, CCM, GCM-SIV, OCB, KW, FF1, FF3-1.  Not covered (always GPU): the *_dev / *_batch
  * / record / key-context / stream / mgpu calls, uaes_ghash, and any call that is handed a device pointer.
  * Environment, read at first use: UAES_HOST_MAX=<bytes>, UAES_HOST_CHAINS=1, UAES_HOST_FALLBACK=1; or
  * UAES_HOST_POLICY=recommended = (4096, 1, 1), the measured crossover on the builder's hosts (profiles/r05_host_policy.md),
@@ -405,6 +405,40 @@ int uaes_ff1_encrypt_batch(int keybits, const uint8_t *key, unsigned radix, cons
 int uaes_ff1_decrypt_batch(int keybits, const uint8_t *key, unsigned radix, const uint8_t *alphabet,
                            const uint8_t *tweaks, size_t tweakLen, size_t tweak_stride,
                            size_t nrec, size_t len, const void *in, void *out, uint8_t *verdicts);
+
+/* ---- FF3-1: replaces AES_FPE_encrypt / AES_FPE_decrypt built with FF_X 3 (SP 800-38G revision 1) ------
+ * micro_aes.c:2150-2248, :2267-2347.  Format-preserving encryption of len numerals, ONE BYTE PER NUMERAL, under a tweak
+ * of exactly SEVEN bytes (the withdrawn 64-bit-tweak FF3 is not served).  radix, alphabet, key and the memory rules are
+ * FF1's: radix = 2..256; alphabet = radix distinct bytes or NULL (the bytes are the digit values); key, alphabet: host
+ * memory; tweak, in, out: host or device memory at any byte offset; out == in works.  No NUL is appended at this level.
+ *   lengths   len at least the smallest n with radix^n >= 1 000 000 (FF1's minimum), at most uaes_ff3_maxlen(radix) =
+ *             2 floor(log_radix 2^96), computed with exact integers (192 at radix 2, 56 decimal, 40 at radix 26, 36 at
+ *             36, 32 at 62 and 64, 24 at 256; 0 for a radix outside 2..256): the reference's floating-point MAXLEN
+ *             (micro_fpe.h:145) is the same number.  Otherwise UAES_E_DATALENGTH, out untouched.
+ *   errors    radix outside 2..256 or a byte twice in the alphabet: UAES_E_ARG.  A byte of `in` that is no numeral:
+ *             UAES_E_ENCRYPTION from encrypt, UAES_E_DECRYPTION from decrypt, out untouched.
+ * Eight Feistel rounds of one AES block each under the byte-reversed key; every number stays below 2^96 on the way into
+ * the cipher and 2^128 on the way out.  One call is a chain, so the host policy applies (`chains`); the GPU's form is
+ * the batch: nrec records of len numerals back to back under one key, sixteen GPU lanes per record, always on the GPU.
+ * tweak_stride 0: one tweak for all records; otherwise record m's tweak is the seven bytes at tweaks + m * tweak_stride.
+ * A record with a byte that is no numeral is left unwritten and gets verdicts[m] = 0, the others 1 (verdicts may be
+ * NULL, host or device memory); the call completes every good record and then returns the encryption / decryption
+ * error if any record was bad.  nrec == 0 returns 0.  A single call that goes to the GPU runs as a batch of one.
+ * Rates (profiles/ff3_rate.md: tools/ff3_rate.py on an MI355X, AES-128, 16-digit decimal records, device-resident):
+ * 2^20 records 2.64 ms = 3.97e8 records/s, 2^16 records 0.19 ms, 2^10 records 0.066 ms, shared or per-record tweaks,
+ * either direction -- the FF1 batch of the same shape in the same run: 5.02 ms, 0.34 ms, 0.10 ms.  One 16-digit call
+ * 88 us from host memory, 71 us from device memory.  The engine's host path on one core: 5.13e5 records/s. */
+size_t uaes_ff3_maxlen(unsigned radix);
+int uaes_ff3_encrypt(int keybits, const uint8_t *key, unsigned radix, const uint8_t *alphabet,
+                     const uint8_t *tweak /* 7 bytes */, const void *in, size_t len, void *out);
+int uaes_ff3_decrypt(int keybits, const uint8_t *key, unsigned radix, const uint8_t *alphabet,
+                     const uint8_t *tweak /* 7 bytes */, const void *in, size_t len, void *out);
+int uaes_ff3_encrypt_batch(int keybits, const uint8_t *key, unsigned radix, const uint8_t *alphabet,
+                           const uint8_t *tweaks, size_t tweak_stride, size_t nrec, size_t len,
+                           const void *in, void *out, uint8_t *verdicts);
+int uaes_ff3_decrypt_batch(int keybits, const uint8_t *key, unsigned radix, const uint8_t *alphabet,
+                           const uint8_t *tweaks, size_t tweak_stride, size_t nrec, size_t len,
+                           const void *in, void *out, uint8_t *verdicts);
 
 /* Poly1305-AES (micro_aes.c:1955-1997): keys = k (keybits / 8 bytes) || r (16 bytes), mac = (h + AES_k(nonce)) mod
  * 2^128 with h the Poly1305 polynomial in the clamped r.  Block-parallel on the VALU (uaes_poly1305.hip): one
@@ -718,6 +752,10 @@ const char *uaes_debug_plan_kw(int dir, size_t len, size_t nkeys, int out[3]);
  * NULL for arguments that make no sense: a radix outside 2..256, a length below the radix's minimum or above the
  * limit.  Works without a device (a 256-CU MI355X).  tests/test_gpu_ff1.py finds the boundary by walking this. */
 const char *uaes_debug_plan_ff1(int dir, unsigned radix, size_t len, size_t nrec, int out[3]);
+/* The planner of FF3-1 (csrc/uaes_plan.h): arguments and `out` as for FF1.  Returns "ff3.batch" (the one arrangement:
+ * sixteen lanes per record, one text is a batch of one), or NULL for a dir other than 0 / 1, a radix outside 2..256, a
+ * length below the radix's minimum or above uaes_ff3_maxlen(radix).  Works without a device (a 256-CU MI355X). */
+const char *uaes_debug_plan_ff3(int dir, unsigned radix, size_t len, size_t nrec, int out[3]);
 
 /* Test hooks of the one-launch GCM / GCM-SIV / streamed-piece arrangements (chunk workgroups + one preparing workgroup
  * in ONE launch; whoever of them arrives last on a counter word folds the chunk hashes and makes the tag -- nobody

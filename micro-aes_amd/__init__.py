@@ -49,6 +49,7 @@ EXPORTS = [
     "uaes_debug_plan_eax_siv", "uaes_debug_plan_chain",
     "uaes_kw_wrap", "uaes_kw_unwrap", "uaes_kw_wrap_batch", "uaes_kw_unwrap_batch", "uaes_debug_plan_kw",
     "uaes_ff1_encrypt", "uaes_ff1_decrypt", "uaes_ff1_encrypt_batch", "uaes_ff1_decrypt_batch", "uaes_debug_plan_ff1",
+    "uaes_ff3_maxlen", "uaes_ff3_encrypt", "uaes_ff3_decrypt", "uaes_ff3_encrypt_batch", "uaes_ff3_decrypt_batch", "uaes_debug_plan_ff3",
     "uaes_mgpu_ctr_xcrypt_at", "uaes_mgpu_xts_sectors", "uaes_mgpu_ctr_encrypt_gather", "uaes_debug_gather_stats", "uaes_debug_gcm_look", "uaes_debug_gcm_chunk_folds",
     "uaes_debug_plan", "uaes_debug_plan_at", "uaes_debug_arrangement_name", "uaes_debug_plan_disable",
     "uaes_mgpu_ecb_encrypt", "uaes_mgpu_ecb_decrypt", "uaes_mgpu_gcm_encrypt", "uaes_mgpu_gcm_decrypt",
@@ -75,6 +76,7 @@ COMPAT_EXPORTS = [
     "AES_CCM_encrypt", "AES_CCM_decrypt", "AES_CMAC", "GCM_SIV_encrypt", "GCM_SIV_decrypt",
     "AES_OCB_encrypt", "AES_OCB_decrypt", "AES_Poly1305", "AES_KEY_wrap", "AES_KEY_unwrap",
     "AES_FPE_encrypt", "AES_FPE_decrypt", "AES_FPE_encrypt_alpha", "AES_FPE_decrypt_alpha",
+    "AES_FF3_encrypt", "AES_FF3_decrypt", "AES_FF3_encrypt_alpha", "AES_FF3_decrypt_alpha",
     "AES_EAX_encrypt", "AES_EAX_decrypt", "AES_EAX_encrypt_lens", "AES_EAX_decrypt_lens", "AES_SIV_encrypt", "AES_SIV_decrypt",
     "AES_CBC_encrypt", "AES_CBC_decrypt", "AES_CFB_encrypt", "AES_CFB_decrypt", "AES_OFB_encrypt", "AES_OFB_decrypt",
 ]
@@ -176,6 +178,14 @@ def engine():
         getattr(L, n).argtypes = [i, vp, C.c_uint, vp, vp, sz, sz, sz, sz, vp, vp, vp]
     L.uaes_debug_plan_ff1.argtypes = [i, C.c_uint, sz, sz, C.POINTER(C.c_int)]
     L.uaes_debug_plan_ff1.restype = C.c_char_p
+    L.uaes_ff3_maxlen.argtypes = [C.c_uint]
+    L.uaes_ff3_maxlen.restype = sz
+    for n in ("uaes_ff3_encrypt", "uaes_ff3_decrypt"):
+        getattr(L, n).argtypes = [i, vp, C.c_uint, vp, vp, vp, sz, vp]
+    for n in ("uaes_ff3_encrypt_batch", "uaes_ff3_decrypt_batch"):
+        getattr(L, n).argtypes = [i, vp, C.c_uint, vp, vp, sz, sz, sz, vp, vp, vp]
+    L.uaes_debug_plan_ff3.argtypes = [i, C.c_uint, sz, sz, C.POINTER(C.c_int)]
+    L.uaes_debug_plan_ff3.restype = C.c_char_p
     for n in ("uaes_cbc_encrypt", "uaes_cbc_decrypt", "uaes_cbc_decrypt_blocks", "uaes_cfb_encrypt", "uaes_cfb_decrypt", "uaes_ofb_xcrypt"):
         getattr(L, n).argtypes = [i, vp, vp, vp, sz, vp]
     for n in ("uaes_ccm_encrypt", "uaes_ccm_decrypt", "uaes_gcmsiv_encrypt", "uaes_gcmsiv_decrypt",
@@ -242,7 +252,8 @@ def engine():
             continue
         if n not in ("uaes_last_error", "uaes_version", "uaes_gcm_key_free", "uaes_gcm_stream_abort", "uaes_debug_gather_stats", "uaes_debug_gcm_look",
                      "uaes_debug_arrangement_name", "uaes_debug_plan_disable", "uaes_debug_plan_poly1305",
-                     "uaes_debug_plan_eax_siv", "uaes_debug_plan_chain", "uaes_debug_plan_kw", "uaes_debug_plan_ff1"):
+                     "uaes_debug_plan_eax_siv", "uaes_debug_plan_chain", "uaes_debug_plan_kw", "uaes_debug_plan_ff1",
+                     "uaes_debug_plan_ff3", "uaes_ff3_maxlen"):
             getattr(L, n).restype = i
     _lib = L
     return L
@@ -788,6 +799,77 @@ def ff1_plan(length, nrec=0, radix=10, decrypt=False):
     return None if name is None else (name.decode(), out[0], out[1], out[2])
 
 
+FF3_TWEAK_LEN = 7
+
+
+def _ff3_tweak(tweak):
+    if len(tweak) != FF3_TWEAK_LEN:
+        raise ValueError("FF3-1 tweak of %d bytes (%d)" % (len(tweak), FF3_TWEAK_LEN))
+    return bytes(tweak)
+
+
+def _ff3(decrypt, key, tweak, text, alphabet, radix, prefill):
+    radix, a = _ff1_alpha(alphabet, radix)
+    o = _out(len(text), prefill)
+    L = engine()
+    fn = L.uaes_ff3_decrypt if decrypt else L.uaes_ff3_encrypt
+    rc = fn(_bits(key), _in(key), radix, a, _in(_ff3_tweak(tweak)), _in(text), len(text), o)
+    if rc < 0 and rc != -2:
+        _check(rc, "AES_FF3_decrypt" if decrypt else "AES_FF3_encrypt")
+    return rc, bytes(o)[:len(text)]
+
+
+def AES_FF3_encrypt(key, tweak, text, alphabet=b"0123456789", radix=None, prefill=0):
+    """micro_aes.c:2326 built with FF_X 3 (FF3-1, SP 800-38G revision 1).  tweak = 7 bytes; text = numerals, one byte
+    each, out of `alphabet` (alphabet=None: raw digit values below `radix`).  Returns (code, output): 0; 1 for a text
+    shorter than the radix's minimum or longer than ff3_maxlen(radix); -2 for a radix outside 2..256 or a repeated
+    alphabet byte; 0x1E for a byte that is no numeral; the output is the prefill unless the code is 0."""
+    return _ff3(False, key, tweak, text, alphabet, radix, prefill)
+
+
+def AES_FF3_decrypt(key, tweak, text, alphabet=b"0123456789", radix=None, prefill=0):
+    """micro_aes.c:2343 built with FF_X 3.  As AES_FF3_encrypt; 0x1D for a byte that is no numeral."""
+    return _ff3(True, key, tweak, text, alphabet, radix, prefill)
+
+
+def ff3_batch(key, tweaks, records, alphabet=b"0123456789", radix=None, decrypt=False, prefill=0, verdicts=True):
+    """FF3-1 of many equal-sized records under one key (uaes_ff3_*_batch).  tweaks = one 7-byte tweak (bytes) for all
+    records or a list of them, one per record.  Returns (code, outputs, verdicts): a record with a byte that is no
+    numeral keeps the prefill and has verdict 0."""
+    n = len(records)
+    radix, a = _ff1_alpha(alphabet, radix)
+    if isinstance(tweaks, (bytes, bytearray)):
+        stride, tb = 0, _ff3_tweak(tweaks)
+    else:
+        if len(tweaks) != n:
+            raise ValueError("one tweak per record")
+        tb = b"".join(_ff3_tweak(t) for t in tweaks)
+        stride = FF3_TWEAK_LEN
+    rl, rb = _records(records, "records")
+    o = _out(n * rl, prefill)
+    v = _out(n)
+    L = engine()
+    fn = L.uaes_ff3_decrypt_batch if decrypt else L.uaes_ff3_encrypt_batch
+    rc = fn(_bits(key), _in(key), radix, a, _in(tb), stride, n, rl, _in(rb), o, v if verdicts else None)
+    if rc < 0 and rc != -2:
+        _check(rc, "uaes_ff3_batch")
+    raw = bytes(o)
+    return rc, _split(raw, rl, n), list(bytes(v)[:n])
+
+
+def ff3_plan(length, nrec=0, radix=10, decrypt=False):
+    """What FF3-1 over a text of `length` numerals would run (uaes_debug_plan_ff3; nrec 0: the one-text calls, else a
+    batch): (arrangement, launches, workgroups, threads per workgroup), or None for arguments that make no sense."""
+    out = (C.c_int * 3)()
+    name = engine().uaes_debug_plan_ff3(int(bool(decrypt)), radix, length, nrec, out)
+    return None if name is None else (name.decode(), out[0], out[1], out[2])
+
+
+def ff3_maxlen(radix):
+    """2 floor(log_radix 2^96), the longest FF3-1 text at this radix; 0 for a radix outside 2..256"""
+    return int(engine().uaes_ff3_maxlen(radix))
+
+
 _compat = {}
 
 
@@ -807,6 +889,12 @@ def compat(bits):
             getattr(lib, n).restype = C.c_char
         for n in ("AES_FPE_encrypt_alpha", "AES_FPE_decrypt_alpha"):
             getattr(lib, n).argtypes = [C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
+            getattr(lib, n).restype = C.c_char
+        for n in ("AES_FF3_encrypt", "AES_FF3_decrypt"):
+            getattr(lib, n).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+            getattr(lib, n).restype = C.c_char
+        for n in ("AES_FF3_encrypt_alpha", "AES_FF3_decrypt_alpha"):
+            getattr(lib, n).argtypes = [C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
             getattr(lib, n).restype = C.c_char
         _compat[bits] = lib
     return _compat[bits]

@@ -270,6 +270,42 @@ char AES_FPE_decrypt_alpha(const char *alphabet, const size_t radix, const uint8
     return fpe("AES_FPE_decrypt", 1, alphabet, radix, key, tweak, tweakLen, crtxt, crtxtLen, pntxt);
 }
 
+/* FF3-1 (micro_aes.c:2150-2248, the reference built with FF_X 3): the same one code per direction and the same NUL */
+static char ff3(const char *fn, int decrypt, const char *alphabet, size_t radix, const uint8_t *key, const uint8_t *tweak,
+                const void *in, size_t len, void *out)
+{
+    const char bad = decrypt ? M_DECRYPTION_ERROR : M_ENCRYPTION_ERROR;
+    int rc;
+    if (radix < 2 || radix > 256) return bad;
+    rc = decrypt ? uaes_ff3_decrypt(KB, key, (unsigned)radix, (const uint8_t *)alphabet, tweak, in, len, out)
+                 : uaes_ff3_encrypt(KB, key, (unsigned)radix, (const uint8_t *)alphabet, tweak, in, len, out);
+    if (rc == 0) { ((char *)out)[len] = 0; return M_RESULT_SUCCESS; }
+    if (rc < 0) fprintf(stderr, "uaes-hip: %s failed (%d): %s\n", fn, rc, uaes_last_error());
+    return bad;
+}
+
+char AES_FF3_encrypt(const uint8_t *key, const uint8_t *tweak, const void *pntxt, const size_t ptextLen, void *crtxt)
+{
+    return ff3("AES_FF3_encrypt", 0, "0123456789", 10, key, tweak, pntxt, ptextLen, crtxt);
+}
+
+char AES_FF3_decrypt(const uint8_t *key, const uint8_t *tweak, const void *crtxt, const size_t crtxtLen, void *pntxt)
+{
+    return ff3("AES_FF3_decrypt", 1, "0123456789", 10, key, tweak, crtxt, crtxtLen, pntxt);
+}
+
+char AES_FF3_encrypt_alpha(const char *alphabet, const size_t radix, const uint8_t *key, const uint8_t *tweak,
+                           const void *pntxt, const size_t ptextLen, void *crtxt)
+{
+    return ff3("AES_FF3_encrypt", 0, alphabet, radix, key, tweak, pntxt, ptextLen, crtxt);
+}
+
+char AES_FF3_decrypt_alpha(const char *alphabet, const size_t radix, const uint8_t *key, const uint8_t *tweak,
+                           const void *crtxt, const size_t crtxtLen, void *pntxt)
+{
+    return ff3("AES_FF3_decrypt", 1, alphabet, radix, key, tweak, crtxt, crtxtLen, pntxt);
+}
+
 /* CTS (micro_aes.h:56) is the caller's compile-time choice too: with CTS 0 the reference's CBC pads its last
  * chunk like ECB (AES_PADDING) instead of stealing (micro_aes.c:704-733) and its decryption wants whole blocks
  * (:761).  Every library exports both families; include/micro_aes.h binds AES_CBC_* to the caller's.      */

@@ -306,6 +306,20 @@ typedef struct {
 int uaesk_ff1_run(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, int decrypt, const uaesk_ff1 *q,
                   const void *tweaks, size_t nrec, const void *in, void *out, void *verdicts, int *bad);
 
+/* FF3-1, SP 800-38G revision 1 (uaes_ff3.hip; AES_FPE_encrypt / AES_FPE_decrypt with FF_X 3, micro_aes.c:2150-2248,
+ * :2267-2314).  ek = the round keys of the key with its BYTES REVERSED (the host reverses it before expansion); inv and
+ * fwd as in uaesk_ff1.  nrec 0: one text of q->len numerals, a batch of one; nrec >= 1: records back to back, record m's
+ * seven-byte tweak at tweaks + m * tweak_stride (0: one tweak for all).  Device pointers at any byte offset; in == out
+ * is fine.  verdicts (may be NULL) receives 1 / 0 per record; a record with a byte that is no numeral is left unwritten
+ * and ORs 1 into *bad. */
+typedef struct {
+    unsigned           radix, len;
+    unsigned long long tweak_stride;
+    unsigned char      inv[256], fwd[256];
+} uaesk_ff3;
+int uaesk_ff3_run(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, int decrypt, const uaesk_ff3 *q,
+                  const void *tweaks, size_t nrec, const void *in, void *out, void *verdicts, int *bad);
+
 /* Device self-test of the primitives; writes a bitmask of failures.        */
 int uaesk_selftest(void *stream, const uaesk_tables *tb, const uaesk_rk *ek128,
                    const uaesk_rk *dk128, unsigned *d_result);

@@ -736,7 +736,7 @@ static void auto_devices_from_env(void)          /* once, from env_init() */
  * By default every call runs on the GPU and fails loudly without one.  Three independent switches, process-wide:
  *   max_bytes  host-pointer calls of at most this many bytes run on the host (0 = never): below ~1 KiB (GCM ~200 B) a
  *              kernel launch costs more than the cipher (profiles/r04_break_even.md);
- *   chains     ONE serial chain given host pointers -- CBC / CFB encryption, OFB, CMAC, CCM, key wrap, FF1 -- runs on the host whatever
+ *   chains     ONE serial chain given host pointers -- CBC / CFB encryption, OFB, CMAC, CCM, key wrap, FF1, FF3-1 -- runs on the host whatever
  *              its length: a chain is a latency-bound single wave on the GPU (36 MiB/s);
  *   fallback   with NO usable HIP device the modes this path implements run on the host instead of failing
  *              (a `void` function of the reference's API cannot report an error).
@@ -1340,7 +1340,7 @@ int stage_text(lane *L, int k, const void *user, size_t n, int prefill, void **d
     return 0;
 }
 
-/* ---- a row batch's arrays (uaes_engine_modes.c: the EAX / SIV, CCM, key-wrap and FF1 batches) ----
+/* ---- a row batch's arrays (uaes_engine_modes.c: the EAX / SIV, CCM, key-wrap, FF1 and FF3-1 batches) ----
  * The caller lists its side arrays (row_array, uaes_engine.h) and its two texts (row_text) and calls row_stage,
  * row_texts, its launcher and row_finish, in this order.  A device array goes to the kernel as it is; host arrays
  * share the lane's scratch, SIDE(bytes) each.  The offsets and the size asked of lane_scratch come from the one list,
@@ -1466,6 +1466,14 @@ const char *uaes_debug_plan_ff1(int dir, unsigned radix, size_t len, size_t nrec
     if (uaesk_plan_ff1(dir, radix, len, nrec, &p)) return NULL;
     if (out) { out[0] = p.launches; out[1] = (int)p.grid; out[2] = (int)p.steps; }
     return uaesk_ff1_arrangement_name(p.arrangement);
+}
+const char *uaes_debug_plan_ff3(int dir, unsigned radix, size_t len, size_t nrec, int out[3])
+{
+    uaes_plan p;
+    memset(&p, 0, sizeof p);
+    if (uaesk_plan_ff3(dir, radix, len, nrec, &p)) return NULL;
+    if (out) { out[0] = p.launches; out[1] = (int)p.grid; out[2] = (int)p.steps; }
+    return uaesk_ff3_arrangement_name(p.arrangement);
 }
 void uaes_debug_plan_disable(unsigned mask) { uaesk_plan_disable(mask); }
 

@@ -1130,23 +1130,33 @@ int uaes_kw_unwrap_batch(int keybits, const uint8_t *kek, size_t nkeys, size_t w
 /* Kernels in uaes_ff1.hip.  What depends on (radix, alphabet, len, tweak length) alone is made here, once per call: the
  * two alphabet tables, b and d with exact integers (uaesh_ff1_b -- not the reference's floating-point LOGRDX form,
  * DESIGN.md), the P block.  cap = the longest text this call takes. */
+/* inv = byte -> digit value (0xFF: no numeral), fwd = digit value -> byte; alphabet NULL: the digit values themselves */
+static int fpe_alphabet(const char *mode, unsigned radix, const uint8_t *alphabet, uint8_t inv[256], uint8_t fwd[256])
+{
+    uint8_t seen[256];
+    unsigned i;
+    if (radix < 2 || radix > 256) return fail(UAES_E_ARG, "%s: radix %u (2..256)", mode, radix);
+    memset(seen, 0, sizeof seen);
+    memset(inv, 0xFF, 256);
+    for (i = 0; i < radix; ++i) {
+        const uint8_t a = alphabet ? alphabet[i] : (uint8_t)i;
+        if (seen[a]) return fail(UAES_E_ARG, "%s: byte 0x%02x occurs twice in the alphabet", mode, a);
+        seen[a] = 1;
+        inv[a] = (uint8_t)i;
+        fwd[i] = a;
+    }
+    return 0;
+}
+
 static int ff1_setup(unsigned radix, const uint8_t *alphabet, size_t tweakLen, size_t tweak_stride, size_t len, size_t cap,
                      uaesk_ff1 *q)
 {
-    uint8_t seen[256], p[16];
+    uint8_t p[16];
     size_t v;
     unsigned i;
-    if (radix < 2 || radix > 256) return fail(UAES_E_ARG, "FF1: radix %u (2..256)", radix);
+    int rc;
     memset(q, 0, sizeof *q);
-    memset(seen, 0, sizeof seen);
-    memset(q->inv, 0xFF, sizeof q->inv);
-    for (i = 0; i < radix; ++i) {
-        const uint8_t a = alphabet ? alphabet[i] : (uint8_t)i;
-        if (seen[a]) return fail(UAES_E_ARG, "FF1: byte 0x%02x occurs twice in the alphabet", a);
-        seen[a] = 1;
-        q->inv[a] = (uint8_t)i;
-        q->fwd[i] = a;
-    }
+    if ((rc = fpe_alphabet("FF1", radix, alphabet, q->inv, q->fwd)) != 0) return rc;
     if (len < uaesh_ff1_minlen(radix) || len > cap || (uint64_t)tweakLen >> 32) return UAES_E_DATALENGTH;
     v = len - len / 2;
     q->radix = radix;
@@ -1252,6 +1262,120 @@ int uaes_ff1_decrypt_batch(int keybits, const uint8_t *key, unsigned radix, cons
                            size_t nrec, size_t len, const void *in, void *out, uint8_t *verdicts)
 {
     return ff1_batch(1, keybits, key, radix, alphabet, tweaks, tweakLen, tweak_stride, nrec, len, in, out, verdicts);
+}
+
+/* ------------------------------------------------------------------------ */
+/* FF3-1, SP 800-38G revision 1 (AES_FPE_encrypt / AES_FPE_decrypt with FF_X 3, micro_aes.c:2150-2248, :2267-2347) */
+/* ------------------------------------------------------------------------ */
+/* Kernel in uaes_ff3.hip.  The cipher runs under the key with its bytes reversed: ks = that key's schedule, for the GPU
+ * and for the host path alike. */
+static int ff3_setup(keysched *ks, int keybits, const uint8_t *key, unsigned radix, const uint8_t *alphabet,
+                     size_t tweak_stride, size_t len, uaesk_ff3 *q)
+{
+    uint8_t rev[32];
+    unsigned i;
+    int rc;
+    if ((keybits != 128 && keybits != 192 && keybits != 256) || !key) return expand_key(ks, key, keybits);   /* its error */
+    for (i = 0; i < (unsigned)keybits / 8; ++i) rev[i] = key[keybits / 8 - 1 - i];
+    rc = expand_key(ks, rev, keybits);
+    burn(rev, sizeof rev);
+    if (rc) return rc;
+    memset(q, 0, sizeof *q);
+    if ((rc = fpe_alphabet("FF3-1", radix, alphabet, q->inv, q->fwd)) != 0) { burn(ks, sizeof *ks); return rc; }
+    if (len < uaesh_ff1_minlen(radix) || len > uaesh_ff3_maxlen(radix)) { burn(ks, sizeof *ks); return UAES_E_DATALENGTH; }
+    q->radix = radix;
+    q->len = (unsigned)len;
+    q->tweak_stride = tweak_stride;
+    return 0;
+}
+
+/* nrec 0: one text.  As ff1_gpu: the output's staging buffer starts as a copy of the caller's. */
+static int ff3_gpu(const keysched *ks, int decrypt, const uaesk_ff3 *q, const uint8_t *tweaks, size_t tweak_bytes,
+                   size_t nrec, const void *in, void *outp, uint8_t *verdicts)
+{
+    context *c;
+    lane *L;
+    const void *d_tweaks = NULL;
+    const size_t n = nrec ? nrec : 1, total = n * q->len;
+    int rc, bad;
+    if ((rc = enter(&c, &L)) != 0) return rc;
+    row_array a[1] = { { verdicts, verdicts ? n : 0, 1, NULL } };
+    row_text t = { in, outp, total, total, 1, NULL, NULL };
+    if ((rc = row_stage(L, a, 1, 1)) != 0) goto out;
+    if ((rc = stage_aad(L, tweaks, tweak_bytes, &d_tweaks)) != 0) goto out;
+    if ((rc = row_texts(L, &t)) != 0) goto out;
+    ES_KCHK("FF3-1", uaesk_ff3_run(L->stream, &c->tb, ks->nr, &ks->ek, decrypt, q, d_tweaks, nrec, t.d_in, t.d_out, a[0].d,
+                                   L->d_status));
+    if ((rc = row_finish(L, &t, a, 1, 1, &bad)) != 0) goto out;
+    rc = bad ? (decrypt ? UAES_E_DECRYPTION : UAES_E_ENCRYPTION) : 0;
+out:
+    DONE(L, rc);
+}
+
+static int ff3_one(int decrypt, int keybits, const uint8_t *key, unsigned radix, const uint8_t *alphabet,
+                   const uint8_t *tweak, const void *in, size_t len, void *out)
+{
+    keysched ks;
+    uaesk_ff3 q;
+    int rc;
+    if ((rc = ff3_setup(&ks, keybits, key, radix, alphabet, 0, len, &q)) != 0) return rc;
+    if (!in || !out || !tweak) { burn(&ks, sizeof ks); return fail(UAES_E_ARG, "NULL pointer"); }
+    if (host_take(in, out, len, 1) && !is_device_ptr(tweak)) {
+        const uaesh_key hk = host_key(&ks);
+        rc = uaesh_ff3(&hk, decrypt, radix, alphabet, tweak, (const uint8_t *)in, len, (uint8_t *)out);
+        burn(&ks, sizeof ks);
+        return rc == UAES_E_ENCRYPTION || rc == UAES_E_DECRYPTION ? rc : host_result(rc);
+    }
+    rc = ff3_gpu(&ks, decrypt, &q, tweak, UAES_FF3_TWEAK, 0, in, out, NULL);
+    burn(&ks, sizeof ks);
+    return rc;
+}
+
+size_t uaes_ff3_maxlen(unsigned radix) { return uaesh_ff3_maxlen(radix); }
+
+int uaes_ff3_encrypt(int keybits, const uint8_t *key, unsigned radix, const uint8_t *alphabet,
+                     const uint8_t *tweak, const void *in, size_t len, void *out)
+{
+    return ff3_one(0, keybits, key, radix, alphabet, tweak, in, len, out);
+}
+
+int uaes_ff3_decrypt(int keybits, const uint8_t *key, unsigned radix, const uint8_t *alphabet,
+                     const uint8_t *tweak, const void *in, size_t len, void *out)
+{
+    return ff3_one(1, keybits, key, radix, alphabet, tweak, in, len, out);
+}
+
+static int ff3_batch(int decrypt, int keybits, const uint8_t *key, unsigned radix, const uint8_t *alphabet,
+                     const uint8_t *tweaks, size_t tweak_stride, size_t nrec, size_t len,
+                     const void *in, void *out, uint8_t *verdicts)
+{
+    keysched ks;
+    uaesk_ff3 q;
+    int rc;
+    if ((rc = ff3_setup(&ks, keybits, key, radix, alphabet, tweak_stride, len, &q)) != 0) return rc;
+    if (nrec == 0) { burn(&ks, sizeof ks); return 0; }
+    if (nrec > (size_t)-1 / len || (tweak_stride && nrec - 1 > ((size_t)-1 - UAES_FF3_TWEAK) / tweak_stride)) {
+        burn(&ks, sizeof ks);
+        return fail(UAES_E_ARG, "batch size overflows");
+    }
+    if (!in || !out || !tweaks) { burn(&ks, sizeof ks); return fail(UAES_E_ARG, "NULL pointer"); }
+    rc = ff3_gpu(&ks, decrypt, &q, tweaks, (nrec - 1) * tweak_stride + UAES_FF3_TWEAK, nrec, in, out, verdicts);
+    burn(&ks, sizeof ks);
+    return rc;
+}
+
+int uaes_ff3_encrypt_batch(int keybits, const uint8_t *key, unsigned radix, const uint8_t *alphabet,
+                           const uint8_t *tweaks, size_t tweak_stride, size_t nrec, size_t len,
+                           const void *in, void *out, uint8_t *verdicts)
+{
+    return ff3_batch(0, keybits, key, radix, alphabet, tweaks, tweak_stride, nrec, len, in, out, verdicts);
+}
+
+int uaes_ff3_decrypt_batch(int keybits, const uint8_t *key, unsigned radix, const uint8_t *alphabet,
+                           const uint8_t *tweaks, size_t tweak_stride, size_t nrec, size_t len,
+                           const void *in, void *out, uint8_t *verdicts)
+{
+    return ff3_batch(1, keybits, key, radix, alphabet, tweaks, tweak_stride, nrec, len, in, out, verdicts);
 }
 
 /* ------------------------------------------------------------------------ */

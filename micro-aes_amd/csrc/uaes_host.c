@@ -1155,3 +1155,67 @@ int uaesh_ff1(const uaesh_key *k, int decrypt, unsigned radix, const uint8_t *al
     memset(limb, 0, sizeof limb); memset(p, 0, sizeof p); memset(r, 0, sizeof r);
     return 0;
 }
+
+/* ---- FF3-1, SP 800-38G revision 1 (FF3_cipher micro_aes.c:2150-2248, FPE_cipher :2267-2314 with FF_X 3) ------------------ */
+typedef unsigned __int128 u128;
+
+/* 2 * the largest k with radix^k <= 2^96: the specification's maxlen, which the reference's 2 * (int)(96.000001 / LOGRDX)
+ * (micro_fpe.h:145) equals */
+size_t uaesh_ff3_maxlen(unsigned radix)
+{
+    const u128 lim = (u128)1 << 96;
+    u128 p = 1;
+    size_t k = 0;
+    if (radix < 2 || radix > 256) return 0;
+    while (p * radix <= lim) { p *= radix; ++k; }
+    return 2 * k;
+}
+
+/* Both halves stay NUMBERS (numeral 0 the least significant digit, below radix^m <= 2^96) through the eight rounds; with
+ * the specification's REV and REVB folded in, a round's block is NUM(the other half) least significant byte first, then
+ * the tweak half reversed with the round number in its last byte, and y is the cipher's output read the same way. */
+int uaesh_ff3(const uaesh_key *k, int decrypt, unsigned radix, const uint8_t *alphabet, const uint8_t *tweak,
+              const uint8_t *in, size_t len, uint8_t *out)
+{
+    uint8_t inv[256], seen[256], blk[16], w[2][4];
+    const size_t u = (len + 1) / 2;
+    u128 num[2] = { 0, 0 }, mod[2] = { 1, 1 };
+    size_t i;
+    int step;
+    if (radix < 2 || radix > 256) return -2;
+    if (len < uaesh_ff1_minlen(radix) || len > uaesh_ff3_maxlen(radix)) return 1;
+    memset(seen, 0, sizeof seen);
+    memset(inv, 0, sizeof inv);
+    for (i = 0; i < radix; ++i) {
+        const uint8_t a = alphabet ? alphabet[i] : (uint8_t)i;
+        if (seen[a]) return -2;
+        seen[a] = 1;
+        inv[a] = (uint8_t)i;
+    }
+    for (i = 0; i < len; ++i)                                 /* every numeral is looked up before anything is written */
+        if (!seen[in[i]]) return decrypt ? 0x1D : 0x1E;
+    for (i = u; i-- > 0;) { num[0] = num[0] * radix + inv[in[i]]; mod[0] *= radix; }
+    for (i = len; i-- > u;) { num[1] = num[1] * radix + inv[in[i]]; mod[1] *= radix; }
+    w[0][0] = (uint8_t)(tweak[3] << 4); w[0][1] = tweak[6]; w[0][2] = tweak[5]; w[0][3] = tweak[4];     /* TR reversed */
+    w[1][0] = tweak[3] & 0xF0; w[1][1] = tweak[2]; w[1][2] = tweak[1]; w[1][3] = tweak[0];              /* TL reversed */
+    for (step = 0; step < 8; ++step) {
+        const int round = decrypt ? 7 - step : step, odd = round & 1;      /* an even round changes the first half */
+        u128 y = 0, t = num[!odd];
+        for (i = 0; i < 12; ++i, t >>= 8) blk[i] = (uint8_t)t;
+        memcpy(blk + 12, w[odd], 4);
+        blk[12] ^= (uint8_t)round;
+        uaesh_encrypt(k->ek, k->nr, blk, blk);
+        for (i = 16; i-- > 0;) y = y << 8 | blk[i];
+        y %= mod[odd];
+        num[odd] = (decrypt ? num[odd] + mod[odd] - y : num[odd] + y) % mod[odd];
+    }
+    for (i = 0; i < len; ++i) {
+        const int h = i >= u;
+        const unsigned dgt = (unsigned)(num[h] % radix);
+        num[h] /= radix;
+        out[i] = alphabet ? alphabet[dgt] : (uint8_t)dgt;
+    }
+    memset(blk, 0, sizeof blk); memset(w, 0, sizeof w);
+    num[0] = num[1] = 0;
+    return 0;
+}

@@ -74,4 +74,11 @@ size_t   uaesh_ff1_b(unsigned radix, size_t v);
 int  uaesh_ff1(const uaesh_key *k, int decrypt, unsigned radix, const uint8_t *alphabet, const uint8_t *tweak,
                size_t tweak_len, const uint8_t *in, size_t len, uint8_t *out);                               /* :2091-2147, :2267-2314 */
 
+/* FF3-1, SP 800-38G revision 1: as uaesh_ff1 with a tweak of exactly seven bytes; k = the schedule of the key with its
+ * BYTES REVERSED.  1 for len below uaesh_ff1_minlen(radix) or above uaesh_ff3_maxlen(radix) = 2 floor(log_radix 2^96)
+ * (exact integers; 0 for a radix outside 2..256). */
+size_t   uaesh_ff3_maxlen(unsigned radix);
+int  uaesh_ff3(const uaesh_key *k, int decrypt, unsigned radix, const uint8_t *alphabet, const uint8_t *tweak7,
+               const uint8_t *in, size_t len, uint8_t *out);                                                 /* :2150-2248, :2267-2314 */
+
 #endif

@@ -57,6 +57,7 @@
  *         kw.batch              k_kw_batch (sixteen lanes per record)               (1)    uaes_kw_*_batch, <= UAES_KW_BATCH_MAX (256 B)
  *   FF1   ff1.batch             k_ff1<16> (sixteen lanes per record, four per wave) (1)    uaes_ff1_*_batch; one text of <= UAES_FF1_BATCH_MAX (128) numerals
  *         ff1.wave              k_ff1<64> (one wave per text)                       (1)    one longer text, <= UAES_FF1_MAX (4096) numerals
+ *   FF3-1 ff3.batch             k_ff3 (sixteen lanes per record, four per wave)     (1)    uaes_ff3_*_batch; one text (<= 192 numerals) is a batch of one
  * The Poly1305 rows have a planner of their own (uaesk_plan_poly1305, uaes_poly1305.hip) and ids outside enum
  * uaes_arrangement (uaes_debug_plan_poly1305 names them); a larger message never goes back to a smaller row.
  * So do the EAX and SIV (RFC 5297) rows (uaesk_plan_eax_siv, uaes_eax_siv.hip; uaes_debug_plan_eax_siv), and the
@@ -64,8 +65,9 @@
  * uaes_mac.hip; uaes_debug_plan_chain); tests/test_gpu_chains.py derives its sizes and message counts from them.  Key wrap has
  * uaesk_plan_kw (uaes_kw.hip; uaes_debug_plan_kw), and tests/test_gpu_kw.py finds its two boundaries by walking it.
  * FF1 has uaesk_plan_ff1 (uaes_ff1.hip; uaes_debug_plan_ff1); tests/test_gpu_ff1.py walks it likewise.
+ * FF3-1 has uaesk_plan_ff3 (uaes_ff3.hip; uaes_debug_plan_ff3): one row, whose limits depend on the radix.
  * The rows that say "sixteen lanes per record / message" -- eax.batch, s2v.batch, ccm.batch, batch.row, kw.batch,
- * ff1.batch -- are the row batches: grid and threads per workgroup are uaesk_row_shape's (uaes_launch.hip.h), the same
+ * ff1.batch, ff3.batch -- are the row batches: grid and threads per workgroup are uaesk_row_shape's (uaes_launch.hip.h), the same
  * for the same number of records in every one of them.
  */
 #ifndef UAES_PLAN_H
@@ -202,6 +204,17 @@ const char *uaesk_kw_arrangement_name(int id);
 enum uaes_ff1_arrangement { UAES_FF1_BATCH = 0, UAES_FF1_WAVE };
 int uaesk_plan_ff1(int dir, unsigned radix, size_t len, size_t nrec, uaes_plan *p);
 const char *uaesk_ff1_arrangement_name(int id);
+
+/* FF3-1, SP 800-38G revision 1 (uaes_ff3.hip).  dir, len, nrec as for FF1; the tweak is always UAES_FF3_TWEAK bytes.  One
+ * arrangement: a text is at most maxlen(radix) = 2 floor(log_radix 2^96) numerals (192 at radix 2, 56 decimal, 24 at
+ * radix 256), so the 64 records of a workgroup always fit the LDS the row4 tables leave (uaes_ff3.hip asserts it) and
+ * one text is a batch of one.  grid = workgroups, steps = threads per workgroup.  Returns a HIP error code for a dir
+ * other than 0 / 1, a radix outside 2..256, a length below the radix's minimum (radix^len >= 1 000 000) or above its
+ * maximum. */
+#define UAES_FF3_TWEAK 7
+enum uaes_ff3_arrangement { UAES_FF3_BATCH = 0 };
+int uaesk_plan_ff3(int dir, unsigned radix, size_t len, size_t nrec, uaes_plan *p);
+const char *uaesk_ff3_arrangement_name(int id);
 
 #ifdef __cplusplus
 }

@@ -94,3 +94,11 @@ print("FF1: a text holds at most UAES_FF1_MAX = %d numerals, a batch record at m
 walk("FF1 batch, k decimal records of 16 numerals (positions/thread: threads per workgroup)",
      lambda k: uaes.ff1_plan(16, max(k, 1))[:2] + (0, uaes.ff1_plan(16, max(k, 1))[3]), 1, 1 << 20, 1,
      lambda k: "%9d records (%9.3f MiB)" % (k, k * 16 / MIB))
+for radix in (2, 10, 36, 256):
+    print("FF3-1, radix %d: one text of %d..%d numerals" % (radix, min(n for n in range(1, 200) if uaes.ff3_plan(n, radix=radix)),
+                                                          uaes.ff3_maxlen(radix)))
+walk("FF3-1 encrypt, one decimal text of n numerals",
+     lambda n: uaes.ff3_plan(max(n, 6))[:2] + (0, 0), 6, uaes.ff3_maxlen(10), 1, lambda n: "%11d numerals" % n)
+walk("FF3-1 batch, k decimal records of 16 numerals (positions/thread: threads per workgroup)",
+     lambda k: uaes.ff3_plan(16, max(k, 1))[:2] + (0, uaes.ff3_plan(16, max(k, 1))[3]), 1, 1 << 20, 1,
+     lambda k: "%9d records (%9.3f MiB)" % (k, k * 16 / MIB))
