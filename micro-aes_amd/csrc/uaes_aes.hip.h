@@ -807,37 +807,54 @@ __device__ __forceinline__ void row_store_full(unsigned char *p, u32 w, u32 c)
     q[0] = (unsigned char)w; q[1] = (unsigned char)(w >> 8); q[2] = (unsigned char)(w >> 16); q[3] = (unsigned char)(w >> 24);
 }
 
+/* a partial block in the row batches (four records per wave: unlike row_store, any row stores): bytes of column c below n */
+__device__ __forceinline__ u32 row_keep(u32 n, u32 c)
+{
+    return n >= 4u * c + 4u ? 0xffffffffu : n <= 4u * c ? 0u : (1u << (8u * (n - 4u * c))) - 1u;
+}
+
+/* the first n bytes of the block whose column words the row holds -> p (one lane per column of the row stores) */
+__device__ __forceinline__ void row_put(unsigned char *p, u32 w, u32 n, u32 c)
+{
+    if (threadIdx.x & 3u) return;
+    if (n >= 16 && (((uintptr_t)p) & 3u) == 0) { ((u32 *)p)[c] = w; return; }
+#pragma unroll
+    for (u32 k = 0; k < 4; ++k)
+        if (4u * c + k < n) p[4u * c + k] = (unsigned char)(w >> (8u * k));
+}
+
 /* f(i, x): the full 16-byte blocks i = 0..nblk-1 at p as column words x.  The text is requested a whole
  * chunk of ROW_CH blocks ahead: the loads of chunk k+1 are issued before the chain walks chunk k and are
  * first touched when it is done (~16 us later), so whatever s_waitcnt vmcnt the compiler places inside a
  * chunk finds them complete -- with a four-block register ring it waited for the newest load in the middle
  * of every fourth block (a register copy the allocator put there) and the chain paid the memory latency.
- * Indices past the end are clamped, not branched around.                                              */
+ * Indices past the end are clamped, not branched around.  CH: a kernel short of registers, whose step is longer than
+ * a block of the cipher, asks for a shorter chunk (2 CH registers).                                        */
 #define ROW_CH 16
-template <bool A4, typename F>
+template <bool A4, u32 CH = ROW_CH, typename F>
 __device__ __forceinline__ void row_walk(const unsigned char *p, u64 nblk, u32 c, F f)
 {
     if (nblk == 0) return;
     const u64 last = nblk - 1;
-    u32 cur[ROW_CH], nxt[ROW_CH];
+    u32 cur[CH], nxt[CH];
 #pragma unroll
-    for (u32 j = 0; j < ROW_CH; ++j) cur[j] = row_load_full<A4>(p + 16u * (j < last ? j : last), c);
-    for (u64 i = 0; i < nblk; i += ROW_CH) {
+    for (u32 j = 0; j < CH; ++j) cur[j] = row_load_full<A4>(p + 16u * (j < last ? j : last), c);
+    for (u64 i = 0; i < nblk; i += CH) {
 #pragma unroll
-        for (u32 j = 0; j < ROW_CH; ++j) {
-            const u64 nx = i + ROW_CH + j;
+        for (u32 j = 0; j < CH; ++j) {
+            const u64 nx = i + CH + j;
             nxt[j] = row_load_full<A4>(p + 16u * (nx < last ? nx : last), c);
         }
-        if (i + ROW_CH <= nblk) {
+        if (i + CH <= nblk) {
 #pragma unroll
-            for (u32 j = 0; j < ROW_CH; ++j) f(i + j, cur[j]);
+            for (u32 j = 0; j < CH; ++j) f(i + j, cur[j]);
         } else {
 #pragma unroll
-            for (u32 j = 0; j < ROW_CH; ++j)
+            for (u32 j = 0; j < CH; ++j)
                 if (i + j < nblk) f(i + j, cur[j]);
         }
 #pragma unroll
-        for (u32 j = 0; j < ROW_CH; ++j) cur[j] = nxt[j];
+        for (u32 j = 0; j < CH; ++j) cur[j] = nxt[j];
     }
 }
 

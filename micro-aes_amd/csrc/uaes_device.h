@@ -163,6 +163,15 @@ int uaesk_gcmsiv_long(void *stream, const uaesk_tables *tb, int nr, const uaesk_
                       const uint8_t *nonce12, const void *aad, size_t aad_len,
                       const void *in, size_t len, void *out, void *scratch, int *status);
 
+/* Batch: nmsg GCM-SIV records under one MASTER key, sixteen lanes per record (k_gcmsiv_batch, uaes_gcmsiv_batch.hip); all
+ * device pointers.  Record m: text at in / out + m msg_bytes (msg_bytes <= UAES_GCMSIV_BATCH_MAX), its first lens[m]
+ * bytes (lens NULL: msg_bytes), nonce at nonces + 12 m, AAD at aad + m aad_bytes (<= UAES_GCMSIV_BATCH_MAX), tag at
+ * tags + 16 m.  The per-nonce keys are derived and expanded in the kernel.  decrypt writes verdicts[m] (1 = authentic)
+ * and ORs 1 into *bad for a forgery, whose output stays as decrypted or is zeroed when wipe != 0. */
+int uaesk_gcmsiv_batch(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *master_ek, int decrypt, int wipe,
+                       const void *nonces, const void *aad, size_t aad_bytes, size_t nmsg, size_t msg_bytes,
+                       const void *lens, const void *in, void *out, void *tags, void *verdicts, int *bad);
+
 /* GHASH only: gh = GHASH_H(aad, ct) with H given (device), for tests.      */
 int uaesk_ghash(void *stream, const uaesk_tables *tb, const uint8_t *H_host,
                 const void *aad, size_t aad_len, const void *ct, size_t ct_len,

@@ -87,22 +87,6 @@ __device__ __forceinline__ u32 pad_col(u32 s, u32 c)
     return (s >> 2) == c ? 0x80u << (8u * (s & 3u)) : 0u;
 }
 
-/* bytes of column c below n */
-__device__ __forceinline__ u32 keep_col(u32 n, u32 c)
-{
-    return n >= 4u * c + 4u ? 0xffffffffu : n <= 4u * c ? 0u : (1u << (8u * (n - 4u * c))) - 1u;
-}
-
-/* the first n bytes of the block whose column words the row holds -> p (one lane per column of the row stores) */
-__device__ __forceinline__ void row_put(unsigned char *p, u32 w, u32 n, u32 c)
-{
-    if (threadIdx.x & 3u) return;
-    if (n >= 16 && (((uintptr_t)p) & 3u) == 0) { ((u32 *)p)[c] = w; return; }
-#pragma unroll
-    for (u32 k = 0; k < 4; ++k)
-        if (4u * c + k < n) p[4u * c + k] = (unsigned char)(w >> (8u * k));
-}
-
 /* K1 = 2 Enc(0), K2 = 4 Enc(0) (getSubkeys :593-605): this lane's columns */
 template <int NR>
 __device__ __forceinline__ void cmac_subkeys(const RowLane<NR> &L, u32 &k1c, u32 &k2c)
@@ -269,7 +253,7 @@ __device__ __forceinline__ u32 eax_text_enc(const uaesk_ctr &ctr, const unsigned
         ks = ctr_col(ctr, i + 1, L.c);
         row_encrypt2<NR>(m, ks, L, L);
     });
-    const u32 y = (row_load(in + 16 * full, s, L.c) ^ ks) & keep_col(s, L.c);
+    const u32 y = (row_load(in + 16 * full, s, L.c) ^ ks) & row_keep(s, L.c);
     row_put(out + 16 * full, y, s, L.c);
     return row_encrypt<NR>(m ^ y ^ (s < 16 ? pad_col(s, L.c) ^ k2c : k1c), L);
 }
@@ -296,11 +280,11 @@ __device__ __forceinline__ u32 s2v_text_dec(const uaesk_ctr &ctr, const unsigned
         row_put(out + 16 * lead, pa, 16, c);
         const u32 r = (u32)(len % 16);
         if (r) {
-            pb = (row_load(in + 16 * (lead + 1), r, c) ^ row_encrypt<NR>(ctr_col(ctr, lead + 1, c), Lc)) & keep_col(r, c);
+            pb = (row_load(in + 16 * (lead + 1), r, c) ^ row_encrypt<NR>(ctr_col(ctr, lead + 1, c), Lc)) & row_keep(r, c);
             row_put(out + 16 * (lead + 1), pb, r, c);
         }
     } else if (len) {
-        pb = (row_load(in, len, c) ^ ks) & keep_col((u32)len, c);
+        pb = (row_load(in, len, c) ^ ks) & row_keep((u32)len, c);
         row_put(out, pb, (u32)len, c);
     }
     return s2v_finish<NR>(m, len, pa, pb, y, Ls, k1c, k2c);

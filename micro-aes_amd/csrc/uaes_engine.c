@@ -1475,6 +1475,14 @@ const char *uaes_debug_plan_ff3(int dir, unsigned radix, size_t len, size_t nrec
     if (out) { out[0] = p.launches; out[1] = (int)p.grid; out[2] = (int)p.steps; }
     return uaesk_ff3_arrangement_name(p.arrangement);
 }
+const char *uaes_debug_plan_gcmsiv_batch(int dir, size_t len, size_t nmsg, int out[3])
+{
+    uaes_plan p;
+    memset(&p, 0, sizeof p);
+    if (uaesk_plan_gcmsiv_batch(dir, len, nmsg, &p)) return NULL;
+    if (out) { out[0] = p.launches; out[1] = (int)p.grid; out[2] = (int)p.steps; }
+    return uaesk_gcmsiv_batch_arrangement_name(p.arrangement);
+}
 void uaes_debug_plan_disable(unsigned mask) { uaesk_plan_disable(mask); }
 
 /* ---- test hooks of the one-launch GCM arrangements (include/uaes_hip.h) ---- */

@@ -837,6 +837,67 @@ int uaes_ccm_decrypt_batch(int keybits, const uint8_t *key, size_t nonceLen, siz
                      (uint8_t *)tags, verdicts);
 }
 
+/* GCM-SIV batches (k_gcmsiv_batch, uaes_gcmsiv_batch.hip): as ccm_batch with 12-byte nonces and 16-byte tags.  `key` is
+ * the MASTER key: only its schedule is made here, every record derives and expands its own keys in the kernel.  Like
+ * the reference's GCM-SIV a decryption writes the text before it knows the tag.  Every argument is checked before the
+ * device is touched. */
+static int gcmsiv_batch(int decrypt, int keybits, const uint8_t *key, size_t nmsg, size_t msg_bytes, const uint32_t *lens,
+                        const uint8_t *nonces, const void *aData, size_t aad_bytes, const void *in, void *outp,
+                        uint8_t *tags, uint8_t *verdicts)
+{
+    context *c;
+    lane *L;
+    keysched ks;
+    const size_t lim = (size_t)-1 / 8;               /* five side arrays and their padding still add up */
+    int rc, bad;
+    if (msg_bytes > UAES_GCMSIV_BATCH_MAX)
+        return fail(UAES_E_ARG, "a GCM-SIV batch record holds at most %zu bytes (got %zu)", (size_t)UAES_GCMSIV_BATCH_MAX, msg_bytes);
+    if (aad_bytes > UAES_GCMSIV_BATCH_MAX)
+        return fail(UAES_E_ARG, "a GCM-SIV batch record takes at most %zu bytes of AAD (got %zu)", (size_t)UAES_GCMSIV_BATCH_MAX, aad_bytes);
+    if (nmsg > lim / (msg_bytes > 16 ? msg_bytes : 16) || (aad_bytes && nmsg > lim / aad_bytes))
+        return fail(UAES_E_ARG, "batch size overflows");
+    if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
+    if (nmsg == 0) { burn(&ks, sizeof ks); return 0; }
+    {
+        const size_t total = nmsg * msg_bytes;
+        if ((total && (!in || !outp)) || !nonces || !tags || (decrypt && !verdicts) || (aad_bytes && !aData)) {
+            burn(&ks, sizeof ks);
+            return fail(UAES_E_ARG, "NULL pointer");
+        }
+        if ((rc = enter(&c, &L)) != 0) { burn(&ks, sizeof ks); return rc; }
+        enum { NONCES, AAD, LENS, TAGS, VERDICTS, NSIDE };
+        row_array a[NSIDE] = { { nonces, nmsg * 12, 0, NULL }, { aData, nmsg * aad_bytes, 0, NULL },
+                               { lens, lens ? nmsg * sizeof *lens : 0, 0, NULL }, { tags, nmsg * 16, !decrypt, NULL },
+                               { verdicts, decrypt ? nmsg : 0, 1, NULL } };
+        row_text t = { in, outp, total, total, lens != NULL, NULL, NULL };
+        if ((rc = row_stage(L, a, NSIDE, decrypt)) != 0) goto out;
+        if ((rc = row_texts(L, &t)) != 0) goto out;
+        ES_KCHK("gcm-siv batch", uaesk_gcmsiv_batch(L->stream, &c->tb, ks.nr, &ks.ek, decrypt, wipe_on_auth_failure(),
+                                                    a[NONCES].d, a[AAD].d, aad_bytes, nmsg, msg_bytes, a[LENS].d, t.d_in,
+                                                    t.d_out, a[TAGS].d, a[VERDICTS].d, L->d_status));
+        if ((rc = row_finish(L, &t, a, NSIDE, decrypt, &bad)) != 0) goto out;
+        rc = bad ? UAES_E_AUTHENTICATION : 0;
+    }
+out:
+    burn(&ks, sizeof ks);
+    DONE(L, rc);
+}
+
+int uaes_gcmsiv_encrypt_batch(int keybits, const uint8_t *key, size_t nmsg, size_t msg_bytes, const uint32_t *lens,
+                              const uint8_t *nonces, const void *aData, size_t aad_bytes,
+                              const void *pntxt, void *crtxt, uint8_t *tags)
+{
+    return gcmsiv_batch(0, keybits, key, nmsg, msg_bytes, lens, nonces, aData, aad_bytes, pntxt, crtxt, tags, NULL);
+}
+
+int uaes_gcmsiv_decrypt_batch(int keybits, const uint8_t *key, size_t nmsg, size_t msg_bytes, const uint32_t *lens,
+                              const uint8_t *nonces, const void *aData, size_t aad_bytes,
+                              const void *crtxt, const uint8_t *tags, void *pntxt, uint8_t *verdicts)
+{
+    return gcmsiv_batch(1, keybits, key, nmsg, msg_bytes, lens, nonces, aData, aad_bytes, crtxt, pntxt, (uint8_t *)tags,
+                        verdicts);
+}
+
 /* ------------------------------------------------------------------------ */
 /* CBC / CFB / OFB                                   */
 /* ------------------------------------------------------------------------ */

@@ -297,22 +297,6 @@ __global__ __launch_bounds__(64) void k_ccm(uaesk_rk rk, uaesk_tables tb, uint4 
 
 /* ---- batches: nmsg CCM records under one key, sixteen lanes per record, four records per wave ---------------------- */
 
-/* bytes of column c below n */
-__device__ __forceinline__ u32 ccm_keep(u32 n, u32 c)
-{
-    return n >= 4u * c + 4u ? 0xffffffffu : n <= 4u * c ? 0u : (1u << (8u * (n - 4u * c))) - 1u;
-}
-
-/* the first n bytes of the block whose column words the row holds -> p (one lane per column of the row stores) */
-__device__ __forceinline__ void ccm_put(unsigned char *p, u32 w, u32 n, u32 c)
-{
-    if (threadIdx.x & 3u) return;
-    if (n >= 16 && (((uintptr_t)p) & 3u) == 0) { ((u32 *)p)[c] = w; return; }
-#pragma unroll
-    for (u32 k = 0; k < 4; ++k)
-        if (4u * c + k < n) p[4u * c + k] = (unsigned char)(w >> (8u * k));
-}
-
 /* this lane's column of A_j: A0 with the counter j in bytes 14..15 (a text of at most UAES_CCM_BATCH_MAX bytes has at
  * most 4096 blocks, so the reference's 56-bit increment of bytes 9..15 never leaves them, whatever the nonce length) */
 __device__ __forceinline__ u32 ccm_a_col(u32 a0c, u32 j, u32 c)
@@ -382,21 +366,21 @@ __global__ __launch_bounds__(UAES_WG) void k_ccm_batch(uaesk_rk rk, uaesk_tables
         });
         if (rem) {                                     /* the partial last block: zero padded into the MAC, cut in the output */
             const u32 x = row_load(src + 16 * (u64)full, rem, c);
-            const u32 y = (x ^ ks) & ccm_keep(rem, c);
-            ccm_put(dst + 16 * (u64)full, y, rem, c);
+            const u32 y = (x ^ ks) & row_keep(rem, c);
+            row_put(dst + 16 * (u64)full, y, rem, c);
             mc ^= DEC ? y : x;
             ks = a0c;
             row_encrypt2<NR>(mc, ks, L, L);
         }
         const u32 t = mc ^ ks;                         /* tag = CBC-MAC ^ Enc(A0) */
         if (!DEC) {
-            ccm_put(tg, t, tag_len, c);
+            row_put(tg, t, tag_len, c);
         } else {
-            const u32 d = (t ^ row_load(tg, tag_len, c)) & ccm_keep(tag_len, c);
+            const u32 d = (t ^ row_load(tg, tag_len, c)) & row_keep(tag_len, c);
             const bool forged = row_any(d != 0u);
             row_verdict((threadIdx.x & 15u) == 0, verdicts, m, !forged, bad);
             if (forged && wipe)
-                for (u32 i = 0; i < len; i += 16) ccm_put(dst + i, 0u, len - i < 16u ? len - i : 16u, c);
+                for (u32 i = 0; i < len; i += 16) row_put(dst + i, 0u, len - i < 16u ? len - i : 16u, c);
         }
     }
 }

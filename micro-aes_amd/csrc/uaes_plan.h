@@ -31,6 +31,7 @@
  *   SIV   SIV_SMALL             k_siv_small                                         (1)    <= 2046 POLYVAL positions
  *         SIV_CHUNKS            k_siv_prep, hash-only k_gcm_chunks<FOLD>, k_ctr*    (3)    <= 512 MiB
  *         SIV_LEVELS            k_siv_prep, k_ghash_pass.., k_siv_tag, k_ctr*       (4-6)  beyond
+ *         gcmsiv.batch          k_gcmsiv_batch (sixteen lanes per record, four per wave) (1)  uaes_gcmsiv_*_batch, records <= UAES_GCMSIV_BATCH_MAX (65535 B)
  *   POLY  poly.small            k_poly_small (one workgroup, AES_k(nonce) inside)   (1)    one message <= UAES_POLY_SMALL_MAX (128 KiB)
  *         poly.chunks           k_poly_chunks, k_poly_fold (+ AES_k(nonce))         (2)    one message beyond
  *         poly.batch            k_poly_batch (one wave per message)                 (1)    uaes_poly1305_batch
@@ -66,8 +67,9 @@
  * uaesk_plan_kw (uaes_kw.hip; uaes_debug_plan_kw), and tests/test_gpu_kw.py finds its two boundaries by walking it.
  * FF1 has uaesk_plan_ff1 (uaes_ff1.hip; uaes_debug_plan_ff1); tests/test_gpu_ff1.py walks it likewise.
  * FF3-1 has uaesk_plan_ff3 (uaes_ff3.hip; uaes_debug_plan_ff3): one row, whose limits depend on the radix.
- * The rows that say "sixteen lanes per record / message" -- eax.batch, s2v.batch, ccm.batch, batch.row, kw.batch,
- * ff1.batch, ff3.batch -- are the row batches: grid and threads per workgroup are uaesk_row_shape's (uaes_launch.hip.h), the same
+ * The GCM-SIV batches have uaesk_plan_gcmsiv_batch (uaes_gcmsiv_batch.hip; uaes_debug_plan_gcmsiv_batch): one row.
+ * The rows that say "sixteen lanes per record / message" -- eax.batch, s2v.batch, ccm.batch, gcmsiv.batch, batch.row,
+ * kw.batch, ff1.batch, ff3.batch -- are the row batches: grid and threads per workgroup are uaesk_row_shape's (uaes_launch.hip.h), the same
  * for the same number of records in every one of them.
  */
 #ifndef UAES_PLAN_H
@@ -215,6 +217,17 @@ const char *uaesk_ff1_arrangement_name(int id);
 enum uaes_ff3_arrangement { UAES_FF3_BATCH = 0 };
 int uaesk_plan_ff3(int dir, unsigned radix, size_t len, size_t nrec, uaes_plan *p);
 const char *uaesk_ff3_arrangement_name(int id);
+
+/* The batches of GCM-SIV records (RFC 8452; uaes_gcmsiv_batch.hip).  dir: 0 encrypt, 1 decrypt; len = bytes per record,
+ * nmsg = records; one arrangement, a row batch at any number of records.  A record is a serial POLYVAL chain and a
+ * serial keystream on sixteen lanes, with a key derivation and a key expansion of its own in front: it is at most
+ * UAES_GCMSIV_BATCH_MAX bytes (the same number as UAES_CCM_BATCH_MAX, and the most AAD a record takes); beyond it the
+ * one-message arrangements above (SIV_CHUNKS from 32 736 B) are the right tool.  grid = workgroups, steps = threads
+ * per workgroup.  Returns a HIP error code for a dir other than 0 / 1 or a length above the limit. */
+#define UAES_GCMSIV_BATCH_MAX ((size_t)65535)
+enum uaes_gcmsiv_batch_arrangement { UAES_GCMSIV_BATCH = 0 };
+int uaesk_plan_gcmsiv_batch(int dir, size_t len, size_t nmsg, uaes_plan *p);
+const char *uaesk_gcmsiv_batch_arrangement_name(int id);
 
 #ifdef __cplusplus
 }

@@ -77,6 +77,11 @@ print("CCM batches: a record holds at most UAES_CCM_BATCH_MAX = %d bytes of text
 walk("CCM batch, k records of 64 bytes (positions/thread: threads per workgroup)",
      lambda k: ccm_batch_plan(k)[:2] + (0, ccm_batch_plan(k)[3]), 1, 1 << 20, 1,
      lambda k: "%9d records (%9.3f MiB)" % (k, k * 64 / MIB))
+top = max(n for n in range(65000, 66000) if uaes.gcmsiv_batch_plan(n, 2) is not None)
+print("GCM-SIV batches: a record holds at most UAES_GCMSIV_BATCH_MAX = %d bytes of text" % top)
+walk("GCM-SIV batch, k records of 64 bytes (positions/thread: threads per workgroup)",
+     lambda k: uaes.gcmsiv_batch_plan(64, max(k, 1))[:2] + (0, uaes.gcmsiv_batch_plan(64, max(k, 1))[3]), 1, 1 << 20, 1,
+     lambda k: "%9d records (%9.3f MiB)" % (k, k * 64 / MIB))
 for dec in (False, True):
     walk("KW %s, one secret of n bytes" % ("unwrap" if dec else "wrap"),
          lambda n: uaes.kw_plan(max(n, 16), unwrap=dec)[:2] + (0, 0), 16, 64 * MIB, 8)
