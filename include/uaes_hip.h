@@ -797,6 +797,14 @@ const char *uaes_debug_plan_ff3(int dir, unsigned radix, size_t len, size_t nrec
  * threads as "ccm.batch" for the same number of records), or NULL for a dir other than 0 / 1 or a length above
  * UAES_GCMSIV_BATCH_MAX.  Works without a device (a 256-CU MI355X). */
 const char *uaes_debug_plan_gcmsiv_batch(int dir, size_t len, size_t nmsg, int out[3]);
+/* The launch shape of OCB (csrc/uaes_plan.h, uaesk_plan_ocb_shape): dir 0 encrypt / 1 decrypt; len / aad_len = bytes of
+ * text / of associated data; aad_aligned = whether the associated data starts at a multiple of 16 bytes in device
+ * memory.  Returns "ocb.small" (one workgroup; out untouched) or "ocb.runs", for which out (may be NULL) receives
+ * { run, run_aad, threads per workgroup, workgroups, hash_blocks }: the consecutive 256-block chunks a wave takes at
+ * once over the text and over long associated data, and the whole blocks of associated data that all workgroups hash
+ * (0: one workgroup hashes all of it -- short, or not aligned; INT_MAX from 32 GiB on).  NULL for a dir other than 0 / 1.  Works without a
+ * device (a 256-CU MI355X).  tests/test_gpu_ocb.py finds the first text of every run length by walking this. */
+const char *uaes_debug_plan_ocb(int dir, size_t len, size_t aad_len, int aad_aligned, int out[5]);
 
 /* Test hooks of the one-launch GCM / GCM-SIV / streamed-piece arrangements (chunk workgroups + one preparing workgroup
  * in ONE launch; whoever of them arrives last on a counter word folds the chunk hashes and makes the tag -- nobody

@@ -43,7 +43,7 @@ EXPORTS = [
     "uaes_ocb_encrypt_ex", "uaes_ocb_decrypt_ex",
     "uaes_cmac", "uaes_ccm_encrypt", "uaes_ccm_decrypt", "uaes_gcmsiv_encrypt", "uaes_gcmsiv_decrypt",
     "uaes_gcmsiv_encrypt_batch", "uaes_gcmsiv_decrypt_batch", "uaes_debug_plan_gcmsiv_batch",
-    "uaes_ocb_encrypt", "uaes_ocb_decrypt", "uaes_ocb_dev",
+    "uaes_ocb_encrypt", "uaes_ocb_decrypt", "uaes_ocb_dev", "uaes_debug_plan_ocb",
     "uaes_poly1305", "uaes_poly1305_dev", "uaes_poly1305_batch", "uaes_debug_plan_poly1305",
     "uaes_eax_encrypt", "uaes_eax_decrypt", "uaes_siv_encrypt", "uaes_siv_decrypt",
     "uaes_eax_encrypt_batch", "uaes_eax_decrypt_batch", "uaes_siv_encrypt_batch", "uaes_siv_decrypt_batch",
@@ -177,6 +177,8 @@ def engine():
     L.uaes_kw_unwrap_batch.argtypes = [i, vp, sz, sz, vp, vp, vp]
     L.uaes_debug_plan_kw.argtypes = [i, sz, sz, C.POINTER(C.c_int)]
     L.uaes_debug_plan_kw.restype = C.c_char_p
+    L.uaes_debug_plan_ocb.argtypes = [i, sz, sz, i, C.POINTER(C.c_int)]
+    L.uaes_debug_plan_ocb.restype = C.c_char_p
     for n in ("uaes_ff1_encrypt", "uaes_ff1_decrypt"):
         getattr(L, n).argtypes = [i, vp, C.c_uint, vp, vp, sz, vp, sz, vp]
     for n in ("uaes_ff1_encrypt_batch", "uaes_ff1_decrypt_batch"):
@@ -258,7 +260,7 @@ def engine():
         if n not in ("uaes_last_error", "uaes_version", "uaes_gcm_key_free", "uaes_gcm_stream_abort", "uaes_debug_gather_stats", "uaes_debug_gcm_look",
                      "uaes_debug_arrangement_name", "uaes_debug_plan_disable", "uaes_debug_plan_poly1305",
                      "uaes_debug_plan_eax_siv", "uaes_debug_plan_chain", "uaes_debug_plan_kw", "uaes_debug_plan_ff1",
-                     "uaes_debug_plan_ff3", "uaes_ff3_maxlen", "uaes_debug_plan_gcmsiv_batch"):
+                     "uaes_debug_plan_ff3", "uaes_ff3_maxlen", "uaes_debug_plan_gcmsiv_batch", "uaes_debug_plan_ocb"):
             getattr(L, n).restype = i
     _lib = L
     return L
@@ -1265,6 +1267,17 @@ def plan(mode, a, b=0, direction=0, flags=0, counter=None):
         _check(engine().uaes_debug_plan_at(MODES[mode], direction, a, b, flags, _fixed(counter, 16, "counter"), out),
                "uaes_debug_plan_at")
     return engine().uaes_debug_arrangement_name(out[0]).decode(), out[1], out[2], out[3]
+
+
+def plan_ocb(length, aad_len=0, decrypt=False, aad_aligned=True):
+    """The launch shape of an OCB call in the runs arrangement (uaes_debug_plan_ocb): (run, run_aad, threads per
+    workgroup, workgroups, hash_blocks) -- the chunks a wave takes at once over the text / over long associated data,
+    and the whole blocks of associated data that all workgroups hash.  None where the call is "ocb.small"."""
+    out = (C.c_int * 5)()
+    name = engine().uaes_debug_plan_ocb(int(bool(decrypt)), length, aad_len, int(bool(aad_aligned)), out)
+    if name is None:
+        raise ValueError("no OCB plan for these arguments")
+    return tuple(out) if name == b"ocb.runs" else None
 
 
 def arrangement_id(name):

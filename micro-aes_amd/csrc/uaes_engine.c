@@ -1483,6 +1483,18 @@ const char *uaes_debug_plan_gcmsiv_batch(int dir, size_t len, size_t nmsg, int o
     if (out) { out[0] = p.launches; out[1] = (int)p.grid; out[2] = (int)p.steps; }
     return uaesk_gcmsiv_batch_arrangement_name(p.arrangement);
 }
+const char *uaes_debug_plan_ocb(int dir, size_t len, size_t aad_len, int aad_aligned, int out[5])
+{
+    uaes_plan p;
+    int shape[5];
+    memset(&p, 0, sizeof p);
+    if (uaesk_plan(UAES_PLAN_OCB, dir, len, aad_len, 0, &p)) return NULL;
+    if (p.arrangement == UAES_ARR_OCB_RUNS) {
+        if (uaesk_plan_ocb_shape(dir, len, aad_len, aad_aligned, shape)) return NULL;
+        if (out) memcpy(out, shape, sizeof shape);
+    }
+    return uaesk_arrangement_name(p.arrangement);
+}
 void uaes_debug_plan_disable(unsigned mask) { uaesk_plan_disable(mask); }
 
 /* ---- test hooks of the one-launch GCM arrangements (include/uaes_hip.h) ---- */

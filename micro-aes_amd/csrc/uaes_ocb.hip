@@ -679,24 +679,22 @@ int uaesk_plan_ocb(int dir, size_t len, size_t aad_len, uaes_plan *p)
     return 0;
 }
 
-template <int NR>
-static int launch_ocb(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *ek, const uaesk_rk *dk,
-                      int decrypt, uint4 nb, u32 bottom, u32 tag_len, const void *aad, size_t aad_len,
-                      const void *in, size_t len, void *out, void *scratch, unsigned *done_word, int *status)
+/* The launch shape of the runs arrangement (k_ocb): the chunks per run of the walk over the text and of the walk over
+ * long associated data, threads per workgroup, workgroups, and the whole blocks of associated data that all
+ * workgroups hash (0: the finishing workgroup hashes all of it).  The one place that decides them: launch_ocb
+ * launches what this answers, and uaesk_plan_ocb_shape hands the same answer to the tests. */
+struct OcbShape {
+    u32 run, run_aad;
+    unsigned wg;
+    u64 grid, hash_blocks;
+};
+
+static OcbShape ocb_shape(u64 len, u64 aad_len, bool aad_aligned)
 {
-    const uaesk_rk &k2 = decrypt ? *dk : *ek;
     const unsigned cus = uaesk_cus_or_256();
-    /* one launch either way, which can carry the call's completion ticket (a decryption's status word must then
-     * be host-visible: the host layer arms a ticket only when it passes a pinned status pointer) */
-    const uaesk_done done = uaesk_ticket_take();
-    if (plan_ocb(len, aad_len).arrangement == UAES_ARR_OCB_SMALL) {         /* short message: one workgroup */
-        return with_bool(decrypt, [&](auto DEC) {
-            return uaesk_launch(k_ocb_small<NR, decltype(DEC)::value>, 1, UAES_WG, OCB_SMALL_LDS, st, *ek, k2, *tb, nb, bottom, aad,
-                                aad_len, in, out, len, status, tag_len, done); });
-    }
     const u64 nblocks = len >> 4;
     /* long associated data (whole blocks, 16-byte aligned) is hashed by all workgroups as a second walk */
-    const u64 hblocks = ((u64)(aad_len >> 4) >= OCB_HASH_SPREAD && ((uintptr_t)aad & 15u) == 0) ? (u64)(aad_len >> 4) : 0;
+    const u64 hblocks = ((u64)(aad_len >> 4) >= OCB_HASH_SPREAD && aad_aligned) ? (u64)(aad_len >> 4) : 0;
     unsigned wg = 256u;
     u64 grid = 1;
     u32 runs_of[2] = { 1, 1 };
@@ -721,15 +719,45 @@ static int launch_ocb(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *ek
     }
     if (grid > cus) grid = cus;
     if (grid > OCB_MAX_WGS) grid = OCB_MAX_WGS;
-    const u32 run = runs_of[0];
+    const OcbShape s = { runs_of[0], runs_of[1], wg, grid, hblocks };
+    return s;
+}
+
+/* out = { run, run_aad, threads per workgroup, workgroups, hash_blocks }.  Returns 0 for the runs arrangement, 1 (and
+ * leaves out alone) where the call is k_ocb_small's, a HIP error code for a dir other than 0 / 1. */
+extern "C" int uaesk_plan_ocb_shape(int dir, size_t len, size_t aad_len, int aad_aligned, int out[5])
+{
+    if (dir < 0 || dir > 1) return (int)hipErrorInvalidValue;
+    if (plan_ocb(len, aad_len).arrangement == UAES_ARR_OCB_SMALL) return 1;
+    const OcbShape s = ocb_shape(len, aad_len, aad_aligned != 0);
+    out[0] = (int)s.run; out[1] = (int)s.run_aad; out[2] = (int)s.wg; out[3] = (int)s.grid;
+    out[4] = s.hash_blocks > 0x7fffffffull ? 0x7fffffff : (int)s.hash_blocks;    /* 32 GiB of associated data and more */
+    return 0;
+}
+
+template <int NR>
+static int launch_ocb(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *ek, const uaesk_rk *dk,
+                      int decrypt, uint4 nb, u32 bottom, u32 tag_len, const void *aad, size_t aad_len,
+                      const void *in, size_t len, void *out, void *scratch, unsigned *done_word, int *status)
+{
+    const uaesk_rk &k2 = decrypt ? *dk : *ek;
+    /* one launch either way, which can carry the call's completion ticket (a decryption's status word must then
+     * be host-visible: the host layer arms a ticket only when it passes a pinned status pointer) */
+    const uaesk_done done = uaesk_ticket_take();
+    if (plan_ocb(len, aad_len).arrangement == UAES_ARR_OCB_SMALL) {         /* short message: one workgroup */
+        return with_bool(decrypt, [&](auto DEC) {
+            return uaesk_launch(k_ocb_small<NR, decltype(DEC)::value>, 1, UAES_WG, OCB_SMALL_LDS, st, *ek, k2, *tb, nb, bottom, aad,
+                                aad_len, in, out, len, status, tag_len, done); });
+    }
+    const OcbShape s = ocb_shape(len, aad_len, ((uintptr_t)aad & 15u) == 0);
     OcbArgs ka;
     ka.ek = *ek; ka.dk = k2; ka.tb = *tb; ka.nonce_block = nb; ka.scr = (uint4 *)scratch; ka.done_word = done_word;
-    ka.nblocks = nblocks; ka.aad_len = aad_len; ka.len = len; ka.aad = (const unsigned char *)aad;
-    ka.hash_blocks = hblocks; ka.run_aad = runs_of[1];
+    ka.nblocks = len >> 4; ka.aad_len = aad_len; ka.len = len; ka.aad = (const unsigned char *)aad;
+    ka.hash_blocks = s.hash_blocks; ka.run_aad = s.run_aad;
     ka.in = (const unsigned char *)in; ka.out = (unsigned char *)out; ka.status = status;
-    ka.bottom = bottom; ka.run = run; ka.tag_len = tag_len; ka.done = done;
+    ka.bottom = bottom; ka.run = s.run; ka.tag_len = tag_len; ka.done = done;
     return with_bool(decrypt, [&](auto DEC) {
-        return uaesk_launch(k_ocb<NR, decltype(DEC)::value>, (unsigned)grid, wg, OCB_LDS, st, ka); });
+        return uaesk_launch(k_ocb<NR, decltype(DEC)::value>, (unsigned)s.grid, s.wg, OCB_LDS, st, ka); });
 }
 
 extern "C" size_t uaesk_ocb_scratch_bytes(void) { return 16u * (OCB_ROW_HASH + OCB_MAX_WGS); }

@@ -68,6 +68,8 @@
  * FF1 has uaesk_plan_ff1 (uaes_ff1.hip; uaes_debug_plan_ff1); tests/test_gpu_ff1.py walks it likewise.
  * FF3-1 has uaesk_plan_ff3 (uaes_ff3.hip; uaes_debug_plan_ff3): one row, whose limits depend on the radix.
  * The GCM-SIV batches have uaesk_plan_gcmsiv_batch (uaes_gcmsiv_batch.hip; uaes_debug_plan_gcmsiv_batch): one row.
+ * OCB_RUNS is one row whose launch shape moves with the size: uaesk_plan_ocb_shape (uaes_ocb.hip; uaes_debug_plan_ocb),
+ * and tests/test_gpu_ocb.py takes its sizes from walking it.
  * The rows that say "sixteen lanes per record / message" -- eax.batch, s2v.batch, ccm.batch, gcmsiv.batch, batch.row,
  * kw.batch, ff1.batch, ff3.batch -- are the row batches: grid and threads per workgroup are uaesk_row_shape's (uaes_launch.hip.h), the same
  * for the same number of records in every one of them.
@@ -136,6 +138,16 @@ int uaesk_plan(int mode, int dir, size_t a, size_t b, unsigned flags, uaes_plan 
 int uaesk_plan_at(int mode, int dir, size_t a, size_t b, unsigned flags, const uint8_t *counter16, uaes_plan *p);
 
 const char *uaesk_arrangement_name(int id);
+
+/* OCB's runs arrangement answers ("ocb.runs", 1, 0, 0) at every size; the shape k_ocb is launched with is a table of
+ * its own (uaes_ocb.hip's ocb_shape, which launch_ocb launches from; uaes_debug_plan_ocb).  dir: 0 encrypt, 1 decrypt;
+ * aad_aligned: whether the associated data starts at a multiple of 16 bytes in device memory (only then do all
+ * workgroups hash it).  out = { run, run_aad, threads per workgroup, workgroups, hash_blocks }: the consecutive
+ * 256-block chunks a wave takes at once on the walk over the text and on the walk over long associated data (powers
+ * of two up to 16; 1 below 8 runs per wave), and the whole blocks of associated data that walk hashes (0: the finishing
+ * workgroup hashes all of it).  Returns 0, or 1 with out untouched where the call is OCB_SMALL's, or a HIP error code
+ * for a dir other than 0 / 1.  tests/test_gpu_ocb.py finds the first text of every run length by walking this. */
+int uaesk_plan_ocb_shape(int dir, size_t len, size_t aad_len, int aad_aligned, int out[5]);
 
 /* Poly1305-AES: len = bytes of one message; nmsg >= 2 = a batch of nmsg messages of len bytes each (nmsg 0 / 1: the
  * one-message calls).  grid = workgroups of the main kernel, steps = blocks per thread (at most). */

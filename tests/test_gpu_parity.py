@@ -1626,7 +1626,9 @@ def test_C4_gcm128_1GiB_device_resident(orc, golden_dir):
 def test_large_single_calls_against_the_oracle(orc):
     """the largest texts the oracle still finishes in seconds: one XTS data unit of 192 MiB (+ a ragged
     end: 12288 groups of 64 chunk tweaks from the parallel expansion, then ciphertext stealing) and one
-    OCB text of 128 MiB (offsets up to L_23, every run length)"""
+    OCB text of 128 MiB: offsets up to L_23 and many chunks per wave, but on a 256-CU device runs of ONE chunk (since the
+    rule became "at least 8 runs per wave", runs of 2 .. 16 chunks begin at 256 MiB .. 2 GiB), so the stepped chunk mask
+    and the interleaving of the runs are not reached here: tests/test_gpu_ocb.py runs every run length at its real size"""
     import hashlib
     import torch
 
