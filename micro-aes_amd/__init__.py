@@ -41,6 +41,7 @@ EXPORTS = [
     "uaes_gcm_encrypt_ex", "uaes_gcm_decrypt_ex", "uaes_ccm_encrypt_ex", "uaes_ccm_decrypt_ex",
     "uaes_ccm_encrypt_batch", "uaes_ccm_decrypt_batch",
     "uaes_ocb_encrypt_ex", "uaes_ocb_decrypt_ex",
+    "uaes_ocb_encrypt_batch", "uaes_ocb_decrypt_batch", "uaes_debug_plan_ocb_batch",
     "uaes_cmac", "uaes_ccm_encrypt", "uaes_ccm_decrypt", "uaes_gcmsiv_encrypt", "uaes_gcmsiv_decrypt",
     "uaes_gcmsiv_encrypt_batch", "uaes_gcmsiv_decrypt_batch", "uaes_debug_plan_gcmsiv_batch",
     "uaes_ocb_encrypt", "uaes_ocb_decrypt", "uaes_ocb_dev", "uaes_debug_plan_ocb",
@@ -160,6 +161,10 @@ def engine():
     L.uaes_eax_decrypt_batch.argtypes = [i, vp, sz, sz, vp, sz, vp, sz, vp, vp, vp, vp]
     L.uaes_ccm_encrypt_batch.argtypes = [i, vp, sz, sz, sz, sz, vp, vp, vp, sz, vp, vp, vp]
     L.uaes_ccm_decrypt_batch.argtypes = [i, vp, sz, sz, sz, sz, vp, vp, vp, sz, vp, vp, vp, vp]
+    L.uaes_ocb_encrypt_batch.argtypes = [i, vp, sz, sz, sz, sz, vp, vp, vp, sz, vp, vp, vp]
+    L.uaes_ocb_decrypt_batch.argtypes = [i, vp, sz, sz, sz, sz, vp, vp, vp, sz, vp, vp, vp, vp]
+    L.uaes_debug_plan_ocb_batch.argtypes = [i, sz, sz, C.POINTER(C.c_int)]
+    L.uaes_debug_plan_ocb_batch.restype = C.c_char_p
     L.uaes_gcmsiv_encrypt_batch.argtypes = [i, vp, sz, sz, vp, vp, vp, sz, vp, vp, vp]
     L.uaes_gcmsiv_decrypt_batch.argtypes = [i, vp, sz, sz, vp, vp, vp, sz, vp, vp, vp, vp]
     L.uaes_debug_plan_gcmsiv_batch.argtypes = [i, sz, sz, C.POINTER(C.c_int)]
@@ -260,7 +265,8 @@ def engine():
         if n not in ("uaes_last_error", "uaes_version", "uaes_gcm_key_free", "uaes_gcm_stream_abort", "uaes_debug_gather_stats", "uaes_debug_gcm_look",
                      "uaes_debug_arrangement_name", "uaes_debug_plan_disable", "uaes_debug_plan_poly1305",
                      "uaes_debug_plan_eax_siv", "uaes_debug_plan_chain", "uaes_debug_plan_kw", "uaes_debug_plan_ff1",
-                     "uaes_debug_plan_ff3", "uaes_ff3_maxlen", "uaes_debug_plan_gcmsiv_batch", "uaes_debug_plan_ocb"):
+                     "uaes_debug_plan_ff3", "uaes_ff3_maxlen", "uaes_debug_plan_gcmsiv_batch", "uaes_debug_plan_ocb",
+                     "uaes_debug_plan_ocb_batch"):
             getattr(L, n).restype = i
     _lib = L
     return L
@@ -682,6 +688,48 @@ def gcmsiv_batch_plan(length, nmsg, decrypt=False):
     launches, workgroups, threads per workgroup), or None for arguments that make no sense."""
     out = (C.c_int * 3)()
     name = engine().uaes_debug_plan_gcmsiv_batch(int(bool(decrypt)), length, nmsg, out)
+    return None if name is None else (name.decode(), out[0], out[1], out[2])
+
+
+def ocb_batch(key, nonces, aads, texts, tag_len=16, decrypt=False, tags=None, prefill=0, lens=None):
+    """OCB (RFC 7253) of many records under one key (uaes_ocb_*_batch): equal-sized nonces (1..15 bytes), AADs (or
+    None) and texts.  encrypt: returns (ciphertexts, tag_len-byte tags); decrypt (tags given): returns (code, plaintexts,
+    verdicts); like the reference's OCB a forged record's plaintext is its decryption (zeros under
+    wipe_on_auth_failure).  lens (optional, one per record): record m is the first lens[m] bytes of its text, and the
+    rest of its output slot stays the prefill."""
+    n = len(texts)
+    aads = aads if aads is not None else [b""] * n
+    if len(nonces) != n or len(aads) != n or (decrypt and (tags is None or len(tags) != n)) or (lens is not None and len(lens) != n):
+        raise ValueError("one nonce, AAD (tag and length) per record")
+    if n == 0:
+        return (0, [], []) if decrypt else ([], [])
+    nl, nb = _records(nonces, "nonces")
+    al, ab = _records(aads, "AADs")
+    ml, mb = _records(texts, "texts")
+    lv = (C.c_uint32 * n)(*lens) if lens is not None else None
+    L = engine()
+    o = _out(n * ml, prefill)
+    if not decrypt:
+        t = _out(n * tag_len)
+        _check(L.uaes_ocb_encrypt_batch(_bits(key), _in(key), nl, tag_len, n, ml, lv, _in(nb), _in(ab), al, _in(mb), o, t),
+               "uaes_ocb_encrypt_batch")
+        raw, tr = bytes(o), bytes(t)
+        return _split(raw, ml, n), _split(tr, tag_len, n)
+    if any(len(x) != tag_len for x in tags):
+        raise ValueError("tags of tag_len bytes")
+    v = _out(n)
+    rc = _check(L.uaes_ocb_decrypt_batch(_bits(key), _in(key), nl, tag_len, n, ml, lv, _in(nb), _in(ab), al, _in(mb),
+                                         _in(b"".join(tags)), o, v), "uaes_ocb_decrypt_batch")
+    raw = bytes(o)
+    return rc, _split(raw, ml, n), list(bytes(v)[:n])
+
+
+def ocb_batch_plan(length, nmsg, decrypt=False):
+    """What an OCB batch of nmsg records of `length` bytes would run (uaes_debug_plan_ocb_batch): (arrangement,
+    launches, workgroups, threads per workgroup), or None for arguments that make no sense.  decrypt may also be an
+    int: a direction other than 0 / 1 has no plan."""
+    out = (C.c_int * 3)()
+    name = engine().uaes_debug_plan_ocb_batch(int(decrypt), length, nmsg, out)
     return None if name is None else (name.decode(), out[0], out[1], out[2])
 
 

@@ -959,4 +959,94 @@ __device__ __forceinline__ u32 row_decrypt(u32 w, const RowLane<NR> &L)
     return w;
 }
 
+/* two independent blocks, round by round: the mirror of row_encrypt2 */
+template <int NR>
+__device__ __forceinline__ void row_decrypt2(u32 &a, u32 &b, const RowLane<NR> &La, const RowLane<NR> &Lb)
+{
+    a ^= La.kc[0];
+    b ^= Lb.kc[0];
+    u32 pa = __builtin_amdgcn_perm(a, La.tmain, La.sel), pb = __builtin_amdgcn_perm(b, Lb.tmain, Lb.sel);
+#pragma unroll
+    for (int r = 1; r <= NR; ++r) {
+        u32 ta = lds_word(pa), tb = lds_word(pb);
+        if (r == NR) { ta = __builtin_amdgcn_perm(ta, 0u, La.lsel); tb = __builtin_amdgcn_perm(tb, 0u, Lb.lsel); }
+        const u32 ya = ta ^ row_dpp<0x123>(ta), yb = tb ^ row_dpp<0x123>(tb);
+        const u32 za = ya ^ row_dpp<0x126>(ya), zb = yb ^ row_dpp<0x126>(yb);
+        a = La.kc[r] ^ row_dpp<0x00>(za);
+        b = Lb.kc[r] ^ row_dpp<0x00>(zb);
+        if (r < NR) {
+            pa = __builtin_amdgcn_perm(a, r + 1 < NR ? La.tmain : La.tlast, La.sel);
+            pb = __builtin_amdgcn_perm(b, r + 1 < NR ? Lb.tmain : Lb.tlast, Lb.sel);
+        }
+    }
+}
+
+/* ---- the FORWARD cipher, sixteen lanes per block, through an UNREPLICATED 1 KiB copy of Te0 ----
+ * For the few encryptions a row needs while the row4 region holds the INVERSE tables (a decrypting OCB record: K_top,
+ * HASH, the pad of a ragged block, the tag).  row_encrypt's arrangement and dependency chain; the lookup differs: lane
+ * (c, r) reads Te0[byte r of its column word] and rotates it by its row, T_r = rotl(Te0, 8 r) -- one v_perm and one
+ * shift-add for the address instead of one v_perm, one v_alignbit behind the read.  The last round takes S[x] from
+ * byte 1 of Te0[x] into byte r.  Unlike the row4 tables the plain table is shared by the four rows of a wave and by
+ * the sixteen lanes of a row: lanes that hit the same bank at different entries take turns.                        */
+template <int NR>
+struct RowTe0 {
+    u32 te0;              /* LDS byte address of the table                                          */
+    u32 bsel;             /* v_perm selector: byte r of the column word -> bits 0..7, zeros above    */
+    u32 rot;              /* 8 r                                                                     */
+    u32 lsel;             /* v_perm selector: byte 1 of the lookup -> byte r, zeros elsewhere        */
+    u32 c;                /* this lane's column                                                      */
+    u32 kc[NR + 1];       /* this lane's column of every round key                                   */
+};
+
+/* te0_at / key_at: LDS byte addresses of the 256 words of Te0 and of the 4 (NR + 1) words of the encryption schedule */
+template <int NR>
+__device__ __forceinline__ RowTe0<NR> row_te0_lane(u32 te0_at, u32 key_at)
+{
+    RowTe0<NR> L;
+    const u32 i = threadIdx.x & 15u, r = i & 3u;
+    L.c = i >> 2;
+    L.te0 = te0_at;
+    L.bsel = 0x0c0c0c00u | (4u + r);
+    L.rot = 8u * r;
+    L.lsel = (0x0c0c0c0cu & ~(0xffu << (8u * r))) | (5u << (8u * r));
+#pragma unroll
+    for (int j = 0; j <= NR; ++j) L.kc[j] = lds_word(key_at + 16u * (u32)j + 4u * L.c);
+    return L;
+}
+
+/* w = this lane's column word of the block (no round key applied) -> the same of its encryption */
+template <int NR>
+__device__ __forceinline__ u32 row_encrypt_te0(u32 w, const RowTe0<NR> &L)
+{
+    w ^= L.kc[0];
+#pragma unroll
+    for (int r = 1; r <= NR; ++r) {
+        u32 t = lds_word(L.te0 + (__builtin_amdgcn_perm(w, 0u, L.bsel) << 2));
+        t = r < NR ? rotl32(t, L.rot) : __builtin_amdgcn_perm(t, 0u, L.lsel);
+        const u32 y = t ^ row_dpp<0x12B>(t);          /* as row_encrypt */
+        const u32 z = y ^ row_dpp<0x126>(y);
+        w = L.kc[r] ^ row_dpp<0x00>(z);
+    }
+    return w;
+}
+
+/* two independent blocks, round by round, as row_encrypt2 */
+template <int NR>
+__device__ __forceinline__ void row_encrypt2_te0(u32 &a, u32 &b, const RowTe0<NR> &L)
+{
+    a ^= L.kc[0];
+    b ^= L.kc[0];
+#pragma unroll
+    for (int r = 1; r <= NR; ++r) {
+        u32 ta = lds_word(L.te0 + (__builtin_amdgcn_perm(a, 0u, L.bsel) << 2));
+        u32 tb = lds_word(L.te0 + (__builtin_amdgcn_perm(b, 0u, L.bsel) << 2));
+        if (r < NR) { ta = rotl32(ta, L.rot); tb = rotl32(tb, L.rot); }
+        else { ta = __builtin_amdgcn_perm(ta, 0u, L.lsel); tb = __builtin_amdgcn_perm(tb, 0u, L.lsel); }
+        const u32 ya = ta ^ row_dpp<0x12B>(ta), yb = tb ^ row_dpp<0x12B>(tb);
+        const u32 za = ya ^ row_dpp<0x126>(ya), zb = yb ^ row_dpp<0x126>(yb);
+        a = L.kc[r] ^ row_dpp<0x00>(za);
+        b = L.kc[r] ^ row_dpp<0x00>(zb);
+    }
+}
+
 #endif

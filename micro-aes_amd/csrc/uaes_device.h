@@ -220,6 +220,15 @@ int uaesk_ocb(void *stream, const uaesk_tables *tb, int nr,
               size_t nonce_len, size_t tag_len,
               const void *aad, size_t aad_len, const void *in, size_t len, void *out,
               void *scratch, unsigned *done_word, int *status);
+/* Batch: nmsg records under one key, sixteen lanes per record (k_ocb_batch); all device pointers.  Record m: text at
+ * in / out + m msg_bytes (msg_bytes <= UAES_OCB_BATCH_MAX), its first lens[m] bytes (lens NULL: msg_bytes), nonce at
+ * nonces + m nonce_len (1..15), AAD at aad + m aad_bytes (<= UAES_OCB_BATCH_MAX), tag at tags + m tag_len (1..16).
+ * dk = equivalent-inverse keys (read when decrypting).  decrypt writes verdicts[m] (1 = authentic) and ORs 1 into *bad
+ * for a forgery, whose output stays as decrypted or is zeroed when wipe != 0. */
+int uaesk_ocb_batch(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, const uaesk_rk *dk, int decrypt,
+                    int wipe, const void *nonces, size_t nonce_len, size_t tag_len, const void *aad, size_t aad_bytes,
+                    size_t nmsg, size_t msg_bytes, const void *lens, const void *in, void *out, void *tags,
+                    void *verdicts, int *bad);
 
 /* A ticket can also ride on the call's ONLY kernel (saves the second launch: 8.9 -> 7 us for an empty kernel,
  * tools/ubench/threadfloor.hip).  The host layer arms one for the calling thread right before a kernel-level call

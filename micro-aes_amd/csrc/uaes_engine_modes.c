@@ -1519,6 +1519,71 @@ int uaes_ocb_decrypt(int keybits, const uint8_t *key, const uint8_t *nonce,
     return ocb_common(keybits, key, nonce, 12, 16, 1, aData, aDataLen, crtxt, crtxtLen, pntxt);
 }
 
+/* OCB batches (k_ocb_batch, uaes_ocb.hip): as ccm_batch, with OCB's nonce and tag lengths and both key schedules (a
+ * decrypting record needs the inverse cipher for its text and the forward one for K_top, HASH, the pad and the tag).
+ * Like the reference's OCB a decryption writes the text before it knows the tag.  The batch always runs on the GPU: the
+ * host policy of the one-message calls does not apply.  Every argument is checked before the device is touched. */
+static int ocb_batch(int decrypt, int keybits, const uint8_t *key, size_t nonceLen, size_t tagLen, size_t nmsg,
+                     size_t msg_bytes, const uint32_t *lens, const uint8_t *nonces, const void *aData, size_t aad_bytes,
+                     const void *in, void *outp, uint8_t *tags, uint8_t *verdicts)
+{
+    context *c;
+    lane *L;
+    keysched ks;
+    const size_t lim = (size_t)-1 / 8;               /* five side arrays and their padding still add up */
+    int rc, bad;
+    if (nonceLen < 1 || nonceLen > 15) return fail(UAES_E_ARG, "OCB nonce length %zu (1..15)", nonceLen);
+    if (tagLen < 1 || tagLen > 16) return fail(UAES_E_ARG, "OCB tag length %zu (1..16)", tagLen);
+    if (msg_bytes > UAES_OCB_BATCH_MAX)
+        return fail(UAES_E_ARG, "an OCB batch record holds at most %zu bytes (got %zu)", (size_t)UAES_OCB_BATCH_MAX, msg_bytes);
+    if (aad_bytes > UAES_OCB_BATCH_MAX)
+        return fail(UAES_E_ARG, "an OCB batch record takes at most %zu bytes of AAD (got %zu)", (size_t)UAES_OCB_BATCH_MAX, aad_bytes);
+    if (nmsg > lim / (msg_bytes > 16 ? msg_bytes : 16) || (aad_bytes && nmsg > lim / aad_bytes))
+        return fail(UAES_E_ARG, "batch size overflows");
+    if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
+    if (nmsg == 0) { burn(&ks, sizeof ks); return 0; }
+    {
+        const size_t total = nmsg * msg_bytes;
+        if ((total && (!in || !outp)) || !nonces || !tags || (decrypt && !verdicts) || (aad_bytes && !aData)) {
+            burn(&ks, sizeof ks);
+            return fail(UAES_E_ARG, "NULL pointer");
+        }
+        if ((rc = enter(&c, &L)) != 0) { burn(&ks, sizeof ks); return rc; }
+        enum { NONCES, AAD, LENS, TAGS, VERDICTS, NSIDE };
+        row_array a[NSIDE] = { { nonces, nmsg * nonceLen, 0, NULL }, { aData, nmsg * aad_bytes, 0, NULL },
+                               { lens, lens ? nmsg * sizeof *lens : 0, 0, NULL }, { tags, nmsg * tagLen, !decrypt, NULL },
+                               { verdicts, decrypt ? nmsg : 0, 1, NULL } };
+        row_text t = { in, outp, total, total, lens != NULL, NULL, NULL };
+        if ((rc = row_stage(L, a, NSIDE, decrypt)) != 0) goto out;
+        if ((rc = row_texts(L, &t)) != 0) goto out;
+        ES_KCHK("ocb batch", uaesk_ocb_batch(L->stream, &c->tb, ks.nr, &ks.ek, &ks.dk, decrypt, wipe_on_auth_failure(),
+                                             a[NONCES].d, nonceLen, tagLen, a[AAD].d, aad_bytes, nmsg, msg_bytes, a[LENS].d,
+                                             t.d_in, t.d_out, a[TAGS].d, a[VERDICTS].d, L->d_status));
+        if ((rc = row_finish(L, &t, a, NSIDE, decrypt, &bad)) != 0) goto out;
+        rc = bad ? UAES_E_AUTHENTICATION : 0;
+    }
+out:
+    burn(&ks, sizeof ks);
+    DONE(L, rc);
+}
+
+int uaes_ocb_encrypt_batch(int keybits, const uint8_t *key, size_t nonceLen, size_t tagLen,
+                           size_t nmsg, size_t msg_bytes, const uint32_t *lens,
+                           const uint8_t *nonces, const void *aData, size_t aad_bytes,
+                           const void *pntxt, void *crtxt, uint8_t *tags)
+{
+    return ocb_batch(0, keybits, key, nonceLen, tagLen, nmsg, msg_bytes, lens, nonces, aData, aad_bytes, pntxt, crtxt, tags, NULL);
+}
+
+int uaes_ocb_decrypt_batch(int keybits, const uint8_t *key, size_t nonceLen, size_t tagLen,
+                           size_t nmsg, size_t msg_bytes, const uint32_t *lens,
+                           const uint8_t *nonces, const void *aData, size_t aad_bytes,
+                           const void *crtxt, const uint8_t *tags, void *pntxt, uint8_t *verdicts)
+{
+    return ocb_batch(1, keybits, key, nonceLen, tagLen, nmsg, msg_bytes, lens, nonces, aData, aad_bytes, crtxt, pntxt,
+                     (uint8_t *)tags, verdicts);
+}
+
 int uaes_ocb_dev(int keybits, const uint8_t *key, const uint8_t *nonce, int decrypt,
                  const void *d_aad, size_t aad_len,
                  const void *d_in, size_t len, void *d_out, int *d_status, void *stream)

@@ -661,6 +661,278 @@ __global__ __launch_bounds__(UAES_WG) void k_ocb_small(uaesk_rk ek, uaesk_rk dk,
 }
 
 /* ------------------------------------------------------------------------ */
+/* batches: many short records under one key (ocb.batch)                       */
+/* ------------------------------------------------------------------------ */
+/* A row batch (uaes_plan.h): sixteen lanes per record, four records per wave, everything in column words.  Behind the
+ * row4 tables and their round keys (uaes_aes.hip.h) sit the encryption schedule and a plain Te0 for the forward blocks
+ * of a DECRYPTING launch (whose row4 region holds the inverse tables) and the first sixteen rows of ocb_setup_lds's L
+ * table: a record of at most UAES_OCB_BATCH_MAX bytes has at most 4095 whole blocks, ntz <= 11, row <= 13. */
+#define OCBB_EK   (131072u + 256u)
+#define OCBB_L    (131072u + 512u)
+#define OCBB_TE0  (131072u + 768u)
+#define OCBB_LDS  (OCBB_TE0 + 1024u)
+static_assert(UAES_OCB_BATCH_MAX / 16 < (1u << 12), "the L table of the batch kernel ends at L_13");
+static_assert(OCBB_LDS <= 160u * 1024u, "one workgroup's LDS");
+
+struct RowNone {};
+template <int NR, bool DEC>
+__device__ __forceinline__ auto ocbb_fwd_lane()
+{
+    if constexpr (DEC) return row_te0_lane<NR>(OCBB_TE0, OCBB_EK);
+    else return RowNone{};
+}
+
+/* this lane's column of row `row` of the L table (0 L_*, 1 L_$, 2 + j L_j) */
+__device__ __forceinline__ u32 ocbb_l(u32 row, u32 c) { return lds_word(OCBB_L + 16u * row + 4u * c); }
+/* this lane's column of the block whose byte n (< 16) is 0x80 */
+__device__ __forceinline__ u32 ocbb_pad80(u32 n, u32 c) { return (n >> 2) == c ? 0x80u << (8u * (n & 3u)) : 0u; }
+
+/* Record m: text at in / out + m msg_bytes (its first lens[m] <= msg_bytes bytes; lens == NULL: all of it), nonce at
+ * nonces + m nonce_len, AAD at aad + m aad_bytes, tag at tags + m tag_len.  Row steps per record, two blocks each
+ * wherever two are independent:  K_top || A_1,  the other AAD blocks in pairs,  the text blocks in pairs,  then
+ * encrypting: a last odd block, the pad of a ragged block and the tag, in pairs (the checksum is over the plaintext, so
+ * the tag waits for neither of them),  decrypting: the odd block (AES^-1), the pad, the tag, one after the other.  With a
+ * blocks of AAD, b whole blocks of text and r = 1 for a ragged one:  1 + ceil((a - 1) / 2) + floor(b / 2)  and then
+ * ceil((b % 2 + r + 1) / 2) encrypting,  b % 2 + r + 1 decrypting.  Offsets are chained, Offset_i = Offset_(i-1) ^ L_ntz(i): one LDS read per even block, L_0 for
+ * every odd one.  A row never reads a lane of another record.  The forward blocks of a decrypting launch go through
+ * row_encrypt_te0 (uaes_aes.hip.h).  Decrypt follows the reference per record (AES_OCB_decrypt :1803-1810): the text
+ * is written before the tag is known; verdicts[m] = 1 if authentic, else 0 and bad[0] |= 1 (a vector atomic), the
+ * output left as decrypted or zeroed when `wipe`.  in == out works: a block is loaded before it is stored.
+ * A4: text 4-byte aligned. */
+template <int NR, bool DEC, bool A4>
+__global__ __launch_bounds__(UAES_WG) void k_ocb_batch(uaesk_rk ek, uaesk_rk dk, uaesk_tables tb, int wipe,
+                                                       const unsigned char *nonces, u32 nonce_len, u32 tag_len,
+                                                       const unsigned char *aad, u32 aad_bytes,
+                                                       u64 nmsg, u32 msg_bytes, const u32 *lens,
+                                                       const unsigned char *in, unsigned char *out,
+                                                       unsigned char *tags, unsigned char *verdicts, int *bad)
+{
+    if (DEC) {                                        /* row4_fill_tables_dec ends in the barrier these need, too */
+        for (u32 i = threadIdx.x; i < 60u; i += blockDim.x) ((u32 *)(uaes_lds + OCBB_EK))[i] = ek.w[i];
+        for (u32 i = threadIdx.x; i < 256u; i += blockDim.x) ((u32 *)(uaes_lds + OCBB_TE0))[i] = tb.te0[i];
+        row4_fill_tables_dec(tb.td0, dk);
+    } else {
+        row4_fill_tables(tb.te0, ek);
+    }
+    const RowLane<NR> L = row4_lane<NR>();
+    const auto F = ocbb_fwd_lane<NR, DEC>();
+    const u32 c = L.c;
+    auto fwd = [&](u32 w) {
+        if constexpr (DEC) return row_encrypt_te0<NR>(w, F); else return row_encrypt<NR>(w, L);
+    };
+    auto fwd2 = [&](u32 &a, u32 &b) {
+        if constexpr (DEC) row_encrypt2_te0<NR>(a, b, F); else row_encrypt2<NR>(a, b, L, L);
+    };
+    if (threadIdx.x < 64u) {                          /* L_* = Enc(0); row r of the table = L_* x^r, one lane each */
+        u32 b[4];
+        row_spread(fwd(0u), b);                       /* lanes 0, 4, 8, 12: the first row's */
+        if (threadIdx.x < 16u) {
+            const B16 ls = { { b[0], b[1], b[2], b[3] } };
+            ((uint4 *)(uaes_lds + OCBB_L))[threadIdx.x] = u4(ocb_times_x_pow(ls, threadIdx.x));
+        }
+    }
+    __syncthreads();
+    const u32 lstar = ocbb_l(0u, c), ldollar = ocbb_l(1u, c), l0 = ocbb_l(2u, c);
+    const u64 rows = blockDim.x >> 4;
+    for (u64 m = (u64)blockIdx.x * rows + (threadIdx.x >> 4); m < nmsg; m += (u64)gridDim.x * rows) {
+        u32 len = msg_bytes;
+        if (lens) { len = lens[m]; if (len > msg_bytes) len = msg_bytes; }
+        const unsigned char *np = nonces + m * nonce_len;
+        const unsigned char *src = in + m * msg_bytes;
+        unsigned char *dst = out + m * msg_bytes;
+        unsigned char *tg = tags + m * tag_len;
+        /* the nonce block (:1705-1708): zeros, a one bit, the nonce; the tag length on top; the low six bits of the last
+         * byte are `bottom` and do not go into K_top */
+        const u32 z0 = 16u - nonce_len;
+        u32 kt = 0;
+#pragma unroll
+        for (u32 k = 0; k < 4; ++k) {
+            const u32 i = 4u * c + k;
+            u32 v = 0;
+            if (i >= z0) v = np[i - z0];
+            if (i + 1u == z0) v |= 1u;
+            kt |= v << (8u * k);
+        }
+        if (c == 0u) kt |= (tag_len << 4) & 0xf0u;
+        const u32 bottom = (kt >> 24) & 63u;          /* column 3's; the others' is never used ... */
+        if (c == 3u) kt &= 0xc0ffffffu;
+        /* HASH(K, A) (:1746-1760): offsets from zero; its first block rides with K_top */
+        u32 hs = 0;
+        {
+            const unsigned char *ap = aad + m * aad_bytes;
+            const u32 afull = aad_bytes >> 4, arem = aad_bytes & 15u, ablk = afull + (arem ? 1u : 0u);
+            u32 ao = 0, ai = 0;
+            auto aad_next = [&]() {                   /* block ai + 1, whitened; the caller knows that there is one */
+                u32 x;
+                if (ai < afull) {
+                    ao ^= (ai & 1u) ? ocbb_l(2u + (u32)__builtin_ctz(ai + 1u), c) : l0;
+                    x = row_load(ap + 16u * ai, 16, c) ^ ao;
+                } else {                              /* A_* || 1 || 0.., Offset_* = Offset_m ^ L_* */
+                    x = row_load(ap + 16u * afull, arem, c) ^ ocbb_pad80(arem, c) ^ ao ^ lstar;
+                }
+                ++ai;
+                return x;
+            };
+            if (ablk) {
+                u32 x = aad_next();
+                fwd2(kt, x);
+                hs = x;
+            } else {
+                kt = fwd(kt);
+            }
+            while (ai < ablk) {
+                u32 x = aad_next();
+                if (ai < ablk) {
+                    u32 y = aad_next();
+                    fwd2(x, y);
+                    hs ^= x ^ y;
+                } else {
+                    hs ^= fwd(x);
+                }
+            }
+        }
+        /* Offset_0 = bits bottom .. bottom + 127 of K_top || (K_top ^ K_top << 8)[0..63] (:1711-1719): every lane needs
+         * all of K_top, from the lanes of its own row */
+        u32 off;
+        {
+            const u32 bt = (u32)__shfl((int)bottom, 12, 16);           /* ... here it comes from column 3 */
+            const u32 k0 = bswap32((u32)__shfl((int)kt, 0, 16)), k1 = bswap32((u32)__shfl((int)kt, 4, 16));
+            const u32 k2 = bswap32((u32)__shfl((int)kt, 8, 16)), k3 = bswap32((u32)__shfl((int)kt, 12, 16));
+            const u64 hi = ((u64)k0 << 32) | k1, lo = ((u64)k2 << 32) | k3;
+            const u64 ext = hi ^ ((hi << 8) | (lo >> 56));
+            const u64 ohi = bt ? (hi << bt) | (lo >> (64u - bt)) : hi;
+            const u64 olo = bt ? (lo << bt) | (ext >> (64u - bt)) : lo;
+            const u64 o = c < 2u ? ohi : olo;
+            off = bswap32((c & 1u) ? (u32)o : (u32)(o >> 32));
+        }
+        /* the text (:1721-1730) */
+        const u32 full = len >> 4, rem = len & 15u;
+        u32 cks = 0, px = 0;
+        /* a decrypting row holds two schedules: it asks for half the chunk (four steps ahead), which keeps every instance
+         * within 128 registers without scratch */
+        row_walk<A4, DEC ? ROW_CH / 2 : ROW_CH>(src, full, c, [&](u64 i, u32 x) {
+            const u32 n = (u32)i + 1u;                /* the block's number, from 1 */
+            if (n & 1u) {
+                px = x;                               /* waits for its partner */
+                if (n < full) return;
+                off ^= l0;                            /* the last block, alone */
+                if (!DEC) { cks ^= x; return; }       /* encrypting: it rides with the pad or the tag, below */
+                const u32 a = row_decrypt<NR>(x ^ off, L) ^ off;
+                cks ^= a;
+                row_store_full<A4>(dst + 16 * i, a, c);
+                return;
+            }
+            const u32 o1 = off ^ l0;
+            off = o1 ^ ocbb_l(2u + (u32)__builtin_ctz(n), c);
+            u32 a = px ^ o1, b = x ^ off;
+            if (DEC) row_decrypt2<NR>(a, b, L, L); else row_encrypt2<NR>(a, b, L, L);
+            a ^= o1;
+            b ^= off;
+            cks ^= DEC ? a ^ b : px ^ x;
+            row_store_full<A4>(dst + 16 * (i - 1), a, c);
+            row_store_full<A4>(dst + 16 * i, b, c);
+        });
+        /* the ragged block (:1736-1741) and the tag (:1743-1744) */
+        u32 t;
+        if (!DEC) {
+            /* the checksum is over the plaintext: neither the tag nor the pad waits for anything but the offsets, so
+             * the last odd block, the pad and the tag -- one, two or three blocks -- take ceil(n / 2) steps */
+            const bool odd = (full & 1u) != 0;
+            const u32 olast = off;                    /* the last odd block's offset, if there is one */
+            u32 x = 0;
+            if (rem) {
+                off ^= lstar;
+                x = row_load(src + 16 * (u64)full, rem, c);
+                cks ^= x ^ ocbb_pad80(rem, c);
+            }
+            t = cks ^ off ^ ldollar;
+            u32 a = odd ? px ^ olast : off;           /* the odd block, else the pad */
+            u32 b = odd && rem ? off : t;             /* the pad if both are there, else the tag */
+            if (odd || rem) {
+                fwd2(a, b);
+                t = odd && rem ? fwd(t) : b;
+            } else {                                  /* the tag alone: a block nobody needs beside it costs a full
+                                                       * batch its share of the LDS all the same (measured: 5 % at 64 B) */
+                t = fwd(t);
+            }
+            if (odd) row_store_full<A4>(dst + 16 * (u64)(full - 1u), a ^ olast, c);
+            if (rem) row_put(dst + 16 * (u64)full, (x ^ (odd ? b : a)) & row_keep(rem, c), rem, c);
+        } else {
+            if (rem) {
+                off ^= lstar;
+                const u32 x = row_load(src + 16 * (u64)full, rem, c);
+                const u32 y = (x ^ fwd(off)) & row_keep(rem, c);
+                cks ^= y ^ ocbb_pad80(rem, c);
+                row_put(dst + 16 * (u64)full, y, rem, c);
+            }
+            t = fwd(cks ^ off ^ ldollar);
+        }
+        t ^= hs;
+        if (!DEC) {
+            row_put(tg, t, tag_len, c);
+        } else {
+            const u32 d = (t ^ row_load(tg, tag_len, c)) & row_keep(tag_len, c);
+            const bool forged = row_any(d != 0u);
+            row_verdict((threadIdx.x & 15u) == 0, verdicts, m, !forged, bad);
+            if (forged && wipe)
+                for (u32 i = 0; i < len; i += 16) row_put(dst + i, 0u, len - i < 16u ? len - i : 16u, c);
+        }
+    }
+}
+
+/* ocb.batch: a row batch at any number of records (uaesk_row_shape) */
+static void plan_ocb_batch(u64 nmsg, uaes_plan *p)
+{
+    const RowShape s = uaesk_row_shape(nmsg);
+    memset(p, 0, sizeof *p);
+    p->arrangement = UAES_OCB_BATCH;
+    p->launches = 1;
+    p->grid = s.grid;
+    p->steps = s.wg;
+}
+
+extern "C" int uaesk_plan_ocb_batch(int dir, size_t len, size_t nmsg, uaes_plan *p)
+{
+    memset(p, 0, sizeof *p);
+    if ((dir != 0 && dir != 1) || len > UAES_OCB_BATCH_MAX) return (int)hipErrorInvalidValue;
+    plan_ocb_batch(nmsg, p);
+    return 0;
+}
+
+extern "C" const char *uaesk_ocb_batch_arrangement_name(int id)
+{
+    return id == UAES_OCB_BATCH ? "ocb.batch" : "?";
+}
+
+template <int NR>
+static int launch_ocb_batch(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *ek, const uaesk_rk *dk, int decrypt,
+                            int wipe, const void *nonces, size_t nonce_len, size_t tag_len, const void *aad,
+                            size_t aad_bytes, size_t nmsg, size_t msg_bytes, const void *lens, const void *in, void *out,
+                            void *tags, void *verdicts, int *bad)
+{
+    uaes_plan p;
+    plan_ocb_batch(nmsg, &p);
+    return with_bool(decrypt, [&](auto DEC) { return with_bool(uaesk_rows_a4(in, out, msg_bytes), [&](auto A4) {
+        return uaesk_launch(k_ocb_batch<NR, decltype(DEC)::value, decltype(A4)::value>, p.grid, p.steps, OCBB_LDS, st, *ek,
+                            decrypt ? *dk : *ek, *tb, wipe, nonces, nonce_len, tag_len, aad, aad_bytes, nmsg, msg_bytes, lens,
+                            in, out, tags, verdicts, bad); }); });
+}
+
+extern "C" int uaesk_ocb_batch(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, const uaesk_rk *dk,
+                               int decrypt, int wipe, const void *nonces, size_t nonce_len, size_t tag_len, const void *aad,
+                               size_t aad_bytes, size_t nmsg, size_t msg_bytes, const void *lens, const void *in, void *out,
+                               void *tags, void *verdicts, int *bad)
+{
+    if (nonce_len < 1 || nonce_len > 15 || tag_len < 1 || tag_len > 16 || aad_bytes > UAES_OCB_BATCH_MAX ||
+        msg_bytes > UAES_OCB_BATCH_MAX)
+        return (int)hipErrorInvalidValue;
+    if (nmsg == 0) return 0;
+    DISPATCH_NR(nr, return (launch_ocb_batch<NR>(S(stream), tb, ek, dk, decrypt, wipe, nonces, nonce_len, tag_len, aad,
+                                                 aad_bytes, nmsg, msg_bytes, lens, in, out, tags, verdicts, bad)));
+    return 0;
+}
+
+/* ------------------------------------------------------------------------ */
 /* launcher                                                                    */
 /* ------------------------------------------------------------------------ */
 /* OCB's rows of the table of arrangements (uaes_plan.h): one workgroup for a short message with short associated data,

@@ -28,6 +28,7 @@
  *         GCM_LEVELS            k_gcm_setup, k_ctr*, k_ghash_pass x0-2, k_ghash_final (3-5) whatever is left (tag-only; > 512 MiB tag-first)
  *   OCB   OCB_SMALL             k_ocb_small                                         (1)    <= OCB_SMALL_BLOCKS blocks and short AAD
  *         OCB_RUNS              k_ocb (last workgroup to arrive makes the tag)      (1)    otherwise
+ *         ocb.batch             k_ocb_batch (sixteen lanes per record, four per wave) (1)  uaes_ocb_*_batch, records <= UAES_OCB_BATCH_MAX (65535 B)
  *   SIV   SIV_SMALL             k_siv_small                                         (1)    <= 2046 POLYVAL positions
  *         SIV_CHUNKS            k_siv_prep, hash-only k_gcm_chunks<FOLD>, k_ctr*    (3)    <= 512 MiB
  *         SIV_LEVELS            k_siv_prep, k_ghash_pass.., k_siv_tag, k_ctr*       (4-6)  beyond
@@ -69,8 +70,9 @@
  * FF3-1 has uaesk_plan_ff3 (uaes_ff3.hip; uaes_debug_plan_ff3): one row, whose limits depend on the radix.
  * The GCM-SIV batches have uaesk_plan_gcmsiv_batch (uaes_gcmsiv_batch.hip; uaes_debug_plan_gcmsiv_batch): one row.
  * OCB_RUNS is one row whose launch shape moves with the size: uaesk_plan_ocb_shape (uaes_ocb.hip; uaes_debug_plan_ocb),
- * and tests/test_gpu_ocb.py takes its sizes from walking it.
- * The rows that say "sixteen lanes per record / message" -- eax.batch, s2v.batch, ccm.batch, gcmsiv.batch, batch.row,
+ * and tests/test_gpu_ocb.py takes its sizes from walking it.  The OCB batches have uaesk_plan_ocb_batch (uaes_ocb.hip;
+ * uaes_debug_plan_ocb_batch): one row, with an id outside enum uaes_arrangement.
+ * The rows that say "sixteen lanes per record / message" -- eax.batch, s2v.batch, ccm.batch, gcmsiv.batch, ocb.batch, batch.row,
  * kw.batch, ff1.batch, ff3.batch -- are the row batches: grid and threads per workgroup are uaesk_row_shape's (uaes_launch.hip.h), the same
  * for the same number of records in every one of them.
  */
@@ -240,6 +242,17 @@ const char *uaesk_ff3_arrangement_name(int id);
 enum uaes_gcmsiv_batch_arrangement { UAES_GCMSIV_BATCH = 0 };
 int uaesk_plan_gcmsiv_batch(int dir, size_t len, size_t nmsg, uaes_plan *p);
 const char *uaesk_gcmsiv_batch_arrangement_name(int id);
+
+/* The batches of OCB records (RFC 7253; k_ocb_batch, uaes_ocb.hip).  dir: 0 encrypt, 1 decrypt; len = bytes per record,
+ * nmsg = records; one arrangement, a row batch at any number of records.  A record is walked by sixteen lanes, two
+ * blocks per step: it is at most UAES_OCB_BATCH_MAX bytes (the same number as UAES_CCM_BATCH_MAX and
+ * UAES_GCMSIV_BATCH_MAX, and the most AAD a record takes), so that its offsets never need more than L_11; beyond it
+ * OCB_SMALL / OCB_RUNS above are the right tool.  grid = workgroups, steps = threads per workgroup.  Returns a HIP
+ * error code for a dir other than 0 / 1 or a length above the limit. */
+#define UAES_OCB_BATCH_MAX ((size_t)65535)
+enum uaes_ocb_batch_arrangement { UAES_OCB_BATCH = 0 };
+int uaesk_plan_ocb_batch(int dir, size_t len, size_t nmsg, uaes_plan *p);
+const char *uaesk_ocb_batch_arrangement_name(int id);
 
 #ifdef __cplusplus
 }
