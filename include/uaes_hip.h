@@ -200,6 +200,50 @@ int uaes_gcm_encrypt_ex(int keybits, const uint8_t *key, const uint8_t *nonce, s
 int uaes_gcm_decrypt_ex(int keybits, const uint8_t *key, const uint8_t *nonce, size_t nonceLen, size_t tagLen,
                         const void *aData, size_t aDataLen,
                         const void *crtxt, size_t crtxtLen, void *pntxt);
+/* Batches with A KEY PER RECORD -- what GCM is terminated in bulk for (TLS, QUIC, IPsec ESP, SRTP, per-object storage
+ * keys) is many short packets of which almost every one belongs to another session and so has another key; one
+ * uaes_gcm_encrypt per packet redoes the key schedule, H and its table kernel every time, and a uaes_gcm_key context
+ * per session with one *_records launch each costs the same when a session has a handful of packets.  Here every record
+ * expands its own key schedule and hashes under its own H, all in the kernel (csrc/uaes_gcm_multikey.hip).  The
+ * conventions are those of the CCM, GCM-SIV and OCB batches: nmsg records in slots of msg_bytes back to back (record m
+ * at m * msg_bytes), sixteen GPU lanes per record, one kernel launch, always on the GPU (the host policy does not
+ * apply).  keys = nmsg * keybits / 8 bytes, PACKED: record m works under the key at keys + m * keybits / 8, and one
+ * keybits serves the whole call.  keys may be host OR DEVICE memory at any byte offset -- the first key argument of this
+ * header that may be device memory.  A table of keys with per-record indices is out of scope: the caller gathers the
+ * keys into the packed array.  A host key array travels through the engine's device scratch, and that copy is cleared
+ * in stream order before the call returns; on the device a schedule exists only in LDS and registers.  nonces = nmsg *
+ * 12 bytes (J0 = nonce || 00000001), aData = nmsg * aad_bytes (aad_bytes 0: no AAD, the pointer may be NULL), tags =
+ * nmsg * tagLen bytes (tagLen 1..16: the first tagLen bytes of each tag), PACKED, not appended to the texts.  lens (may
+ * be NULL: every record is msg_bytes long) = nmsg 32-bit lengths: record m is the first lens[m] <= msg_bytes bytes of
+ * its slot (a longer entry is taken as msg_bytes) and the bytes of an output slot beyond lens[m] are not written.  Every
+ * record is bit for bit what uaes_gcm_encrypt_ex / uaes_gcm_decrypt_ex give for it under its key with nonceLen 12 and
+ * this tagLen, at all three key sizes.  Decrypt keeps N7 per record, as uaes_gcm_key_decrypt_records does: a record is
+ * hashed first and its text is written only if the tag matches, so a forged record's output slot is UNTOUCHED (with
+ * crtxt == pntxt it stays ciphertext); verdicts[m] = 1 (authentic) / 0 (required), the call returns 0 when every record
+ * is authentic, else UAES_E_AUTHENTICATION, and uaes_set_wipe_on_auth_failure does not apply.  UAES_E_ARG (before the
+ * device is touched): key bits other than 128 / 192 / 256, tagLen outside 1..16, msg_bytes or aad_bytes > 65535
+ * (UAES_GCM_MULTIKEY_BATCH_MAX, csrc/uaes_plan.h: a record then has at most 4096 counter blocks; beyond it a key
+ * context per key is the right tool), a size product that overflows, a needed pointer that is NULL (keys and verdicts
+ * included).  nmsg == 0 returns 0 after the length and key-size checks.  Every array host or device memory at any byte
+ * offset (lens: 4-byte aligned device memory, or host memory); crtxt == pntxt works.  A host-memory output of a
+ * decryption, or of any call with lens, is copied in first, so that what the kernel leaves unwritten stays the caller's.
+ * Measured on an MI355X (tools/gcm_multikey_rate.py -> profiles/gcm_multikey_batch_rate.md; device-resident arrays and
+ * keys, 12 bytes of AAD, 16-byte tags; synchronous calls, the host round trip included), AES-128 and AES-256, encrypt /
+ * decrypt:
+ *   2^10 records of 16 B     22.3 / 37.3 and 22.8 / 37.8 us per call  (2^10 uaes_gcm_encrypt calls, a key each: 16.6 / 17.3 us EACH)
+ *   2^20 records of 16 B     2.29 / 1.84 and 2.06 / 1.69 G records per second
+ *   2^20 records of 64 B     1.58 / 1.35 and 1.41 / 1.21 G records per second
+ *   2^20 records of 1024 B   0.204 / 0.211 and 0.177 / 0.188 G records per second
+ * 0.70 .. 1.07x the time of uaes_gcmsiv_encrypt_batch / _decrypt_batch under ONE key at the same shape, and 0.24 .. 0.36x
+ * that of uaes_gcm_key_encrypt_records / _decrypt_records under one key at 16 and 64 bytes, 1.03 .. 1.09x at 1024. */
+int uaes_gcm_multikey_encrypt_batch(int keybits, const uint8_t *keys, size_t tagLen,
+                                    size_t nmsg, size_t msg_bytes, const uint32_t *lens,
+                                    const uint8_t *nonces, const void *aData, size_t aad_bytes,
+                                    const void *pntxt, void *crtxt, uint8_t *tags);
+int uaes_gcm_multikey_decrypt_batch(int keybits, const uint8_t *keys, size_t tagLen,
+                                    size_t nmsg, size_t msg_bytes, const uint32_t *lens,
+                                    const uint8_t *nonces, const void *aData, size_t aad_bytes,
+                                    const void *crtxt, const uint8_t *tags, void *pntxt, uint8_t *verdicts);
 /* GHASH_H(aData, crtxt) of micro_aes.c:1127-1137 with an explicit H (test
  * hook for the carry-less-multiply kernels); gh receives 16 bytes.           */
 int uaes_ghash(const uint8_t H[16], const void *aData, size_t aDataLen,
@@ -832,6 +876,11 @@ const char *uaes_debug_plan_ff3(int dir, unsigned radix, size_t len, size_t nrec
  * threads as "ccm.batch" for the same number of records), or NULL for a dir other than 0 / 1 or a length above
  * UAES_GCMSIV_BATCH_MAX.  Works without a device (a 256-CU MI355X). */
 const char *uaes_debug_plan_gcmsiv_batch(int dir, size_t len, size_t nmsg, int out[3]);
+/* The planner of the multi-key GCM batches (csrc/uaes_plan.h): dir 0 encrypt / 1 decrypt; len = bytes per record, nmsg =
+ * records; `out` as for FF1.  Returns "gcm.multikey" (the one arrangement: sixteen lanes per record, the same grid and
+ * threads as "ccm.batch" for the same number of records), or NULL for a dir other than 0 / 1 or a length above
+ * UAES_GCM_MULTIKEY_BATCH_MAX.  Works without a device (a 256-CU MI355X). */
+const char *uaes_debug_plan_gcm_multikey_batch(int dir, size_t len, size_t nmsg, int out[3]);
 /* The launch shape of OCB (csrc/uaes_plan.h, uaesk_plan_ocb_shape): dir 0 encrypt / 1 decrypt; len / aad_len = bytes of
  * text / of associated data; aad_aligned = whether the associated data starts at a multiple of 16 bytes in device
  * memory.  Returns "ocb.small" (one workgroup; out untouched) or "ocb.runs", for which out (may be NULL) receives

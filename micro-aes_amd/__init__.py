@@ -44,6 +44,7 @@ EXPORTS = [
     "uaes_ocb_encrypt_batch", "uaes_ocb_decrypt_batch", "uaes_debug_plan_ocb_batch",
     "uaes_cmac", "uaes_ccm_encrypt", "uaes_ccm_decrypt", "uaes_gcmsiv_encrypt", "uaes_gcmsiv_decrypt",
     "uaes_gcmsiv_encrypt_batch", "uaes_gcmsiv_decrypt_batch", "uaes_debug_plan_gcmsiv_batch",
+    "uaes_gcm_multikey_encrypt_batch", "uaes_gcm_multikey_decrypt_batch", "uaes_debug_plan_gcm_multikey_batch",
     "uaes_ocb_encrypt", "uaes_ocb_decrypt", "uaes_ocb_dev", "uaes_debug_plan_ocb",
     "uaes_poly1305", "uaes_poly1305_dev", "uaes_poly1305_batch", "uaes_debug_plan_poly1305",
     "uaes_eax_encrypt", "uaes_eax_decrypt", "uaes_siv_encrypt", "uaes_siv_decrypt",
@@ -169,6 +170,10 @@ def engine():
     L.uaes_gcmsiv_decrypt_batch.argtypes = [i, vp, sz, sz, vp, vp, vp, sz, vp, vp, vp, vp]
     L.uaes_debug_plan_gcmsiv_batch.argtypes = [i, sz, sz, C.POINTER(C.c_int)]
     L.uaes_debug_plan_gcmsiv_batch.restype = C.c_char_p
+    L.uaes_gcm_multikey_encrypt_batch.argtypes = [i, vp, sz, sz, sz, vp, vp, vp, sz, vp, vp, vp]
+    L.uaes_gcm_multikey_decrypt_batch.argtypes = [i, vp, sz, sz, sz, vp, vp, vp, sz, vp, vp, vp, vp]
+    L.uaes_debug_plan_gcm_multikey_batch.argtypes = [i, sz, sz, C.POINTER(C.c_int)]
+    L.uaes_debug_plan_gcm_multikey_batch.restype = C.c_char_p
     L.uaes_siv_encrypt_batch.argtypes = [i, vp, sz, sz, vp, sz, vp, vp, vp]
     L.uaes_siv_decrypt_batch.argtypes = [i, vp, sz, sz, vp, sz, vp, vp, vp, vp]
     L.uaes_debug_plan_eax_siv.argtypes = [i, i, sz, sz, C.POINTER(C.c_int)]
@@ -266,7 +271,7 @@ def engine():
                      "uaes_debug_arrangement_name", "uaes_debug_plan_disable", "uaes_debug_plan_poly1305",
                      "uaes_debug_plan_eax_siv", "uaes_debug_plan_chain", "uaes_debug_plan_kw", "uaes_debug_plan_ff1",
                      "uaes_debug_plan_ff3", "uaes_ff3_maxlen", "uaes_debug_plan_gcmsiv_batch", "uaes_debug_plan_ocb",
-                     "uaes_debug_plan_ocb_batch"):
+                     "uaes_debug_plan_ocb_batch", "uaes_debug_plan_gcm_multikey_batch"):
             getattr(L, n).restype = i
     _lib = L
     return L
@@ -688,6 +693,49 @@ def gcmsiv_batch_plan(length, nmsg, decrypt=False):
     launches, workgroups, threads per workgroup), or None for arguments that make no sense."""
     out = (C.c_int * 3)()
     name = engine().uaes_debug_plan_gcmsiv_batch(int(bool(decrypt)), length, nmsg, out)
+    return None if name is None else (name.decode(), out[0], out[1], out[2])
+
+
+def gcm_multikey_batch(keys, nonces, aads, texts, decrypt=False, tags=None, tag_len=16, prefill=0, lens=None):
+    """GCM of many records, each under a key of its own (uaes_gcm_multikey_*_batch): equal-sized keys (16, 24 or 32
+    bytes), 12-byte nonces, equal-sized AADs (or None) and texts.  encrypt: returns (ciphertexts, tag_len-byte tags);
+    decrypt (tags given): returns (code, plaintexts, verdicts); a forged record's output slot is untouched: it stays
+    the prefill, whatever wipe_on_auth_failure says.  lens (optional, one per record): record m is the first lens[m]
+    bytes of its text, and the rest of its output slot stays the prefill."""
+    n = len(texts)
+    aads = aads if aads is not None else [b""] * n
+    if len(keys) != n or len(nonces) != n or len(aads) != n or (decrypt and (tags is None or len(tags) != n)) or \
+            (lens is not None and len(lens) != n):
+        raise ValueError("one key, nonce, AAD (tag and length) per record")
+    if n == 0:
+        return (0, [], []) if decrypt else ([], [])
+    if any(len(x) != 12 for x in nonces) or (decrypt and any(len(x) != tag_len for x in tags)):
+        raise ValueError("nonces of 12 bytes (tags of tag_len)")
+    kl, kb = _records(keys, "keys")
+    nb = b"".join(nonces)
+    al, ab = _records(aads, "AADs")
+    ml, mb = _records(texts, "texts")
+    lv = (C.c_uint32 * n)(*lens) if lens is not None else None
+    L = engine()
+    o = _out(n * ml, prefill)
+    if not decrypt:
+        t = _out(n * tag_len)
+        _check(L.uaes_gcm_multikey_encrypt_batch(8 * kl, _in(kb), tag_len, n, ml, lv, _in(nb), _in(ab), al, _in(mb), o, t),
+               "uaes_gcm_multikey_encrypt_batch")
+        raw, tr = bytes(o), bytes(t)
+        return _split(raw, ml, n), _split(tr, tag_len, n)
+    v = _out(n)
+    rc = _check(L.uaes_gcm_multikey_decrypt_batch(8 * kl, _in(kb), tag_len, n, ml, lv, _in(nb), _in(ab), al, _in(mb),
+                                                  _in(b"".join(tags)), o, v), "uaes_gcm_multikey_decrypt_batch")
+    raw = bytes(o)
+    return rc, _split(raw, ml, n), list(bytes(v)[:n])
+
+
+def gcm_multikey_batch_plan(length, nmsg, decrypt=False):
+    """What a multi-key GCM batch of nmsg records of `length` bytes would run (uaes_debug_plan_gcm_multikey_batch):
+    (arrangement, launches, workgroups, threads per workgroup), or None for arguments that make no sense."""
+    out = (C.c_int * 3)()
+    name = engine().uaes_debug_plan_gcm_multikey_batch(int(bool(decrypt)), length, nmsg, out)
     return None if name is None else (name.decode(), out[0], out[1], out[2])
 
 

@@ -666,7 +666,9 @@ __device__ __forceinline__ RowLane<NR> row_lane(u32 key_at = 65536u)   /* key_at
  * constant, which the same v_perm selector already copies); the round keys follow at 128 KiB.                 */
 #define UAES_LDS_ROW4  (131072u + 256u)
 
-__device__ __forceinline__ void row4_fill_tables(const u32 *__restrict__ te0, const uaesk_rk &rk)
+/* the tables alone, no barrier: a kernel whose records bring their own keys has no round keys to put behind them
+ * (k_gcm_multikey) and places the __syncthreads itself */
+__device__ __forceinline__ void row4_fill_tables_only(const u32 *__restrict__ te0)
 {
     for (u32 j0 = threadIdx.x; j0 < 8192u; j0 += 8u * blockDim.x) {      /* 256 entries x 32 pieces of 16 bytes */
         u32 t[8];
@@ -686,6 +688,11 @@ __device__ __forceinline__ void row4_fill_tables(const u32 *__restrict__ te0, co
             }
         }
     }
+}
+
+__device__ __forceinline__ void row4_fill_tables(const u32 *__restrict__ te0, const uaesk_rk &rk)
+{
+    row4_fill_tables_only(te0);
     for (u32 i = threadIdx.x; i < 60u; i += blockDim.x) ((u32 *)(uaes_lds + 131072u))[i] = rk.w[i];
     __syncthreads();
 }

@@ -172,6 +172,17 @@ int uaesk_gcmsiv_batch(void *stream, const uaesk_tables *tb, int nr, const uaesk
                        const void *nonces, const void *aad, size_t aad_bytes, size_t nmsg, size_t msg_bytes,
                        const void *lens, const void *in, void *out, void *tags, void *verdicts, int *bad);
 
+/* Batch: nmsg GCM records, EACH UNDER ITS OWN KEY, sixteen lanes per record (k_gcm_multikey, uaes_gcm_multikey.hip);
+ * all device pointers, the keys included.  Record m: key at keys + m * 4 (nr - 6) bytes (any byte offset), text at in /
+ * out + m msg_bytes (msg_bytes <= UAES_GCM_MULTIKEY_BATCH_MAX), its first lens[m] bytes (lens NULL: msg_bytes), nonce at
+ * nonces + 12 m, AAD at aad + m aad_bytes (<= UAES_GCM_MULTIKEY_BATCH_MAX), the first tag_len (1..16) bytes of the tag
+ * at tags + m tag_len.  Every schedule is expanded in the kernel, into LDS.  decrypt writes verdicts[m] (1 = authentic)
+ * and ORs 1 into *bad for a forgery, whose output is not written at all. */
+int uaesk_gcm_multikey_batch(void *stream, const uaesk_tables *tb, int nr, int decrypt, size_t tag_len,
+                             const void *keys, const void *nonces, const void *aad, size_t aad_bytes,
+                             size_t nmsg, size_t msg_bytes, const void *lens, const void *in, void *out,
+                             void *tags, void *verdicts, int *bad);
+
 /* GHASH only: gh = GHASH_H(aad, ct) with H given (device), for tests.      */
 int uaesk_ghash(void *stream, const uaesk_tables *tb, const uint8_t *H_host,
                 const void *aad, size_t aad_len, const void *ct, size_t ct_len,

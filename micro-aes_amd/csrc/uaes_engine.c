@@ -1483,6 +1483,14 @@ const char *uaes_debug_plan_gcmsiv_batch(int dir, size_t len, size_t nmsg, int o
     if (out) { out[0] = p.launches; out[1] = (int)p.grid; out[2] = (int)p.steps; }
     return uaesk_gcmsiv_batch_arrangement_name(p.arrangement);
 }
+const char *uaes_debug_plan_gcm_multikey_batch(int dir, size_t len, size_t nmsg, int out[3])
+{
+    uaes_plan p;
+    memset(&p, 0, sizeof p);
+    if (uaesk_plan_gcm_multikey_batch(dir, len, nmsg, &p)) return NULL;
+    if (out) { out[0] = p.launches; out[1] = (int)p.grid; out[2] = (int)p.steps; }
+    return uaesk_gcm_multikey_arrangement_name(p.arrangement);
+}
 const char *uaes_debug_plan_ocb_batch(int dir, size_t len, size_t nmsg, int out[3])
 {
     uaes_plan p;

@@ -898,6 +898,76 @@ int uaes_gcmsiv_decrypt_batch(int keybits, const uint8_t *key, size_t nmsg, size
                         verdicts);
 }
 
+/* Multi-key GCM batches (k_gcm_multikey, uaes_gcm_multikey.hip): as gcmsiv_batch with packed tags of tagLen bytes and
+ * `keys` as one more side array, nmsg * keybits / 8 bytes in host or device memory -- no key is expanded here, every
+ * record's schedule is made in the kernel, so keybits is validated on its own.  A host key array travels through the
+ * lane's scratch like the other side arrays, and that copy is cleared in stream order before the call returns, whether
+ * the launch was reached or not.  Decrypt keeps N7 per record: the kernel writes an authentic record only, so the
+ * output's staging starts as the caller's buffer, and uaes_set_wipe_on_auth_failure does not apply.  Every argument is
+ * checked before the device is touched. */
+static int gcm_multikey_batch(int decrypt, int keybits, const uint8_t *keys, size_t tagLen, size_t nmsg, size_t msg_bytes,
+                              const uint32_t *lens, const uint8_t *nonces, const void *aData, size_t aad_bytes,
+                              const void *in, void *outp, uint8_t *tags, uint8_t *verdicts)
+{
+    context *c;
+    lane *L;
+    const size_t lim = (size_t)-1 / 8;               /* six side arrays and their padding still add up */
+    int rc, bad;
+    if (keybits != 128 && keybits != 192 && keybits != 256) return fail(UAES_E_ARG, "key bits must be 128, 192 or 256 (got %d)", keybits);
+    if (tagLen < 1 || tagLen > 16) return fail(UAES_E_ARG, "a GCM tag has 1 to 16 bytes (got %zu)", tagLen);
+    if (msg_bytes > UAES_GCM_MULTIKEY_BATCH_MAX)
+        return fail(UAES_E_ARG, "a multi-key GCM batch record holds at most %zu bytes (got %zu)", (size_t)UAES_GCM_MULTIKEY_BATCH_MAX, msg_bytes);
+    if (aad_bytes > UAES_GCM_MULTIKEY_BATCH_MAX)
+        return fail(UAES_E_ARG, "a multi-key GCM batch record takes at most %zu bytes of AAD (got %zu)", (size_t)UAES_GCM_MULTIKEY_BATCH_MAX, aad_bytes);
+    if (nmsg > lim / (msg_bytes > 32 ? msg_bytes : 32) || (aad_bytes && nmsg > lim / aad_bytes))    /* 32: the longest key */
+        return fail(UAES_E_ARG, "batch size overflows");
+    if (nmsg == 0) return 0;
+    {
+        const size_t total = nmsg * msg_bytes, key_bytes = nmsg * ((size_t)keybits / 8);
+        if ((total && (!in || !outp)) || !keys || !nonces || !tags || (decrypt && !verdicts) || (aad_bytes && !aData))
+            return fail(UAES_E_ARG, "NULL pointer");
+        if ((rc = enter(&c, &L)) != 0) return rc;
+        enum { KEYS, NONCES, AAD, LENS, TAGS, VERDICTS, NSIDE };
+        row_array a[NSIDE] = { { keys, key_bytes, 0, NULL }, { nonces, nmsg * 12, 0, NULL }, { aData, nmsg * aad_bytes, 0, NULL },
+                               { lens, lens ? nmsg * sizeof *lens : 0, 0, NULL }, { tags, nmsg * tagLen, !decrypt, NULL },
+                               { verdicts, decrypt ? nmsg : 0, 1, NULL } };
+        row_text t = { in, outp, total, total, decrypt || lens != NULL, NULL, NULL };
+        if ((rc = row_stage(L, a, NSIDE, decrypt)) == 0 && (rc = row_texts(L, &t)) == 0) {
+            const int e = uaesk_gcm_multikey_batch(L->stream, &c->tb, keybits / 32 + 6, decrypt, tagLen, a[KEYS].d, a[NONCES].d,
+                                                   a[AAD].d, aad_bytes, nmsg, msg_bytes, a[LENS].d, t.d_in, t.d_out, a[TAGS].d,
+                                                   a[VERDICTS].d, L->d_status);
+            if (e != 0) rc = fail(UAES_E_HIP, "gcm multi-key batch failed: %s", hipGetErrorString((hipError_t)e));
+        }
+        /* the staged copy of a host key array (row_stage lists KEYS first: the start of the scratch, if it got that far) */
+        if (a[KEYS].d && a[KEYS].d != (const void *)keys &&
+            hipMemsetAsync(a[KEYS].d, 0, key_bytes, (hipStream_t)L->stream) != hipSuccess && rc == 0)
+            rc = fail(UAES_E_HIP, "clearing the staged keys failed");
+        if (rc) {
+            (void)hipStreamSynchronize((hipStream_t)L->stream);
+            goto out;
+        }
+        if ((rc = row_finish(L, &t, a, NSIDE, decrypt, &bad)) != 0) goto out;
+        rc = bad ? UAES_E_AUTHENTICATION : 0;
+    }
+out:
+    DONE(L, rc);
+}
+
+int uaes_gcm_multikey_encrypt_batch(int keybits, const uint8_t *keys, size_t tagLen, size_t nmsg, size_t msg_bytes,
+                                    const uint32_t *lens, const uint8_t *nonces, const void *aData, size_t aad_bytes,
+                                    const void *pntxt, void *crtxt, uint8_t *tags)
+{
+    return gcm_multikey_batch(0, keybits, keys, tagLen, nmsg, msg_bytes, lens, nonces, aData, aad_bytes, pntxt, crtxt, tags, NULL);
+}
+
+int uaes_gcm_multikey_decrypt_batch(int keybits, const uint8_t *keys, size_t tagLen, size_t nmsg, size_t msg_bytes,
+                                    const uint32_t *lens, const uint8_t *nonces, const void *aData, size_t aad_bytes,
+                                    const void *crtxt, const uint8_t *tags, void *pntxt, uint8_t *verdicts)
+{
+    return gcm_multikey_batch(1, keybits, keys, tagLen, nmsg, msg_bytes, lens, nonces, aData, aad_bytes, crtxt, pntxt,
+                              (uint8_t *)tags, verdicts);
+}
+
 /* ------------------------------------------------------------------------ */
 /* CBC / CFB / OFB                                   */
 /* ------------------------------------------------------------------------ */

@@ -26,6 +26,7 @@
  *         GCM_TWOPHASE          k_ctr_shared2, then hash-only k_gcm_chunks<FOLD>    (2)    encrypt / one-pass decrypt, 16 .. 128 MiB
  *         GCM_STRIPED           k_gcm_setup | k_gcm_ej0, k_gcm_fused, k_ghash_final (3)    encrypt / one-pass decrypt beyond (C4: 1 GiB)
  *         GCM_LEVELS            k_gcm_setup, k_ctr*, k_ghash_pass x0-2, k_ghash_final (3-5) whatever is left (tag-only; > 512 MiB tag-first)
+ *         gcm.multikey          k_gcm_multikey (sixteen lanes per record, four per wave; a key per record) (1)  uaes_gcm_multikey_*_batch, records <= UAES_GCM_MULTIKEY_BATCH_MAX (65535 B)
  *   OCB   OCB_SMALL             k_ocb_small                                         (1)    <= OCB_SMALL_BLOCKS blocks and short AAD
  *         OCB_RUNS              k_ocb (last workgroup to arrive makes the tag)      (1)    otherwise
  *         ocb.batch             k_ocb_batch (sixteen lanes per record, four per wave) (1)  uaes_ocb_*_batch, records <= UAES_OCB_BATCH_MAX (65535 B)
@@ -71,8 +72,9 @@
  * The GCM-SIV batches have uaesk_plan_gcmsiv_batch (uaes_gcmsiv_batch.hip; uaes_debug_plan_gcmsiv_batch): one row.
  * OCB_RUNS is one row whose launch shape moves with the size: uaesk_plan_ocb_shape (uaes_ocb.hip; uaes_debug_plan_ocb),
  * and tests/test_gpu_ocb.py takes its sizes from walking it.  The OCB batches have uaesk_plan_ocb_batch (uaes_ocb.hip;
- * uaes_debug_plan_ocb_batch): one row, with an id outside enum uaes_arrangement.
- * The rows that say "sixteen lanes per record / message" -- eax.batch, s2v.batch, ccm.batch, gcmsiv.batch, ocb.batch, batch.row,
+ * uaes_debug_plan_ocb_batch): one row, with an id outside enum uaes_arrangement.  So do the multi-key GCM batches:
+ * uaesk_plan_gcm_multikey_batch (uaes_gcm_multikey.hip; uaes_debug_plan_gcm_multikey_batch).
+ * The rows that say "sixteen lanes per record / message" -- eax.batch, s2v.batch, ccm.batch, gcmsiv.batch, gcm.multikey, ocb.batch, batch.row,
  * kw.batch, ff1.batch, ff3.batch -- are the row batches: grid and threads per workgroup are uaesk_row_shape's (uaes_launch.hip.h), the same
  * for the same number of records in every one of them.
  */
@@ -253,6 +255,20 @@ const char *uaesk_gcmsiv_batch_arrangement_name(int id);
 enum uaes_ocb_batch_arrangement { UAES_OCB_BATCH = 0 };
 int uaesk_plan_ocb_batch(int dir, size_t len, size_t nmsg, uaes_plan *p);
 const char *uaesk_ocb_batch_arrangement_name(int id);
+
+/* The batches of GCM records with a key per record (k_gcm_multikey, uaes_gcm_multikey.hip).  dir: 0 encrypt, 1 decrypt;
+ * len = bytes per record, nmsg = records; one arrangement, a row batch at any number of records.  A record is a key
+ * expansion, a serial hash and a serial keystream on sixteen lanes: it is at most UAES_GCM_MULTIKEY_BATCH_MAX bytes (the
+ * same number as the other batch caps, and the most AAD a record takes); beyond it a uaes_gcm_key context per key is the
+ * right tool.  A record then has at most 4096 blocks and its counters are J0 + 1 .. J0 + 4096 with J0 = nonce ||
+ * 00000001: the 32-bit counter stays below 2^16, so only bytes 14..15 of the counter block ever change (asserted
+ * below; the kernel builds the counter's column from them).  grid = workgroups, steps = threads per workgroup.  Returns
+ * a HIP error code for a dir other than 0 / 1 or a length above the limit. */
+#define UAES_GCM_MULTIKEY_BATCH_MAX ((size_t)65535)
+typedef char uaes_gcm_multikey_counter_stays_in_bytes_14_15[(UAES_GCM_MULTIKEY_BATCH_MAX + 15) / 16 + 1 <= 0xFFFF ? 1 : -1];
+enum uaes_gcm_multikey_arrangement { UAES_GCM_MULTIKEY = 0 };
+int uaesk_plan_gcm_multikey_batch(int dir, size_t len, size_t nmsg, uaes_plan *p);
+const char *uaesk_gcm_multikey_arrangement_name(int id);
 
 #ifdef __cplusplus
 }

@@ -82,6 +82,11 @@ print("GCM-SIV batches: a record holds at most UAES_GCMSIV_BATCH_MAX = %d bytes 
 walk("GCM-SIV batch, k records of 64 bytes (positions/thread: threads per workgroup)",
      lambda k: uaes.gcmsiv_batch_plan(64, max(k, 1))[:2] + (0, uaes.gcmsiv_batch_plan(64, max(k, 1))[3]), 1, 1 << 20, 1,
      lambda k: "%9d records (%9.3f MiB)" % (k, k * 64 / MIB))
+top = max(n for n in range(65000, 66000) if uaes.gcm_multikey_batch_plan(n, 2) is not None)
+print("Multi-key GCM batches: a record holds at most UAES_GCM_MULTIKEY_BATCH_MAX = %d bytes of text" % top)
+walk("Multi-key GCM batch, k records of 64 bytes (positions/thread: threads per workgroup)",
+     lambda k: uaes.gcm_multikey_batch_plan(64, max(k, 1))[:2] + (0, uaes.gcm_multikey_batch_plan(64, max(k, 1))[3]), 1, 1 << 20, 1,
+     lambda k: "%9d records (%9.3f MiB)" % (k, k * 64 / MIB))
 top = max(n for n in range(65000, 66000) if uaes.ocb_batch_plan(n, 2) is not None)
 print("OCB batches: a record holds at most UAES_OCB_BATCH_MAX = %d bytes of text" % top)
 walk("OCB batch, k records of 64 bytes (positions/thread: threads per workgroup)",
