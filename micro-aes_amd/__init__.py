@@ -594,32 +594,61 @@ def _records(items, what):
     return size, b"".join(bytes(x) for x in items)
 
 
+def _aead_batch(fn, what, per_record, aads, texts, lens, decrypt, tags, tag_len, prefill, head, tags_first=False):
+    """What the AEAD record batches share (eax_batch, ccm_batch, gcmsiv_batch, gcm_multikey_batch, ocb_batch, siv_batch):
+    one item per record in every list, the packing, the buffers, the uaes_<fn>_encrypt_batch / _decrypt_batch call and
+    the split.  per_record: the mode's own lists (AADs, tags and lens are everybody's); head(n, ml, lv): the mode's own
+    checks, then the call's arguments before the AAD; tags_first: SIV's IVs stand before the text, in the call and in
+    what an encryption returns.  Returns (texts, tags), or (code, texts, verdicts) for a decryption."""
+    n = len(texts)
+    aads = aads if aads is not None else [b""] * n
+    if any(len(x) != n for x in per_record + [aads]) or (decrypt and (tags is None or len(tags) != n)) or \
+            (lens is not None and len(lens) != n):
+        raise ValueError("one %s per record" % what)
+    if n == 0:
+        return (0, [], []) if decrypt else ([], [])
+    al, ab = _records(aads, "AADs")
+    ml, mb = _records(texts, "texts")
+    lv = (C.c_uint32 * n)(*lens) if lens is not None else None
+    name = "uaes_%s_%s_batch" % (fn, "decrypt" if decrypt else "encrypt")
+    call = getattr(engine(), name)
+    a = tuple(head(n, ml, lv)) + (_in(ab), al)
+    o = _out(n * ml, prefill)
+    if not decrypt:
+        t = _out(n * tag_len)
+        _check(call(*a, _in(mb), *((t, o) if tags_first else (o, t))), name)
+        out, tr = _split(bytes(o), ml, n), _split(bytes(t), tag_len, n)
+        return (tr, out) if tags_first else (out, tr)
+    v, t = _out(n), _in(b"".join(tags))
+    rc = _check(call(*a, *((t, _in(mb)) if tags_first else (_in(mb), t)), o, v), name)
+    return rc, _split(bytes(o), ml, n), list(bytes(v)[:n])
+
+
+def _batch_plan(hook, direction, length, nmsg):
+    """(arrangement, launches, workgroups, threads per workgroup) from a row batch's plan hook, or None"""
+    out = (C.c_int * 3)()
+    name = getattr(engine(), hook)(direction, length, nmsg, out)
+    return None if name is None else (name.decode(), out[0], out[1], out[2])
+
+
+def _nonce_tag_batch(fn, key, nonces, aads, texts, tag_len, decrypt, tags, prefill, lens):
+    """ccm_batch and ocb_batch: the nonce and tag lengths are arguments of the call"""
+    def head(n, ml, lv):
+        nl, nb = _records(nonces, "nonces")
+        if decrypt and any(len(x) != tag_len for x in tags):
+            raise ValueError("tags of tag_len bytes")
+        return _bits(key), _in(key), nl, tag_len, n, ml, lv, _in(nb)
+    return _aead_batch(fn, "nonce, AAD (tag and length)", [nonces], aads, texts, lens, decrypt, tags, tag_len, prefill, head)
+
+
 def eax_batch(key, nonces, aads, texts, decrypt=False, tags=None, prefill=0):
     """EAX of many records under one key (uaes_eax_*_batch): equal-sized nonces, AADs (or None) and texts.
     encrypt: returns (ciphertexts, 16-byte tags); decrypt (tags given): returns (code, plaintexts, verdicts), a
     forged record's plaintext stays the prefill."""
-    n = len(texts)
-    aads = aads if aads is not None else [b""] * n
-    if len(nonces) != n or len(aads) != n or (decrypt and (tags is None or len(tags) != n)):
-        raise ValueError("one nonce, AAD (and tag) per record")
-    if n == 0:
-        return (0, [], []) if decrypt else ([], [])
-    nl, nb = _records(nonces, "nonces")
-    al, ab = _records(aads, "AADs")
-    ml, mb = _records(texts, "texts")
-    L = engine()
-    o = _out(n * ml, prefill)
-    if not decrypt:
-        t = _out(n * 16)
-        _check(L.uaes_eax_encrypt_batch(_bits(key), _in(key), n, ml, _in(nb), nl, _in(ab), al, _in(mb), o, t),
-               "uaes_eax_encrypt_batch")
-        raw, tr = bytes(o), bytes(t)
-        return _split(raw, ml, n), _split(tr, 16, n)
-    v = _out(n)
-    rc = _check(L.uaes_eax_decrypt_batch(_bits(key), _in(key), n, ml, _in(nb), nl, _in(ab), al, _in(mb),
-                                         _in(b"".join(tags)), o, v), "uaes_eax_decrypt_batch")
-    raw = bytes(o)
-    return rc, _split(raw, ml, n), list(bytes(v)[:n])
+    def head(n, ml, lv):
+        nl, nb = _records(nonces, "nonces")
+        return _bits(key), _in(key), n, ml, _in(nb), nl
+    return _aead_batch("eax", "nonce, AAD (and tag)", [nonces], aads, texts, None, decrypt, tags, 16, prefill, head)
 
 
 def ccm_batch(key, nonces, aads, texts, tag_len=16, decrypt=False, tags=None, prefill=0, lens=None):
@@ -628,31 +657,7 @@ def ccm_batch(key, nonces, aads, texts, tag_len=16, decrypt=False, tags=None, pr
     verdicts); like the reference's CCM a forged record's plaintext is what CTR made of it (zeros under
     wipe_on_auth_failure).  lens (optional, one per record): record m is the first lens[m] bytes of its text, and the
     rest of its output slot stays the prefill."""
-    n = len(texts)
-    aads = aads if aads is not None else [b""] * n
-    if len(nonces) != n or len(aads) != n or (decrypt and (tags is None or len(tags) != n)) or (lens is not None and len(lens) != n):
-        raise ValueError("one nonce, AAD (tag and length) per record")
-    if n == 0:
-        return (0, [], []) if decrypt else ([], [])
-    nl, nb = _records(nonces, "nonces")
-    al, ab = _records(aads, "AADs")
-    ml, mb = _records(texts, "texts")
-    lv = (C.c_uint32 * n)(*lens) if lens is not None else None
-    L = engine()
-    o = _out(n * ml, prefill)
-    if not decrypt:
-        t = _out(n * tag_len)
-        _check(L.uaes_ccm_encrypt_batch(_bits(key), _in(key), nl, tag_len, n, ml, lv, _in(nb), _in(ab), al, _in(mb), o, t),
-               "uaes_ccm_encrypt_batch")
-        raw, tr = bytes(o), bytes(t)
-        return _split(raw, ml, n), _split(tr, tag_len, n)
-    if any(len(x) != tag_len for x in tags):
-        raise ValueError("tags of tag_len bytes")
-    v = _out(n)
-    rc = _check(L.uaes_ccm_decrypt_batch(_bits(key), _in(key), nl, tag_len, n, ml, lv, _in(nb), _in(ab), al, _in(mb),
-                                         _in(b"".join(tags)), o, v), "uaes_ccm_decrypt_batch")
-    raw = bytes(o)
-    return rc, _split(raw, ml, n), list(bytes(v)[:n])
+    return _nonce_tag_batch("ccm", key, nonces, aads, texts, tag_len, decrypt, tags, prefill, lens)
 
 
 def gcmsiv_batch(key, nonces, aads, texts, decrypt=False, tags=None, prefill=0, lens=None):
@@ -661,39 +666,17 @@ def gcmsiv_batch(key, nonces, aads, texts, decrypt=False, tags=None, prefill=0, 
     verdicts); like the reference's GCM-SIV a forged record's plaintext is what CTR made of it (zeros under
     wipe_on_auth_failure).  lens (optional, one per record): record m is the first lens[m] bytes of its text, and the
     rest of its output slot stays the prefill."""
-    n = len(texts)
-    aads = aads if aads is not None else [b""] * n
-    if len(nonces) != n or len(aads) != n or (decrypt and (tags is None or len(tags) != n)) or (lens is not None and len(lens) != n):
-        raise ValueError("one nonce, AAD (tag and length) per record")
-    if n == 0:
-        return (0, [], []) if decrypt else ([], [])
-    if any(len(x) != 12 for x in nonces) or (decrypt and any(len(x) != 16 for x in tags)):
-        raise ValueError("nonces of 12 bytes (tags of 16)")
-    nb = b"".join(nonces)
-    al, ab = _records(aads, "AADs")
-    ml, mb = _records(texts, "texts")
-    lv = (C.c_uint32 * n)(*lens) if lens is not None else None
-    L = engine()
-    o = _out(n * ml, prefill)
-    if not decrypt:
-        t = _out(n * 16)
-        _check(L.uaes_gcmsiv_encrypt_batch(_bits(key), _in(key), n, ml, lv, _in(nb), _in(ab), al, _in(mb), o, t),
-               "uaes_gcmsiv_encrypt_batch")
-        raw, tr = bytes(o), bytes(t)
-        return _split(raw, ml, n), _split(tr, 16, n)
-    v = _out(n)
-    rc = _check(L.uaes_gcmsiv_decrypt_batch(_bits(key), _in(key), n, ml, lv, _in(nb), _in(ab), al, _in(mb),
-                                            _in(b"".join(tags)), o, v), "uaes_gcmsiv_decrypt_batch")
-    raw = bytes(o)
-    return rc, _split(raw, ml, n), list(bytes(v)[:n])
+    def head(n, ml, lv):
+        if any(len(x) != 12 for x in nonces) or (decrypt and any(len(x) != 16 for x in tags)):
+            raise ValueError("nonces of 12 bytes (tags of 16)")
+        return _bits(key), _in(key), n, ml, lv, _in(b"".join(nonces))
+    return _aead_batch("gcmsiv", "nonce, AAD (tag and length)", [nonces], aads, texts, lens, decrypt, tags, 16, prefill, head)
 
 
 def gcmsiv_batch_plan(length, nmsg, decrypt=False):
     """What a GCM-SIV batch of nmsg records of `length` bytes would run (uaes_debug_plan_gcmsiv_batch): (arrangement,
     launches, workgroups, threads per workgroup), or None for arguments that make no sense."""
-    out = (C.c_int * 3)()
-    name = engine().uaes_debug_plan_gcmsiv_batch(int(bool(decrypt)), length, nmsg, out)
-    return None if name is None else (name.decode(), out[0], out[1], out[2])
+    return _batch_plan("uaes_debug_plan_gcmsiv_batch", int(bool(decrypt)), length, nmsg)
 
 
 def gcm_multikey_batch(keys, nonces, aads, texts, decrypt=False, tags=None, tag_len=16, prefill=0, lens=None):
@@ -702,41 +685,19 @@ def gcm_multikey_batch(keys, nonces, aads, texts, decrypt=False, tags=None, tag_
     decrypt (tags given): returns (code, plaintexts, verdicts); a forged record's output slot is untouched: it stays
     the prefill, whatever wipe_on_auth_failure says.  lens (optional, one per record): record m is the first lens[m]
     bytes of its text, and the rest of its output slot stays the prefill."""
-    n = len(texts)
-    aads = aads if aads is not None else [b""] * n
-    if len(keys) != n or len(nonces) != n or len(aads) != n or (decrypt and (tags is None or len(tags) != n)) or \
-            (lens is not None and len(lens) != n):
-        raise ValueError("one key, nonce, AAD (tag and length) per record")
-    if n == 0:
-        return (0, [], []) if decrypt else ([], [])
-    if any(len(x) != 12 for x in nonces) or (decrypt and any(len(x) != tag_len for x in tags)):
-        raise ValueError("nonces of 12 bytes (tags of tag_len)")
-    kl, kb = _records(keys, "keys")
-    nb = b"".join(nonces)
-    al, ab = _records(aads, "AADs")
-    ml, mb = _records(texts, "texts")
-    lv = (C.c_uint32 * n)(*lens) if lens is not None else None
-    L = engine()
-    o = _out(n * ml, prefill)
-    if not decrypt:
-        t = _out(n * tag_len)
-        _check(L.uaes_gcm_multikey_encrypt_batch(8 * kl, _in(kb), tag_len, n, ml, lv, _in(nb), _in(ab), al, _in(mb), o, t),
-               "uaes_gcm_multikey_encrypt_batch")
-        raw, tr = bytes(o), bytes(t)
-        return _split(raw, ml, n), _split(tr, tag_len, n)
-    v = _out(n)
-    rc = _check(L.uaes_gcm_multikey_decrypt_batch(8 * kl, _in(kb), tag_len, n, ml, lv, _in(nb), _in(ab), al, _in(mb),
-                                                  _in(b"".join(tags)), o, v), "uaes_gcm_multikey_decrypt_batch")
-    raw = bytes(o)
-    return rc, _split(raw, ml, n), list(bytes(v)[:n])
+    def head(n, ml, lv):
+        if any(len(x) != 12 for x in nonces) or (decrypt and any(len(x) != tag_len for x in tags)):
+            raise ValueError("nonces of 12 bytes (tags of tag_len)")
+        kl, kb = _records(keys, "keys")
+        return 8 * kl, _in(kb), tag_len, n, ml, lv, _in(b"".join(nonces))
+    return _aead_batch("gcm_multikey", "key, nonce, AAD (tag and length)", [keys, nonces], aads, texts, lens, decrypt, tags, tag_len,
+                       prefill, head)
 
 
 def gcm_multikey_batch_plan(length, nmsg, decrypt=False):
     """What a multi-key GCM batch of nmsg records of `length` bytes would run (uaes_debug_plan_gcm_multikey_batch):
     (arrangement, launches, workgroups, threads per workgroup), or None for arguments that make no sense."""
-    out = (C.c_int * 3)()
-    name = engine().uaes_debug_plan_gcm_multikey_batch(int(bool(decrypt)), length, nmsg, out)
-    return None if name is None else (name.decode(), out[0], out[1], out[2])
+    return _batch_plan("uaes_debug_plan_gcm_multikey_batch", int(bool(decrypt)), length, nmsg)
 
 
 def ocb_batch(key, nonces, aads, texts, tag_len=16, decrypt=False, tags=None, prefill=0, lens=None):
@@ -745,66 +706,22 @@ def ocb_batch(key, nonces, aads, texts, tag_len=16, decrypt=False, tags=None, pr
     verdicts); like the reference's OCB a forged record's plaintext is its decryption (zeros under
     wipe_on_auth_failure).  lens (optional, one per record): record m is the first lens[m] bytes of its text, and the
     rest of its output slot stays the prefill."""
-    n = len(texts)
-    aads = aads if aads is not None else [b""] * n
-    if len(nonces) != n or len(aads) != n or (decrypt and (tags is None or len(tags) != n)) or (lens is not None and len(lens) != n):
-        raise ValueError("one nonce, AAD (tag and length) per record")
-    if n == 0:
-        return (0, [], []) if decrypt else ([], [])
-    nl, nb = _records(nonces, "nonces")
-    al, ab = _records(aads, "AADs")
-    ml, mb = _records(texts, "texts")
-    lv = (C.c_uint32 * n)(*lens) if lens is not None else None
-    L = engine()
-    o = _out(n * ml, prefill)
-    if not decrypt:
-        t = _out(n * tag_len)
-        _check(L.uaes_ocb_encrypt_batch(_bits(key), _in(key), nl, tag_len, n, ml, lv, _in(nb), _in(ab), al, _in(mb), o, t),
-               "uaes_ocb_encrypt_batch")
-        raw, tr = bytes(o), bytes(t)
-        return _split(raw, ml, n), _split(tr, tag_len, n)
-    if any(len(x) != tag_len for x in tags):
-        raise ValueError("tags of tag_len bytes")
-    v = _out(n)
-    rc = _check(L.uaes_ocb_decrypt_batch(_bits(key), _in(key), nl, tag_len, n, ml, lv, _in(nb), _in(ab), al, _in(mb),
-                                         _in(b"".join(tags)), o, v), "uaes_ocb_decrypt_batch")
-    raw = bytes(o)
-    return rc, _split(raw, ml, n), list(bytes(v)[:n])
+    return _nonce_tag_batch("ocb", key, nonces, aads, texts, tag_len, decrypt, tags, prefill, lens)
 
 
 def ocb_batch_plan(length, nmsg, decrypt=False):
     """What an OCB batch of nmsg records of `length` bytes would run (uaes_debug_plan_ocb_batch): (arrangement,
     launches, workgroups, threads per workgroup), or None for arguments that make no sense.  decrypt may also be an
     int: a direction other than 0 / 1 has no plan."""
-    out = (C.c_int * 3)()
-    name = engine().uaes_debug_plan_ocb_batch(int(decrypt), length, nmsg, out)
-    return None if name is None else (name.decode(), out[0], out[1], out[2])
+    return _batch_plan("uaes_debug_plan_ocb_batch", int(decrypt), length, nmsg)
 
 
 def siv_batch(keys, aads, texts, decrypt=False, ivs=None, prefill=0):
     """SIV (RFC 5297) of many records under one key pair (uaes_siv_*_batch): equal-sized AADs (or None) and texts.
     encrypt: returns (ivs, ciphertexts); decrypt (ivs given): returns (code, plaintexts, verdicts)."""
-    n = len(texts)
-    aads = aads if aads is not None else [b""] * n
-    if len(aads) != n or (decrypt and (ivs is None or len(ivs) != n)):
-        raise ValueError("one AAD (and IV) per record")
-    if n == 0:
-        return (0, [], []) if decrypt else ([], [])
-    al, ab = _records(aads, "AADs")
-    ml, mb = _records(texts, "texts")
-    L = engine()
-    o = _out(n * ml, prefill)
-    if not decrypt:
-        t = _out(n * 16)
-        _check(L.uaes_siv_encrypt_batch(_bits(keys, 2), _in(keys), n, ml, _in(ab), al, _in(mb), t, o),
-               "uaes_siv_encrypt_batch")
-        raw, tr = bytes(o), bytes(t)
-        return _split(tr, 16, n), _split(raw, ml, n)
-    v = _out(n)
-    rc = _check(L.uaes_siv_decrypt_batch(_bits(keys, 2), _in(keys), n, ml, _in(ab), al, _in(b"".join(ivs)), _in(mb), o, v),
-                "uaes_siv_decrypt_batch")
-    raw = bytes(o)
-    return rc, _split(raw, ml, n), list(bytes(v)[:n])
+    def head(n, ml, lv):
+        return _bits(keys, 2), _in(keys), n, ml
+    return _aead_batch("siv", "AAD (and IV)", [], aads, texts, None, decrypt, ivs, 16, prefill, head, tags_first=True)
 
 
 def eax_siv_plan(siv, length, nmsg=1, decrypt=False):

@@ -1340,7 +1340,8 @@ int stage_text(lane *L, int k, const void *user, size_t n, int prefill, void **d
     return 0;
 }
 
-/* ---- a row batch's arrays (uaes_engine_modes.c: the EAX / SIV, CCM, key-wrap, FF1 and FF3-1 batches) ----
+/* ---- a row batch's arrays (uaes_engine_modes.c: aead_rows_staged for every AEAD record batch -- EAX, SIV, CCM,
+ * GCM-SIV, multi-key GCM and OCB -- and the key-wrap, FF1 and FF3-1 batches) ----
  * The caller lists its side arrays (row_array, uaes_engine.h) and its two texts (row_text) and calls row_stage,
  * row_texts, its launcher and row_finish, in this order.  A device array goes to the kernel as it is; host arrays
  * share the lane's scratch, SIDE(bytes) each.  The offsets and the size asked of lane_scratch come from the one list,
@@ -1475,29 +1476,27 @@ const char *uaes_debug_plan_ff3(int dir, unsigned radix, size_t len, size_t nrec
     if (out) { out[0] = p.launches; out[1] = (int)p.grid; out[2] = (int)p.steps; }
     return uaesk_ff3_arrangement_name(p.arrangement);
 }
-const char *uaes_debug_plan_gcmsiv_batch(int dir, size_t len, size_t nmsg, int out[3])
+/* a row batch's hook: the plan of (dir, len, nmsg) under its arrangement's name; NULL for arguments its planner refuses */
+static const char *debug_plan_rows(int (*plan)(int, size_t, size_t, uaes_plan *), const char *(*name)(int), int dir, size_t len,
+                                   size_t nmsg, int out[3])
 {
     uaes_plan p;
     memset(&p, 0, sizeof p);
-    if (uaesk_plan_gcmsiv_batch(dir, len, nmsg, &p)) return NULL;
+    if (plan(dir, len, nmsg, &p)) return NULL;
     if (out) { out[0] = p.launches; out[1] = (int)p.grid; out[2] = (int)p.steps; }
-    return uaesk_gcmsiv_batch_arrangement_name(p.arrangement);
+    return name(p.arrangement);
+}
+const char *uaes_debug_plan_gcmsiv_batch(int dir, size_t len, size_t nmsg, int out[3])
+{
+    return debug_plan_rows(uaesk_plan_gcmsiv_batch, uaesk_gcmsiv_batch_arrangement_name, dir, len, nmsg, out);
 }
 const char *uaes_debug_plan_gcm_multikey_batch(int dir, size_t len, size_t nmsg, int out[3])
 {
-    uaes_plan p;
-    memset(&p, 0, sizeof p);
-    if (uaesk_plan_gcm_multikey_batch(dir, len, nmsg, &p)) return NULL;
-    if (out) { out[0] = p.launches; out[1] = (int)p.grid; out[2] = (int)p.steps; }
-    return uaesk_gcm_multikey_arrangement_name(p.arrangement);
+    return debug_plan_rows(uaesk_plan_gcm_multikey_batch, uaesk_gcm_multikey_arrangement_name, dir, len, nmsg, out);
 }
 const char *uaes_debug_plan_ocb_batch(int dir, size_t len, size_t nmsg, int out[3])
 {
-    uaes_plan p;
-    memset(&p, 0, sizeof p);
-    if (uaesk_plan_ocb_batch(dir, len, nmsg, &p)) return NULL;
-    if (out) { out[0] = p.launches; out[1] = (int)p.grid; out[2] = (int)p.steps; }
-    return uaesk_ocb_batch_arrangement_name(p.arrangement);
+    return debug_plan_rows(uaesk_plan_ocb_batch, uaesk_ocb_batch_arrangement_name, dir, len, nmsg, out);
 }
 const char *uaes_debug_plan_ocb(int dir, size_t len, size_t aad_len, int aad_aligned, int out[5])
 {

@@ -698,126 +698,157 @@ int uaes_siv_decrypt(int keybits, const uint8_t *keys, const uint8_t iv[16], con
     return siv_common(keybits, keys, 1, (uint8_t *)iv, aData, aDataLen, crtxt, crtxtLen, pntxt);
 }
 
-/* Batches: nmsg records of msg_bytes each under one key, sixteen lanes per record.  Every array may be host or
- * device memory; host arrays travel through the lane's staging buffers and scratch.  An EAX decryption writes only
- * authentic records: the output buffer starts as the caller's (host memory is copied in first).                   */
-static int aead_batch(int siv, int decrypt, int keybits, const uint8_t *key, size_t nmsg, size_t msg_bytes,
-                      const uint8_t *nonces, size_t nonce_len, const void *aData, size_t aad_bytes,
-                      const void *in, void *outp, uint8_t *tags, uint8_t *verdicts)
+/* ---- AEAD record batches: EAX, SIV, CCM, GCM-SIV, multi-key GCM and OCB ----
+ * nmsg records of msg_bytes each in one launch, sixteen lanes per record.  Every array may be host or device memory;
+ * host arrays travel through the lane's staging buffers and scratch.  A mode checks its own limits, describes the call
+ * in an aead_rows and hands it to aead_rows_run, which does everything the modes share, in this order: the sizes, the
+ * key, nothing more for no records, the pointers, and only then the device.  What a mode adds is its launch.       */
+enum { AB_KEYS, AB_NONCES, AB_AAD, AB_LENS, AB_TAGS, AB_VERDICTS, AB_NSIDE };      /* the side arrays, in scratch order */
+
+typedef struct aead_rows aead_rows;
+struct aead_rows {
+    const char    *name;                /* of the mode, for a launch that fails */
+    int            nkeys, keybits;      /* host key schedules made of `key`: 1, SIV's 2, or 0 (AB_KEYS: the kernel expands them) */
+    const uint8_t *key;
+    int            decrypt;             /* tags are read and verdicts written, not tags written */
+    int            prefill;             /* the kernel leaves records unwritten: the output's staging starts as the caller's
+                                         * buffer (row_text).  With AB_LENS it does so whatever this says: the rest of a slot */
+    size_t         nmsg, msg_bytes;
+    const void    *in;
+    void          *out;
+    struct { const void *p; size_t each; } side[AB_NSIDE];   /* the caller's arrays and their bytes per record; 0: the
+                                                              * call has no such array */
+    int          (*launch)(const aead_rows *b, context *c, lane *L, const keysched *ks, const row_array *a, const row_text *t);
+};
+
+static int aead_rows_staged(const aead_rows *b, const keysched *ks)
 {
     context *c;
     lane *L;
-    keysched k1, k2;
-    int rc, bad;
-    if ((msg_bytes && nmsg > (size_t)-1 / msg_bytes) || (nonce_len && nmsg > (size_t)-1 / nonce_len) ||
-        (aad_bytes && nmsg > (size_t)-1 / aad_bytes) || nmsg > (size_t)-1 / 16)
-        return fail(UAES_E_ARG, "batch size overflows");
-    if ((rc = siv ? siv_keys(&k1, &k2, key, keybits) : expand_key(&k1, key, keybits)) != 0) return rc;
-    if (nmsg == 0) { burn(&k1, sizeof k1); burn(&k2, sizeof k2); return 0; }
-    {
-        const size_t total = nmsg * msg_bytes;
-        if ((total && (!in || !outp)) || !tags || (decrypt && !verdicts) || (!siv && nonce_len && !nonces) ||
-            (aad_bytes && !aData)) {
-            burn(&k1, sizeof k1); burn(&k2, sizeof k2);
-            return fail(UAES_E_ARG, "NULL pointer");
-        }
-        if ((rc = enter(&c, &L)) != 0) { burn(&k1, sizeof k1); burn(&k2, sizeof k2); return rc; }
-        enum { NONCES, AAD, TAGS, VERDICTS, NSIDE };
-        row_array a[NSIDE] = { { nonces, siv ? 0 : nmsg * nonce_len, 0, NULL }, { aData, nmsg * aad_bytes, 0, NULL },
-                               { tags, nmsg * 16, !decrypt, NULL }, { verdicts, decrypt ? nmsg : 0, 1, NULL } };
-        row_text t = { in, outp, total, total, decrypt && !siv, NULL, NULL };
-        if ((rc = row_stage(L, a, NSIDE, decrypt)) != 0) goto out;
-        if ((rc = row_texts(L, &t)) != 0) goto out;
-        if (siv)
-            ES_KCHK("siv batch", uaesk_s2v_batch(L->stream, &c->tb, k1.nr, &k1.ek, &k2.ek, decrypt, wipe_on_auth_failure(),
-                                                 a[AAD].d, aad_bytes, nmsg, msg_bytes, t.d_in, t.d_out, a[TAGS].d,
-                                                 a[VERDICTS].d, L->d_status));
-        else
-            ES_KCHK("eax batch", uaesk_eax_batch(L->stream, &c->tb, k1.nr, &k1.ek, decrypt, a[NONCES].d, nonce_len, a[AAD].d,
-                                                 aad_bytes, nmsg, msg_bytes, t.d_in, t.d_out, a[TAGS].d, a[VERDICTS].d,
-                                                 L->d_status));
-        if ((rc = row_finish(L, &t, a, NSIDE, decrypt, &bad)) != 0) goto out;
-        rc = bad ? UAES_E_AUTHENTICATION : 0;
+    const size_t total = b->nmsg * b->msg_bytes;
+    row_array a[AB_NSIDE];
+    row_text t = { b->in, b->out, total, total, b->prefill || b->side[AB_LENS].each, NULL, NULL };
+    int i, rc, bad;
+    if (total && (!b->in || !b->out)) return fail(UAES_E_ARG, "NULL pointer");
+    for (i = 0; i < AB_NSIDE; ++i) {
+        if (b->side[i].each && !b->side[i].p) return fail(UAES_E_ARG, "NULL pointer");
+        a[i] = (row_array){ b->side[i].p, b->nmsg * b->side[i].each, i == AB_VERDICTS || (i == AB_TAGS && !b->decrypt), NULL };
     }
-out:
-    burn(&k1, sizeof k1);
-    burn(&k2, sizeof k2);
+    if ((rc = enter(&c, &L)) != 0) return rc;
+    if ((rc = row_stage(L, a, AB_NSIDE, b->decrypt)) == 0 && (rc = row_texts(L, &t)) == 0) {
+        const int e = b->launch(b, c, L, ks, a, &t);
+        if (e != 0) rc = fail(UAES_E_HIP, "%s launch: %s", b->name, hipGetErrorString((hipError_t)e));
+    }
+    if (b->side[AB_KEYS].each) {
+        /* keys in host memory went through the scratch: that copy is cleared in stream order before the call returns,
+         * however far it got (a failure to clear is reported if nothing failed before), and an error waits for it */
+        if (a[AB_KEYS].d && a[AB_KEYS].d != b->side[AB_KEYS].p &&
+            hipMemsetAsync(a[AB_KEYS].d, 0, a[AB_KEYS].bytes, (hipStream_t)L->stream) != hipSuccess && rc == 0)
+            rc = fail(UAES_E_HIP, "clearing the staged keys failed");
+        if (rc) (void)hipStreamSynchronize((hipStream_t)L->stream);
+    }
+    if (rc == 0 && (rc = row_finish(L, &t, a, AB_NSIDE, b->decrypt, &bad)) == 0 && bad) rc = UAES_E_AUTHENTICATION;
     DONE(L, rc);
+}
+
+static int aead_rows_run(const aead_rows *b)
+{
+    keysched ks[2];
+    size_t widest = b->msg_bytes;
+    int i, rc;
+    for (i = 0; i < AB_NSIDE; ++i)
+        if (b->side[i].each > widest) widest = b->side[i].each;
+    if (widest && b->nmsg > (size_t)-1 / 8 / widest)     /* / 8: the side arrays and their padding still add up */
+        return fail(UAES_E_ARG, "batch size overflows");
+    rc = b->nkeys == 2 ? siv_keys(&ks[0], &ks[1], b->key, b->keybits) : b->nkeys ? expand_key(&ks[0], b->key, b->keybits) : 0;
+    if (rc == 0 && b->nmsg) rc = aead_rows_staged(b, ks);
+    burn(ks, (size_t)b->nkeys * sizeof ks[0]);
+    return rc;
+}
+
+/* EAX and SIV batches (k_eax_batch, k_s2v_batch: uaes_eax_siv.hip): 16-byte tags; SIV has no nonces, and its IVs are
+ * its tags.  An EAX decryption writes only authentic records, so its output starts as the caller's buffer. */
+static int eax_batch_launch(const aead_rows *b, context *c, lane *L, const keysched *ks, const row_array *a, const row_text *t)
+{
+    return uaesk_eax_batch(L->stream, &c->tb, ks->nr, &ks->ek, b->decrypt, a[AB_NONCES].d, b->side[AB_NONCES].each, a[AB_AAD].d,
+                           b->side[AB_AAD].each, b->nmsg, b->msg_bytes, t->d_in, t->d_out, a[AB_TAGS].d, a[AB_VERDICTS].d,
+                           L->d_status);
+}
+
+static int siv_batch_launch(const aead_rows *b, context *c, lane *L, const keysched *ks, const row_array *a, const row_text *t)
+{
+    return uaesk_s2v_batch(L->stream, &c->tb, ks[0].nr, &ks[0].ek, &ks[1].ek, b->decrypt, wipe_on_auth_failure(), a[AB_AAD].d,
+                           b->side[AB_AAD].each, b->nmsg, b->msg_bytes, t->d_in, t->d_out, a[AB_TAGS].d, a[AB_VERDICTS].d,
+                           L->d_status);
+}
+
+static int eax_siv_batch(int siv, int decrypt, int keybits, const uint8_t *key, size_t nmsg, size_t msg_bytes,
+                         const uint8_t *nonces, size_t nonce_len, const void *aData, size_t aad_bytes,
+                         const void *in, void *outp, uint8_t *tags, uint8_t *verdicts)
+{
+    const aead_rows b = {
+        .name = siv ? "siv batch" : "eax batch", .launch = siv ? siv_batch_launch : eax_batch_launch,
+        .nkeys = siv ? 2 : 1, .keybits = keybits, .key = key, .decrypt = decrypt, .prefill = decrypt && !siv,
+        .nmsg = nmsg, .msg_bytes = msg_bytes, .in = in, .out = outp,
+        .side = { [AB_NONCES] = { nonces, nonce_len }, [AB_AAD] = { aData, aad_bytes }, [AB_TAGS] = { tags, 16 },
+                  [AB_VERDICTS] = { verdicts, decrypt } } };
+    return aead_rows_run(&b);
 }
 
 int uaes_eax_encrypt_batch(int keybits, const uint8_t *key, size_t nmsg, size_t msg_bytes,
                            const uint8_t *nonces, size_t nonce_len, const void *aData, size_t aad_bytes,
                            const void *pntxt, void *crtxt, uint8_t *tags)
 {
-    return aead_batch(0, 0, keybits, key, nmsg, msg_bytes, nonces, nonce_len, aData, aad_bytes, pntxt, crtxt, tags, NULL);
+    return eax_siv_batch(0, 0, keybits, key, nmsg, msg_bytes, nonces, nonce_len, aData, aad_bytes, pntxt, crtxt, tags, NULL);
 }
 
 int uaes_eax_decrypt_batch(int keybits, const uint8_t *key, size_t nmsg, size_t msg_bytes,
                            const uint8_t *nonces, size_t nonce_len, const void *aData, size_t aad_bytes,
                            const void *crtxt, const uint8_t *tags, void *pntxt, uint8_t *verdicts)
 {
-    return aead_batch(0, 1, keybits, key, nmsg, msg_bytes, nonces, nonce_len, aData, aad_bytes, crtxt, pntxt,
-                      (uint8_t *)tags, verdicts);
+    return eax_siv_batch(0, 1, keybits, key, nmsg, msg_bytes, nonces, nonce_len, aData, aad_bytes, crtxt, pntxt,
+                         (uint8_t *)tags, verdicts);
 }
 
 int uaes_siv_encrypt_batch(int keybits, const uint8_t *keys, size_t nmsg, size_t msg_bytes,
                            const void *aData, size_t aad_bytes, const void *pntxt, uint8_t *ivs, void *crtxt)
 {
-    return aead_batch(1, 0, keybits, keys, nmsg, msg_bytes, NULL, 0, aData, aad_bytes, pntxt, crtxt, ivs, NULL);
+    return eax_siv_batch(1, 0, keybits, keys, nmsg, msg_bytes, NULL, 0, aData, aad_bytes, pntxt, crtxt, ivs, NULL);
 }
 
 int uaes_siv_decrypt_batch(int keybits, const uint8_t *keys, size_t nmsg, size_t msg_bytes,
                            const void *aData, size_t aad_bytes, const uint8_t *ivs, const void *crtxt, void *pntxt,
                            uint8_t *verdicts)
 {
-    return aead_batch(1, 1, keybits, keys, nmsg, msg_bytes, NULL, 0, aData, aad_bytes, crtxt, pntxt, (uint8_t *)ivs,
-                      verdicts);
+    return eax_siv_batch(1, 1, keybits, keys, nmsg, msg_bytes, NULL, 0, aData, aad_bytes, crtxt, pntxt, (uint8_t *)ivs,
+                         verdicts);
 }
 
-/* CCM batches (k_ccm_batch, uaes_mac.hip): as aead_batch, with the nonce and tag lengths, packed tags of tagLen bytes
- * and optional per-record lengths.  Like the reference's CCM a decryption writes the text before it knows the tag, so
- * the output buffer need not start as the caller's -- except with `lens`, where the remainder of a slot is not written
- * and a host buffer is copied in first.  Every argument is checked before the device is touched.                   */
+/* CCM batches (k_ccm_batch, uaes_mac.hip): the nonce and tag lengths are arguments, the tags are packed, tagLen bytes
+ * each, and `lens` may give every record a length of its own.  Like the reference's CCM a decryption writes the text
+ * before it knows the tag, so the output need not start as the caller's buffer. */
+static int ccm_batch_launch(const aead_rows *b, context *c, lane *L, const keysched *ks, const row_array *a, const row_text *t)
+{
+    return uaesk_ccm_batch(L->stream, &c->tb, ks->nr, &ks->ek, b->decrypt, wipe_on_auth_failure(), a[AB_NONCES].d,
+                           b->side[AB_NONCES].each, b->side[AB_TAGS].each, a[AB_AAD].d, b->side[AB_AAD].each, b->nmsg,
+                           b->msg_bytes, a[AB_LENS].d, t->d_in, t->d_out, a[AB_TAGS].d, a[AB_VERDICTS].d, L->d_status);
+}
+
 static int ccm_batch(int decrypt, int keybits, const uint8_t *key, size_t nonceLen, size_t tagLen, size_t nmsg,
                      size_t msg_bytes, const uint32_t *lens, const uint8_t *nonces, const void *aData, size_t aad_bytes,
                      const void *in, void *outp, uint8_t *tags, uint8_t *verdicts)
 {
-    context *c;
-    lane *L;
-    keysched ks;
-    const size_t lim = (size_t)-1 / 8;               /* five side arrays and their padding still add up */
-    int rc, bad;
+    const aead_rows b = {
+        .name = "ccm batch", .launch = ccm_batch_launch, .nkeys = 1, .keybits = keybits, .key = key, .decrypt = decrypt,
+        .nmsg = nmsg, .msg_bytes = msg_bytes, .in = in, .out = outp,
+        .side = { [AB_NONCES] = { nonces, nonceLen }, [AB_AAD] = { aData, aad_bytes },
+                  [AB_LENS] = { lens, lens ? sizeof *lens : 0 }, [AB_TAGS] = { tags, tagLen }, [AB_VERDICTS] = { verdicts, decrypt } } };
+    int rc;
     if ((rc = ccm_lens_ok(nonceLen, tagLen)) != 0) return rc;
     if (msg_bytes > UAES_CCM_BATCH_MAX)
         return fail(UAES_E_ARG, "a CCM batch record holds at most %zu bytes (got %zu)", (size_t)UAES_CCM_BATCH_MAX, msg_bytes);
     if (aad_bytes > 0xFEFF) return fail(UAES_E_ARG, "a CCM batch record takes at most 65279 bytes of AAD (got %zu)", aad_bytes);
-    if (nmsg > lim / (msg_bytes > 16 ? msg_bytes : 16) || (aad_bytes && nmsg > lim / aad_bytes))
-        return fail(UAES_E_ARG, "batch size overflows");
-    if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
-    if (nmsg == 0) { burn(&ks, sizeof ks); return 0; }
-    {
-        const size_t total = nmsg * msg_bytes;
-        if ((total && (!in || !outp)) || !nonces || !tags || (decrypt && !verdicts) || (aad_bytes && !aData)) {
-            burn(&ks, sizeof ks);
-            return fail(UAES_E_ARG, "NULL pointer");
-        }
-        if ((rc = enter(&c, &L)) != 0) { burn(&ks, sizeof ks); return rc; }
-        enum { NONCES, AAD, LENS, TAGS, VERDICTS, NSIDE };
-        row_array a[NSIDE] = { { nonces, nmsg * nonceLen, 0, NULL }, { aData, nmsg * aad_bytes, 0, NULL },
-                               { lens, lens ? nmsg * sizeof *lens : 0, 0, NULL }, { tags, nmsg * tagLen, !decrypt, NULL },
-                               { verdicts, decrypt ? nmsg : 0, 1, NULL } };
-        row_text t = { in, outp, total, total, lens != NULL, NULL, NULL };
-        if ((rc = row_stage(L, a, NSIDE, decrypt)) != 0) goto out;
-        if ((rc = row_texts(L, &t)) != 0) goto out;
-        ES_KCHK("ccm batch", uaesk_ccm_batch(L->stream, &c->tb, ks.nr, &ks.ek, decrypt, wipe_on_auth_failure(), a[NONCES].d,
-                                             nonceLen, tagLen, a[AAD].d, aad_bytes, nmsg, msg_bytes, a[LENS].d, t.d_in, t.d_out,
-                                             a[TAGS].d, a[VERDICTS].d, L->d_status));
-        if ((rc = row_finish(L, &t, a, NSIDE, decrypt, &bad)) != 0) goto out;
-        rc = bad ? UAES_E_AUTHENTICATION : 0;
-    }
-out:
-    burn(&ks, sizeof ks);
-    DONE(L, rc);
+    return aead_rows_run(&b);
 }
 
 int uaes_ccm_encrypt_batch(int keybits, const uint8_t *key, size_t nonceLen, size_t tagLen,
@@ -839,48 +870,28 @@ int uaes_ccm_decrypt_batch(int keybits, const uint8_t *key, size_t nonceLen, siz
 
 /* GCM-SIV batches (k_gcmsiv_batch, uaes_gcmsiv_batch.hip): as ccm_batch with 12-byte nonces and 16-byte tags.  `key` is
  * the MASTER key: only its schedule is made here, every record derives and expands its own keys in the kernel.  Like
- * the reference's GCM-SIV a decryption writes the text before it knows the tag.  Every argument is checked before the
- * device is touched. */
+ * the reference's GCM-SIV a decryption writes the text before it knows the tag. */
+static int gcmsiv_batch_launch(const aead_rows *b, context *c, lane *L, const keysched *ks, const row_array *a, const row_text *t)
+{
+    return uaesk_gcmsiv_batch(L->stream, &c->tb, ks->nr, &ks->ek, b->decrypt, wipe_on_auth_failure(), a[AB_NONCES].d, a[AB_AAD].d,
+                              b->side[AB_AAD].each, b->nmsg, b->msg_bytes, a[AB_LENS].d, t->d_in, t->d_out, a[AB_TAGS].d,
+                              a[AB_VERDICTS].d, L->d_status);
+}
+
 static int gcmsiv_batch(int decrypt, int keybits, const uint8_t *key, size_t nmsg, size_t msg_bytes, const uint32_t *lens,
                         const uint8_t *nonces, const void *aData, size_t aad_bytes, const void *in, void *outp,
                         uint8_t *tags, uint8_t *verdicts)
 {
-    context *c;
-    lane *L;
-    keysched ks;
-    const size_t lim = (size_t)-1 / 8;               /* five side arrays and their padding still add up */
-    int rc, bad;
+    const aead_rows b = {
+        .name = "gcm-siv batch", .launch = gcmsiv_batch_launch, .nkeys = 1, .keybits = keybits, .key = key, .decrypt = decrypt,
+        .nmsg = nmsg, .msg_bytes = msg_bytes, .in = in, .out = outp,
+        .side = { [AB_NONCES] = { nonces, 12 }, [AB_AAD] = { aData, aad_bytes },
+                  [AB_LENS] = { lens, lens ? sizeof *lens : 0 }, [AB_TAGS] = { tags, 16 }, [AB_VERDICTS] = { verdicts, decrypt } } };
     if (msg_bytes > UAES_GCMSIV_BATCH_MAX)
         return fail(UAES_E_ARG, "a GCM-SIV batch record holds at most %zu bytes (got %zu)", (size_t)UAES_GCMSIV_BATCH_MAX, msg_bytes);
     if (aad_bytes > UAES_GCMSIV_BATCH_MAX)
         return fail(UAES_E_ARG, "a GCM-SIV batch record takes at most %zu bytes of AAD (got %zu)", (size_t)UAES_GCMSIV_BATCH_MAX, aad_bytes);
-    if (nmsg > lim / (msg_bytes > 16 ? msg_bytes : 16) || (aad_bytes && nmsg > lim / aad_bytes))
-        return fail(UAES_E_ARG, "batch size overflows");
-    if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
-    if (nmsg == 0) { burn(&ks, sizeof ks); return 0; }
-    {
-        const size_t total = nmsg * msg_bytes;
-        if ((total && (!in || !outp)) || !nonces || !tags || (decrypt && !verdicts) || (aad_bytes && !aData)) {
-            burn(&ks, sizeof ks);
-            return fail(UAES_E_ARG, "NULL pointer");
-        }
-        if ((rc = enter(&c, &L)) != 0) { burn(&ks, sizeof ks); return rc; }
-        enum { NONCES, AAD, LENS, TAGS, VERDICTS, NSIDE };
-        row_array a[NSIDE] = { { nonces, nmsg * 12, 0, NULL }, { aData, nmsg * aad_bytes, 0, NULL },
-                               { lens, lens ? nmsg * sizeof *lens : 0, 0, NULL }, { tags, nmsg * 16, !decrypt, NULL },
-                               { verdicts, decrypt ? nmsg : 0, 1, NULL } };
-        row_text t = { in, outp, total, total, lens != NULL, NULL, NULL };
-        if ((rc = row_stage(L, a, NSIDE, decrypt)) != 0) goto out;
-        if ((rc = row_texts(L, &t)) != 0) goto out;
-        ES_KCHK("gcm-siv batch", uaesk_gcmsiv_batch(L->stream, &c->tb, ks.nr, &ks.ek, decrypt, wipe_on_auth_failure(),
-                                                    a[NONCES].d, a[AAD].d, aad_bytes, nmsg, msg_bytes, a[LENS].d, t.d_in,
-                                                    t.d_out, a[TAGS].d, a[VERDICTS].d, L->d_status));
-        if ((rc = row_finish(L, &t, a, NSIDE, decrypt, &bad)) != 0) goto out;
-        rc = bad ? UAES_E_AUTHENTICATION : 0;
-    }
-out:
-    burn(&ks, sizeof ks);
-    DONE(L, rc);
+    return aead_rows_run(&b);
 }
 
 int uaes_gcmsiv_encrypt_batch(int keybits, const uint8_t *key, size_t nmsg, size_t msg_bytes, const uint32_t *lens,
@@ -900,57 +911,35 @@ int uaes_gcmsiv_decrypt_batch(int keybits, const uint8_t *key, size_t nmsg, size
 
 /* Multi-key GCM batches (k_gcm_multikey, uaes_gcm_multikey.hip): as gcmsiv_batch with packed tags of tagLen bytes and
  * `keys` as one more side array, nmsg * keybits / 8 bytes in host or device memory -- no key is expanded here, every
- * record's schedule is made in the kernel, so keybits is validated on its own.  A host key array travels through the
- * lane's scratch like the other side arrays, and that copy is cleared in stream order before the call returns, whether
- * the launch was reached or not.  Decrypt keeps N7 per record: the kernel writes an authentic record only, so the
- * output's staging starts as the caller's buffer, and uaes_set_wipe_on_auth_failure does not apply.  Every argument is
- * checked before the device is touched. */
+ * record's schedule is made in the kernel, so keybits is validated on its own.  (A host key array's way through the
+ * scratch, and how that copy is cleared: aead_rows_staged.)  Decrypt keeps N7 per record: the kernel writes an
+ * authentic record only, so the output's staging starts as the caller's buffer, and uaes_set_wipe_on_auth_failure does
+ * not apply. */
+static int gcm_multikey_batch_launch(const aead_rows *b, context *c, lane *L, const keysched *ks, const row_array *a,
+                                     const row_text *t)
+{
+    (void)ks;
+    return uaesk_gcm_multikey_batch(L->stream, &c->tb, b->keybits / 32 + 6, b->decrypt, b->side[AB_TAGS].each, a[AB_KEYS].d,
+                                    a[AB_NONCES].d, a[AB_AAD].d, b->side[AB_AAD].each, b->nmsg, b->msg_bytes, a[AB_LENS].d, t->d_in,
+                                    t->d_out, a[AB_TAGS].d, a[AB_VERDICTS].d, L->d_status);
+}
+
 static int gcm_multikey_batch(int decrypt, int keybits, const uint8_t *keys, size_t tagLen, size_t nmsg, size_t msg_bytes,
                               const uint32_t *lens, const uint8_t *nonces, const void *aData, size_t aad_bytes,
                               const void *in, void *outp, uint8_t *tags, uint8_t *verdicts)
 {
-    context *c;
-    lane *L;
-    const size_t lim = (size_t)-1 / 8;               /* six side arrays and their padding still add up */
-    int rc, bad;
+    const aead_rows b = {
+        .name = "gcm multi-key batch", .launch = gcm_multikey_batch_launch, .nkeys = 0, .keybits = keybits, .decrypt = decrypt,
+        .prefill = decrypt, .nmsg = nmsg, .msg_bytes = msg_bytes, .in = in, .out = outp,
+        .side = { [AB_KEYS] = { keys, (size_t)keybits / 8 }, [AB_NONCES] = { nonces, 12 }, [AB_AAD] = { aData, aad_bytes },
+                  [AB_LENS] = { lens, lens ? sizeof *lens : 0 }, [AB_TAGS] = { tags, tagLen }, [AB_VERDICTS] = { verdicts, decrypt } } };
     if (keybits != 128 && keybits != 192 && keybits != 256) return fail(UAES_E_ARG, "key bits must be 128, 192 or 256 (got %d)", keybits);
     if (tagLen < 1 || tagLen > 16) return fail(UAES_E_ARG, "a GCM tag has 1 to 16 bytes (got %zu)", tagLen);
     if (msg_bytes > UAES_GCM_MULTIKEY_BATCH_MAX)
         return fail(UAES_E_ARG, "a multi-key GCM batch record holds at most %zu bytes (got %zu)", (size_t)UAES_GCM_MULTIKEY_BATCH_MAX, msg_bytes);
     if (aad_bytes > UAES_GCM_MULTIKEY_BATCH_MAX)
         return fail(UAES_E_ARG, "a multi-key GCM batch record takes at most %zu bytes of AAD (got %zu)", (size_t)UAES_GCM_MULTIKEY_BATCH_MAX, aad_bytes);
-    if (nmsg > lim / (msg_bytes > 32 ? msg_bytes : 32) || (aad_bytes && nmsg > lim / aad_bytes))    /* 32: the longest key */
-        return fail(UAES_E_ARG, "batch size overflows");
-    if (nmsg == 0) return 0;
-    {
-        const size_t total = nmsg * msg_bytes, key_bytes = nmsg * ((size_t)keybits / 8);
-        if ((total && (!in || !outp)) || !keys || !nonces || !tags || (decrypt && !verdicts) || (aad_bytes && !aData))
-            return fail(UAES_E_ARG, "NULL pointer");
-        if ((rc = enter(&c, &L)) != 0) return rc;
-        enum { KEYS, NONCES, AAD, LENS, TAGS, VERDICTS, NSIDE };
-        row_array a[NSIDE] = { { keys, key_bytes, 0, NULL }, { nonces, nmsg * 12, 0, NULL }, { aData, nmsg * aad_bytes, 0, NULL },
-                               { lens, lens ? nmsg * sizeof *lens : 0, 0, NULL }, { tags, nmsg * tagLen, !decrypt, NULL },
-                               { verdicts, decrypt ? nmsg : 0, 1, NULL } };
-        row_text t = { in, outp, total, total, decrypt || lens != NULL, NULL, NULL };
-        if ((rc = row_stage(L, a, NSIDE, decrypt)) == 0 && (rc = row_texts(L, &t)) == 0) {
-            const int e = uaesk_gcm_multikey_batch(L->stream, &c->tb, keybits / 32 + 6, decrypt, tagLen, a[KEYS].d, a[NONCES].d,
-                                                   a[AAD].d, aad_bytes, nmsg, msg_bytes, a[LENS].d, t.d_in, t.d_out, a[TAGS].d,
-                                                   a[VERDICTS].d, L->d_status);
-            if (e != 0) rc = fail(UAES_E_HIP, "gcm multi-key batch failed: %s", hipGetErrorString((hipError_t)e));
-        }
-        /* the staged copy of a host key array (row_stage lists KEYS first: the start of the scratch, if it got that far) */
-        if (a[KEYS].d && a[KEYS].d != (const void *)keys &&
-            hipMemsetAsync(a[KEYS].d, 0, key_bytes, (hipStream_t)L->stream) != hipSuccess && rc == 0)
-            rc = fail(UAES_E_HIP, "clearing the staged keys failed");
-        if (rc) {
-            (void)hipStreamSynchronize((hipStream_t)L->stream);
-            goto out;
-        }
-        if ((rc = row_finish(L, &t, a, NSIDE, decrypt, &bad)) != 0) goto out;
-        rc = bad ? UAES_E_AUTHENTICATION : 0;
-    }
-out:
-    DONE(L, rc);
+    return aead_rows_run(&b);
 }
 
 int uaes_gcm_multikey_encrypt_batch(int keybits, const uint8_t *keys, size_t tagLen, size_t nmsg, size_t msg_bytes,
@@ -1589,52 +1578,33 @@ int uaes_ocb_decrypt(int keybits, const uint8_t *key, const uint8_t *nonce,
     return ocb_common(keybits, key, nonce, 12, 16, 1, aData, aDataLen, crtxt, crtxtLen, pntxt);
 }
 
-/* OCB batches (k_ocb_batch, uaes_ocb.hip): as ccm_batch, with OCB's nonce and tag lengths and both key schedules (a
- * decrypting record needs the inverse cipher for its text and the forward one for K_top, HASH, the pad and the tag).
- * Like the reference's OCB a decryption writes the text before it knows the tag.  The batch always runs on the GPU: the
- * host policy of the one-message calls does not apply.  Every argument is checked before the device is touched. */
+/* OCB batches (k_ocb_batch, uaes_ocb.hip): as ccm_batch (aead_rows_run), with OCB's nonce and tag lengths and both key
+ * schedules (a decrypting record needs the inverse cipher for its text and the forward one for K_top, HASH, the pad and
+ * the tag).  Like the reference's OCB a decryption writes the text before it knows the tag.  The batch always runs on
+ * the GPU: the host policy of the one-message calls does not apply. */
+static int ocb_batch_launch(const aead_rows *b, context *c, lane *L, const keysched *ks, const row_array *a, const row_text *t)
+{
+    return uaesk_ocb_batch(L->stream, &c->tb, ks->nr, &ks->ek, &ks->dk, b->decrypt, wipe_on_auth_failure(), a[AB_NONCES].d,
+                           b->side[AB_NONCES].each, b->side[AB_TAGS].each, a[AB_AAD].d, b->side[AB_AAD].each, b->nmsg,
+                           b->msg_bytes, a[AB_LENS].d, t->d_in, t->d_out, a[AB_TAGS].d, a[AB_VERDICTS].d, L->d_status);
+}
+
 static int ocb_batch(int decrypt, int keybits, const uint8_t *key, size_t nonceLen, size_t tagLen, size_t nmsg,
                      size_t msg_bytes, const uint32_t *lens, const uint8_t *nonces, const void *aData, size_t aad_bytes,
                      const void *in, void *outp, uint8_t *tags, uint8_t *verdicts)
 {
-    context *c;
-    lane *L;
-    keysched ks;
-    const size_t lim = (size_t)-1 / 8;               /* five side arrays and their padding still add up */
-    int rc, bad;
+    const aead_rows b = {
+        .name = "ocb batch", .launch = ocb_batch_launch, .nkeys = 1, .keybits = keybits, .key = key, .decrypt = decrypt,
+        .nmsg = nmsg, .msg_bytes = msg_bytes, .in = in, .out = outp,
+        .side = { [AB_NONCES] = { nonces, nonceLen }, [AB_AAD] = { aData, aad_bytes },
+                  [AB_LENS] = { lens, lens ? sizeof *lens : 0 }, [AB_TAGS] = { tags, tagLen }, [AB_VERDICTS] = { verdicts, decrypt } } };
     if (nonceLen < 1 || nonceLen > 15) return fail(UAES_E_ARG, "OCB nonce length %zu (1..15)", nonceLen);
     if (tagLen < 1 || tagLen > 16) return fail(UAES_E_ARG, "OCB tag length %zu (1..16)", tagLen);
     if (msg_bytes > UAES_OCB_BATCH_MAX)
         return fail(UAES_E_ARG, "an OCB batch record holds at most %zu bytes (got %zu)", (size_t)UAES_OCB_BATCH_MAX, msg_bytes);
     if (aad_bytes > UAES_OCB_BATCH_MAX)
         return fail(UAES_E_ARG, "an OCB batch record takes at most %zu bytes of AAD (got %zu)", (size_t)UAES_OCB_BATCH_MAX, aad_bytes);
-    if (nmsg > lim / (msg_bytes > 16 ? msg_bytes : 16) || (aad_bytes && nmsg > lim / aad_bytes))
-        return fail(UAES_E_ARG, "batch size overflows");
-    if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
-    if (nmsg == 0) { burn(&ks, sizeof ks); return 0; }
-    {
-        const size_t total = nmsg * msg_bytes;
-        if ((total && (!in || !outp)) || !nonces || !tags || (decrypt && !verdicts) || (aad_bytes && !aData)) {
-            burn(&ks, sizeof ks);
-            return fail(UAES_E_ARG, "NULL pointer");
-        }
-        if ((rc = enter(&c, &L)) != 0) { burn(&ks, sizeof ks); return rc; }
-        enum { NONCES, AAD, LENS, TAGS, VERDICTS, NSIDE };
-        row_array a[NSIDE] = { { nonces, nmsg * nonceLen, 0, NULL }, { aData, nmsg * aad_bytes, 0, NULL },
-                               { lens, lens ? nmsg * sizeof *lens : 0, 0, NULL }, { tags, nmsg * tagLen, !decrypt, NULL },
-                               { verdicts, decrypt ? nmsg : 0, 1, NULL } };
-        row_text t = { in, outp, total, total, lens != NULL, NULL, NULL };
-        if ((rc = row_stage(L, a, NSIDE, decrypt)) != 0) goto out;
-        if ((rc = row_texts(L, &t)) != 0) goto out;
-        ES_KCHK("ocb batch", uaesk_ocb_batch(L->stream, &c->tb, ks.nr, &ks.ek, &ks.dk, decrypt, wipe_on_auth_failure(),
-                                             a[NONCES].d, nonceLen, tagLen, a[AAD].d, aad_bytes, nmsg, msg_bytes, a[LENS].d,
-                                             t.d_in, t.d_out, a[TAGS].d, a[VERDICTS].d, L->d_status));
-        if ((rc = row_finish(L, &t, a, NSIDE, decrypt, &bad)) != 0) goto out;
-        rc = bad ? UAES_E_AUTHENTICATION : 0;
-    }
-out:
-    burn(&ks, sizeof ks);
-    DONE(L, rc);
+    return aead_rows_run(&b);
 }
 
 int uaes_ocb_encrypt_batch(int keybits, const uint8_t *key, size_t nonceLen, size_t tagLen,

@@ -177,21 +177,11 @@ __global__ __launch_bounds__(UAES_WG) void k_gcm_multikey(uaesk_tables tb, u32 t
 
 /* ---- the plan (uaes_plan.h) ---------------------------------------------------------------------------------------- */
 /* gcm.multikey: a row batch at any number of records (uaesk_row_shape) */
-static void plan_gcm_multikey(u64 nmsg, uaes_plan *p)
-{
-    const RowShape s = uaesk_row_shape(nmsg);
-    memset(p, 0, sizeof *p);
-    p->arrangement = UAES_GCM_MULTIKEY;
-    p->launches = 1;
-    p->grid = s.grid;
-    p->steps = s.wg;
-}
-
 extern "C" int uaesk_plan_gcm_multikey_batch(int dir, size_t len, size_t nmsg, uaes_plan *p)
 {
     memset(p, 0, sizeof *p);
     if ((dir != 0 && dir != 1) || len > UAES_GCM_MULTIKEY_BATCH_MAX) return (int)hipErrorInvalidValue;
-    plan_gcm_multikey(nmsg, p);
+    uaesk_row_plan(UAES_GCM_MULTIKEY, nmsg, p);
     return 0;
 }
 
@@ -207,7 +197,7 @@ static int launch_gcm_multikey(hipStream_t st, const uaesk_tables *tb, int decry
                                const void *lens, const void *in, void *out, void *tags, void *verdicts, int *bad)
 {
     uaes_plan p;
-    plan_gcm_multikey(nmsg, &p);
+    uaesk_row_plan(UAES_GCM_MULTIKEY, nmsg, &p);
     return with_bool(decrypt, [&](auto DEC) { return with_bool(uaesk_rows_a4(in, out, msg_bytes), [&](auto A4) {
         return uaesk_launch(k_gcm_multikey<NR, decltype(DEC)::value, decltype(A4)::value>, p.grid, p.steps, GMK_LDS(p.steps), st,
                             *tb, tag_len, keys, nonces, aad, aad_bytes, nmsg, msg_bytes, lens, in, out, tags, verdicts, bad); }); });

@@ -164,21 +164,11 @@ __global__ __launch_bounds__(UAES_WG) void k_gcmsiv_batch(uaesk_rk mk, uaesk_tab
 
 /* ---- the plan (uaes_plan.h) ---------------------------------------------------------------------------------------- */
 /* gcmsiv.batch: a row batch at any number of records (uaesk_row_shape) */
-static void plan_gcmsiv_batch(u64 nmsg, uaes_plan *p)
-{
-    const RowShape s = uaesk_row_shape(nmsg);
-    memset(p, 0, sizeof *p);
-    p->arrangement = UAES_GCMSIV_BATCH;
-    p->launches = 1;
-    p->grid = s.grid;
-    p->steps = s.wg;
-}
-
 extern "C" int uaesk_plan_gcmsiv_batch(int dir, size_t len, size_t nmsg, uaes_plan *p)
 {
     memset(p, 0, sizeof *p);
     if ((dir != 0 && dir != 1) || len > UAES_GCMSIV_BATCH_MAX) return (int)hipErrorInvalidValue;
-    plan_gcmsiv_batch(nmsg, p);
+    uaesk_row_plan(UAES_GCMSIV_BATCH, nmsg, p);
     return 0;
 }
 
@@ -194,7 +184,7 @@ static int launch_gcmsiv_batch(hipStream_t st, const uaesk_tables *tb, const uae
                                const void *lens, const void *in, void *out, void *tags, void *verdicts, int *bad)
 {
     uaes_plan p;
-    plan_gcmsiv_batch(nmsg, &p);
+    uaesk_row_plan(UAES_GCMSIV_BATCH, nmsg, &p);
     return with_bool(decrypt, [&](auto DEC) { return with_bool(uaesk_rows_a4(in, out, msg_bytes), [&](auto A4) {
         return uaesk_launch(k_gcmsiv_batch<NR, decltype(DEC)::value, decltype(A4)::value>, p.grid, p.steps, GSB_LDS(p.steps), st,
                             *mk, *tb, wipe, nonces, aad, aad_bytes, nmsg, msg_bytes, lens, in, out, tags, verdicts, bad); }); });

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include "uaes_device.h"
+#include "uaes_plan.h"
 
 /* ---- completion ticket riding on a kernel (uaes_device.h: uaesk_done; device side: ticket_release) ---- */
 uaesk_done uaesk_ticket_take();                     /* the calling host thread's armed ticket (cleared), uaes_kernels.hip */
@@ -53,6 +54,16 @@ static inline RowShape uaesk_row_shape(unsigned long long nrec)
     const unsigned wg = (nrec + 63) / 64 * 2 <= cus ? 256u : UAESK_ROW_WG;
     const unsigned long long want = (nrec + wg / 16 - 1) / (wg / 16);
     return RowShape{ (unsigned)(want < cus ? (want ? want : 1) : cus), wg };
+}
+
+/* the plan of a row batch that is one launch of that shape: steps = threads per workgroup */
+static inline void uaesk_row_plan(int arrangement, unsigned long long nrec, uaes_plan *p)
+{
+    const RowShape s = uaesk_row_shape(nrec);
+    p->arrangement = arrangement;
+    p->launches = 1;
+    p->grid = s.grid;
+    p->steps = s.wg;
 }
 
 /* the row kernels' A4: both texts and the record size are 4-byte aligned, so every record is */

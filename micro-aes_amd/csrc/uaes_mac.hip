@@ -414,21 +414,11 @@ extern "C" int uaesk_plan_mac(int what, int dir, size_t a, uaes_plan *p)
 }
 
 /* ccm.batch: a row batch at any number of records (uaesk_row_shape) */
-static void plan_ccm_batch(u64 nmsg, uaes_plan *p)
-{
-    const RowShape s = uaesk_row_shape(nmsg);
-    memset(p, 0, sizeof *p);
-    p->arrangement = UAES_CCM_BATCH;
-    p->launches = 1;
-    p->grid = s.grid;
-    p->steps = s.wg;
-}
-
 extern "C" int uaesk_plan_ccm_batch(int dir, size_t len, size_t nmsg, uaes_plan *p)
 {
     memset(p, 0, sizeof *p);
     if ((dir != 0 && dir != 1) || len > UAES_CCM_BATCH_MAX) return (int)hipErrorInvalidValue;
-    plan_ccm_batch(nmsg, p);
+    uaesk_row_plan(UAES_CCM_BATCH, nmsg, p);
     return 0;
 }
 
@@ -439,7 +429,7 @@ static int launch_ccm_batch(hipStream_t st, const uaesk_tables *tb, const uaesk_
                             void *verdicts, int *bad)
 {
     uaes_plan p;
-    plan_ccm_batch(nmsg, &p);
+    uaesk_row_plan(UAES_CCM_BATCH, nmsg, &p);
     return with_bool(decrypt, [&](auto DEC) { return with_bool(uaesk_rows_a4(in, out, msg_bytes), [&](auto A4) {
         return uaesk_launch(k_ccm_batch<NR, decltype(DEC)::value, decltype(A4)::value>, p.grid, p.steps, UAES_LDS_ROW4, st, *ek, *tb,
                             wipe, nonces, nonce_len, tag_len, aad, aad_bytes, nmsg, msg_bytes, lens, in, out, tags, verdicts,

@@ -881,21 +881,11 @@ __global__ __launch_bounds__(UAES_WG) void k_ocb_batch(uaesk_rk ek, uaesk_rk dk,
 }
 
 /* ocb.batch: a row batch at any number of records (uaesk_row_shape) */
-static void plan_ocb_batch(u64 nmsg, uaes_plan *p)
-{
-    const RowShape s = uaesk_row_shape(nmsg);
-    memset(p, 0, sizeof *p);
-    p->arrangement = UAES_OCB_BATCH;
-    p->launches = 1;
-    p->grid = s.grid;
-    p->steps = s.wg;
-}
-
 extern "C" int uaesk_plan_ocb_batch(int dir, size_t len, size_t nmsg, uaes_plan *p)
 {
     memset(p, 0, sizeof *p);
     if ((dir != 0 && dir != 1) || len > UAES_OCB_BATCH_MAX) return (int)hipErrorInvalidValue;
-    plan_ocb_batch(nmsg, p);
+    uaesk_row_plan(UAES_OCB_BATCH, nmsg, p);
     return 0;
 }
 
@@ -911,7 +901,7 @@ static int launch_ocb_batch(hipStream_t st, const uaesk_tables *tb, const uaesk_
                             void *tags, void *verdicts, int *bad)
 {
     uaes_plan p;
-    plan_ocb_batch(nmsg, &p);
+    uaesk_row_plan(UAES_OCB_BATCH, nmsg, &p);
     return with_bool(decrypt, [&](auto DEC) { return with_bool(uaesk_rows_a4(in, out, msg_bytes), [&](auto A4) {
         return uaesk_launch(k_ocb_batch<NR, decltype(DEC)::value, decltype(A4)::value>, p.grid, p.steps, OCBB_LDS, st, *ek,
                             decrypt ? *dk : *ek, *tb, wipe, nonces, nonce_len, tag_len, aad, aad_bytes, nmsg, msg_bytes, lens,

@@ -117,7 +117,7 @@ def main():
     emit("A CCM decryption against the EAX ENCRYPTION of the same shape (us per call more than the CCM encryption, ratio "
          "to EAX encrypt): " + ", ".join("%d B x 2^%d: +%.1f, %.2f" % e for e in extra) + ".  What the code shows as "
          "the cause where that ratio is above 1: the kernel's decrypting direction is the encrypting one plus a tag load, "
-         "a ballot and a verdict byte per record, but the host side of every decrypting batch (ccm_batch, like aead_batch, "
+         "a ballot and a verdict byte per record, but the host side of every decrypting batch (aead_rows_staged, "
          "uaes_engine_modes.c) clears the `bad` word before the launch (hipMemsetAsync) and fetches it after it "
          "(a hipMemcpyAsync to host memory in front of the stream synchronisation), which the encrypting call does "
          "not: a cost per call, not per record, that a short call cannot hide.\n")
