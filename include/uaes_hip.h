@@ -153,6 +153,12 @@ int uaes_ctr_xcrypt_iv(int keybits, const uint8_t *key, const uint8_t *iv, size_
 int uaes_ctr_xcrypt_at(int keybits, const uint8_t *key, const uint8_t ctr0[16],
                        uint64_t block_offset,
                        const void *in, size_t len, void *out);
+/* Batch: nmsg records in slots of msg_bytes, a counter block each, one launch -- a cipher batch; its conventions (lens,
+ * memory, in place, refusals) stand with uaes_cbc_decrypt_batch below.  ctrs + 16 m = record m's first counter block,
+ * as uaes_ctr_xcrypt_at(.., ctr0, 0, ..): 56-bit counter in bytes 9..15, with the reference's carry and wrap; bytes
+ * 0..8 never change.  Any record length: there is no cap on a record's blocks. */
+int uaes_ctr_xcrypt_batch(int keybits, const uint8_t *key, const uint8_t *ctrs, size_t nmsg,
+                          size_t msg_bytes, const uint32_t *lens, const void *in, void *out);
 
 /* ---- XTS: replaces AES_XTS_encrypt / AES_XTS_decrypt --------------------
  * micro_aes.h:239-249, micro_aes.c:1008-1093.  keys = key1 || key2
@@ -384,6 +390,60 @@ int uaes_cbc_encrypt_batch(int keybits, const uint8_t *key, const uint8_t *ivs, 
                            size_t msg_bytes, const void *pntxt, void *crtxt);
 int uaes_cmac_batch(int keybits, const uint8_t *key, size_t nmsg, size_t msg_bytes,
                     const void *data, uint8_t *macs);
+/* Cipher batches -- the decrypt counterpart of uaes_cbc_encrypt_batch, ordinary CBC (no swap) in both directions, and
+ * CFB and OFB over many short records with an IV each (uaes_ctr_xcrypt_batch stands with CTR above).  The conventions
+ * are those of the AEAD record batches (uaes_ccm_encrypt_batch): nmsg records in slots of msg_bytes back to back
+ * (record m at m * msg_bytes), sixteen GPU lanes per record, four records per wave, one kernel launch
+ * (csrc/uaes_cipher_batch.hip) at any number of records, always on the GPU (the host policy does not apply).  key: host
+ * memory.  ivs = nmsg * 16 bytes and the texts: host or device memory at any byte offset.  out == in works in every
+ * mode, the block-parallel decrypting ones included.  Every record is bit for bit what the one-message call of its mode
+ * gives for it, at all three key sizes:
+ *   uaes_cbc_decrypt_batch         uaes_cbc_decrypt: the inverse of uaes_cbc_encrypt_batch, CS3 swap included (the last
+ *                                  two blocks of a record of two or more arrive swapped; a one-block record has none)
+ *   uaes_cbc_encrypt_blocks_batch  uaes_cbc_encrypt_padded with padding 0: ordinary CBC, which interoperates
+ *   uaes_cbc_decrypt_blocks_batch  uaes_cbc_decrypt_blocks
+ *   uaes_cfb_encrypt_batch / uaes_cfb_decrypt_batch / uaes_ofb_xcrypt_batch
+ *                                  uaes_cfb_encrypt / uaes_cfb_decrypt / uaes_ofb_xcrypt
+ * The CBC forms take whole blocks only and have no lens: msg_bytes < 16 or msg_bytes % 16 -> UAES_E_ARG.  The others
+ * take any msg_bytes from 0 to UINT32_MAX and lens (may be NULL: every record is msg_bytes long) = nmsg 32-bit
+ * lengths with the CCM batch's meaning: record m is the first lens[m] <= msg_bytes bytes of its slot (a longer entry is
+ * taken as msg_bytes, a zero length writes nothing), the bytes of an output slot beyond lens[m] are not written, and a
+ * host-memory output is copied in first, so that this remainder stays the caller's; lens is host memory or 4-byte
+ * aligned device memory (else UAES_E_ARG).  UAES_E_ARG before the device is touched: a size product that overflows, a
+ * needed pointer that is NULL, key bits other than 128 / 192 / 256.  nmsg == 0 returns 0.  There are no verdicts and no
+ * status word.  Row steps per record: one per block in the serial directions (CBC encrypt, CFB encrypt, OFB: the pace
+ * of uaes_cbc_encrypt_batch's sixteen-lane form), one per TWO blocks where blocks do not wait for each other (CBC
+ * decrypt, CFB decrypt, CTR).
+ * Measured on an MI355X (tools/cipher_batch_rate.py -> profiles/cipher_batch_rate.md; device-resident arrays,
+ * synchronous calls, the host round trip included), AES-128 and AES-256:
+ *   2^10 records of 16 B     18.9 .. 19.2 and 19.8 .. 20.0 us per call, the two CBC decrypts 22.1 .. 22.2 and 21.1 .. 21.2
+ *                            (2^10 one-message calls of the same mode: 12.5 .. 14.7 and 12.4 .. 14.2 us EACH)
+ *   2^20 records of 16 / 64 / 1024 B, G records per second:
+ *     CBC decrypt            5.72 / 4.24 / 0.564 and 5.46 / 3.72 / 0.419      over blocks 6.15 / 4.44 / 0.584 and 5.70 / 3.80 / 0.444
+ *     CBC encrypt over blocks 6.30 / 4.10 / 0.480 and 5.84 / 3.45 / 0.362
+ *     CFB encrypt            6.09 / 4.00 / 0.476 and 5.58 / 3.37 / 0.360      decrypt 5.98 / 4.37 / 0.577 and 5.62 / 3.81 / 0.441
+ *     OFB                    6.04 / 4.01 / 0.484 and 5.60 / 3.37 / 0.366
+ *     CTR                    5.87 / 4.11 / 0.503 and 5.52 / 3.59 / 0.390
+ * The CTR batch takes 0.51 .. 0.58x the time of uaes_ccm_encrypt_batch at these 2^20-record shapes, 0.58 .. 0.69x at 2^16
+ * records and 0.86x at 2^10 (two CCM runs of one shape differ by at most 0.8 us up to 2^16 records and by at most 0.4 %
+ * at 2^20).  uaes_cbc_encrypt_blocks_batch is NOT within that spread of uaes_cbc_encrypt_batch: where both run sixteen
+ * lanes per record (2^10 and 2^16 records) it takes 2.1 .. 5.6 us per call more whatever the work (16 .. 191 us per call:
+ * the same chain at the same pace, and a host side that ends in a stream synchronise where uaes_cbc_encrypt_batch spins
+ * on a ticket and waits once less for the caller's stream; not timed apart), and at 2^20 records uaes_cbc_encrypt_batch
+ * is its one-lane-per-record arrangement, which these batches do not have, and is 2.5 .. 5.8x faster.  For 2^17 records
+ * and more that want CS3, or can swap the last two blocks themselves, it remains the faster call. */
+int uaes_cbc_decrypt_batch(int keybits, const uint8_t *key, const uint8_t *ivs, size_t nmsg,
+                           size_t msg_bytes, const void *crtxt, void *pntxt);
+int uaes_cbc_encrypt_blocks_batch(int keybits, const uint8_t *key, const uint8_t *ivs, size_t nmsg,
+                                  size_t msg_bytes, const void *pntxt, void *crtxt);
+int uaes_cbc_decrypt_blocks_batch(int keybits, const uint8_t *key, const uint8_t *ivs, size_t nmsg,
+                                  size_t msg_bytes, const void *crtxt, void *pntxt);
+int uaes_cfb_encrypt_batch(int keybits, const uint8_t *key, const uint8_t *ivs, size_t nmsg,
+                           size_t msg_bytes, const uint32_t *lens, const void *pntxt, void *crtxt);
+int uaes_cfb_decrypt_batch(int keybits, const uint8_t *key, const uint8_t *ivs, size_t nmsg,
+                           size_t msg_bytes, const uint32_t *lens, const void *crtxt, void *pntxt);
+int uaes_ofb_xcrypt_batch(int keybits, const uint8_t *key, const uint8_t *ivs, size_t nmsg,
+                          size_t msg_bytes, const uint32_t *lens, const void *in, void *out);
 
 /* ---- KW: replaces AES_KEY_wrap / AES_KEY_unwrap (RFC 3394, SP 800-38F KW) ------
  * micro_aes.c:1829-1894.  kek = the key-encryption key (host memory).  wrap writes secretLen + 8 bytes: A || R_1..R_n
@@ -894,6 +954,13 @@ const char *uaes_debug_plan_ocb(int dir, size_t len, size_t aad_len, int aad_ali
  * arrangement: sixteen lanes per record, the same grid and threads as "ccm.batch" for the same number of records), or
  * NULL for a dir other than 0 / 1 or a length above UAES_OCB_BATCH_MAX.  Works without a device (a 256-CU MI355X). */
 const char *uaes_debug_plan_ocb_batch(int dir, size_t len, size_t nmsg, int out[3]);
+/* The planner of the cipher batches (csrc/uaes_plan.h): mode 0 uaes_cbc_decrypt_batch, 1 uaes_cbc_decrypt_blocks_batch,
+ * 2 uaes_cbc_encrypt_blocks_batch, 3 uaes_cfb_encrypt_batch, 4 uaes_cfb_decrypt_batch, 5 uaes_ofb_xcrypt_batch,
+ * 6 uaes_ctr_xcrypt_batch; len = bytes per record, nmsg = records; out (may be NULL) receives { launches, workgroups,
+ * threads per workgroup }.  Returns "cipher.batch" (the one arrangement: sixteen lanes per record, the same grid and
+ * threads as "ccm.batch" for the same number of records), or NULL for another mode, a CBC record that is not a whole
+ * number of blocks or a record of the other modes above UINT32_MAX bytes.  Works without a device (a 256-CU MI355X). */
+const char *uaes_debug_plan_cipher_batch(int mode, size_t len, size_t nmsg, int out[3]);
 
 /* Test hooks of the one-launch GCM / GCM-SIV / streamed-piece arrangements (chunk workgroups + one preparing workgroup
  * in ONE launch; whoever of them arrives last on a counter word folds the chunk hashes and makes the tag -- nobody

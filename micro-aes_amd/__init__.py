@@ -65,6 +65,8 @@ EXPORTS = [
     "uaes_gcm_key_encrypt_records_v_dev", "uaes_gcm_key_decrypt_records_v_dev",
     "uaes_gcm_stream_begin", "uaes_gcm_stream_update", "uaes_gcm_stream_finish", "uaes_gcm_stream_abort",
     "uaes_cbc_encrypt_batch", "uaes_cmac_batch", "uaes_cbc_encrypt", "uaes_cbc_decrypt", "uaes_cbc_encrypt_padded", "uaes_cbc_decrypt_blocks", "uaes_cfb_encrypt", "uaes_cfb_decrypt", "uaes_ofb_xcrypt",
+    "uaes_cbc_decrypt_batch", "uaes_cbc_encrypt_blocks_batch", "uaes_cbc_decrypt_blocks_batch", "uaes_cfb_encrypt_batch",
+    "uaes_cfb_decrypt_batch", "uaes_ofb_xcrypt_batch", "uaes_ctr_xcrypt_batch", "uaes_debug_plan_cipher_batch",
     "uaes_ecb_dev", "uaes_ctr_xcrypt_at_dev", "uaes_xts_sectors_dev",
     "uaes_gcm_encrypt_dev", "uaes_gcm_decrypt_dev", "uaes_gcm_partial_dev", "uaes_gcm_shard_dev",
 ]
@@ -132,6 +134,12 @@ def engine():
     L.uaes_clock_probe_dev.argtypes = [vp, C.c_uint, vp]
     L.uaes_cbc_encrypt_batch.argtypes = [i, vp, vp, sz, sz, vp, vp]
     L.uaes_cmac_batch.argtypes = [i, vp, sz, sz, vp, vp]
+    for n in ("uaes_cbc_decrypt_batch", "uaes_cbc_encrypt_blocks_batch", "uaes_cbc_decrypt_blocks_batch"):
+        getattr(L, n).argtypes = [i, vp, vp, sz, sz, vp, vp]
+    for n in ("uaes_cfb_encrypt_batch", "uaes_cfb_decrypt_batch", "uaes_ofb_xcrypt_batch", "uaes_ctr_xcrypt_batch"):
+        getattr(L, n).argtypes = [i, vp, vp, sz, sz, vp, vp, vp]
+    L.uaes_debug_plan_cipher_batch.argtypes = [i, sz, sz, C.POINTER(C.c_int)]
+    L.uaes_debug_plan_cipher_batch.restype = C.c_char_p
     L.uaes_ecb_encrypt_padded.argtypes = [i, vp, i, vp, sz, vp]
     L.uaes_ctr_xcrypt.argtypes = [i, vp, vp, vp, sz, vp]
     L.uaes_ctr_xcrypt_at.argtypes = [i, vp, vp, u64, vp, sz, vp]
@@ -271,7 +279,7 @@ def engine():
                      "uaes_debug_arrangement_name", "uaes_debug_plan_disable", "uaes_debug_plan_poly1305",
                      "uaes_debug_plan_eax_siv", "uaes_debug_plan_chain", "uaes_debug_plan_kw", "uaes_debug_plan_ff1",
                      "uaes_debug_plan_ff3", "uaes_ff3_maxlen", "uaes_debug_plan_gcmsiv_batch", "uaes_debug_plan_ocb",
-                     "uaes_debug_plan_ocb_batch", "uaes_debug_plan_gcm_multikey_batch"):
+                     "uaes_debug_plan_ocb_batch", "uaes_debug_plan_gcm_multikey_batch", "uaes_debug_plan_cipher_batch"):
             getattr(L, n).restype = i
     _lib = L
     return L
@@ -465,6 +473,67 @@ def cbc_encrypt_batch(key, ivs, messages):
                                            _in(b"".join(messages)), o), "uaes_cbc_encrypt_batch")
     raw = bytes(o)
     return _split(raw, size, n)
+
+
+CIPHER_BATCH_MODES = ("cbc_decrypt", "cbc_decrypt_blocks", "cbc_encrypt_blocks", "cfb_encrypt", "cfb_decrypt", "ofb", "ctr")
+
+
+def _cipher_batch(name, key, ivs, records, ragged):
+    """What the cipher batches share (uaes_cbc_*_batch, uaes_cfb_*_batch, uaes_ofb_xcrypt_batch, uaes_ctr_xcrypt_batch):
+    one 16-byte IV (CTR: first counter block) per record, the records packed into slots of the longest one, the call and
+    the split.  ragged: the call takes `lens`, and records of different lengths become it; else they must be equal."""
+    n = len(records)
+    if len(ivs) != n or any(len(v) != 16 for v in ivs):
+        raise ValueError("one 16-byte IV per record")
+    if n == 0:
+        return []
+    sizes = [len(r) for r in records]
+    size = max(sizes)
+    if not ragged and min(sizes) != size:
+        raise ValueError("equal-sized messages")
+    lens = (C.c_uint32 * n)(*sizes) if min(sizes) != size else None
+    packed = b"".join(bytes(r) + bytes(size - len(r)) for r in records)
+    o = _out(n * size)
+    args = (_bits(key), _in(key), _in(b"".join(bytes(v) for v in ivs)), n, size) + ((lens,) if ragged else ()) + (_in(packed), o)
+    _check(getattr(engine(), name)(*args), name)
+    raw = bytes(o)
+    return [raw[m * size: m * size + sizes[m]] for m in range(n)]
+
+
+def cbc_decrypt_batch(key, ivs, messages):
+    """The inverse of cbc_encrypt_batch, CS3 swap included: == [AES_CBC_decrypt(key, iv, m)[1] for iv, m in ...]."""
+    return _cipher_batch("uaes_cbc_decrypt_batch", key, ivs, messages, False)
+
+
+def cbc_blocks_batch(key, ivs, messages, decrypt=False):
+    """Ordinary CBC over whole blocks, no swap: == [AES_CBC_encrypt(key, iv, m, cts=False)[1] ...], or with decrypt
+    [AES_CBC_decrypt(key, iv, m, cts=False)[1] ...]."""
+    return _cipher_batch("uaes_cbc_decrypt_blocks_batch" if decrypt else "uaes_cbc_encrypt_blocks_batch", key, ivs, messages, False)
+
+
+def cfb_batch(key, ivs, messages, decrypt=False):
+    """CFB of many records, an IV each: == [AES_CFB_encrypt(key, iv, m) ...] (decrypt: AES_CFB_decrypt).  The records
+    may differ in length: they travel in slots of the longest one, with their lengths as the call's `lens`."""
+    return _cipher_batch("uaes_cfb_decrypt_batch" if decrypt else "uaes_cfb_encrypt_batch", key, ivs, messages, True)
+
+
+def ofb_batch(key, ivs, messages):
+    """OFB of many records, an IV each: == [AES_OFB_encrypt(key, iv, m) ...]; lengths as in cfb_batch."""
+    return _cipher_batch("uaes_ofb_xcrypt_batch", key, ivs, messages, True)
+
+
+def ctr_batch(key, ctrs, messages):
+    """CTR of many records, a 16-byte first counter block each: == [ctr_xcrypt_at(key, ctr0, 0, m) ...]; lengths as in
+    cfb_batch."""
+    return _cipher_batch("uaes_ctr_xcrypt_batch", key, ctrs, messages, True)
+
+
+def cipher_batch_plan(nmsg, mode="ctr", length=16):
+    """What a cipher batch of nmsg records of `length` bytes would run (uaes_debug_plan_cipher_batch): (arrangement,
+    launches, workgroups, threads per workgroup), or None for arguments that make no sense.  mode: a name from
+    CIPHER_BATCH_MODES or its number."""
+    return _batch_plan("uaes_debug_plan_cipher_batch", CIPHER_BATCH_MODES.index(mode) if isinstance(mode, str) else int(mode),
+                       length, nmsg)
 
 
 def cmac_batch(key, messages):

@@ -220,6 +220,15 @@ int uaesk_feedback(void *stream, const uaesk_tables *tb, int nr,
 int uaesk_chain_batch(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, int mac,
                       const void *ivs, size_t nmsg, size_t msg_bytes, const void *in, void *out);
 
+/* Batches of the plain cipher modes, sixteen lanes per record (k_cipher_batch, uaes_cipher_batch.hip); all device
+ * pointers at any byte offset (lens: 4-byte aligned).  mode = enum uaes_cipher_batch_mode (uaes_plan.h).  Record m: text
+ * at in / out + m msg_bytes, its first lens[m] bytes (lens NULL: msg_bytes; the three CBC modes ignore lens and want
+ * msg_bytes a multiple of 16, >= 16), IV -- CTR: first counter block -- at ivs + 16 m.  ek / dk: encryption /
+ * equivalent-inverse keys (the two decrypting CBC modes read dk, the others ek).  in == out is fine in every mode.
+ * The plan (uaesk_plan_cipher_batch, uaes_plan.h) is one row, cipher.batch. */
+int uaesk_cipher_batch(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, const uaesk_rk *dk, int mode,
+                       const void *ivs, size_t nmsg, size_t msg_bytes, const void *lens, const void *in, void *out);
+
 /* OCB (AES_OCB_encrypt/decrypt, micro_aes.c:1693-1811): nonce (host) of nonce_len = 1..15 bytes, tag_len
  * (1..16) bytes of tag at out+len (encrypt) / read at in+len (decrypt, *status = 0 / 0x1A; the text
  * is written either way, as in the reference).  dk = equivalent-inverse keys.  ONE launch; done_word = a device

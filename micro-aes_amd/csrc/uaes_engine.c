@@ -1341,7 +1341,8 @@ int stage_text(lane *L, int k, const void *user, size_t n, int prefill, void **d
 }
 
 /* ---- a row batch's arrays (uaes_engine_modes.c: aead_rows_staged for every AEAD record batch -- EAX, SIV, CCM,
- * GCM-SIV, multi-key GCM and OCB -- and the key-wrap, FF1 and FF3-1 batches) ----
+ * GCM-SIV, multi-key GCM and OCB -- cipher_rows for the batches of the plain cipher modes, and the key-wrap, FF1 and
+ * FF3-1 batches) ----
  * The caller lists its side arrays (row_array, uaes_engine.h) and its two texts (row_text) and calls row_stage,
  * row_texts, its launcher and row_finish, in this order.  A device array goes to the kernel as it is; host arrays
  * share the lane's scratch, SIDE(bytes) each.  The offsets and the size asked of lane_scratch come from the one list,
@@ -1497,6 +1498,10 @@ const char *uaes_debug_plan_gcm_multikey_batch(int dir, size_t len, size_t nmsg,
 const char *uaes_debug_plan_ocb_batch(int dir, size_t len, size_t nmsg, int out[3])
 {
     return debug_plan_rows(uaesk_plan_ocb_batch, uaesk_ocb_batch_arrangement_name, dir, len, nmsg, out);
+}
+const char *uaes_debug_plan_cipher_batch(int mode, size_t len, size_t nmsg, int out[3])
+{
+    return debug_plan_rows(uaesk_plan_cipher_batch, uaesk_cipher_batch_arrangement_name, mode, len, nmsg, out);
 }
 const char *uaes_debug_plan_ocb(int dir, size_t len, size_t aad_len, int aad_aligned, int out[5])
 {

@@ -1113,6 +1113,95 @@ int uaes_cmac_batch(int keybits, const uint8_t *key, size_t nmsg, size_t msg_byt
 }
 
 /* ------------------------------------------------------------------------ */
+/* batches of the plain cipher modes (sixteen GPU lanes per record)             */
+/* ------------------------------------------------------------------------ */
+/* CBC decrypt (with the CS3 swap and without), CBC encrypt without it, CFB, OFB and CTR over nmsg records in slots of
+ * msg_bytes, one launch of k_cipher_batch (uaes_cipher_batch.hip), always on the GPU.  mode = enum
+ * uaes_cipher_batch_mode; ivs = 16 bytes per record (CTR: its first counter block).  The conventions are the AEAD record
+ * batches': every array host or device memory at any byte offset, host arrays through the lane's scratch and staging
+ * buffers (row_stage / row_texts / row_finish), `lens` as in the CCM batch -- with it a host-memory output starts as a
+ * copy of the caller's buffer, so that what the kernel leaves unwritten stays the caller's.  No verdicts, no status
+ * word.  The order is the AEAD batches' too: the sizes, the key, nothing more for no records, the pointers, and only
+ * then the device. */
+static int cipher_rows(int mode, int keybits, const uint8_t *key, const uint8_t *ivs, size_t nmsg, size_t msg_bytes,
+                       const uint32_t *lens, const void *in, void *outp)
+{
+    const int cbc = mode == UAES_CB_CBC_DEC || mode == UAES_CB_CBC_DEC_BLOCKS || mode == UAES_CB_CBC_ENC_BLOCKS;
+    const size_t total = nmsg * msg_bytes;
+    context *c;
+    lane *L;
+    keysched ks;
+    int rc, bad;
+    if (cbc && (msg_bytes < 16 || msg_bytes % 16))
+        return fail(UAES_E_ARG, "batched CBC: every message must be a whole number of blocks (got %zu bytes)", msg_bytes);
+    if (!cbc && msg_bytes > UINT32_MAX)
+        return fail(UAES_E_ARG, "a batch record holds at most %u bytes (got %zu)", UINT32_MAX, msg_bytes);
+    if (nmsg > (size_t)-1 / 2 / (msg_bytes > 16 ? msg_bytes : 16))     /* / 2: the IVs, the lengths and their padding */
+        return fail(UAES_E_ARG, "batch size overflows");
+    if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
+    if (total == 0) { burn(&ks, sizeof ks); return 0; }                /* no records, or records of no bytes */
+    if (!ivs || !in || !outp) { burn(&ks, sizeof ks); return fail(UAES_E_ARG, "NULL pointer"); }
+    if (cbc) lens = NULL;
+    if ((rc = enter(&c, &L)) != 0) { burn(&ks, sizeof ks); return rc; }
+    row_array a[2] = { { ivs, nmsg * 16, 0, NULL }, { lens, lens ? nmsg * sizeof *lens : 0, 0, NULL } };
+    row_text t = { in, outp, total, total, lens != NULL, NULL, NULL };
+    if (lens && is_device_ptr(lens) && ((uintptr_t)lens & 3u)) {
+        rc = fail(UAES_E_ARG, "a device array of lengths must be 4-byte aligned");
+        goto out;
+    }
+    if ((rc = row_stage(L, a, 2, 0)) != 0) goto out;
+    if ((rc = row_texts(L, &t)) != 0) goto out;
+    ES_KCHK("cipher batch", uaesk_cipher_batch(L->stream, &c->tb, ks.nr, &ks.ek, &ks.dk, mode, a[0].d, nmsg, msg_bytes, a[1].d,
+                                               t.d_in, t.d_out));
+    rc = row_finish(L, &t, a, 2, 0, &bad);
+out:
+    burn(&ks, sizeof ks);
+    DONE(L, rc);
+}
+
+int uaes_cbc_decrypt_batch(int keybits, const uint8_t *key, const uint8_t *ivs, size_t nmsg,
+                           size_t msg_bytes, const void *crtxt, void *pntxt)
+{
+    return cipher_rows(UAES_CB_CBC_DEC, keybits, key, ivs, nmsg, msg_bytes, NULL, crtxt, pntxt);
+}
+
+int uaes_cbc_encrypt_blocks_batch(int keybits, const uint8_t *key, const uint8_t *ivs, size_t nmsg,
+                                  size_t msg_bytes, const void *pntxt, void *crtxt)
+{
+    return cipher_rows(UAES_CB_CBC_ENC_BLOCKS, keybits, key, ivs, nmsg, msg_bytes, NULL, pntxt, crtxt);
+}
+
+int uaes_cbc_decrypt_blocks_batch(int keybits, const uint8_t *key, const uint8_t *ivs, size_t nmsg,
+                                  size_t msg_bytes, const void *crtxt, void *pntxt)
+{
+    return cipher_rows(UAES_CB_CBC_DEC_BLOCKS, keybits, key, ivs, nmsg, msg_bytes, NULL, crtxt, pntxt);
+}
+
+int uaes_cfb_encrypt_batch(int keybits, const uint8_t *key, const uint8_t *ivs, size_t nmsg,
+                           size_t msg_bytes, const uint32_t *lens, const void *pntxt, void *crtxt)
+{
+    return cipher_rows(UAES_CB_CFB_ENC, keybits, key, ivs, nmsg, msg_bytes, lens, pntxt, crtxt);
+}
+
+int uaes_cfb_decrypt_batch(int keybits, const uint8_t *key, const uint8_t *ivs, size_t nmsg,
+                           size_t msg_bytes, const uint32_t *lens, const void *crtxt, void *pntxt)
+{
+    return cipher_rows(UAES_CB_CFB_DEC, keybits, key, ivs, nmsg, msg_bytes, lens, crtxt, pntxt);
+}
+
+int uaes_ofb_xcrypt_batch(int keybits, const uint8_t *key, const uint8_t *ivs, size_t nmsg,
+                          size_t msg_bytes, const uint32_t *lens, const void *in, void *out)
+{
+    return cipher_rows(UAES_CB_OFB, keybits, key, ivs, nmsg, msg_bytes, lens, in, out);
+}
+
+int uaes_ctr_xcrypt_batch(int keybits, const uint8_t *key, const uint8_t *ctrs, size_t nmsg,
+                          size_t msg_bytes, const uint32_t *lens, const void *in, void *out)
+{
+    return cipher_rows(UAES_CB_CTR, keybits, key, ctrs, nmsg, msg_bytes, lens, in, out);
+}
+
+/* ------------------------------------------------------------------------ */
 /* key wrap, RFC 3394 (AES_KEY_wrap / AES_KEY_unwrap, micro_aes.c:1829-1894)    */
 /* ------------------------------------------------------------------------ */
 /* One serial chain of 6 n block operations, one wave (uaes_kw.hip).  A secret of at most UAES_KW_LDS_MAX bytes in host

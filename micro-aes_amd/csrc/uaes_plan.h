@@ -55,6 +55,9 @@
  *   batch batch.row             k_chain_batch_row (sixteen lanes per message)       (1)    uaes_cbc_encrypt_batch / uaes_cmac_batch,
  *                                                                                          <= UAES_BATCH_ROW_MAX messages (81 919)
  *         batch.lane            k_chain_batch (one lane per message)                (1)    more messages
+ *         cipher.batch          k_cipher_batch (sixteen lanes per record, four per wave) (1)  uaes_cbc_decrypt_batch, uaes_cbc_*_blocks_batch,
+ *                                                                                          uaes_cfb_*_batch, uaes_ofb_xcrypt_batch,
+ *                                                                                          uaes_ctr_xcrypt_batch: any number of records
  *   KW    kw.lds                k_kw<LDS> (one wave; the semiblocks in LDS)         (1)    secret <= UAES_KW_LDS_MAX (4 KiB)
  *         kw.global             k_kw<in place> (one wave; loads a chunk ahead)      (1)    beyond
  *         kw.batch              k_kw_batch (sixteen lanes per record)               (1)    uaes_kw_*_batch, <= UAES_KW_BATCH_MAX (256 B)
@@ -73,9 +76,10 @@
  * OCB_RUNS is one row whose launch shape moves with the size: uaesk_plan_ocb_shape (uaes_ocb.hip; uaes_debug_plan_ocb),
  * and tests/test_gpu_ocb.py takes its sizes from walking it.  The OCB batches have uaesk_plan_ocb_batch (uaes_ocb.hip;
  * uaes_debug_plan_ocb_batch): one row, with an id outside enum uaes_arrangement.  So do the multi-key GCM batches:
- * uaesk_plan_gcm_multikey_batch (uaes_gcm_multikey.hip; uaes_debug_plan_gcm_multikey_batch).
+ * uaesk_plan_gcm_multikey_batch (uaes_gcm_multikey.hip; uaes_debug_plan_gcm_multikey_batch), and the batches of the plain
+ * cipher modes: uaesk_plan_cipher_batch (uaes_cipher_batch.hip; uaes_debug_plan_cipher_batch).
  * The rows that say "sixteen lanes per record / message" -- eax.batch, s2v.batch, ccm.batch, gcmsiv.batch, gcm.multikey, ocb.batch, batch.row,
- * kw.batch, ff1.batch, ff3.batch -- are the row batches: grid and threads per workgroup are uaesk_row_shape's (uaes_launch.hip.h), the same
+ * cipher.batch, kw.batch, ff1.batch, ff3.batch -- are the row batches: grid and threads per workgroup are uaesk_row_shape's (uaes_launch.hip.h), the same
  * for the same number of records in every one of them.
  */
 #ifndef UAES_PLAN_H
@@ -269,6 +273,18 @@ typedef char uaes_gcm_multikey_counter_stays_in_bytes_14_15[(UAES_GCM_MULTIKEY_B
 enum uaes_gcm_multikey_arrangement { UAES_GCM_MULTIKEY = 0 };
 int uaesk_plan_gcm_multikey_batch(int dir, size_t len, size_t nmsg, uaes_plan *p);
 const char *uaesk_gcm_multikey_arrangement_name(int id);
+
+/* The batches of the plain cipher modes (k_cipher_batch, uaes_cipher_batch.hip).  mode = enum uaes_cipher_batch_mode;
+ * len = bytes per record, nmsg = records; one arrangement, a row batch at any number of records and any record length
+ * (the walk over a record counts its blocks in 64 bits, and CTR's counter is the 56-bit one of the one-message call).
+ * grid = workgroups, steps = threads per workgroup.  Returns a HIP error code for a mode outside the enum, a CBC record
+ * that is not a whole number of blocks (at least one), or a record of the other modes above UINT32_MAX bytes (what a
+ * 32-bit length can say). */
+enum uaes_cipher_batch_mode { UAES_CB_CBC_DEC = 0, UAES_CB_CBC_DEC_BLOCKS, UAES_CB_CBC_ENC_BLOCKS, UAES_CB_CFB_ENC,
+                              UAES_CB_CFB_DEC, UAES_CB_OFB, UAES_CB_CTR, UAES_CB_MODES };
+enum uaes_cipher_batch_arrangement { UAES_CIPHER_BATCH = 0 };
+int uaesk_plan_cipher_batch(int mode, size_t len, size_t nmsg, uaes_plan *p);
+const char *uaesk_cipher_batch_arrangement_name(int id);
 
 #ifdef __cplusplus
 }
