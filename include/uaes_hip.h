@@ -754,7 +754,9 @@ int  uaes_gcm_key_decrypt_dev(uaes_gcm_key *k, const uint8_t *nonce, const void 
  * Byte for byte what uaes_gcm_key_encrypt / _decrypt give record by record.  Strides are multiples of 16,
  * in / out 16-byte aligned (device flavour), rec_len <= uaes_gcm_record_max(aad_len) (32 KiB - 48 without AAD).
  * The *_dev flavour takes device pointers for everything, enqueues on `stream`, and reports through
- * d_verdicts / *d_status (zeroed by the call, 0x1A ORed in); any number of record calls may share one context. */
+ * d_verdicts / *d_status (zeroed by the call, 0x1A ORed in); any number of record calls may share one context.
+ * Empty records (rec_len 0: a batch of GMACs) take up to 16 * 2045 bytes of AAD; uaes_gcm_record_max is 0 from there
+ * on, and more AAD is UAES_E_ARG like a record that is too long.  nrec == 0 returns 0 and looks at no pointer.      */
 size_t uaes_gcm_record_max(size_t aad_len);
 int  uaes_gcm_key_encrypt_records(uaes_gcm_key *k, size_t nrec, const uint8_t *nonces,
                                   const void *aad, size_t aad_len, size_t aad_stride,

@@ -521,7 +521,9 @@ static int records_args_ok(size_t nrec, const void *nonces, const void *aad, siz
 {
     if (!nrec) return 0;
     if (!nonces || !in || !out || (aad_len && !aad)) return fail(UAES_E_ARG, "NULL pointer");
-    if (rec_len > uaesk_gcm_record_max(aad_len))
+    /* uaesk_gcm_record_max(aad_len) is 0 both when only empty records fit and when the AAD alone is too long, so count
+     * the GHASH positions -- AAD blocks, text blocks, the length block -- against those of the longest record there is */
+    if ((aad_len + 15) / 16 + (rec_len + 15) / 16 + 1 > uaesk_gcm_record_max(0) / 16 + 1)
         return fail(UAES_E_ARG, "a record of %zu bytes with %zu bytes of AAD is too long for the record call (%zu)",
                     rec_len, aad_len, uaesk_gcm_record_max(aad_len));
     if ((in_stride | out_stride) & 15u) return fail(UAES_E_ARG, "record strides must be multiples of 16");
@@ -541,6 +543,7 @@ static int records_enc_dev(uaes_gcm_key *k, size_t nrec, const uint8_t *d_nonces
     if ((rc = key_device_ok(k)) != 0) return rc;
     if ((rc = records_args_ok(nrec, d_nonces, d_aad, aad_len, d_in, rec_len, in_stride, rec_len,
                               d_out, out_stride, rec_len + 16)) != 0) return rc;
+    if (!nrec) return 0;                                      /* no records: no pointer is looked at */
     if ((rc = dev_ptrs_ok(d_in, d_out, 1)) != 0) return rc;
     if ((rc = get_context(&c)) != 0) return rc;
     KCHK(uaesk_gcm_records(stream, &c->tb, k->ks.nr, &k->ks.ek, 0, d_nonces, d_aad, aad_len, aad_stride,
@@ -573,9 +576,13 @@ static int records_dec_dev(uaes_gcm_key *k, size_t nrec, const uint8_t *d_nonces
     context *c;
     int rc;
     if ((rc = key_device_ok(k)) != 0) return rc;
-    if (!d_status) return fail(UAES_E_ARG, "NULL d_status");
+    if (nrec && !d_status) return fail(UAES_E_ARG, "NULL d_status");
     if ((rc = records_args_ok(nrec, d_nonces, d_aad, aad_len, d_in, rec_len, in_stride, rec_len + 16,
                               d_out, out_stride, rec_len)) != 0) return rc;
+    if (!nrec) {                                              /* no records: nothing failed, no other pointer is looked at */
+        if (d_status) HIPCHK(hipMemsetAsync(d_status, 0, sizeof(int), (hipStream_t)stream));
+        return 0;
+    }
     if ((rc = dev_ptrs_ok(d_in, d_out, 1)) != 0) return rc;
     if ((rc = get_context(&c)) != 0) return rc;
     HIPCHK(hipMemsetAsync(d_status, 0, sizeof(int), (hipStream_t)stream));
@@ -657,6 +664,9 @@ static int records_sync(uaes_gcm_key *k, int decrypt, size_t nrec, const uint8_t
         if (in_place && !decrypt) {
             d_out = (unsigned char *)L->stage[0];             /* sized in_span + 64: the last tag fits */
             d_ver = NULL;
+            /* variable-length records: whole slots are copied back (below), and the last slot's sixteen bytes behind
+             * max_len were not staged -- a last record shorter than max_len leaves them as an earlier call left them */
+            if (lens && hipMemsetAsync(d_out + in_span, 0, out_span - in_span, st) != hipSuccess) { rc = fail(UAES_E_HIP, "memset failed"); break; }
         } else {
             if (grow_on(st, &L->stage[1], &L->stage_cap[1], ver_off + nrec + 64)) { rc = UAES_E_HIP; break; }
             d_out = (unsigned char *)L->stage[1];
@@ -739,7 +749,8 @@ int uaes_gcm_key_decrypt_records(uaes_gcm_key *k, size_t nrec, const uint8_t *no
 /* records of DIFFERENT lengths in slots of one size (packet buffers): record r is lens[r] <= max_len bytes at the start of
  * its slot, its tag follows its own text.  What else of a slot's first max_len + 16 output bytes holds afterwards is
  * unspecified, but never another call's data: the synchronous flavour copies whole slots back from a staging buffer
- * whose slots were zeroed before the launch, so the tail of a slot reads as zeros. */
+ * whose slots were zeroed before the launch, so the tail of a slot reads as zeros (in place: as the caller's own
+ * bytes, and zeros where the last slot was not staged). */
 int uaes_gcm_key_encrypt_records_v(uaes_gcm_key *k, size_t nrec, const uint8_t *nonces,
                                    const void *aad, size_t aad_len, size_t aad_stride,
                                    const void *in, const uint32_t *lens, size_t max_len, size_t in_stride,
