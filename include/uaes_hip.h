@@ -974,6 +974,11 @@ const char *uaes_debug_plan_cipher_batch(int mode, size_t len, size_t nmsg, int 
 void uaes_debug_gcm_look(unsigned long long ticks_100mhz);
 int uaes_debug_gcm_chunk_folds(unsigned *out);
 
+/* Test hook of the key wipe: how many expanded key schedules the process holds at this moment.  Every call expands
+ * its key into a schedule on its own stack and wipes it on every way out, so between calls the count is the number
+ * of open key contexts (uaes_gcm_key) and streams (uaes_gcm_stream).  Works without a device. */
+int uaes_debug_live_key_schedules(void);
+
 /* ---- sharded GCM (multi-GPU) ------------------------------------------------
  * One message, cut into 16-byte aligned ciphertext shards, one per GPU.  Each
  * rank encrypts its shard with uaes_ctr_xcrypt_at_dev(ctr0 = nonce || 00000001,

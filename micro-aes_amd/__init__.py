@@ -54,7 +54,7 @@ EXPORTS = [
     "uaes_ff1_encrypt", "uaes_ff1_decrypt", "uaes_ff1_encrypt_batch", "uaes_ff1_decrypt_batch", "uaes_debug_plan_ff1",
     "uaes_ff3_maxlen", "uaes_ff3_encrypt", "uaes_ff3_decrypt", "uaes_ff3_encrypt_batch", "uaes_ff3_decrypt_batch", "uaes_debug_plan_ff3",
     "uaes_mgpu_ctr_xcrypt_at", "uaes_mgpu_xts_sectors", "uaes_mgpu_ctr_encrypt_gather", "uaes_debug_gather_stats", "uaes_debug_gcm_look", "uaes_debug_gcm_chunk_folds",
-    "uaes_debug_plan", "uaes_debug_plan_at", "uaes_debug_arrangement_name", "uaes_debug_plan_disable",
+    "uaes_debug_live_key_schedules", "uaes_debug_plan", "uaes_debug_plan_at", "uaes_debug_arrangement_name", "uaes_debug_plan_disable",
     "uaes_mgpu_ecb_encrypt", "uaes_mgpu_ecb_decrypt", "uaes_mgpu_gcm_encrypt", "uaes_mgpu_gcm_decrypt",
     "uaes_set_devices", "uaes_set_producer_stream", "uaes_set_host_policy", "uaes_get_host_policy",
     "uaes_gcm_key_new", "uaes_gcm_key_free", "uaes_gcm_key_encrypt", "uaes_gcm_key_decrypt",
@@ -231,6 +231,8 @@ def engine():
         L.uaes_debug_arrangement_name.restype = C.c_char_p
         L.uaes_debug_plan_disable.argtypes = [C.c_uint]
         L.uaes_debug_plan_disable.restype = None
+    if hasattr(L, "uaes_debug_live_key_schedules"):
+        L.uaes_debug_live_key_schedules.argtypes = []
     if hasattr(L, "uaes_debug_plan_at"):
         L.uaes_debug_plan_at.argtypes = [i, i, sz, sz, C.c_uint, vp, C.POINTER(C.c_int)]
     L.uaes_mgpu_ecb_encrypt.argtypes = [i, C.POINTER(C.c_int), i, vp, i, vp, sz, vp]

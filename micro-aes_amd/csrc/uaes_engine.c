@@ -32,6 +32,12 @@ int fail(int code, const char *fmt, ...)
     return code;
 }
 
+/* what a kernel launcher (uaes_device.h) answered: 0, or the runtime's error under the name of what was launched */
+int launched(const char *what, int k)
+{
+    return k ? fail(UAES_E_HIP, "%s launch: %s", what, hipGetErrorString((hipError_t)k)) : 0;
+}
+
 const char *uaes_last_error(void) { return tls_err; }
 const char *uaes_version(void) { return UAES_VERSION; }
 
@@ -186,10 +192,29 @@ static uint32_t inv_mix_word(uint32_t w)
     return r;
 }
 
+/* schedules expanded and not yet wiped, process-wide (uaes_debug_live_key_schedules) */
+static int g_live_schedules;
+
+void burn(void *p, size_t n)
+{
+    volatile unsigned char *v = (volatile unsigned char *)p;
+    while (n--) *v++ = 0;
+}
+
+/* burn()'s effect at memset's speed (the byte-wise volatile loop was 0.1 us of every call, profiles/key_wipe_latency.md):
+ * the empty asm may read the memory for all the compiler knows, so the stores stay */
+void keysched_wipe(keysched *sched)
+{
+    if (sched->nr) __atomic_fetch_sub(&g_live_schedules, 1, __ATOMIC_RELAXED);
+    memset(sched, 0, sizeof *sched);
+    __asm__ __volatile__("" : : "r"(sched) : "memory");
+}
+
 int expand_key(keysched *ks, const uint8_t *key, int keybits)
 {
     int nk, total, i;
     uint8_t rcon = 1;
+    ks->nr = 0;
     if (keybits != 128 && keybits != 192 && keybits != 256)
         return fail(UAES_E_ARG, "keybits must be 128, 192 or 256 (got %d)", keybits);
     if (!key) return fail(UAES_E_ARG, "NULL key");
@@ -219,13 +244,14 @@ int expand_key(keysched *ks, const uint8_t *key, int keybits)
         for (c = 0; c < 4; ++c)
             ks->dk.w[4 * i + c] = inv_mix_word(ks->ek.w[4 * (ks->nr - i) + c]);
     }
+    __atomic_fetch_add(&g_live_schedules, 1, __ATOMIC_RELAXED);
     return 0;
 }
 
 /* diagnostic export: lets the CPU test-suite check the schedule without a GPU */
 int uaes_expand_key(int keybits, const uint8_t *key, uint32_t enc_words[60], uint32_t dec_words[60])
 {
-    keysched ks;
+    KEYSCHED(ks);
     int rc = expand_key(&ks, key, keybits);
     if (rc) return rc;
     if (enc_words) memcpy(enc_words, ks.ek.w, sizeof ks.ek.w);
@@ -774,13 +800,7 @@ static void host_policy_from_env(void)             /* once, from env_init() */
     g_host.fallback = env_int("UAES_HOST_FALLBACK", g_host.fallback, 0, 1);
 }
 
-/* leaving through the host path: the schedule on the caller's stack is wiped (the reference BURNs its RoundKey after
- * every call, micro_aes.c:360) and a non-zero code gets its text in uaes_last_error() like the device path's */
-void burn(void *p, size_t n)
-{
-    volatile unsigned char *v = (volatile unsigned char *)p;
-    while (n--) *v++ = 0;
-}
+/* leaving through the host path: a non-zero code gets its text in uaes_last_error() like the device path's */
 int host_result(int rc)
 {
     if (rc == UAES_E_AUTHENTICATION) return fail(rc, "authentication failed (host path)");
@@ -1056,7 +1076,7 @@ static void *pipe_worker(void *p)
         e = hipMemcpyAsync(d, j->in + off, len, hipMemcpyHostToDevice, st);
         if (e != hipSuccess) PFAIL(j, "slice copy in: %s", hipGetErrorString(e));
         int k = j->fn(j->arg, j->worker, st, d, d, off, len);
-        if (k > 0) PFAIL(j, "slice launch: %s", hipGetErrorString((hipError_t)k));
+        if (k > 0 && launched("slice", k)) PFAIL(j, "%s", uaes_last_error());
         if (k < 0) PFAIL(j, "slice at offset %zu: %s", off, uaes_last_error());   /* this thread's message */
         e = hipMemcpyAsync(j->out + off, d, olen, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -1232,7 +1252,7 @@ int uaes_selftest(void)
 {
     context *c;
     lane *L;
-    keysched ks;
+    KEYSCHED(ks);
     uint8_t key[16];
     unsigned result = 0;
     int i, rc;
@@ -1243,7 +1263,7 @@ int uaes_selftest(void)
         unsigned *d = (unsigned *)L->d_status;
         if (hipMemsetAsync(d, 0, 4, (hipStream_t)L->stream) != hipSuccess) { rc = fail(UAES_E_HIP, "hipMemset failed"); break; }
         int k = uaesk_selftest(L->stream, &c->tb, &ks.ek, &ks.dk, d);
-        if (k) { rc = fail(UAES_E_HIP, "selftest launch: %s", hipGetErrorString((hipError_t)k)); break; }
+        if ((rc = launched("selftest", k)) != 0) break;
         if ((rc = lane_fetch(L, &result, d, 4)) != 0) break;
         rc = (int)result;
     } while (0);
@@ -1516,6 +1536,8 @@ const char *uaes_debug_plan_ocb(int dir, size_t len, size_t aad_len, int aad_ali
     return uaesk_arrangement_name(p.arrangement);
 }
 void uaes_debug_plan_disable(unsigned mask) { uaesk_plan_disable(mask); }
+
+int uaes_debug_live_key_schedules(void) { return __atomic_load_n(&g_live_schedules, __ATOMIC_RELAXED); }
 
 /* ---- test hooks of the one-launch GCM arrangements (include/uaes_hip.h) ---- */
 void uaes_debug_gcm_look(unsigned long long ticks_100mhz) { uaesk_debug_gcm_look(ticks_100mhz); }

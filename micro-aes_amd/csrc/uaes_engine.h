@@ -44,9 +44,16 @@
 
 /* ---- key schedule ---- */
 typedef struct {
-    int      nr;
+    int      nr;                    /* 0: never expanded, or wiped */
     uaesk_rk ek, dk;
 } keysched;
+
+/* A schedule on the stack is declared with KEYSCHED(ks); at the top of its function (before any label), never as a
+ * plain local: every way out of the scope then wipes it (keysched_wipe; the reference BURNs its RoundKey after every
+ * call, micro_aes.c:360), also one taken before expand_key was reached (nr = 0 is all the declaration sets: the rest
+ * is expand_key's to fill).  A keysched is handed on by pointer only.                                              */
+void keysched_wipe(keysched *ks);
+#define KEYSCHED(name) keysched name __attribute__((cleanup(keysched_wipe))); name.nr = 0
 
 /* ---- per-device context and per-thread lanes ---- */
 /* Device scratch (GHASH tables and accumulators, XTS chunk tweaks, OCB offsets) is private
@@ -124,9 +131,7 @@ typedef struct lane {
 #define SCRATCH_TAIL 256u
 enum { SCRATCH_OTHER = 0, SCRATCH_GCM_KEYED = 1 };
 
-/* ---- host path, staging of the caller's buffers, the slice pipeline ---- */
-#define HOST_RET(ksv, rc) do { const int hr_ = (rc); burn(&(ksv), sizeof (ksv)); return host_result(hr_); } while (0)
-
+/* ---- staging of the caller's buffers, the slice pipeline ---- */
 /* Resolve (in, out) to device pointers, staging whatever is host memory or
  * misaligned.  in_len bytes are copied in; the caller copies out_len back
  * with finish_io().                                                          */
@@ -177,6 +182,7 @@ typedef struct {
 
 /* ---- uaes_engine.c ---- */
 int fail(int code, const char *fmt, ...);
+int launched(const char *what, int k);
 int wipe_on_auth_failure(void);
 int gcm_decrypt_mode(void);
 int tags_differ(const uint8_t *a, const uint8_t *b, size_t n);

@@ -23,11 +23,9 @@ static int lane_gcm_keyed(lane *L, const keysched *ks, const uint8_t *key, int k
     if (L->gk_state && L->gk_bits == keybits && memcmp(L->gk, key, kb) == 0) {
         if (L->gk_state == GK_TABLES) return 1;
         if (++L->gk_state < GK_BUILD_AT) return 0;
-        {
-            int k = uaesk_gcm_key_tables(L->stream, &L->c->tb, ks->nr, &ks->ek, L->scratch);
-            if (k) return fail(UAES_E_HIP, "key table launch: %s", hipGetErrorString((hipError_t)k));
-            L->gk_state = GK_TABLES;
-        }
+        const int rc = launched("key table", uaesk_gcm_key_tables(L->stream, &L->c->tb, ks->nr, &ks->ek, L->scratch));
+        if (rc) return rc;
+        L->gk_state = GK_TABLES;
         return 1;
     }
     memset(L->gk, 0, sizeof L->gk);
@@ -119,7 +117,7 @@ int uaes_gcm_encrypt_ex(int keybits, const uint8_t *key, const uint8_t *nonce, s
 {
     context *c;
     lane *L;
-    keysched ks;
+    KEYSCHED(ks);
     io_plan io;
     const void *d_aad;
     uint8_t j0[16];
@@ -131,7 +129,7 @@ int uaes_gcm_encrypt_ex(int keybits, const uint8_t *key, const uint8_t *nonce, s
     if (aDataLen && !aData) return fail(UAES_E_ARG, "NULL aData with aDataLen != 0");
     if (host_take_mode(pntxt, crtxt, ptextLen, 0, 1) && !is_device_ptr(aData)) {
         const uaesh_key hk = host_key(&ks);
-        HOST_RET(ks, uaesh_gcm(&hk, 0, nonce, nonceLen, tagLen, (const uint8_t *)aData, aDataLen, (const uint8_t *)pntxt, ptextLen, (uint8_t *)crtxt));
+        return host_result(uaesh_gcm(&hk, 0, nonce, nonceLen, tagLen, (const uint8_t *)aData, aDataLen, (const uint8_t *)pntxt, ptextLen, (uint8_t *)crtxt));
     }
     if (nonceLen == 12 && tagLen == 16) {
         int devs[MAX_DEVICES];
@@ -165,7 +163,7 @@ int uaes_gcm_encrypt_ex(int keybits, const uint8_t *key, const uint8_t *nonce, s
                                   io.din, ptextLen, io.dout, L->scratch, NULL);
         arm_done_word(NULL);
         ticket_armed_launch_done(L);
-        if (k) { rc = fail(UAES_E_HIP, "gcm launch: %s", hipGetErrorString((hipError_t)k)); break; }
+        if ((rc = launched("gcm", k)) != 0) break;
         rc = finish_io(&io, ptextLen + tagLen);
     } while (0);
     DONE(L, rc);
@@ -191,7 +189,7 @@ int uaes_gcm_decrypt_ex(int keybits, const uint8_t *key, const uint8_t *nonce, s
 {
     context *c;
     lane *L;
-    keysched ks;
+    KEYSCHED(ks);
     io_plan io;
     const void *d_aad;
     uint8_t j0[16];
@@ -203,7 +201,7 @@ int uaes_gcm_decrypt_ex(int keybits, const uint8_t *key, const uint8_t *nonce, s
     if (aDataLen && !aData) return fail(UAES_E_ARG, "NULL aData with aDataLen != 0");
     if (host_take_mode(crtxt, pntxt, crtxtLen, 0, 1) && !is_device_ptr(aData)) {
         const uaesh_key hk = host_key(&ks);
-        HOST_RET(ks, uaesh_gcm(&hk, 1, nonce, nonceLen, tagLen, (const uint8_t *)aData, aDataLen, (const uint8_t *)crtxt, crtxtLen, (uint8_t *)pntxt));
+        return host_result(uaesh_gcm(&hk, 1, nonce, nonceLen, tagLen, (const uint8_t *)aData, aDataLen, (const uint8_t *)crtxt, crtxtLen, (uint8_t *)pntxt));
     }
     if (nonceLen == 12 && tagLen == 16) {
         int devs[MAX_DEVICES];
@@ -232,7 +230,7 @@ int uaes_gcm_decrypt_ex(int keybits, const uint8_t *key, const uint8_t *nonce, s
                                             io.din, crtxtLen, NULL, L->scratch, L->d_status + 4)
                           : uaesk_gcm(L->stream, &c->tb, ks.nr, &ks.ek, 3, j0, d_aad, aDataLen,
                                       io.din, crtxtLen, NULL, L->scratch, L->d_status + 4);
-            if (k) { rc = fail(UAES_E_HIP, "gcm launch: %s", hipGetErrorString((hipError_t)k)); break; }
+            if ((rc = launched("gcm", k)) != 0) break;
             if ((rc = lane_fetch(L, full, L->d_status + 4, 16)) != 0) break;
             if (is_device_ptr(io.din)) {
                 if (hipMemcpy(given, (const char *)io.din + crtxtLen, tagLen, hipMemcpyDeviceToHost) != hipSuccess) {
@@ -244,7 +242,7 @@ int uaes_gcm_decrypt_ex(int keybits, const uint8_t *key, const uint8_t *nonce, s
             }
             if (tags_differ(full, given, tagLen)) { rc = UAES_E_AUTHENTICATION; break; }
             k = uaesk_gcm_ctr(L->stream, &c->tb, ks.nr, &ks.ek, j0, io.din, crtxtLen, io.dout);
-            if (k) { rc = fail(UAES_E_HIP, "gcm launch: %s", hipGetErrorString((hipError_t)k)); break; }
+            if ((rc = launched("gcm", k)) != 0) break;
             rc = finish_io(&io, crtxtLen);
             break;
         }
@@ -266,7 +264,7 @@ int uaes_gcm_decrypt_ex(int keybits, const uint8_t *key, const uint8_t *nonce, s
                                   L->scratch, st_where);
         arm_done_word(NULL);
         ticket_armed_launch_done(L);
-        if (k) { rc = fail(UAES_E_HIP, "gcm launch: %s", hipGetErrorString((hipError_t)k)); break; }
+        if ((rc = launched("gcm", k)) != 0) break;
         if ((rc = lane_read_status(L, st_where, &status)) != 0) break;
         if (status != 0) { rc = UAES_E_AUTHENTICATION; break; }  /* N7: pntxt untouched */
         io.drained = 1;
@@ -294,7 +292,7 @@ int uaes_gcm_encrypt_dev(int keybits, const uint8_t *key, const uint8_t *nonce,
                          const void *d_in, size_t len, void *d_out, void *stream)
 {
     context *c;
-    keysched ks;
+    KEYSCHED(ks);
     void *scr;
     uint8_t j0[16];
     int rc, slot;
@@ -317,7 +315,7 @@ int uaes_gcm_decrypt_dev(int keybits, const uint8_t *key, const uint8_t *nonce,
                          int *d_status, void *stream)
 {
     context *c;
-    keysched ks;
+    KEYSCHED(ks);
     void *scr;
     uint8_t j0[16];
     int rc, slot;
@@ -357,7 +355,7 @@ int uaes_gcm_key_new(uaes_gcm_key **out, int keybits, const uint8_t *key)
     if ((k = (uaes_gcm_key *)calloc(1, sizeof *k)) == NULL) return fail(UAES_E_HIP, "out of host memory");
     /* every way out below wipes the expanded key before the memory goes back to the allocator */
     if ((rc = expand_key(&k->ks, key, keybits)) != 0 || (rc = enter(&c, &L)) != 0) {
-        memset(k, 0, sizeof *k);
+        keysched_wipe(&k->ks);
         free(k);
         return rc;
     }
@@ -369,13 +367,12 @@ int uaes_gcm_key_new(uaes_gcm_key **out, int keybits, const uint8_t *key)
     if (rc == 0 && hipMemsetAsync(KEY_DONE_WORD(k), 0, SCRATCH_TAIL, (hipStream_t)L->stream) != hipSuccess)
         rc = fail(UAES_E_HIP, "key context: hipMemsetAsync failed");
     if (rc == 0) {
-        int kk = uaesk_gcm_key_tables(L->stream, &c->tb, k->ks.nr, &k->ks.ek, k->scratch);
-        if (kk) rc = fail(UAES_E_HIP, "key table launch: %s", hipGetErrorString((hipError_t)kk));
-        else if (hipStreamSynchronize((hipStream_t)L->stream) != hipSuccess) rc = fail(UAES_E_HIP, "key table build failed");
+        rc = launched("key table", uaesk_gcm_key_tables(L->stream, &c->tb, k->ks.nr, &k->ks.ek, k->scratch));
+        if (rc == 0 && hipStreamSynchronize((hipStream_t)L->stream) != hipSuccess) rc = fail(UAES_E_HIP, "key table build failed");
     }
     if (rc) {
         if (k->scratch) (void)hipFree(k->scratch);
-        memset(k, 0, sizeof *k);
+        keysched_wipe(&k->ks);
         free(k);
         return rc;
     }
@@ -391,7 +388,7 @@ void uaes_gcm_key_free(uaes_gcm_key *k)
         (void)hipMemset(k->scratch, 0, uaesk_gcm_scratch_bytes());    /* H and its tables are key material */
         (void)hipFree(k->scratch);
     }
-    memset(k, 0, sizeof *k);
+    keysched_wipe(&k->ks);
     free(k);
 }
 
@@ -426,7 +423,7 @@ int uaes_gcm_key_encrypt(uaes_gcm_key *k, const uint8_t *nonce, const void *aDat
                                  io.din, ptextLen, io.dout, k->scratch, NULL);
         arm_done_word(NULL);
         ticket_armed_launch_done(L);
-        if (kk) { rc = fail(UAES_E_HIP, "gcm launch: %s", hipGetErrorString((hipError_t)kk)); break; }
+        if ((rc = launched("gcm", kk)) != 0) break;
         rc = finish_io(&io, ptextLen + 16);
     } while (0);
     DONE(L, rc);
@@ -460,7 +457,7 @@ int uaes_gcm_key_decrypt(uaes_gcm_key *k, const uint8_t *nonce, const void *aDat
                                  io.din, crtxtLen, io.dout, k->scratch, st_where);
         arm_done_word(NULL);
         ticket_armed_launch_done(L);
-        if (kk) { rc = fail(UAES_E_HIP, "gcm launch: %s", hipGetErrorString((hipError_t)kk)); break; }
+        if ((rc = launched("gcm", kk)) != 0) break;
         if ((rc = lane_read_status(L, st_where, &status)) != 0) break;
         if (status != 0) { rc = UAES_E_AUTHENTICATION; break; }  /* N7: pntxt untouched */
         io.drained = 1;
@@ -682,7 +679,7 @@ static int records_sync(uaes_gcm_key *k, int decrypt, size_t nrec, const uint8_t
                                        aad_span ? d_meta + non_span : NULL, aad_len, aad_stride, d_in, rec_len, in_stride,
                                        d_out, out_stride, nrec, k->scratch, decrypt ? d_ver : NULL, decrypt ? L->d_status : NULL,
                                        lens ? d_meta + lens_off : NULL);
-            if (kk) { rc = fail(UAES_E_HIP, "gcm records launch: %s", hipGetErrorString((hipError_t)kk)); break; }
+            if ((rc = launched("gcm records", kk)) != 0) break;
         }
         if (decrypt) {
             if ((rc = lane_fetch(L, &status, L->d_status, sizeof status)) != 0) break;
@@ -775,7 +772,7 @@ int uaes_gcm_partial_dev(int keybits, const uint8_t *key, const uint8_t *nonce,
                          uint64_t total_len, void *d_partial16, void *stream)
 {
     context *c;
-    keysched ks;
+    KEYSCHED(ks);
     void *scr;
     int rc, slot;
     if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
@@ -799,7 +796,7 @@ int uaes_gcm_shard_dev(int keybits, const uint8_t *key, const uint8_t *nonce, in
                        void *d_out, void *d_partial16, void *stream)
 {
     context *c;
-    keysched ks;
+    KEYSCHED(ks);
     void *scr;
     int rc, slot;
     if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
@@ -833,7 +830,7 @@ int uaes_ghash(const uint8_t H[16], const void *aData, size_t aDataLen,
         if ((rc = stage_aad(L, aData, aDataLen, &d_aad)) != 0) break;
         if ((rc = plan_io(L, crtxt, crtxtLen, NULL, 0, &io)) != 0) break;
         int k = uaesk_ghash(L->stream, &c->tb, H, d_aad, aDataLen, io.din, crtxtLen, L->scratch, L->d_status + 4);
-        if (k) { rc = fail(UAES_E_HIP, "ghash launch: %s", hipGetErrorString((hipError_t)k)); break; }
+        if ((rc = launched("ghash", k)) != 0) break;
         rc = lane_fetch(L, gh, L->d_status + 4, 16);
     } while (0);
     DONE(L, rc);
@@ -851,6 +848,7 @@ int uaes_gcmsiv_encrypt(int keybits, const uint8_t *key, const uint8_t *nonce,
 {
     context *c;
     lane *L;
+    KEYSCHED(mk);
     io_plan io;
     const void *d_aad;
     int rc;
@@ -858,13 +856,10 @@ int uaes_gcmsiv_encrypt(int keybits, const uint8_t *key, const uint8_t *nonce,
         return fail(UAES_E_ARG, "keybits must be 128, 192 or 256 (got %d)", keybits);
     if (!key || !nonce || !crtxt || (ptextLen && !pntxt)) return fail(UAES_E_ARG, "NULL pointer");
     if (aDataLen && !aData) return fail(UAES_E_ARG, "NULL aData with aDataLen != 0");
+    if ((rc = expand_key(&mk, key, keybits)) != 0) return rc;       /* (checked above: it cannot fail) */
     if (host_take(pntxt, crtxt, ptextLen, 0) && !is_device_ptr(aData)) {
-        keysched mk;
-        uaesh_key hk;
-        if ((rc = expand_key(&mk, key, keybits)) != 0) return rc;
-        hk = host_key(&mk);
+        const uaesh_key hk = host_key(&mk);
         rc = uaesh_gcmsiv(&hk, keybits, 0, nonce, (const uint8_t *)aData, aDataLen, (const uint8_t *)pntxt, ptextLen, (uint8_t *)crtxt, uaes_expand_key);
-        burn(&mk, sizeof mk);
         return host_result(rc);
     }
     if ((rc = enter(&c, &L)) != 0) return rc;
@@ -874,24 +869,18 @@ int uaes_gcmsiv_encrypt(int keybits, const uint8_t *key, const uint8_t *nonce,
         if ((rc = plan_io(L, pntxt, ptextLen, crtxt, ptextLen + 16, &io)) != 0) break;
         {   /* a short message is ONE launch (k_siv_small): key derivation, POLYVAL, tag and keystream in one
              * workgroup; the host only expands the master key */
-            keysched master;
-            if ((rc = expand_key(&master, key, keybits)) != 0) break;
-            int ks = uaesk_gcmsiv_small(L->stream, &c->tb, master.nr, &master.ek, 0, nonce, d_aad, aDataLen,
+            int ks = uaesk_gcmsiv_small(L->stream, &c->tb, mk.nr, &mk.ek, 0, nonce, d_aad, aDataLen,
                                         io.din, ptextLen, io.dout, NULL);
-            memset(&master, 0, sizeof master);
-            if (ks > 0) { rc = fail(UAES_E_HIP, "gcm-siv launch: %s", hipGetErrorString((hipError_t)ks)); break; }
+            if (ks > 0 && (rc = launched("gcm-siv", ks)) != 0) break;
             if (ks == 0) { rc = finish_io(&io, ptextLen + 16); break; }
         }
         {   /* a longer one: six or seven launches one behind the other, the per-nonce key, the hash, the tag and the
              * counter made of it stay on the device (uaesk_gcmsiv_long) -- the host waits once, in finish_io */
-            keysched master;
-            if ((rc = expand_key(&master, key, keybits)) != 0) break;
             arm_done_word(scratch_done_word(L->scratch, L->scratch_cap));
-            int kl = uaesk_gcmsiv_long(L->stream, &c->tb, master.nr, &master.ek, 0, nonce, d_aad, aDataLen,
+            int kl = uaesk_gcmsiv_long(L->stream, &c->tb, mk.nr, &mk.ek, 0, nonce, d_aad, aDataLen,
                                        io.din, ptextLen, io.dout, L->scratch, NULL);
             arm_done_word(NULL);
-            memset(&master, 0, sizeof master);
-            if (kl) { rc = fail(UAES_E_HIP, "gcm-siv launch: %s", hipGetErrorString((hipError_t)kl)); break; }
+            if ((rc = launched("gcm-siv", kl)) != 0) break;
         }
         rc = finish_io(&io, ptextLen + 16);
     } while (0);
@@ -904,6 +893,7 @@ int uaes_gcmsiv_decrypt(int keybits, const uint8_t *key, const uint8_t *nonce,
 {
     context *c;
     lane *L;
+    KEYSCHED(mk);
     io_plan io;
     const void *d_aad;
     int rc;
@@ -911,13 +901,10 @@ int uaes_gcmsiv_decrypt(int keybits, const uint8_t *key, const uint8_t *nonce,
         return fail(UAES_E_ARG, "keybits must be 128, 192 or 256 (got %d)", keybits);
     if (!key || !nonce || !crtxt || (crtxtLen && !pntxt)) return fail(UAES_E_ARG, "NULL pointer");
     if (aDataLen && !aData) return fail(UAES_E_ARG, "NULL aData with aDataLen != 0");
+    if ((rc = expand_key(&mk, key, keybits)) != 0) return rc;       /* (checked above: it cannot fail) */
     if (host_take(crtxt, pntxt, crtxtLen, 0) && !is_device_ptr(aData)) {
-        keysched mk;
-        uaesh_key hk;
-        if ((rc = expand_key(&mk, key, keybits)) != 0) return rc;
-        hk = host_key(&mk);
+        const uaesh_key hk = host_key(&mk);
         rc = uaesh_gcmsiv(&hk, keybits, 1, nonce, (const uint8_t *)aData, aDataLen, (const uint8_t *)crtxt, crtxtLen, (uint8_t *)pntxt, uaes_expand_key);
-        burn(&mk, sizeof mk);
         if (rc == UAES_E_AUTHENTICATION && wipe_on_auth_failure()) memset(pntxt, 0, crtxtLen);
         return host_result(rc);
     }
@@ -927,12 +914,9 @@ int uaes_gcmsiv_decrypt(int keybits, const uint8_t *key, const uint8_t *nonce,
         if ((rc = stage_aad(L, aData, aDataLen, &d_aad)) != 0) break;
         if ((rc = plan_io(L, crtxt, crtxtLen + 16, pntxt, crtxtLen, &io)) != 0) break;
         {   /* a short message is ONE launch (k_siv_small), key derivation included */
-            keysched master;
-            if ((rc = expand_key(&master, key, keybits)) != 0) break;
-            int ks = uaesk_gcmsiv_small(L->stream, &c->tb, master.nr, &master.ek, 1, nonce, d_aad, aDataLen,
+            int ks = uaesk_gcmsiv_small(L->stream, &c->tb, mk.nr, &mk.ek, 1, nonce, d_aad, aDataLen,
                                         io.din, crtxtLen, io.dout, L->d_status);
-            memset(&master, 0, sizeof master);
-            if (ks > 0) { rc = fail(UAES_E_HIP, "gcm-siv launch: %s", hipGetErrorString((hipError_t)ks)); break; }
+            if (ks > 0 && (rc = launched("gcm-siv", ks)) != 0) break;
             if (ks == 0) {
                 int status = -1;
                 if ((rc = lane_fetch(L, &status, L->d_status, sizeof status)) != 0) break;
@@ -945,15 +929,12 @@ int uaes_gcmsiv_decrypt(int keybits, const uint8_t *key, const uint8_t *nonce,
         {   /* like the reference: decrypt with the RECEIVED tag as counter, then authenticate (:1500-1502) -- all of
              * it on the device (uaesk_gcmsiv_long); the text stays (SABOTAGE is a no-op) unless
              * uaes_set_wipe_on_auth_failure(1) */
-            keysched master;
             int status = -1;
-            if ((rc = expand_key(&master, key, keybits)) != 0) break;
             arm_done_word(scratch_done_word(L->scratch, L->scratch_cap));
-            int kl = uaesk_gcmsiv_long(L->stream, &c->tb, master.nr, &master.ek, 1, nonce, d_aad, aDataLen,
+            int kl = uaesk_gcmsiv_long(L->stream, &c->tb, mk.nr, &mk.ek, 1, nonce, d_aad, aDataLen,
                                        io.din, crtxtLen, io.dout, L->scratch, L->d_status);
             arm_done_word(NULL);
-            memset(&master, 0, sizeof master);
-            if (kl) { rc = fail(UAES_E_HIP, "gcm-siv launch: %s", hipGetErrorString((hipError_t)kl)); break; }
+            if ((rc = launched("gcm-siv", kl)) != 0) break;
             if ((rc = lane_fetch(L, &status, L->d_status, sizeof status)) != 0) break;
             io.drained = 1;
             if ((rc = status ? finish_io_unauthenticated(&io, crtxtLen) : finish_io(&io, crtxtLen)) != 0) break;
@@ -993,7 +974,7 @@ int uaes_gcm_stream_begin(uaes_gcm_stream **out, int keybits, const uint8_t *key
     if (!out || !nonce) return fail(UAES_E_ARG, "NULL pointer");
     *out = NULL;
     if ((s = (uaes_gcm_stream *)calloc(1, sizeof *s)) == NULL) return fail(UAES_E_HIP, "out of host memory");
-    if ((rc = expand_key(&s->ks, key, keybits)) != 0 || (rc = enter(&c, &L)) != 0) { memset(s, 0, sizeof *s); free(s); return rc; }
+    if ((rc = expand_key(&s->ks, key, keybits)) != 0 || (rc = enter(&c, &L)) != 0) { keysched_wipe(&s->ks); free(s); return rc; }
     memcpy(s->nonce, nonce, 12);
     s->decrypt = decrypt != 0;
     s->aad_len = aDataLen;
@@ -1002,7 +983,7 @@ int uaes_gcm_stream_begin(uaes_gcm_stream **out, int keybits, const uint8_t *key
     pthread_mutex_unlock(&c->mu);
     if (hipGetDevice(&s->device) != hipSuccess ||
         (!s->scratch && hipMalloc(&s->scratch, STREAM_SCRATCH_BYTES + 64) != hipSuccess)) {
-        memset(s, 0, sizeof *s);
+        keysched_wipe(&s->ks);
         free(s);
         return fail(UAES_E_HIP, "stream scratch allocation failed");
     }
@@ -1013,10 +994,10 @@ int uaes_gcm_stream_begin(uaes_gcm_stream **out, int keybits, const uint8_t *key
         if ((rc = stage_aad(L, aData, aDataLen, &d_aad)) != 0) break;
         int k = uaesk_gcm_stream_absorb(L->stream, &c->tb, s->ks.nr, &s->ks.ek, s->nonce, 0, d_aad, aDataLen,
                                         0, 0, s->scratch, &s->plan_state);
-        if (k) { rc = fail(UAES_E_HIP, "gcm stream launch: %s", hipGetErrorString((hipError_t)k)); break; }
+        if ((rc = launched("gcm stream", k)) != 0) break;
         rc = lane_sync(L);
     } while (0);
-    if (rc) { (void)lane_abandon(L, rc); (void)hipFree(s->scratch); memset(s, 0, sizeof *s); free(s); return rc; }
+    if (rc) { (void)lane_abandon(L, rc); (void)hipFree(s->scratch); keysched_wipe(&s->ks); free(s); return rc; }
     *out = s;
     return 0;
 }
@@ -1060,7 +1041,7 @@ static int gcm_stream_update_on_device(uaes_gcm_stream *s, const void *in, size_
         k = uaesk_gcm_stream_piece(L->stream, &c->tb, s->ks.nr, &s->ks.ek, s->nonce, s->decrypt, io.din, len, s->done, io.dout,
                                    s->scratch, &s->plan_state, stream_done_word(s));
         if (k == 0) { rc = finish_io(&io, len); break; }
-        if (k != 1) { rc = fail(UAES_E_HIP, "gcm stream launch: %s", hipGetErrorString((hipError_t)k)); break; }
+        if (k != 1 && (rc = launched("gcm stream", k)) != 0) break;
         if (s->decrypt) {                             /* hash the ciphertext before it may be overwritten */
             k = uaesk_gcm_stream_absorb(L->stream, &c->tb, s->ks.nr, &s->ks.ek, s->nonce, 1, io.din, len, 0, 0, s->scratch, &s->plan_state);
             if (!k) k = uaesk_ctr_xcrypt(L->stream, &c->tb, s->ks.nr, &s->ks.ek, &ctr, io.din, io.dout, len, NULL);
@@ -1068,7 +1049,7 @@ static int gcm_stream_update_on_device(uaes_gcm_stream *s, const void *in, size_
             k = uaesk_ctr_xcrypt(L->stream, &c->tb, s->ks.nr, &s->ks.ek, &ctr, io.din, io.dout, len, NULL);
             if (!k) k = uaesk_gcm_stream_absorb(L->stream, &c->tb, s->ks.nr, &s->ks.ek, s->nonce, 1, io.dout, len, 0, 0, s->scratch, &s->plan_state);
         }
-        if (k) { rc = fail(UAES_E_HIP, "gcm stream launch: %s", hipGetErrorString((hipError_t)k)); break; }
+        if ((rc = launched("gcm stream", k)) != 0) break;
         rc = finish_io(&io, len);
     } while (0);
     if (rc) (void)lane_abandon(L, rc);
@@ -1139,7 +1120,7 @@ void uaes_gcm_stream_abort(uaes_gcm_stream *s)
             (void)fail(UAES_E_HIP, "uaes_gcm_stream_abort: hipFree of the stream scratch failed");
         if (prev >= 0 && prev != s->device) (void)hipSetDevice(prev);
     }
-    memset(s, 0, sizeof *s);                          /* key schedule */
+    keysched_wipe(&s->ks);
     free(s);
 }
 
@@ -1154,7 +1135,7 @@ int gcm_shard_sync(int keybits, const uint8_t *key, const uint8_t *nonce, int mo
 {
     context *c;
     lane *L;
-    keysched ks;
+    KEYSCHED(ks);
     io_plan io;
     const void *d_aad = NULL;
     int rc;
@@ -1167,10 +1148,9 @@ int gcm_shard_sync(int keybits, const uint8_t *key, const uint8_t *nonce, int mo
         if ((rc = plan_io(L, in, len, mode == 1 ? NULL : out, mode == 1 ? 0 : len, &io)) != 0) break;
         k = uaesk_gcm_shard(L->stream, &c->tb, ks.nr, &ks.ek, mode, nonce, d_aad, aDataLen, io.din, len, off, total,
                             mode == 1 ? NULL : io.dout, L->scratch, L->d_status + 4);
-        if (k) { rc = fail(UAES_E_HIP, "gcm shard launch: %s", hipGetErrorString((hipError_t)k)); break; }
+        if ((rc = launched("gcm shard", k)) != 0) break;
         if ((rc = lane_fetch(L, share, L->d_status + 4, 16)) != 0) break;
         if (mode != 1) { io.drained = 1; rc = finish_io(&io, len); }
     } while (0);
-    memset(&ks, 0, sizeof ks);
     DONE(L, rc);
 }

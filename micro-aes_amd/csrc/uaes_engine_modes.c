@@ -25,7 +25,7 @@ static int ecb_common(int keybits, const uint8_t *key, int decrypt, int padding,
 {
     context *c;
     lane *L;
-    keysched ks;
+    KEYSCHED(ks);
     io_plan io;
     int rc;
     const size_t rem = len % 16, nfull = len / 16;
@@ -36,9 +36,9 @@ static int ecb_common(int keybits, const uint8_t *key, int decrypt, int padding,
     if ((len && !in) || !out) return fail(UAES_E_ARG, "NULL data pointer");
     if (host_take(in, out, len, 0)) {
         const uaesh_key hk = host_key(&ks);
-        if (!decrypt) { uaesh_ecb_encrypt(&hk, padding, (const uint8_t *)in, len, (uint8_t *)out); HOST_RET(ks, 0); }
+        if (!decrypt) { uaesh_ecb_encrypt(&hk, padding, (const uint8_t *)in, len, (uint8_t *)out); return host_result(0); }
         uaesh_ecb_decrypt(&hk, (const uint8_t *)in, len, (uint8_t *)out);
-        HOST_RET(ks, rem ? UAES_E_DECRYPTION : 0);
+        return host_result(rem ? UAES_E_DECRYPTION : 0);
     }
     {
         int devs[MAX_DEVICES];
@@ -64,7 +64,7 @@ static int ecb_common(int keybits, const uint8_t *key, int decrypt, int padding,
         int k = uaesk_ecb(L->stream, &c->tb, ks.nr, decrypt ? &ks.dk : &ks.ek, decrypt,
                           io.din, io.dout, nfull, decrypt ? 0 : (unsigned)rem, decrypt ? 0 : (unsigned)padding);
         ticket_armed_launch_done(L);
-        if (k) { rc = fail(UAES_E_HIP, "ecb launch: %s", hipGetErrorString((hipError_t)k)); break; }
+        if ((rc = launched("ecb", k)) != 0) break;
         if ((rc = finish_io(&io, out_len)) != 0) break;
         rc = (decrypt && rem) ? UAES_E_DECRYPTION : 0;           /* :679 */
     } while (0);
@@ -91,7 +91,7 @@ int uaes_ecb_dev(int keybits, const uint8_t *key, int decrypt,
                  const void *d_in, size_t len, void *d_out, void *stream)
 {
     context *c;
-    keysched ks;
+    KEYSCHED(ks);
     int rc;
     if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
     if ((rc = dev_ptrs_ok(d_in, d_out, len)) != 0) return rc;
@@ -110,7 +110,7 @@ int uaes_ctr_xcrypt_at_dev(int keybits, const uint8_t *key, const uint8_t ctr0[1
                            const void *d_in, size_t len, void *d_out, void *stream)
 {
     context *c;
-    keysched ks;
+    KEYSCHED(ks);
     uaesk_ctr ctr;
     int rc;
     if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
@@ -138,7 +138,7 @@ int uaes_ctr_xcrypt_at(int keybits, const uint8_t *key, const uint8_t ctr0[16],
 {
     context *c;
     lane *L;
-    keysched ks;
+    KEYSCHED(ks);
     uaesk_ctr ctr;
     io_plan io;
     int rc;
@@ -149,7 +149,7 @@ int uaes_ctr_xcrypt_at(int keybits, const uint8_t *key, const uint8_t ctr0[16],
     if (host_take(in, out, len, 0)) {
         const uaesh_key hk = host_key(&ks);
         uaesh_ctr(&hk, ctr0, block_offset, (const uint8_t *)in, len, (uint8_t *)out);
-        HOST_RET(ks, 0);
+        return host_result(0);
     }
     {
         int devs[MAX_DEVICES];
@@ -166,7 +166,7 @@ int uaes_ctr_xcrypt_at(int keybits, const uint8_t *key, const uint8_t ctr0[16],
         ticket_arm(L, len);
         int k = uaesk_ctr_xcrypt(L->stream, &c->tb, ks.nr, &ks.ek, &ctr, io.din, io.dout, len, NULL);
         ticket_armed_launch_done(L);
-        if (k) { rc = fail(UAES_E_HIP, "ctr launch: %s", hipGetErrorString((hipError_t)k)); break; }
+        if ((rc = launched("ctr", k)) != 0) break;
         rc = finish_io(&io, len);
     } while (0);
     DONE(L, rc);
@@ -220,8 +220,7 @@ static int xts_run(context *c, void *stream, keysched *k1, keysched *k2, int enc
     k = uaesk_xts(stream, &c->tb, k1->nr, encrypt ? &k1->ek : &k1->dk, &k2->ek, !encrypt,
                   tweak16, first_sector, sector_bytes, nsectors, din, dout, scratch);
     if (slot >= 0) scratch_unpin(c, slot);
-    if (k) return fail(UAES_E_HIP, "xts launch: %s", hipGetErrorString((hipError_t)k));
-    return 0;
+    return launched("xts", k);
 }
 
 typedef struct { context *c; keysched *k1, *k2; int encrypt; uint64_t first_sector; size_t sector_bytes; } xts_pipe_arg;
@@ -246,7 +245,8 @@ static int xts_common(int keybits, const uint8_t *keys, const uint8_t *tweak, in
 {
     context *c;
     lane *L;
-    keysched k1, k2;
+    KEYSCHED(k1);
+    KEYSCHED(k2);
     io_plan io;
     uint8_t zero[16] = { 0 };
     int rc;
@@ -259,7 +259,7 @@ static int xts_common(int keybits, const uint8_t *keys, const uint8_t *tweak, in
         const uaesh_key h1 = host_key(&k1), h2 = host_key(&k2);
         if (raw_tweak) uaesh_xts_unit(&h1, &h2, encrypt, tweak ? tweak : zero, (const uint8_t *)in, sector_bytes, (uint8_t *)out);
         else uaesh_xts_sectors(&h1, &h2, encrypt, first_sector, sector_bytes, nsectors, (const uint8_t *)in, (uint8_t *)out);
-        do { burn(&k2, sizeof k2); HOST_RET(k1, 0); } while (0);
+        return host_result(0);
     }
     if (!raw_tweak && nsectors > 1) {
         int devs[MAX_DEVICES];
@@ -306,7 +306,8 @@ int uaes_xts_sectors_dev(int keybits, const uint8_t *keys, uint64_t first_sector
                          const void *d_in, void *d_out, int encrypt, void *stream)
 {
     context *c;
-    keysched k1, k2;
+    KEYSCHED(k1);
+    KEYSCHED(k2);
     int rc;
     if ((rc = xts_keys(&k1, &k2, keys, keybits)) != 0) return rc;
     if ((rc = dev_ptrs_ok(d_in, d_out, sector_bytes * nsectors)) != 0) return rc;
@@ -322,7 +323,7 @@ int uaes_cmac(int keybits, const uint8_t *key, const void *data, size_t dataSize
 {
     context *c;
     lane *L;
-    keysched ks;
+    KEYSCHED(ks);
     io_plan io;
     int rc;
     if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
@@ -330,13 +331,13 @@ int uaes_cmac(int keybits, const uint8_t *key, const void *data, size_t dataSize
     if (host_take(data, NULL, dataSize, 1)) {
         const uaesh_key hk = host_key(&ks);
         uaesh_cmac(&hk, (const uint8_t *)data, dataSize, mac);
-        HOST_RET(ks, 0);
+        return host_result(0);
     }
     if ((rc = enter(&c, &L)) != 0) return rc;
     do {
         if ((rc = plan_io(L, data, dataSize, NULL, 0, &io)) != 0) break;
         int k = uaesk_cmac(L->stream, &c->tb, ks.nr, &ks.ek, io.din, dataSize, L->d_status + 4);
-        if (k) { rc = fail(UAES_E_HIP, "cmac launch: %s", hipGetErrorString((hipError_t)k)); break; }
+        if ((rc = launched("cmac", k)) != 0) break;
         rc = lane_fetch(L, mac, L->d_status + 4, 16);
     } while (0);
     DONE(L, rc);
@@ -352,7 +353,7 @@ int uaes_poly1305(int keybits, const uint8_t *keys, const uint8_t nonce[16],
 {
     context *c;
     lane *L;
-    keysched ks;
+    KEYSCHED(ks);
     io_plan io;
     int rc;
     if (!keys || !nonce || !mac || (dataSize && !data)) return fail(UAES_E_ARG, "NULL pointer");
@@ -361,19 +362,18 @@ int uaes_poly1305(int keybits, const uint8_t *keys, const uint8_t nonce[16],
     if (host_take(data, NULL, dataSize, 0)) {
         const uaesh_key hk = host_key(&ks);
         uaesh_poly1305(&hk, r, nonce, (const uint8_t *)data, dataSize, mac);
-        HOST_RET(ks, 0);
+        return host_result(0);
     }
-    if ((rc = enter(&c, &L)) != 0) { burn(&ks, sizeof ks); return rc; }
+    if ((rc = enter(&c, &L)) != 0) return rc;
     do {
         const size_t need = uaesk_poly1305_scratch_bytes(dataSize);
         if ((rc = plan_io(L, data, dataSize, NULL, 0, &io)) != 0) break;
         if (need && (rc = lane_scratch(L, need, SCRATCH_OTHER)) != 0) break;
         int k = uaesk_poly1305(L->stream, &c->tb, ks.nr, &ks.ek, r, nonce, io.din, dataSize, L->d_status + 4,
                                need ? L->scratch : NULL);
-        if (k) { rc = fail(UAES_E_HIP, "poly1305 launch: %s", hipGetErrorString((hipError_t)k)); break; }
+        if ((rc = launched("poly1305", k)) != 0) break;
         rc = lane_fetch(L, mac, L->d_status + 4, 16);
     } while (0);
-    burn(&ks, sizeof ks);
     DONE(L, rc);
 }
 
@@ -381,21 +381,20 @@ int uaes_poly1305_dev(int keybits, const uint8_t *keys, const uint8_t nonce[16],
                       const void *d_data, size_t len, void *d_mac, void *stream)
 {
     context *c;
-    keysched ks;
+    KEYSCHED(ks);
     void *scr = NULL;
     int rc, slot = -1;
     if (!keys || !nonce || !d_mac || (len && !d_data)) return fail(UAES_E_ARG, "NULL pointer");
     if ((rc = expand_key(&ks, keys, keybits)) != 0) return rc;
     const size_t need = uaesk_poly1305_scratch_bytes(len);
-    if ((rc = get_context(&c)) != 0) { burn(&ks, sizeof ks); return rc; }
+    if ((rc = get_context(&c)) != 0) return rc;
     if (need) {
         pthread_mutex_lock(&c->mu);
         rc = scratch_pin(c, stream, need, &scr, &slot);
         pthread_mutex_unlock(&c->mu);
-        if (rc) { burn(&ks, sizeof ks); return fail(UAES_E_HIP, "poly1305 scratch"); }
+        if (rc) return fail(UAES_E_HIP, "poly1305 scratch");
     }
     rc = uaesk_poly1305(stream, &c->tb, ks.nr, &ks.ek, keys + keybits / 8, nonce, d_data, len, d_mac, scr);
-    burn(&ks, sizeof ks);
     KCHK_PINNED(c, slot, rc);
     return 0;
 }
@@ -405,15 +404,15 @@ int uaes_poly1305_batch(int keybits, const uint8_t *keys, const uint8_t *nonces,
 {
     context *c;
     lane *L;
-    keysched ks;
+    KEYSCHED(ks);
     io_plan io;
     const void *d_nonces = NULL;
     int rc;
     if (msg_bytes && nmsg > (size_t)-1 / msg_bytes) return fail(UAES_E_ARG, "batch size overflows");
     if (!keys || (nmsg && (!nonces || !macs)) || (nmsg && msg_bytes && !data)) return fail(UAES_E_ARG, "NULL pointer");
     if ((rc = expand_key(&ks, keys, keybits)) != 0) return rc;
-    if (nmsg == 0) { burn(&ks, sizeof ks); return 0; }
-    if ((rc = enter(&c, &L)) != 0) { burn(&ks, sizeof ks); return rc; }
+    if (nmsg == 0) return 0;
+    if ((rc = enter(&c, &L)) != 0) return rc;
     do {
         if ((rc = stage_aad(L, nonces, nmsg * 16, &d_nonces)) != 0) break;       /* host nonces -> device */
         if ((rc = plan_io(L, data, nmsg * msg_bytes, macs, nmsg * 16, &io)) != 0) break;
@@ -423,10 +422,9 @@ int uaes_poly1305_batch(int keybits, const uint8_t *keys, const uint8_t *nonces,
         }
         int k = uaesk_poly1305_batch(L->stream, &c->tb, ks.nr, &ks.ek, keys + keybits / 8, d_nonces, nmsg, msg_bytes,
                                      io.din, io.dout);
-        if (k) { rc = fail(UAES_E_HIP, "poly1305 batch launch: %s", hipGetErrorString((hipError_t)k)); break; }
+        if ((rc = launched("poly1305 batch", k)) != 0) break;
         rc = finish_io(&io, nmsg * 16);
     } while (0);
-    burn(&ks, sizeof ks);
     DONE(L, rc);
 }
 
@@ -444,7 +442,7 @@ int uaes_ccm_encrypt_ex(int keybits, const uint8_t *key, const uint8_t *nonce, s
 {
     context *c;
     lane *L;
-    keysched ks;
+    KEYSCHED(ks);
     io_plan io;
     const void *d_aad;
     int rc;
@@ -454,7 +452,7 @@ int uaes_ccm_encrypt_ex(int keybits, const uint8_t *key, const uint8_t *nonce, s
     if (aDataLen && !aData) return fail(UAES_E_ARG, "NULL aData with aDataLen != 0");
     if (host_take(pntxt, crtxt, ptextLen, 1) && !is_device_ptr(aData)) {
         const uaesh_key hk = host_key(&ks);
-        HOST_RET(ks, uaesh_ccm(&hk, 0, nonce, nonceLen, tagLen, (const uint8_t *)aData, aDataLen, (const uint8_t *)pntxt, ptextLen, (uint8_t *)crtxt));
+        return host_result(uaesh_ccm(&hk, 0, nonce, nonceLen, tagLen, (const uint8_t *)aData, aDataLen, (const uint8_t *)pntxt, ptextLen, (uint8_t *)crtxt));
     }
     if ((rc = enter(&c, &L)) != 0) return rc;
     do {
@@ -462,7 +460,7 @@ int uaes_ccm_encrypt_ex(int keybits, const uint8_t *key, const uint8_t *nonce, s
         if ((rc = plan_io(L, pntxt, ptextLen, crtxt, ptextLen + tagLen, &io)) != 0) break;
         int k = uaesk_ccm(L->stream, &c->tb, ks.nr, &ks.ek, 0, nonce, nonceLen, tagLen, d_aad, aDataLen,
                           io.din, ptextLen, io.dout, NULL);
-        if (k) { rc = fail(UAES_E_HIP, "ccm launch: %s", hipGetErrorString((hipError_t)k)); break; }
+        if ((rc = launched("ccm", k)) != 0) break;
         rc = finish_io(&io, ptextLen + tagLen);
     } while (0);
     DONE(L, rc);
@@ -481,7 +479,7 @@ int uaes_ccm_decrypt_ex(int keybits, const uint8_t *key, const uint8_t *nonce, s
 {
     context *c;
     lane *L;
-    keysched ks;
+    KEYSCHED(ks);
     io_plan io;
     const void *d_aad;
     int rc, status = -1;
@@ -493,7 +491,7 @@ int uaes_ccm_decrypt_ex(int keybits, const uint8_t *key, const uint8_t *nonce, s
         const uaesh_key hk = host_key(&ks);
         rc = uaesh_ccm(&hk, 1, nonce, nonceLen, tagLen, (const uint8_t *)aData, aDataLen, (const uint8_t *)crtxt, crtxtLen, (uint8_t *)pntxt);
         if (rc && wipe_on_auth_failure()) memset(pntxt, 0, crtxtLen);       /* (the default leaves the text, as the reference does) */
-        HOST_RET(ks, rc);
+        return host_result(rc);
     }
     if ((rc = enter(&c, &L)) != 0) return rc;
     do {
@@ -501,7 +499,7 @@ int uaes_ccm_decrypt_ex(int keybits, const uint8_t *key, const uint8_t *nonce, s
         if ((rc = plan_io(L, crtxt, crtxtLen + tagLen, pntxt, crtxtLen, &io)) != 0) break;
         int k = uaesk_ccm(L->stream, &c->tb, ks.nr, &ks.ek, 1, nonce, nonceLen, tagLen, d_aad, aDataLen,
                           io.din, crtxtLen, io.dout, L->d_status);
-        if (k) { rc = fail(UAES_E_HIP, "ccm launch: %s", hipGetErrorString((hipError_t)k)); break; }
+        if ((rc = launched("ccm", k)) != 0) break;
         if ((rc = lane_fetch(L, &status, L->d_status, sizeof status)) != 0) break;
         io.drained = 1;                              /* (a second wait costs another ticket kernel) */
         /* the reference decrypts before it authenticates and (SABOTAGE being a
@@ -526,22 +524,16 @@ int uaes_ccm_decrypt(int keybits, const uint8_t *key, const uint8_t *nonce,
  * independent chains in one launch, reads the counter block (and the verdict) back in one fetch and hands it to the
  * positioned CTR kernels.  Side arrays (nonce, AAD) in host memory travel through the lane's scratch.             */
 
-#define ES_KCHK(what, call)                                                                           \
-    do {                                                                                              \
-        const int k_ = (call);                                                                        \
-        if (k_) { rc = fail(UAES_E_HIP, what " launch: %s", hipGetErrorString((hipError_t)k_)); goto out; } \
-    } while (0)
-
 static int eax_common(int keybits, const uint8_t *key, int decrypt, const uint8_t *nonce, size_t nonceLen, size_t tagLen,
                       const void *aData, size_t aDataLen, const void *in, size_t len, void *outp)
 {
     context *c;
     lane *L;
-    keysched ks;
+    KEYSCHED(ks);
     io_plan io;
     const void *d_nonce, *d_aad;
     size_t off = 0;
-    int rc, status = 0;
+    int rc, k, status = 0;
     uint8_t res[32];
     if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
     if (!in || (len && !outp) || (nonceLen && !nonce)) return fail(UAES_E_ARG, "NULL pointer");
@@ -550,10 +542,10 @@ static int eax_common(int keybits, const uint8_t *key, int decrypt, const uint8_
     if (aDataLen && !aData) return fail(UAES_E_ARG, "NULL aData with aDataLen != 0");
     if (host_take(in, outp, len, 1) && !is_device_ptr(aData) && !is_device_ptr(nonce)) {
         const uaesh_key hk = host_key(&ks);
-        HOST_RET(ks, uaesh_eax(&hk, decrypt, nonce, nonceLen, tagLen, (const uint8_t *)aData, aDataLen,
-                               (const uint8_t *)in, len, (uint8_t *)outp));
+        return host_result(uaesh_eax(&hk, decrypt, nonce, nonceLen, tagLen, (const uint8_t *)aData, aDataLen,
+                                     (const uint8_t *)in, len, (uint8_t *)outp));
     }
-    if ((rc = enter(&c, &L)) != 0) { burn(&ks, sizeof ks); return rc; }
+    if ((rc = enter(&c, &L)) != 0) return rc;
     if ((rc = lane_scratch(L, SIDE(nonceLen) + SIDE(aDataLen), SCRATCH_OTHER)) != 0) goto out;
     if ((rc = side_in(L, &off, nonce, nonceLen, &d_nonce)) != 0) goto out;
     if ((rc = side_in(L, &off, aData, aDataLen, &d_aad)) != 0) goto out;
@@ -564,26 +556,30 @@ static int eax_common(int keybits, const uint8_t *key, int decrypt, const uint8_
         unsigned char *tag = decrypt ? (unsigned char *)io.din + len : (unsigned char *)io.dout + len;
         const unsigned tl = (unsigned)tagLen;
         if (len <= UAES_EAX_SIV_SMALL_MAX) {             /* eax.small: one launch */
-            ES_KCHK("eax", uaesk_eax_small(L->stream, &c->tb, ks.nr, &ks.ek, decrypt, d_nonce, nonceLen, d_aad, aDataLen,
-                                           io.din, len, io.dout, tag, tl, decrypt ? L->d_status : NULL));
+            k = uaesk_eax_small(L->stream, &c->tb, ks.nr, &ks.ek, decrypt, d_nonce, nonceLen, d_aad, aDataLen,
+                                io.din, len, io.dout, tag, tl, decrypt ? L->d_status : NULL);
+            if ((rc = launched("eax", k)) != 0) goto out;
             if (decrypt) {
                 if ((rc = lane_fetch(L, &status, L->d_status, sizeof status)) != 0) goto out;
                 io.drained = 1;
             }
         } else {                                          /* eax.long: the chains, one fetch, then CTR */
             uaesk_ctr ctr;
-            ES_KCHK("eax", uaesk_eax_macs(L->stream, &c->tb, ks.nr, &ks.ek, decrypt ? 1 : 0, d_nonce, nonceLen,
-                                          d_aad, aDataLen, decrypt ? io.din : NULL, decrypt ? len : 0, tag, tl, L->d_status));
+            k = uaesk_eax_macs(L->stream, &c->tb, ks.nr, &ks.ek, decrypt ? 1 : 0, d_nonce, nonceLen,
+                               d_aad, aDataLen, decrypt ? io.din : NULL, decrypt ? len : 0, tag, tl, L->d_status);
+            if ((rc = launched("eax", k)) != 0) goto out;
             if ((rc = lane_fetch(L, res, L->d_status, sizeof res)) != 0) goto out;
             memcpy(&status, res, sizeof status);
             if (decrypt && status) {
                 io.drained = 1;
             } else {
                 make_ctr(&ctr, res + 16, 0);
-                ES_KCHK("eax ctr", uaesk_ctr_xcrypt(L->stream, &c->tb, ks.nr, &ks.ek, &ctr, io.din, io.dout, len, NULL));
-                if (!decrypt)
-                    ES_KCHK("eax", uaesk_eax_macs(L->stream, &c->tb, ks.nr, &ks.ek, 2, NULL, 0, NULL, 0, io.dout, len,
-                                                  tag, tl, L->d_status));
+                k = uaesk_ctr_xcrypt(L->stream, &c->tb, ks.nr, &ks.ek, &ctr, io.din, io.dout, len, NULL);
+                if ((rc = launched("eax ctr", k)) != 0) goto out;
+                if (!decrypt) {
+                    k = uaesk_eax_macs(L->stream, &c->tb, ks.nr, &ks.ek, 2, NULL, 0, NULL, 0, io.dout, len, tag, tl, L->d_status);
+                    if ((rc = launched("eax", k)) != 0) goto out;
+                }
             }
         }
     }
@@ -591,7 +587,6 @@ static int eax_common(int keybits, const uint8_t *key, int decrypt, const uint8_
     if (decrypt && status) rc = UAES_E_AUTHENTICATION;
     else rc = finish_io(&io, decrypt ? len : len + tagLen);
 out:
-    burn(&ks, sizeof ks);
     memset(res, 0, sizeof res);
     DONE(L, rc);
 }
@@ -622,11 +617,12 @@ static int siv_common(int keybits, const uint8_t *keys, int decrypt, uint8_t *iv
 {
     context *c;
     lane *L;
-    keysched k1, k2;
+    KEYSCHED(k1);
+    KEYSCHED(k2);
     io_plan io;
     const void *d_aad;
     size_t off = 0;
-    int rc, status = 0;
+    int rc, k, status = 0;
     uint8_t v[16], res[32];
     if ((rc = siv_keys(&k1, &k2, keys, keybits)) != 0) return rc;
     if (!iv || (len && (!in || !outp))) return fail(UAES_E_ARG, "NULL pointer");
@@ -635,31 +631,31 @@ static int siv_common(int keybits, const uint8_t *keys, int decrypt, uint8_t *iv
     if (host_take(in, outp, len, 1) && !is_device_ptr(aData) && !is_device_ptr(iv)) {
         const uaesh_key h1 = host_key(&k1), h2 = host_key(&k2);
         rc = uaesh_siv(&h1, &h2, decrypt, v, (const uint8_t *)aData, aDataLen, (const uint8_t *)in, len, (uint8_t *)outp);
-        burn(&k1, sizeof k1);
-        burn(&k2, sizeof k2);
         if (!decrypt) memcpy(iv, v, 16);
         if (rc && len && wipe_on_auth_failure()) memset(outp, 0, len);       /* (the default leaves the text, as the reference does) */
         return host_result(rc);
     }
-    if ((rc = enter(&c, &L)) != 0) { burn(&k1, sizeof k1); burn(&k2, sizeof k2); return rc; }
+    if ((rc = enter(&c, &L)) != 0) return rc;
     if ((rc = lane_scratch(L, SIDE(aDataLen), SCRATCH_OTHER)) != 0) goto out;
     if ((rc = side_in(L, &off, aData, aDataLen, &d_aad)) != 0) goto out;
     if ((rc = plan_io(L, len ? in : NULL, len, len ? outp : NULL, len, &io)) != 0) goto out;
     if (len <= UAES_EAX_SIV_SMALL_MAX) {                  /* s2v.small: one launch */
-        ES_KCHK("siv", uaesk_s2v_small(L->stream, &c->tb, k1.nr, &k1.ek, &k2.ek, decrypt, decrypt ? v : NULL, d_aad,
-                                       aDataLen, io.din, len, io.dout, (char *)L->d_status + 16,
-                                       decrypt ? L->d_status : NULL));
+        k = uaesk_s2v_small(L->stream, &c->tb, k1.nr, &k1.ek, &k2.ek, decrypt, decrypt ? v : NULL, d_aad, aDataLen,
+                            io.din, len, io.dout, (char *)L->d_status + 16, decrypt ? L->d_status : NULL);
+        if ((rc = launched("siv", k)) != 0) goto out;
         if ((rc = lane_fetch(L, res, L->d_status, sizeof res)) != 0) goto out;
         io.drained = 1;
     } else if (!decrypt) {                                /* s2v.long: the chains, one fetch, then CTR(V') */
         uaesk_ctr ctr;
-        ES_KCHK("siv", uaesk_s2v_macs(L->stream, &c->tb, k1.nr, &k1.ek, 0, NULL, d_aad, aDataLen, io.din, len, L->d_status));
+        k = uaesk_s2v_macs(L->stream, &c->tb, k1.nr, &k1.ek, 0, NULL, d_aad, aDataLen, io.din, len, L->d_status);
+        if ((rc = launched("siv", k)) != 0) goto out;
         if ((rc = lane_fetch(L, res, L->d_status, sizeof res)) != 0) goto out;
         memcpy(v, res + 16, 16);
         v[8] &= 0x7F;
         v[12] &= 0x7F;
         make_ctr(&ctr, v, 0);
-        ES_KCHK("siv ctr", uaesk_ctr_xcrypt(L->stream, &c->tb, k2.nr, &k2.ek, &ctr, io.din, io.dout, len, NULL));
+        k = uaesk_ctr_xcrypt(L->stream, &c->tb, k2.nr, &k2.ek, &ctr, io.din, io.dout, len, NULL);
+        if ((rc = launched("siv ctr", k)) != 0) goto out;
     } else {                                              /* decrypt: CTR(iv') first, S2V over what it wrote, one fetch */
         uaesk_ctr ctr;
         uint8_t cv[16];
@@ -667,8 +663,10 @@ static int siv_common(int keybits, const uint8_t *keys, int decrypt, uint8_t *iv
         cv[8] &= 0x7F;
         cv[12] &= 0x7F;
         make_ctr(&ctr, cv, 0);
-        ES_KCHK("siv ctr", uaesk_ctr_xcrypt(L->stream, &c->tb, k2.nr, &k2.ek, &ctr, io.din, io.dout, len, NULL));
-        ES_KCHK("siv", uaesk_s2v_macs(L->stream, &c->tb, k1.nr, &k1.ek, 1, v, d_aad, aDataLen, io.dout, len, L->d_status));
+        k = uaesk_ctr_xcrypt(L->stream, &c->tb, k2.nr, &k2.ek, &ctr, io.din, io.dout, len, NULL);
+        if ((rc = launched("siv ctr", k)) != 0) goto out;
+        k = uaesk_s2v_macs(L->stream, &c->tb, k1.nr, &k1.ek, 1, v, d_aad, aDataLen, io.dout, len, L->d_status);
+        if ((rc = launched("siv", k)) != 0) goto out;
         if ((rc = lane_fetch(L, res, L->d_status, sizeof res)) != 0) goto out;
         io.drained = 1;
     }
@@ -681,8 +679,6 @@ static int siv_common(int keybits, const uint8_t *keys, int decrypt, uint8_t *iv
         if ((rc = finish_io(&io, len)) == 0) rc = iv_write(iv, v);
     }
 out:
-    burn(&k1, sizeof k1);
-    burn(&k2, sizeof k2);
     DONE(L, rc);
 }
 
@@ -718,10 +714,10 @@ struct aead_rows {
     void          *out;
     struct { const void *p; size_t each; } side[AB_NSIDE];   /* the caller's arrays and their bytes per record; 0: the
                                                               * call has no such array */
-    int          (*launch)(const aead_rows *b, context *c, lane *L, const keysched *ks, const row_array *a, const row_text *t);
+    int          (*launch)(const aead_rows *b, context *c, lane *L, const keysched *const ks[2], const row_array *a, const row_text *t);
 };
 
-static int aead_rows_staged(const aead_rows *b, const keysched *ks)
+static int aead_rows_staged(const aead_rows *b, const keysched *const ks[2])
 {
     context *c;
     lane *L;
@@ -735,10 +731,8 @@ static int aead_rows_staged(const aead_rows *b, const keysched *ks)
         a[i] = (row_array){ b->side[i].p, b->nmsg * b->side[i].each, i == AB_VERDICTS || (i == AB_TAGS && !b->decrypt), NULL };
     }
     if ((rc = enter(&c, &L)) != 0) return rc;
-    if ((rc = row_stage(L, a, AB_NSIDE, b->decrypt)) == 0 && (rc = row_texts(L, &t)) == 0) {
-        const int e = b->launch(b, c, L, ks, a, &t);
-        if (e != 0) rc = fail(UAES_E_HIP, "%s launch: %s", b->name, hipGetErrorString((hipError_t)e));
-    }
+    if ((rc = row_stage(L, a, AB_NSIDE, b->decrypt)) == 0 && (rc = row_texts(L, &t)) == 0)
+        rc = launched(b->name, b->launch(b, c, L, ks, a, &t));
     if (b->side[AB_KEYS].each) {
         /* keys in host memory went through the scratch: that copy is cleared in stream order before the call returns,
          * however far it got (a failure to clear is reported if nothing failed before), and an error waits for it */
@@ -753,31 +747,32 @@ static int aead_rows_staged(const aead_rows *b, const keysched *ks)
 
 static int aead_rows_run(const aead_rows *b)
 {
-    keysched ks[2];
+    KEYSCHED(k1);
+    KEYSCHED(k2);
+    const keysched *const ks[2] = { &k1, &k2 };
     size_t widest = b->msg_bytes;
     int i, rc;
     for (i = 0; i < AB_NSIDE; ++i)
         if (b->side[i].each > widest) widest = b->side[i].each;
     if (widest && b->nmsg > (size_t)-1 / 8 / widest)     /* / 8: the side arrays and their padding still add up */
         return fail(UAES_E_ARG, "batch size overflows");
-    rc = b->nkeys == 2 ? siv_keys(&ks[0], &ks[1], b->key, b->keybits) : b->nkeys ? expand_key(&ks[0], b->key, b->keybits) : 0;
+    rc = b->nkeys == 2 ? siv_keys(&k1, &k2, b->key, b->keybits) : b->nkeys ? expand_key(&k1, b->key, b->keybits) : 0;
     if (rc == 0 && b->nmsg) rc = aead_rows_staged(b, ks);
-    burn(ks, (size_t)b->nkeys * sizeof ks[0]);
     return rc;
 }
 
 /* EAX and SIV batches (k_eax_batch, k_s2v_batch: uaes_eax_siv.hip): 16-byte tags; SIV has no nonces, and its IVs are
  * its tags.  An EAX decryption writes only authentic records, so its output starts as the caller's buffer. */
-static int eax_batch_launch(const aead_rows *b, context *c, lane *L, const keysched *ks, const row_array *a, const row_text *t)
+static int eax_batch_launch(const aead_rows *b, context *c, lane *L, const keysched *const ks[2], const row_array *a, const row_text *t)
 {
-    return uaesk_eax_batch(L->stream, &c->tb, ks->nr, &ks->ek, b->decrypt, a[AB_NONCES].d, b->side[AB_NONCES].each, a[AB_AAD].d,
+    return uaesk_eax_batch(L->stream, &c->tb, ks[0]->nr, &ks[0]->ek, b->decrypt, a[AB_NONCES].d, b->side[AB_NONCES].each, a[AB_AAD].d,
                            b->side[AB_AAD].each, b->nmsg, b->msg_bytes, t->d_in, t->d_out, a[AB_TAGS].d, a[AB_VERDICTS].d,
                            L->d_status);
 }
 
-static int siv_batch_launch(const aead_rows *b, context *c, lane *L, const keysched *ks, const row_array *a, const row_text *t)
+static int siv_batch_launch(const aead_rows *b, context *c, lane *L, const keysched *const ks[2], const row_array *a, const row_text *t)
 {
-    return uaesk_s2v_batch(L->stream, &c->tb, ks[0].nr, &ks[0].ek, &ks[1].ek, b->decrypt, wipe_on_auth_failure(), a[AB_AAD].d,
+    return uaesk_s2v_batch(L->stream, &c->tb, ks[0]->nr, &ks[0]->ek, &ks[1]->ek, b->decrypt, wipe_on_auth_failure(), a[AB_AAD].d,
                            b->side[AB_AAD].each, b->nmsg, b->msg_bytes, t->d_in, t->d_out, a[AB_TAGS].d, a[AB_VERDICTS].d,
                            L->d_status);
 }
@@ -827,9 +822,9 @@ int uaes_siv_decrypt_batch(int keybits, const uint8_t *keys, size_t nmsg, size_t
 /* CCM batches (k_ccm_batch, uaes_mac.hip): the nonce and tag lengths are arguments, the tags are packed, tagLen bytes
  * each, and `lens` may give every record a length of its own.  Like the reference's CCM a decryption writes the text
  * before it knows the tag, so the output need not start as the caller's buffer. */
-static int ccm_batch_launch(const aead_rows *b, context *c, lane *L, const keysched *ks, const row_array *a, const row_text *t)
+static int ccm_batch_launch(const aead_rows *b, context *c, lane *L, const keysched *const ks[2], const row_array *a, const row_text *t)
 {
-    return uaesk_ccm_batch(L->stream, &c->tb, ks->nr, &ks->ek, b->decrypt, wipe_on_auth_failure(), a[AB_NONCES].d,
+    return uaesk_ccm_batch(L->stream, &c->tb, ks[0]->nr, &ks[0]->ek, b->decrypt, wipe_on_auth_failure(), a[AB_NONCES].d,
                            b->side[AB_NONCES].each, b->side[AB_TAGS].each, a[AB_AAD].d, b->side[AB_AAD].each, b->nmsg,
                            b->msg_bytes, a[AB_LENS].d, t->d_in, t->d_out, a[AB_TAGS].d, a[AB_VERDICTS].d, L->d_status);
 }
@@ -871,9 +866,9 @@ int uaes_ccm_decrypt_batch(int keybits, const uint8_t *key, size_t nonceLen, siz
 /* GCM-SIV batches (k_gcmsiv_batch, uaes_gcmsiv_batch.hip): as ccm_batch with 12-byte nonces and 16-byte tags.  `key` is
  * the MASTER key: only its schedule is made here, every record derives and expands its own keys in the kernel.  Like
  * the reference's GCM-SIV a decryption writes the text before it knows the tag. */
-static int gcmsiv_batch_launch(const aead_rows *b, context *c, lane *L, const keysched *ks, const row_array *a, const row_text *t)
+static int gcmsiv_batch_launch(const aead_rows *b, context *c, lane *L, const keysched *const ks[2], const row_array *a, const row_text *t)
 {
-    return uaesk_gcmsiv_batch(L->stream, &c->tb, ks->nr, &ks->ek, b->decrypt, wipe_on_auth_failure(), a[AB_NONCES].d, a[AB_AAD].d,
+    return uaesk_gcmsiv_batch(L->stream, &c->tb, ks[0]->nr, &ks[0]->ek, b->decrypt, wipe_on_auth_failure(), a[AB_NONCES].d, a[AB_AAD].d,
                               b->side[AB_AAD].each, b->nmsg, b->msg_bytes, a[AB_LENS].d, t->d_in, t->d_out, a[AB_TAGS].d,
                               a[AB_VERDICTS].d, L->d_status);
 }
@@ -915,7 +910,7 @@ int uaes_gcmsiv_decrypt_batch(int keybits, const uint8_t *key, size_t nmsg, size
  * scratch, and how that copy is cleared: aead_rows_staged.)  Decrypt keeps N7 per record: the kernel writes an
  * authentic record only, so the output's staging starts as the caller's buffer, and uaes_set_wipe_on_auth_failure does
  * not apply. */
-static int gcm_multikey_batch_launch(const aead_rows *b, context *c, lane *L, const keysched *ks, const row_array *a,
+static int gcm_multikey_batch_launch(const aead_rows *b, context *c, lane *L, const keysched *const ks[2], const row_array *a,
                                      const row_text *t)
 {
     (void)ks;
@@ -967,7 +962,7 @@ static int feedback_common(int keybits, const uint8_t *key, const uint8_t *iVec,
 {
     context *c;
     lane *L;
-    keysched ks;
+    KEYSCHED(ks);
     io_plan io;
     int rc;
     size_t out_len = len;
@@ -987,13 +982,13 @@ static int feedback_common(int keybits, const uint8_t *key, const uint8_t *iVec,
         const uint8_t *x = (const uint8_t *)in;
         uint8_t *y = (uint8_t *)out;
         switch (mode) {
-        case 0: HOST_RET(ks, uaesh_cbc_encrypt(&hk, iVec, 1, 0, x, len, y));
-        case 1: HOST_RET(ks, uaesh_cbc_decrypt(&hk, iVec, 1, x, len, y));
-        case 2: uaesh_cfb(&hk, iVec, 1, x, len, y); HOST_RET(ks, 0);
-        case 3: uaesh_cfb(&hk, iVec, 0, x, len, y); HOST_RET(ks, 0);
-        case 4: uaesh_ofb(&hk, iVec, x, len, y); HOST_RET(ks, 0);
-        case 8: HOST_RET(ks, uaesh_cbc_decrypt(&hk, iVec, 0, x, len, y));
-        default: HOST_RET(ks, uaesh_cbc_encrypt(&hk, iVec, 0, mode - 5, x, len, y));
+        case 0: return host_result(uaesh_cbc_encrypt(&hk, iVec, 1, 0, x, len, y));
+        case 1: return host_result(uaesh_cbc_decrypt(&hk, iVec, 1, x, len, y));
+        case 2: uaesh_cfb(&hk, iVec, 1, x, len, y); return host_result(0);
+        case 3: uaesh_cfb(&hk, iVec, 0, x, len, y); return host_result(0);
+        case 4: uaesh_ofb(&hk, iVec, x, len, y); return host_result(0);
+        case 8: return host_result(uaesh_cbc_decrypt(&hk, iVec, 0, x, len, y));
+        default: return host_result(uaesh_cbc_encrypt(&hk, iVec, 0, mode - 5, x, len, y));
         }
     }
     if ((rc = enter(&c, &L)) != 0) return rc;
@@ -1009,7 +1004,7 @@ static int feedback_common(int keybits, const uint8_t *key, const uint8_t *iVec,
             io.din = L->stage[1];
         }
         int k = uaesk_feedback(L->stream, &c->tb, ks.nr, &ks.ek, &ks.dk, mode, iVec, io.din, len, io.dout);
-        if (k) { rc = fail(UAES_E_HIP, "feedback-mode launch: %s", hipGetErrorString((hipError_t)k)); break; }
+        if ((rc = launched("feedback-mode", k)) != 0) break;
         rc = finish_io(&io, out_len);
     } while (0);
     DONE(L, rc);
@@ -1070,20 +1065,18 @@ static int batch_common(int keybits, const uint8_t *key, int mac, const uint8_t 
 {
     context *c;
     lane *L;
-    keysched ks;
+    KEYSCHED(ks);
     io_plan io;
     const void *d_ivs = NULL;
     int rc;
     const size_t total = nmsg * msg_bytes, out_len = mac ? nmsg * 16 : total;
     if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
-    if (!mac && (msg_bytes < 16 || msg_bytes % 16)) {
-        burn(&ks, sizeof ks);
+    if (!mac && (msg_bytes < 16 || msg_bytes % 16))
         return fail(UAES_E_ARG, "batched CBC: every message must be a whole number of blocks (got %zu bytes)", msg_bytes);
-    }
-    if (msg_bytes && nmsg > (size_t)-1 / msg_bytes) { burn(&ks, sizeof ks); return fail(UAES_E_ARG, "batch size overflows"); }
-    if (nmsg == 0) { burn(&ks, sizeof ks); return 0; }
-    if ((total && !in) || !out || (!mac && !ivs)) { burn(&ks, sizeof ks); return fail(UAES_E_ARG, "NULL pointer"); }
-    if ((rc = enter(&c, &L)) != 0) { burn(&ks, sizeof ks); return rc; }
+    if (msg_bytes && nmsg > (size_t)-1 / msg_bytes) return fail(UAES_E_ARG, "batch size overflows");
+    if (nmsg == 0) return 0;
+    if ((total && !in) || !out || (!mac && !ivs)) return fail(UAES_E_ARG, "NULL pointer");
+    if ((rc = enter(&c, &L)) != 0) return rc;
     do {
         if (!mac && (rc = stage_aad(L, ivs, nmsg * 16, &d_ivs)) != 0) break;     /* host IVs -> device */
         if (!mac && (((uintptr_t)d_ivs) & 15u)) { rc = fail(UAES_E_ARG, "device IV array must be 16-byte aligned"); break; }
@@ -1093,10 +1086,9 @@ static int batch_common(int keybits, const uint8_t *key, int mac, const uint8_t 
             io.dout = L->stage[1];
         }
         int k = uaesk_chain_batch(L->stream, &c->tb, ks.nr, &ks.ek, mac, d_ivs, nmsg, msg_bytes, io.din, io.dout);
-        if (k) { rc = fail(UAES_E_HIP, "batch launch: %s", hipGetErrorString((hipError_t)k)); break; }
+        if ((rc = launched("batch", k)) != 0) break;
         rc = finish_io(&io, out_len);
     } while (0);
-    burn(&ks, sizeof ks);
     DONE(L, rc);
 }
 
@@ -1130,8 +1122,8 @@ static int cipher_rows(int mode, int keybits, const uint8_t *key, const uint8_t 
     const size_t total = nmsg * msg_bytes;
     context *c;
     lane *L;
-    keysched ks;
-    int rc, bad;
+    KEYSCHED(ks);
+    int rc, k, bad;
     if (cbc && (msg_bytes < 16 || msg_bytes % 16))
         return fail(UAES_E_ARG, "batched CBC: every message must be a whole number of blocks (got %zu bytes)", msg_bytes);
     if (!cbc && msg_bytes > UINT32_MAX)
@@ -1139,10 +1131,10 @@ static int cipher_rows(int mode, int keybits, const uint8_t *key, const uint8_t 
     if (nmsg > (size_t)-1 / 2 / (msg_bytes > 16 ? msg_bytes : 16))     /* / 2: the IVs, the lengths and their padding */
         return fail(UAES_E_ARG, "batch size overflows");
     if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
-    if (total == 0) { burn(&ks, sizeof ks); return 0; }                /* no records, or records of no bytes */
-    if (!ivs || !in || !outp) { burn(&ks, sizeof ks); return fail(UAES_E_ARG, "NULL pointer"); }
+    if (total == 0) return 0;                                     /* no records, or records of no bytes */
+    if (!ivs || !in || !outp) return fail(UAES_E_ARG, "NULL pointer");
     if (cbc) lens = NULL;
-    if ((rc = enter(&c, &L)) != 0) { burn(&ks, sizeof ks); return rc; }
+    if ((rc = enter(&c, &L)) != 0) return rc;
     row_array a[2] = { { ivs, nmsg * 16, 0, NULL }, { lens, lens ? nmsg * sizeof *lens : 0, 0, NULL } };
     row_text t = { in, outp, total, total, lens != NULL, NULL, NULL };
     if (lens && is_device_ptr(lens) && ((uintptr_t)lens & 3u)) {
@@ -1151,11 +1143,10 @@ static int cipher_rows(int mode, int keybits, const uint8_t *key, const uint8_t 
     }
     if ((rc = row_stage(L, a, 2, 0)) != 0) goto out;
     if ((rc = row_texts(L, &t)) != 0) goto out;
-    ES_KCHK("cipher batch", uaesk_cipher_batch(L->stream, &c->tb, ks.nr, &ks.ek, &ks.dk, mode, a[0].d, nmsg, msg_bytes, a[1].d,
-                                               t.d_in, t.d_out));
+    k = uaesk_cipher_batch(L->stream, &c->tb, ks.nr, &ks.ek, &ks.dk, mode, a[0].d, nmsg, msg_bytes, a[1].d, t.d_in, t.d_out);
+    if ((rc = launched("cipher batch", k)) != 0) goto out;
     rc = row_finish(L, &t, a, 2, 0, &bad);
 out:
-    burn(&ks, sizeof ks);
     DONE(L, rc);
 }
 
@@ -1232,25 +1223,24 @@ int uaes_kw_wrap(int keybits, const uint8_t *kek, const void *secret, size_t sec
 {
     context *c;
     lane *L;
-    keysched ks;
+    KEYSCHED(ks);
     io_plan io;
     int rc;
     if ((rc = expand_key(&ks, kek, keybits)) != 0) return rc;
-    if (secretLen % 8 || secretLen / 8 < 2) { burn(&ks, sizeof ks); return UAES_E_DATALENGTH; }     /* (:1837) */
-    if (!secret || !wrapped) { burn(&ks, sizeof ks); return fail(UAES_E_ARG, "NULL pointer"); }
-    if (secretLen > (size_t)-1 - 8) { burn(&ks, sizeof ks); return fail(UAES_E_ARG, "length overflows"); }
+    if (secretLen % 8 || secretLen / 8 < 2) return UAES_E_DATALENGTH;     /* (:1837) */
+    if (!secret || !wrapped) return fail(UAES_E_ARG, "NULL pointer");
+    if (secretLen > (size_t)-1 - 8) return fail(UAES_E_ARG, "length overflows");
     if (host_take(secret, wrapped, secretLen, 1)) {
         const uaesh_key hk = host_key(&ks);
-        HOST_RET(ks, uaesh_kw_wrap(&hk, (const uint8_t *)secret, secretLen, (uint8_t *)wrapped));
+        return host_result(uaesh_kw_wrap(&hk, (const uint8_t *)secret, secretLen, (uint8_t *)wrapped));
     }
-    if ((rc = enter(&c, &L)) != 0) { burn(&ks, sizeof ks); return rc; }
+    if ((rc = enter(&c, &L)) != 0) return rc;
     do {
         if ((rc = kw_io(L, secret, secretLen, wrapped, secretLen + 8, secretLen, &io)) != 0) break;
         int k = uaesk_kw(L->stream, &c->tb, ks.nr, &ks.ek, &ks.dk, 0, io.din, secretLen, io.dout, NULL);
-        if (k) { rc = fail(UAES_E_HIP, "key wrap launch: %s", hipGetErrorString((hipError_t)k)); break; }
+        if ((rc = launched("key wrap", k)) != 0) break;
         rc = finish_io(&io, secretLen + 8);
     } while (0);
-    burn(&ks, sizeof ks);
     DONE(L, rc);
 }
 
@@ -1258,32 +1248,30 @@ int uaes_kw_unwrap(int keybits, const uint8_t *kek, const void *wrapped, size_t 
 {
     context *c;
     lane *L;
-    keysched ks;
+    KEYSCHED(ks);
     io_plan io;
     int rc, status = 0;
     size_t len;
     if ((rc = expand_key(&ks, kek, keybits)) != 0) return rc;
-    if (wrapLen % 8 || wrapLen / 8 < 3) { burn(&ks, sizeof ks); return UAES_E_DATALENGTH; }        /* (:1873) */
+    if (wrapLen % 8 || wrapLen / 8 < 3) return UAES_E_DATALENGTH;        /* (:1873) */
     len = wrapLen - 8;
-    if (!secret || !wrapped) { burn(&ks, sizeof ks); return fail(UAES_E_ARG, "NULL pointer"); }
+    if (!secret || !wrapped) return fail(UAES_E_ARG, "NULL pointer");
     if (host_take(wrapped, secret, wrapLen, 1)) {
         const uaesh_key hk = host_key(&ks);
         rc = uaesh_kw_unwrap(&hk, (const uint8_t *)wrapped, wrapLen, (uint8_t *)secret);
-        burn(&ks, sizeof ks);
         if (rc == UAES_E_AUTHENTICATION && wipe_on_auth_failure()) memset(secret, 0, len);   /* (the default leaves it, as the reference does) */
         return host_result(rc);
     }
-    if ((rc = enter(&c, &L)) != 0) { burn(&ks, sizeof ks); return rc; }
+    if ((rc = enter(&c, &L)) != 0) return rc;
     do {
         if ((rc = kw_io(L, wrapped, wrapLen, secret, len, len, &io)) != 0) break;
         int k = uaesk_kw(L->stream, &c->tb, ks.nr, &ks.ek, &ks.dk, 1, io.din, len, io.dout, L->d_status);
-        if (k) { rc = fail(UAES_E_HIP, "key unwrap launch: %s", hipGetErrorString((hipError_t)k)); break; }
+        if ((rc = launched("key unwrap", k)) != 0) break;
         if ((rc = lane_fetch(L, &status, L->d_status, sizeof status)) != 0) break;
         io.drained = 1;
         /* like the reference: the secret is written before A is checked; SABOTAGE = uaes_set_wipe_on_auth_failure */
         if ((rc = status ? finish_io_unauthenticated(&io, len) : finish_io(&io, len)) == 0 && status) rc = UAES_E_AUTHENTICATION;
     } while (0);
-    burn(&ks, sizeof ks);
     DONE(L, rc);
 }
 
@@ -1294,29 +1282,27 @@ static int kw_batch(int unwrap, int keybits, const uint8_t *kek, size_t nkeys, s
 {
     context *c;
     lane *L;
-    keysched ks;
-    int rc, bad;
+    KEYSCHED(ks);
+    int rc, k, bad;
     const size_t in_rec = unwrap ? secret_bytes + 8 : secret_bytes, out_rec = unwrap ? secret_bytes : secret_bytes + 8;
     if ((rc = expand_key(&ks, kek, keybits)) != 0) return rc;
-    if (secret_bytes > UAES_KW_BATCH_MAX) {
-        burn(&ks, sizeof ks);
+    if (secret_bytes > UAES_KW_BATCH_MAX)
         return fail(UAES_E_ARG, "batched key wrap: a record holds at most %zu bytes of secret (got %zu)",
                     (size_t)UAES_KW_BATCH_MAX, secret_bytes);
-    }
-    if (nkeys > (size_t)-1 / (secret_bytes + 8)) { burn(&ks, sizeof ks); return fail(UAES_E_ARG, "batch size overflows"); }
-    if (nkeys == 0) { burn(&ks, sizeof ks); return 0; }
-    if (!in || !outp || (unwrap && !verdicts)) { burn(&ks, sizeof ks); return fail(UAES_E_ARG, "NULL pointer"); }
-    if ((rc = enter(&c, &L)) != 0) { burn(&ks, sizeof ks); return rc; }
+    if (nkeys > (size_t)-1 / (secret_bytes + 8)) return fail(UAES_E_ARG, "batch size overflows");
+    if (nkeys == 0) return 0;
+    if (!in || !outp || (unwrap && !verdicts)) return fail(UAES_E_ARG, "NULL pointer");
+    if ((rc = enter(&c, &L)) != 0) return rc;
     row_array a[1] = { { verdicts, unwrap ? nkeys : 0, 1, NULL } };
     row_text t = { in, outp, nkeys * in_rec, nkeys * out_rec, 0, NULL, NULL };
     if ((rc = row_stage(L, a, 1, unwrap)) != 0) goto out;
     if ((rc = row_texts(L, &t)) != 0) goto out;
-    ES_KCHK("key wrap batch", uaesk_kw_batch(L->stream, &c->tb, ks.nr, &ks.ek, &ks.dk, unwrap, wipe_on_auth_failure(), nkeys,
-                                             secret_bytes, t.d_in, t.d_out, a[0].d, L->d_status));
+    k = uaesk_kw_batch(L->stream, &c->tb, ks.nr, &ks.ek, &ks.dk, unwrap, wipe_on_auth_failure(), nkeys, secret_bytes,
+                       t.d_in, t.d_out, a[0].d, L->d_status);
+    if ((rc = launched("key wrap batch", k)) != 0) goto out;
     if ((rc = row_finish(L, &t, a, 1, unwrap, &bad)) != 0) goto out;
     rc = bad ? UAES_E_AUTHENTICATION : 0;
 out:
-    burn(&ks, sizeof ks);
     DONE(L, rc);
 }
 
@@ -1390,15 +1376,15 @@ static int ff1_gpu(const keysched *ks, int decrypt, const uaesk_ff1 *q, const ui
     lane *L;
     const void *d_tweaks = NULL;
     const size_t n = nrec ? nrec : 1, total = n * q->len;
-    int rc, bad;
+    int rc, k, bad;
     if ((rc = enter(&c, &L)) != 0) return rc;
     row_array a[1] = { { verdicts, verdicts ? n : 0, 1, NULL } };
     row_text t = { in, outp, total, total, 1, NULL, NULL };
     if ((rc = row_stage(L, a, 1, 1)) != 0) goto out;
     if ((rc = stage_aad(L, tweaks, tweak_bytes, &d_tweaks)) != 0) goto out;
     if ((rc = row_texts(L, &t)) != 0) goto out;
-    ES_KCHK("FF1", uaesk_ff1_run(L->stream, &c->tb, ks->nr, &ks->ek, decrypt, q, d_tweaks, nrec, t.d_in, t.d_out, a[0].d,
-                                 L->d_status));
+    k = uaesk_ff1_run(L->stream, &c->tb, ks->nr, &ks->ek, decrypt, q, d_tweaks, nrec, t.d_in, t.d_out, a[0].d, L->d_status);
+    if ((rc = launched("FF1", k)) != 0) goto out;
     if ((rc = row_finish(L, &t, a, 1, 1, &bad)) != 0) goto out;
     rc = bad ? (decrypt ? UAES_E_DECRYPTION : UAES_E_ENCRYPTION) : 0;
 out:
@@ -1408,20 +1394,18 @@ out:
 static int ff1_one(int decrypt, int keybits, const uint8_t *key, unsigned radix, const uint8_t *alphabet,
                    const uint8_t *tweak, size_t tweakLen, const void *in, size_t len, void *out)
 {
-    keysched ks;
+    KEYSCHED(ks);
     uaesk_ff1 q;
     int rc;
     if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
-    if ((rc = ff1_setup(radix, alphabet, tweakLen, 0, len, UAES_FF1_MAX, &q)) != 0) { burn(&ks, sizeof ks); return rc; }
-    if (!in || !out || (tweakLen && !tweak)) { burn(&ks, sizeof ks); return fail(UAES_E_ARG, "NULL pointer"); }
+    if ((rc = ff1_setup(radix, alphabet, tweakLen, 0, len, UAES_FF1_MAX, &q)) != 0) return rc;
+    if (!in || !out || (tweakLen && !tweak)) return fail(UAES_E_ARG, "NULL pointer");
     if (host_take(in, out, len, 1) && !(tweakLen && is_device_ptr(tweak))) {
         const uaesh_key hk = host_key(&ks);
         rc = uaesh_ff1(&hk, decrypt, radix, alphabet, tweak, tweakLen, (const uint8_t *)in, len, (uint8_t *)out);
-        burn(&ks, sizeof ks);
         return rc == UAES_E_ENCRYPTION || rc == UAES_E_DECRYPTION ? rc : host_result(rc);
     }
     rc = ff1_gpu(&ks, decrypt, &q, tweak, tweakLen, 0, in, out, NULL);
-    burn(&ks, sizeof ks);
     return rc;
 }
 
@@ -1441,21 +1425,18 @@ static int ff1_batch(int decrypt, int keybits, const uint8_t *key, unsigned radi
                      const uint8_t *tweaks, size_t tweakLen, size_t tweak_stride, size_t nrec, size_t len,
                      const void *in, void *out, uint8_t *verdicts)
 {
-    keysched ks;
+    KEYSCHED(ks);
     uaesk_ff1 q;
     size_t tweak_bytes;
     int rc;
     if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
-    if ((rc = ff1_setup(radix, alphabet, tweakLen, tweak_stride, len, UAES_FF1_BATCH_MAX, &q)) != 0) { burn(&ks, sizeof ks); return rc; }
-    if (nrec == 0) { burn(&ks, sizeof ks); return 0; }
-    if (nrec > (size_t)-1 / len || (tweak_stride && nrec - 1 > ((size_t)-1 - tweakLen) / tweak_stride)) {
-        burn(&ks, sizeof ks);
+    if ((rc = ff1_setup(radix, alphabet, tweakLen, tweak_stride, len, UAES_FF1_BATCH_MAX, &q)) != 0) return rc;
+    if (nrec == 0) return 0;
+    if (nrec > (size_t)-1 / len || (tweak_stride && nrec - 1 > ((size_t)-1 - tweakLen) / tweak_stride))
         return fail(UAES_E_ARG, "batch size overflows");
-    }
-    if (!in || !out || (tweakLen && !tweaks)) { burn(&ks, sizeof ks); return fail(UAES_E_ARG, "NULL pointer"); }
+    if (!in || !out || (tweakLen && !tweaks)) return fail(UAES_E_ARG, "NULL pointer");
     tweak_bytes = tweakLen ? (nrec - 1) * tweak_stride + tweakLen : 0;
     rc = ff1_gpu(&ks, decrypt, &q, tweaks, tweak_bytes, nrec, in, out, verdicts);
-    burn(&ks, sizeof ks);
     return rc;
 }
 
@@ -1490,8 +1471,8 @@ static int ff3_setup(keysched *ks, int keybits, const uint8_t *key, unsigned rad
     burn(rev, sizeof rev);
     if (rc) return rc;
     memset(q, 0, sizeof *q);
-    if ((rc = fpe_alphabet("FF3-1", radix, alphabet, q->inv, q->fwd)) != 0) { burn(ks, sizeof *ks); return rc; }
-    if (len < uaesh_ff1_minlen(radix) || len > uaesh_ff3_maxlen(radix)) { burn(ks, sizeof *ks); return UAES_E_DATALENGTH; }
+    if ((rc = fpe_alphabet("FF3-1", radix, alphabet, q->inv, q->fwd)) != 0) return rc;
+    if (len < uaesh_ff1_minlen(radix) || len > uaesh_ff3_maxlen(radix)) return UAES_E_DATALENGTH;
     q->radix = radix;
     q->len = (unsigned)len;
     q->tweak_stride = tweak_stride;
@@ -1506,15 +1487,15 @@ static int ff3_gpu(const keysched *ks, int decrypt, const uaesk_ff3 *q, const ui
     lane *L;
     const void *d_tweaks = NULL;
     const size_t n = nrec ? nrec : 1, total = n * q->len;
-    int rc, bad;
+    int rc, k, bad;
     if ((rc = enter(&c, &L)) != 0) return rc;
     row_array a[1] = { { verdicts, verdicts ? n : 0, 1, NULL } };
     row_text t = { in, outp, total, total, 1, NULL, NULL };
     if ((rc = row_stage(L, a, 1, 1)) != 0) goto out;
     if ((rc = stage_aad(L, tweaks, tweak_bytes, &d_tweaks)) != 0) goto out;
     if ((rc = row_texts(L, &t)) != 0) goto out;
-    ES_KCHK("FF3-1", uaesk_ff3_run(L->stream, &c->tb, ks->nr, &ks->ek, decrypt, q, d_tweaks, nrec, t.d_in, t.d_out, a[0].d,
-                                   L->d_status));
+    k = uaesk_ff3_run(L->stream, &c->tb, ks->nr, &ks->ek, decrypt, q, d_tweaks, nrec, t.d_in, t.d_out, a[0].d, L->d_status);
+    if ((rc = launched("FF3-1", k)) != 0) goto out;
     if ((rc = row_finish(L, &t, a, 1, 1, &bad)) != 0) goto out;
     rc = bad ? (decrypt ? UAES_E_DECRYPTION : UAES_E_ENCRYPTION) : 0;
 out:
@@ -1524,19 +1505,17 @@ out:
 static int ff3_one(int decrypt, int keybits, const uint8_t *key, unsigned radix, const uint8_t *alphabet,
                    const uint8_t *tweak, const void *in, size_t len, void *out)
 {
-    keysched ks;
+    KEYSCHED(ks);
     uaesk_ff3 q;
     int rc;
     if ((rc = ff3_setup(&ks, keybits, key, radix, alphabet, 0, len, &q)) != 0) return rc;
-    if (!in || !out || !tweak) { burn(&ks, sizeof ks); return fail(UAES_E_ARG, "NULL pointer"); }
+    if (!in || !out || !tweak) return fail(UAES_E_ARG, "NULL pointer");
     if (host_take(in, out, len, 1) && !is_device_ptr(tweak)) {
         const uaesh_key hk = host_key(&ks);
         rc = uaesh_ff3(&hk, decrypt, radix, alphabet, tweak, (const uint8_t *)in, len, (uint8_t *)out);
-        burn(&ks, sizeof ks);
         return rc == UAES_E_ENCRYPTION || rc == UAES_E_DECRYPTION ? rc : host_result(rc);
     }
     rc = ff3_gpu(&ks, decrypt, &q, tweak, UAES_FF3_TWEAK, 0, in, out, NULL);
-    burn(&ks, sizeof ks);
     return rc;
 }
 
@@ -1558,18 +1537,15 @@ static int ff3_batch(int decrypt, int keybits, const uint8_t *key, unsigned radi
                      const uint8_t *tweaks, size_t tweak_stride, size_t nrec, size_t len,
                      const void *in, void *out, uint8_t *verdicts)
 {
-    keysched ks;
+    KEYSCHED(ks);
     uaesk_ff3 q;
     int rc;
     if ((rc = ff3_setup(&ks, keybits, key, radix, alphabet, tweak_stride, len, &q)) != 0) return rc;
-    if (nrec == 0) { burn(&ks, sizeof ks); return 0; }
-    if (nrec > (size_t)-1 / len || (tweak_stride && nrec - 1 > ((size_t)-1 - UAES_FF3_TWEAK) / tweak_stride)) {
-        burn(&ks, sizeof ks);
+    if (nrec == 0) return 0;
+    if (nrec > (size_t)-1 / len || (tweak_stride && nrec - 1 > ((size_t)-1 - UAES_FF3_TWEAK) / tweak_stride))
         return fail(UAES_E_ARG, "batch size overflows");
-    }
-    if (!in || !out || !tweaks) { burn(&ks, sizeof ks); return fail(UAES_E_ARG, "NULL pointer"); }
+    if (!in || !out || !tweaks) return fail(UAES_E_ARG, "NULL pointer");
     rc = ff3_gpu(&ks, decrypt, &q, tweaks, (nrec - 1) * tweak_stride + UAES_FF3_TWEAK, nrec, in, out, verdicts);
-    burn(&ks, sizeof ks);
     return rc;
 }
 
@@ -1596,7 +1572,7 @@ static int ocb_common(int keybits, const uint8_t *key, const uint8_t *nonce, siz
 {
     context *c;
     lane *L;
-    keysched ks;
+    KEYSCHED(ks);
     io_plan io;
     const void *d_aad;
     int rc, status = -1;
@@ -1611,7 +1587,7 @@ static int ocb_common(int keybits, const uint8_t *key, const uint8_t *nonce, siz
         rc = uaesh_ocb(&hk, decrypt, nonce, nonceLen, tagLen, (const uint8_t *)aData, aDataLen, (const uint8_t *)in, len, (uint8_t *)out);
         if (rc < 0) return fail(UAES_E_HIP, "out of host memory");
         if (rc == UAES_E_AUTHENTICATION && wipe_on_auth_failure()) memset(out, 0, len);
-        HOST_RET(ks, rc);
+        return host_result(rc);
     }
     if ((rc = enter(&c, &L)) != 0) return rc;
     do {
@@ -1626,7 +1602,7 @@ static int ocb_common(int keybits, const uint8_t *key, const uint8_t *nonce, siz
         int k = uaesk_ocb(L->stream, &c->tb, ks.nr, &ks.ek, &ks.dk, decrypt, nonce, nonceLen, tagLen, d_aad, aDataLen,
                           io.din, len, io.dout, L->scratch, scratch_done_word(L->scratch, L->scratch_cap), st_where);
         ticket_armed_launch_done(L);
-        if (k) { rc = fail(UAES_E_HIP, "ocb launch: %s", hipGetErrorString((hipError_t)k)); break; }
+        if ((rc = launched("ocb", k)) != 0) break;
         if (decrypt) {
             if ((rc = lane_read_status(L, st_where, &status)) != 0) break;
             io.drained = 1;
@@ -1671,9 +1647,9 @@ int uaes_ocb_decrypt(int keybits, const uint8_t *key, const uint8_t *nonce,
  * schedules (a decrypting record needs the inverse cipher for its text and the forward one for K_top, HASH, the pad and
  * the tag).  Like the reference's OCB a decryption writes the text before it knows the tag.  The batch always runs on
  * the GPU: the host policy of the one-message calls does not apply. */
-static int ocb_batch_launch(const aead_rows *b, context *c, lane *L, const keysched *ks, const row_array *a, const row_text *t)
+static int ocb_batch_launch(const aead_rows *b, context *c, lane *L, const keysched *const ks[2], const row_array *a, const row_text *t)
 {
-    return uaesk_ocb_batch(L->stream, &c->tb, ks->nr, &ks->ek, &ks->dk, b->decrypt, wipe_on_auth_failure(), a[AB_NONCES].d,
+    return uaesk_ocb_batch(L->stream, &c->tb, ks[0]->nr, &ks[0]->ek, &ks[0]->dk, b->decrypt, wipe_on_auth_failure(), a[AB_NONCES].d,
                            b->side[AB_NONCES].each, b->side[AB_TAGS].each, a[AB_AAD].d, b->side[AB_AAD].each, b->nmsg,
                            b->msg_bytes, a[AB_LENS].d, t->d_in, t->d_out, a[AB_TAGS].d, a[AB_VERDICTS].d, L->d_status);
 }
@@ -1718,7 +1694,7 @@ int uaes_ocb_dev(int keybits, const uint8_t *key, const uint8_t *nonce, int decr
                  const void *d_in, size_t len, void *d_out, int *d_status, void *stream)
 {
     context *c;
-    keysched ks;
+    KEYSCHED(ks);
     void *scr;
     int rc, slot;
     if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
