@@ -496,9 +496,9 @@ int uaes_kw_unwrap_batch(int keybits, const uint8_t *kek, size_t nkeys, size_t w
  * the encryption / decryption error if any record was bad.  nrec == 0 returns 0.  A single call of up to
  * UAES_FF1_BATCH_MAX numerals runs as a batch of one, a longer one on a wave of its own.
  * Rates (profiles/ff1_rate.md: tools/ff1_rate.py on an MI355X, AES-128, 16-digit decimal records, device-resident):
- * 2^20 records 5.02 ms = 2.09e8 records/s, 2^16 records 0.34 ms, 2^10 records 0.10 ms, shared or per-record tweaks,
- * either direction; one 16-digit call 105 us; one 4096-digit call 20 ms.  One host core: the reference 2.62e5
- * records/s, the engine's host path 4.13e5.                                                                       */
+ * 2^20 records 5.02 ms = 2.09e8 records/s, 2^16 records 0.35 ms, 2^10 records 0.10 ms, shared or per-record tweaks,
+ * either direction; one 16-digit call 108 us; one 4096-digit call 20 ms.  One host core: the reference 2.58e5
+ * records/s, the engine's host path 4.46e5.                                                                       */
 int uaes_ff1_encrypt(int keybits, const uint8_t *key, unsigned radix, const uint8_t *alphabet,
                      const uint8_t *tweak, size_t tweakLen, const void *in, size_t len, void *out);
 int uaes_ff1_decrypt(int keybits, const uint8_t *key, unsigned radix, const uint8_t *alphabet,
@@ -530,8 +530,8 @@ int uaes_ff1_decrypt_batch(int keybits, const uint8_t *key, unsigned radix, cons
  * error if any record was bad.  nrec == 0 returns 0.  A single call that goes to the GPU runs as a batch of one.
  * Rates (profiles/ff3_rate.md: tools/ff3_rate.py on an MI355X, AES-128, 16-digit decimal records, device-resident):
  * 2^20 records 2.64 ms = 3.97e8 records/s, 2^16 records 0.19 ms, 2^10 records 0.066 ms, shared or per-record tweaks,
- * either direction -- the FF1 batch of the same shape in the same run: 5.02 ms, 0.34 ms, 0.10 ms.  One 16-digit call
- * 88 us from host memory, 71 us from device memory.  The engine's host path on one core: 5.13e5 records/s. */
+ * either direction -- the FF1 batch of the same shape in the same run: 5.04 ms, 0.35 ms, 0.10 ms.  One 16-digit call
+ * 94 us from host memory, 75 us from device memory.  The engine's host path on one core: 5.47e5 records/s. */
 size_t uaes_ff3_maxlen(unsigned radix);
 int uaes_ff3_encrypt(int keybits, const uint8_t *key, unsigned radix, const uint8_t *alphabet,
                      const uint8_t *tweak /* 7 bytes */, const void *in, size_t len, void *out);

@@ -864,7 +864,10 @@ def kw_plan(length, nkeys=0, unwrap=False):
     return None if name is None else (name.decode(), out[0], out[1], out[2])
 
 
-def _ff1_alpha(alphabet, radix):
+FF3_TWEAK_LEN = 7
+
+
+def _fpe_alpha(alphabet, radix):
     """(radix, alphabet argument): alphabet = the bytes of the numerals, or None with radix = raw digit values"""
     if alphabet is None:
         if radix is None:
@@ -874,14 +877,21 @@ def _ff1_alpha(alphabet, radix):
     return len(alphabet), _in(alphabet)
 
 
-def _ff1(decrypt, key, tweak, text, alphabet, radix, prefill):
-    radix, a = _ff1_alpha(alphabet, radix)
+def _ff3_tweak(tweak):
+    if len(tweak) != FF3_TWEAK_LEN:
+        raise ValueError("FF3-1 tweak of %d bytes (%d)" % (len(tweak), FF3_TWEAK_LEN))
+    return bytes(tweak)
+
+
+def _fpe(ff3, decrypt, key, tweak, text, alphabet, radix, prefill):
+    """The one-text calls of FF1 and FF3-1: FF1 passes the tweak's length, FF3-1's is fixed"""
+    radix, a = _fpe_alpha(alphabet, radix)
     o = _out(len(text), prefill)
-    L = engine()
-    fn = L.uaes_ff1_decrypt if decrypt else L.uaes_ff1_encrypt
-    rc = fn(_bits(key), _in(key), radix, a, _in(tweak), len(tweak), _in(text), len(text), o)
+    fn = getattr(engine(), "uaes_%s_%s" % ("ff3" if ff3 else "ff1", "decrypt" if decrypt else "encrypt"))
+    tw = (_in(_ff3_tweak(tweak)),) if ff3 else (_in(tweak), len(tweak))
+    rc = fn(_bits(key), _in(key), radix, a, *tw, _in(text), len(text), o)
     if rc < 0 and rc != -2:
-        _check(rc, "AES_FPE_decrypt" if decrypt else "AES_FPE_encrypt")
+        _check(rc, "AES_%s_%s" % ("FF3" if ff3 else "FPE", "decrypt" if decrypt else "encrypt"))
     return rc, bytes(o)[:len(text)]
 
 
@@ -890,65 +900,12 @@ def AES_FPE_encrypt(key, tweak, text, alphabet=b"0123456789", radix=None, prefil
     values below `radix`).  Returns (code, output): 0; 1 for a text shorter than the radix's minimum or longer than
     4096; -2 for a radix outside 2..256 or a repeated alphabet byte; 0x1E for a byte that is no numeral; the output is
     the prefill unless the code is 0."""
-    return _ff1(False, key, tweak, text, alphabet, radix, prefill)
+    return _fpe(False, False, key, tweak, text, alphabet, radix, prefill)
 
 
 def AES_FPE_decrypt(key, tweak, text, alphabet=b"0123456789", radix=None, prefill=0):
     """micro_aes.c:2343.  As AES_FPE_encrypt; 0x1D for a byte that is no numeral."""
-    return _ff1(True, key, tweak, text, alphabet, radix, prefill)
-
-
-def ff1_batch(key, tweaks, records, alphabet=b"0123456789", radix=None, decrypt=False, prefill=0, verdicts=True):
-    """FF1 of many equal-sized records under one key (uaes_ff1_*_batch).  tweaks = one tweak (bytes) for all records or a
-    list of equal-sized tweaks, one per record.  Returns (code, outputs, verdicts): a record with a byte that is no
-    numeral keeps the prefill and has verdict 0."""
-    n = len(records)
-    radix, a = _ff1_alpha(alphabet, radix)
-    if isinstance(tweaks, (bytes, bytearray)):
-        tl, stride, tb = len(tweaks), 0, bytes(tweaks)
-    else:
-        if len(tweaks) != n:
-            raise ValueError("one tweak per record")
-        tl, tb = _records(tweaks, "tweaks")
-        stride = tl
-    rl, rb = _records(records, "records")
-    o = _out(n * rl, prefill)
-    v = _out(n)
-    L = engine()
-    fn = L.uaes_ff1_decrypt_batch if decrypt else L.uaes_ff1_encrypt_batch
-    rc = fn(_bits(key), _in(key), radix, a, _in(tb), tl, stride, n, rl, _in(rb), o, v if verdicts else None)
-    if rc < 0 and rc != -2:
-        _check(rc, "uaes_ff1_batch")
-    raw = bytes(o)
-    return rc, _split(raw, rl, n), list(bytes(v)[:n])
-
-
-def ff1_plan(length, nrec=0, radix=10, decrypt=False):
-    """What FF1 over a text of `length` numerals would run (uaes_debug_plan_ff1; nrec 0: the one-text calls, else a
-    batch): (arrangement, launches, workgroups, threads per workgroup), or None for arguments that make no sense."""
-    out = (C.c_int * 3)()
-    name = engine().uaes_debug_plan_ff1(int(bool(decrypt)), radix, length, nrec, out)
-    return None if name is None else (name.decode(), out[0], out[1], out[2])
-
-
-FF3_TWEAK_LEN = 7
-
-
-def _ff3_tweak(tweak):
-    if len(tweak) != FF3_TWEAK_LEN:
-        raise ValueError("FF3-1 tweak of %d bytes (%d)" % (len(tweak), FF3_TWEAK_LEN))
-    return bytes(tweak)
-
-
-def _ff3(decrypt, key, tweak, text, alphabet, radix, prefill):
-    radix, a = _ff1_alpha(alphabet, radix)
-    o = _out(len(text), prefill)
-    L = engine()
-    fn = L.uaes_ff3_decrypt if decrypt else L.uaes_ff3_encrypt
-    rc = fn(_bits(key), _in(key), radix, a, _in(_ff3_tweak(tweak)), _in(text), len(text), o)
-    if rc < 0 and rc != -2:
-        _check(rc, "AES_FF3_decrypt" if decrypt else "AES_FF3_encrypt")
-    return rc, bytes(o)[:len(text)]
+    return _fpe(False, True, key, tweak, text, alphabet, radix, prefill)
 
 
 def AES_FF3_encrypt(key, tweak, text, alphabet=b"0123456789", radix=None, prefill=0):
@@ -956,45 +913,68 @@ def AES_FF3_encrypt(key, tweak, text, alphabet=b"0123456789", radix=None, prefil
     each, out of `alphabet` (alphabet=None: raw digit values below `radix`).  Returns (code, output): 0; 1 for a text
     shorter than the radix's minimum or longer than ff3_maxlen(radix); -2 for a radix outside 2..256 or a repeated
     alphabet byte; 0x1E for a byte that is no numeral; the output is the prefill unless the code is 0."""
-    return _ff3(False, key, tweak, text, alphabet, radix, prefill)
+    return _fpe(True, False, key, tweak, text, alphabet, radix, prefill)
 
 
 def AES_FF3_decrypt(key, tweak, text, alphabet=b"0123456789", radix=None, prefill=0):
     """micro_aes.c:2343 built with FF_X 3.  As AES_FF3_encrypt; 0x1D for a byte that is no numeral."""
-    return _ff3(True, key, tweak, text, alphabet, radix, prefill)
+    return _fpe(True, True, key, tweak, text, alphabet, radix, prefill)
+
+
+def _fpe_batch(ff3, key, tweaks, records, alphabet, radix, decrypt, prefill, verdicts):
+    """The batches of FF1 and FF3-1: FF1 passes the tweaks' length, FF3-1's is fixed"""
+    n = len(records)
+    radix, a = _fpe_alpha(alphabet, radix)
+    if isinstance(tweaks, (bytes, bytearray)):
+        tl, stride, tb = len(tweaks), 0, _ff3_tweak(tweaks) if ff3 else bytes(tweaks)
+    else:
+        if len(tweaks) != n:
+            raise ValueError("one tweak per record")
+        tl, tb = _records([_ff3_tweak(t) for t in tweaks] if ff3 else tweaks, "tweaks")
+        stride = tl
+    rl, rb = _records(records, "records")
+    o = _out(n * rl, prefill)
+    v = _out(n)
+    name = "uaes_%s_batch" % ("ff3" if ff3 else "ff1")
+    fn = getattr(engine(), name.replace("batch", "decrypt_batch" if decrypt else "encrypt_batch"))
+    tw = (_in(tb), stride) if ff3 else (_in(tb), tl, stride)
+    rc = fn(_bits(key), _in(key), radix, a, *tw, n, rl, _in(rb), o, v if verdicts else None)
+    if rc < 0 and rc != -2:
+        _check(rc, name)
+    raw = bytes(o)
+    return rc, _split(raw, rl, n), list(bytes(v)[:n])
+
+
+def ff1_batch(key, tweaks, records, alphabet=b"0123456789", radix=None, decrypt=False, prefill=0, verdicts=True):
+    """FF1 of many equal-sized records under one key (uaes_ff1_*_batch).  tweaks = one tweak (bytes) for all records or a
+    list of equal-sized tweaks, one per record.  Returns (code, outputs, verdicts): a record with a byte that is no
+    numeral keeps the prefill and has verdict 0."""
+    return _fpe_batch(False, key, tweaks, records, alphabet, radix, decrypt, prefill, verdicts)
 
 
 def ff3_batch(key, tweaks, records, alphabet=b"0123456789", radix=None, decrypt=False, prefill=0, verdicts=True):
     """FF3-1 of many equal-sized records under one key (uaes_ff3_*_batch).  tweaks = one 7-byte tweak (bytes) for all
     records or a list of them, one per record.  Returns (code, outputs, verdicts): a record with a byte that is no
     numeral keeps the prefill and has verdict 0."""
-    n = len(records)
-    radix, a = _ff1_alpha(alphabet, radix)
-    if isinstance(tweaks, (bytes, bytearray)):
-        stride, tb = 0, _ff3_tweak(tweaks)
-    else:
-        if len(tweaks) != n:
-            raise ValueError("one tweak per record")
-        tb = b"".join(_ff3_tweak(t) for t in tweaks)
-        stride = FF3_TWEAK_LEN
-    rl, rb = _records(records, "records")
-    o = _out(n * rl, prefill)
-    v = _out(n)
-    L = engine()
-    fn = L.uaes_ff3_decrypt_batch if decrypt else L.uaes_ff3_encrypt_batch
-    rc = fn(_bits(key), _in(key), radix, a, _in(tb), stride, n, rl, _in(rb), o, v if verdicts else None)
-    if rc < 0 and rc != -2:
-        _check(rc, "uaes_ff3_batch")
-    raw = bytes(o)
-    return rc, _split(raw, rl, n), list(bytes(v)[:n])
+    return _fpe_batch(True, key, tweaks, records, alphabet, radix, decrypt, prefill, verdicts)
+
+
+def _fpe_plan(hook, length, nrec, radix, decrypt):
+    out = (C.c_int * 3)()
+    name = getattr(engine(), hook)(int(bool(decrypt)), radix, length, nrec, out)
+    return None if name is None else (name.decode(), out[0], out[1], out[2])
+
+
+def ff1_plan(length, nrec=0, radix=10, decrypt=False):
+    """What FF1 over a text of `length` numerals would run (uaes_debug_plan_ff1; nrec 0: the one-text calls, else a
+    batch): (arrangement, launches, workgroups, threads per workgroup), or None for arguments that make no sense."""
+    return _fpe_plan("uaes_debug_plan_ff1", length, nrec, radix, decrypt)
 
 
 def ff3_plan(length, nrec=0, radix=10, decrypt=False):
     """What FF3-1 over a text of `length` numerals would run (uaes_debug_plan_ff3; nrec 0: the one-text calls, else a
     batch): (arrangement, launches, workgroups, threads per workgroup), or None for arguments that make no sense."""
-    out = (C.c_int * 3)()
-    name = engine().uaes_debug_plan_ff3(int(bool(decrypt)), radix, length, nrec, out)
-    return None if name is None else (name.decode(), out[0], out[1], out[2])
+    return _fpe_plan("uaes_debug_plan_ff3", length, nrec, radix, decrypt)
 
 
 def ff3_maxlen(radix):

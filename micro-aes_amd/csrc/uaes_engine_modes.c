@@ -1325,21 +1325,13 @@ int uaes_kw_unwrap_batch(int keybits, const uint8_t *kek, size_t nkeys, size_t w
 /* Kernels in uaes_ff1.hip.  What depends on (radix, alphabet, len, tweak length) alone is made here, once per call: the
  * two alphabet tables, b and d with exact integers (uaesh_ff1_b -- not the reference's floating-point LOGRDX form,
  * DESIGN.md), the P block.  cap = the longest text this call takes. */
-/* inv = byte -> digit value (0xFF: no numeral), fwd = digit value -> byte; alphabet NULL: the digit values themselves */
+/* the two tables as the host path makes them (uaesh_fpe_alphabet), with the engine's messages */
 static int fpe_alphabet(const char *mode, unsigned radix, const uint8_t *alphabet, uint8_t inv[256], uint8_t fwd[256])
 {
-    uint8_t seen[256];
-    unsigned i;
+    int twice;
     if (radix < 2 || radix > 256) return fail(UAES_E_ARG, "%s: radix %u (2..256)", mode, radix);
-    memset(seen, 0, sizeof seen);
-    memset(inv, 0xFF, 256);
-    for (i = 0; i < radix; ++i) {
-        const uint8_t a = alphabet ? alphabet[i] : (uint8_t)i;
-        if (seen[a]) return fail(UAES_E_ARG, "%s: byte 0x%02x occurs twice in the alphabet", mode, a);
-        seen[a] = 1;
-        inv[a] = (uint8_t)i;
-        fwd[i] = a;
-    }
+    if ((twice = uaesh_fpe_alphabet(radix, alphabet, inv, fwd)) >= 0)
+        return fail(UAES_E_ARG, "%s: byte 0x%02x occurs twice in the alphabet", mode, twice);
     return 0;
 }
 
@@ -1367,15 +1359,15 @@ static int ff1_setup(unsigned radix, const uint8_t *alphabet, size_t tweakLen, s
     return 0;
 }
 
-/* nrec 0: one text.  Host arrays travel through the lane's staging buffers; the output's buffer starts as a copy of
- * the caller's, so that a record the kernel leaves unwritten comes back as it was. */
-static int ff1_gpu(const keysched *ks, int decrypt, const uaesk_ff1 *q, const uint8_t *tweaks, size_t tweak_bytes,
-                   size_t nrec, const void *in, void *outp, uint8_t *verdicts)
+/* FF1 (f1) or FF3-1 (f3, f1 NULL).  nrec 0: one text.  Host arrays travel through the lane's staging buffers; the
+ * output's buffer starts as a copy of the caller's, so that a record the kernel leaves unwritten comes back as it was. */
+static int fpe_gpu(const keysched *ks, int decrypt, const uaesk_ff1 *f1, const uaesk_ff3 *f3, const uint8_t *tweaks,
+                   size_t tweak_bytes, size_t nrec, const void *in, void *outp, uint8_t *verdicts)
 {
     context *c;
     lane *L;
     const void *d_tweaks = NULL;
-    const size_t n = nrec ? nrec : 1, total = n * q->len;
+    const size_t n = nrec ? nrec : 1, total = n * (f1 ? f1->len : f3->len);
     int rc, k, bad;
     if ((rc = enter(&c, &L)) != 0) return rc;
     row_array a[1] = { { verdicts, verdicts ? n : 0, 1, NULL } };
@@ -1383,12 +1375,30 @@ static int ff1_gpu(const keysched *ks, int decrypt, const uaesk_ff1 *q, const ui
     if ((rc = row_stage(L, a, 1, 1)) != 0) goto out;
     if ((rc = stage_aad(L, tweaks, tweak_bytes, &d_tweaks)) != 0) goto out;
     if ((rc = row_texts(L, &t)) != 0) goto out;
-    k = uaesk_ff1_run(L->stream, &c->tb, ks->nr, &ks->ek, decrypt, q, d_tweaks, nrec, t.d_in, t.d_out, a[0].d, L->d_status);
-    if ((rc = launched("FF1", k)) != 0) goto out;
+    if (f1) k = uaesk_ff1_run(L->stream, &c->tb, ks->nr, &ks->ek, decrypt, f1, d_tweaks, nrec, t.d_in, t.d_out, a[0].d, L->d_status);
+    else k = uaesk_ff3_run(L->stream, &c->tb, ks->nr, &ks->ek, decrypt, f3, d_tweaks, nrec, t.d_in, t.d_out, a[0].d, L->d_status);
+    if ((rc = launched(f1 ? "FF1" : "FF3-1", k)) != 0) goto out;
     if ((rc = row_finish(L, &t, a, 1, 1, &bad)) != 0) goto out;
     rc = bad ? (decrypt ? UAES_E_DECRYPTION : UAES_E_ENCRYPTION) : 0;
 out:
     DONE(L, rc);
+}
+
+/* what a batch checks once its setup has passed and nrec is not 0; tweakLen 0: no tweaks.  *tweak_bytes = their span */
+static int fpe_batch_args(size_t nrec, size_t len, size_t tweakLen, size_t tweak_stride, const void *tweaks,
+                          const void *in, const void *out, size_t *tweak_bytes)
+{
+    if (nrec > (size_t)-1 / len || (tweak_stride && nrec - 1 > ((size_t)-1 - tweakLen) / tweak_stride))
+        return fail(UAES_E_ARG, "batch size overflows");
+    if (!in || !out || (tweakLen && !tweaks)) return fail(UAES_E_ARG, "NULL pointer");
+    *tweak_bytes = tweakLen ? (nrec - 1) * tweak_stride + tweakLen : 0;
+    return 0;
+}
+
+/* the host path's answer: a byte that is no numeral is the caller's code, anything else goes through host_result */
+static int fpe_host_result(int rc)
+{
+    return rc == UAES_E_ENCRYPTION || rc == UAES_E_DECRYPTION ? rc : host_result(rc);
 }
 
 static int ff1_one(int decrypt, int keybits, const uint8_t *key, unsigned radix, const uint8_t *alphabet,
@@ -1402,11 +1412,9 @@ static int ff1_one(int decrypt, int keybits, const uint8_t *key, unsigned radix,
     if (!in || !out || (tweakLen && !tweak)) return fail(UAES_E_ARG, "NULL pointer");
     if (host_take(in, out, len, 1) && !(tweakLen && is_device_ptr(tweak))) {
         const uaesh_key hk = host_key(&ks);
-        rc = uaesh_ff1(&hk, decrypt, radix, alphabet, tweak, tweakLen, (const uint8_t *)in, len, (uint8_t *)out);
-        return rc == UAES_E_ENCRYPTION || rc == UAES_E_DECRYPTION ? rc : host_result(rc);
+        return fpe_host_result(uaesh_ff1(&hk, decrypt, radix, alphabet, tweak, tweakLen, (const uint8_t *)in, len, (uint8_t *)out));
     }
-    rc = ff1_gpu(&ks, decrypt, &q, tweak, tweakLen, 0, in, out, NULL);
-    return rc;
+    return fpe_gpu(&ks, decrypt, &q, NULL, tweak, tweakLen, 0, in, out, NULL);
 }
 
 int uaes_ff1_encrypt(int keybits, const uint8_t *key, unsigned radix, const uint8_t *alphabet,
@@ -1432,12 +1440,8 @@ static int ff1_batch(int decrypt, int keybits, const uint8_t *key, unsigned radi
     if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
     if ((rc = ff1_setup(radix, alphabet, tweakLen, tweak_stride, len, UAES_FF1_BATCH_MAX, &q)) != 0) return rc;
     if (nrec == 0) return 0;
-    if (nrec > (size_t)-1 / len || (tweak_stride && nrec - 1 > ((size_t)-1 - tweakLen) / tweak_stride))
-        return fail(UAES_E_ARG, "batch size overflows");
-    if (!in || !out || (tweakLen && !tweaks)) return fail(UAES_E_ARG, "NULL pointer");
-    tweak_bytes = tweakLen ? (nrec - 1) * tweak_stride + tweakLen : 0;
-    rc = ff1_gpu(&ks, decrypt, &q, tweaks, tweak_bytes, nrec, in, out, verdicts);
-    return rc;
+    if ((rc = fpe_batch_args(nrec, len, tweakLen, tweak_stride, tweaks, in, out, &tweak_bytes)) != 0) return rc;
+    return fpe_gpu(&ks, decrypt, &q, NULL, tweaks, tweak_bytes, nrec, in, out, verdicts);
 }
 
 int uaes_ff1_encrypt_batch(int keybits, const uint8_t *key, unsigned radix, const uint8_t *alphabet,
@@ -1479,29 +1483,6 @@ static int ff3_setup(keysched *ks, int keybits, const uint8_t *key, unsigned rad
     return 0;
 }
 
-/* nrec 0: one text.  As ff1_gpu: the output's staging buffer starts as a copy of the caller's. */
-static int ff3_gpu(const keysched *ks, int decrypt, const uaesk_ff3 *q, const uint8_t *tweaks, size_t tweak_bytes,
-                   size_t nrec, const void *in, void *outp, uint8_t *verdicts)
-{
-    context *c;
-    lane *L;
-    const void *d_tweaks = NULL;
-    const size_t n = nrec ? nrec : 1, total = n * q->len;
-    int rc, k, bad;
-    if ((rc = enter(&c, &L)) != 0) return rc;
-    row_array a[1] = { { verdicts, verdicts ? n : 0, 1, NULL } };
-    row_text t = { in, outp, total, total, 1, NULL, NULL };
-    if ((rc = row_stage(L, a, 1, 1)) != 0) goto out;
-    if ((rc = stage_aad(L, tweaks, tweak_bytes, &d_tweaks)) != 0) goto out;
-    if ((rc = row_texts(L, &t)) != 0) goto out;
-    k = uaesk_ff3_run(L->stream, &c->tb, ks->nr, &ks->ek, decrypt, q, d_tweaks, nrec, t.d_in, t.d_out, a[0].d, L->d_status);
-    if ((rc = launched("FF3-1", k)) != 0) goto out;
-    if ((rc = row_finish(L, &t, a, 1, 1, &bad)) != 0) goto out;
-    rc = bad ? (decrypt ? UAES_E_DECRYPTION : UAES_E_ENCRYPTION) : 0;
-out:
-    DONE(L, rc);
-}
-
 static int ff3_one(int decrypt, int keybits, const uint8_t *key, unsigned radix, const uint8_t *alphabet,
                    const uint8_t *tweak, const void *in, size_t len, void *out)
 {
@@ -1512,11 +1493,9 @@ static int ff3_one(int decrypt, int keybits, const uint8_t *key, unsigned radix,
     if (!in || !out || !tweak) return fail(UAES_E_ARG, "NULL pointer");
     if (host_take(in, out, len, 1) && !is_device_ptr(tweak)) {
         const uaesh_key hk = host_key(&ks);
-        rc = uaesh_ff3(&hk, decrypt, radix, alphabet, tweak, (const uint8_t *)in, len, (uint8_t *)out);
-        return rc == UAES_E_ENCRYPTION || rc == UAES_E_DECRYPTION ? rc : host_result(rc);
+        return fpe_host_result(uaesh_ff3(&hk, decrypt, radix, alphabet, tweak, (const uint8_t *)in, len, (uint8_t *)out));
     }
-    rc = ff3_gpu(&ks, decrypt, &q, tweak, UAES_FF3_TWEAK, 0, in, out, NULL);
-    return rc;
+    return fpe_gpu(&ks, decrypt, NULL, &q, tweak, UAES_FF3_TWEAK, 0, in, out, NULL);
 }
 
 size_t uaes_ff3_maxlen(unsigned radix) { return uaesh_ff3_maxlen(radix); }
@@ -1539,14 +1518,12 @@ static int ff3_batch(int decrypt, int keybits, const uint8_t *key, unsigned radi
 {
     KEYSCHED(ks);
     uaesk_ff3 q;
+    size_t tweak_bytes;
     int rc;
     if ((rc = ff3_setup(&ks, keybits, key, radix, alphabet, tweak_stride, len, &q)) != 0) return rc;
     if (nrec == 0) return 0;
-    if (nrec > (size_t)-1 / len || (tweak_stride && nrec - 1 > ((size_t)-1 - UAES_FF3_TWEAK) / tweak_stride))
-        return fail(UAES_E_ARG, "batch size overflows");
-    if (!in || !out || !tweaks) return fail(UAES_E_ARG, "NULL pointer");
-    rc = ff3_gpu(&ks, decrypt, &q, tweaks, (nrec - 1) * tweak_stride + UAES_FF3_TWEAK, nrec, in, out, verdicts);
-    return rc;
+    if ((rc = fpe_batch_args(nrec, len, UAES_FF3_TWEAK, tweak_stride, tweaks, in, out, &tweak_bytes)) != 0) return rc;
+    return fpe_gpu(&ks, decrypt, NULL, &q, tweaks, tweak_bytes, nrec, in, out, verdicts);
 }
 
 int uaes_ff3_encrypt_batch(int keybits, const uint8_t *key, unsigned radix, const uint8_t *alphabet,

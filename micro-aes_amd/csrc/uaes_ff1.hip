@@ -20,10 +20,7 @@
  *   NUM(B)    the number is 16-bit limbs in LDS, least significant first, a run of CL limbs per lane.  Step s (numeral s
  *             of B, most significant first) is N = N * radix + numeral; lane l does step s in iteration s + l, taking
  *             as carry-in what lane l - 1 carried out of the same step one iteration earlier (lane 0: the numeral).
- *   STR_m(y)  the digits are bytes in LDS, least significant first, a run of CD digits per lane.  Step s (16 bits of S,
- *             most significant first) is D = D * 65536 + word in radix-radix digits; same skew.  The carry out of
- *             digit m - 1 is dropped, which is the reduction modulo radix^m.  A digit step divides by the radix with a
- *             reciprocal (radix <= 256, the dividend below 2^25: the estimate is at most one too large).
+ *   STR_m(y)  fpe_str (uaes_fpe.hip.h) over the d / 2 16-bit words of S, through all W lanes.
  * The digit-wise addition with carry is m steps on lane 0.  How this is spread decides speed only.
  *
  * LDS of a record (a slot): the numerals X[len] (digit values), NS (NUM(B), then the bytes of S), the digits C.  All
@@ -33,96 +30,42 @@
  */
 #include <hip/hip_runtime.h>
 #include <string.h>
-#include "uaes_aes.hip.h"
+#include "uaes_fpe.hip.h"
 #include "uaes_device.h"
 #include "uaes_plan.h"
 
 extern "C" unsigned uaesh_ff1_minlen(unsigned radix);       /* uaes_host.c */
 
-#define FF1_ALPHA      512u                                 /* inv[256] | fwd[256] behind the round keys */
 #define FF1_NS(N, W)   ((N) / 2u + 2u * (W))               /* limbs: <= N/2 + 2W - 2 bytes; S: <= N/2 + 22 */
 #define FF1_C(N, W)    ((N) / 2u + (W))                     /* digits: <= N/2 + W - 1 */
 #define FF1_SLOT(N, W) ((N) + FF1_NS(N, W) + FF1_C(N, W) + 4u)   /* + 4: neighbouring slots start on different banks */
-#define FF1_ROOM16     (160u * 1024u - UAES_LDS_ROW4 - FF1_ALPHA)
+#define FF1_ROOM16     (160u * 1024u - UAES_LDS_ROW4 - FPE_ALPHA)
 
 static_assert(UAES_FF1_BATCH_MAX >= 64 && (UAES_FF1_BATCH_MAX & (UAES_FF1_BATCH_MAX - 1)) == 0, "a power of two, at least 64");
 static_assert((UAES_WG / 16u) * FF1_SLOT((unsigned)UAES_FF1_BATCH_MAX, 16u) <= FF1_ROOM16, "64 records share a workgroup");
 static_assert((UAES_WG / 16u) * FF1_SLOT(2u * (unsigned)UAES_FF1_BATCH_MAX, 16u) > FF1_ROOM16, "the largest such power of two");
-static_assert(UAES_LDS_ROW + FF1_ALPHA + FF1_SLOT((unsigned)UAES_FF1_MAX, 64u) <= 160u * 1024u, "LDS of one CU");
+static_assert(UAES_LDS_ROW + FPE_ALPHA + FF1_SLOT((unsigned)UAES_FF1_MAX, 64u) <= 160u * 1024u, "LDS of one CU");
 static_assert(FF1_SLOT((unsigned)UAES_FF1_BATCH_MAX, 16u) % 4u == 0 && UAES_FF1_MAX % 4 == 0, "NS is word aligned");
-
-typedef __attribute__((address_space(3))) unsigned char lds_u8;
-typedef __attribute__((address_space(3))) unsigned short lds_u16;
-typedef __attribute__((address_space(3))) u32 lds_u32;
-
-__device__ __forceinline__ u32 ff1_ld8(u32 a) { return *(lds_u8 *)(uintptr_t)a; }
-__device__ __forceinline__ void ff1_st8(u32 a, u32 v) { *(lds_u8 *)(uintptr_t)a = (unsigned char)v; }
-__device__ __forceinline__ u32 ff1_ld16(u32 a) { return *(lds_u16 *)(uintptr_t)a; }
-__device__ __forceinline__ void ff1_st16(u32 a, u32 v) { *(lds_u16 *)(uintptr_t)a = (unsigned short)v; }
-__device__ __forceinline__ void ff1_st32(u32 a, u32 v) { *(lds_u32 *)(uintptr_t)a = v; }
-
-/* between two phases: what the wave's lanes stored is what its lanes read next */
-#define FF1_PHASE() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 
 /* NUM_radix of the n numerals at LDS address src (most significant first) into the limbs at ns: W * cl of them */
 template <u32 W>
 __device__ __forceinline__ void ff1_num(u32 src, u32 n, u32 radix, u32 ns, u32 cl, u32 li)
 {
     const u32 mine = ns + 2u * li * cl;
-    for (u32 k = 0; k < cl; ++k) ff1_st16(mine + 2u * k, 0u);
+    for (u32 k = 0; k < cl; ++k) fpe_st16(mine + 2u * k, 0u);
     u32 cout = 0;
     for (u32 it = 0; it < n + W - 1u; ++it) {
         u32 cin = (u32)__shfl_up((int)cout, 1, (int)W);
-        if (li == 0) cin = it < n ? ff1_ld8(src + it) : 0u;
+        if (li == 0) cin = it < n ? fpe_ld8(src + it) : 0u;
         cout = 0;
         if ((int)(it - li) < (int)n) {                      /* before its first step a lane multiplies zeros */
             for (u32 k = 0; k < cl; ++k) {
-                const u32 t = ff1_ld16(mine + 2u * k) * radix + cin;
-                ff1_st16(mine + 2u * k, t & 0xffffu);
+                const u32 t = fpe_ld16(mine + 2u * k) * radix + cin;
+                fpe_st16(mine + 2u * k, t & 0xffffu);
                 cin = t >> 16;
             }
             cout = cin;
         }
-    }
-}
-
-/* the first d bytes at ns, a big-endian number, modulo radix^m, as m digits at cd, least significant first */
-template <u32 W>
-__device__ __forceinline__ void ff1_str(u32 ns, u32 d, u32 radix, u32 recip, u32 cd, u32 m, u32 li)
-{
-    const u32 per = (m + W - 1u) / W, lo = li * per;
-    const u32 cnt = lo < m ? (m - lo < per ? m - lo : per) : 0u;
-    const u32 mine = cd + lo, nw = d / 2u;
-    for (u32 k = 0; k < cnt; ++k) ff1_st8(mine + k, 0u);
-    u32 cout = 0;
-    for (u32 it = 0; it < nw + W - 1u; ++it) {
-        u32 cin = (u32)__shfl_up((int)cout, 1, (int)W);
-        if (li == 0) cin = it < nw ? (ff1_ld8(ns + 2u * it) << 8) | ff1_ld8(ns + 2u * it + 1u) : 0u;
-        cout = 0;
-        if ((int)(it - li) < (int)nw) {
-            u32 x = cin;                                    /* below 2^17 */
-            for (u32 k = 0; k < cnt; ++k) {
-                x += ff1_ld8(mine + k) << 16;
-                u32 q = __umulhi(x, recip), r = x - q * radix;
-                if ((int)r < 0) { --q; r += radix; }
-                ff1_st8(mine + k, r);
-                x = q;
-            }
-            cout = x;
-        }
-    }
-}
-
-/* X[a .. a + m) += / -= the digits at cd, modulo radix^m (addRadix / subRadix); one lane */
-__device__ __forceinline__ void ff1_add(u32 xa, u32 cd, u32 m, u32 radix, bool dec)
-{
-    int carry = 0;
-    for (u32 p = 0; p < m; ++p) {
-        const u32 at = xa + m - 1u - p;
-        int t = (int)ff1_ld8(at) + (dec ? -(int)ff1_ld8(cd + p) - carry : (int)ff1_ld8(cd + p) + carry);
-        carry = dec ? t < 0 : t >= (int)radix;
-        if (carry) t += dec ? (int)radix : -(int)radix;
-        ff1_st8(at, (u32)t);
     }
 }
 
@@ -136,11 +79,11 @@ __global__ __launch_bounds__(W == 16u ? UAES_WG : 64u) void k_ff1(uaesk_rk rk, u
 {
     constexpr u32 NMAX = W == 16u ? (u32)UAES_FF1_BATCH_MAX : (u32)UAES_FF1_MAX;
     constexpr u32 AT = W == 16u ? UAES_LDS_ROW4 : UAES_LDS_ROW;
-    for (u32 i = threadIdx.x; i < FF1_ALPHA; i += blockDim.x) ff1_st8(AT + i, i < 256u ? q.inv[i] : q.fwd[i - 256u]);
+    fpe_fill_alphabet(AT, q);
     if (W == 16u) row4_fill_tables(tb.te0, rk); else row_fill_tables(tb.te0, rk);        /* ends in a barrier */
     const RowLane<NR> L = W == 16u ? row4_lane<NR>() : row_lane<NR>();
     const u32 grp = threadIdx.x / W, li = threadIdx.x % W, groups = blockDim.x / W;
-    const u32 xat = AT + FF1_ALPHA + grp * FF1_SLOT(NMAX, W), ns = xat + NMAX, cd = ns + FF1_NS(NMAX, W);
+    const u32 xat = AT + FPE_ALPHA + grp * FF1_SLOT(NMAX, W), ns = xat + NMAX, cd = ns + FF1_NS(NMAX, W);
     const u32 radix = q.radix, len = q.len, u = len / 2u, v = len - u, b = q.b, d = q.d;
     const u32 recip = (u32)((0x100000000ull + radix - 1u) / radix);
     const u64 tfull = q.tweak_len & ~15ull;
@@ -152,14 +95,9 @@ __global__ __launch_bounds__(W == 16u ? UAES_WG : 64u) void k_ff1(uaesk_rk rk, u
         const bool live = base + grp < nrec;
         const u64 rec = live ? base + grp : 0;              /* a group without a record redoes record 0 and writes nothing */
         const unsigned char *src = in + rec * len, *tw = tweaks + rec * q.tweak_stride;
-        bool foreign = false;
-        for (u32 i = li; i < len; i += W) {
-            const u32 dg = ff1_ld8(AT + src[i]);
-            foreign |= dg >= radix;
-            ff1_st8(xat + i, dg);
-        }
+        const bool foreign = fpe_load<W>(AT, src, len, radix, xat, li);
         const bool good = W == 16u ? !row_any(foreign) : __ballot(foreign) == 0;
-        FF1_PHASE();
+        FPE_PHASE();
 
         u32 y = row_encrypt<NR>(row_pick(q.p, L.c), L);     /* E(P), then the tweak's full blocks */
         for (u64 j = 0; j < tfull; j += 16) y = row_encrypt<NR>(y ^ row_load(tw + j, 16, L.c), L);
@@ -169,36 +107,34 @@ __global__ __launch_bounds__(W == 16u ? UAES_WG : 64u) void k_ff1(uaesk_rk rk, u
             const u32 round = dec ? 9u - step : step, odd = round & 1u;
             const u32 m = odd ? v : u, n = odd ? u : v, xa = xat + (odd ? u : 0u), xb = xat + (odd ? 0u : u);
             ff1_num<W>(xb, n, radix, ns, cl, li);
-            FF1_PHASE();
+            FPE_PHASE();
             u32 w = y;
             for (u32 k = 0; k < nblk; ++k) {
                 u32 word = k == 0 ? twtail : 0u;
 #pragma unroll
                 for (u32 j = 0; j < 4u; ++j) {
                     const int tp = (int)(16u * k + 4u * L.c + j) - (int)pre;       /* 0: the round byte; 1..b: NUM(B) */
-                    const u32 byte = ff1_ld8(ns + (tp > 0 ? b - (u32)tp : 0u));
+                    const u32 byte = fpe_ld8(ns + (tp > 0 ? b - (u32)tp : 0u));
                     word |= (tp < 0 ? 0u : tp == 0 ? round : byte) << (8u * j);
                 }
                 w = row_encrypt<NR>(w ^ word, L);
             }
-            FF1_PHASE();
+            FPE_PHASE();
             for (u32 j = 0; j < nsb; ++j) {
                 const u32 e = j == 0 ? w : row_encrypt<NR>(w ^ (L.c == 3u ? bswap32(j) : 0u), L);
-                if ((li & 3u) == 0) ff1_st32(ns + 16u * j + 4u * L.c, e);
+                if ((li & 3u) == 0) fpe_st32(ns + 16u * j + 4u * L.c, e);
             }
-            FF1_PHASE();
-            ff1_str<W>(ns, d, radix, recip, cd, m, li);
-            FF1_PHASE();
-            if (li == 0) ff1_add(xa, cd, m, radix, dec);
-            FF1_PHASE();
+            FPE_PHASE();
+            const auto s16 = [ns](u32 s) { return fpe_ld8(ns + 2u * s) << 8 | fpe_ld8(ns + 2u * s + 1u); };
+            fpe_str<W>(d / 2u, W, s16, radix, recip, cd, m, li);       /* S = the first d bytes at ns, a big-endian number */
+            FPE_PHASE();
+            if (li == 0) fpe_add<true>(xa, cd, m, radix, dec);
+            FPE_PHASE();
         }
 
-        if (live && good) {
-            unsigned char *dst = out + rec * len;
-            for (u32 i = li; i < len; i += W) dst[i] = (unsigned char)ff1_ld8(AT + 256u + ff1_ld8(xat + i));
-        }
+        if (live && good) fpe_store<W>(AT, out + rec * len, len, xat, li);
         row_verdict<true>(live && li == 0, verdicts, rec, good, bad);
-        FF1_PHASE();
+        FPE_PHASE();
     }
 }
 
@@ -244,10 +180,10 @@ static int launch_ff1(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *k,
     if (e) return e;
     const u64 n = nrec ? nrec : 1;
     if (p.arrangement == UAES_FF1_WAVE)
-        return uaesk_launch(k_ff1<NR, 64u>, p.grid, p.steps, UAES_LDS_ROW + FF1_ALPHA + FF1_SLOT((unsigned)UAES_FF1_MAX, 64u), st,
+        return uaesk_launch(k_ff1<NR, 64u>, p.grid, p.steps, UAES_LDS_ROW + FPE_ALPHA + FF1_SLOT((unsigned)UAES_FF1_MAX, 64u), st,
                             *k, *tb, *q, decrypt, n, tweaks, in, out, verdicts, bad);
     return uaesk_launch(k_ff1<NR, 16u>, p.grid, p.steps,
-                        UAES_LDS_ROW4 + FF1_ALPHA + (p.steps / 16u) * FF1_SLOT((unsigned)UAES_FF1_BATCH_MAX, 16u), st,
+                        UAES_LDS_ROW4 + FPE_ALPHA + (p.steps / 16u) * FF1_SLOT((unsigned)UAES_FF1_BATCH_MAX, 16u), st,
                         *k, *tb, *q, decrypt, n, tweaks, in, out, verdicts, bad);
 }
 

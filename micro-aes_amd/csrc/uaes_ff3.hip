@@ -19,13 +19,8 @@
  *   NUM       below 2^96 (radix^m <= 2^96 is what maxlen means): three 32-bit words that EVERY lane of the row
  *             computes for itself by Horner's rule over the numerals in LDS (the same address in sixteen lanes is one
  *             broadcast read); a lane then simply picks the column word of the block it owns.  No communication.
- *   STR_m(y)  ff1_str's systolic pipeline: the digits are bytes in LDS, least significant first, a run of
- *             ceil(m / 16) per lane.  Step s (16 bits of y, most significant first) is D = D * 65536 + word in
- *             radix-radix digits; lane l does step s in iteration s + l, taking as carry-in what lane l - 1 carried out of
- *             the same step one iteration earlier, so the loop is 8 + (lanes that hold digits) - 1 iterations.  The
- *             carry out of digit m - 1 is dropped: the reduction modulo radix^m.  A digit step divides by the radix
- *             with a reciprocal (radix <= 256, the dividend below 2^25: the estimate is at most one too large, and is
- *             corrected).
+ *   STR_m(y)  fpe_str (uaes_fpe.hip.h) over the 8 16-bit words of y, through the lanes that hold digits only: the
+ *             loop is 8 + (those lanes) - 1 iterations.
  *   the sum   m digit steps on lane 0.
  * How this is spread over the lanes decides speed only.
  *
@@ -39,35 +34,24 @@
  * scratch, no spills (8 waves per SIMD by registers).  LDS is dynamic: 151 552 bytes at 1024 threads (row4 tables and
  * round keys 131 328, alphabet 512, 64 slots of 308), 136 768 at 256 threads -- one workgroup per CU either way, so
  * four waves per SIMD in the large shape and one in the small.  Rates (profiles/ff3_rate.md, tools/ff3_rate.py): 2^20
- * 16-digit decimal records in 2.64 ms = 3.97e8 records/s, the FF1 batch of the same shape 5.02 ms in the same run.
+ * 16-digit decimal records in 2.64 ms = 3.97e8 records/s, the FF1 batch of the same shape 5.04 ms in the same run.
  */
 #include <hip/hip_runtime.h>
 #include <string.h>
-#include "uaes_aes.hip.h"
+#include "uaes_fpe.hip.h"
 #include "uaes_device.h"
 #include "uaes_plan.h"
 
 extern "C" unsigned uaesh_ff1_minlen(unsigned radix);       /* uaes_host.c */
 extern "C" size_t uaesh_ff3_maxlen(unsigned radix);
 
-#define FF3_ALPHA   512u                                    /* inv[256] | fwd[256] behind the round keys */
 #define FF3_N       192u                                    /* maxlen(2): the longest text */
 #define FF3_HALF    (FF3_N / 2u)
 #define FF3_SLOT    (FF3_N + 16u + FF3_HALF + 4u)           /* + 4: neighbouring slots start on different banks */
-#define FF3_ROOM    (160u * 1024u - UAES_LDS_ROW4 - FF3_ALPHA)
+#define FF3_ROOM    (160u * 1024u - UAES_LDS_ROW4 - FPE_ALPHA)
 
 static_assert((UAES_WG / 16u) * FF3_SLOT <= FF3_ROOM, "64 records share a workgroup");
-static_assert(FF3_N % 4u == 0 && FF3_SLOT % 4u == 0 && (UAES_LDS_ROW4 + FF3_ALPHA) % 4u == 0, "the block is word aligned");
-
-typedef __attribute__((address_space(3))) unsigned char lds_u8;
-typedef __attribute__((address_space(3))) u32 lds_u32;
-
-__device__ __forceinline__ u32 ff3_ld8(u32 a) { return *(lds_u8 *)(uintptr_t)a; }
-__device__ __forceinline__ void ff3_st8(u32 a, u32 v) { *(lds_u8 *)(uintptr_t)a = (unsigned char)v; }
-__device__ __forceinline__ void ff3_st32(u32 a, u32 v) { *(lds_u32 *)(uintptr_t)a = v; }
-
-/* between two phases: what the wave's lanes stored is what its lanes read next */
-#define FF3_PHASE() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
+static_assert(FF3_N % 4u == 0 && FF3_SLOT % 4u == 0 && (UAES_LDS_ROW4 + FPE_ALPHA) % 4u == 0, "the block is word aligned");
 
 /* NUM_radix of the n numerals at LDS address src, numeral 0 the least significant, modulo 2^96 (a valid half is below
  * it): n[0] the least significant word.  Every lane computes all of it. */
@@ -75,49 +59,11 @@ __device__ __forceinline__ void ff3_num(u32 src, u32 n, u32 radix, u32 (&w)[3])
 {
     w[0] = w[1] = w[2] = 0;
     for (u32 k = n; k-- > 0u;) {
-        const u64 t0 = (u64)w[0] * radix + ff3_ld8(src + k);
+        const u64 t0 = (u64)w[0] * radix + fpe_ld8(src + k);
         const u64 t1 = (u64)w[1] * radix + (u32)(t0 >> 32);
         w[0] = (u32)t0;
         w[1] = (u32)t1;
         w[2] = w[2] * radix + (u32)(t1 >> 32);
-    }
-}
-
-/* the 16 bytes at blk, a little-endian number, modulo radix^m, as m digits at cd, least significant first */
-__device__ __forceinline__ void ff3_str(u32 blk, u32 radix, u32 recip, u32 cd, u32 m, u32 li)
-{
-    const u32 per = (m + 15u) / 16u, lo = li * per;
-    const u32 cnt = lo < m ? (m - lo < per ? m - lo : per) : 0u;
-    const u32 mine = cd + lo, lanes = (m + per - 1u) / per;         /* lanes that hold digits: the pipeline's depth */
-    for (u32 k = 0; k < cnt; ++k) ff3_st8(mine + k, 0u);
-    u32 cout = 0;
-    for (u32 it = 0; it < 8u + lanes - 1u; ++it) {
-        u32 cin = (u32)__shfl_up((int)cout, 1, 16);
-        if (li == 0) cin = it < 8u ? (ff3_ld8(blk + 15u - 2u * it) << 8) | ff3_ld8(blk + 14u - 2u * it) : 0u;
-        cout = 0;
-        if ((int)(it - li) < 8) {                           /* before its first step a lane divides zeros */
-            u32 x = cin;                                    /* below 2^17 */
-            for (u32 k = 0; k < cnt; ++k) {
-                x += ff3_ld8(mine + k) << 16;
-                u32 q = __umulhi(x, recip), r = x - q * radix;
-                if ((int)r < 0) { --q; r += radix; }
-                ff3_st8(mine + k, r);
-                x = q;
-            }
-            cout = x;
-        }
-    }
-}
-
-/* X[xa .. xa + m) += / -= the digits at cd, modulo radix^m, both least significant first; one lane */
-__device__ __forceinline__ void ff3_add(u32 xa, u32 cd, u32 m, u32 radix, bool dec)
-{
-    int carry = 0;
-    for (u32 p = 0; p < m; ++p) {
-        int t = (int)ff3_ld8(xa + p) + (dec ? -(int)ff3_ld8(cd + p) - carry : (int)ff3_ld8(cd + p) + carry);
-        carry = dec ? t < 0 : t >= (int)radix;
-        if (carry) t += dec ? (int)radix : -(int)radix;
-        ff3_st8(xa + p, (u32)t);
     }
 }
 
@@ -130,11 +76,11 @@ __global__ __launch_bounds__(UAES_WG) void k_ff3(uaesk_rk rk, uaesk_tables tb, u
                                                  unsigned char *out, unsigned char *verdicts, int *bad)
 {
     constexpr u32 AT = UAES_LDS_ROW4;
-    for (u32 i = threadIdx.x; i < FF3_ALPHA; i += blockDim.x) ff3_st8(AT + i, i < 256u ? q.inv[i] : q.fwd[i - 256u]);
+    fpe_fill_alphabet(AT, q);
     row4_fill_tables(tb.te0, rk);                           /* ends in a barrier */
     const RowLane<NR> L = row4_lane<NR>();
     const u32 grp = threadIdx.x / 16u, li = threadIdx.x % 16u, groups = blockDim.x / 16u;
-    const u32 xat = AT + FF3_ALPHA + grp * FF3_SLOT, blk = xat + FF3_N, cd = blk + 16u;
+    const u32 xat = AT + FPE_ALPHA + grp * FF3_SLOT, blk = xat + FF3_N, cd = blk + 16u;
     const u32 radix = q.radix, len = q.len < FF3_N ? q.len : FF3_N, u = (len + 1u) / 2u, v = len - u;
     const u32 recip = (u32)((0x100000000ull + radix - 1u) / radix);
     const bool dec = decrypt != 0;
@@ -143,18 +89,12 @@ __global__ __launch_bounds__(UAES_WG) void k_ff3(uaesk_rk rk, uaesk_tables tb, u
         const bool live = base + grp < nrec;
         const u64 rec = live ? base + grp : 0;              /* a group without a record redoes record 0 and writes nothing */
         const unsigned char *src = in + rec * len, *tw = tweaks + rec * q.tweak_stride;
-        bool foreign = false;
-        for (u32 i = li; i < len; i += 16u) {
-            const u32 dg = ff3_ld8(AT + src[i]);
-            foreign |= dg >= radix;
-            ff3_st8(xat + i, dg);
-        }
-        const bool good = !row_any(foreign);
+        const bool good = !row_any(fpe_load<16u>(AT, src, len, radix, xat, li));
         /* bytes 12..15 of the block: W reversed */
         const u32 t3 = tw[3];
         const u32 wr = ((t3 << 4) & 0xffu) | (u32)tw[6] << 8 | (u32)tw[5] << 16 | (u32)tw[4] << 24;
         const u32 wl = (t3 & 0xf0u) | (u32)tw[2] << 8 | (u32)tw[1] << 16 | (u32)tw[0] << 24;
-        FF3_PHASE();
+        FPE_PHASE();
 
         for (u32 step = 0; step < 8u; ++step) {
             const u32 round = dec ? 7u - step : step, odd = round & 1u;
@@ -163,20 +103,19 @@ __global__ __launch_bounds__(UAES_WG) void k_ff3(uaesk_rk rk, uaesk_tables tb, u
             ff3_num(xb, n, radix, num);
             const u32 word = L.c == 0u ? num[0] : L.c == 1u ? num[1] : L.c == 2u ? num[2] : (odd ? wl : wr) ^ round;
             const u32 y = row_encrypt<NR>(word, L);
-            if ((li & 3u) == 0) ff3_st32(blk + 4u * L.c, y);
-            FF3_PHASE();
-            ff3_str(blk, radix, recip, cd, m, li);
-            FF3_PHASE();
-            if (li == 0) ff3_add(xa, cd, m, radix, dec);
-            FF3_PHASE();
+            if ((li & 3u) == 0) fpe_st32(blk + 4u * L.c, y);
+            FPE_PHASE();
+            const u32 per = (m + 15u) / 16u;                 /* y = the 16 bytes at blk, a little-endian number */
+            const auto y16 = [blk](u32 s) { return fpe_ld8(blk + 15u - 2u * s) << 8 | fpe_ld8(blk + 14u - 2u * s); };
+            fpe_str<16u>(8u, (m + per - 1u) / per, y16, radix, recip, cd, m, li);
+            FPE_PHASE();
+            if (li == 0) fpe_add<false>(xa, cd, m, radix, dec);
+            FPE_PHASE();
         }
 
-        if (live && good) {
-            unsigned char *dst = out + rec * len;
-            for (u32 i = li; i < len; i += 16u) dst[i] = (unsigned char)ff3_ld8(AT + 256u + ff3_ld8(xat + i));
-        }
+        if (live && good) fpe_store<16u>(AT, out + rec * len, len, xat, li);
         row_verdict<true>(live && li == 0, verdicts, rec, good, bad);
-        FF3_PHASE();
+        FPE_PHASE();
     }
 }
 
@@ -212,7 +151,7 @@ static int launch_ff3(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *k,
     uaes_plan p;
     const int e = plan_ff3(decrypt != 0, q->radix, q->len, nrec, &p);
     if (e) return e;
-    return uaesk_launch(k_ff3<NR>, p.grid, p.steps, UAES_LDS_ROW4 + FF3_ALPHA + (p.steps / 16u) * FF3_SLOT, st,
+    return uaesk_launch(k_ff3<NR>, p.grid, p.steps, UAES_LDS_ROW4 + FPE_ALPHA + (p.steps / 16u) * FF3_SLOT, st,
                         *k, *tb, *q, decrypt, nrec ? nrec : 1, tweaks, in, out, verdicts, bad);
 }
 

@@ -1055,6 +1055,22 @@ size_t uaesh_ff1_b(unsigned radix, size_t v)
     return (bits + 7) / 8;
 }
 
+/* The alphabet of FF1 and FF3-1, radix = 2..256 distinct bytes (NULL: the digit values themselves): inv = byte -> digit
+ * value, fwd = digit value -> byte.  A byte that is no numeral keeps inv 0xFF, which is >= radix unless every byte is a
+ * numeral.  Returns -1, or the byte that occurs twice (its first occurrence is a digit below 0xFF: not the last). */
+int uaesh_fpe_alphabet(unsigned radix, const uint8_t *alphabet, uint8_t inv[256], uint8_t fwd[256])
+{
+    unsigned i;
+    memset(inv, 0xFF, 256);
+    for (i = 0; i < radix; ++i) {
+        const uint8_t a = alphabet ? alphabet[i] : (uint8_t)i;
+        if (inv[a] != 0xFF) return a;
+        inv[a] = (uint8_t)i;
+        fwd[i] = a;
+    }
+    return -1;
+}
+
 #define FF1_MAX   4096u
 #define FF1_HALF  (FF1_MAX / 2)
 
@@ -1088,23 +1104,16 @@ static void ff1_str(const uint8_t *num, size_t d, unsigned radix, uint8_t *s, si
 int uaesh_ff1(const uaesh_key *k, int decrypt, unsigned radix, const uint8_t *alphabet,
               const uint8_t *tweak, size_t tweak_len, const uint8_t *in, size_t len, uint8_t *out)
 {
-    uint8_t x[FF1_MAX], y[FF1_HALF], q[FF1_HALF + 64], inv[256], seen[256], p[16], r[16], blk[16];
+    uint8_t x[FF1_MAX], y[FF1_HALF], q[FF1_HALF + 64], inv[256], fwd[256], p[16], r[16], blk[16];
     uint32_t limb[FF1_HALF / 4 + 1];
     const size_t u = len / 2, v = len - u, tfull = tweak_len & ~(size_t)15, trem = tweak_len & 15;
     size_t b, d, z, i, j, tail;
     int round, step;
     if (radix < 2 || radix > 256) return -2;
     if (len < uaesh_ff1_minlen(radix) || len > FF1_MAX || (uint64_t)tweak_len >> 32) return 1;
-    memset(seen, 0, sizeof seen);
-    memset(inv, 0, sizeof inv);
-    for (i = 0; i < radix; ++i) {
-        const uint8_t a = alphabet ? alphabet[i] : (uint8_t)i;
-        if (seen[a]) return -2;
-        seen[a] = 1;
-        inv[a] = (uint8_t)i;
-    }
+    if (uaesh_fpe_alphabet(radix, alphabet, inv, fwd) >= 0) return -2;
     for (i = 0; i < len; ++i) {                               /* every numeral is looked up before anything is written */
-        if (!seen[in[i]]) return decrypt ? 0x1D : 0x1E;
+        if (inv[in[i]] >= radix) return decrypt ? 0x1D : 0x1E;
         x[i] = inv[in[i]];
     }
     b = uaesh_ff1_b(radix, v);
@@ -1150,7 +1159,7 @@ int uaesh_ff1(const uaesh_key *k, int decrypt, unsigned radix, const uint8_t *al
                 for (i = m, c = 1; i--; c /= radix) { c += radix - 1 + a[i] - y[i]; a[i] = (uint8_t)(c % radix); }
         }
     }
-    for (i = 0; i < len; ++i) out[i] = alphabet ? alphabet[x[i]] : x[i];
+    for (i = 0; i < len; ++i) out[i] = fwd[x[i]];
     memset(x, 0, sizeof x); memset(y, 0, sizeof y); memset(q, 0, sizeof q);
     memset(limb, 0, sizeof limb); memset(p, 0, sizeof p); memset(r, 0, sizeof r);
     return 0;
@@ -1177,23 +1186,16 @@ size_t uaesh_ff3_maxlen(unsigned radix)
 int uaesh_ff3(const uaesh_key *k, int decrypt, unsigned radix, const uint8_t *alphabet, const uint8_t *tweak,
               const uint8_t *in, size_t len, uint8_t *out)
 {
-    uint8_t inv[256], seen[256], blk[16], w[2][4];
+    uint8_t inv[256], fwd[256], blk[16], w[2][4];
     const size_t u = (len + 1) / 2;
     u128 num[2] = { 0, 0 }, mod[2] = { 1, 1 };
     size_t i;
     int step;
     if (radix < 2 || radix > 256) return -2;
     if (len < uaesh_ff1_minlen(radix) || len > uaesh_ff3_maxlen(radix)) return 1;
-    memset(seen, 0, sizeof seen);
-    memset(inv, 0, sizeof inv);
-    for (i = 0; i < radix; ++i) {
-        const uint8_t a = alphabet ? alphabet[i] : (uint8_t)i;
-        if (seen[a]) return -2;
-        seen[a] = 1;
-        inv[a] = (uint8_t)i;
-    }
+    if (uaesh_fpe_alphabet(radix, alphabet, inv, fwd) >= 0) return -2;
     for (i = 0; i < len; ++i)                                 /* every numeral is looked up before anything is written */
-        if (!seen[in[i]]) return decrypt ? 0x1D : 0x1E;
+        if (inv[in[i]] >= radix) return decrypt ? 0x1D : 0x1E;
     for (i = u; i-- > 0;) { num[0] = num[0] * radix + inv[in[i]]; mod[0] *= radix; }
     for (i = len; i-- > u;) { num[1] = num[1] * radix + inv[in[i]]; mod[1] *= radix; }
     w[0][0] = (uint8_t)(tweak[3] << 4); w[0][1] = tweak[6]; w[0][2] = tweak[5]; w[0][3] = tweak[4];     /* TR reversed */
@@ -1213,7 +1215,7 @@ int uaesh_ff3(const uaesh_key *k, int decrypt, unsigned radix, const uint8_t *al
         const int h = i >= u;
         const unsigned dgt = (unsigned)(num[h] % radix);
         num[h] /= radix;
-        out[i] = alphabet ? alphabet[dgt] : (uint8_t)dgt;
+        out[i] = fwd[dgt];
     }
     memset(blk, 0, sizeof blk); memset(w, 0, sizeof w);
     num[0] = num[1] = 0;

@@ -70,6 +70,7 @@ int  uaesh_kw_unwrap(const uaesh_key *k, const uint8_t *wrapped, size_t wrap_len
  * outside 2..256, a repeated alphabet byte); 0x1E / 0x1D (encrypt / decrypt: a byte that is no numeral).  Nothing is
  * written unless it returns 0.  uaesh_ff1_b = the b of the specification for a half of v numerals, exact integers. */
 unsigned uaesh_ff1_minlen(unsigned radix);
+int  uaesh_fpe_alphabet(unsigned radix, const uint8_t *alphabet, uint8_t inv[256], uint8_t fwd[256]);   /* uaes_host.c */
 size_t   uaesh_ff1_b(unsigned radix, size_t v);
 int  uaesh_ff1(const uaesh_key *k, int decrypt, unsigned radix, const uint8_t *alphabet, const uint8_t *tweak,
                size_t tweak_len, const uint8_t *in, size_t len, uint8_t *out);                               /* :2091-2147, :2267-2314 */

@@ -5,6 +5,7 @@ whose AES is the oracle's ECB and whose b is exact.  The model is the checker fo
 which the reference's floating-point b is one too large (v log2(radix) a multiple of 8 at 136 bits or more)."""
 import ctypes as C
 import os
+import random
 
 from tests import refbuilt
 
@@ -126,6 +127,24 @@ def model_text(orc, key, tweak, text, alphabet, decrypt=False):
     idx = {c: i for i, c in enumerate(alphabet)}
     out = model(orc, key, tweak, [idx[c] for c in bytes(text)], len(alphabet), decrypt)
     return bytes(alphabet[d] for d in out)
+
+
+_wave = {}
+
+
+def wave_cases(orc, batch, top):
+    """the one-text shapes that only the wave form takes, at the ends of the radix range: twelve of (radix, key, tweak,
+    digits, the model's answer), one key size per case; made once for the GPU test and its host twin"""
+    if (batch, top) not in _wave:
+        rng = random.Random(64)
+        cases = []
+        for radix in (2, 255, 256):
+            for n in (batch + 1, 1000, top - 1, top):
+                key, tweak = rng.randbytes(rng.choice([16, 24, 32])), rng.randbytes(rng.choice([0, 3, 16, 21]))
+                digits = bytes(rng.randrange(radix) for _ in range(n))
+                cases.append((radix, key, tweak, digits, bytes(model(orc, key, tweak, list(digits), radix))))
+        _wave[(batch, top)] = tuple(cases)
+    return _wave[(batch, top)]
 
 
 def vectors(golden_dir):

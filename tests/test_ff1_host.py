@@ -114,6 +114,19 @@ def test_radices_against_the_model(host_forced, orc, radix):
         assert uaes.AES_FPE_decrypt(key, tweak, ct, alphabet) == (0, text), case
 
 
+def test_wave_shapes_at_the_ends_of_the_radix_range(host_forced, orc):
+    """the twelve cases of tests/test_gpu_ff1.py's wave-form test through the host path, which shares no code with the
+    kernel: the model's answers are confirmed here"""
+    lens = [n for n in range(6, 8200) if uaes.ff1_plan(n) is not None]
+    batch, top = max(n for n in lens if uaes.ff1_plan(n)[0] == "ff1.batch"), lens[-1]
+    cases = R.wave_cases(orc, batch, top)
+    assert len(cases) == 12 and sorted(set(len(c[3]) for c in cases)) == [batch + 1, 1000, top - 1, top]
+    for radix, key, tweak, digits, want in cases:
+        case = (radix, len(digits), key.hex(), tweak.hex())
+        assert uaes.AES_FPE_encrypt(key, tweak, digits, None, radix) == (0, want), case
+        assert uaes.AES_FPE_decrypt(key, tweak, want, None, radix) == (0, digits), case
+
+
 def test_minimum_lengths_are_the_references():
     """radix^minlen >= 1 000 000, exact; equal to micro_fpe.h's MINLEN = 1 + (int)(19.931561 / log2(radix))"""
     import math

@@ -136,6 +136,18 @@ def test_radices_against_the_model(orc, radix):
         assert uaes.AES_FPE_decrypt(key, tweak, ct, alphabet) == (0, text), case
 
 
+def test_wave_form_at_the_ends_of_the_radix_range(orc):
+    """k_ff1<NR,64>: 64 lanes and digit runs of up to 32 a lane, which the vector file reaches up to radix 72 only"""
+    batch, top = plan_limits()
+    cases = R.wave_cases(orc, batch, top)
+    assert len(cases) == 12
+    for radix, key, tweak, digits, want in cases:
+        case = (radix, len(digits), key.hex(), tweak.hex())
+        assert uaes.ff1_plan(len(digits), radix=radix)[0] == "ff1.wave", case
+        assert uaes.AES_FPE_encrypt(key, tweak, digits, None, radix) == (0, want), case
+        assert uaes.AES_FPE_decrypt(key, tweak, want, None, radix) == (0, digits), case
+
+
 # ---- batches ----------------------------------------------------------------------------------------------------------
 BATCH_KEY = bytes(range(0x40, 0x50))
 SHARED_TWEAK = bytes(range(11))
