@@ -951,6 +951,15 @@ const char *uaes_debug_plan_gcm_multikey_batch(int dir, size_t len, size_t nmsg,
  * (0: one workgroup hashes all of it -- short, or not aligned; INT_MAX from 32 GiB on).  NULL for a dir other than 0 / 1.  Works without a
  * device (a 256-CU MI355X).  tests/test_gpu_ocb.py finds the first text of every run length by walking this. */
 const char *uaes_debug_plan_ocb(int dir, size_t len, size_t aad_len, int aad_aligned, int out[5]);
+/* The launch shape of XTS (csrc/uaes_plan.h, uaesk_plan_xts_shape): sector_bytes = bytes per data unit, nsectors = units,
+ * explicit_tweak = whether the call gives a 16-byte tweak (uaes_xts_encrypt / _decrypt) and not unit numbers.  Returns
+ * "xts.small", "xts.packed" or "xts.bulk" as uaes_debug_plan does; out (may be NULL) receives { threads per workgroup,
+ * workgroups, chunks_per_sector, nmain, chunks in all, serial, aligned, all-full } of the call's main kernel: the
+ * 256-block chunks of a unit (the one with the first block of a stealing pair included), the chunks the kernel's main
+ * loop takes a chunk per wave and all chunks (the rest goes by quarters), and whether one thread walks a unit's chunk
+ * tweaks, every block lies at a multiple of 16 bytes, every chunk is whole.  NULL for a unit below 16 bytes or no unit.
+ * Works without a device (a 256-CU MI355X).  tests/test_gpu_xts.py takes its unit counts from this. */
+const char *uaes_debug_plan_xts(size_t sector_bytes, size_t nsectors, int explicit_tweak, uint64_t out[8]);
 /* The planner of the OCB batches (csrc/uaes_plan.h): dir 0 encrypt / 1 decrypt; len = bytes per record, nmsg = records;
  * out (may be NULL) receives { launches, workgroups, threads per workgroup }.  Returns "ocb.batch" (the one
  * arrangement: sixteen lanes per record, the same grid and threads as "ccm.batch" for the same number of records), or

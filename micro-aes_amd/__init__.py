@@ -18,6 +18,7 @@ import it through the alias module at the repo root::
 
     import micro_aes_amd as uaes
 """
+import collections
 import ctypes as C
 import os
 import subprocess
@@ -45,7 +46,7 @@ EXPORTS = [
     "uaes_cmac", "uaes_ccm_encrypt", "uaes_ccm_decrypt", "uaes_gcmsiv_encrypt", "uaes_gcmsiv_decrypt",
     "uaes_gcmsiv_encrypt_batch", "uaes_gcmsiv_decrypt_batch", "uaes_debug_plan_gcmsiv_batch",
     "uaes_gcm_multikey_encrypt_batch", "uaes_gcm_multikey_decrypt_batch", "uaes_debug_plan_gcm_multikey_batch",
-    "uaes_ocb_encrypt", "uaes_ocb_decrypt", "uaes_ocb_dev", "uaes_debug_plan_ocb",
+    "uaes_ocb_encrypt", "uaes_ocb_decrypt", "uaes_ocb_dev", "uaes_debug_plan_ocb", "uaes_debug_plan_xts",
     "uaes_poly1305", "uaes_poly1305_dev", "uaes_poly1305_batch", "uaes_debug_plan_poly1305",
     "uaes_eax_encrypt", "uaes_eax_decrypt", "uaes_siv_encrypt", "uaes_siv_decrypt",
     "uaes_eax_encrypt_batch", "uaes_eax_decrypt_batch", "uaes_siv_encrypt_batch", "uaes_siv_decrypt_batch",
@@ -197,6 +198,8 @@ def engine():
     L.uaes_debug_plan_kw.restype = C.c_char_p
     L.uaes_debug_plan_ocb.argtypes = [i, sz, sz, i, C.POINTER(C.c_int)]
     L.uaes_debug_plan_ocb.restype = C.c_char_p
+    L.uaes_debug_plan_xts.argtypes = [sz, sz, i, C.POINTER(C.c_uint64)]
+    L.uaes_debug_plan_xts.restype = C.c_char_p
     for n in ("uaes_ff1_encrypt", "uaes_ff1_decrypt"):
         getattr(L, n).argtypes = [i, vp, C.c_uint, vp, vp, sz, vp, sz, vp]
     for n in ("uaes_ff1_encrypt_batch", "uaes_ff1_decrypt_batch"):
@@ -280,7 +283,7 @@ def engine():
         if n not in ("uaes_last_error", "uaes_version", "uaes_gcm_key_free", "uaes_gcm_stream_abort", "uaes_debug_gather_stats", "uaes_debug_gcm_look",
                      "uaes_debug_arrangement_name", "uaes_debug_plan_disable", "uaes_debug_plan_poly1305",
                      "uaes_debug_plan_eax_siv", "uaes_debug_plan_chain", "uaes_debug_plan_kw", "uaes_debug_plan_ff1",
-                     "uaes_debug_plan_ff3", "uaes_ff3_maxlen", "uaes_debug_plan_gcmsiv_batch", "uaes_debug_plan_ocb",
+                     "uaes_debug_plan_ff3", "uaes_ff3_maxlen", "uaes_debug_plan_gcmsiv_batch", "uaes_debug_plan_ocb", "uaes_debug_plan_xts",
                      "uaes_debug_plan_ocb_batch", "uaes_debug_plan_gcm_multikey_batch", "uaes_debug_plan_cipher_batch"):
             getattr(L, n).restype = i
     _lib = L
@@ -1342,6 +1345,21 @@ def plan_ocb(length, aad_len=0, decrypt=False, aad_aligned=True):
     if name is None:
         raise ValueError("no OCB plan for these arguments")
     return tuple(out) if name == b"ocb.runs" else None
+
+
+XtsPlan = collections.namedtuple("XtsPlan", "name threads grid cps nmain chunks serial aligned allfull")
+
+
+def xts_plan(sector_bytes, nsectors=1, explicit_tweak=False):
+    """The launch shape of an XTS call (uaes_debug_plan_xts): the arrangement's name, threads per workgroup and workgroups
+    of its main kernel, the 256-block chunks per unit, the chunks of the kernel's main loop, the chunks in all (the rest
+    goes by quarters), and whether the unit's chunk tweaks are walked by one thread, every block is 16-byte aligned and
+    every chunk is whole."""
+    out = (C.c_uint64 * 8)()
+    name = engine().uaes_debug_plan_xts(sector_bytes, nsectors, int(bool(explicit_tweak)), out)
+    if name is None:
+        raise ValueError("no XTS plan for these arguments")
+    return XtsPlan(name.decode(), *[int(v) for v in out[:5]], *[bool(v) for v in out[5:]])
 
 
 def arrangement_id(name):

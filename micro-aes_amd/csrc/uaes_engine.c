@@ -1535,6 +1535,16 @@ const char *uaes_debug_plan_ocb(int dir, size_t len, size_t aad_len, int aad_ali
     }
     return uaesk_arrangement_name(p.arrangement);
 }
+const char *uaes_debug_plan_xts(size_t sector_bytes, size_t nsectors, int explicit_tweak, uint64_t out[8])
+{
+    uaes_plan p;
+    uint64_t shape[8];
+    memset(&p, 0, sizeof p);
+    if (uaesk_plan_xts_shape(sector_bytes, nsectors, explicit_tweak, shape)) return NULL;
+    if (uaesk_plan(UAES_PLAN_XTS, 0, sector_bytes, nsectors, explicit_tweak ? 2u : 0u, &p)) return NULL;
+    if (out) memcpy(out, shape, sizeof shape);
+    return uaesk_arrangement_name(p.arrangement);
+}
 void uaes_debug_plan_disable(unsigned mask) { uaesk_plan_disable(mask); }
 
 int uaes_debug_live_key_schedules(void) { return __atomic_load_n(&g_live_schedules, __ATOMIC_RELAXED); }

@@ -194,4 +194,22 @@ UAES_HD Tw tw_mul_a256(Tw t, uint32_t l)
     return t;
 }
 
+/* Host only: lo[i], hi[i] = alpha^(2^(14+i)), i < n -- the constants k_xts_expand and k_xts_small multiply a unit's
+ * tweak by (one per set bit of the number of a group of 64 chunks, uaes_kernels.hip).  Repeated squaring from
+ * alpha^(2^14) = 256 word shifts of 1 (checked against Python integers in tests/test_gf_helpers.py). */
+static inline void tw_pow_table(uint64_t *lo, uint64_t *hi, int n)
+{
+    Tw e = { 1, 0 };
+    for (int i = 0; i < 256; ++i) e = tw_mul_pow64(e);
+    for (int i = 0; i < n; ++i) {
+        lo[i] = e.lo; hi[i] = e.hi;
+        Tw a = e, acc = { 0, 0 };
+        for (int b = 0; b < 128; ++b) {          /* e * e, bit-serial */
+            if (((b < 64 ? e.lo : e.hi) >> (b & 63)) & 1) { acc.lo ^= a.lo; acc.hi ^= a.hi; }
+            a = tw_mul_pow(a, 1);
+        }
+        e = acc;
+    }
+}
+
 #endif

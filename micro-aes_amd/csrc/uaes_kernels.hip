@@ -1024,24 +1024,12 @@ extern "C" int uaesk_ctr_xcrypt(void *stream, const uaesk_tables *tb, int nr, co
 
 #define XTS_SERIAL_CPS 128u      /* up to this many chunks per unit the pre-pass thread walks them itself */
 
-/* alpha^(2^(14+i)), i < XTS_POW_N: repeated squaring from alpha^(2^14) = 256 word shifts of 1 */
+/* alpha^(2^(14+i)), i < XTS_POW_N: made once on the host (tw_pow_table, uaes_gf.h) */
 static const XtsPow *xts_pow_table()
 {
     static XtsPow tab;
     static std::once_flag once;
-    std::call_once(once, [] {
-        Tw e = { 1, 0 };
-        for (int i = 0; i < 256; ++i) e = tw_mul_pow64(e);
-        for (int i = 0; i < XTS_POW_N; ++i) {
-            tab.lo[i] = e.lo; tab.hi[i] = e.hi;
-            Tw a = e, acc = { 0, 0 };
-            for (int b = 0; b < 128; ++b) {          /* e * e, bit-serial */
-                if (((b < 64 ? e.lo : e.hi) >> (b & 63)) & 1) { acc.lo ^= a.lo; acc.hi ^= a.hi; }
-                a = tw_mul_pow(a, 1);
-            }
-            e = acc;
-        }
-    });
+    std::call_once(once, [] { tw_pow_table(tab.lo, tab.hi, XTS_POW_N); });
     return &tab;
 }
 
@@ -1090,34 +1078,100 @@ static uaes_plan plan_xts(size_t sector_bytes, size_t nsectors, bool explicit_tw
     return p;
 }
 
+/* The launch shape of an XTS call: what plan_xts does not say -- threads per workgroup and workgroups of the main kernel
+ * (k_xts_small or k_xts), the chunks of a unit, the chunks k_xts's two-buffer loop takes (nmain) and the chunks in all
+ * (those behind nmain go by quarters), and which form of k_xts runs.  The one place that decides them: launch_xts
+ * launches what this answers, and uaesk_plan_xts_shape hands the same answer to the tests. */
+struct XtsShape {
+    uaes_plan pl;
+    u64 mb, cps;             /* blocks before the stealing pair and chunks, per unit (xts_geometry) */
+    u32 r;
+    unsigned wg, grid;       /* 0, 0: no main kernel (units of 17..31 bytes are a stealing pair and nothing else) */
+    u64 nmain, all;
+    bool serial, aligned, allfull;
+};
+
+static XtsShape xts_shape(size_t sector_bytes, size_t nsectors, bool explicit_tweak)
+{
+    XtsShape s;
+    xts_geometry(sector_bytes, &s.mb, &s.r, &s.cps);
+    const u64 mb = s.mb, cps = s.cps;
+    s.pl = plan_xts(sector_bytes, nsectors, explicit_tweak);
+    s.serial = cps <= XTS_SERIAL_CPS;
+    /* every block address is a multiple of 16 unless units of ragged size follow one another */
+    s.aligned = sector_bytes % 16 == 0 || nsectors == 1;
+    s.allfull = false;
+    s.wg = 0; s.grid = 0; s.nmain = 0;
+    s.all = (u64)nsectors * cps;
+    if (s.pl.arrangement == UAES_ARR_XTS_SMALL) {
+        /* a workgroup per 1024 blocks (one per lane), as many as half the CUs: a 64 KiB unit runs on four CUs at the
+         * latency of one block */
+        s.wg = UAES_WG; s.grid = s.pl.grid; s.nmain = s.all;
+        return s;
+    }
+    const unsigned cus = uaesk_cus_or_256();
+    /* units shorter than a chunk (whole blocks, a multiple of four): the flat, packed arrangement (k_xts) */
+    if (s.pl.arrangement == UAES_ARR_XTS_PACKED) {
+        const u64 total = (u64)nsectors * mb, nchunks = (total + XTS_CHUNK - 1) / XTS_CHUNK;
+        s.wg = grid_for(nchunks, UAES_WG / 64, cus) * 2 <= cus ? 256u : UAES_WG;
+        s.grid = grid_for(nchunks, s.wg / 64, cus);
+        s.nmain = s.all = nchunks;
+        return s;
+    }
+    if (mb > 0) {
+        const u64 nchunks = (u64)nsectors * ((mb + XTS_CHUNK - 1) / XTS_CHUNK);
+        /* one wave per 256-block chunk: a short text on 16-wave workgroups would sit on a few CUs,
+         * so below half a GPU's worth of chunks the workgroups shrink to 4 waves              */
+        s.wg = grid_for(nchunks, UAES_WG / 64, cus) * 2 <= cus ? 256u : UAES_WG;
+        s.grid = grid_for(nchunks, s.wg / 64, cus);
+        const u64 nwaves = (u64)s.grid * (s.wg / 64);
+        /* the remainder of the last round by quarter chunks when it covers less than 80 % of the waves (k_xts) */
+        const u64 pct = 80;                                   /* (as CTR_TAIL_PCT) */
+        const u64 rounds = nchunks / nwaves, left = nchunks % nwaves;
+        s.nmain = (rounds && left && left * 100 < nwaves * pct) ? rounds * nwaves : nchunks;
+        s.allfull = s.aligned && mb % XTS_CHUNK == 0;         /* every chunk whole */
+    }
+    return s;
+}
+
+/* out = { threads per workgroup, workgroups, chunks_per_sector, nmain, chunks in all, serial, aligned, all-full } of
+ * the call's main kernel (uaes_plan.h).  Returns 0, or a HIP error code for a unit below 16 bytes or no unit. */
+extern "C" int uaesk_plan_xts_shape(size_t sector_bytes, size_t nsectors, int explicit_tweak, uint64_t out[8])
+{
+    if (sector_bytes < 16 || nsectors == 0) return (int)hipErrorInvalidValue;
+    const XtsShape s = xts_shape(sector_bytes, nsectors, explicit_tweak != 0);
+    out[0] = s.wg; out[1] = s.grid; out[2] = s.cps; out[3] = s.nmain; out[4] = s.all;
+    out[5] = s.serial; out[6] = s.aligned; out[7] = s.allfull;
+    return 0;
+}
+
 template <int NR, bool DEC>
 static int launch_xts(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *k1, const uaesk_rk *k2,
                       const uint8_t *tweak16, u64 first_sector, size_t sector_bytes, size_t nsectors,
                       const void *in, void *out, void *scratch)
 {
-    u64 mb, cps; u32 r;
-    xts_geometry(sector_bytes, &mb, &r, &cps);
+    const XtsShape s = xts_shape(sector_bytes, nsectors, tweak16 != nullptr);
+    const u64 mb = s.mb, cps = s.cps;
+    const u32 r = s.r;
     const unsigned lds = DEC ? UAES_LDS_DEC : UAES_LDS_ENC;
     const u32 explicit_tweak = tweak16 != nullptr;
     int rc;
 
     uint4 raw = make_uint4(0, 0, 0, 0);
     if (tweak16) memcpy(&raw, tweak16, 16);
-    const uaes_plan pl = plan_xts(sector_bytes, nsectors, tweak16 != nullptr);
-    if (pl.arrangement == UAES_ARR_XTS_SMALL) {
+    if (s.pl.arrangement == UAES_ARR_XTS_SMALL) {
         uaesk_done done = { nullptr, nullptr, 0 };
         if (!r) done = uaesk_ticket_take();                   /* no stealing kernel behind it: it carries the ticket */
-        /* a workgroup per 1024 blocks (one per lane), as many as half the CUs: a 64 KiB unit runs on four CUs at the
-         * latency of one block.  FEW: several whole-block units numbered from first_sector, never with an explicit
-         * tweak (plan_xts); else one unit */
+        /* FEW: several whole-block units numbered from first_sector, never with an explicit tweak (plan_xts); else
+         * one unit */
         rc = with_bool(nsectors > 1, [&](auto FEW) {
-            return uaesk_launch(k_xts_small<NR, DEC, decltype(FEW)::value>, pl.grid, UAES_WG, XTS_SMALL_LDS, st, *k1, *k2, *tb, raw,
+            return uaesk_launch(k_xts_small<NR, DEC, decltype(FEW)::value>, s.grid, s.wg, XTS_SMALL_LDS, st, *k1, *k2, *tb, raw,
                                 explicit_tweak, first_sector, scratch, cps, mb, in, out, done, *xts_pow_table(), nsectors,
                                 sector_bytes); });
         if (rc || !r) return rc;
         return uaesk_launch(k_xts_cts<NR, DEC>, 1, UAES_WG, lds, st, *k1, *tb, scratch, 1, cps, mb, r, sector_bytes, in, out);
     }
-    const bool serial = cps <= XTS_SERIAL_CPS;
+    const bool serial = s.serial;
     const unsigned cus = uaesk_cus_or_256();
     if (!serial && ((cps + 63) / 64) >> XTS_POW_N) return (int)hipErrorInvalidValue;
     if (nsectors <= 65536)                   /* few units: one-wave workgroups on a plain table (k_xts_tweaks) */
@@ -1132,34 +1186,20 @@ static int launch_xts(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *k1
                           nsectors, cps, scratch);
         if (rc) return rc;
     }
-    /* units shorter than a chunk (whole blocks, a multiple of four): the flat, packed arrangement (k_xts) */
-    if (pl.arrangement == UAES_ARR_XTS_PACKED) {
-        const u64 total = (u64)nsectors * mb, nchunks = (total + XTS_CHUNK - 1) / XTS_CHUNK;
-        const unsigned wg = grid_for(nchunks, UAES_WG / 64, cus) * 2 <= cus ? 256u : UAES_WG;
-        const unsigned xgrid = grid_for(nchunks, wg / 64, cus);
-        const u64 adv = (u64)xgrid * (wg / 64) * XTS_CHUNK;
-        return uaesk_launch(k_xts<NR, DEC, true, true>, xgrid, wg, lds, st, *k1, *tb, scratch, nsectors, mb, total, sector_bytes,
-                            adv / mb, adv % mb, in, out, nchunks, ((1u << 24) + mb - 1) / mb);
+    if (s.pl.arrangement == UAES_ARR_XTS_PACKED) {
+        const u64 total = (u64)nsectors * mb;
+        const u64 adv = (u64)s.grid * (s.wg / 64) * XTS_CHUNK;
+        return uaesk_launch(k_xts<NR, DEC, true, true>, s.grid, s.wg, lds, st, *k1, *tb, scratch, nsectors, mb, total, sector_bytes,
+                            adv / mb, adv % mb, in, out, s.nmain, ((1u << 24) + mb - 1) / mb);
     }
     if (mb > 0) {
-        const u64 nchunks = (u64)nsectors * ((mb + XTS_CHUNK - 1) / XTS_CHUNK);
-        /* one wave per 256-block chunk: a short text on 16-wave workgroups would sit on a few CUs,
-         * so below half a GPU's worth of chunks the workgroups shrink to 4 waves              */
-        const unsigned wg = grid_for(nchunks, UAES_WG / 64, cus) * 2 <= cus ? 256u : UAES_WG;
-        const unsigned xgrid = grid_for(nchunks, wg / 64, cus);
-        const u64 nwaves = (u64)xgrid * (wg / 64), step_q = nwaves / cps, step_r = nwaves % cps;
-        /* the remainder of the last round by quarter chunks when it covers less than 80 % of the waves (k_xts) */
-        const u64 pct = 80;                                   /* (as CTR_TAIL_PCT) */
-        const u64 rounds = nchunks / nwaves, left = nchunks % nwaves;
-        const u64 nmain = (rounds && left && left * 100 < nwaves * pct) ? rounds * nwaves : nchunks;
-        /* every block address is a multiple of 16 unless units of ragged size follow one another */
-        const bool aligned = sector_bytes % 16 == 0 || nsectors == 1;
+        const u64 nwaves = (u64)s.grid * (s.wg / 64), step_q = nwaves / cps, step_r = nwaves % cps;
         auto bulk = [&](auto kern) {
-            return uaesk_launch(kern, xgrid, wg, lds, st, *k1, *tb, scratch, nsectors, cps, mb, sector_bytes, step_q, step_r,
-                                in, out, nmain, 0u);
+            return uaesk_launch(kern, s.grid, s.wg, lds, st, *k1, *tb, scratch, nsectors, cps, mb, sector_bytes, step_q, step_r,
+                                in, out, s.nmain, 0u);
         };
-        rc = aligned && mb % XTS_CHUNK == 0 ? bulk(k_xts<NR, DEC, true, false, true>)       /* every chunk whole: ALLFULL */
-             : aligned ? bulk(k_xts<NR, DEC, true>) : bulk(k_xts<NR, DEC, false>);
+        rc = s.allfull ? bulk(k_xts<NR, DEC, true, false, true>)                            /* every chunk whole: ALLFULL */
+             : s.aligned ? bulk(k_xts<NR, DEC, true>) : bulk(k_xts<NR, DEC, false>);
         if (rc) return rc;
     }
     if (r)

@@ -73,6 +73,9 @@
  * FF1 has uaesk_plan_ff1 (uaes_ff1.hip; uaes_debug_plan_ff1); tests/test_gpu_ff1.py walks it likewise.
  * FF3-1 has uaesk_plan_ff3 (uaes_ff3.hip; uaes_debug_plan_ff3): one row, whose limits depend on the radix.
  * The GCM-SIV batches have uaesk_plan_gcmsiv_batch (uaes_gcmsiv_batch.hip; uaes_debug_plan_gcmsiv_batch): one row.
+ * The XTS rows say which kernels run; the shape they are launched with -- workgroups, the main loop's share of the chunks,
+ * which form of k_xts -- is uaesk_plan_xts_shape (uaes_kernels.hip; uaes_debug_plan_xts), and tests/test_gpu_xts.py takes its
+ * unit counts from it.
  * OCB_RUNS is one row whose launch shape moves with the size: uaesk_plan_ocb_shape (uaes_ocb.hip; uaes_debug_plan_ocb),
  * and tests/test_gpu_ocb.py takes its sizes from walking it.  The OCB batches have uaesk_plan_ocb_batch (uaes_ocb.hip;
  * uaes_debug_plan_ocb_batch): one row, with an id outside enum uaes_arrangement.  So do the multi-key GCM batches:
@@ -156,6 +159,18 @@ const char *uaesk_arrangement_name(int id);
  * workgroup hashes all of it).  Returns 0, or 1 with out untouched where the call is OCB_SMALL's, or a HIP error code
  * for a dir other than 0 / 1.  tests/test_gpu_ocb.py finds the first text of every run length by walking this. */
 int uaesk_plan_ocb_shape(int dir, size_t len, size_t aad_len, int aad_aligned, int out[5]);
+
+/* The XTS rows answer ("xts.bulk", n, 0, 0) and ("xts.packed", 2, 0, 0) at every size; the shape their main kernel is
+ * launched with is uaes_kernels.hip's xts_shape, which launch_xts launches from (uaes_debug_plan_xts).  out = { threads
+ * per workgroup, workgroups, chunks_per_sector, nmain, chunks in all, serial, aligned, all-full }: of k_xts_small for
+ * XTS_SMALL, else of k_xts (0 threads and workgroups where a unit is a stealing pair and nothing else).  A chunk is 256
+ * blocks.  chunks_per_sector counts the chunk that holds the first block of the stealing pair, which is one more than
+ * the chunks with blocks of k_xts's when that block is the first of a chunk.  k_xts takes chunks [0, nmain) a chunk per
+ * wave and [nmain, chunks in all) by quarters (XTS_PACKED numbers the chunks of the whole text, the others unit by
+ * unit); serial: k_xts_tweaks walks a unit's chunk tweaks itself (else k_xts_expand); aligned: every block at a
+ * multiple of 16 bytes; all-full: every chunk has 256 blocks.  Returns 0, or a HIP error code for a unit below 16 bytes
+ * or no unit. */
+int uaesk_plan_xts_shape(size_t sector_bytes, size_t nsectors, int explicit_tweak, uint64_t out[8]);
 
 /* Poly1305-AES: len = bytes of one message; nmsg >= 2 = a batch of nmsg messages of len bytes each (nmsg 0 / 1: the
  * one-message calls).  grid = workgroups of the main kernel, steps = blocks per thread (at most). */

@@ -124,4 +124,39 @@ void gfc_tw_pow(const uint8_t t[16], uint32_t k, uint8_t out[16])
     memcpy(out, &r.lo, 8); memcpy(out + 8, &r.hi, 8);
 }
 
+// the XTS power table as the launcher makes it (tw_pow_table): n constants alpha^(2^(14+i)), 16-byte LE blocks
+void gfc_tw_pow_table(uint8_t *out, int n)
+{
+    std::vector<uint64_t> lo(n), hi(n);
+    tw_pow_table(lo.data(), hi.data(), n);
+    for (int i = 0; i < n; ++i) { memcpy(out + 16 * i, &lo[i], 8); memcpy(out + 16 * i + 8, &hi[i], 8); }
+}
+
+// t * e the way one wave does it (wave_tw_mul, uaes_kernels.hip): lane l contributes t * alpha^l where bit l of e is
+// set and t * alpha^(64 + l) where bit 64 + l is; an XOR butterfly over the 64 lanes leaves the sum in every lane.
+// Returns 1 when all 64 lanes ended with the same value (lane 0's is written to out).
+int gfc_wave_tw_mul(const uint8_t t[16], const uint8_t e[16], uint8_t out[16])
+{
+    Tw x, z[64];
+    uint64_t elo, ehi;
+    memcpy(&x.lo, t, 8); memcpy(&x.hi, t + 8, 8);
+    memcpy(&elo, e, 8); memcpy(&ehi, e + 8, 8);
+    for (uint32_t lane = 0; lane < 64; ++lane) {
+        const Tw xl = tw_mul_pow(x, lane), xh = tw_mul_pow64(xl);
+        Tw v = { 0, 0 };
+        if ((elo >> lane) & 1) v = xl;
+        if ((ehi >> lane) & 1) { v.lo ^= xh.lo; v.hi ^= xh.hi; }
+        z[lane] = v;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        Tw n[64];
+        for (int lane = 0; lane < 64; ++lane) n[lane] = tw_xor(z[lane], z[lane ^ off]);
+        memcpy(z, n, sizeof z);
+    }
+    int same = 1;
+    for (int lane = 1; lane < 64; ++lane) same &= z[lane].lo == z[0].lo && z[lane].hi == z[0].hi;
+    memcpy(out, &z[0].lo, 8); memcpy(out + 8, &z[0].hi, 8);
+    return same;
+}
+
 }

@@ -117,3 +117,67 @@ def test_xts_chunk_tweak_by_sparse_powers(gfc):
             assert int.from_bytes(bytes(o), "little") == cur, l
             for _ in range(256):
                 cur = double(cur)
+
+
+XTS_P = (1 << 128) | 0x87                       # x^128 + x^7 + x^2 + x + 1; bit k of the integer = coefficient of x^k
+
+
+def xts_mul(a, b):
+    """a * b modulo XTS_P on Python integers (the XTS bit order: a block is a 128-bit little-endian integer)"""
+    z = 0
+    while b:
+        if b & 1:
+            z ^= a
+        a <<= 1
+        if a >> 128:
+            a ^= XTS_P
+        b >>= 1
+    return z
+
+
+def xts_alpha_pow(e):
+    """alpha^e by square-and-multiply, alpha = x"""
+    z, base = 1, 2
+    while e:
+        if e & 1:
+            z = xts_mul(z, base)
+        base = xts_mul(base, base)
+        e >>= 1
+    return z
+
+
+def xts_pow_table(gfc, n=40):
+    o = (C.c_uint8 * (16 * n))()
+    gfc.gfc_tw_pow_table(o, n)
+    return [int.from_bytes(bytes(o[16 * i:16 * i + 16]), "little") for i in range(n)]
+
+
+def test_xts_power_table_all_40_constants(gfc):
+    """tw_pow_table (what xts_pow_table() of uaes_kernels.hip hands k_xts_expand and k_xts_small): entry i is
+    alpha^(2^(14+i)) for every i < 40 -- no GPU test reaches more than the first twelve (a unit of 2^(14+i) chunks of
+    4 KiB is 2^(26+i) bytes).  The reference exponentiation shares no code with the table: square-and-multiply on
+    Python integers, itself checked against plain doubling where that is cheap."""
+    cur = 1
+    for k in range(1, 1025):
+        cur <<= 1
+        if cur >> 128:
+            cur ^= XTS_P
+        if k in (1, 127, 128, 129, 1024):
+            assert xts_alpha_pow(k) == cur, k
+    table = xts_pow_table(gfc)
+    assert len(table) == len(set(table)) == 40
+    for i, got in enumerate(table):
+        assert got == xts_alpha_pow(1 << (14 + i)), "entry %d" % i
+
+
+def test_xts_wave_wide_product(gfc):
+    """wave_tw_mul's arithmetic on 64 simulated lanes with an XOR butterfly: t * e for the 40 constants and for random
+    e, all lanes agreeing"""
+    rnd = random.Random(40)
+    es = xts_pow_table(gfc) + [0, 1, 1 << 63, 1 << 64, 1 << 127, (1 << 128) - 1] + [rnd.getrandbits(128) for _ in range(200)]
+    for e in es:
+        for t in (rnd.getrandbits(128), 1, (1 << 128) - 1):
+            o = (C.c_uint8 * 16)()
+            same = gfc.gfc_wave_tw_mul(buf(t.to_bytes(16, "little")), buf(e.to_bytes(16, "little")), o)
+            assert same == 1, (hex(t), hex(e))
+            assert int.from_bytes(bytes(o), "little") == xts_mul(t, e), (hex(t), hex(e))
