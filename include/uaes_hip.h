@@ -972,6 +972,18 @@ const char *uaes_debug_plan_ocb_batch(int dir, size_t len, size_t nmsg, int out[
  * threads as "ccm.batch" for the same number of records), or NULL for another mode, a CBC record that is not a whole
  * number of blocks or a record of the other modes above UINT32_MAX bytes.  Works without a device (a 256-CU MI355X). */
 const char *uaes_debug_plan_cipher_batch(int mode, size_t len, size_t nmsg, int out[3]);
+/* The plan of one piece of a streamed GCM message (csrc/uaes_plan.h, uaesk_plan_gcm_piece: the function
+ * uaes_gcm_stream_update's kernel layer switches on): decrypt 0 / 1; len = bytes of the piece; done_bytes = text the
+ * stream has taken before it (a multiple of 16), which decides where the piece's groups of 256 counters fall.  The
+ * stream is taken to use a 12-byte nonce and to have made its first absorb.  out = { arrangement id, launches,
+ * workgroups, GHASH positions per thread } as for uaes_debug_plan; the arrangement "gcm.levels" (launches 0) means that
+ * the piece is not taken: the CTR kernel and the GHASH levels run (the absorb path).  Returns 0, or UAES_E_ARG for a
+ * done_bytes that is no multiple of 16.  Works without a device (a 256-CU MI355X).  tests/gcm_stream_cases.py derives
+ * its piece lengths from this. */
+int uaes_debug_plan_gcm_piece(int decrypt, size_t len, uint64_t done_bytes, int out[4]);
+/* The table cache of a stream (plan_state): bit 31 = the tables of the stream's key are in its scratch, low byte = logA
+ * of the bulk GHASH table there (0: none), bit 8 = the B table is there, bit 9 = the striped kernel's tables are there. */
+unsigned uaes_debug_gcm_stream_tables(const uaes_gcm_stream *s);
 
 /* Test hooks of the one-launch GCM / GCM-SIV / streamed-piece arrangements (chunk workgroups + one preparing workgroup
  * in ONE launch; whoever of them arrives last on a counter word folds the chunk hashes and makes the tag -- nobody

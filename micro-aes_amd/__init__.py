@@ -47,6 +47,7 @@ EXPORTS = [
     "uaes_gcmsiv_encrypt_batch", "uaes_gcmsiv_decrypt_batch", "uaes_debug_plan_gcmsiv_batch",
     "uaes_gcm_multikey_encrypt_batch", "uaes_gcm_multikey_decrypt_batch", "uaes_debug_plan_gcm_multikey_batch",
     "uaes_ocb_encrypt", "uaes_ocb_decrypt", "uaes_ocb_dev", "uaes_debug_plan_ocb", "uaes_debug_plan_xts",
+    "uaes_debug_plan_gcm_piece", "uaes_debug_gcm_stream_tables",
     "uaes_poly1305", "uaes_poly1305_dev", "uaes_poly1305_batch", "uaes_debug_plan_poly1305",
     "uaes_eax_encrypt", "uaes_eax_decrypt", "uaes_siv_encrypt", "uaes_siv_decrypt",
     "uaes_eax_encrypt_batch", "uaes_eax_decrypt_batch", "uaes_siv_encrypt_batch", "uaes_siv_decrypt_batch",
@@ -200,6 +201,9 @@ def engine():
     L.uaes_debug_plan_ocb.restype = C.c_char_p
     L.uaes_debug_plan_xts.argtypes = [sz, sz, i, C.POINTER(C.c_uint64)]
     L.uaes_debug_plan_xts.restype = C.c_char_p
+    L.uaes_debug_plan_gcm_piece.argtypes = [i, sz, u64, C.POINTER(C.c_int)]
+    L.uaes_debug_gcm_stream_tables.argtypes = [vp]
+    L.uaes_debug_gcm_stream_tables.restype = C.c_uint
     for n in ("uaes_ff1_encrypt", "uaes_ff1_decrypt"):
         getattr(L, n).argtypes = [i, vp, C.c_uint, vp, vp, sz, vp, sz, vp]
     for n in ("uaes_ff1_encrypt_batch", "uaes_ff1_decrypt_batch"):
@@ -284,7 +288,7 @@ def engine():
                      "uaes_debug_arrangement_name", "uaes_debug_plan_disable", "uaes_debug_plan_poly1305",
                      "uaes_debug_plan_eax_siv", "uaes_debug_plan_chain", "uaes_debug_plan_kw", "uaes_debug_plan_ff1",
                      "uaes_debug_plan_ff3", "uaes_ff3_maxlen", "uaes_debug_plan_gcmsiv_batch", "uaes_debug_plan_ocb", "uaes_debug_plan_xts",
-                     "uaes_debug_plan_ocb_batch", "uaes_debug_plan_gcm_multikey_batch", "uaes_debug_plan_cipher_batch"):
+                     "uaes_debug_gcm_stream_tables", "uaes_debug_plan_ocb_batch", "uaes_debug_plan_gcm_multikey_batch", "uaes_debug_plan_cipher_batch"):
             getattr(L, n).restype = i
     _lib = L
     return L
@@ -1307,6 +1311,17 @@ class GcmStream:
         _check(engine().uaes_gcm_stream_update(self._h, _in(piece), len(piece), o), "uaes_gcm_stream_update")
         return bytes(o)[: len(piece)]
 
+    def update_dev(self, src, n, dst):
+        """One piece of n bytes in device memory: src and dst are torch tensors or raw device pointers, handed straight
+        to uaes_gcm_stream_update; dst may be src.  Returns when the piece is done."""
+        s, d = (C.c_void_p(t if isinstance(t, int) else t.data_ptr()) for t in (src, dst))
+        _check(engine().uaes_gcm_stream_update(self._h, s, n, d), "uaes_gcm_stream_update")
+
+    def tables(self):
+        """The stream's table cache (uaes_debug_gcm_stream_tables) as (valid, logA, has_B, has_striped)."""
+        w = engine().uaes_debug_gcm_stream_tables(self._h)
+        return bool(w >> 31), w & 0xff, bool((w >> 8) & 1), bool((w >> 9) & 1)
+
     def finish(self, tag=None):
         """encrypt: returns the tag; decrypt: returns 0 or M_AUTHENTICATION_ERROR for the given tag."""
         t = _fixed(tag if self._decrypt else bytes(16), 16, "tag")
@@ -1314,10 +1329,14 @@ class GcmStream:
         rc = _check(engine().uaes_gcm_stream_finish(h, t), "uaes_gcm_stream_finish")
         return rc if self._decrypt else bytes(t)
 
-    def __del__(self):
+    def abort(self):
+        """give the stream up (uaes_gcm_stream_abort); a stream that is dropped unfinished is aborted too"""
         if getattr(self, "_h", None):
             engine().uaes_gcm_stream_abort(self._h)
             self._h = None
+
+    def __del__(self):
+        self.abort()
 
 
 MODES = {"ecb": 0, "ctr": 1, "xts": 2, "gcm": 3, "ocb": 4, "siv": 5}
@@ -1333,6 +1352,14 @@ def plan(mode, a, b=0, direction=0, flags=0, counter=None):
     else:
         _check(engine().uaes_debug_plan_at(MODES[mode], direction, a, b, flags, _fixed(counter, 16, "counter"), out),
                "uaes_debug_plan_at")
+    return engine().uaes_debug_arrangement_name(out[0]).decode(), out[1], out[2], out[3]
+
+
+def plan_gcm_piece(length, done=0, decrypt=False):
+    """What uaes_gcm_stream_update runs for a piece of `length` bytes behind `done` bytes of text (uaes_debug_plan_gcm_piece):
+    (arrangement name, launches, workgroups, positions per thread); "gcm.levels" = not taken, the absorb path."""
+    out = (C.c_int * 4)()
+    _check(engine().uaes_debug_plan_gcm_piece(int(bool(decrypt)), length, done, out), "uaes_debug_plan_gcm_piece")
     return engine().uaes_debug_arrangement_name(out[0]).decode(), out[1], out[2], out[3]
 
 

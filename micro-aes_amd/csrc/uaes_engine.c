@@ -1545,6 +1545,15 @@ const char *uaes_debug_plan_xts(size_t sector_bytes, size_t nsectors, int explic
     if (out) memcpy(out, shape, sizeof shape);
     return uaesk_arrangement_name(p.arrangement);
 }
+int uaes_debug_plan_gcm_piece(int decrypt, size_t len, uint64_t done_bytes, int out[4])
+{
+    uaes_plan p;
+    if (!out) return fail(UAES_E_ARG, "NULL pointer");
+    memset(&p, 0, sizeof p);
+    if (uaesk_plan_gcm_piece(decrypt, len, done_bytes, &p)) return fail(UAES_E_ARG, "no piece plan behind %llu bytes", (unsigned long long)done_bytes);
+    out[0] = p.arrangement; out[1] = p.launches; out[2] = (int)p.grid; out[3] = (int)p.steps;
+    return 0;
+}
 void uaes_debug_plan_disable(unsigned mask) { uaesk_plan_disable(mask); }
 
 int uaes_debug_live_key_schedules(void) { return __atomic_load_n(&g_live_schedules, __ATOMIC_RELAXED); }

@@ -1106,6 +1106,9 @@ restore:
     return rc;
 }
 
+/* test hook (include/uaes_hip.h): which GHASH tables the stream's scratch holds */
+unsigned uaes_debug_gcm_stream_tables(const uaes_gcm_stream *s) { return s ? s->plan_state : 0u; }
+
 void uaes_gcm_stream_abort(uaes_gcm_stream *s)
 {
     int prev = -1;

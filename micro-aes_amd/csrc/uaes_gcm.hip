@@ -1329,6 +1329,26 @@ static void gcm_counter_from_j0(uaesk_ctr &c, const unsigned char j0b[16], u64 b
     c.v0 = (v + 1 + block_offset) & 0x00FFFFFFFFFFFFFFull;
 }
 
+/* The plan of one piece of a streamed message (uaesk_gcm_stream_piece switches on it): len bytes behind done_bytes of
+ * text under J0 = j0b; c receives the piece's first counter.  has_word: the stream has a counter word; chunks_ready:
+ * the tables of Y are in its scratch.  GCM_LEVELS = not taken: the absorb path. */
+static GcmPlan gcm_piece_plan(int decrypt, u64 len, u64 done_bytes, const unsigned char j0b[16], bool has_word, bool chunks_ready,
+                              uaesk_ctr &c)
+{
+    gcm_counter_from_j0(c, j0b, done_bytes / 16);
+    return gcm_plan(decrypt ? 2 : 0, len, 0, c, has_word, true, chunks_ready);
+}
+
+/* ... as data, for a 12-byte nonce and a stream that has its counter word and its tables (uaes_debug_plan_gcm_piece) */
+int uaesk_plan_gcm_piece(int decrypt, size_t len, uint64_t done_bytes, uaes_plan *p)
+{
+    const unsigned char j0b[16] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1 };
+    uaesk_ctr c;
+    if (done_bytes % 16) return (int)hipErrorInvalidValue;
+    *p = gcm_piece_plan(decrypt, len, done_bytes, j0b, true, true, c).p;
+    return 0;
+}
+
 /* j0: the call's J0, or NULL for a 12-byte nonce (J0 ends in 00000001); the stripes follow its counter as gcm_body's do */
 int uaesk_plan_gcm(int dir, size_t len, size_t aad_len, unsigned flags, const uint8_t *j0, uaes_plan *p)
 {
@@ -1842,8 +1862,9 @@ extern "C" int uaesk_gcm_stream_absorb(void *stream, const uaesk_tables *tb, int
     return uaesk_launch(k_gcm_fold, 1, 64, 0, st, sc, nv, kind == 0);
 }
 
-/* One piece of a streamed message, CTR and GHASH in ONE pass when the piece is long enough for the striped kernel
- * (8 MiB on 256 CUs): what uaesk_gcm_shard does for a slice, with the running value folded (k_gcm_fold) instead of a
+/* One piece of a streamed message, CTR and GHASH in ONE pass when the piece is the striped kernel's by the table
+ * (gcm_piece_plan: past 128 MiB, or from one stripe per CU on -- 8 MiB on 256 CUs -- where the chunk arrangements are
+ * switched off): what uaesk_gcm_shard does for a slice, with the running value folded (k_gcm_fold) instead of a
  * weighted share.  Returns 1 if it was not taken (the caller then runs uaesk_ctr_xcrypt + uaesk_gcm_stream_absorb as
  * before: CTR kernel, GHASH levels, fold -- two passes over the piece, 415 GiB/s for one 256 MiB piece), 0 when the
  * work is enqueued, else a hipError_t.  done_bytes = text absorbed so far (a multiple of 16); a piece of a length
@@ -1861,7 +1882,7 @@ static int launch_stream_chunks(hipStream_t st, const uaesk_tables *tb, const ua
     return hash_only ? chunks(k_gcm_chunks<NR, 1, true>) : decrypt ? chunks(k_gcm_chunks<NR, 2, true>) : chunks(k_gcm_chunks<NR, 0, true>);
 }
 
-/* ... and a piece of 16 KiB .. 8 MiB is ONE launch: the chunk workgroups of the medium-sized one-shot call (k_gcm_chunks,
+/* ... and a piece of 16 KiB .. 16 MiB is ONE launch: the chunk workgroups of the medium-sized one-shot call (k_gcm_chunks,
  * FOLD) with a finisher that folds the piece's raw hash into the running value (GmcFin.mode 2) -- needs done_word (a
  * word that is zero between calls) and the key's nibble tables in the scratch (the stream's first absorb made them). */
 extern "C" int uaesk_gcm_stream_piece(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek,
@@ -1878,12 +1899,11 @@ extern "C" int uaesk_gcm_stream_piece(void *stream, const uaesk_tables *tb, int 
     j0b[12] = j0b[13] = j0b[14] = 0; j0b[15] = 1;
     memcpy(&j0, j0b, 16);
     uaesk_ctr c;
-    gcm_counter_from_j0(c, j0b, done_bytes / 16);
     /* as for a one-shot call (gcm_plan): up to 16 MiB the chunk workgroups (CTR and GHASH together), from there to the
      * end of their round two phases -- the bulk CTR kernel and the hash-only chunk workgroups over the piece's
      * ciphertext (a decryption hashes first: in may be out) --, beyond that the striped pass; a piece none of them
      * takes goes back to the caller (1: the absorb path) */
-    const GcmPlan plan = gcm_plan(decrypt ? 2 : 0, len, 0, c, done_word != nullptr, true, (*plan_state >> 31) != 0);
+    const GcmPlan plan = gcm_piece_plan(decrypt, len, done_bytes, j0b, done_word != nullptr, (*plan_state >> 31) != 0, c);
     const GcmStripes &sp = plan.s;
     const int cus = sp.cus;
     const u64 nfull = len / 16, h0 = sp.h0, g_lo = sp.g_lo, n8 = sp.n8, h1 = sp.h1;

@@ -148,6 +148,14 @@ int uaesk_plan(int mode, int dir, size_t a, size_t b, unsigned flags, uaes_plan 
  * start value 1; GCM: a 12-byte nonce).  Other modes ignore it. */
 int uaesk_plan_at(int mode, int dir, size_t a, size_t b, unsigned flags, const uint8_t *counter16, uaes_plan *p);
 
+/* one piece of a streamed GCM message (uaes_gcm.hip's gcm_piece_plan, which uaesk_gcm_stream_piece switches on;
+ * uaes_debug_plan_gcm_piece): len bytes of text behind done_bytes (a multiple of 16) already taken, under a 12-byte
+ * nonce, in a stream that has its counter word and the tables of its first absorb.  A piece has no small arrangement
+ * and no AAD; where its stripes fall depends on done_bytes (the first counter is 2 + done_bytes / 16).  GCM_LEVELS
+ * (launches 0) = not taken: the caller runs the CTR kernel and uaesk_gcm_stream_absorb.  tests/gcm_stream_cases.py
+ * derives its piece lengths from this. */
+int uaesk_plan_gcm_piece(int decrypt, size_t len, uint64_t done_bytes, uaes_plan *p);
+
 const char *uaesk_arrangement_name(int id);
 
 /* OCB's runs arrangement answers ("ocb.runs", 1, 0, 0) at every size; the shape k_ocb is launched with is a table of

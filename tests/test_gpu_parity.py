@@ -373,8 +373,10 @@ def test_gcm_stream_equals_one_shot(orc, bits):
     for pieces, aad_len in [([16], 0), ([5], 3), ([16, 16, 7], 20), ([4096, 16, 65536, 1], 0),
                             ([(1 << 20) + 16, 48, (600 << 10), 12345], 4097), ([0, 32, 0, 16], 16),
                             ([40 << 10, 2 << 20, 64, 5 << 20, 2 << 20, 100], 1),    # level plans change back and forth
-                            # pieces long enough for the one-pass kernel (8 MiB on 256 CUs) between short ones: its
-                            # tables are made once per stream, a later short piece's setup must leave them alone
+                            # long pieces between short ones.  (On 256 CUs a piece goes to the chunk workgroups up to 16 MiB
+                            # and to the two phases up to 128 MiB; the one-pass striped kernel, whose tables are made once
+                            # per stream and left alone by a later short piece's setup, takes pieces past that, and no
+                            # piece here is that long: tests/test_gpu_gcm_stream.py runs it.)
                             ([9 << 20, 4096, (17 << 20) + 16, 16, (8 << 20) + 5], 33), ([(12 << 20) + 7], 0),
                             # pieces of 16 .. 128 MiB: two phases (bulk CTR kernel + hash-only chunk workgroups), 2^k blocks too
                             ([16 << 20, (33 << 20) + 48, 32, 32 << 20, (20 << 20) + 9], 5)][: 11 if bits == 128 else 10]:

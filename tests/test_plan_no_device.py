@@ -326,3 +326,58 @@ def test_planning_is_what_it_was(hook):
     assert got
     wrong = [g for g in got if g[3] != g[2]]
     assert not wrong, wrong[:8]
+
+
+# uaes.plan_gcm_piece(len, done, decrypt): what uaes_gcm_stream_update runs for one piece of a streamed GCM message, from
+# the function uaesk_gcm_stream_piece switches on (gcm_piece_plan, csrc/uaes_gcm.hip).  Worked by hand from gcm_plan for 256
+# CUs: no chunk workgroups below 1024 GHASH positions ("gcm.levels", 0 launches: the absorb path), then one launch of
+# ceil(positions / (1024 * steps)) chunk workgroups with the smallest power-of-two steps that fits 256 of them, two
+# phases past 2^20 positions, the striped pass past 2^23 (three launches, five for a decryption: the tail's CTR kernel and
+# its GHASH come apart).  A ragged piece counts its last block.
+KIB = 1024
+PIECE_EXPECTED = [
+    ((16,), ("gcm.levels", 0, 0, 0)),
+    ((16 * KIB - 16,), ("gcm.levels", 0, 0, 0)),
+    ((16 * KIB - 3,), ("gcm.chunks", 1, 1, 1)),
+    ((16 * KIB,), ("gcm.chunks", 1, 1, 1)),
+    ((16 * KIB + 1,), ("gcm.chunks", 1, 2, 1)),
+    ((16 * KIB, 16 * 253, True), ("gcm.chunks", 1, 1, 1)),
+    ((4 * MIB,), ("gcm.chunks", 1, 256, 1)),
+    ((4 * MIB + 16,), ("gcm.chunks", 1, 129, 2)),
+    ((8 * MIB,), ("gcm.chunks", 1, 256, 2)),
+    ((8 * MIB + 16,), ("gcm.chunks", 1, 129, 4)),
+    ((16 * MIB,), ("gcm.chunks", 1, 256, 4)),
+    ((16 * MIB, 0, True), ("gcm.chunks", 1, 256, 4)),
+    ((16 * MIB + 16,), ("gcm.twophase", 2, 129, 8)),
+    ((16 * MIB + 16, 16 * 254, True), ("gcm.twophase", 2, 129, 8)),
+    ((64 * MIB,), ("gcm.twophase", 2, 256, 16)),
+    ((128 * MIB,), ("gcm.twophase", 2, 256, 32)),
+    ((128 * MIB + 16,), ("gcm.striped", 3, 256, 0)),
+    ((128 * MIB + 16, 0, True), ("gcm.striped", 5, 256, 0)),
+    ((128 * MIB + 16, 16 * 254), ("gcm.striped", 3, 256, 0)),
+    ((128 * MIB + 16, 128 * MIB + 32 * KIB + 16, True), ("gcm.striped", 5, 256, 0)),
+    ((GIB,), ("gcm.striped", 3, 256, 0)),
+]
+
+
+def test_piece_planning_without_a_device():
+    got = [(args, want, uaes.plan_gcm_piece(*args)) for args, want in PIECE_EXPECTED]
+    wrong = [g for g in got if g[2] != g[1]]
+    assert not wrong, wrong
+    # up to the two phases a piece is planned like a one-shot encryption of the same length without its small arrangement
+    for n in (MIB, 4 * MIB + 16, 16 * MIB, 16 * MIB + 16, 128 * MIB):
+        piece, whole = uaes.plan_gcm_piece(n), uaes.plan("gcm", n)
+        assert (piece[0], piece[2], piece[3]) == (whole[0], whole[2], whole[3]), n
+    with pytest.raises(uaes.EngineError):
+        uaes.plan_gcm_piece(4096, done=8)
+    # with the chunk arrangements switched off a piece is striped from one stripe per CU on, counted from its first group
+    L = uaes.engine()
+    off = (1 << uaes.arrangement_id("gcm.chunks")) | (1 << uaes.arrangement_id("gcm.twophase"))
+    try:
+        L.uaes_debug_plan_disable(off)
+        for done, h0 in ((0, 254), (16 * 253, 1), (16 * 254, 0), (16 * 255, 255)):
+            n = 16 * (h0 + 2048 * 256)
+            assert uaes.plan_gcm_piece(n, done) == ("gcm.striped", 3, 256, 0), (done, h0)
+            assert uaes.plan_gcm_piece(n - 16, done) == ("gcm.levels", 0, 0, 0), (done, h0)
+    finally:
+        L.uaes_debug_plan_disable(0)
