@@ -85,27 +85,23 @@ int uaesk_gcm_j0(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *e
                  const void *d_iv, size_t iv_len, void *scratch, void *j0_out16);
 /* decrypt: 0 = encrypt; 1 = decrypt, nothing written unless the tag matches (two passes over the text);
  * 2 = decrypt, long texts in one pass: `out` is written before the tag is known and zeroed if it
- * turns out wrong (for callers that accept a wiped buffer, or whose `out` is private staging) */
+ * turns out wrong (for callers that accept a wiped buffer, or whose `out` is private staging).
+ * keyed != 0 promises that uaesk_gcm_key_tables has filled `scratch` under this key and nothing but uaesk_gcm calls
+ * with keyed != 0 under the same key has written it since: per message only Enc(J0) is computed then, unless the
+ * text needs a size-dependent bulk table.  One call at a time per buffer.                            */
 int uaesk_gcm(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek,
               int decrypt, const uint8_t *j0_16,
               const void *aad, size_t aad_len,
               const void *in, size_t len, void *out,
-              void *scratch, int *status);
+              void *scratch, int *status, int keyed);
 
-/* decrypt == 3 (uaesk_gcm only): just the tag of (aad, `in` as ciphertext), 16 bytes written at `status`; the
+/* decrypt == 3: just the tag of (aad, `in` as ciphertext), 16 bytes written at `status`; the
  * host layer compares a truncated tag (GCM_TAG_LEN < 16) itself and then calls uaesk_gcm_ctr for the text */
 int uaesk_gcm_ctr(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek,
                   const uint8_t *j0_16, const void *in, size_t len, void *out);
 
-/* Key context: uaesk_gcm_key_tables fills a scratch buffer (uaesk_gcm_scratch_bytes()) with every table
- * that depends on the key only; uaesk_gcm_keyed is uaesk_gcm on such a buffer -- per message it computes
- * just Enc(J0), unless the text needs a size-dependent bulk table.  One call at a time per buffer.  */
+/* Key context: every table that depends on the key only, into a scratch buffer (uaesk_gcm_scratch_bytes()) */
 int uaesk_gcm_key_tables(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, void *key_scratch);
-int uaesk_gcm_keyed(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek,
-                    int decrypt, const uint8_t *j0_16,
-                    const void *aad, size_t aad_len,
-                    const void *in, size_t len, void *out,
-                    void *key_scratch, int *status);
 
 /* Many short messages under one key context in one launch (k_gcm_records): record r = rec_len bytes at
  * in + r * in_stride under nonce nonces12 + 12 r with the AAD at aad + r * aad_stride (stride 0: shared);
@@ -262,7 +258,7 @@ typedef struct {
 } uaesk_done;
 void uaesk_ticket_arm(void *pinned_flag, void *d_count, unsigned seq);
 /* a device word that is zero between calls and that nothing else writes, for the calling thread's NEXT kernel-level
- * call (uaesk_gcm / uaesk_gcm_keyed take it: with it a medium-sized text is one launch); NULL disarms */
+ * call (uaesk_gcm takes it: with it a medium-sized text is one launch); NULL disarms */
 void uaesk_done_word_arm(unsigned *w);
 /* test hooks: the preparing workgroup's bounded look (100 MHz ticks; 0 = count in without looking) and the number of
  * folds a CHUNK workgroup has done on the current device (uaes_gcm.hip, "FOLD") */

@@ -9,7 +9,7 @@
 /* ------------------------------------------------------------------------ */
 /* GCM                                                                        */
 /* ------------------------------------------------------------------------ */
-/* 1: the tables of `key` are in the lane's scratch (this call may run as a call on a key context, uaesk_gcm_keyed),
+/* 1: the tables of `key` are in the lane's scratch (this call may run as a call on a key context, uaesk_gcm's keyed),
  * 0: they are not (the one-shot path), < 0: error.  Call with the scratch allocated (gcm_scratch).  A call on a key
  * context is 2-4 us shorter than a one-shot call and the table set costs ~20 us once, so it is built when the EIGHTH
  * call in a row comes under one key (a sequence that stops there has lost those 20 us, a longer one gains 10-15 %
@@ -108,9 +108,122 @@ static int gcm_encrypt_pipelined(keysched *ks, const uint8_t *nonce, const void 
     return took;
 }
 
-/* nonceLen / tagLen = the reference's compile-time GCM_NONCE_LEN / GCM_TAG_LEN (micro_aes.h:108-109).  The kernels
- * always produce the 16-byte tag behind the text; a shorter tag is the host layer's business: the text goes
- * through a buffer with room for sixteen bytes and ptextLen + tagLen bytes are handed over (:1178).         */
+/* What a GCM call runs on, whichever front door it came through: the one-shot calls (the lane's scratch, keyed once
+ * lane_gcm_keyed has built the key's tables there) and the calls on a key context (its own scratch, always keyed). */
+typedef struct {
+    const keysched *ks;             /* by pointer only (KEYSCHED) */
+    int             keyed;          /* `scratch` holds the tables of ks: uaesk_gcm's keyed */
+    void           *scratch;
+    unsigned       *done_word;      /* the zero-between-calls word behind `scratch` */
+} gcm_how;
+
+/* The kernels always produce the 16-byte tag behind the text; a shorter tag (the one-shot calls only) is the host
+ * layer's business: the text goes through a buffer with room for sixteen bytes and ptextLen + tag_len bytes are handed
+ * over (micro_aes.c:1178). */
+static int gcm_encrypt_on_lane(context *c, lane *L, const gcm_how *how, const uint8_t j0[16], size_t tag_len,
+                               const void *aData, size_t aDataLen, const void *pntxt, size_t ptextLen, void *crtxt)
+{
+    io_plan io;
+    const void *d_aad;
+    int rc, k;
+    if ((rc = stage_aad(L, aData, aDataLen, &d_aad)) != 0) return rc;
+    if ((rc = plan_io(L, pntxt, ptextLen, crtxt, ptextLen + tag_len, &io)) != 0) return rc;
+    if (tag_len < 16 && io.dout == crtxt) {
+        /* the caller's own device buffer ends tag_len bytes behind the text: run into staging, copy back */
+        if (grow_on(L->stream, &L->stage[1], &L->stage_cap[1], ptextLen + 64)) return UAES_E_HIP;
+        io.dout = L->stage[1];
+        io.copy_back = 1;
+    }
+    ticket_arm(L, ptextLen);
+    arm_done_word(how->done_word);
+    k = uaesk_gcm(L->stream, &c->tb, how->ks->nr, &how->ks->ek, 0, j0, d_aad, aDataLen, io.din, ptextLen, io.dout,
+                  how->scratch, NULL, how->keyed);
+    arm_done_word(NULL);
+    ticket_armed_launch_done(L);
+    if ((rc = launched("gcm", k)) != 0) return rc;
+    return finish_io(&io, ptextLen + tag_len);
+}
+
+/* Nothing reaches the caller's buffer before the whole text has been authenticated (N7). */
+static int gcm_decrypt_on_lane(context *c, lane *L, const gcm_how *how, const uint8_t j0[16], size_t tag_len,
+                               const void *aData, size_t aDataLen, const void *crtxt, size_t crtxtLen, void *pntxt)
+{
+    io_plan io;
+    const void *d_aad;
+    int rc, k, status = -1;
+    if ((rc = stage_aad(L, aData, aDataLen, &d_aad)) != 0) return rc;
+    /* input is CT || tag; output is crtxtLen bytes */
+    if ((rc = plan_io(L, crtxt, crtxtLen + tag_len, pntxt, crtxtLen, &io)) != 0) return rc;
+    if (tag_len < 16) {
+        /* a truncated tag (GCM_TAG_LEN < 16, :1204) is compared here: the device computes the full tag of the
+         * ciphertext (nothing is decrypted), its first tag_len bytes are checked against the ones behind the
+         * text in constant time, and only then does the CTR pass write the caller's buffer (N7)          */
+        uint8_t full[16], given[16];
+        k = uaesk_gcm(L->stream, &c->tb, how->ks->nr, &how->ks->ek, 3, j0, d_aad, aDataLen, io.din, crtxtLen, NULL,
+                      how->scratch, L->d_status + 4, how->keyed);
+        if ((rc = launched("gcm", k)) != 0) return rc;
+        if ((rc = lane_fetch(L, full, L->d_status + 4, 16)) != 0) return rc;
+        if (is_device_ptr(io.din)) {
+            if (hipMemcpy(given, (const char *)io.din + crtxtLen, tag_len, hipMemcpyDeviceToHost) != hipSuccess)
+                return fail(UAES_E_HIP, "reading the tag back failed");
+        } else {
+            memcpy(given, (const char *)io.din + crtxtLen, tag_len);    /* the mapped pinned window */
+        }
+        if (tags_differ(full, given, tag_len)) return UAES_E_AUTHENTICATION;
+        k = uaesk_gcm_ctr(L->stream, &c->tb, how->ks->nr, &how->ks->ek, j0, io.din, crtxtLen, io.dout);
+        if ((rc = launched("gcm", k)) != 0) return rc;
+        return finish_io(&io, crtxtLen);
+    }
+    if (io.dout == io.din && io.copy_back) {
+        /* host -> host: decrypt into the second staging buffer so that a
+         * failed authentication can leave the caller's buffer untouched   */
+        if (grow_on(L->stream, &L->stage[1], &L->stage_cap[1], crtxtLen + 64)) return UAES_E_HIP;
+        io.dout = L->stage[1];
+    }
+    /* a private staging buffer may be written before the tag is known: one pass */
+    const int dmode = io.copy_back || io.dout == L->pin[1] ? 2 : gcm_decrypt_mode();
+    int *st_where = lane_status(L);
+    if (st_where != L->d_status) { *(volatile int *)st_where = -1; ticket_arm(L, crtxtLen); }   /* host-visible status: a
+                                                 * one-launch decryption may carry the completion ticket itself */
+    arm_done_word(how->done_word);
+    k = uaesk_gcm(L->stream, &c->tb, how->ks->nr, &how->ks->ek, dmode, j0, d_aad, aDataLen, io.din, crtxtLen, io.dout,
+                  how->scratch, st_where, how->keyed);
+    arm_done_word(NULL);
+    ticket_armed_launch_done(L);
+    if ((rc = launched("gcm", k)) != 0) return rc;
+    if ((rc = lane_read_status(L, st_where, &status)) != 0) return rc;
+    if (status != 0) return UAES_E_AUTHENTICATION;            /* N7: pntxt untouched */
+    io.drained = 1;
+    return finish_io(&io, crtxtLen);
+}
+
+/* The checks of the one-shot calls.  nonceLen / tagLen = the reference's compile-time GCM_NONCE_LEN / GCM_TAG_LEN
+ * (micro_aes.h:108-109); `tagged` is the buffer that holds the tag (never NULL), `text` the other one. */
+static int gcm_args_ok(const uint8_t *nonce, size_t nonceLen, size_t tagLen, const void *aData, size_t aDataLen,
+                       const void *tagged, const void *text, size_t len)
+{
+    if (!nonce || !tagged || (len && !text)) return fail(UAES_E_ARG, "NULL pointer");
+    if (tagLen < 1 || tagLen > 16) return fail(UAES_E_ARG, "GCM tag length %zu (1..16)", tagLen);
+    if (nonceLen == 0) return fail(UAES_E_ARG, "empty GCM nonce");
+    if (aDataLen && !aData) return fail(UAES_E_ARG, "NULL aData with aDataLen != 0");
+    return 0;
+}
+
+/* The lane's scratch made ready for a one-shot call under `key`: whether it holds the key's tables, and the call's J0. */
+static int gcm_lane_prepare(lane *L, keysched *ks, const uint8_t *key, int keybits, const uint8_t *nonce, size_t nonceLen,
+                            int *keyed, uint8_t j0[16])
+{
+    int rc;
+    if ((rc = gcm_scratch(L, SCRATCH_GCM_KEYED)) != 0) return rc;
+    /* (before anything of this call writes the scratch under its key.  A one-shot setup builds only the tables its
+     * message reaches and leaves the others undefined: with a nonce whose J0 is a GHASH of its own, which runs such
+     * a setup, the call stays one-shot and the cache starts over) */
+    *keyed = nonceLen == 12 ? lane_gcm_keyed(L, ks, key, keybits) : 0;
+    if (*keyed < 0) return *keyed;
+    if (nonceLen != 12) lane_scratch_clobbered(L);
+    return gcm_j0(L, ks, nonce, nonceLen, j0);
+}
+
 int uaes_gcm_encrypt_ex(int keybits, const uint8_t *key, const uint8_t *nonce, size_t nonceLen, size_t tagLen,
                         const void *aData, size_t aDataLen,
                         const void *pntxt, size_t ptextLen, void *crtxt)
@@ -118,15 +231,10 @@ int uaes_gcm_encrypt_ex(int keybits, const uint8_t *key, const uint8_t *nonce, s
     context *c;
     lane *L;
     KEYSCHED(ks);
-    io_plan io;
-    const void *d_aad;
     uint8_t j0[16];
-    int rc;
+    int rc, keyed;
     if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
-    if (!nonce || !crtxt || (ptextLen && !pntxt)) return fail(UAES_E_ARG, "NULL pointer");
-    if (tagLen < 1 || tagLen > 16) return fail(UAES_E_ARG, "GCM tag length %zu (1..16)", tagLen);
-    if (nonceLen == 0) return fail(UAES_E_ARG, "empty GCM nonce");
-    if (aDataLen && !aData) return fail(UAES_E_ARG, "NULL aData with aDataLen != 0");
+    if ((rc = gcm_args_ok(nonce, nonceLen, tagLen, aData, aDataLen, crtxt, pntxt, ptextLen)) != 0) return rc;
     if (host_take_mode(pntxt, crtxt, ptextLen, 0, 1) && !is_device_ptr(aData)) {
         const uaesh_key hk = host_key(&ks);
         return host_result(uaesh_gcm(&hk, 0, nonce, nonceLen, tagLen, (const uint8_t *)aData, aDataLen, (const uint8_t *)pntxt, ptextLen, (uint8_t *)crtxt));
@@ -138,34 +246,10 @@ int uaes_gcm_encrypt_ex(int keybits, const uint8_t *key, const uint8_t *nonce, s
         if (gcm_encrypt_pipelined(&ks, nonce, aData, aDataLen, pntxt, ptextLen, crtxt, &rc)) return rc;
     }
     if ((rc = enter(&c, &L)) != 0) return rc;
-    do {
-        if ((rc = gcm_scratch(L, SCRATCH_GCM_KEYED)) != 0) break;
-        /* (before anything of this call writes the scratch under its key.  A one-shot setup builds only the tables its
-         * message reaches and leaves the others undefined: with a nonce whose J0 is a GHASH of its own, which runs such
-         * a setup, the call stays one-shot and the cache starts over) */
-        int keyed = nonceLen == 12 ? lane_gcm_keyed(L, &ks, key, keybits) : 0;
-        if (keyed < 0) { rc = keyed; break; }
-        if (nonceLen != 12) lane_scratch_clobbered(L);
-        if ((rc = gcm_j0(L, &ks, nonce, nonceLen, j0)) != 0) break;
-        if ((rc = stage_aad(L, aData, aDataLen, &d_aad)) != 0) break;
-        if ((rc = plan_io(L, pntxt, ptextLen, crtxt, ptextLen + tagLen, &io)) != 0) break;
-        if (tagLen < 16 && io.dout == crtxt) {
-            /* the caller's own device buffer ends tagLen bytes behind the text: run into staging, copy back */
-            if (grow_on(L->stream, &L->stage[1], &L->stage_cap[1], ptextLen + 64)) { rc = UAES_E_HIP; break; }
-            io.dout = L->stage[1];
-            io.copy_back = 1;
-        }
-        ticket_arm(L, ptextLen);
-        arm_done_word(scratch_done_word(L->scratch, L->scratch_cap));
-        int k = keyed ? uaesk_gcm_keyed(L->stream, &c->tb, ks.nr, &ks.ek, 0, j0, d_aad, aDataLen,
-                                        io.din, ptextLen, io.dout, L->scratch, NULL)
-                      : uaesk_gcm(L->stream, &c->tb, ks.nr, &ks.ek, 0, j0, d_aad, aDataLen,
-                                  io.din, ptextLen, io.dout, L->scratch, NULL);
-        arm_done_word(NULL);
-        ticket_armed_launch_done(L);
-        if ((rc = launched("gcm", k)) != 0) break;
-        rc = finish_io(&io, ptextLen + tagLen);
-    } while (0);
+    if ((rc = gcm_lane_prepare(L, &ks, key, keybits, nonce, nonceLen, &keyed, j0)) == 0) {
+        const gcm_how how = { &ks, keyed, L->scratch, scratch_done_word(L->scratch, L->scratch_cap) };
+        rc = gcm_encrypt_on_lane(c, L, &how, j0, tagLen, aData, aDataLen, pntxt, ptextLen, crtxt);
+    }
     DONE(L, rc);
 }
 
@@ -190,15 +274,10 @@ int uaes_gcm_decrypt_ex(int keybits, const uint8_t *key, const uint8_t *nonce, s
     context *c;
     lane *L;
     KEYSCHED(ks);
-    io_plan io;
-    const void *d_aad;
     uint8_t j0[16];
-    int rc, status = -1;
+    int rc, keyed;
     if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
-    if (!nonce || !crtxt || (crtxtLen && !pntxt)) return fail(UAES_E_ARG, "NULL pointer");
-    if (tagLen < 1 || tagLen > 16) return fail(UAES_E_ARG, "GCM tag length %zu (1..16)", tagLen);
-    if (nonceLen == 0) return fail(UAES_E_ARG, "empty GCM nonce");
-    if (aDataLen && !aData) return fail(UAES_E_ARG, "NULL aData with aDataLen != 0");
+    if ((rc = gcm_args_ok(nonce, nonceLen, tagLen, aData, aDataLen, crtxt, pntxt, crtxtLen)) != 0) return rc;
     if (host_take_mode(crtxt, pntxt, crtxtLen, 0, 1) && !is_device_ptr(aData)) {
         const uaesh_key hk = host_key(&ks);
         return host_result(uaesh_gcm(&hk, 1, nonce, nonceLen, tagLen, (const uint8_t *)aData, aDataLen, (const uint8_t *)crtxt, crtxtLen, (uint8_t *)pntxt));
@@ -209,67 +288,10 @@ int uaes_gcm_decrypt_ex(int keybits, const uint8_t *key, const uint8_t *nonce, s
         if (nd) return uaes_mgpu_gcm_decrypt(nd, devs, keybits, key, nonce, aData, aDataLen, crtxt, crtxtLen, pntxt);
     }
     if ((rc = enter(&c, &L)) != 0) return rc;
-    do {
-        if ((rc = gcm_scratch(L, SCRATCH_GCM_KEYED)) != 0) break;
-        /* (before anything of this call writes the scratch under its key.  A one-shot setup builds only the tables its
-         * message reaches and leaves the others undefined: with a nonce whose J0 is a GHASH of its own, which runs such
-         * a setup, the call stays one-shot and the cache starts over) */
-        int keyed = nonceLen == 12 ? lane_gcm_keyed(L, &ks, key, keybits) : 0;
-        if (keyed < 0) { rc = keyed; break; }
-        if (nonceLen != 12) lane_scratch_clobbered(L);
-        if ((rc = gcm_j0(L, &ks, nonce, nonceLen, j0)) != 0) break;
-        if ((rc = stage_aad(L, aData, aDataLen, &d_aad)) != 0) break;
-        /* input is CT || tag; output is crtxtLen bytes */
-        if ((rc = plan_io(L, crtxt, crtxtLen + tagLen, pntxt, crtxtLen, &io)) != 0) break;
-        if (tagLen < 16) {
-            /* a truncated tag (GCM_TAG_LEN < 16, :1204) is compared here: the device computes the full tag of the
-             * ciphertext (nothing is decrypted), its first tagLen bytes are checked against the ones behind the
-             * text in constant time, and only then does the CTR pass write the caller's buffer (N7)          */
-            uint8_t full[16], given[16];
-            int k = keyed ? uaesk_gcm_keyed(L->stream, &c->tb, ks.nr, &ks.ek, 3, j0, d_aad, aDataLen,
-                                            io.din, crtxtLen, NULL, L->scratch, L->d_status + 4)
-                          : uaesk_gcm(L->stream, &c->tb, ks.nr, &ks.ek, 3, j0, d_aad, aDataLen,
-                                      io.din, crtxtLen, NULL, L->scratch, L->d_status + 4);
-            if ((rc = launched("gcm", k)) != 0) break;
-            if ((rc = lane_fetch(L, full, L->d_status + 4, 16)) != 0) break;
-            if (is_device_ptr(io.din)) {
-                if (hipMemcpy(given, (const char *)io.din + crtxtLen, tagLen, hipMemcpyDeviceToHost) != hipSuccess) {
-                    rc = fail(UAES_E_HIP, "reading the tag back failed");
-                    break;
-                }
-            } else {
-                memcpy(given, (const char *)io.din + crtxtLen, tagLen);     /* the mapped pinned window */
-            }
-            if (tags_differ(full, given, tagLen)) { rc = UAES_E_AUTHENTICATION; break; }
-            k = uaesk_gcm_ctr(L->stream, &c->tb, ks.nr, &ks.ek, j0, io.din, crtxtLen, io.dout);
-            if ((rc = launched("gcm", k)) != 0) break;
-            rc = finish_io(&io, crtxtLen);
-            break;
-        }
-        if (io.dout == io.din && io.copy_back) {
-            /* host -> host: decrypt into the second staging buffer so that a
-             * failed authentication can leave the caller's buffer untouched   */
-            if (grow_on(L->stream, &L->stage[1], &L->stage_cap[1], crtxtLen + 64)) { rc = UAES_E_HIP; break; }
-            io.dout = L->stage[1];
-        }
-        /* a private staging buffer may be written before the tag is known: one pass */
-        int *st_where = lane_status(L);
-        if (st_where != L->d_status) { *(volatile int *)st_where = -1; ticket_arm(L, crtxtLen); }   /* host-visible status: a
-                                                     * one-launch decryption may carry the completion ticket itself */
-        arm_done_word(scratch_done_word(L->scratch, L->scratch_cap));
-        const int dmode = io.copy_back || io.dout == L->pin[1] ? 2 : gcm_decrypt_mode();
-        int k = keyed ? uaesk_gcm_keyed(L->stream, &c->tb, ks.nr, &ks.ek, dmode, j0, d_aad, aDataLen, io.din, crtxtLen, io.dout,
-                                        L->scratch, st_where)
-                      : uaesk_gcm(L->stream, &c->tb, ks.nr, &ks.ek, dmode, j0, d_aad, aDataLen, io.din, crtxtLen, io.dout,
-                                  L->scratch, st_where);
-        arm_done_word(NULL);
-        ticket_armed_launch_done(L);
-        if ((rc = launched("gcm", k)) != 0) break;
-        if ((rc = lane_read_status(L, st_where, &status)) != 0) break;
-        if (status != 0) { rc = UAES_E_AUTHENTICATION; break; }  /* N7: pntxt untouched */
-        io.drained = 1;
-        rc = finish_io(&io, crtxtLen);
-    } while (0);
+    if ((rc = gcm_lane_prepare(L, &ks, key, keybits, nonce, nonceLen, &keyed, j0)) == 0) {
+        const gcm_how how = { &ks, keyed, L->scratch, scratch_done_word(L->scratch, L->scratch_cap) };
+        rc = gcm_decrypt_on_lane(c, L, &how, j0, tagLen, aData, aDataLen, crtxt, crtxtLen, pntxt);
+    }
     DONE(L, rc);
 }
 
@@ -287,6 +309,23 @@ int uaes_gcm_decrypt(int keybits, const uint8_t *key, const uint8_t *nonce,
     return uaes_gcm_decrypt_iv(keybits, key, nonce, 12, aData, aDataLen, crtxt, crtxtLen, pntxt);
 }
 
+/* The *_dev calls: one uaesk_gcm under a 12-byte nonce on the caller's stream, nothing waited for.  slot >= 0: `how`'s
+ * scratch is that pinned slot of the context, dropped once the launch is issued. */
+static int gcm_call_dev(context *c, const gcm_how *how, int slot, int mode, const uint8_t *nonce,
+                        const void *d_aad, size_t aad_len, const void *d_in, size_t len, void *d_out,
+                        int *d_status, void *stream)
+{
+    uint8_t j0[16];
+    int k;
+    j0_of_nonce12(nonce, j0);
+    arm_done_word(how->done_word);
+    k = uaesk_gcm(stream, &c->tb, how->ks->nr, &how->ks->ek, mode, j0, d_aad, aad_len, d_in, len, d_out,
+                  how->scratch, d_status, how->keyed);
+    disarm_done_word_dev(stream, k);
+    if (slot >= 0) scratch_unpin(c, slot);
+    return k ? fail(UAES_E_HIP, "uaesk_gcm failed: %s", hipGetErrorString((hipError_t)k)) : 0;
+}
+
 int uaes_gcm_encrypt_dev(int keybits, const uint8_t *key, const uint8_t *nonce,
                          const void *d_aad, size_t aad_len,
                          const void *d_in, size_t len, void *d_out, void *stream)
@@ -294,19 +333,14 @@ int uaes_gcm_encrypt_dev(int keybits, const uint8_t *key, const uint8_t *nonce,
     context *c;
     KEYSCHED(ks);
     void *scr;
-    uint8_t j0[16];
     int rc, slot;
     if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
     if (!nonce || !d_out) return fail(UAES_E_ARG, "NULL pointer");
     if ((rc = dev_ptrs_ok(d_in, d_out, len)) != 0) return rc;
     if ((rc = get_context(&c)) != 0) return rc;
     if ((rc = gcm_scratch_locked(c, stream, &scr, &slot)) != 0) return rc;
-    j0_of_nonce12(nonce, j0);
-    arm_done_word(scratch_done_word(scr, c->slot[slot].cap));
-    rc = uaesk_gcm(stream, &c->tb, ks.nr, &ks.ek, 0, j0, d_aad, aad_len, d_in, len, d_out, scr, NULL);
-    disarm_done_word_dev(stream, rc);
-    KCHK_PINNED(c, slot, rc);
-    return 0;
+    const gcm_how how = { &ks, 0, scr, scratch_done_word(scr, c->slot[slot].cap) };
+    return gcm_call_dev(c, &how, slot, 0, nonce, d_aad, aad_len, d_in, len, d_out, NULL, stream);
 }
 
 int uaes_gcm_decrypt_dev(int keybits, const uint8_t *key, const uint8_t *nonce,
@@ -317,7 +351,6 @@ int uaes_gcm_decrypt_dev(int keybits, const uint8_t *key, const uint8_t *nonce,
     context *c;
     KEYSCHED(ks);
     void *scr;
-    uint8_t j0[16];
     int rc, slot;
     if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
     if (!nonce || !d_in) return fail(UAES_E_ARG, "NULL pointer");
@@ -325,12 +358,8 @@ int uaes_gcm_decrypt_dev(int keybits, const uint8_t *key, const uint8_t *nonce,
     if (!d_status) return fail(UAES_E_ARG, "NULL d_status");
     if ((rc = get_context(&c)) != 0) return rc;
     if ((rc = gcm_scratch_locked(c, stream, &scr, &slot)) != 0) return rc;
-    j0_of_nonce12(nonce, j0);
-    arm_done_word(scratch_done_word(scr, c->slot[slot].cap));
-    rc = uaesk_gcm(stream, &c->tb, ks.nr, &ks.ek, gcm_decrypt_mode(), j0, d_aad, aad_len, d_in, len, d_out, scr, d_status);
-    disarm_done_word_dev(stream, rc);
-    KCHK_PINNED(c, slot, rc);
-    return 0;
+    const gcm_how how = { &ks, 0, scr, scratch_done_word(scr, c->slot[slot].cap) };
+    return gcm_call_dev(c, &how, slot, gcm_decrypt_mode(), nonce, d_aad, aad_len, d_in, len, d_out, d_status, stream);
 }
 
 /* ------------------------------------------------------------------------ */
@@ -343,6 +372,7 @@ struct uaes_gcm_key {
                                      * of zero-between-calls words like the lanes' scratch buffers have */
 };
 #define KEY_DONE_WORD(k) ((unsigned *)((char *)(k)->scratch + uaesk_gcm_scratch_bytes()))
+#define KEY_HOW(k)       { &(k)->ks, 1, (k)->scratch, KEY_DONE_WORD(k) }     /* a gcm_how: the calls on the context */
 
 int uaes_gcm_key_new(uaes_gcm_key **out, int keybits, const uint8_t *key)
 {
@@ -406,27 +436,14 @@ int uaes_gcm_key_encrypt(uaes_gcm_key *k, const uint8_t *nonce, const void *aDat
 {
     context *c;
     lane *L;
-    io_plan io;
-    const void *d_aad;
     uint8_t j0[16];
     int rc;
     if ((rc = key_device_ok(k)) != 0) return rc;
     if (!nonce || !crtxt || (ptextLen && !pntxt)) return fail(UAES_E_ARG, "NULL pointer");
     if ((rc = enter(&c, &L)) != 0) return rc;
+    const gcm_how how = KEY_HOW(k);
     j0_of_nonce12(nonce, j0);
-    do {
-        if ((rc = stage_aad(L, aData, aDataLen, &d_aad)) != 0) break;
-        if ((rc = plan_io(L, pntxt, ptextLen, crtxt, ptextLen + 16, &io)) != 0) break;
-        ticket_arm(L, ptextLen);
-        arm_done_word(KEY_DONE_WORD(k));
-        int kk = uaesk_gcm_keyed(L->stream, &c->tb, k->ks.nr, &k->ks.ek, 0, j0, d_aad, aDataLen,
-                                 io.din, ptextLen, io.dout, k->scratch, NULL);
-        arm_done_word(NULL);
-        ticket_armed_launch_done(L);
-        if ((rc = launched("gcm", kk)) != 0) break;
-        rc = finish_io(&io, ptextLen + 16);
-    } while (0);
-    DONE(L, rc);
+    DONE(L, gcm_encrypt_on_lane(c, L, &how, j0, 16, aData, aDataLen, pntxt, ptextLen, crtxt));
 }
 
 int uaes_gcm_key_decrypt(uaes_gcm_key *k, const uint8_t *nonce, const void *aData, size_t aDataLen,
@@ -434,72 +451,40 @@ int uaes_gcm_key_decrypt(uaes_gcm_key *k, const uint8_t *nonce, const void *aDat
 {
     context *c;
     lane *L;
-    io_plan io;
-    const void *d_aad;
     uint8_t j0[16];
-    int rc, status = -1;
+    int rc;
     if ((rc = key_device_ok(k)) != 0) return rc;
     if (!nonce || !crtxt || (crtxtLen && !pntxt)) return fail(UAES_E_ARG, "NULL pointer");
     if ((rc = enter(&c, &L)) != 0) return rc;
+    const gcm_how how = KEY_HOW(k);
     j0_of_nonce12(nonce, j0);
-    do {
-        if ((rc = stage_aad(L, aData, aDataLen, &d_aad)) != 0) break;
-        if ((rc = plan_io(L, crtxt, crtxtLen + 16, pntxt, crtxtLen, &io)) != 0) break;
-        if (io.dout == io.din && io.copy_back) {      /* host -> host: keep the caller's buffer untouched on 0x1A */
-            if (grow_on(L->stream, &L->stage[1], &L->stage_cap[1], crtxtLen + 64)) { rc = UAES_E_HIP; break; }
-            io.dout = L->stage[1];
-        }
-        int *st_where = lane_status(L);
-        if (st_where != L->d_status) { *(volatile int *)st_where = -1; ticket_arm(L, crtxtLen); }
-        arm_done_word(KEY_DONE_WORD(k));
-        int kk = uaesk_gcm_keyed(L->stream, &c->tb, k->ks.nr, &k->ks.ek,
-                                 io.copy_back || io.dout == L->pin[1] ? 2 : gcm_decrypt_mode(), j0, d_aad, aDataLen,
-                                 io.din, crtxtLen, io.dout, k->scratch, st_where);
-        arm_done_word(NULL);
-        ticket_armed_launch_done(L);
-        if ((rc = launched("gcm", kk)) != 0) break;
-        if ((rc = lane_read_status(L, st_where, &status)) != 0) break;
-        if (status != 0) { rc = UAES_E_AUTHENTICATION; break; }  /* N7: pntxt untouched */
-        io.drained = 1;
-        rc = finish_io(&io, crtxtLen);
-    } while (0);
-    DONE(L, rc);
+    DONE(L, gcm_decrypt_on_lane(c, L, &how, j0, 16, aData, aDataLen, crtxt, crtxtLen, pntxt));
 }
 
 int uaes_gcm_key_encrypt_dev(uaes_gcm_key *k, const uint8_t *nonce, const void *d_aad, size_t aad_len,
                              const void *d_in, size_t len, void *d_out, void *stream)
 {
     context *c;
-    uint8_t j0[16];
     int rc;
     if ((rc = key_device_ok(k)) != 0) return rc;
     if (!nonce || !d_out) return fail(UAES_E_ARG, "NULL pointer");
     if ((rc = dev_ptrs_ok(d_in, d_out, len)) != 0) return rc;
     if ((rc = get_context(&c)) != 0) return rc;
-    j0_of_nonce12(nonce, j0);
-    arm_done_word(KEY_DONE_WORD(k));
-    rc = uaesk_gcm_keyed(stream, &c->tb, k->ks.nr, &k->ks.ek, 0, j0, d_aad, aad_len, d_in, len, d_out, k->scratch, NULL);
-    disarm_done_word_dev(stream, rc);
-    KCHK(rc);
-    return 0;
+    const gcm_how how = KEY_HOW(k);
+    return gcm_call_dev(c, &how, -1, 0, nonce, d_aad, aad_len, d_in, len, d_out, NULL, stream);
 }
 
 int uaes_gcm_key_decrypt_dev(uaes_gcm_key *k, const uint8_t *nonce, const void *d_aad, size_t aad_len,
                              const void *d_in, size_t len, void *d_out, int *d_status, void *stream)
 {
     context *c;
-    uint8_t j0[16];
     int rc;
     if ((rc = key_device_ok(k)) != 0) return rc;
     if (!nonce || !d_in || !d_status) return fail(UAES_E_ARG, "NULL pointer");
     if ((rc = dev_ptrs_ok(d_in, d_out, len)) != 0) return rc;
     if ((rc = get_context(&c)) != 0) return rc;
-    j0_of_nonce12(nonce, j0);
-    arm_done_word(KEY_DONE_WORD(k));
-    rc = uaesk_gcm_keyed(stream, &c->tb, k->ks.nr, &k->ks.ek, gcm_decrypt_mode(), j0, d_aad, aad_len, d_in, len, d_out, k->scratch, d_status);
-    disarm_done_word_dev(stream, rc);
-    KCHK(rc);
-    return 0;
+    const gcm_how how = KEY_HOW(k);
+    return gcm_call_dev(c, &how, -1, gcm_decrypt_mode(), nonce, d_aad, aad_len, d_in, len, d_out, d_status, stream);
 }
 
 /* ---- many short messages under one key context in one launch (uaesk_gcm_records) -------------------------
@@ -842,6 +827,37 @@ int uaes_ghash(const uint8_t H[16], const void *aData, size_t aDataLen,
 /* Host orchestration only: the host expands the MASTER key and enqueues; key derivation, the derived key's
  * expansion, POLYVAL, the tag and the LE32 counter stream run in kernels and their per-nonce values never leave the
  * device (k_siv_small for a short message, uaesk_gcmsiv_long otherwise).                                       */
+static int gcmsiv_on_lane(context *c, lane *L, const keysched *mk, int decrypt, const uint8_t *nonce,
+                          const void *aData, size_t aDataLen, const void *in, size_t len, void *out)
+{
+    io_plan io;
+    const void *d_aad;
+    int *const d_status = decrypt ? L->d_status : NULL;
+    int rc, k, status = -1;
+    if ((rc = gcm_scratch(L, SCRATCH_OTHER)) != 0) return rc;
+    if ((rc = stage_aad(L, aData, aDataLen, &d_aad)) != 0) return rc;
+    if ((rc = plan_io(L, in, len + (decrypt ? 16 : 0), out, len + (decrypt ? 0 : 16), &io)) != 0) return rc;
+    /* a short message is ONE launch (k_siv_small): key derivation, POLYVAL, tag and keystream in one workgroup; the
+     * host only expands the master key (< 0: too long for it) */
+    k = uaesk_gcmsiv_small(L->stream, &c->tb, mk->nr, &mk->ek, decrypt, nonce, d_aad, aDataLen, io.din, len, io.dout, d_status);
+    if (k < 0) {
+        /* a longer one: six or seven launches one behind the other, the per-nonce key, the hash, the tag and the
+         * counter made of it stay on the device (uaesk_gcmsiv_long) -- the host waits once.  Decryption is like the
+         * reference's: decrypt with the RECEIVED tag as counter, then authenticate (:1500-1502) */
+        arm_done_word(scratch_done_word(L->scratch, L->scratch_cap));
+        k = uaesk_gcmsiv_long(L->stream, &c->tb, mk->nr, &mk->ek, decrypt, nonce, d_aad, aDataLen, io.din, len, io.dout,
+                              L->scratch, d_status);
+        arm_done_word(NULL);
+    }
+    if ((rc = launched("gcm-siv", k)) != 0) return rc;
+    if (!decrypt) return finish_io(&io, len + 16);
+    /* the text stays (SABOTAGE is a no-op) unless uaes_set_wipe_on_auth_failure(1) */
+    if ((rc = lane_fetch(L, &status, L->d_status, sizeof status)) != 0) return rc;
+    io.drained = 1;
+    if ((rc = status ? finish_io_unauthenticated(&io, len) : finish_io(&io, len)) != 0) return rc;
+    return status ? UAES_E_AUTHENTICATION : 0;
+}
+
 int uaes_gcmsiv_encrypt(int keybits, const uint8_t *key, const uint8_t *nonce,
                         const void *aData, size_t aDataLen,
                         const void *pntxt, size_t ptextLen, void *crtxt)
@@ -849,8 +865,6 @@ int uaes_gcmsiv_encrypt(int keybits, const uint8_t *key, const uint8_t *nonce,
     context *c;
     lane *L;
     KEYSCHED(mk);
-    io_plan io;
-    const void *d_aad;
     int rc;
     if (keybits != 128 && keybits != 192 && keybits != 256)
         return fail(UAES_E_ARG, "keybits must be 128, 192 or 256 (got %d)", keybits);
@@ -863,28 +877,7 @@ int uaes_gcmsiv_encrypt(int keybits, const uint8_t *key, const uint8_t *nonce,
         return host_result(rc);
     }
     if ((rc = enter(&c, &L)) != 0) return rc;
-    do {
-        if ((rc = gcm_scratch(L, SCRATCH_OTHER)) != 0) break;
-        if ((rc = stage_aad(L, aData, aDataLen, &d_aad)) != 0) break;
-        if ((rc = plan_io(L, pntxt, ptextLen, crtxt, ptextLen + 16, &io)) != 0) break;
-        {   /* a short message is ONE launch (k_siv_small): key derivation, POLYVAL, tag and keystream in one
-             * workgroup; the host only expands the master key */
-            int ks = uaesk_gcmsiv_small(L->stream, &c->tb, mk.nr, &mk.ek, 0, nonce, d_aad, aDataLen,
-                                        io.din, ptextLen, io.dout, NULL);
-            if (ks > 0 && (rc = launched("gcm-siv", ks)) != 0) break;
-            if (ks == 0) { rc = finish_io(&io, ptextLen + 16); break; }
-        }
-        {   /* a longer one: six or seven launches one behind the other, the per-nonce key, the hash, the tag and the
-             * counter made of it stay on the device (uaesk_gcmsiv_long) -- the host waits once, in finish_io */
-            arm_done_word(scratch_done_word(L->scratch, L->scratch_cap));
-            int kl = uaesk_gcmsiv_long(L->stream, &c->tb, mk.nr, &mk.ek, 0, nonce, d_aad, aDataLen,
-                                       io.din, ptextLen, io.dout, L->scratch, NULL);
-            arm_done_word(NULL);
-            if ((rc = launched("gcm-siv", kl)) != 0) break;
-        }
-        rc = finish_io(&io, ptextLen + 16);
-    } while (0);
-    DONE(L, rc);
+    DONE(L, gcmsiv_on_lane(c, L, &mk, 0, nonce, aData, aDataLen, pntxt, ptextLen, crtxt));
 }
 
 int uaes_gcmsiv_decrypt(int keybits, const uint8_t *key, const uint8_t *nonce,
@@ -894,8 +887,6 @@ int uaes_gcmsiv_decrypt(int keybits, const uint8_t *key, const uint8_t *nonce,
     context *c;
     lane *L;
     KEYSCHED(mk);
-    io_plan io;
-    const void *d_aad;
     int rc;
     if (keybits != 128 && keybits != 192 && keybits != 256)
         return fail(UAES_E_ARG, "keybits must be 128, 192 or 256 (got %d)", keybits);
@@ -909,39 +900,7 @@ int uaes_gcmsiv_decrypt(int keybits, const uint8_t *key, const uint8_t *nonce,
         return host_result(rc);
     }
     if ((rc = enter(&c, &L)) != 0) return rc;
-    do {
-        if ((rc = gcm_scratch(L, SCRATCH_OTHER)) != 0) break;
-        if ((rc = stage_aad(L, aData, aDataLen, &d_aad)) != 0) break;
-        if ((rc = plan_io(L, crtxt, crtxtLen + 16, pntxt, crtxtLen, &io)) != 0) break;
-        {   /* a short message is ONE launch (k_siv_small), key derivation included */
-            int ks = uaesk_gcmsiv_small(L->stream, &c->tb, mk.nr, &mk.ek, 1, nonce, d_aad, aDataLen,
-                                        io.din, crtxtLen, io.dout, L->d_status);
-            if (ks > 0 && (rc = launched("gcm-siv", ks)) != 0) break;
-            if (ks == 0) {
-                int status = -1;
-                if ((rc = lane_fetch(L, &status, L->d_status, sizeof status)) != 0) break;
-                io.drained = 1;
-                if ((rc = status ? finish_io_unauthenticated(&io, crtxtLen) : finish_io(&io, crtxtLen)) != 0) break;
-                rc = status ? UAES_E_AUTHENTICATION : 0;
-                break;
-            }
-        }
-        {   /* like the reference: decrypt with the RECEIVED tag as counter, then authenticate (:1500-1502) -- all of
-             * it on the device (uaesk_gcmsiv_long); the text stays (SABOTAGE is a no-op) unless
-             * uaes_set_wipe_on_auth_failure(1) */
-            int status = -1;
-            arm_done_word(scratch_done_word(L->scratch, L->scratch_cap));
-            int kl = uaesk_gcmsiv_long(L->stream, &c->tb, mk.nr, &mk.ek, 1, nonce, d_aad, aDataLen,
-                                       io.din, crtxtLen, io.dout, L->scratch, L->d_status);
-            arm_done_word(NULL);
-            if ((rc = launched("gcm-siv", kl)) != 0) break;
-            if ((rc = lane_fetch(L, &status, L->d_status, sizeof status)) != 0) break;
-            io.drained = 1;
-            if ((rc = status ? finish_io_unauthenticated(&io, crtxtLen) : finish_io(&io, crtxtLen)) != 0) break;
-            rc = status ? UAES_E_AUTHENTICATION : 0;
-        }
-    } while (0);
-    DONE(L, rc);
+    DONE(L, gcmsiv_on_lane(c, L, &mk, 1, nonce, aData, aDataLen, crtxt, crtxtLen, pntxt));
 }
 
 /* ------------------------------------------------------------------------ */

@@ -1294,7 +1294,7 @@ static GcmPlan gcm_plan(int dir, u64 len, u64 aad_len, const uaesk_ctr &c, bool 
         const bool fold_ok = has_word && (int)g.p.grid <= g.s.cus;       /* one launch: chunk workgroups + fold */
         if ((dir == 1 && !piece) || gmac || nvh <= GMC_ONEPASS_MAX_NV) {
             if (uaesk_arr_on(UAES_ARR_GCM_CHUNKS)) {
-                const int dmode = (gmac && dir == 2) ? 1 : dir;            /* (gcm_body) */
+                const int dmode = (gmac && dir == 2) ? 1 : dir;            /* (uaesk_gcm) */
                 g.p.arrangement = UAES_ARR_GCM_CHUNKS;
                 g.p.launches = ((fold_ok && dmode != 2) || piece ? 1 : 2) + ((dmode == 1 && !gmac && !piece) ? 1 : 0);
                 return g;
@@ -1349,7 +1349,7 @@ int uaesk_plan_gcm_piece(int decrypt, size_t len, uint64_t done_bytes, uaes_plan
     return 0;
 }
 
-/* j0: the call's J0, or NULL for a 12-byte nonce (J0 ends in 00000001); the stripes follow its counter as gcm_body's do */
+/* j0: the call's J0, or NULL for a 12-byte nonce (J0 ends in 00000001); the stripes follow its counter as uaesk_gcm's do */
 int uaesk_plan_gcm(int dir, size_t len, size_t aad_len, unsigned flags, const uint8_t *j0, uaes_plan *p)
 {
     if (dir < 0 || dir > 3) return (int)hipErrorInvalidValue;
@@ -1395,11 +1395,11 @@ int uaesk_plan_siv(int dir, size_t len, size_t aad_len, unsigned flags, uaes_pla
 /* keyed != 0: `scratch` belongs to a key context whose tables (nibble tables, H^S table, Y/Z powers, all
  * H^(2^k)) uaesk_gcm_key_tables built; then only Enc(J0) is computed per message unless the text needs
  * a size-dependent bulk table (two-pass texts over 512 KiB), for which the full setup runs as usual. */
-static int gcm_body(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek,
-                    int decrypt, const uint8_t *j0_16,
-                    const void *aad, size_t aad_len,
-                    const void *in, size_t len, void *out,
-                    void *scratch, int *status, int keyed)
+extern "C" int uaesk_gcm(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek,
+                         int decrypt, const uint8_t *j0_16,
+                         const void *aad, size_t aad_len,
+                         const void *in, size_t len, void *out,
+                         void *scratch, int *status, int keyed)
 {
     hipStream_t st = S(stream);
     unsigned char *sc = (unsigned char *)scratch;
@@ -1550,37 +1550,13 @@ static int gcm_body(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk
     return uaesk_ctr_xcrypt(stream, tb, nr, ek, &c, in, out, len, status);
 }
 
-extern "C" int uaesk_gcm(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek,
-                         int decrypt, const uint8_t *j0_16,
-                         const void *aad, size_t aad_len,
-                         const void *in, size_t len, void *out,
-                         void *scratch, int *status)
-{
-    return gcm_body(stream, tb, nr, ek, decrypt, j0_16, aad, aad_len, in, len, out, scratch, status, 0);
-}
-
 /* the CTR half alone: in -> out under the keystream that starts at J0 + 1 (CTR_cipher mode CCM_GCM, :938-940) */
 extern "C" int uaesk_gcm_ctr(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek,
                              const uint8_t *j0_16, const void *in, size_t len, void *out)
 {
     uaesk_ctr c;
-    memset(&c, 0, sizeof c);
-    memcpy(&c.w0, j0_16, 4);
-    memcpy(&c.w1, j0_16 + 4, 4);
-    c.b8 = j0_16[8];
-    uint64_t v = 0;
-    for (int i = 9; i < 16; ++i) v = (v << 8) | j0_16[i];
-    c.v0 = (v + 1) & 0x00FFFFFFFFFFFFFFull;
+    gcm_counter_from_j0(c, j0_16, 0);
     return uaesk_ctr_xcrypt(stream, tb, nr, ek, &c, in, out, len, nullptr);
-}
-
-extern "C" int uaesk_gcm_keyed(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek,
-                               int decrypt, const uint8_t *j0_16,
-                               const void *aad, size_t aad_len,
-                               const void *in, size_t len, void *out,
-                               void *key_scratch, int *status)
-{
-    return gcm_body(stream, tb, nr, ek, decrypt, j0_16, aad, aad_len, in, len, out, key_scratch, status, 1);
 }
 
 /* everything of the GCM setup that depends on the key only, into a key context's scratch */
@@ -1708,7 +1684,7 @@ extern "C" int uaesk_gcm_shard(void *stream, const uaesk_tables *tb, int nr, con
     const uint4 z = make_uint4(0, 0, 0, 0);
     int rc;
 
-    if (mode != 1) {                            /* CTR and GHASH of a long shard in one pass: gcm_body's conditions */
+    if (mode != 1) {                            /* CTR and GHASH of a long shard in one pass: uaesk_gcm's conditions */
         const u64 nfull = shard_len / 16, ablk = (msg.aad_len + 15) >> 4;
         const GcmStripes sp = gcm_stripes(c, shard_len, ablk);
         const int cus = sp.cus;

@@ -1433,6 +1433,140 @@ def test_gcm_key_context_equals_the_one_shot_calls(orc, bits):
     k.close()
 
 
+def test_gcm_front_doors_share_one_call_path(orc):
+    """The one-shot calls and the calls on a key context run the same host functions (gcm_encrypt_on_lane,
+    gcm_decrypt_on_lane, gcm_call_dev): identical bytes and verdicts, both equal to the oracle, at every branch those
+    functions select.  Sizes 0, 1, 4096 and one byte more than the pinned bounce buffers hold (UAES_PIN_KIB defaults to
+    1024 in env_init: the host path then goes through the staging buffers, not the mapped pinned windows); AAD of 0 and
+    5 bytes; host buffers, device buffers out of place and in place through the synchronous calls, and the *_dev
+    calls; tag lengths 16 and 12 on the one-shot side.  A flipped text bit and a flipped tag bit per placement: 0x1A,
+    the 0xCC prefill still in a host or out-of-place device output, the ciphertext still in an in-place device buffer
+    (the one-pass switch is off).  Once with a key the lane's key cache has not seen, once with the cache keyed (nine
+    one-shot calls under the key first: GK_BUILD_AT is 8).  AES-128 carries the matrix, AES-256 the host buffers."""
+    import torch
+    L = uaes.engine()
+    rnd = random.Random(20261020)
+    big = (1 << 20) + 1
+    other = rnd.randbytes(16)
+    vp = C.c_void_p
+    oracle = {}                                               # (bits, n, alen): computed once, shared by both cache states
+
+    def dev(b, room=32):
+        return torch.frombuffer(bytearray(bytes(b) + b"\xCC" * room), dtype=torch.uint8).cuda()
+
+    def back(t, n):
+        return bytes(t[:n].cpu().numpy())
+
+    def host(b):
+        return (C.c_uint8 * max(len(b), 1)).from_buffer_copy(bytes(b) or b"\0")
+
+    def matrix(key, placements, keyed):
+        bits = len(key) * 8
+        ctx = uaes.GcmKey(key)
+
+        def one_sync(decrypt, tl):
+            fn = L.uaes_gcm_decrypt_ex if decrypt else L.uaes_gcm_encrypt_ex
+
+            def call(nonce, aad, src, n, dst):
+                if not keyed:                                 # a call under another key: the cache starts over
+                    assert L.uaes_gcm_encrypt(128, other, nonce, None, 0, None, 0, host(bytes(16))) == 0
+                return fn(bits, key, nonce, 12, tl, aad, len(aad), src, n, dst)
+            return call
+
+        def ctx_sync(decrypt):
+            fn = L.uaes_gcm_key_decrypt if decrypt else L.uaes_gcm_key_encrypt
+            return lambda nonce, aad, src, n, dst: fn(ctx._h, nonce, aad, len(aad), src, n, dst)
+
+        def one_dev(decrypt):
+            if decrypt:
+                return lambda nonce, a, src, n, dst, st: uaes.gcm_decrypt_dev(key, nonce, a, src, n, dst, st)
+            return lambda nonce, a, src, n, dst, st: uaes.gcm_encrypt_dev(key, nonce, a, src, n, dst)
+
+        def ctx_dev(decrypt):
+            if decrypt:
+                return lambda nonce, a, src, n, dst, st: ctx.decrypt_dev(nonce, a, src, n, dst, st)
+            return lambda nonce, a, src, n, dst, st: ctx.encrypt_dev(nonce, a, src, n, dst)
+
+        def through(place, enc, dec, tl, nonce, aad, pt, forged):
+            """(ciphertext || tag, then per decryption -- the good text and the forgeries -- its verdict and output)"""
+            n, got = len(pt), []
+            if place == "host":
+                o = host(b"\xCC" * (n + 16))
+                assert enc(nonce, aad, host(pt), n, o) == 0
+                got.append(bytes(o)[: n + tl])
+                for ct in [got[0]] + forged:
+                    o = host(b"\xCC" * n)
+                    got.append((dec(nonce, aad, host(ct), n, o), bytes(o)[:n]))
+            elif place == "device":
+                s, o = dev(pt), dev(b"", n + 32)
+                assert enc(nonce, aad, vp(s.data_ptr()), n, vp(o.data_ptr())) == 0
+                got.append(back(o, n + tl))
+                assert back(o, n + 32)[n + tl:] == b"\xCC" * (32 - tl)            # nothing behind the tag
+                for ct in [got[0]] + forged:
+                    s, o = dev(ct), dev(b"", n + 32)
+                    got.append((dec(nonce, aad, vp(s.data_ptr()), n, vp(o.data_ptr())), back(o, n)))
+                    assert back(o, n + 32)[n:] == b"\xCC" * 32
+            elif place == "in place":
+                o = dev(pt)
+                assert enc(nonce, aad, vp(o.data_ptr()), n, vp(o.data_ptr())) == 0
+                got.append(back(o, n + tl))
+                assert back(o, n + 32)[n + tl:] == b"\xCC" * (32 - tl)
+                for ct in [got[0]] + forged:
+                    o = dev(ct)
+                    got.append((dec(nonce, aad, vp(o.data_ptr()), n, vp(o.data_ptr())), back(o, n)))
+                    assert back(o, n + tl + 32)[n:] == ct[n:] + b"\xCC" * 32      # the tag and what follows it stay
+            else:
+                a = dev(aad, 0) if aad else None              # (the wrapper takes the tensor's size as the AAD's length)
+                o, st = dev(b"", n + 32), torch.full((1,), -1, dtype=torch.int32, device="cuda")
+                enc(nonce, a, dev(pt), n, o, None)
+                got.append(back(o, n + 16))
+                for ct in [got[0]] + forged:
+                    o = dev(b"", n + 32)
+                    st.fill_(-1)
+                    dec(nonce, a, dev(ct), n, o, st)
+                    got.append((int(st.item()), back(o, n)))
+                    assert back(o, n + 32)[n:] == b"\xCC" * 32
+            return got
+
+        try:
+            if keyed:
+                for _ in range(9):
+                    assert L.uaes_gcm_encrypt(bits, key, bytes(12), None, 0, None, 0, host(bytes(16))) == 0
+            for n in (0, 1, 4096, big):
+                for alen in (0, 5):
+                    case = (bits, n, alen)
+                    if case not in oracle:
+                        nonce, aad, pt = rnd.randbytes(12), rnd.randbytes(alen), orc.splitmix(n + alen, n)
+                        want = orc.gcm_encrypt(key, nonce, aad, pt)
+                        # (a truncated tag is the head of the full one: the oracle computes it where that is cheap)
+                        want12 = orc.gcm_encrypt(key, nonce, aad, pt, tag_len=12) if n <= 4096 else want[: n + 12]
+                        oracle[case] = nonce, aad, pt, {16: want, 12: want12}
+                    nonce, aad, pt, wants = oracle[case]
+                    for place in placements:
+                        for tl in (16, 12):
+                            want = wants[tl]
+                            spots = ([n // 2] if n else []) + [n + tl - 1]
+                            forged = [want[:p] + bytes([want[p] ^ 0x20]) + want[p + 1:] for p in spots]
+                            kept = [f[:n] if place == "in place" else b"\xCC" * n for f in forged]
+                            expect = [want, (0, pt)] + [(0x1A, k) for k in kept]
+                            where = (bits, keyed, n, alen, place, tl)
+                            if place == "dev calls":
+                                if tl == 16:
+                                    assert through(place, one_dev(0), one_dev(1), 16, nonce, aad, pt, forged) == expect, where
+                                    assert through(place, ctx_dev(0), ctx_dev(1), 16, nonce, aad, pt, forged) == expect, where
+                                continue
+                            assert through(place, one_sync(0, tl), one_sync(1, tl), tl, nonce, aad, pt, forged) == expect, where
+                            if tl == 16:                      # (a key context has no truncated tags)
+                                assert through(place, ctx_sync(0), ctx_sync(1), 16, nonce, aad, pt, forged) == expect, where
+        finally:
+            ctx.close()
+
+    k128, k256 = rnd.randbytes(16), rnd.randbytes(32)
+    for keyed in (False, True):
+        matrix(k128, ("host", "device", "in place", "dev calls"), keyed)
+        matrix(k256, ("host",), keyed)
+
+
 @pytest.mark.parametrize("bits", [128, 192, 256])
 def test_gcm_record_calls_equal_a_call_per_record(orc, bits):
     """uaes_gcm_key_{en,de}crypt_records: many equally long messages in one launch, each with its own nonce (and
