@@ -104,7 +104,7 @@ int         uaes_stream_release(void *stream);
  *   fallback   with NO usable HIP device the calls below run on the host instead of returning UAES_E_HIP -- the
  *              reference's `void` functions cannot report an error.
  * Covered: every synchronous one-message call of this header -- ECB, CTR, XTS (unit and sectors), GCM (any nonce / tag
- * length), CBC (CTS and CTS-0 forms), CFB, OFB, CMAC, CCM, GCM-SIV, OCB, KW, FF1, FF3-1.  Not covered (always GPU): the *_dev / *_batch
+ * length), CBC (CTS and CTS-0 forms), CFB, OFB, CMAC, CCM, GCM-SIV, OCB, KW, KWP, FF1, FF3-1.  Not covered (always GPU): the *_dev / *_batch
  * / record / key-context / stream / mgpu calls, uaes_ghash, and any call that is handed a device pointer.
  * Environment, read at first use: UAES_HOST_MAX=<bytes>, UAES_HOST_CHAINS=1, UAES_HOST_FALLBACK=1; or
  * UAES_HOST_POLICY=recommended = (4096, 1, 1), the measured crossover on the builder's hosts (profiles/r05_host_policy.md),
@@ -455,9 +455,9 @@ int uaes_ofb_xcrypt_batch(int keybits, const uint8_t *key, const uint8_t *ivs, s
  * disjoint, or the secret sits 8 bytes into the wrapped buffer (secret == (uint8_t *)wrapped + 8, the reference's own
  * in-place form); any other overlap is undefined.  The host policy applies (one serial chain: `chains`).
  * One wave walks the chain, sixteen lanes per block: a secret of up to 4 KiB keeps its semiblocks in LDS, a longer one
- * is worked on in place in device memory with its loads issued a chunk of steps ahead.  No rate is stated: none has
- * been measured yet (tools/kw_rate.py times one call, the batches and a chain step in both directions on the GPU and
- * writes profiles/kw_rate.md, which does not exist yet).
+ * is worked on in place in device memory with its loads issued a chunk of steps ahead.  Measured (tools/kw_rate.py,
+ * profiles/kw_rate.md, AES-128): 23 .. 25 us for one 32-byte secret, 72 us to wrap and 80 us to unwrap 65 536 of them in
+ * one batch, 0.46 / 0.48 us per chain step.
  * Batches: nkeys records of one length under one kek, back to back -- secret m at m * secret_bytes, wrapped record m at
  * m * (secret_bytes + 8) -- sixteen GPU lanes per record, always on the GPU; a record holds at most 256 bytes of secret
  * (UAES_E_ARG beyond; a 2048-bit secret fits), lengths as above (UAES_E_DATALENGTH).  unwrap_batch sets verdicts[m] =
@@ -469,6 +469,64 @@ int uaes_kw_wrap_batch(int keybits, const uint8_t *kek, size_t nkeys, size_t sec
                        const void *secrets, void *wrapped);
 int uaes_kw_unwrap_batch(int keybits, const uint8_t *kek, size_t nkeys, size_t wrapped_bytes,
                          const void *wrapped, void *secrets, uint8_t *verdicts);
+
+/* ---- KWP: key wrap with padding (RFC 5649, SP 800-38F KWP; PKCS#11 CKM_AES_KEY_WRAP_KWP) ------
+ * The reference has none: this goes past it, for the secrets KW cannot take -- any length from 1 to 2^32 - 1 bytes (a
+ * PKCS#8 blob, a 66-byte P-521 scalar, a PIN).  The secret is zero-filled to n = ceil(secretLen / 8) semiblocks and A
+ * starts as A6 59 59 A6 || secretLen (32 bits, big-endian: the MLI).  n >= 2 runs KW's chain of 6 n blocks with that A;
+ * n = 1 is one block of the cipher over A || the filled semiblock, no chain.
+ *   wrap      writes uaes_kwp_wrapped_len(secretLen) = 8 n + 8 bytes; secretLen 0 or above 2^32 - 1 -> UAES_E_DATALENGTH,
+ *             wrapped untouched.
+ *   unwrap    wrapLen % 8 != 0, wrapLen < 16 or wrapLen - 8 > 2^32 (more than an MLI can describe) -> UAES_E_DATALENGTH,
+ *             secret untouched.  `secret` holds wrapLen - 8 bytes and ALL of them are written: the secret and, behind
+ *             *secretLen, its zero fill.  A 16-byte input is one inverse block, a longer one the inverse chain.  Then
+ *             three conditions must hold: MSB32(A) = A65959A6; 8 (n - 1) < MLI <= 8 n; the 8 n - MLI bytes behind the
+ *             secret are zero.  All three are evaluated and combined without an early exit, and the outcome is ONE
+ *             verdict that does not say which failed: UAES_E_AUTHENTICATION with *secretLen = 0 and, as uaes_kw_unwrap,
+ *             what the chain made left in secret (zeros under uaes_set_wipe_on_auth_failure(1)).  On the GPU the
+ *             verdict is computed by the kernel.
+ * kek: host memory.  Data pointers host or device memory at any byte offset; the buffers are disjoint, or the in-place
+ * form secret == (uint8_t *)wrapped + 8 (a wrap then writes the zero fill into `wrapped`; a wrap of at most 8 bytes reads
+ * its input before it writes); any other overlap is undefined.  No byte behind the secretLen bytes of `secret` is read.
+ * The host policy applies as for KW (`chains`).  Checks in KW's order: the key, the lengths, NULL pointers (secretLen
+ * included), all before the device is touched.  Arrangements as KW's, by the padded length (uaes_debug_plan_kwp).
+ * Batches: always on the GPU, one launch, sixteen lanes per record, a length per record.
+ *   wrap_batch    secret m at m * secret_bytes, secret_bytes = 1 .. 256 and need not be a multiple of 8 (UAES_E_ARG
+ *                 otherwise); wrapped record m at m * uaes_kwp_wrapped_len(secret_bytes).  lens == NULL: every secret is
+ *                 secret_bytes long.  Else lens[m] = 1 .. secret_bytes (host memory, or 4-byte-aligned device memory),
+ *                 record m writes uaes_kwp_wrapped_len(lens[m]) bytes and the rest of its slot is not written (a host
+ *                 output is copied in first, as the CCM batch does).  An entry of 0 or above secret_bytes writes nothing
+ *                 for that record; every other record is finished and the call returns UAES_E_DATALENGTH.
+ *   unwrap_batch  wrapped_bytes = a multiple of 8 in 16 .. 264 (UAES_E_ARG otherwise); wrapped record m at
+ *                 m * wrapped_bytes, secret m at m * (wrapped_bytes - 8).  wlens == NULL: every record is wrapped_bytes
+ *                 long; else an entry that is no multiple of 8, below 16 or above wrapped_bytes makes that record fail
+ *                 unwritten.  lens_out[m] = the MLI of an authentic record, 0 otherwise; verdicts[m] = 1 / 0;
+ *                 UAES_E_AUTHENTICATION if any record failed.  A record writes its wlens[m] - 8 bytes (zeros for a
+ *                 failed one under the wipe switch).
+ * nkeys == 0 returns 0.  Arrays host or device memory; no in-place form; no byte outside the arrays is read or written
+ * (a secret whose last semiblock is short is loaded bytewise, never rounded up).  Measured beside KW (profiles/kw_rate.md):
+ * 13 .. 15 us for one secret of 7 bytes, 19 .. 25 us at 20 and 32 bytes; 2^20 records of 32 bytes wrap in 0.91 ms and
+ * unwrap in 0.88 ms, 1.07 and 1.02 times the KW batch of that shape. */
+#ifndef UAES_STATIC_INLINE
+#if defined(__cplusplus) || (defined(__STDC_VERSION__) && __STDC_VERSION__ >= 199901L)
+#define UAES_STATIC_INLINE static inline
+#else
+#define UAES_STATIC_INLINE static __inline
+#endif
+#endif
+/* 8 * ceil(len / 8) + 8; 0 for len == 0 or len > 2^32 - 1 */
+UAES_STATIC_INLINE size_t uaes_kwp_wrapped_len(size_t secretLen)
+{
+    const uint64_t m = secretLen;
+    return m == 0 || m > 0xFFFFFFFFu ? 0 : (size_t)((m + 7) / 8 * 8 + 8);
+}
+int uaes_kwp_wrap(int keybits, const uint8_t *kek, const void *secret, size_t secretLen, void *wrapped);
+int uaes_kwp_unwrap(int keybits, const uint8_t *kek, const void *wrapped, size_t wrapLen, void *secret, size_t *secretLen);
+int uaes_kwp_wrap_batch(int keybits, const uint8_t *kek, size_t nkeys, size_t secret_bytes,
+                        const uint32_t *lens, const void *secrets, void *wrapped);
+int uaes_kwp_unwrap_batch(int keybits, const uint8_t *kek, size_t nkeys, size_t wrapped_bytes,
+                          const uint32_t *wlens, const void *wrapped, void *secrets,
+                          uint32_t *lens_out, uint8_t *verdicts);
 
 /* ---- FF1: replaces AES_FPE_encrypt / AES_FPE_decrypt (SP 800-38G, FF_X 1) ------
  * micro_aes.c:2091-2147, :2267-2347.  Format-preserving encryption of len numerals, ONE BYTE PER NUMERAL.  radix =
@@ -922,6 +980,12 @@ const char *uaes_debug_plan_chain(int what, int dir, size_t a, size_t b, int out
  * no sense: a length that is no multiple of 8 or below 16, a batch record above the limit.  Works without a device (a
  * 256-CU MI355X).  tests/test_gpu_kw.py finds the two boundaries by walking this. */
 const char *uaes_debug_plan_kw(int dir, size_t len, size_t nkeys, int out[3]);
+/* The planner of key wrap with padding (csrc/uaes_plan.h): dir 0 wrap / 1 unwrap; len = bytes of the secret for a wrap,
+ * wrapLen - 8 for an unwrap; nkeys 0 = uaes_kwp_wrap / uaes_kwp_unwrap, nkeys >= 1 = a batch of that many slots of len
+ * bytes.  out as above.  Returns "kwp.block" (padded length 8: one block, no chain), "kwp.lds", "kwp.global" or
+ * "kwp.batch", or NULL: a length of 0 or beyond the MLI's range, an unwrap length that is no multiple of 8, a batch slot
+ * above the limit.  Works without a device.  tests/test_gpu_kwp.py takes its boundaries from this. */
+const char *uaes_debug_plan_kwp(int dir, size_t len, size_t nkeys, int out[3]);
 /* The planner of FF1 (csrc/uaes_plan.h, its own rows): dir 0 encrypt / 1 decrypt; len = numerals of one text; nrec 0 =
  * uaes_ff1_encrypt / uaes_ff1_decrypt, nrec >= 1 = a batch of that many records.  out (may be NULL) receives
  * { launches, workgroups, threads per workgroup } (a batch: sixteen threads per record).  Returns "ff1.batch" (sixteen

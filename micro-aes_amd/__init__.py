@@ -53,6 +53,7 @@ EXPORTS = [
     "uaes_eax_encrypt_batch", "uaes_eax_decrypt_batch", "uaes_siv_encrypt_batch", "uaes_siv_decrypt_batch",
     "uaes_debug_plan_eax_siv", "uaes_debug_plan_chain",
     "uaes_kw_wrap", "uaes_kw_unwrap", "uaes_kw_wrap_batch", "uaes_kw_unwrap_batch", "uaes_debug_plan_kw",
+    "uaes_kwp_wrap", "uaes_kwp_unwrap", "uaes_kwp_wrap_batch", "uaes_kwp_unwrap_batch", "uaes_debug_plan_kwp",
     "uaes_ff1_encrypt", "uaes_ff1_decrypt", "uaes_ff1_encrypt_batch", "uaes_ff1_decrypt_batch", "uaes_debug_plan_ff1",
     "uaes_ff3_maxlen", "uaes_ff3_encrypt", "uaes_ff3_decrypt", "uaes_ff3_encrypt_batch", "uaes_ff3_decrypt_batch", "uaes_debug_plan_ff3",
     "uaes_mgpu_ctr_xcrypt_at", "uaes_mgpu_xts_sectors", "uaes_mgpu_ctr_encrypt_gather", "uaes_debug_gather_stats", "uaes_debug_gcm_look", "uaes_debug_gcm_chunk_folds",
@@ -197,6 +198,12 @@ def engine():
     L.uaes_kw_unwrap_batch.argtypes = [i, vp, sz, sz, vp, vp, vp]
     L.uaes_debug_plan_kw.argtypes = [i, sz, sz, C.POINTER(C.c_int)]
     L.uaes_debug_plan_kw.restype = C.c_char_p
+    L.uaes_kwp_wrap.argtypes = [i, vp, vp, sz, vp]
+    L.uaes_kwp_unwrap.argtypes = [i, vp, vp, sz, vp, C.POINTER(sz)]
+    L.uaes_kwp_wrap_batch.argtypes = [i, vp, sz, sz, vp, vp, vp]
+    L.uaes_kwp_unwrap_batch.argtypes = [i, vp, sz, sz, vp, vp, vp, vp, vp]
+    L.uaes_debug_plan_kwp.argtypes = [i, sz, sz, C.POINTER(C.c_int)]
+    L.uaes_debug_plan_kwp.restype = C.c_char_p
     L.uaes_debug_plan_ocb.argtypes = [i, sz, sz, i, C.POINTER(C.c_int)]
     L.uaes_debug_plan_ocb.restype = C.c_char_p
     L.uaes_debug_plan_xts.argtypes = [sz, sz, i, C.POINTER(C.c_uint64)]
@@ -286,7 +293,7 @@ def engine():
             continue
         if n not in ("uaes_last_error", "uaes_version", "uaes_gcm_key_free", "uaes_gcm_stream_abort", "uaes_debug_gather_stats", "uaes_debug_gcm_look",
                      "uaes_debug_arrangement_name", "uaes_debug_plan_disable", "uaes_debug_plan_poly1305",
-                     "uaes_debug_plan_eax_siv", "uaes_debug_plan_chain", "uaes_debug_plan_kw", "uaes_debug_plan_ff1",
+                     "uaes_debug_plan_eax_siv", "uaes_debug_plan_chain", "uaes_debug_plan_kw", "uaes_debug_plan_kwp", "uaes_debug_plan_ff1",
                      "uaes_debug_plan_ff3", "uaes_ff3_maxlen", "uaes_debug_plan_gcmsiv_batch", "uaes_debug_plan_ocb", "uaes_debug_plan_xts",
                      "uaes_debug_gcm_stream_tables", "uaes_debug_plan_ocb_batch", "uaes_debug_plan_gcm_multikey_batch", "uaes_debug_plan_cipher_batch"):
             getattr(L, n).restype = i
@@ -868,6 +875,66 @@ def kw_plan(length, nkeys=0, unwrap=False):
     batch): (arrangement, launches, workgroups, threads per workgroup), or None for arguments that make no sense."""
     out = (C.c_int * 3)()
     name = engine().uaes_debug_plan_kw(int(bool(unwrap)), length, nkeys, out)
+    return None if name is None else (name.decode(), out[0], out[1], out[2])
+
+
+def kwp_wrapped_len(n):
+    """uaes_kwp_wrapped_len: bytes of the wrapped form of a secret of n bytes; 0 for a length KWP does not take"""
+    return (n + 7) // 8 * 8 + 8 if 1 <= n <= 0xFFFFFFFF else 0
+
+
+def kwp_wrap(kek, secret, prefill=0):
+    """Key wrap with padding, RFC 5649 (uaes_kwp_wrap): a secret of any length from 1 byte.  Returns (code, output buffer
+    of 8 * ceil(len / 8) + 8 bytes): code 1 for an empty secret, the buffer untouched then."""
+    n = (len(secret) + 7) // 8 * 8 + 8
+    o = _out(n, prefill)
+    rc = _check(engine().uaes_kwp_wrap(_bits(kek), _in(kek), _in(secret), len(secret), o), "uaes_kwp_wrap")
+    return rc, bytes(o)[:n]
+
+
+def kwp_unwrap(kek, wrapped, prefill=0):
+    """uaes_kwp_unwrap.  Returns (code, output buffer of len(wrapped) - 8 bytes, length of the secret): the secret is the
+    first `length` bytes of the buffer and zeros follow; code 0x1A comes with length 0 and what the chain made (zeros
+    under the wipe switch), code 1 (a length that is no multiple of 8 or below 16) with the buffer untouched."""
+    n = max(len(wrapped) - 8, 0)
+    o = _out(n, prefill)
+    ln = C.c_size_t(0)
+    rc = _check(engine().uaes_kwp_unwrap(_bits(kek), _in(kek), _in(wrapped), len(wrapped), o, C.byref(ln)), "uaes_kwp_unwrap")
+    return rc, bytes(o)[:n], ln.value
+
+
+def kwp_batch(kek, records, unwrap=False, slot=None, prefill=0):
+    """Key wrap with padding of many records under one key-encryption key, each with a length of its own
+    (uaes_kwp_*_batch).  slot = bytes per input record slot (default: the longest record).  wrap: returns (code, wrapped
+    records); unwrap: returns (code, unwrapped records of len(wrapped) - 8 bytes each, lengths of the secrets, verdicts).
+    A record whose length the call refuses comes back as the prefill."""
+    n = len(records)
+    if n == 0:
+        return (0, [], [], []) if unwrap else (0, [])
+    slot = max(len(r) for r in records) if slot is None else slot
+    if any(len(r) > slot for r in records):
+        raise ValueError("a record longer than its slot")
+    lens = None if all(len(r) == slot for r in records) else (C.c_uint32 * n)(*[len(r) for r in records])
+    rb = b"".join(bytes(r) + bytes(slot - len(r)) for r in records)
+    oslot = max(slot - 8, 0) if unwrap else (slot + 7) // 8 * 8 + 8
+    o = _out(n * oslot, prefill)
+    L = engine()
+    if not unwrap:
+        rc = _check(L.uaes_kwp_wrap_batch(_bits(kek), _in(kek), n, slot, lens, _in(rb), o), "uaes_kwp_wrap_batch")
+        raw = bytes(o)
+        return rc, [raw[m * oslot:m * oslot + (len(r) + 7) // 8 * 8 + 8] for m, r in enumerate(records)]
+    v, lo = _out(n), (C.c_uint32 * n)()
+    rc = _check(L.uaes_kwp_unwrap_batch(_bits(kek), _in(kek), n, slot, lens, _in(rb), o, lo, v), "uaes_kwp_unwrap_batch")
+    raw = bytes(o)
+    return rc, [raw[m * oslot:m * oslot + max(len(r) - 8, 0)] for m, r in enumerate(records)], list(lo), list(bytes(v)[:n])
+
+
+def kwp_plan(length, nkeys=0, unwrap=False):
+    """What a key wrap with padding would run (uaes_debug_plan_kwp; length = bytes of the secret, or of the wrapped form
+    - 8 for an unwrap; nkeys 0: the one-secret calls, else a batch): (arrangement, launches, workgroups, threads per
+    workgroup), or None for arguments that make no sense."""
+    out = (C.c_int * 3)()
+    name = engine().uaes_debug_plan_kwp(int(bool(unwrap)), length, nkeys, out)
     return None if name is None else (name.decode(), out[0], out[1], out[2])
 
 

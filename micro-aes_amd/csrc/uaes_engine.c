@@ -1481,6 +1481,14 @@ const char *uaes_debug_plan_kw(int dir, size_t len, size_t nkeys, int out[3])
     if (out) { out[0] = p.launches; out[1] = (int)p.grid; out[2] = (int)p.steps; }
     return uaesk_kw_arrangement_name(p.arrangement);
 }
+const char *uaes_debug_plan_kwp(int dir, size_t len, size_t nkeys, int out[3])
+{
+    uaes_plan p;
+    memset(&p, 0, sizeof p);
+    if (uaesk_plan_kwp(dir, len, nkeys, &p)) return NULL;
+    if (out) { out[0] = p.launches; out[1] = (int)p.grid; out[2] = (int)p.steps; }
+    return uaesk_kwp_arrangement_name(p.arrangement);
+}
 const char *uaes_debug_plan_ff1(int dir, unsigned radix, size_t len, size_t nrec, int out[3])
 {
     uaes_plan p;

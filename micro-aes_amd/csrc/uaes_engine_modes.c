@@ -1,8 +1,8 @@
 /*
  * uaes_engine_modes.c -- entry points of the modes other than GCM: ECB, CTR, XTS, CMAC, Poly1305, CCM, EAX, SIV,
- * CBC / CFB / OFB, the chain batches and OCB.  They mirror the reference's mode drivers (AES_ECB_*, AES_CTR_*,
- * AES_XTS_* ...; micro_aes.c:636-680, :962-990, :1066-1093): argument checking, the reference's error behaviour
- * and buffer plumbing on top of the core (uaes_engine.c, through uaes_engine.h).
+ * CBC / CFB / OFB, the chain batches, OCB, key wrap (KW and KWP), FF1 and FF3-1.  They mirror the reference's mode
+ * drivers (AES_ECB_*, AES_CTR_*, AES_XTS_* ...; micro_aes.c:636-680, :962-990, :1066-1093): argument checking, the
+ * reference's error behaviour and buffer plumbing on top of the core (uaes_engine.c, through uaes_engine.h).
  */
 #include "uaes_engine.h"
 
@@ -1317,6 +1317,126 @@ int uaes_kw_unwrap_batch(int keybits, const uint8_t *kek, size_t nkeys, size_t w
 {
     if (wrapped_bytes % 8 || wrapped_bytes / 8 < 3) return UAES_E_DATALENGTH;
     return kw_batch(1, keybits, kek, nkeys, wrapped_bytes - 8, wrapped, secrets, verdicts);
+}
+
+/* ------------------------------------------------------------------------ */
+/* key wrap with padding, RFC 5649 / SP 800-38F KWP (the reference has none)    */
+/* ------------------------------------------------------------------------ */
+/* Key wrap's chain, buffers and host path (kw_io by the padded length), with a secret of any length, the one-block case
+ * and a verdict of three conditions that the kernel computes: status[0] = 0 / 0x1A, status[1] = the length indicator. */
+int uaes_kwp_wrap(int keybits, const uint8_t *kek, const void *secret, size_t secretLen, void *wrapped)
+{
+    context *c;
+    lane *L;
+    KEYSCHED(ks);
+    io_plan io;
+    int rc;
+    const size_t out_len = uaes_kwp_wrapped_len(secretLen);
+    if ((rc = expand_key(&ks, kek, keybits)) != 0) return rc;
+    if (out_len == 0) return UAES_E_DATALENGTH;
+    if (!secret || !wrapped) return fail(UAES_E_ARG, "NULL pointer");
+    if (host_take(secret, wrapped, out_len, 1)) {
+        const uaesh_key hk = host_key(&ks);
+        return host_result(uaesh_kwp_wrap(&hk, (const uint8_t *)secret, secretLen, (uint8_t *)wrapped));
+    }
+    if ((rc = enter(&c, &L)) != 0) return rc;
+    do {
+        if ((rc = kw_io(L, secret, secretLen, wrapped, out_len, out_len - 8, &io)) != 0) break;
+        int k = uaesk_kwp(L->stream, &c->tb, ks.nr, &ks.ek, &ks.dk, 0, io.din, secretLen, io.dout, NULL);
+        if ((rc = launched("key wrap with padding", k)) != 0) break;
+        rc = finish_io(&io, out_len);
+    } while (0);
+    DONE(L, rc);
+}
+
+int uaes_kwp_unwrap(int keybits, const uint8_t *kek, const void *wrapped, size_t wrapLen, void *secret, size_t *secretLen)
+{
+    context *c;
+    lane *L;
+    KEYSCHED(ks);
+    io_plan io;
+    int rc, status[2] = { 0, 0 };
+    size_t len;
+    if ((rc = expand_key(&ks, kek, keybits)) != 0) return rc;
+    if (wrapLen % 8 || wrapLen < 16 || (uint64_t)(wrapLen - 8) > (uint64_t)1 << 32) return UAES_E_DATALENGTH;
+    len = wrapLen - 8;
+    if (!secret || !wrapped || !secretLen) return fail(UAES_E_ARG, "NULL pointer");
+    *secretLen = 0;
+    if (host_take(wrapped, secret, wrapLen, 1)) {
+        const uaesh_key hk = host_key(&ks);
+        uint32_t mli = 0;
+        rc = uaesh_kwp_unwrap(&hk, (const uint8_t *)wrapped, wrapLen, (uint8_t *)secret, &mli);
+        if (rc == UAES_E_AUTHENTICATION && wipe_on_auth_failure()) memset(secret, 0, len);
+        *secretLen = mli;
+        return host_result(rc);
+    }
+    if ((rc = enter(&c, &L)) != 0) return rc;
+    do {
+        if ((rc = kw_io(L, wrapped, wrapLen, secret, len, len, &io)) != 0) break;
+        int k = uaesk_kwp(L->stream, &c->tb, ks.nr, &ks.ek, &ks.dk, 1, io.din, len, io.dout, L->d_status);
+        if ((rc = launched("key unwrap with padding", k)) != 0) break;
+        if ((rc = lane_fetch(L, status, L->d_status, sizeof status)) != 0) break;
+        io.drained = 1;
+        if ((rc = status[0] ? finish_io_unauthenticated(&io, len) : finish_io(&io, len)) != 0) break;
+        if (status[0]) rc = UAES_E_AUTHENTICATION;
+        else *secretLen = (uint32_t)status[1];
+    } while (0);
+    DONE(L, rc);
+}
+
+/* Batches: nkeys slots under one key-encryption key, a length per record (lens, NULL: every record fills its slot), always
+ * on the GPU.  rec = bytes of a secret's slot (unwrap: the wrapped slot - 8).  The status word takes two bits: 1 for a
+ * record that does not authenticate, 2 for a wrap length of 0 or beyond the slot. */
+static int kwp_batch(int unwrap, int keybits, const uint8_t *kek, size_t nkeys, size_t rec, const uint32_t *lens,
+                     const void *in, void *outp, uint32_t *lens_out, uint8_t *verdicts)
+{
+    context *c;
+    lane *L;
+    KEYSCHED(ks);
+    int rc, k, bad;
+    const size_t wslot = uaes_kwp_wrapped_len(rec), in_rec = unwrap ? wslot : rec, out_rec = unwrap ? rec : wslot;
+    const int status = unwrap || lens != NULL;
+    if ((rc = expand_key(&ks, kek, keybits)) != 0) return rc;
+    if (nkeys > (size_t)-1 / wslot) return fail(UAES_E_ARG, "batch size overflows");
+    if (nkeys == 0) return 0;
+    if (!in || !outp || (unwrap && (!verdicts || !lens_out))) return fail(UAES_E_ARG, "NULL pointer");
+    if ((rc = enter(&c, &L)) != 0) return rc;
+    row_array a[3] = { { lens, lens ? nkeys * sizeof *lens : 0, 0, NULL }, { lens_out, unwrap ? nkeys * sizeof *lens_out : 0, 1, NULL },
+                       { verdicts, unwrap ? nkeys : 0, 1, NULL } };
+    /* with lens a record may leave part of its slot, or all of it, unwritten: a host output starts as the caller's bytes */
+    row_text t = { in, outp, nkeys * in_rec, nkeys * out_rec, lens != NULL, NULL, NULL };
+    if ((lens && is_device_ptr(lens) && ((uintptr_t)lens & 3u)) || (lens_out && is_device_ptr(lens_out) && ((uintptr_t)lens_out & 3u))) {
+        rc = fail(UAES_E_ARG, "a device array of lengths must be 4-byte aligned");
+        goto out;
+    }
+    /* a wrap without lens has nothing to report: no status word, as the key-wrap batch */
+    if ((rc = row_stage(L, a, 3, status)) != 0) goto out;
+    if ((rc = row_texts(L, &t)) != 0) goto out;
+    k = uaesk_kwp_batch(L->stream, &c->tb, ks.nr, &ks.ek, &ks.dk, unwrap, wipe_on_auth_failure(), nkeys, rec, a[0].d,
+                        t.d_in, t.d_out, a[1].d, a[2].d, L->d_status);
+    if ((rc = launched("key wrap with padding batch", k)) != 0) goto out;
+    if ((rc = row_finish(L, &t, a, 3, status, &bad)) != 0) goto out;
+    rc = (bad & 1) ? UAES_E_AUTHENTICATION : (bad & 2) ? UAES_E_DATALENGTH : 0;
+out:
+    DONE(L, rc);
+}
+
+int uaes_kwp_wrap_batch(int keybits, const uint8_t *kek, size_t nkeys, size_t secret_bytes, const uint32_t *lens,
+                        const void *secrets, void *wrapped)
+{
+    if (secret_bytes == 0 || secret_bytes > UAES_KW_BATCH_MAX)
+        return fail(UAES_E_ARG, "batched key wrap with padding: a record holds 1 .. %zu bytes of secret (got %zu)",
+                    (size_t)UAES_KW_BATCH_MAX, secret_bytes);
+    return kwp_batch(0, keybits, kek, nkeys, secret_bytes, lens, secrets, wrapped, NULL, NULL);
+}
+
+int uaes_kwp_unwrap_batch(int keybits, const uint8_t *kek, size_t nkeys, size_t wrapped_bytes, const uint32_t *wlens,
+                          const void *wrapped, void *secrets, uint32_t *lens_out, uint8_t *verdicts)
+{
+    if (wrapped_bytes % 8 || wrapped_bytes < 16 || wrapped_bytes > UAES_KW_BATCH_MAX + 8)
+        return fail(UAES_E_ARG, "batched key unwrap with padding: a wrapped record is a multiple of 8 in 16 .. %zu bytes (got %zu)",
+                    (size_t)UAES_KW_BATCH_MAX + 8, wrapped_bytes);
+    return kwp_batch(1, keybits, kek, nkeys, wrapped_bytes - 8, wlens, wrapped, secrets, lens_out, verdicts);
 }
 
 /* ------------------------------------------------------------------------ */

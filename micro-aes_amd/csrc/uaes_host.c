@@ -977,22 +977,43 @@ static void kw_xor_step(uint8_t a[16], uint64_t t)
     for (i = 7; i >= 0 && t; --i, t >>= 8) a[i] ^= (uint8_t)t;
 }
 
-/* secret and wrapped are disjoint, or secret == wrapped + 8 (the reference's own in-place form) */
-int uaesh_kw_wrap(const uaesh_key *k, const uint8_t *secret, size_t len, uint8_t *wrapped)
+/* W of SP 800-38F over the n semiblocks at r0, 6 n steps; A = a[0..7] on entry and on return (a[8..15] is scratch) */
+static void kw_chain(const uaesh_key *k, uint8_t a[16], uint8_t *r0, size_t n)
 {
-    const size_t n = len / 8;
-    uint8_t a[16], *r = wrapped + 8;
+    uint8_t *r = r0, *const last = r0 + 8 * (n - 1);
     uint64_t t;
-    if (n < 2 || len % 8) return 1;                     /* M_DATALENGTH_ERROR */
-    memset(a, 0xA6, 8);
-    memmove(r, secret, len);
     for (t = 1; t <= 6 * (uint64_t)n; ++t) {
         memcpy(a + 8, r, 8);
         uaesh_encrypt(k->ek, k->nr, a, a);
         memcpy(r, a + 8, 8);
         kw_xor_step(a, t);
-        r = (r == wrapped + len ? wrapped : r) + 8;
+        r = r == last ? r0 : r + 8;
     }
+}
+
+/* its inverse */
+static void kw_chain_inv(const uaesh_key *k, uint8_t a[16], uint8_t *r0, size_t n)
+{
+    uint8_t *r = r0, *const end = r0 + 8 * n;
+    uint64_t t;
+    for (t = 6 * (uint64_t)n; t; --t) {
+        r = (r == r0 ? end : r) - 8;
+        kw_xor_step(a, t);
+        memcpy(a + 8, r, 8);
+        uaesh_decrypt(k->dk, k->nr, a, a);
+        memcpy(r, a + 8, 8);
+    }
+}
+
+/* secret and wrapped are disjoint, or secret == wrapped + 8 (the reference's own in-place form) */
+int uaesh_kw_wrap(const uaesh_key *k, const uint8_t *secret, size_t len, uint8_t *wrapped)
+{
+    const size_t n = len / 8;
+    uint8_t a[16];
+    if (n < 2 || len % 8) return 1;                     /* M_DATALENGTH_ERROR */
+    memset(a, 0xA6, 8);
+    memmove(wrapped + 8, secret, len);
+    kw_chain(k, a, wrapped + 8, n);
     memcpy(wrapped, a, 8);
     memset(a, 0, sizeof a);
     return 0;
@@ -1002,21 +1023,70 @@ int uaesh_kw_wrap(const uaesh_key *k, const uint8_t *secret, size_t len, uint8_t
 int uaesh_kw_unwrap(const uaesh_key *k, const uint8_t *wrapped, size_t wrap_len, uint8_t *secret)
 {
     const size_t n = wrap_len / 8;
-    uint8_t a[16], *r = secret, *end, bad = 0;
-    uint64_t t;
+    uint8_t a[16], bad = 0;
     int i;
     if (n < 3 || wrap_len % 8) return 1;
-    end = secret + wrap_len - 8;
     memcpy(a, wrapped, 8);
     memmove(secret, wrapped + 8, wrap_len - 8);
-    for (t = 6 * (uint64_t)(n - 1); t; --t) {
-        r = (r == secret ? end : r) - 8;
-        kw_xor_step(a, t);
-        memcpy(a + 8, r, 8);
-        uaesh_decrypt(k->dk, k->nr, a, a);
-        memcpy(r, a + 8, 8);
-    }
+    kw_chain_inv(k, a, secret, n - 1);
     for (i = 0; i < 8; ++i) bad |= a[i] ^ 0xA6;
+    memset(a, 0, sizeof a);
+    return bad ? 0x1A : 0;
+}
+
+/* ---- key wrap with padding, RFC 5649 / SP 800-38F KWP (the reference has none) ----------------------------------------- */
+/* A = A6 59 59 A6 || len (32 bits, big-endian) over the secret zero-filled to n = ceil(len / 8) semiblocks: the chain
+ * above for n >= 2, one block of the cipher for n = 1.  Writes 8 n + 8 bytes; the zero fill lands in `wrapped` first, so
+ * the in-place form works.  1 for len = 0 or above 2^32 - 1, nothing written */
+int uaesh_kwp_wrap(const uaesh_key *k, const uint8_t *secret, size_t len, uint8_t *wrapped)
+{
+    const size_t n = (len + 7) / 8;
+    uint8_t a[16];
+    if (len == 0 || (uint64_t)len > 0xFFFFFFFFu) return 1;
+    a[0] = a[3] = 0xA6; a[1] = a[2] = 0x59;
+    a[4] = (uint8_t)(len >> 24); a[5] = (uint8_t)(len >> 16); a[6] = (uint8_t)(len >> 8); a[7] = (uint8_t)len;
+    if (n == 1) {
+        memset(a + 8, 0, 8);
+        memcpy(a + 8, secret, len);                     /* read before anything is written */
+        uaesh_encrypt(k->ek, k->nr, a, a);
+        memcpy(wrapped, a, 16);
+    } else {
+        memmove(wrapped + 8, secret, len);
+        memset(wrapped + 8 + len, 0, 8 * n - len);
+        kw_chain(k, a, wrapped + 8, n);
+        memcpy(wrapped, a, 8);
+    }
+    memset(a, 0, sizeof a);
+    return 0;
+}
+
+/* writes the wrap_len - 8 bytes the chain makes whatever the verdict; *secret_len = the length indicator of an authentic
+ * secret, 0 otherwise.  The three conditions -- the constant, 8 (n - 1) < MLI <= 8 n, zeros behind the secret -- are all
+ * evaluated and ORed: one verdict, no early exit.  1 for a length that is no multiple of 8, below 16 or beyond what the
+ * indicator can describe */
+int uaesh_kwp_unwrap(const uaesh_key *k, const uint8_t *wrapped, size_t wrap_len, uint8_t *secret, uint32_t *secret_len)
+{
+    const size_t n = wrap_len / 8 - 1;
+    const uint64_t top = 8 * (uint64_t)n;
+    uint8_t a[16];
+    uint64_t mli;
+    unsigned bad, pad, i;
+    if (wrap_len % 8 || wrap_len < 16 || top > (uint64_t)1 << 32) return 1;
+    if (n == 1) {
+        memcpy(a, wrapped, 16);
+        uaesh_decrypt(k->dk, k->nr, a, a);
+        memcpy(secret, a + 8, 8);
+    } else {
+        memcpy(a, wrapped, 8);
+        memmove(secret, wrapped + 8, wrap_len - 8);
+        kw_chain_inv(k, a, secret, n);
+    }
+    mli = ((uint32_t)a[4] << 24) | ((uint32_t)a[5] << 16) | ((uint32_t)a[6] << 8) | a[7];
+    bad = (unsigned)(a[0] ^ 0xA6) | (unsigned)(a[1] ^ 0x59) | (unsigned)(a[2] ^ 0x59) | (unsigned)(a[3] ^ 0xA6);
+    bad |= (unsigned)(mli + 8 <= top) | (unsigned)(mli > top);
+    pad = (unsigned)(top - mli) & 7u;                   /* meaningful when the indicator is in range */
+    for (i = 0; i < 8; ++i) bad |= secret[8 * (n - 1) + i] & (0u - (unsigned)(i + pad >= 8));
+    *secret_len = bad ? 0 : (uint32_t)mli;
     memset(a, 0, sizeof a);
     return bad ? 0x1A : 0;
 }

@@ -65,6 +65,12 @@ int  uaesh_ocb(const uaesh_key *k, int decrypt, const uint8_t *nonce, size_t non
 int  uaesh_kw_wrap(const uaesh_key *k, const uint8_t *secret, size_t len, uint8_t *wrapped);                  /* :1829-1855 */
 int  uaesh_kw_unwrap(const uaesh_key *k, const uint8_t *wrapped, size_t wrap_len, uint8_t *secret);           /* :1865-1894 */
 
+/* RFC 5649 key wrap with padding over the same chain (the reference has none): a secret of 1 .. 2^32 - 1 bytes becomes
+ * 8 ceil(len / 8) + 8 bytes.  unwrap writes wrap_len - 8 bytes (the secret and its zero fill) whatever the verdict and
+ * *secret_len = the length indicator / 0.  0, 1 (the length; nothing written) or 0x1A; in place as above */
+int  uaesh_kwp_wrap(const uaesh_key *k, const uint8_t *secret, size_t len, uint8_t *wrapped);
+int  uaesh_kwp_unwrap(const uaesh_key *k, const uint8_t *wrapped, size_t wrap_len, uint8_t *secret, uint32_t *secret_len);
+
 /* FF1, SP 800-38G: len numerals of one byte each (digit values, or bytes of `alphabet` = radix distinct bytes), in
  * place allowed.  0; 1 (len below uaesh_ff1_minlen(radix), above 4096, or a tweak of 2^32 bytes or more); -2 (radix
  * outside 2..256, a repeated alphabet byte); 0x1E / 0x1D (encrypt / decrypt: a byte that is no numeral).  Nothing is

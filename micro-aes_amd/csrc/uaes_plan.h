@@ -61,6 +61,10 @@
  *   KW    kw.lds                k_kw<LDS> (one wave; the semiblocks in LDS)         (1)    secret <= UAES_KW_LDS_MAX (4 KiB)
  *         kw.global             k_kw<in place> (one wave; loads a chunk ahead)      (1)    beyond
  *         kw.batch              k_kw_batch (sixteen lanes per record)               (1)    uaes_kw_*_batch, <= UAES_KW_BATCH_MAX (256 B)
+ *   KWP   kwp.block             k_kwp<block> (one wave; one block, no chain)        (1)    secret <= 8 B (padded length 8)
+ *         kwp.lds               k_kwp<LDS> (one wave; the semiblocks in LDS)        (1)    padded length <= UAES_KW_LDS_MAX (4 KiB)
+ *         kwp.global            k_kwp<in place> (one wave; loads a chunk ahead)     (1)    beyond
+ *         kwp.batch             k_kwp_batch (sixteen lanes per record, lengths per record) (1)  uaes_kwp_*_batch, <= UAES_KW_BATCH_MAX (256 B)
  *   FF1   ff1.batch             k_ff1<16> (sixteen lanes per record, four per wave) (1)    uaes_ff1_*_batch; one text of <= UAES_FF1_BATCH_MAX (128) numerals
  *         ff1.wave              k_ff1<64> (one wave per text)                       (1)    one longer text, <= UAES_FF1_MAX (4096) numerals
  *   FF3-1 ff3.batch             k_ff3 (sixteen lanes per record, four per wave)     (1)    uaes_ff3_*_batch; one text (<= 192 numerals) is a batch of one
@@ -69,7 +73,8 @@
  * So do the EAX and SIV (RFC 5297) rows (uaesk_plan_eax_siv, uaes_eax_siv.hip; uaes_debug_plan_eax_siv), and the
  * CBC / CFB / OFB / CMAC / CCM / batch rows (uaesk_plan_chain, uaes_chain.hip, and uaesk_plan_mac / uaesk_plan_ccm_batch,
  * uaes_mac.hip; uaes_debug_plan_chain); tests/test_gpu_chains.py derives its sizes and message counts from them.  Key wrap has
- * uaesk_plan_kw (uaes_kw.hip; uaes_debug_plan_kw), and tests/test_gpu_kw.py finds its two boundaries by walking it.
+ * uaesk_plan_kw (uaes_kw.hip; uaes_debug_plan_kw), and tests/test_gpu_kw.py finds its two boundaries by walking it; key
+ * wrap with padding has uaesk_plan_kwp beside it (uaes_debug_plan_kwp; tests/test_gpu_kwp.py).
  * FF1 has uaesk_plan_ff1 (uaes_ff1.hip; uaes_debug_plan_ff1); tests/test_gpu_ff1.py walks it likewise.
  * FF3-1 has uaesk_plan_ff3 (uaes_ff3.hip; uaes_debug_plan_ff3): one row, whose limits depend on the radix.
  * The GCM-SIV batches have uaesk_plan_gcmsiv_batch (uaes_gcmsiv_batch.hip; uaes_debug_plan_gcmsiv_batch): one row.
@@ -82,7 +87,7 @@
  * uaesk_plan_gcm_multikey_batch (uaes_gcm_multikey.hip; uaes_debug_plan_gcm_multikey_batch), and the batches of the plain
  * cipher modes: uaesk_plan_cipher_batch (uaes_cipher_batch.hip; uaes_debug_plan_cipher_batch).
  * The rows that say "sixteen lanes per record / message" -- eax.batch, s2v.batch, ccm.batch, gcmsiv.batch, gcm.multikey, ocb.batch, batch.row,
- * cipher.batch, kw.batch, ff1.batch, ff3.batch -- are the row batches: grid and threads per workgroup are uaesk_row_shape's (uaes_launch.hip.h), the same
+ * cipher.batch, kw.batch, kwp.batch, ff1.batch, ff3.batch -- are the row batches: grid and threads per workgroup are uaesk_row_shape's (uaes_launch.hip.h), the same
  * for the same number of records in every one of them.
  */
 #ifndef UAES_PLAN_H
@@ -235,6 +240,17 @@ const char *uaesk_chain_arrangement_name(int id);
 enum uaes_kw_arrangement { UAES_KW_LDS = 0, UAES_KW_GLOBAL, UAES_KW_BATCH };
 int uaesk_plan_kw(int dir, size_t len, size_t nkeys, uaes_plan *p);
 const char *uaesk_kw_arrangement_name(int id);
+
+/* AES key wrap with padding (RFC 5649, SP 800-38F KWP; uaes_kw.hip).  dir: 0 wrap, 1 unwrap; len = bytes of the secret
+ * for a wrap (1 .. UAES_KWP_MAX, what the 32-bit length indicator can say) and bytes of the wrapped form - 8 for an
+ * unwrap (a multiple of 8); nkeys 0 = the one-secret calls, nkeys >= 1 = a batch whose slots hold len bytes (at most
+ * UAES_KW_BATCH_MAX).  A padded length of 8 is one block of the cipher and no chain; beyond that the arrangements are
+ * key wrap's, decided by the padded length with key wrap's limits.  Returns a HIP error code for a length of 0, an
+ * unwrap length that is no multiple of 8, a length beyond the indicator's range or a batch slot above the limit. */
+#define UAES_KWP_MAX ((size_t)0xFFFFFFFFu)
+enum uaes_kwp_arrangement { UAES_KWP_BLOCK = 0, UAES_KWP_LDS, UAES_KWP_GLOBAL, UAES_KWP_BATCH };
+int uaesk_plan_kwp(int dir, size_t len, size_t nkeys, uaes_plan *p);
+const char *uaesk_kwp_arrangement_name(int id);
 
 /* FF1, SP 800-38G (uaes_ff1.hip).  dir: 0 encrypt, 1 decrypt; len = numerals of one text (one byte each); nrec 0 = the
  * one-text calls, nrec >= 1 = a batch of nrec records of len numerals.  A text is at most UAES_FF1_MAX numerals: the

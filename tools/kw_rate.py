@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""AES key wrap (RFC 3394) rates, written as markdown (to profiles/kw_rate.md unless --out names another file):
+"""AES key wrap (RFC 3394) and key wrap with padding (RFC 5649) rates, written as markdown (to profiles/kw_rate.md unless
+--out names another file).  Key wrap:
   latency   one 32-byte secret through uaes_kw_wrap / uaes_kw_unwrap, host data and device data (host round trip
             included: the calls are synchronous)
   batch     65 536 secrets of 32 bytes, device-resident, uaes_kw_wrap_batch / uaes_kw_unwrap_batch: keys per second
@@ -7,6 +8,12 @@
             step of row_encrypt and of row_decrypt, next to the per-block time of the CMAC chain (row_encrypt) over the
             same number of blocks in the same run
   cpu       the compiled reference's AES_KEY_wrap / AES_KEY_unwrap looped on one host core (oracle/_ref)
+Key wrap with padding, in the same run (kwp_sections):
+  latency   one secret of 7, 20, 32, 4096 and 4097 bytes through uaes_kwp_wrap / uaes_kwp_unwrap, host and device data
+  batch     2^10 and 2^20 records of 20, 32 and 256 bytes, device-resident, both directions; at 32 and 256 bytes the KW
+            batch of the same shape is timed twice, once before and once after the KWP batch, and the spread of those two
+            runs is the margin the KWP batch is held against
+  mixed     2^20 records whose lengths cycle through 1, 8, 9 and 256 (lens) against 2^20 records of 256 bytes
 Every figure: warm-up, then REPS repetitions; median, minimum and maximum.  AES-128 unless said otherwise.
 Usage: kw_rate.py [--out FILE] [--quick]"""
 import ctypes as C
@@ -47,11 +54,116 @@ def dev(b):
     return torch.frombuffer(bytearray(b), dtype=torch.uint8).to("cuda")
 
 
+def kwp_sections(emit, quick):
+    """key wrap with padding beside key wrap (the module's docstring); the outputs are checked before they are timed"""
+    bits = 128
+    kek = (C.c_uint8 * 16).from_buffer_copy(bytes(range(16)))
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    emit("# AES key wrap with padding (RFC 5649): measured rates, same run\n")
+    emit("## Latency of one secret, AES-128\n")
+    emit("| call | bytes | arrangement | data | us per call |\n|---|---|---|---|---|")
+    for m in (7, 20, 32, 4096, 4097):
+        secret = bytes((37 * i + 11) & 0xFF for i in range(m))
+        rc, wrapped = uaes.kwp_wrap(bytes(kek), secret)
+        assert rc == 0 and uaes.kwp_unwrap(bytes(kek), wrapped)[0::2] == (0, m)
+        wl, ln = len(wrapped), C.c_size_t(0)
+        hs, hw, ho = (C.c_uint8 * m).from_buffer_copy(secret), (C.c_uint8 * wl).from_buffer_copy(wrapped), (C.c_uint8 * wl)()
+        ds, dw, do = dev(secret), dev(wrapped), dev(bytes(wl + 64))
+        calls = (20 if quick else 50) if m > 1024 else (100 if quick else 400)
+        name = uaes.kwp_plan(m)[0]
+        for data, a, b, o in (("host", hs, hw, ho), ("device", ptr(ds), ptr(dw), ptr(do))):
+            emit("| uaes_kwp_wrap | %d | %s | %s | %s |" % (m, name, data, cell(reps_of(lambda: L.uaes_kwp_wrap(bits, kek, a, m, o), calls))))
+            emit("| uaes_kwp_unwrap | %d | %s | %s | %s |" %
+                 (m, name, data, cell(reps_of(lambda: L.uaes_kwp_unwrap(bits, kek, b, wl, o, C.byref(ln)), calls))))
+        assert bytes(do.cpu().numpy())[:m] == secret and ln.value == m
+    emit("")
+    top = 1 << 14 if quick else 1 << 20
+    slot_max = 256
+    secrets = torch.randint(0, 256, (top * slot_max,), dtype=torch.uint8, device="cuda")
+    wrapped = torch.zeros(top * (slot_max + 8), dtype=torch.uint8, device="cuda")
+    wrapped_kw = torch.zeros(top * (slot_max + 8), dtype=torch.uint8, device="cuda")      # each family unwraps its own
+    back = torch.zeros(top * slot_max, dtype=torch.uint8, device="cuda")
+    ver = torch.zeros(top, dtype=torch.uint8, device="cuda")
+    lo = torch.zeros(top, dtype=torch.int32, device="cuda")
+    p_s, p_w, p_k, p_b, p_v, p_l = (ptr(t) for t in (secrets, wrapped, wrapped_kw, back, ver, lo))
+
+    def kw_pair(n, size):
+        assert L.uaes_kw_wrap_batch(bits, kek, n, size, p_s, p_k) == 0
+        assert L.uaes_kw_unwrap_batch(bits, kek, n, size + 8, p_k, p_b, p_v) == 0
+        assert torch.equal(back[:n * size], secrets[:n * size]) and int(ver[:n].sum()) == n
+        return (lambda: L.uaes_kw_wrap_batch(bits, kek, n, size, p_s, p_k),
+                lambda: L.uaes_kw_unwrap_batch(bits, kek, n, size + 8, p_k, p_b, p_v))
+
+    def kwp_pair(n, size, lens=None, wlens=None, expect=None):
+        ws = (size + 7) // 8 * 8 + 8
+        assert L.uaes_kwp_wrap_batch(bits, kek, n, size, lens, p_s, p_w) == 0
+        assert L.uaes_kwp_unwrap_batch(bits, kek, n, ws, wlens, p_w, p_b, p_l, p_v) == 0
+        assert int(ver[:n].sum()) == n and int(lo[:n].sum()) == (expect if expect is not None else n * size)
+        if lens is None and size % 8 == 0:
+            assert torch.equal(back[:n * size], secrets[:n * size])
+        return (lambda: L.uaes_kwp_wrap_batch(bits, kek, n, size, lens, p_s, p_w),
+                lambda: L.uaes_kwp_unwrap_batch(bits, kek, n, ws, wlens, p_w, p_b, p_l, p_v))
+
+    emit("## Batches, device-resident, AES-128: KWP beside the KW batch of the same shape\n")
+    emit("Each KW shape is timed twice, before (A) and after (B) the KWP batch of that shape.  The margin is the spread "
+         "of those two runs: (largest - smallest window) / median over the windows of both.  The KWP batch runs the same "
+         "chain plus the length check, so its median is held against the median of the two KW runs plus that margin.\n")
+    emit("| records | bytes | direction | KW A, us | KWP, us | KW B, us | KWP / KW | margin | verdict |\n|---|---|---|---|---|---|---|---|---|")
+    verdicts = []
+    for n in ((1 << 10, top) if not quick else (1 << 10,)):
+        calls = 5 if n > 1 << 16 else 40
+        for size in (20, 32, 256):
+            kwp = kwp_pair(n, size)
+            if size % 8:
+                for d in (0, 1):
+                    emit("| %d | %d | %s | - | %s | - | - | - | KW takes no such length |" %
+                         (n, size, ("wrap", "unwrap")[d], cell(reps_of(kwp[d], calls))))
+                continue
+            kw = kw_pair(n, size)
+            for d in (0, 1):
+                a = reps_of(kw[d], calls)
+                p = reps_of(kwp[d], calls)
+                b = reps_of(kw[d], calls)
+                both = a + b
+                margin = (max(both) - min(both)) / statistics.median(both)
+                ratio = statistics.median(p) / statistics.median(both)
+                ok = ratio <= 1 + margin
+                verdicts.append((n, size, d, ratio, margin, ok))
+                emit("| %d | %d | %s | %s | %s | %s | %.3f | %.3f | %s |" %
+                     (n, size, ("wrap", "unwrap")[d], cell(a), cell(p), cell(b), ratio, margin, "within" if ok else "EXCEEDS"))
+    emit("")
+    over = [v for v in verdicts if not v[5]]
+    if over:
+        emit("KWP exceeds the margin at %s.  This tool times whole calls: it does not say where inside the call the "
+             "time goes; that was not found here.\n" %
+             ", ".join("%d x %d B %s (%.3f against 1 + %.3f)" % (n, size, ("wrap", "unwrap")[d], r, m) for n, size, d, r, m, _ in over))
+    else:
+        emit("KWP stays within the margin at every shape KW can be timed at.\n")
+    n = top
+    cyc = torch.tensor([1, 8, 9, 256], dtype=torch.int32, device="cuda").repeat(n // 4)
+    wcyc = (cyc + 7) // 8 * 8 + 8
+    expect = int(cyc.sum())
+    mixed = kwp_pair(n, 256, ptr(cyc), ptr(wcyc), expect)
+    uniform = kwp_pair(n, 256)
+    emit("## A batch of mixed lengths against a uniform one: %d records, slots of 256 bytes, lens cycling 1, 8, 9, 256\n" % n)
+    emit("A wave costs its longest row, and every wave of the mixed batch holds one 256-byte record, so the mixed batch "
+         "cannot take longer than the uniform one but for its lens array; it moves about a quarter of the bytes.\n")
+    emit("| direction | uniform 256 B, us | mixed, us | mixed / uniform |\n|---|---|---|---|")
+    for d in (0, 1):
+        u = reps_of(uniform[d], 5)
+        x = reps_of(mixed[d], 5)
+        emit("| %s | %s | %s | %.3f |" % (("wrap", "unwrap")[d], cell(u), cell(x), statistics.median(x) / statistics.median(u)))
+    emit("")
+
+
 def main():
     quick = "--quick" in sys.argv
     out_path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(ROOT, "profiles", "kw_rate.md")
     rows = []
-    emit = rows.append
+
+    def emit(line):                                       # printed as it comes: a long run shows where it is
+        rows.append(line)
+        print(line, flush=True)
     props = torch.cuda.get_device_properties(0)
     emit("# AES key wrap (RFC 3394): measured rates\n")
     emit("Output of `tools/kw_rate.py` on %s (%d CUs).  Microseconds are median (minimum .. maximum) of %d windows "
@@ -151,8 +263,8 @@ def main():
             us = us[1:]
             emit("| %s | %s | %.3g |" % (name, cell(us), 1e6 / statistics.median(us)))
         emit("\n(Looped through ctypes: the call overhead of about a microsecond is inside these figures.)\n")
+    kwp_sections(emit, quick)
     text = "\n".join(rows) + "\n"
-    print(text)
     os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
     with open(out_path, "w") as f:
         f.write(text)

@@ -103,6 +103,15 @@ print("KW batches: a record holds at most UAES_KW_BATCH_MAX = %d bytes of secret
 walk("KW batch, k secrets of 32 bytes (positions/thread: threads per workgroup)",
      lambda k: uaes.kw_plan(32, max(k, 1))[:2] + (0, uaes.kw_plan(32, max(k, 1))[3]), 1, 1 << 20, 1,
      lambda k: "%9d keys (%9.3f MiB)" % (k, k * 32 / MIB))
+walk("KWP wrap, one secret of n bytes",
+     lambda n: uaes.kwp_plan(max(n, 1))[:2] + (0, 0), 1, 64 * MIB, 1)
+walk("KWP unwrap, one wrapped form of n + 8 bytes",
+     lambda n: uaes.kwp_plan(max(n, 8), unwrap=True)[:2] + (0, 0), 8, 64 * MIB, 8)
+top = max(n for n in range(1, 1 << 13) if uaes.kwp_plan(n, 2) is not None)
+print("KWP batches: a secret's slot holds at most UAES_KW_BATCH_MAX = %d bytes, each record with a length of its own" % top)
+walk("KWP batch, k secrets in slots of 20 bytes (positions/thread: threads per workgroup)",
+     lambda k: uaes.kwp_plan(20, max(k, 1))[:2] + (0, uaes.kwp_plan(20, max(k, 1))[3]), 1, 1 << 20, 1,
+     lambda k: "%9d keys (%9.3f MiB)" % (k, k * 20 / MIB))
 for dec in (False, True):
     walk("FF1 %s, one decimal text of n numerals" % ("decrypt" if dec else "encrypt"),
          lambda n: uaes.ff1_plan(max(n, 6), decrypt=dec)[:2] + (0, 0), 6, 4096, 1, lambda n: "%11d numerals" % n)
