@@ -832,50 +832,76 @@ def chain_plan(what, a, b=0, decrypt=False):
     return name.decode(), out[0], out[1], out[2]
 
 
+def _kw(pad, unwrap, kek, data, prefill):
+    """The one-secret calls of key wrap and key wrap with padding: padding fills the wrapped form up to whole semiblocks,
+    and its unwrap also answers the secret's length"""
+    n = max(len(data) - 8, 0) if unwrap else ((len(data) + 7) // 8 * 8 if pad else len(data)) + 8
+    o = _out(n, prefill)
+    way = "unwrap" if unwrap else "wrap"
+    ln = C.c_size_t(0)
+    tail = (C.byref(ln),) if pad and unwrap else ()
+    fn = getattr(engine(), "uaes_%s_%s" % ("kwp" if pad else "kw", way))
+    rc = _check(fn(_bits(kek), _in(kek), _in(data), len(data), o, *tail), "uaes_kwp_" + way if pad else "AES_KEY_" + way)
+    return (rc, bytes(o)[:n]) + ((ln.value,) if tail else ())
+
+
 def AES_KEY_wrap(kek, secret, prefill=0):
     """micro_aes.c:1829 (RFC 3394).  Returns (code, output buffer of len(secret) + 8 bytes): code 1 for a secret that is
     no multiple of 8 bytes or shorter than 16, the buffer untouched then."""
-    n = len(secret) + 8
-    o = _out(n, prefill)
-    rc = _check(engine().uaes_kw_wrap(_bits(kek), _in(kek), _in(secret), len(secret), o), "AES_KEY_wrap")
-    return rc, bytes(o)[:n]
+    return _kw(False, False, kek, secret, prefill)
 
 
 def AES_KEY_unwrap(kek, wrapped, prefill=0):
     """micro_aes.c:1865.  Returns (code, output buffer of len(wrapped) - 8 bytes); like the reference the unwrapped
     bytes are returned even when the code is 0x1A (zeros under the wipe switch)."""
-    n = max(len(wrapped) - 8, 0)
-    o = _out(n, prefill)
-    rc = _check(engine().uaes_kw_unwrap(_bits(kek), _in(kek), _in(wrapped), len(wrapped), o), "AES_KEY_unwrap")
-    return rc, bytes(o)[:n]
+    return _kw(False, True, kek, wrapped, prefill)
+
+
+def _kw_batch(pad, kek, records, unwrap, slot, prefill):
+    """The batches of key wrap and key wrap with padding.  Padding takes records of any length, each in a slot, passes a
+    length per record unless every record fills its slot, and its unwrap also answers the secrets' lengths."""
+    n = len(records)
+    if n == 0:
+        return ((0, [], [], []) if pad else (0, [], [])) if unwrap else (0, [])
+    lens = None
+    if pad:
+        slot = max(len(r) for r in records) if slot is None else slot
+        if any(len(r) > slot for r in records):
+            raise ValueError("a record longer than its slot")
+        if any(len(r) != slot for r in records):
+            lens = (C.c_uint32 * n)(*[len(r) for r in records])
+        rb = b"".join(bytes(r) + bytes(slot - len(r)) for r in records)
+    else:
+        slot, rb = _records(records, "records")
+    whole = (lambda x: (x + 7) // 8 * 8) if pad else (lambda x: x)
+    oslot = max(slot - 8, 0) if unwrap else whole(slot) + 8
+    o, v, lo = _out(n * oslot, prefill), _out(n), (C.c_uint32 * n)()
+    name = "uaes_%s_%s_batch" % ("kwp" if pad else "kw", "unwrap" if unwrap else "wrap")
+    args = ((lens,) if pad else ()) + (_in(rb), o) + ((lo,) if pad and unwrap else ()) + ((v,) if unwrap else ())
+    rc = _check(getattr(engine(), name)(_bits(kek), _in(kek), n, slot, *args), name)
+    raw = bytes(o)
+    outs = [raw[m * oslot:m * oslot + (max(len(r) - 8, 0) if unwrap else whole(len(r)) + 8)] for m, r in enumerate(records)]
+    if not unwrap:
+        return rc, outs
+    return (rc, outs) + ((list(lo),) if pad else ()) + (list(bytes(v)[:n]),)
 
 
 def kw_batch(kek, records, unwrap=False, prefill=0):
     """Key wrap of many equal-sized records under one key-encryption key (uaes_kw_*_batch).  wrap: returns (code, wrapped
     records); unwrap: returns (code, secrets, verdicts)."""
-    n = len(records)
-    if n == 0:
-        return (0, [], []) if unwrap else (0, [])
-    rl, rb = _records(records, "records")
-    ol = rl - 8 if unwrap else rl + 8
-    o = _out(n * max(ol, 0), prefill)
-    L = engine()
-    if not unwrap:
-        rc = _check(L.uaes_kw_wrap_batch(_bits(kek), _in(kek), n, rl, _in(rb), o), "uaes_kw_wrap_batch")
-        raw = bytes(o)
-        return rc, _split(raw, ol, n)
-    v = _out(n)
-    rc = _check(L.uaes_kw_unwrap_batch(_bits(kek), _in(kek), n, rl, _in(rb), o, v), "uaes_kw_unwrap_batch")
-    raw = bytes(o)
-    return rc, _split(raw, ol, n), list(bytes(v)[:n])
+    return _kw_batch(False, kek, records, unwrap, None, prefill)
+
+
+def _kw_plan(hook, length, nkeys, unwrap):
+    out = (C.c_int * 3)()
+    name = getattr(engine(), hook)(int(bool(unwrap)), length, nkeys, out)
+    return None if name is None else (name.decode(), out[0], out[1], out[2])
 
 
 def kw_plan(length, nkeys=0, unwrap=False):
     """What a key wrap of a secret of `length` bytes would run (uaes_debug_plan_kw; nkeys 0: the one-secret calls, else a
     batch): (arrangement, launches, workgroups, threads per workgroup), or None for arguments that make no sense."""
-    out = (C.c_int * 3)()
-    name = engine().uaes_debug_plan_kw(int(bool(unwrap)), length, nkeys, out)
-    return None if name is None else (name.decode(), out[0], out[1], out[2])
+    return _kw_plan("uaes_debug_plan_kw", length, nkeys, unwrap)
 
 
 def kwp_wrapped_len(n):
@@ -886,21 +912,14 @@ def kwp_wrapped_len(n):
 def kwp_wrap(kek, secret, prefill=0):
     """Key wrap with padding, RFC 5649 (uaes_kwp_wrap): a secret of any length from 1 byte.  Returns (code, output buffer
     of 8 * ceil(len / 8) + 8 bytes): code 1 for an empty secret, the buffer untouched then."""
-    n = (len(secret) + 7) // 8 * 8 + 8
-    o = _out(n, prefill)
-    rc = _check(engine().uaes_kwp_wrap(_bits(kek), _in(kek), _in(secret), len(secret), o), "uaes_kwp_wrap")
-    return rc, bytes(o)[:n]
+    return _kw(True, False, kek, secret, prefill)
 
 
 def kwp_unwrap(kek, wrapped, prefill=0):
     """uaes_kwp_unwrap.  Returns (code, output buffer of len(wrapped) - 8 bytes, length of the secret): the secret is the
     first `length` bytes of the buffer and zeros follow; code 0x1A comes with length 0 and what the chain made (zeros
     under the wipe switch), code 1 (a length that is no multiple of 8 or below 16) with the buffer untouched."""
-    n = max(len(wrapped) - 8, 0)
-    o = _out(n, prefill)
-    ln = C.c_size_t(0)
-    rc = _check(engine().uaes_kwp_unwrap(_bits(kek), _in(kek), _in(wrapped), len(wrapped), o, C.byref(ln)), "uaes_kwp_unwrap")
-    return rc, bytes(o)[:n], ln.value
+    return _kw(True, True, kek, wrapped, prefill)
 
 
 def kwp_batch(kek, records, unwrap=False, slot=None, prefill=0):
@@ -908,34 +927,14 @@ def kwp_batch(kek, records, unwrap=False, slot=None, prefill=0):
     (uaes_kwp_*_batch).  slot = bytes per input record slot (default: the longest record).  wrap: returns (code, wrapped
     records); unwrap: returns (code, unwrapped records of len(wrapped) - 8 bytes each, lengths of the secrets, verdicts).
     A record whose length the call refuses comes back as the prefill."""
-    n = len(records)
-    if n == 0:
-        return (0, [], [], []) if unwrap else (0, [])
-    slot = max(len(r) for r in records) if slot is None else slot
-    if any(len(r) > slot for r in records):
-        raise ValueError("a record longer than its slot")
-    lens = None if all(len(r) == slot for r in records) else (C.c_uint32 * n)(*[len(r) for r in records])
-    rb = b"".join(bytes(r) + bytes(slot - len(r)) for r in records)
-    oslot = max(slot - 8, 0) if unwrap else (slot + 7) // 8 * 8 + 8
-    o = _out(n * oslot, prefill)
-    L = engine()
-    if not unwrap:
-        rc = _check(L.uaes_kwp_wrap_batch(_bits(kek), _in(kek), n, slot, lens, _in(rb), o), "uaes_kwp_wrap_batch")
-        raw = bytes(o)
-        return rc, [raw[m * oslot:m * oslot + (len(r) + 7) // 8 * 8 + 8] for m, r in enumerate(records)]
-    v, lo = _out(n), (C.c_uint32 * n)()
-    rc = _check(L.uaes_kwp_unwrap_batch(_bits(kek), _in(kek), n, slot, lens, _in(rb), o, lo, v), "uaes_kwp_unwrap_batch")
-    raw = bytes(o)
-    return rc, [raw[m * oslot:m * oslot + max(len(r) - 8, 0)] for m, r in enumerate(records)], list(lo), list(bytes(v)[:n])
+    return _kw_batch(True, kek, records, unwrap, slot, prefill)
 
 
 def kwp_plan(length, nkeys=0, unwrap=False):
     """What a key wrap with padding would run (uaes_debug_plan_kwp; length = bytes of the secret, or of the wrapped form
     - 8 for an unwrap; nkeys 0: the one-secret calls, else a batch): (arrangement, launches, workgroups, threads per
     workgroup), or None for arguments that make no sense."""
-    out = (C.c_int * 3)()
-    name = engine().uaes_debug_plan_kwp(int(bool(unwrap)), length, nkeys, out)
-    return None if name is None else (name.decode(), out[0], out[1], out[2])
+    return _kw_plan("uaes_debug_plan_kwp", length, nkeys, unwrap)
 
 
 FF3_TWEAK_LEN = 7

@@ -311,35 +311,30 @@ int uaesk_s2v_batch(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk
                     int decrypt, int wipe, const void *aad, size_t aad_bytes,
                     size_t nmsg, size_t msg_bytes, const void *in, void *out, void *ivs, void *verdicts, int *bad);
 
-/* AES key wrap, RFC 3394 (uaes_kw.hip; AES_KEY_wrap / AES_KEY_unwrap, micro_aes.c:1829-1894); device pointers at any
- * byte offset.  secret_len = bytes of the secret (a multiple of 8, >= 16) in both directions.  wrap: in = the secret,
- * out receives secret_len + 8 bytes; unwrap: in = the wrapped form (secret_len + 8 bytes), out receives the secret
- * whatever the verdict and *status = 0 / 0x1A.  in and out are disjoint, or the secret sits 8 bytes into the wrapped
- * buffer.  ek / dk: encryption / equivalent-inverse keys (wrap reads ek, unwrap dk).
- * Batch: nkeys records of secret_bytes (<= UAES_KW_BATCH_MAX) back to back, wrapped record m at m (secret_bytes + 8);
- * unwrap writes verdicts[m] (1 = authentic), ORs 1 into *bad for a forgery and zeroes a forged record when wipe. */
-int uaesk_kw(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, const uaesk_rk *dk, int unwrap,
-             const void *in, size_t secret_len, void *out, int *status);
-int uaesk_kw_batch(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, const uaesk_rk *dk,
-                   int unwrap, int wipe, size_t nkeys, size_t secret_bytes, const void *in, void *out,
-                   void *verdicts, int *bad);
-
-/* AES key wrap with padding, RFC 5649 (uaes_kw.hip; the reference has none); device pointers at any byte offset.
- * wrap: in = the secret of len bytes (1 .. 2^32 - 1), out receives 8 ceil(len / 8) + 8 bytes.  unwrap: in = the wrapped
- * form, len = its bytes - 8 (a multiple of 8), out receives len bytes whatever the verdict, status[0] = 0 / 0x1A and
- * status[1] = the length indicator of an authentic secret / 0.  Buffers disjoint or the secret 8 bytes into the wrapped
- * buffer.  No byte beyond the len bytes of a short secret is read.
- * Batch: nkeys slots.  wrap: rec = bytes per secret slot (1 .. UAES_KW_BATCH_MAX), the wrapped slot is
+/* AES key wrap, RFC 3394 (pad 0; AES_KEY_wrap / AES_KEY_unwrap, micro_aes.c:1829-1894), and key wrap with padding,
+ * RFC 5649 (pad 1; the reference has none): uaes_kw.hip; device pointers at any byte offset.  ek / dk: encryption /
+ * equivalent-inverse keys (wrap reads ek, unwrap dk).  in and out are disjoint, or the secret sits 8 bytes into the
+ * wrapped buffer.
+ * pad 0: len = bytes of the secret (a multiple of 8, >= 16) in both directions.  wrap: in = the secret, out receives
+ * len + 8 bytes; unwrap: in = the wrapped form (len + 8 bytes), out receives the secret whatever the verdict and
+ * *status = 0 / 0x1A.
+ * pad 1: wrap: in = the secret of len bytes (1 .. 2^32 - 1), out receives 8 ceil(len / 8) + 8 bytes.  unwrap: in = the
+ * wrapped form, len = its bytes - 8 (a multiple of 8), out receives len bytes whatever the verdict, status[0] = 0 / 0x1A
+ * and status[1] = the length indicator of an authentic secret / 0.  No byte beyond the len bytes of a short secret is read.
+ * Batch, pad 0: nkeys records of rec bytes of secret (<= UAES_KW_BATCH_MAX) back to back, wrapped record m at
+ * m (rec + 8); lens and lens_out are not read (NULL).
+ * Batch, pad 1: nkeys slots.  wrap: rec = bytes per secret slot (1 .. UAES_KW_BATCH_MAX), the wrapped slot is
  * 8 ceil(rec / 8) + 8; lens (NULL: every record fills its slot) = u32 per record, 1 .. rec, else the record is skipped and
  * 2 is ORed into *bad.  unwrap: rec = the wrapped slot - 8; lens = bytes of each wrapped record (NULL: the slot), a
- * multiple of 8 in 16 .. rec + 8, else the record fails unwritten; verdicts[m] = 1 / 0, lens_out[m] = the length
- * indicator / 0, 1 is ORed into *bad for a record that fails, a forged record is zeroed when wipe.  lens and lens_out
- * are 4-byte aligned. */
-int uaesk_kwp(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, const uaesk_rk *dk, int unwrap,
-              const void *in, size_t len, void *out, int *status);
-int uaesk_kwp_batch(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, const uaesk_rk *dk,
-                    int unwrap, int wipe, size_t nkeys, size_t rec, const void *lens, const void *in, void *out,
-                    void *lens_out, void *verdicts, int *bad);
+ * multiple of 8 in 16 .. rec + 8, else the record fails unwritten; lens_out[m] = the length indicator / 0.  lens and
+ * lens_out are 4-byte aligned.
+ * Either batch: unwrap writes verdicts[m] (1 = authentic), ORs 1 into *bad for a record that fails and zeroes a forged
+ * record when wipe. */
+int uaesk_kw(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, const uaesk_rk *dk, int pad, int unwrap,
+             const void *in, size_t len, void *out, int *status);
+int uaesk_kw_batch(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, const uaesk_rk *dk, int pad,
+                   int unwrap, int wipe, size_t nkeys, size_t rec, const void *lens, const void *in, void *out,
+                   void *lens_out, void *verdicts, int *bad);
 
 /* FF1, SP 800-38G (uaes_ff1.hip; AES_FPE_encrypt / AES_FPE_decrypt with FF_X 1, micro_aes.c:2091-2147, :2267-2314).
  * What depends on (radix, len, tweak length, alphabet) alone is made once on the host: b and d with exact integers,

@@ -1473,22 +1473,6 @@ const char *uaes_debug_plan_chain(int what, int dir, size_t a, size_t b, int out
     if (out) { out[0] = p.launches; out[1] = (int)p.grid; out[2] = (int)p.steps; }
     return uaesk_chain_arrangement_name(p.arrangement);
 }
-const char *uaes_debug_plan_kw(int dir, size_t len, size_t nkeys, int out[3])
-{
-    uaes_plan p;
-    memset(&p, 0, sizeof p);
-    if (uaesk_plan_kw(dir, len, nkeys, &p)) return NULL;
-    if (out) { out[0] = p.launches; out[1] = (int)p.grid; out[2] = (int)p.steps; }
-    return uaesk_kw_arrangement_name(p.arrangement);
-}
-const char *uaes_debug_plan_kwp(int dir, size_t len, size_t nkeys, int out[3])
-{
-    uaes_plan p;
-    memset(&p, 0, sizeof p);
-    if (uaesk_plan_kwp(dir, len, nkeys, &p)) return NULL;
-    if (out) { out[0] = p.launches; out[1] = (int)p.grid; out[2] = (int)p.steps; }
-    return uaesk_kwp_arrangement_name(p.arrangement);
-}
 const char *uaes_debug_plan_ff1(int dir, unsigned radix, size_t len, size_t nrec, int out[3])
 {
     uaes_plan p;
@@ -1505,7 +1489,8 @@ const char *uaes_debug_plan_ff3(int dir, unsigned radix, size_t len, size_t nrec
     if (out) { out[0] = p.launches; out[1] = (int)p.grid; out[2] = (int)p.steps; }
     return uaesk_ff3_arrangement_name(p.arrangement);
 }
-/* a row batch's hook: the plan of (dir, len, nmsg) under its arrangement's name; NULL for arguments its planner refuses */
+/* the hook of a planner that takes (dir, len, nmsg) -- the row batches and the two key wraps: the plan under its
+ * arrangement's name; NULL for arguments the planner refuses */
 static const char *debug_plan_rows(int (*plan)(int, size_t, size_t, uaes_plan *), const char *(*name)(int), int dir, size_t len,
                                    size_t nmsg, int out[3])
 {
@@ -1514,6 +1499,14 @@ static const char *debug_plan_rows(int (*plan)(int, size_t, size_t, uaes_plan *)
     if (plan(dir, len, nmsg, &p)) return NULL;
     if (out) { out[0] = p.launches; out[1] = (int)p.grid; out[2] = (int)p.steps; }
     return name(p.arrangement);
+}
+const char *uaes_debug_plan_kw(int dir, size_t len, size_t nkeys, int out[3])
+{
+    return debug_plan_rows(uaesk_plan_kw, uaesk_kw_arrangement_name, dir, len, nkeys, out);
+}
+const char *uaes_debug_plan_kwp(int dir, size_t len, size_t nkeys, int out[3])
+{
+    return debug_plan_rows(uaesk_plan_kwp, uaesk_kwp_arrangement_name, dir, len, nkeys, out);
 }
 const char *uaes_debug_plan_gcmsiv_batch(int dir, size_t len, size_t nmsg, int out[3])
 {

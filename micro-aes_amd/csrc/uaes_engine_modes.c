@@ -1193,14 +1193,15 @@ int uaes_ctr_xcrypt_batch(int keybits, const uint8_t *key, const uint8_t *ctrs, 
 }
 
 /* ------------------------------------------------------------------------ */
-/* key wrap, RFC 3394 (AES_KEY_wrap / AES_KEY_unwrap, micro_aes.c:1829-1894)    */
+/* key wrap, RFC 3394 (AES_KEY_wrap / AES_KEY_unwrap, micro_aes.c:1829-1894),   */
+/* and key wrap with padding, RFC 5649 / SP 800-38F KWP (the reference has none) */
 /* ------------------------------------------------------------------------ */
 /* One serial chain of 6 n block operations, one wave (uaes_kw.hip).  A secret of at most UAES_KW_LDS_MAX bytes in host
  * memory travels like any short text (plan_io: the mapped pinned buffers); the kernel reads all of it before it writes,
  * so plan_io's one staging buffer for both directions is fine.  A longer one is worked on in place in the output
  * buffer, which therefore is device memory of its own -- never the mapped host window, and never the input's staging
  * buffer (the secret sits 8 bytes into the wrapped form).  Device buffers go to the kernels as they are, at any byte
- * offset, the in-place form secret == wrapped + 8 included. */
+ * offset, the in-place form secret == wrapped + 8 included.  secret_len: padded. */
 static int kw_io(lane *L, const void *in, size_t in_len, void *out, size_t out_len, size_t secret_len, io_plan *io)
 {
     void *d_in, *d_out;
@@ -1219,189 +1220,145 @@ static int kw_io(lane *L, const void *in, size_t in_len, void *out, size_t out_l
     return 0;
 }
 
-int uaes_kw_wrap(int keybits, const uint8_t *kek, const void *secret, size_t secretLen, void *wrapped)
+/* What the two modes differ in once a call's arguments have passed its own checks.  Padding adds a secret of any length,
+ * the one-block case and a verdict of three conditions, all in the kernel and the host path; here it shows as a second
+ * status word, the length indicator, which the unwrap reports. */
+typedef struct {
+    int pad;                                       /* the kernels' switch; 1 + pad status words */
+    const char *wrap, *unwrap, *batch;             /* what launched() calls the kernels */
+    int (*host_wrap)(const uaesh_key *k, const uint8_t *secret, size_t len, uint8_t *wrapped);
+    int (*host_unwrap)(const uaesh_key *k, const uint8_t *wrapped, size_t wrap_len, uint8_t *secret, uint32_t *secret_len);
+} kw_mode;
+
+static int kw_host_unwrap(const uaesh_key *k, const uint8_t *wrapped, size_t wrap_len, uint8_t *secret, uint32_t *secret_len)
+{
+    (void)secret_len;
+    return uaesh_kw_unwrap(k, wrapped, wrap_len, secret);
+}
+
+static const kw_mode KW = { 0, "key wrap", "key unwrap", "key wrap batch", uaesh_kw_wrap, kw_host_unwrap };
+static const kw_mode KWP = { 1, "key wrap with padding", "key unwrap with padding", "key wrap with padding batch",
+                             uaesh_kwp_wrap, uaesh_kwp_unwrap };
+
+/* out_len = bytes of the wrapped form; host_len = the length the host policy goes by */
+static int kw_wrap(const kw_mode *m, const keysched *ks, const void *secret, size_t secretLen, void *wrapped, size_t out_len,
+                   size_t host_len)
 {
     context *c;
     lane *L;
-    KEYSCHED(ks);
     io_plan io;
     int rc;
-    if ((rc = expand_key(&ks, kek, keybits)) != 0) return rc;
-    if (secretLen % 8 || secretLen / 8 < 2) return UAES_E_DATALENGTH;     /* (:1837) */
-    if (!secret || !wrapped) return fail(UAES_E_ARG, "NULL pointer");
-    if (secretLen > (size_t)-1 - 8) return fail(UAES_E_ARG, "length overflows");
-    if (host_take(secret, wrapped, secretLen, 1)) {
-        const uaesh_key hk = host_key(&ks);
-        return host_result(uaesh_kw_wrap(&hk, (const uint8_t *)secret, secretLen, (uint8_t *)wrapped));
-    }
-    if ((rc = enter(&c, &L)) != 0) return rc;
-    do {
-        if ((rc = kw_io(L, secret, secretLen, wrapped, secretLen + 8, secretLen, &io)) != 0) break;
-        int k = uaesk_kw(L->stream, &c->tb, ks.nr, &ks.ek, &ks.dk, 0, io.din, secretLen, io.dout, NULL);
-        if ((rc = launched("key wrap", k)) != 0) break;
-        rc = finish_io(&io, secretLen + 8);
-    } while (0);
-    DONE(L, rc);
-}
-
-int uaes_kw_unwrap(int keybits, const uint8_t *kek, const void *wrapped, size_t wrapLen, void *secret)
-{
-    context *c;
-    lane *L;
-    KEYSCHED(ks);
-    io_plan io;
-    int rc, status = 0;
-    size_t len;
-    if ((rc = expand_key(&ks, kek, keybits)) != 0) return rc;
-    if (wrapLen % 8 || wrapLen / 8 < 3) return UAES_E_DATALENGTH;        /* (:1873) */
-    len = wrapLen - 8;
-    if (!secret || !wrapped) return fail(UAES_E_ARG, "NULL pointer");
-    if (host_take(wrapped, secret, wrapLen, 1)) {
-        const uaesh_key hk = host_key(&ks);
-        rc = uaesh_kw_unwrap(&hk, (const uint8_t *)wrapped, wrapLen, (uint8_t *)secret);
-        if (rc == UAES_E_AUTHENTICATION && wipe_on_auth_failure()) memset(secret, 0, len);   /* (the default leaves it, as the reference does) */
-        return host_result(rc);
-    }
-    if ((rc = enter(&c, &L)) != 0) return rc;
-    do {
-        if ((rc = kw_io(L, wrapped, wrapLen, secret, len, len, &io)) != 0) break;
-        int k = uaesk_kw(L->stream, &c->tb, ks.nr, &ks.ek, &ks.dk, 1, io.din, len, io.dout, L->d_status);
-        if ((rc = launched("key unwrap", k)) != 0) break;
-        if ((rc = lane_fetch(L, &status, L->d_status, sizeof status)) != 0) break;
-        io.drained = 1;
-        /* like the reference: the secret is written before A is checked; SABOTAGE = uaes_set_wipe_on_auth_failure */
-        if ((rc = status ? finish_io_unauthenticated(&io, len) : finish_io(&io, len)) == 0 && status) rc = UAES_E_AUTHENTICATION;
-    } while (0);
-    DONE(L, rc);
-}
-
-/* Batches: nkeys records of one length under one key-encryption key, sixteen lanes per record, always on the GPU.
- * Either array may be host or device memory; host arrays travel through the lane's staging buffers. */
-static int kw_batch(int unwrap, int keybits, const uint8_t *kek, size_t nkeys, size_t secret_bytes,
-                    const void *in, void *outp, uint8_t *verdicts)
-{
-    context *c;
-    lane *L;
-    KEYSCHED(ks);
-    int rc, k, bad;
-    const size_t in_rec = unwrap ? secret_bytes + 8 : secret_bytes, out_rec = unwrap ? secret_bytes : secret_bytes + 8;
-    if ((rc = expand_key(&ks, kek, keybits)) != 0) return rc;
-    if (secret_bytes > UAES_KW_BATCH_MAX)
-        return fail(UAES_E_ARG, "batched key wrap: a record holds at most %zu bytes of secret (got %zu)",
-                    (size_t)UAES_KW_BATCH_MAX, secret_bytes);
-    if (nkeys > (size_t)-1 / (secret_bytes + 8)) return fail(UAES_E_ARG, "batch size overflows");
-    if (nkeys == 0) return 0;
-    if (!in || !outp || (unwrap && !verdicts)) return fail(UAES_E_ARG, "NULL pointer");
-    if ((rc = enter(&c, &L)) != 0) return rc;
-    row_array a[1] = { { verdicts, unwrap ? nkeys : 0, 1, NULL } };
-    row_text t = { in, outp, nkeys * in_rec, nkeys * out_rec, 0, NULL, NULL };
-    if ((rc = row_stage(L, a, 1, unwrap)) != 0) goto out;
-    if ((rc = row_texts(L, &t)) != 0) goto out;
-    k = uaesk_kw_batch(L->stream, &c->tb, ks.nr, &ks.ek, &ks.dk, unwrap, wipe_on_auth_failure(), nkeys, secret_bytes,
-                       t.d_in, t.d_out, a[0].d, L->d_status);
-    if ((rc = launched("key wrap batch", k)) != 0) goto out;
-    if ((rc = row_finish(L, &t, a, 1, unwrap, &bad)) != 0) goto out;
-    rc = bad ? UAES_E_AUTHENTICATION : 0;
-out:
-    DONE(L, rc);
-}
-
-int uaes_kw_wrap_batch(int keybits, const uint8_t *kek, size_t nkeys, size_t secret_bytes, const void *secrets, void *wrapped)
-{
-    if (secret_bytes % 8 || secret_bytes / 8 < 2) return UAES_E_DATALENGTH;
-    return kw_batch(0, keybits, kek, nkeys, secret_bytes, secrets, wrapped, NULL);
-}
-
-int uaes_kw_unwrap_batch(int keybits, const uint8_t *kek, size_t nkeys, size_t wrapped_bytes, const void *wrapped,
-                         void *secrets, uint8_t *verdicts)
-{
-    if (wrapped_bytes % 8 || wrapped_bytes / 8 < 3) return UAES_E_DATALENGTH;
-    return kw_batch(1, keybits, kek, nkeys, wrapped_bytes - 8, wrapped, secrets, verdicts);
-}
-
-/* ------------------------------------------------------------------------ */
-/* key wrap with padding, RFC 5649 / SP 800-38F KWP (the reference has none)    */
-/* ------------------------------------------------------------------------ */
-/* Key wrap's chain, buffers and host path (kw_io by the padded length), with a secret of any length, the one-block case
- * and a verdict of three conditions that the kernel computes: status[0] = 0 / 0x1A, status[1] = the length indicator. */
-int uaes_kwp_wrap(int keybits, const uint8_t *kek, const void *secret, size_t secretLen, void *wrapped)
-{
-    context *c;
-    lane *L;
-    KEYSCHED(ks);
-    io_plan io;
-    int rc;
-    const size_t out_len = uaes_kwp_wrapped_len(secretLen);
-    if ((rc = expand_key(&ks, kek, keybits)) != 0) return rc;
-    if (out_len == 0) return UAES_E_DATALENGTH;
-    if (!secret || !wrapped) return fail(UAES_E_ARG, "NULL pointer");
-    if (host_take(secret, wrapped, out_len, 1)) {
-        const uaesh_key hk = host_key(&ks);
-        return host_result(uaesh_kwp_wrap(&hk, (const uint8_t *)secret, secretLen, (uint8_t *)wrapped));
+    if (host_take(secret, wrapped, host_len, 1)) {
+        const uaesh_key hk = host_key(ks);
+        return host_result(m->host_wrap(&hk, (const uint8_t *)secret, secretLen, (uint8_t *)wrapped));
     }
     if ((rc = enter(&c, &L)) != 0) return rc;
     do {
         if ((rc = kw_io(L, secret, secretLen, wrapped, out_len, out_len - 8, &io)) != 0) break;
-        int k = uaesk_kwp(L->stream, &c->tb, ks.nr, &ks.ek, &ks.dk, 0, io.din, secretLen, io.dout, NULL);
-        if ((rc = launched("key wrap with padding", k)) != 0) break;
+        int k = uaesk_kw(L->stream, &c->tb, ks->nr, &ks->ek, &ks->dk, m->pad, 0, io.din, secretLen, io.dout, NULL);
+        if ((rc = launched(m->wrap, k)) != 0) break;
         rc = finish_io(&io, out_len);
     } while (0);
     DONE(L, rc);
 }
 
-int uaes_kwp_unwrap(int keybits, const uint8_t *kek, const void *wrapped, size_t wrapLen, void *secret, size_t *secretLen)
+/* secretLen (padding; else NULL) receives the length indicator of an authentic secret */
+static int kw_unwrap(const kw_mode *m, const keysched *ks, const void *wrapped, size_t wrapLen, void *secret, size_t *secretLen)
 {
     context *c;
     lane *L;
-    KEYSCHED(ks);
     io_plan io;
     int rc, status[2] = { 0, 0 };
-    size_t len;
-    if ((rc = expand_key(&ks, kek, keybits)) != 0) return rc;
-    if (wrapLen % 8 || wrapLen < 16 || (uint64_t)(wrapLen - 8) > (uint64_t)1 << 32) return UAES_E_DATALENGTH;
-    len = wrapLen - 8;
-    if (!secret || !wrapped || !secretLen) return fail(UAES_E_ARG, "NULL pointer");
-    *secretLen = 0;
+    const size_t len = wrapLen - 8;
     if (host_take(wrapped, secret, wrapLen, 1)) {
-        const uaesh_key hk = host_key(&ks);
+        const uaesh_key hk = host_key(ks);
         uint32_t mli = 0;
-        rc = uaesh_kwp_unwrap(&hk, (const uint8_t *)wrapped, wrapLen, (uint8_t *)secret, &mli);
-        if (rc == UAES_E_AUTHENTICATION && wipe_on_auth_failure()) memset(secret, 0, len);
-        *secretLen = mli;
+        rc = m->host_unwrap(&hk, (const uint8_t *)wrapped, wrapLen, (uint8_t *)secret, &mli);
+        if (rc == UAES_E_AUTHENTICATION && wipe_on_auth_failure()) memset(secret, 0, len);   /* (the default leaves it, as the reference does) */
+        if (secretLen) *secretLen = mli;
         return host_result(rc);
     }
     if ((rc = enter(&c, &L)) != 0) return rc;
     do {
         if ((rc = kw_io(L, wrapped, wrapLen, secret, len, len, &io)) != 0) break;
-        int k = uaesk_kwp(L->stream, &c->tb, ks.nr, &ks.ek, &ks.dk, 1, io.din, len, io.dout, L->d_status);
-        if ((rc = launched("key unwrap with padding", k)) != 0) break;
-        if ((rc = lane_fetch(L, status, L->d_status, sizeof status)) != 0) break;
+        int k = uaesk_kw(L->stream, &c->tb, ks->nr, &ks->ek, &ks->dk, m->pad, 1, io.din, len, io.dout, L->d_status);
+        if ((rc = launched(m->unwrap, k)) != 0) break;
+        if ((rc = lane_fetch(L, status, L->d_status, (1 + m->pad) * sizeof status[0])) != 0) break;
         io.drained = 1;
+        /* like the reference: the secret is written before A is checked; SABOTAGE = uaes_set_wipe_on_auth_failure */
         if ((rc = status[0] ? finish_io_unauthenticated(&io, len) : finish_io(&io, len)) != 0) break;
         if (status[0]) rc = UAES_E_AUTHENTICATION;
-        else *secretLen = (uint32_t)status[1];
+        else if (secretLen) *secretLen = (uint32_t)status[1];
     } while (0);
     DONE(L, rc);
 }
 
-/* Batches: nkeys slots under one key-encryption key, a length per record (lens, NULL: every record fills its slot), always
- * on the GPU.  rec = bytes of a secret's slot (unwrap: the wrapped slot - 8).  The status word takes two bits: 1 for a
- * record that does not authenticate, 2 for a wrap length of 0 or beyond the slot. */
-static int kwp_batch(int unwrap, int keybits, const uint8_t *kek, size_t nkeys, size_t rec, const uint32_t *lens,
-                     const void *in, void *outp, uint32_t *lens_out, uint8_t *verdicts)
+int uaes_kw_wrap(int keybits, const uint8_t *kek, const void *secret, size_t secretLen, void *wrapped)
+{
+    KEYSCHED(ks);
+    int rc;
+    if ((rc = expand_key(&ks, kek, keybits)) != 0) return rc;
+    if (secretLen % 8 || secretLen / 8 < 2) return UAES_E_DATALENGTH;     /* (:1837) */
+    if (!secret || !wrapped) return fail(UAES_E_ARG, "NULL pointer");
+    if (secretLen > (size_t)-1 - 8) return fail(UAES_E_ARG, "length overflows");
+    return kw_wrap(&KW, &ks, secret, secretLen, wrapped, secretLen + 8, secretLen);
+}
+
+int uaes_kw_unwrap(int keybits, const uint8_t *kek, const void *wrapped, size_t wrapLen, void *secret)
+{
+    KEYSCHED(ks);
+    int rc;
+    if ((rc = expand_key(&ks, kek, keybits)) != 0) return rc;
+    if (wrapLen % 8 || wrapLen / 8 < 3) return UAES_E_DATALENGTH;        /* (:1873) */
+    if (!secret || !wrapped) return fail(UAES_E_ARG, "NULL pointer");
+    return kw_unwrap(&KW, &ks, wrapped, wrapLen, secret, NULL);
+}
+
+int uaes_kwp_wrap(int keybits, const uint8_t *kek, const void *secret, size_t secretLen, void *wrapped)
+{
+    KEYSCHED(ks);
+    int rc;
+    const size_t out_len = uaes_kwp_wrapped_len(secretLen);
+    if ((rc = expand_key(&ks, kek, keybits)) != 0) return rc;
+    if (out_len == 0) return UAES_E_DATALENGTH;
+    if (!secret || !wrapped) return fail(UAES_E_ARG, "NULL pointer");
+    return kw_wrap(&KWP, &ks, secret, secretLen, wrapped, out_len, out_len);
+}
+
+int uaes_kwp_unwrap(int keybits, const uint8_t *kek, const void *wrapped, size_t wrapLen, void *secret, size_t *secretLen)
+{
+    KEYSCHED(ks);
+    int rc;
+    if ((rc = expand_key(&ks, kek, keybits)) != 0) return rc;
+    if (wrapLen % 8 || wrapLen < 16 || (uint64_t)(wrapLen - 8) > (uint64_t)1 << 32) return UAES_E_DATALENGTH;
+    if (!secret || !wrapped || !secretLen) return fail(UAES_E_ARG, "NULL pointer");
+    *secretLen = 0;
+    return kw_unwrap(&KWP, &ks, wrapped, wrapLen, secret, secretLen);
+}
+
+/* Batches: nkeys slots under one key-encryption key, sixteen lanes per record, always on the GPU.  rec = bytes of a
+ * secret's slot (unwrap: the wrapped slot - 8).  Padding gives each record a length of its own (lens, NULL: every record
+ * fills its slot) and reports the secrets' lengths (lens_out); without it both are NULL.  Any array may be host or device
+ * memory; host arrays travel through the lane's staging buffers.  The status word takes two bits: 1 for a record that
+ * does not authenticate, 2 for a wrap length of 0 or beyond the slot. */
+static int kw_batch(const kw_mode *m, int unwrap, int keybits, const uint8_t *kek, size_t nkeys, size_t rec, const uint32_t *lens,
+                    const void *in, void *outp, uint32_t *lens_out, uint8_t *verdicts)
 {
     context *c;
     lane *L;
     KEYSCHED(ks);
     int rc, k, bad;
-    const size_t wslot = uaes_kwp_wrapped_len(rec), in_rec = unwrap ? wslot : rec, out_rec = unwrap ? rec : wslot;
+    const size_t wslot = (rec + 7) / 8 * 8 + 8, in_rec = unwrap ? wslot : rec, out_rec = unwrap ? rec : wslot;
     const int status = unwrap || lens != NULL;
     if ((rc = expand_key(&ks, kek, keybits)) != 0) return rc;
+    if (rec > UAES_KW_BATCH_MAX)                          /* (key wrap with padding has refused it before the key) */
+        return fail(UAES_E_ARG, "batched key wrap: a record holds at most %zu bytes of secret (got %zu)",
+                    (size_t)UAES_KW_BATCH_MAX, rec);
     if (nkeys > (size_t)-1 / wslot) return fail(UAES_E_ARG, "batch size overflows");
     if (nkeys == 0) return 0;
-    if (!in || !outp || (unwrap && (!verdicts || !lens_out))) return fail(UAES_E_ARG, "NULL pointer");
+    if (!in || !outp || (unwrap && (!verdicts || (m->pad && !lens_out)))) return fail(UAES_E_ARG, "NULL pointer");
     if ((rc = enter(&c, &L)) != 0) return rc;
-    row_array a[3] = { { lens, lens ? nkeys * sizeof *lens : 0, 0, NULL }, { lens_out, unwrap ? nkeys * sizeof *lens_out : 0, 1, NULL },
+    row_array a[3] = { { lens, lens ? nkeys * sizeof *lens : 0, 0, NULL }, { lens_out, lens_out ? nkeys * sizeof *lens_out : 0, 1, NULL },
                        { verdicts, unwrap ? nkeys : 0, 1, NULL } };
     /* with lens a record may leave part of its slot, or all of it, unwritten: a host output starts as the caller's bytes */
     row_text t = { in, outp, nkeys * in_rec, nkeys * out_rec, lens != NULL, NULL, NULL };
@@ -1409,16 +1366,29 @@ static int kwp_batch(int unwrap, int keybits, const uint8_t *kek, size_t nkeys, 
         rc = fail(UAES_E_ARG, "a device array of lengths must be 4-byte aligned");
         goto out;
     }
-    /* a wrap without lens has nothing to report: no status word, as the key-wrap batch */
+    /* a wrap without lens has nothing to report: no status word */
     if ((rc = row_stage(L, a, 3, status)) != 0) goto out;
     if ((rc = row_texts(L, &t)) != 0) goto out;
-    k = uaesk_kwp_batch(L->stream, &c->tb, ks.nr, &ks.ek, &ks.dk, unwrap, wipe_on_auth_failure(), nkeys, rec, a[0].d,
-                        t.d_in, t.d_out, a[1].d, a[2].d, L->d_status);
-    if ((rc = launched("key wrap with padding batch", k)) != 0) goto out;
+    k = uaesk_kw_batch(L->stream, &c->tb, ks.nr, &ks.ek, &ks.dk, m->pad, unwrap, wipe_on_auth_failure(), nkeys, rec, a[0].d,
+                       t.d_in, t.d_out, a[1].d, a[2].d, L->d_status);
+    if ((rc = launched(m->batch, k)) != 0) goto out;
     if ((rc = row_finish(L, &t, a, 3, status, &bad)) != 0) goto out;
     rc = (bad & 1) ? UAES_E_AUTHENTICATION : (bad & 2) ? UAES_E_DATALENGTH : 0;
 out:
     DONE(L, rc);
+}
+
+int uaes_kw_wrap_batch(int keybits, const uint8_t *kek, size_t nkeys, size_t secret_bytes, const void *secrets, void *wrapped)
+{
+    if (secret_bytes % 8 || secret_bytes / 8 < 2) return UAES_E_DATALENGTH;
+    return kw_batch(&KW, 0, keybits, kek, nkeys, secret_bytes, NULL, secrets, wrapped, NULL, NULL);
+}
+
+int uaes_kw_unwrap_batch(int keybits, const uint8_t *kek, size_t nkeys, size_t wrapped_bytes, const void *wrapped,
+                         void *secrets, uint8_t *verdicts)
+{
+    if (wrapped_bytes % 8 || wrapped_bytes / 8 < 3) return UAES_E_DATALENGTH;
+    return kw_batch(&KW, 1, keybits, kek, nkeys, wrapped_bytes - 8, NULL, wrapped, secrets, NULL, verdicts);
 }
 
 int uaes_kwp_wrap_batch(int keybits, const uint8_t *kek, size_t nkeys, size_t secret_bytes, const uint32_t *lens,
@@ -1427,7 +1397,7 @@ int uaes_kwp_wrap_batch(int keybits, const uint8_t *kek, size_t nkeys, size_t se
     if (secret_bytes == 0 || secret_bytes > UAES_KW_BATCH_MAX)
         return fail(UAES_E_ARG, "batched key wrap with padding: a record holds 1 .. %zu bytes of secret (got %zu)",
                     (size_t)UAES_KW_BATCH_MAX, secret_bytes);
-    return kwp_batch(0, keybits, kek, nkeys, secret_bytes, lens, secrets, wrapped, NULL, NULL);
+    return kw_batch(&KWP, 0, keybits, kek, nkeys, secret_bytes, lens, secrets, wrapped, NULL, NULL);
 }
 
 int uaes_kwp_unwrap_batch(int keybits, const uint8_t *kek, size_t nkeys, size_t wrapped_bytes, const uint32_t *wlens,
@@ -1436,7 +1406,7 @@ int uaes_kwp_unwrap_batch(int keybits, const uint8_t *kek, size_t nkeys, size_t 
     if (wrapped_bytes % 8 || wrapped_bytes < 16 || wrapped_bytes > UAES_KW_BATCH_MAX + 8)
         return fail(UAES_E_ARG, "batched key unwrap with padding: a wrapped record is a multiple of 8 in 16 .. %zu bytes (got %zu)",
                     (size_t)UAES_KW_BATCH_MAX + 8, wrapped_bytes);
-    return kwp_batch(1, keybits, kek, nkeys, wrapped_bytes - 8, wlens, wrapped, secrets, lens_out, verdicts);
+    return kw_batch(&KWP, 1, keybits, kek, nkeys, wrapped_bytes - 8, wlens, wrapped, secrets, lens_out, verdicts);
 }
 
 /* ------------------------------------------------------------------------ */

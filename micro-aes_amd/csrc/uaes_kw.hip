@@ -1,9 +1,9 @@
 /*
  * uaes_kw.hip -- AES key wrap, RFC 3394 / SP 800-38F KW, and key wrap with padding, RFC 5649 / SP 800-38F KWP.
  *
- *   k_kw        <- AES_KEY_wrap :1829-1855, AES_KEY_unwrap :1865-1894: one secret, one wave
- *   k_kw_batch  many secrets of one length under one key-encryption key, sixteen lanes per record
- *   k_kwp, k_kwp_batch  the same chain for secrets of any length (the reference has none): further down, with what differs
+ *   k_kw        one secret, one wave: KW <- AES_KEY_wrap :1829-1855, AES_KEY_unwrap :1865-1894; KWP (the reference has none)
+ *   k_kw_batch  many secrets under one key-encryption key, sixteen lanes per record
+ * Both modes are instances of both kernels; the template argument PAD says which.
  *
  * The wrap of n semiblocks (8 bytes each) is ONE chain of 6 n block operations:
  *     B = AES(A | R_i);  A = MSB64(B) ^ t;  R_i = LSB64(B)         t = 1 .. 6 n, i walking 1 .. n round and round
@@ -11,7 +11,8 @@
  * the sixteen lanes of a DPP row share it (row_encrypt / row_decrypt, uaes_aes.hip.h).  The state is a column word per
  * lane: columns 0 and 1 are A, which never leaves the registers; columns 2 and 3 are R_i, which the lanes of those
  * columns fetch and put back.  t is a 64-bit big-endian number ending at byte 7 of A (xorBEint, MIDST): the lanes of
- * column 0 XOR its high word, those of column 1 its low word.
+ * column 0 XOR its high word, those of column 1 its low word.  KW: the secret is whole semiblocks, n >= 2, A starts as
+ * A6 A6 .. A6 and the unwrap accepts when it ends as that.
  *
  * Where R lives (the plan, uaes_plan.h):
  *   kw.lds     secrets up to UAES_KW_LDS_MAX: in LDS behind the row tables.  R_(i+1) was stored at least one step ago
@@ -25,6 +26,17 @@
  *              LDS behind the tables; the slot stride is 8 bytes more than a multiple of 128, meant to put the rows of a
  *              wave on different banks (a design intention: no conflict counter has been read; it decides speed only).
  * Every loop is bounded by the lengths passed in; no workgroup waits for another.
+ *
+ * What padding adds (PAD; kwp.lds, kwp.global and kwp.batch are the arrangements above by the padded length): a secret
+ * of any length m = 1 .. 2^32 - 1 bytes is zero-filled to n = ceil(m / 8) semiblocks and A starts as A6 59 59 A6 || m
+ * (big-endian, the MLI).  n = 1 is ONE block AES(A | R_1), no chain (kwp.block).  Unwrap accepts when MSB32(A) is the
+ * constant, 8 (n - 1) < MLI <= 8 n and the 8 n - MLI bytes behind the secret are zero: all three are computed and ORed,
+ * no branch, and the outcome is the MLI or 0 (an authentic MLI is at least 1).  Only the wrap's input is ever short: it
+ * is zero-filled on its way into LDS (kwp.lds, kwp.batch) or handed to the first pass of kw_chain_global as a register
+ * (kwp.global); everything written is whole semiblocks.  In a batch the records of a wave have lengths of their own
+ * (lens), so the four rows leave the chain loop at different trips and some take the one-block path: the row primitives
+ * read within their row only (DPP row rotates, quad permutes, the row's LDS slot), and the verdict takes A from the row's
+ * own lanes (a bpermute within the row, whose lanes are active together).
  */
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -33,6 +45,7 @@
 #include "uaes_plan.h"
 
 #define KW_IV      0xA6A6A6A6u
+#define KWP_IV     0xA65959A6u                            /* A6 59 59 A6: the same word in either byte order */
 #define KW_CH      16u                                    /* kw.global: steps a load runs ahead of its use */
 #define KW_R_AT    UAES_LDS_ROW                           /* kw.lds: LDS byte address of R (+ 8 bytes nobody reads) */
 #define KW_LDS     (UAES_LDS_ROW + (unsigned)UAES_KW_LDS_MAX + 8u)
@@ -43,13 +56,25 @@
 static_assert(UAES_KW_LDS_MAX / 8 >= 2 * KW_CH, "kw.global loads two chunks ahead of the oldest store it may meet");
 static_assert(KW_LDS <= 160u * 1024u && KW_BATCH_LDS <= 160u * 1024u, "LDS of one CU");
 static_assert(UAES_KW_BATCH_MAX >= 64 && UAES_KW_BATCH_MAX % 8 == 0, "a batch record holds at least 64 bytes");
-static_assert(KW_SLOT / 64u == 4u && UAES_KW_BATCH_MAX <= 256, "k_kwp_batch stages a record as four words a lane; the slot is 256 + 8 bytes");
+static_assert(KW_SLOT / 64u == 4u && UAES_KW_BATCH_MAX <= 256, "k_kw_batch stages a padded record as four words a lane; the slot is 256 + 8 bytes");
 
 template <bool A4>
 __device__ __forceinline__ u32 kw_ld(const unsigned char *p)
 {
     if (A4) return *(const u32 *)p;
     return (u32)p[0] | ((u32)p[1] << 8) | ((u32)p[2] << 16) | ((u32)p[3] << 24);
+}
+
+/* the word at p of which only the first `avail` bytes (may be <= 0) exist: zeros behind them, and they are not read */
+template <bool A4>
+__device__ __forceinline__ u32 kwp_ld(const unsigned char *p, long long avail)
+{
+    if (avail >= 4) return kw_ld<A4>(p);
+    u32 v = 0;
+#pragma unroll
+    for (u32 k = 0; k < 3; ++k)
+        if ((long long)k < avail) v |= (u32)p[k] << (8u * k);
+    return v;
 }
 
 template <bool A4>
@@ -111,19 +136,31 @@ __device__ __forceinline__ u32 kw_chain_lds(u32 a, u32 base, u32 n, const RowLan
     return a;
 }
 
+/* n = 1 (padding only): the semiblock at LDS `base` and A through one block of the cipher, stored as kw_chain_lds stores
+ * a step */
+template <int NR, bool DEC>
+__device__ __forceinline__ u32 kwp_block(u32 a, u32 base, const RowLane<NR> &L)
+{
+    const u32 half = 4u * (L.c & 1u);
+    const u32 x = L.c < 2u ? a : lds_word(base + half);
+    const u32 e = DEC ? row_decrypt<NR>(x, L) : row_encrypt<NR>(x, L);
+    kw_lds_st(L.c < 2u ? base + 8u + half : base + half, e);
+    return e;
+}
+
 /* the whole chain in place in global memory (kw.global, above): the first n steps read rin, the others rout, the loads a
- * chunk of KW_CH steps ahead; n >= 2 KW_CH; returns the final A word.  PAD (KWP's wrap): semiblock n - 1 of rin may be
- * short; this lane's word of it, zero-filled, comes in `lastw`, and rin is not read there */
-template <int NR, bool DEC, bool A4, bool PAD = false>
+ * chunk of KW_CH steps ahead; n >= 2 KW_CH; returns the final A word.  SHORT (the wrap of a padded secret): semiblock
+ * n - 1 of rin may be short; this lane's word of it, zero-filled, comes in `lastw`, and rin is not read there */
+template <int NR, bool DEC, bool A4, bool SHORT>
 __device__ __forceinline__ u32 kw_chain_global(u32 a, const unsigned char *rin, unsigned char *rout, u64 n,
-                                               const RowLane<NR> &L, u32 lastw = 0u)
+                                               const RowLane<NR> &L, u32 lastw)
 {
     const u32 half = 4u * (L.c & 1u);
     const u64 steps = 6 * n;
     u64 kp = 0, ip = 0;                                         /* the step the next load is for, and kp mod n */
     auto fetch = [&]() {
         const u64 e = DEC ? n - 1 - ip : ip;
-        const bool part = PAD && kp == n - 1;                   /* the short semiblock: a whole one is loaded instead */
+        const bool part = SHORT && kp == n - 1;                 /* the short semiblock: a whole one is loaded instead */
         const u32 v = kw_ld<A4>((kp < n ? rin : rout) + 8 * (part ? e - 1 : e) + half);
         ++kp;
         if (++ip == n) ip = 0;                                  /* past the last step: a semiblock nobody uses */
@@ -157,121 +194,21 @@ __device__ __forceinline__ u32 kw_chain_global(u32 a, const unsigned char *rin, 
     return a;
 }
 
-/* is A the initial value?  (one secret per wave: every row holds the same A) */
+/* this lane's word of the initial A of a wrap (padded: of m bytes) */
+template <bool PAD>
+__device__ __forceinline__ u32 kw_a0(u32 m, u32 c)
+{
+    return !PAD ? KW_IV : c == 1u ? bswap32(m) : KWP_IV;
+}
+
+/* is A the initial value of a wrap without padding?  (one secret per wave: every row holds the same A) */
 __device__ __forceinline__ bool kw_forged_wave(u32 a)
 {
     return (u32)__builtin_amdgcn_readlane((int)a, 0) != KW_IV || (u32)__builtin_amdgcn_readlane((int)a, 4) != KW_IV;
 }
 
-/* in: the secret (wrap) / A || R (unwrap); out: A || R / the secret; n = semiblocks of the secret.  in and out are
- * disjoint or the in-place form (the secret at wrapped + 8); unwrap writes *status = 0 / 0x1A and leaves what the
- * chain made in `out` either way, like the reference.  A4: both pointers 4-byte aligned. */
-template <int NR, bool DEC, bool GLOBAL, bool A4>
-__global__ __launch_bounds__(64) void k_kw(uaesk_rk rk, uaesk_tables tb, const unsigned char *in, unsigned char *out,
-                                           u64 n, int *status)
-{
-    if (DEC) row_fill_tables_dec(tb.td0, rk); else row_fill_tables(tb.te0, rk);
-    const RowLane<NR> L = row_lane<NR>();
-    const u32 half = 4u * (L.c & 1u);
-    const unsigned char *rin = DEC ? in + 8 : in;
-    unsigned char *rout = DEC ? out : out + 8;
-    u32 a = DEC ? kw_ld<A4>(in + half) : KW_IV;
-    if (!GLOBAL) {
-        const u32 nw = 2u * (u32)n;
-        for (u32 j = threadIdx.x; j < nw; j += 64u) kw_lds_st(KW_R_AT + 4u * j, kw_ld<A4>(rin + 4u * j));
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          /* one wave: its LDS operations complete in order */
-        a = kw_chain_lds<NR, DEC>(a, KW_R_AT, (u32)n, L);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        for (u32 j = threadIdx.x; j < nw; j += 64u) kw_st<A4>(rout + 4u * j, lds_word(KW_R_AT + 4u * j));
-    } else {
-        a = kw_chain_global<NR, DEC, A4>(a, rin, rout, n, L);
-    }
-    if (!DEC) {
-        if (threadIdx.x < 8u && (threadIdx.x & 3u) == 0) kw_st<A4>(out + half, a);     /* lanes 0 and 4: A */
-    } else {
-        const bool forged = kw_forged_wave(a);
-        if (threadIdx.x == 0) *status = forged ? 0x1A : 0;
-    }
-}
-
-/* nkeys records of n semiblocks each, back to back: the secret of record m at m * 8 n, its wrapped form at
- * m * (8 n + 8).  Unwrap: verdicts[m] = 1 (authentic) / 0, *bad |= 1 for a forgery, and a forged record's output is
- * what the chain made of it, or zeros when wipe != 0.  A4: both arrays 4-byte aligned. */
-template <int NR, bool DEC, bool A4>
-__global__ __launch_bounds__(UAES_WG) void k_kw_batch(uaesk_rk rk, uaesk_tables tb, u64 nkeys, u32 n,
-                                                      const unsigned char *in, unsigned char *out,
-                                                      unsigned char *verdicts, int *bad, int wipe)
-{
-    if (DEC) row4_fill_tables_dec(tb.td0, rk); else row4_fill_tables(tb.te0, rk);
-    const RowLane<NR> L = row4_lane<NR>();
-    const u32 row = threadIdx.x >> 4, li = threadIdx.x & 15u, half = 4u * (L.c & 1u), nw = 2u * n;
-    const u32 slot = KW_BATCH_AT + row * KW_SLOT;
-    const u64 rows = blockDim.x >> 4, sb = 8ull * n, wb = sb + 8;
-    for (u64 m = (u64)blockIdx.x * rows + row; m < nkeys; m += (u64)gridDim.x * rows) {
-        const unsigned char *src = in + m * (DEC ? wb : sb);
-        unsigned char *dst = out + m * (DEC ? sb : wb);
-        const unsigned char *rin = DEC ? src + 8 : src;
-        unsigned char *rout = DEC ? dst : dst + 8;
-        u32 a = DEC ? kw_ld<A4>(src + half) : KW_IV;
-        for (u32 j = li; j < nw; j += 16u) kw_lds_st(slot + 4u * j, kw_ld<A4>(rin + 4u * j));
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          /* the record's sixteen lanes are one wave's */
-        a = kw_chain_lds<NR, DEC>(a, slot, n, L);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        bool zero = false;
-        if (DEC) {
-            const bool forged = row_any(L.c < 2u && a != KW_IV);
-            row_verdict(li == 0, verdicts, m, !forged, bad);
-            zero = forged && wipe;
-        } else if (li < 8u && (li & 3u) == 0) {
-            kw_st<A4>(dst + half, a);
-        }
-        for (u32 j = li; j < nw; j += 16u) kw_st<A4>(rout + 4u * j, zero ? 0u : lds_word(slot + 4u * j));
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          /* read out before the next record is staged */
-    }
-}
-
-/* ---- KWP, RFC 5649 / SP 800-38F KWP: a secret of any length m = 1 .. 2^32 - 1 bytes ---------------------------------
- * The secret is zero-filled to n = ceil(m / 8) semiblocks and A starts as A6 59 59 A6 || m (big-endian, the MLI).
- * n >= 2 is the chain above with that A; n = 1 is ONE block AES(A | R_1), no chain (kwp.block).  Unwrap accepts when
- * MSB32(A) is the constant, 8 (n - 1) < MLI <= 8 n and the 8 n - MLI bytes behind the secret are zero: all three are
- * computed and ORed, no branch, and the outcome is the MLI or 0 (an authentic MLI is at least 1).
- * Only the wrap's input is ever short: it is zero-filled on its way into LDS (kwp.lds, kwp.batch) or handed to the first
- * pass of kw_chain_global as a register (kwp.global); everything written is whole semiblocks.  In a batch the records of
- * a wave have lengths of their own (lens), so the four rows leave the chain loop at different trips and some take the
- * one-block path: the row primitives read within their row only (DPP row rotates, quad permutes, the row's LDS slot),
- * and the verdict takes A from the row's own lanes (a bpermute within the row, whose lanes are active together). */
-#define KWP_IV 0xA65959A6u                                /* A6 59 59 A6: the same word in either byte order */
-
-/* the word at p of which only the first `avail` bytes (may be <= 0) exist: zeros behind them, and they are not read */
-template <bool A4>
-__device__ __forceinline__ u32 kwp_ld(const unsigned char *p, long long avail)
-{
-    if (avail >= 4) return kw_ld<A4>(p);
-    u32 v = 0;
-#pragma unroll
-    for (u32 k = 0; k < 3; ++k)
-        if ((long long)k < avail) v |= (u32)p[k] << (8u * k);
-    return v;
-}
-
-/* this lane's word of the initial A of a wrap of m bytes */
-__device__ __forceinline__ u32 kwp_a0(u32 m, u32 c)
-{
-    return c == 1u ? bswap32(m) : KWP_IV;
-}
-
-/* n = 1: the semiblock at LDS `base` and A through one block of the cipher, stored as kw_chain_lds stores a step */
-template <int NR, bool DEC>
-__device__ __forceinline__ u32 kwp_block(u32 a, u32 base, const RowLane<NR> &L)
-{
-    const u32 half = 4u * (L.c & 1u);
-    const u32 x = L.c < 2u ? a : lds_word(base + half);
-    const u32 e = DEC ? row_decrypt<NR>(x, L) : row_encrypt<NR>(x, L);
-    kw_lds_st(L.c < 2u ? base + 8u + half : base + half, e);
-    return e;
-}
-
-/* a0, a1: the words of A after the unwrap; w0, w1: those of the last semiblock R_n.  The MLI, or 0 for a forgery */
+/* padding's verdict.  a0, a1: the words of A after the unwrap; w0, w1: those of the last semiblock R_n.  The MLI, or 0
+ * for a forgery */
 __device__ __forceinline__ u32 kwp_verdict(u32 a0, u32 a1, u64 n, u32 w0, u32 w1)
 {
     const u64 mli = bswap32(a1), top = 8 * n;
@@ -281,36 +218,40 @@ __device__ __forceinline__ u32 kwp_verdict(u32 a0, u32 a1, u64 n, u32 w0, u32 w1
     return bad ? 0u : (u32)mli;
 }
 
-/* One secret, one wave.  wrap: in = the secret of `len` bytes, out = the 8 n + 8 bytes of A || R; unwrap: in = A || R,
- * len = its bytes - 8, out = the 8 n bytes the chain makes (the secret and its zero fill), status[0] = 0 / 0x1A and
- * status[1] = the MLI / 0.  ARR = enum uaes_kwp_arrangement.  Disjoint buffers or the in-place form, as k_kw; what sits
- * in LDS is read whole before anything is written.  A4: both pointers 4-byte aligned. */
-template <int NR, bool DEC, int ARR, bool A4>
-__global__ __launch_bounds__(64) void k_kwp(uaesk_rk rk, uaesk_tables tb, const unsigned char *in, unsigned char *out,
-                                            u64 len, int *status)
+/* One secret, one wave; ARR = enum uaes_kw_arrangement.  len = semiblocks of the secret, or PAD: its bytes (wrap) / the
+ * bytes of the wrapped form - 8 (unwrap).  wrap: in = the secret, out = the 8 n + 8 bytes of A || R; unwrap: in = A || R,
+ * out = the 8 n bytes the chain makes (the secret and, padded, its zero fill), left there whatever the verdict, like the
+ * reference; status[0] = 0 / 0x1A and, PAD, status[1] = the MLI / 0.  in and out are disjoint or the in-place form (the
+ * secret at wrapped + 8); what sits in LDS is read whole before anything is written.  A4: both pointers 4-byte aligned. */
+template <int NR, bool DEC, int ARR, bool A4, bool PAD>
+__global__ __launch_bounds__(64) void k_kw(uaesk_rk rk, uaesk_tables tb, const unsigned char *in, unsigned char *out,
+                                           u64 len, int *status)
 {
     if (DEC) row_fill_tables_dec(tb.td0, rk); else row_fill_tables(tb.te0, rk);
     const RowLane<NR> L = row_lane<NR>();
     const u32 half = 4u * (L.c & 1u);
-    const u64 n = (len + 7) / 8;
+    const u64 n = PAD ? (len + 7) / 8 : len;
     const unsigned char *rin = DEC ? in + 8 : in;
     unsigned char *rout = DEC ? out : out + 8;
-    u32 a = DEC ? kw_ld<A4>(in + half) : kwp_a0((u32)len, L.c);
+    u32 a = DEC ? kw_ld<A4>(in + half) : kw_a0<PAD>((u32)len, L.c);
     u32 w0 = 0u, w1 = 0u;
-    if (ARR != UAES_KWP_GLOBAL) {
+    if (ARR != UAES_KW_GLOBAL) {
         const u32 nw = 2u * (u32)n;
         for (u32 j = threadIdx.x; j < nw; j += 64u)
-            kw_lds_st(KW_R_AT + 4u * j, DEC ? kw_ld<A4>(rin + 4u * j) : kwp_ld<A4>(rin + 4u * j, (long long)len - 4ll * j));
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        a = ARR == UAES_KWP_BLOCK ? kwp_block<NR, DEC>(a, KW_R_AT, L) : kw_chain_lds<NR, DEC>(a, KW_R_AT, (u32)n, L);
+            kw_lds_st(KW_R_AT + 4u * j, PAD && !DEC ? kwp_ld<A4>(rin + 4u * j, (long long)len - 4ll * j) : kw_ld<A4>(rin + 4u * j));
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          /* one wave: its LDS operations complete in order */
+        a = ARR == UAES_KW_BLOCK ? kwp_block<NR, DEC>(a, KW_R_AT, L) : kw_chain_lds<NR, DEC>(a, KW_R_AT, (u32)n, L);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         for (u32 j = threadIdx.x; j < nw; j += 64u) kw_st<A4>(rout + 4u * j, lds_word(KW_R_AT + 4u * j));
-        w0 = lds_word(KW_R_AT + 4u * nw - 8u);
-        w1 = lds_word(KW_R_AT + 4u * nw - 4u);
+        if (PAD && DEC) {
+            w0 = lds_word(KW_R_AT + 4u * nw - 8u);
+            w1 = lds_word(KW_R_AT + 4u * nw - 4u);
+        }
     } else {
         const u64 at = 8 * (n - 1) + half;
-        a = kw_chain_global<NR, DEC, A4, !DEC>(a, rin, rout, n, L, DEC ? 0u : kwp_ld<A4>(rin + at, (long long)(len - at)));
-        if (DEC) {                                        /* R_n as this wave stored it, 5 n steps ago or later */
+        a = kw_chain_global<NR, DEC, A4, PAD && !DEC>(a, rin, rout, n, L,
+                                                      PAD && !DEC ? kwp_ld<A4>(rin + at, (long long)(len - at)) : 0u);
+        if (PAD && DEC) {                                 /* R_n as this wave stored it, 5 n steps ago or later */
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             w0 = kw_ld<A4>(rout + 8 * (n - 1));
             w1 = kw_ld<A4>(rout + 8 * (n - 1) + 4);
@@ -318,6 +259,9 @@ __global__ __launch_bounds__(64) void k_kwp(uaesk_rk rk, uaesk_tables tb, const 
     }
     if (!DEC) {
         if (threadIdx.x < 8u && (threadIdx.x & 3u) == 0) kw_st<A4>(out + half, a);     /* lanes 0 and 4: A */
+    } else if (!PAD) {
+        const bool forged = kw_forged_wave(a);
+        if (threadIdx.x == 0) *status = forged ? 0x1A : 0;
     } else {
         const u32 mli = kwp_verdict((u32)__builtin_amdgcn_readlane((int)a, 0), (u32)__builtin_amdgcn_readlane((int)a, 4),
                                     n, w0, w1);
@@ -325,28 +269,30 @@ __global__ __launch_bounds__(64) void k_kwp(uaesk_rk rk, uaesk_tables tb, const 
     }
 }
 
-/* nkeys records in slots.  wrap: secret m at m * rec, `lens[m]` (NULL: rec) of its bytes count, its wrapped form goes
- * to m * (8 ceil(rec / 8) + 8) and is 8 ceil(lens[m] / 8) + 8 bytes; a length of 0 or above rec writes nothing and sets
- * bit 1 of *bad.  unwrap: rec = the wrapped slot - 8 (a multiple of 8); wrapped record m at m * (rec + 8), lens[m]
- * (NULL: rec + 8) bytes of it count, the 8 n it unwraps to go to m * rec, verdicts[m] = 1 / 0, lens_out[m] = the MLI / 0,
- * bit 0 of *bad for a record that fails; a length that is no multiple of 8, below 16 or above rec + 8 fails unwritten;
- * a forged record's output is what the chain made, or zeros when wipe != 0.  A4: both arrays and both slot sizes are
- * 4-byte aligned. */
-template <int NR, bool DEC, bool A4>
-__global__ __launch_bounds__(UAES_WG) void k_kwp_batch(uaesk_rk rk, uaesk_tables tb, u64 nkeys, u32 rec, const u32 *lens,
-                                                       const unsigned char *in, unsigned char *out, u32 *lens_out,
-                                                       unsigned char *verdicts, int *bad, int wipe)
+/* nkeys records in slots, back to back.  !PAD: rec = semiblocks of every secret; the secret of record m at m * 8 rec, its
+ * wrapped form at m * (8 rec + 8); lens and lens_out are not read.  PAD: rec = bytes of a secret's slot (unwrap: the
+ * wrapped slot - 8, a multiple of 8).  wrap: secret m at m * rec, `lens[m]` (NULL: rec) of its bytes count, its wrapped
+ * form goes to m * (8 ceil(rec / 8) + 8) and is 8 ceil(lens[m] / 8) + 8 bytes; a length of 0 or above rec writes nothing
+ * and sets bit 1 of *bad.  unwrap: wrapped record m at m * (rec + 8), lens[m] (NULL: rec + 8) bytes of it count, the 8 n it
+ * unwraps to go to m * rec, lens_out[m] = the MLI / 0; a length that is no multiple of 8, below 16 or above rec + 8 fails
+ * unwritten.  Either: unwrap writes verdicts[m] = 1 (authentic) / 0 and bit 0 of *bad for a record that fails, and a forged
+ * record's output is what the chain made of it, or zeros when wipe != 0.  A4: both arrays and both slot sizes are 4-byte
+ * aligned. */
+template <int NR, bool DEC, bool A4, bool PAD>
+__global__ __launch_bounds__(UAES_WG) void k_kw_batch(uaesk_rk rk, uaesk_tables tb, u64 nkeys, u32 rec, const u32 *lens,
+                                                      const unsigned char *in, unsigned char *out, u32 *lens_out,
+                                                      unsigned char *verdicts, int *bad, int wipe)
 {
     if (DEC) row4_fill_tables_dec(tb.td0, rk); else row4_fill_tables(tb.te0, rk);
     const RowLane<NR> L = row4_lane<NR>();
     const u32 row = threadIdx.x >> 4, li = threadIdx.x & 15u, half = 4u * (L.c & 1u);
     const u32 slot = KW_BATCH_AT + row * KW_SLOT;
-    const u64 rows = blockDim.x >> 4, wb = 8ull * ((rec + 7u) / 8u) + 8;
+    const u64 rows = blockDim.x >> 4, sb = PAD ? (u64)rec : 8ull * rec, wb = PAD ? 8ull * ((rec + 7u) / 8u) + 8 : sb + 8;
     for (u64 m = (u64)blockIdx.x * rows + row; m < nkeys; m += (u64)gridDim.x * rows) {
-        const unsigned char *src = in + m * (DEC ? wb : (u64)rec);
-        unsigned char *dst = out + m * (DEC ? (u64)rec : wb);
-        const u32 given = lens ? lens[m] : DEC ? rec + 8u : rec;
-        const bool valid = DEC ? (given & 7u) == 0 && given >= 16u && given <= rec + 8u : given - 1u < rec;
+        const unsigned char *src = in + m * (DEC ? wb : sb);
+        unsigned char *dst = out + m * (DEC ? sb : wb);
+        const u32 given = !PAD ? rec : lens ? lens[m] : DEC ? rec + 8u : rec;
+        const bool valid = !PAD || (DEC ? (given & 7u) == 0 && given >= 16u && given <= rec + 8u : given - 1u < rec);
         if (!valid) {
             if (DEC) {
                 row_verdict(li == 0, verdicts, m, false, bad);
@@ -356,11 +302,11 @@ __global__ __launch_bounds__(UAES_WG) void k_kwp_batch(uaesk_rk rk, uaesk_tables
             }
             continue;
         }
-        const u32 len = DEC ? given - 8u : given, n = (len + 7u) / 8u, nw = 2u * n;
+        const u32 len = DEC ? given - 8u : given, n = PAD ? (len + 7u) / 8u : rec, nw = 2u * n;
         const unsigned char *rin = DEC ? src + 8 : src;
         unsigned char *rout = DEC ? dst : dst + 8;
-        u32 a = DEC ? kw_ld<A4>(src + half) : kwp_a0(len, L.c);
-        if (DEC) {
+        u32 a = DEC ? kw_ld<A4>(src + half) : kw_a0<PAD>(len, L.c);
+        if (DEC || !PAD) {
             for (u32 j = li; j < nw; j += 16u) kw_lds_st(slot + 4u * j, kw_ld<A4>(rin + 4u * j));
         } else {
             /* a lane's up to four words (KW_SLOT: 64 words a record) are requested together, clamped to the last whole
@@ -380,11 +326,15 @@ __global__ __launch_bounds__(UAES_WG) void k_kwp_batch(uaesk_rk rk, uaesk_tables
             }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          /* the record's sixteen lanes are one wave's */
-        if (n == 1u) a = kwp_block<NR, DEC>(a, slot, L);
+        if (PAD && n == 1u) a = kwp_block<NR, DEC>(a, slot, L);
         else a = kw_chain_lds<NR, DEC>(a, slot, n, L);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         bool zero = false;
-        if (DEC) {
+        if (DEC && !PAD) {
+            const bool forged = row_any(L.c < 2u && a != KW_IV);
+            row_verdict(li == 0, verdicts, m, !forged, bad);
+            zero = forged && wipe;
+        } else if (DEC) {
             const int lane0 = (int)(threadIdx.x & 48u);             /* this row's first lane within the wave */
             const u32 mli = kwp_verdict((u32)__shfl((int)a, lane0), (u32)__shfl((int)a, lane0 + 4), n,
                                         lds_word(slot + 4u * nw - 8u), lds_word(slot + 4u * nw - 4u));
@@ -400,44 +350,15 @@ __global__ __launch_bounds__(UAES_WG) void k_kwp_batch(uaesk_rk rk, uaesk_tables
 }
 
 /* ---- the plan (uaes_plan.h) ---------------------------------------------------------------------------------------- */
-static int plan_kwp(int dir, size_t len, size_t nkeys, uaes_plan *p)
+static int plan_kw(bool pad, int dir, size_t len, size_t nkeys, uaes_plan *p)
 {
     memset(p, 0, sizeof *p);
-    if ((dir != 0 && dir != 1) || len == 0) return (int)hipErrorInvalidValue;
-    if (dir ? len % 8 != 0 || len > UAES_KWP_MAX + 1 : len > UAES_KWP_MAX) return (int)hipErrorInvalidValue;
-    p->launches = 1;
-    if (nkeys == 0) {
-        p->arrangement = len <= 8 ? UAES_KWP_BLOCK : (len + 7) / 8 * 8 <= UAES_KW_LDS_MAX ? UAES_KWP_LDS : UAES_KWP_GLOBAL;
-        p->grid = 1;
-        p->steps = 64;
-        return 0;
-    }
-    if (len > UAES_KW_BATCH_MAX) return (int)hipErrorInvalidValue;
-    const RowShape s = uaesk_row_shape(nkeys);
-    p->arrangement = UAES_KWP_BATCH;
-    p->grid = s.grid;
-    p->steps = s.wg;
-    return 0;
-}
-
-extern "C" int uaesk_plan_kwp(int dir, size_t len, size_t nkeys, uaes_plan *p)
-{
-    return plan_kwp(dir, len, nkeys, p);
-}
-
-extern "C" const char *uaesk_kwp_arrangement_name(int id)
-{
-    static const char *const names[] = { "kwp.block", "kwp.lds", "kwp.global", "kwp.batch" };
-    return id >= 0 && id < 4 ? names[id] : "?";
-}
-
-static int plan_kw(int dir, size_t len, size_t nkeys, uaes_plan *p)
-{
-    memset(p, 0, sizeof *p);
-    if ((dir != 0 && dir != 1) || len % 8 || len < 16) return (int)hipErrorInvalidValue;
+    if (dir != 0 && dir != 1) return (int)hipErrorInvalidValue;
+    if (pad ? len == 0 || (dir ? len % 8 != 0 || len > UAES_KWP_MAX + 1 : len > UAES_KWP_MAX) : len % 8 || len < 16)
+        return (int)hipErrorInvalidValue;
     p->launches = 1;
     if (nkeys == 0) {                                     /* one wave: sixteen lanes per block, four rows redundantly */
-        p->arrangement = len <= UAES_KW_LDS_MAX ? UAES_KW_LDS : UAES_KW_GLOBAL;
+        p->arrangement = len <= 8 ? UAES_KW_BLOCK : (len + 7) / 8 * 8 <= UAES_KW_LDS_MAX ? UAES_KW_LDS : UAES_KW_GLOBAL;
         p->grid = 1;
         p->steps = 64;
         return 0;
@@ -450,103 +371,68 @@ static int plan_kw(int dir, size_t len, size_t nkeys, uaes_plan *p)
     return 0;
 }
 
-extern "C" int uaesk_plan_kw(int dir, size_t len, size_t nkeys, uaes_plan *p)
+extern "C" int uaesk_plan_kw(int dir, size_t len, size_t nkeys, uaes_plan *p) { return plan_kw(false, dir, len, nkeys, p); }
+extern "C" int uaesk_plan_kwp(int dir, size_t len, size_t nkeys, uaes_plan *p) { return plan_kw(true, dir, len, nkeys, p); }
+
+static const char *kw_name(bool pad, int id)
 {
-    return plan_kw(dir, len, nkeys, p);
+    static const char *const names[2][4] = { { "?", "kw.lds", "kw.global", "kw.batch" },
+                                             { "kwp.block", "kwp.lds", "kwp.global", "kwp.batch" } };
+    return id >= 0 && id < 4 ? names[pad][id] : "?";
 }
 
-extern "C" const char *uaesk_kw_arrangement_name(int id)
-{
-    static const char *const names[] = { "kw.lds", "kw.global", "kw.batch" };
-    return id >= 0 && id < 3 ? names[id] : "?";
-}
+extern "C" const char *uaesk_kw_arrangement_name(int id) { return kw_name(false, id); }
+extern "C" const char *uaesk_kwp_arrangement_name(int id) { return kw_name(true, id); }
 
 /* ---- launchers ------------------------------------------------------------------------------------------------------ */
-template <int NR>
+template <int NR, bool PAD>
 static int launch_kw(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *k, bool dec, const void *in, size_t len,
                      void *out, int *status)
 {
     uaes_plan p;
-    const int e = plan_kw(dec, len, 0, &p);
-    if (e) return e;
-    return with_bool(dec, [&](auto DEC) {
-        return with_bool(p.arrangement == UAES_KW_GLOBAL, [&](auto G) {
-            return with_bool(uaesk_rows_a4(in, out, len), [&](auto A4) {
-                return uaesk_launch(k_kw<NR, decltype(DEC)::value, decltype(G)::value, decltype(A4)::value>, p.grid, p.steps,
-                                    KW_LDS, st, *k, *tb, in, out, len / 8, status); }); }); });
-}
-
-template <int NR>
-static int launch_kw_batch(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *k, bool dec, int wipe, size_t nkeys,
-                           size_t len, const void *in, void *out, void *verdicts, int *bad)
-{
-    uaes_plan p;
-    const int e = plan_kw(dec, len, nkeys, &p);
-    if (e) return e;
-    return with_bool(dec, [&](auto DEC) {
-        return with_bool(uaesk_rows_a4(in, out, len), [&](auto A4) {
-            return uaesk_launch(k_kw_batch<NR, decltype(DEC)::value, decltype(A4)::value>, p.grid, p.steps, KW_BATCH_LDS, st,
-                                *k, *tb, nkeys, len / 8, in, out, verdicts, bad, wipe); }); });
-}
-
-extern "C" int uaesk_kw(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, const uaesk_rk *dk, int unwrap,
-                        const void *in, size_t secret_len, void *out, int *status)
-{
-    DISPATCH_NR(nr, return (launch_kw<NR>(S(stream), tb, unwrap ? dk : ek, unwrap != 0, in, secret_len, out, status)));
-    return 0;
-}
-
-template <int NR>
-static int launch_kwp(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *k, bool dec, const void *in, size_t len,
-                      void *out, int *status)
-{
-    uaes_plan p;
-    const int e = plan_kwp(dec, len, 0, &p);
+    const int e = plan_kw(PAD, dec, len, 0, &p);
     if (e) return e;
     return with_bool(dec, [&](auto DEC) {
         return with_bool(uaesk_rows_a4(in, out, 0), [&](auto A4) {
             constexpr bool D = decltype(DEC)::value, A = decltype(A4)::value;
-            auto *kern = p.arrangement == UAES_KWP_BLOCK ? k_kwp<NR, D, UAES_KWP_BLOCK, A>
-                         : p.arrangement == UAES_KWP_LDS ? k_kwp<NR, D, UAES_KWP_LDS, A> : k_kwp<NR, D, UAES_KWP_GLOBAL, A>;
-            return uaesk_launch(kern, p.grid, p.steps, KW_LDS, st, *k, *tb, in, out, len, status); }); });
+            /* without padding the plan never says block, and no such instance is made */
+            auto *kern = p.arrangement == UAES_KW_GLOBAL ? k_kw<NR, D, UAES_KW_GLOBAL, A, PAD>
+                         : p.arrangement == UAES_KW_LDS ? k_kw<NR, D, UAES_KW_LDS, A, PAD>
+                                                        : k_kw<NR, D, PAD ? UAES_KW_BLOCK : UAES_KW_LDS, A, PAD>;
+            return uaesk_launch(kern, p.grid, p.steps, KW_LDS, st, *k, *tb, in, out, PAD ? len : len / 8, status); }); });
 }
 
-template <int NR>
-static int launch_kwp_batch(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *k, bool dec, int wipe, size_t nkeys,
-                            size_t rec, const void *lens, const void *in, void *out, void *lens_out, void *verdicts, int *bad)
+template <int NR, bool PAD>
+static int launch_kw_batch(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *k, bool dec, int wipe, size_t nkeys,
+                           size_t rec, const void *lens, const void *in, void *out, void *lens_out, void *verdicts, int *bad)
 {
     uaes_plan p;
-    const int e = plan_kwp(dec, rec, nkeys, &p);
+    const int e = plan_kw(PAD, dec, rec, nkeys, &p);
     if (e) return e;
     return with_bool(dec, [&](auto DEC) {
         return with_bool(uaesk_rows_a4(in, out, dec ? 0 : rec), [&](auto A4) {
-            return uaesk_launch(k_kwp_batch<NR, decltype(DEC)::value, decltype(A4)::value>, p.grid, p.steps, KW_BATCH_LDS, st,
-                                *k, *tb, nkeys, rec, lens, in, out, lens_out, verdicts, bad, wipe); }); });
+            return uaesk_launch(k_kw_batch<NR, decltype(DEC)::value, decltype(A4)::value, PAD>, p.grid, p.steps, KW_BATCH_LDS,
+                                st, *k, *tb, nkeys, PAD ? rec : rec / 8, lens, in, out, lens_out, verdicts, bad, wipe); }); });
 }
 
-extern "C" int uaesk_kwp(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, const uaesk_rk *dk, int unwrap,
-                         const void *in, size_t len, void *out, int *status)
+extern "C" int uaesk_kw(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, const uaesk_rk *dk, int pad,
+                        int unwrap, const void *in, size_t len, void *out, int *status)
 {
-    DISPATCH_NR(nr, return (launch_kwp<NR>(S(stream), tb, unwrap ? dk : ek, unwrap != 0, in, len, out, status)));
+    const uaesk_rk *k = unwrap ? dk : ek;
+    DISPATCH_NR(nr, return (pad ? launch_kw<NR, true>(S(stream), tb, k, unwrap != 0, in, len, out, status)
+                                : launch_kw<NR, false>(S(stream), tb, k, unwrap != 0, in, len, out, status)));
     return 0;
 }
 
-extern "C" int uaesk_kwp_batch(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, const uaesk_rk *dk,
-                               int unwrap, int wipe, size_t nkeys, size_t rec, const void *lens, const void *in, void *out,
-                               void *lens_out, void *verdicts, int *bad)
+extern "C" int uaesk_kw_batch(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, const uaesk_rk *dk, int pad,
+                              int unwrap, int wipe, size_t nkeys, size_t rec, const void *lens, const void *in, void *out,
+                              void *lens_out, void *verdicts, int *bad)
 {
+    const uaesk_rk *k = unwrap ? dk : ek;
     if (nkeys == 0) return 0;
-    DISPATCH_NR(nr, return (launch_kwp_batch<NR>(S(stream), tb, unwrap ? dk : ek, unwrap != 0, wipe, nkeys, rec, lens, in,
-                                                 out, lens_out, verdicts, bad)));
-    return 0;
-}
-
-extern "C" int uaesk_kw_batch(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, const uaesk_rk *dk,
-                              int unwrap, int wipe, size_t nkeys, size_t secret_bytes, const void *in, void *out,
-                              void *verdicts, int *bad)
-{
-    if (nkeys == 0) return 0;
-    DISPATCH_NR(nr, return (launch_kw_batch<NR>(S(stream), tb, unwrap ? dk : ek, unwrap != 0, wipe, nkeys, secret_bytes,
-                                                in, out, verdicts, bad)));
+    DISPATCH_NR(nr, return (pad ? launch_kw_batch<NR, true>(S(stream), tb, k, unwrap != 0, wipe, nkeys, rec, lens, in, out,
+                                                            lens_out, verdicts, bad)
+                                : launch_kw_batch<NR, false>(S(stream), tb, k, unwrap != 0, wipe, nkeys, rec, NULL, in, out,
+                                                             NULL, verdicts, bad)));
     return 0;
 }

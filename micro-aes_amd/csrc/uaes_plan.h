@@ -61,10 +61,10 @@
  *   KW    kw.lds                k_kw<LDS> (one wave; the semiblocks in LDS)         (1)    secret <= UAES_KW_LDS_MAX (4 KiB)
  *         kw.global             k_kw<in place> (one wave; loads a chunk ahead)      (1)    beyond
  *         kw.batch              k_kw_batch (sixteen lanes per record)               (1)    uaes_kw_*_batch, <= UAES_KW_BATCH_MAX (256 B)
- *   KWP   kwp.block             k_kwp<block> (one wave; one block, no chain)        (1)    secret <= 8 B (padded length 8)
- *         kwp.lds               k_kwp<LDS> (one wave; the semiblocks in LDS)        (1)    padded length <= UAES_KW_LDS_MAX (4 KiB)
- *         kwp.global            k_kwp<in place> (one wave; loads a chunk ahead)     (1)    beyond
- *         kwp.batch             k_kwp_batch (sixteen lanes per record, lengths per record) (1)  uaes_kwp_*_batch, <= UAES_KW_BATCH_MAX (256 B)
+ *   KWP   kwp.block             k_kw<block, padded> (one wave; one block, no chain) (1)    secret <= 8 B (padded length 8)
+ *         kwp.lds               k_kw<LDS, padded>                                   (1)    padded length <= UAES_KW_LDS_MAX (4 KiB)
+ *         kwp.global            k_kw<in place, padded>                              (1)    beyond
+ *         kwp.batch             k_kw_batch<padded> (lengths per record)             (1)    uaes_kwp_*_batch, <= UAES_KW_BATCH_MAX (256 B)
  *   FF1   ff1.batch             k_ff1<16> (sixteen lanes per record, four per wave) (1)    uaes_ff1_*_batch; one text of <= UAES_FF1_BATCH_MAX (128) numerals
  *         ff1.wave              k_ff1<64> (one wave per text)                       (1)    one longer text, <= UAES_FF1_MAX (4096) numerals
  *   FF3-1 ff3.batch             k_ff3 (sixteen lanes per record, four per wave)     (1)    uaes_ff3_*_batch; one text (<= 192 numerals) is a batch of one
@@ -237,7 +237,8 @@ const char *uaesk_chain_arrangement_name(int id);
  * Returns a HIP error code for a length that is no multiple of 8 or below 16, or a batch record above the limit. */
 #define UAES_KW_LDS_MAX   ((size_t)4096)
 #define UAES_KW_BATCH_MAX ((size_t)256)
-enum uaes_kw_arrangement { UAES_KW_LDS = 0, UAES_KW_GLOBAL, UAES_KW_BATCH };
+/* one enum for both planners (block: uaesk_plan_kwp alone); each has its own names, kw.* and kwp.* */
+enum uaes_kw_arrangement { UAES_KW_BLOCK = 0, UAES_KW_LDS, UAES_KW_GLOBAL, UAES_KW_BATCH };
 int uaesk_plan_kw(int dir, size_t len, size_t nkeys, uaes_plan *p);
 const char *uaesk_kw_arrangement_name(int id);
 
@@ -248,7 +249,6 @@ const char *uaesk_kw_arrangement_name(int id);
  * key wrap's, decided by the padded length with key wrap's limits.  Returns a HIP error code for a length of 0, an
  * unwrap length that is no multiple of 8, a length beyond the indicator's range or a batch slot above the limit. */
 #define UAES_KWP_MAX ((size_t)0xFFFFFFFFu)
-enum uaes_kwp_arrangement { UAES_KWP_BLOCK = 0, UAES_KWP_LDS, UAES_KWP_GLOBAL, UAES_KWP_BATCH };
 int uaesk_plan_kwp(int dir, size_t len, size_t nkeys, uaes_plan *p);
 const char *uaesk_kwp_arrangement_name(int id);
 

@@ -125,6 +125,10 @@ ARG_CASES = {
     "uaes_kw_unwrap": ((128, KEY, B, 16, B), DATALENGTH),
     "uaes_kw_wrap_batch": ((128, KEY, 1, 16, None, B), ARG),
     "uaes_kw_unwrap_batch": ((128, KEY, 1, 24, None, B, B), ARG),
+    "uaes_kwp_wrap": ((128, KEY, B, 0, B), DATALENGTH),                  # an empty secret
+    "uaes_kwp_unwrap": ((128, KEY, B, 8, B, None), DATALENGTH),
+    "uaes_kwp_wrap_batch": ((128, KEY, 1, 20, None, None, B), ARG),
+    "uaes_kwp_unwrap_batch": ((128, KEY, 1, 24, None, None, B, B, B), ARG),
     "uaes_ff1_encrypt": ((128, KEY, 10, None, None, 0, None, 10, B), ARG),
     "uaes_ff1_decrypt": ((128, KEY, 10, None, None, 0, None, 10, B), ARG),
     "uaes_ff1_encrypt_batch": ((128, KEY, 10, None, None, 0, 0, 1, 10, None, B, None), ARG),
@@ -201,6 +205,15 @@ def _kw(n, mem):
     yield "uaes_kw_unwrap", (128, KEY, wrapped, n + 8, out), AUTH
 
 
+def _kwp(n, mem):
+    wl = (n + 7) // 8 * 8 + 8                     # 16 bytes: whole semiblocks; 17: seven bytes of fill
+    wrapped, out, ln = mem.out(wl), mem.out(wl - 8), C.c_size_t(0)
+    yield "uaes_kwp_wrap", (128, KEY, mem.inp(text(n)), n, wrapped), OK
+    yield "uaes_kwp_unwrap", (128, KEY, wrapped, wl, out, C.byref(ln)), OK
+    wrapped[5] ^= 1
+    yield "uaes_kwp_unwrap", (128, KEY, wrapped, wl, out, C.byref(ln)), AUTH
+
+
 def _fpe(n, mem):
     ct = mem.out(n)
     yield "uaes_ff1_encrypt", (128, KEY, 10, None, b"tw", 2, mem.inp(DIGITS[:n]), n, ct), OK
@@ -229,5 +242,5 @@ TEXT_CASES = [
     _aead("uaes_gcmsiv_encrypt", "uaes_gcmsiv_decrypt", (N16,)),
     _aead("uaes_ocb_encrypt", "uaes_ocb_decrypt", (N16,)),
     _aead("uaes_ocb_encrypt_ex", "uaes_ocb_decrypt_ex", (N16, 12, 8), tag=8),
-    _siv, _kw, _fpe,
+    _siv, _kw, _fpe, _kwp,
 ]

@@ -108,6 +108,11 @@ def _batches():
     yield "uaes_kw_unwrap_batch", (128, KEY, n, m + 8, ct, out, ver), OK
     ct[1] ^= 1
     yield "uaes_kw_unwrap_batch", (128, KEY, n, m + 8, ct, out, ver), AUTH
+    lens_out = (C.c_uint32 * n)()
+    yield "uaes_kwp_wrap_batch", (128, KEY, n, m, None, pt, ct), OK
+    yield "uaes_kwp_unwrap_batch", (128, KEY, n, m + 8, None, ct, out, lens_out, ver), OK
+    ct[1] ^= 1
+    yield "uaes_kwp_unwrap_batch", (128, KEY, n, m + 8, None, ct, out, lens_out, ver), AUTH
     digits = bytes(i % 10 for i in range(n * m))
     yield "uaes_ff1_encrypt_batch", (128, KEY, 10, None, nonces, 4, 16, n, m, digits, ct, ver), OK
     yield "uaes_ff1_decrypt_batch", (128, KEY, 10, None, nonces, 4, 16, n, m, ct, out, ver), OK
@@ -121,6 +126,16 @@ def test_batch_entries_with_three_records():
         checked(name, args, want)
         ran.add(name)
     assert ran == {n for n in keyed_exports() if n.endswith("_batch")}
+
+
+def test_kwp_batches_with_three_records():
+    """key wrap with padding by name: the wrap, the unwrap of what it wrote, and the unwrap of a forged record"""
+    ran = []
+    for name, args, want in _batches():
+        if name.startswith("uaes_kwp_"):
+            checked(name, args, want)
+            ran.append((name, want))
+    assert ran == [("uaes_kwp_wrap_batch", OK), ("uaes_kwp_unwrap_batch", OK), ("uaes_kwp_unwrap_batch", AUTH)]
 
 
 # ---- the slice pipeline: a long host text leaves its function through run_pipelined's return

@@ -1,6 +1,7 @@
 """AES key wrap (RFC 3394) on the GPU (uaes_kw.hip) against the compiled reference: the RFC's six parameter sets, every
 short length, the lengths where the step counter grows a byte, the LDS / in-place boundary read from the planner at
-byte offsets 0..3, forgeries, the wipe switch and error lengths on device pointers, the in-place form, batches whose
+byte offsets 0..3, every residue of the chain's length against the look-ahead chunk, forgeries, a wrapping of the other
+mode (key wrap with padding runs the same kernels), the wipe switch and error lengths on device pointers, the in-place form, batches whose
 shapes come from the planner (with forged records in the first workgroup and in the stride loop's second turn) and a
 seeded fuzz of round trips.  Every failing case prints the tuple that reproduces it."""
 import ctypes as C
@@ -11,44 +12,13 @@ import pytest
 
 import micro_aes_amd as uaes
 from tests import kw_ref as R
+from tests import kwp_ref as P
+from tests.guarded_mem import Mem
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 0xA5
 E_ARG = -2
-
-
-class Mem:
-    """`size` bytes (starting with `data`, then `fill`) in host or device memory, `off` bytes behind an aligned base,
-    with guard bytes in front of and behind them"""
-
-    def __init__(self, data=b"", device=False, off=0, size=None, fill=0x5C, room=64):
-        data = bytes(data)
-        self.size = max(len(data), size or 0)
-        self.off, self.device = off, device
-        raw = bytes([GUARD]) * off + data + bytes([fill]) * (self.size - len(data)) + bytes([GUARD]) * room
-        if device:
-            import torch
-            self.t = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to("cuda")
-            self.ptr = C.c_void_p(self.t.data_ptr() + off)
-        else:
-            self.h = (C.c_uint8 * len(raw)).from_buffer_copy(raw)
-            self.ptr = C.c_void_p(C.addressof(self.h) + off)
-
-    def raw(self):
-        if self.device:
-            import torch
-            torch.cuda.synchronize()
-            return bytes(self.t.cpu().numpy())
-        return bytes(self.h)
-
-    def get(self, n=None):
-        return self.raw()[self.off:self.off + (self.size if n is None else n)]
-
-    def intact(self):
-        """nothing outside the `size` bytes was written"""
-        r = self.raw()
-        return set(r[:self.off]) | set(r[self.off + self.size:]) <= {GUARD}
+CHUNK = 16                                      # KW_CH: the steps kw.global's loads run ahead (uaes_kw.hip)
 
 
 def kbuf(kek):
@@ -146,6 +116,65 @@ def test_lds_boundary_at_every_offset(bits, unwrapping):
             assert unwrap(kek, w, False, 1, 2) == (0, s), (bits, size)
         else:
             assert wrap(kek, s, False, 1, 2) == (0, w), (bits, size)
+
+
+@pytest.mark.parametrize("unwrapping", [False, True])
+def test_global_chunk_edges(unwrapping):
+    """kw.global's loads run CHUNK steps ahead of the chain and its last chunk is short unless 6 n is a multiple of
+    CHUNK.  6 n is even, so the residues 1 and 15 do not exist: the eight n above the boundary give every residue that
+    does (0, 2, .. 14; 0, 2 and 14 are asserted to be among them); host and device memory in turn"""
+    n0 = lds_max() // 8 + 1
+    assert {0, 2, CHUNK - 2} <= {6 * n % CHUNK for n in range(n0, n0 + 8)}
+    rng = random.Random(16 + unwrapping)
+    for k, n in enumerate(range(n0, n0 + 8)):
+        bits = (128, 192, 256)[k % 3]
+        kek, s = rng.randbytes(bits // 8), rng.randbytes(8 * n)
+        assert uaes.kw_plan(8 * n, unwrap=unwrapping)[0] == "kw.global"
+        w = R.wrap(kek, s)[1]
+        if unwrapping:
+            assert unwrap(kek, w, device=k % 2 == 0) == (0, s), (bits, n)
+        else:
+            assert wrap(kek, s, device=k % 2 == 0) == (0, w), (bits, n)
+
+
+def unwrap_padded(kek, wrapped, device):
+    """uaes_kwp_unwrap: (code, the output buffer, *secretLen)"""
+    src, dst, ln = Mem(wrapped, device), Mem(b"", device, size=len(wrapped) - 8), C.c_size_t(77)
+    rc = uaes.engine().uaes_kwp_unwrap(len(kek) * 8, kbuf(kek), src.ptr, len(wrapped), dst.ptr, C.byref(ln))
+    assert dst.intact() and src.get() == wrapped
+    return rc, dst.get(), ln.value
+
+
+@pytest.mark.parametrize("wipe", [0, 1])
+def test_one_mode_does_not_unwrap_the_other(wipe):
+    """Both modes run the same two kernels and differ in a template argument: a key wrap does not unwrap as a key wrap
+    with padding, nor the padded wrap of a whole-semiblock secret as a key wrap -- 0x1A, and the output is what the chain
+    made (zeros under the wipe switch), as in test_forgeries_and_the_wipe_switch.  One secret in LDS, one in place, and
+    batches of five records of the shortest and the longest size"""
+    rng = random.Random(3394 + 5649)
+    eng = uaes.engine()
+    kek = rng.randbytes(24)
+    left = (lambda text: bytes(len(text))) if wipe else (lambda text: text)
+    eng.uaes_set_wipe_on_auth_failure(wipe)
+    try:
+        for size, name in ((16, "lds"), (lds_max() + 8, "global")):
+            assert uaes.kw_plan(size, unwrap=True)[0] == "kw." + name and uaes.kwp_plan(size, unwrap=True)[0] == "kwp." + name
+            s = rng.randbytes(size)
+            plain, padded = R.wrap(kek, s)[1], P.wrap(kek, s)
+            assert len(plain) == len(padded) == size + 8
+            as_padded, as_plain = P.unwrap(kek, plain), R.unwrap(kek, padded)
+            assert as_padded[0] == as_plain[0] == 0x1A
+            for device in (False, True):
+                assert unwrap_padded(kek, plain, device) == (0x1A, left(as_padded[1]), 0), (size, device)
+                assert unwrap(kek, padded, device) == (0x1A, left(as_plain[1])), (size, device)
+        for size in (16, batch_max()):
+            assert batch_max() == 256
+            secrets = [rng.randbytes(size) for _ in range(5)]
+            plain, padded = [R.wrap(kek, s)[1] for s in secrets], [P.wrap(kek, s) for s in secrets]
+            assert uaes.kwp_batch(kek, plain, unwrap=True) == (0x1A, [left(P.unwrap(kek, w)[1]) for w in plain], [0] * 5, [0] * 5), size
+            assert uaes.kw_batch(kek, padded, unwrap=True) == (0x1A, [left(R.unwrap(kek, w)[1]) for w in padded], [0] * 5), size
+    finally:
+        eng.uaes_set_wipe_on_auth_failure(0)
 
 
 @pytest.mark.parametrize("bits", [128, 192, 256])

@@ -50,6 +50,34 @@ def test_host_path_call_leaves_no_schedule(host_forced, case, n):
     assert ran
 
 
+# ---- key wrap with padding by name: its calls came into the lists last, from a module of their own that is gone, and
+# these say so in the ids whatever position the lists give them
+KWP_TEXT = next(c for c in TEXT_CASES if next(c(16, HostMem))[0] == "uaes_kwp_wrap")
+
+
+def test_the_lists_hold_the_kwp_calls():
+    names = {n for n in keyed_exports() if n.startswith("uaes_kwp_")}
+    assert len(names) == 4 and names <= set(ARG_CASES)
+    assert {name for name, _, _ in KWP_TEXT(17, HostMem)} == {n for n in names if not n.endswith("_batch")}
+
+
+@pytest.mark.parametrize("name", ["uaes_kwp_unwrap", "uaes_kwp_unwrap_batch", "uaes_kwp_wrap", "uaes_kwp_wrap_batch"])
+def test_kwp_argument_error_leaves_no_schedule(name):
+    args, want = ARG_CASES[name]
+    assert want == (1 if name in ("uaes_kwp_wrap", "uaes_kwp_unwrap") else -2)      # a length; a NULL array
+    checked(name, args, want)
+
+
+@pytest.mark.parametrize("n", [16, 17])
+def test_kwp_host_path_wraps_unwraps_and_refuses_a_forgery(host_forced, n):
+    """16 bytes: whole semiblocks; 17: seven fill bytes"""
+    ran = []
+    for name, args, want in KWP_TEXT(n, HostMem):
+        checked(name, args, want)
+        ran.append((name, want))
+    assert ran == [("uaes_kwp_wrap", 0), ("uaes_kwp_unwrap", 0), ("uaes_kwp_unwrap", 0x1A)]
+
+
 def test_host_cases_reach_every_export_with_a_host_path(host_forced):
     reached = set()
     for case in TEXT_CASES:
