@@ -250,6 +250,47 @@ int uaes_gcm_multikey_decrypt_batch(int keybits, const uint8_t *keys, size_t tag
                                     size_t nmsg, size_t msg_bytes, const uint32_t *lens,
                                     const uint8_t *nonces, const void *aData, size_t aad_bytes,
                                     const void *crtxt, const uint8_t *tags, void *pntxt, uint8_t *verdicts);
+/* XAES-256-GCM, the C2SP specification c2sp.org/XAES-256-GCM: AES-256-GCM with a 192-bit nonce.  RANDOM 24-BYTE NONCES
+ * ARE THE POINT: GCM's 96-bit nonce makes a caller with random nonces stop at about 2^32 messages per key, and many
+ * senders -- the workload the batches were built for -- cannot share a nonce counter.  Here the first half of the nonce
+ * makes a fresh AES-256 key, Kx = CMAC_K(00 01 58 00 || N[0:12]) || CMAC_K(00 02 58 00 || N[0:12]) (SP 800-108, counter
+ * mode), and plain AES-256-GCM runs under Kx with N[12:24] as its nonce.  The bound on messages per key is therefore
+ * the specification's (2^80 messages of random nonces for a collision risk of 2^-32), not GCM's.  The key is always 32
+ * bytes, the nonce 24, the tag 16: the specification has nothing else, so nothing else is offered (no *_dev variants,
+ * no key contexts -- the working key belongs to the nonce -- and the reference has no such call to be compatible with).
+ *   uaes_xaes256gcm_derive   kx <- Kx; three blocks of the host cipher, no device is touched.
+ *   uaes_xaes256gcm_encrypt / _decrypt   arguments, return codes, host or device pointers and what a failed
+ *       authentication leaves behind as uaes_gcm_encrypt / uaes_gcm_decrypt: crtxt receives ptextLen + 16 bytes, crtxt of
+ *       a decryption holds crtxtLen + 16.  Kx is derived on the host and the call then IS the one-call GCM path under it:
+ *       the fused kernels for a long text, the host data path for a short one where uaes_set_host_policy switched it on.
+ *       Kx, K1 and both schedules are wiped on every way out.  UAES_E_ARG for a NULL key or nonce, before any device is
+ *       touched.
+ *   uaes_xaes256gcm_encrypt_batch / _decrypt_batch   nmsg records under one master key in ONE launch, sixteen GPU
+ *       lanes per record (csrc/uaes_xaes.hip): every record derives Kx, expands it and runs GCM under it in the kernel,
+ *       where Kx lives in LDS and registers only.  Array layout, lens, placement (every array host or device memory at
+ *       any byte offset; lens 4-byte aligned device memory, or host memory) and return codes as uaes_gcmsiv_*_batch, with
+ *       nonces = nmsg * 24 bytes and tags = nmsg * 16.  Decrypt as uaes_gcm_multikey_decrypt_batch: a record is hashed
+ *       first and written only if its tag matches, so a forged record's output slot is UNTOUCHED whatever
+ *       uaes_set_wipe_on_auth_failure says; verdicts[m] = 1 / 0 (verdicts may be NULL: the return code still
+ *       tells); the call returns UAES_E_AUTHENTICATION if any record was forged.  UAES_E_ARG (before the device is
+ *       touched): msg_bytes or aad_bytes > 65535 (UAES_XAES_GCM_BATCH_MAX, csrc/uaes_plan.h: the multi-key bound, for the
+ *       same reason), a size product that overflows, a needed pointer that is NULL.  nmsg == 0 returns 0.  Always on the
+ *       GPU: the host policy does not apply.  Every record is bit for bit what uaes_xaes256gcm_encrypt / _decrypt give
+ *       for it.  Measured on an MI355X (tools/gcm_multikey_rate.py --xaes -> profiles/xaes_gcm_batch_rate.md; device-
+ *       resident arrays, 12 bytes of AAD; synchronous calls), encrypt / decrypt: 2^20 records of 16 B 1.80 / 1.53, of 64 B
+ *       1.29 / 1.13, of 1024 B 0.176 / 0.187 G records per second: 1.14 .. 1.01x the time of
+ *       uaes_gcm_multikey_encrypt_batch / _decrypt_batch at AES-256 on the same texts (one more two-block step a record). */
+int uaes_xaes256gcm_derive(const uint8_t key[32], const uint8_t nonce[24], uint8_t kx[32]);
+int uaes_xaes256gcm_encrypt(const uint8_t key[32], const uint8_t nonce[24], const void *aData, size_t aDataLen,
+                            const void *pntxt, size_t ptextLen, void *crtxt);
+int uaes_xaes256gcm_decrypt(const uint8_t key[32], const uint8_t nonce[24], const void *aData, size_t aDataLen,
+                            const void *crtxt, size_t crtxtLen, void *pntxt);
+int uaes_xaes256gcm_encrypt_batch(const uint8_t key[32], size_t nmsg, size_t msg_bytes, const uint32_t *lens,
+                                  const uint8_t *nonces, const void *aData, size_t aad_bytes,
+                                  const void *pntxt, void *crtxt, uint8_t *tags);
+int uaes_xaes256gcm_decrypt_batch(const uint8_t key[32], size_t nmsg, size_t msg_bytes, const uint32_t *lens,
+                                  const uint8_t *nonces, const void *aData, size_t aad_bytes,
+                                  const void *crtxt, const uint8_t *tags, void *pntxt, uint8_t *verdicts);
 /* GHASH_H(aData, crtxt) of micro_aes.c:1127-1137 with an explicit H (test
  * hook for the carry-less-multiply kernels); gh receives 16 bytes.           */
 int uaes_ghash(const uint8_t H[16], const void *aData, size_t aDataLen,
@@ -1007,6 +1048,11 @@ const char *uaes_debug_plan_gcmsiv_batch(int dir, size_t len, size_t nmsg, int o
  * threads as "ccm.batch" for the same number of records), or NULL for a dir other than 0 / 1 or a length above
  * UAES_GCM_MULTIKEY_BATCH_MAX.  Works without a device (a 256-CU MI355X). */
 const char *uaes_debug_plan_gcm_multikey_batch(int dir, size_t len, size_t nmsg, int out[3]);
+/* The planner of the XAES-256-GCM batches (csrc/uaes_plan.h): dir 0 encrypt / 1 decrypt; len = bytes per record, nmsg =
+ * records; `out` as for FF1.  Returns "xaes.gcm" (the one arrangement: sixteen lanes per record, the same grid and
+ * threads as "gcmsiv.batch" for the same number of records), or NULL for a dir other than 0 / 1 or a length above
+ * UAES_XAES_GCM_BATCH_MAX.  Works without a device (a 256-CU MI355X). */
+const char *uaes_debug_plan_xaes256gcm_batch(int dir, size_t len, size_t nmsg, int out[3]);
 /* The launch shape of OCB (csrc/uaes_plan.h, uaesk_plan_ocb_shape): dir 0 encrypt / 1 decrypt; len / aad_len = bytes of
  * text / of associated data; aad_aligned = whether the associated data starts at a multiple of 16 bytes in device
  * memory.  Returns "ocb.small" (one workgroup; out untouched) or "ocb.runs", for which out (may be NULL) receives

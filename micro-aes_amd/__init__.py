@@ -46,6 +46,8 @@ EXPORTS = [
     "uaes_cmac", "uaes_ccm_encrypt", "uaes_ccm_decrypt", "uaes_gcmsiv_encrypt", "uaes_gcmsiv_decrypt",
     "uaes_gcmsiv_encrypt_batch", "uaes_gcmsiv_decrypt_batch", "uaes_debug_plan_gcmsiv_batch",
     "uaes_gcm_multikey_encrypt_batch", "uaes_gcm_multikey_decrypt_batch", "uaes_debug_plan_gcm_multikey_batch",
+    "uaes_xaes256gcm_derive", "uaes_xaes256gcm_encrypt", "uaes_xaes256gcm_decrypt",
+    "uaes_xaes256gcm_encrypt_batch", "uaes_xaes256gcm_decrypt_batch", "uaes_debug_plan_xaes256gcm_batch",
     "uaes_ocb_encrypt", "uaes_ocb_decrypt", "uaes_ocb_dev", "uaes_debug_plan_ocb", "uaes_debug_plan_xts",
     "uaes_debug_plan_gcm_piece", "uaes_debug_gcm_stream_tables",
     "uaes_poly1305", "uaes_poly1305_dev", "uaes_poly1305_batch", "uaes_debug_plan_poly1305",
@@ -185,6 +187,13 @@ def engine():
     L.uaes_gcm_multikey_decrypt_batch.argtypes = [i, vp, sz, sz, sz, vp, vp, vp, sz, vp, vp, vp, vp]
     L.uaes_debug_plan_gcm_multikey_batch.argtypes = [i, sz, sz, C.POINTER(C.c_int)]
     L.uaes_debug_plan_gcm_multikey_batch.restype = C.c_char_p
+    L.uaes_xaes256gcm_derive.argtypes = [vp, vp, vp]
+    L.uaes_xaes256gcm_encrypt.argtypes = [vp, vp, vp, sz, vp, sz, vp]
+    L.uaes_xaes256gcm_decrypt.argtypes = [vp, vp, vp, sz, vp, sz, vp]
+    L.uaes_xaes256gcm_encrypt_batch.argtypes = [vp, sz, sz, vp, vp, vp, sz, vp, vp, vp]
+    L.uaes_xaes256gcm_decrypt_batch.argtypes = [vp, sz, sz, vp, vp, vp, sz, vp, vp, vp, vp]
+    L.uaes_debug_plan_xaes256gcm_batch.argtypes = [i, sz, sz, C.POINTER(C.c_int)]
+    L.uaes_debug_plan_xaes256gcm_batch.restype = C.c_char_p
     L.uaes_siv_encrypt_batch.argtypes = [i, vp, sz, sz, vp, sz, vp, vp, vp]
     L.uaes_siv_decrypt_batch.argtypes = [i, vp, sz, sz, vp, sz, vp, vp, vp, vp]
     L.uaes_debug_plan_eax_siv.argtypes = [i, i, sz, sz, C.POINTER(C.c_int)]
@@ -295,7 +304,8 @@ def engine():
                      "uaes_debug_arrangement_name", "uaes_debug_plan_disable", "uaes_debug_plan_poly1305",
                      "uaes_debug_plan_eax_siv", "uaes_debug_plan_chain", "uaes_debug_plan_kw", "uaes_debug_plan_kwp", "uaes_debug_plan_ff1",
                      "uaes_debug_plan_ff3", "uaes_ff3_maxlen", "uaes_debug_plan_gcmsiv_batch", "uaes_debug_plan_ocb", "uaes_debug_plan_xts",
-                     "uaes_debug_gcm_stream_tables", "uaes_debug_plan_ocb_batch", "uaes_debug_plan_gcm_multikey_batch", "uaes_debug_plan_cipher_batch"):
+                     "uaes_debug_gcm_stream_tables", "uaes_debug_plan_ocb_batch", "uaes_debug_plan_gcm_multikey_batch", "uaes_debug_plan_cipher_batch",
+                     "uaes_debug_plan_xaes256gcm_batch"):
             getattr(L, n).restype = i
     _lib = L
     return L
@@ -783,6 +793,52 @@ def gcm_multikey_batch_plan(length, nmsg, decrypt=False):
     """What a multi-key GCM batch of nmsg records of `length` bytes would run (uaes_debug_plan_gcm_multikey_batch):
     (arrangement, launches, workgroups, threads per workgroup), or None for arguments that make no sense."""
     return _batch_plan("uaes_debug_plan_gcm_multikey_batch", int(bool(decrypt)), length, nmsg)
+
+
+def xaes256gcm_derive(key, nonce):
+    """The AES-256 key XAES-256-GCM (C2SP) runs GCM under for this 32-byte key and 24-byte nonce: CMAC_K(00 01 58 00 ||
+    nonce[:12]) || CMAC_K(00 02 58 00 || nonce[:12]) (uaes_xaes256gcm_derive; the host cipher, no device)."""
+    o = _out(32)
+    _check(engine().uaes_xaes256gcm_derive(_fixed(key, 32, "key"), _fixed(nonce, 24, "nonce"), o), "xaes256gcm_derive")
+    return bytes(o)
+
+
+def xaes256gcm_encrypt(key, nonce, aad, pt):
+    """XAES-256-GCM (c2sp.org/XAES-256-GCM): a 32-byte key, a 24-byte nonce; returns ciphertext || 16-byte tag."""
+    o = _out(len(pt) + 16)
+    _check(engine().uaes_xaes256gcm_encrypt(_fixed(key, 32, "key"), _fixed(nonce, 24, "nonce"), _in(aad), len(aad),
+                                            _in(pt), len(pt), o), "xaes256gcm_encrypt")
+    return bytes(o)[: len(pt) + 16]
+
+
+def xaes256gcm_decrypt(key, nonce, aad, ct_and_tag, prefill=0):
+    """Returns (code, text); the tag is checked first, so on 0x1A the text is the untouched prefill."""
+    n = len(ct_and_tag) - 16
+    if n < 0:
+        raise ValueError("shorter than the tag")
+    o = _out(n, prefill)
+    rc = _check(engine().uaes_xaes256gcm_decrypt(_fixed(key, 32, "key"), _fixed(nonce, 24, "nonce"), _in(aad), len(aad),
+                                                 _in(ct_and_tag), n, o), "xaes256gcm_decrypt")
+    return rc, bytes(o)[:n]
+
+
+def xaes256gcm_batch(key, nonces, aads, texts, decrypt=False, tags=None, prefill=0, lens=None):
+    """XAES-256-GCM of many records under one 32-byte master key (uaes_xaes256gcm_*_batch): 24-byte nonces, equal-sized
+    AADs (or None) and texts; every record derives the key of its nonce in the kernel.  encrypt: returns (ciphertexts,
+    16-byte tags); decrypt (tags given): returns (code, plaintexts, verdicts); a forged record's output slot is
+    untouched: it stays the prefill, whatever wipe_on_auth_failure says.  lens (optional, one per record): record m is the
+    first lens[m] bytes of its text, and the rest of its output slot stays the prefill."""
+    def head(n, ml, lv):
+        if any(len(x) != 24 for x in nonces) or (decrypt and any(len(x) != 16 for x in tags)):
+            raise ValueError("nonces of 24 bytes (tags of 16)")
+        return _fixed(key, 32, "key"), n, ml, lv, _in(b"".join(nonces))
+    return _aead_batch("xaes256gcm", "nonce, AAD (tag and length)", [nonces], aads, texts, lens, decrypt, tags, 16, prefill, head)
+
+
+def xaes256gcm_batch_plan(length, nmsg, decrypt=False):
+    """What an XAES-256-GCM batch of nmsg records of `length` bytes would run (uaes_debug_plan_xaes256gcm_batch):
+    (arrangement, launches, workgroups, threads per workgroup), or None for arguments that make no sense."""
+    return _batch_plan("uaes_debug_plan_xaes256gcm_batch", int(bool(decrypt)), length, nmsg)
 
 
 def ocb_batch(key, nonces, aads, texts, tag_len=16, decrypt=False, tags=None, prefill=0, lens=None):

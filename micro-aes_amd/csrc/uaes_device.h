@@ -179,6 +179,22 @@ int uaesk_gcm_multikey_batch(void *stream, const uaesk_tables *tb, int nr, int d
                              size_t nmsg, size_t msg_bytes, const void *lens, const void *in, void *out,
                              void *tags, void *verdicts, int *bad);
 
+/* one block as little-endian column words, by value into a kernel's arguments */
+typedef struct {
+    uint32_t w[4];
+} uaesk_block;
+
+/* Batch: nmsg XAES-256-GCM records (C2SP) under one MASTER AES-256 key, sixteen lanes per record (k_xaes_gcm_batch,
+ * uaes_xaes.hip); all device pointers.  k1 = CMAC's first subkey under the master key (2 AES_K(0) in GF(2^128)).  Record
+ * m: text at in / out + m msg_bytes (msg_bytes <= UAES_XAES_GCM_BATCH_MAX), its first lens[m] bytes (lens NULL:
+ * msg_bytes), nonce at nonces + 24 m (any byte offset), AAD at aad + m aad_bytes (<= UAES_XAES_GCM_BATCH_MAX), tag at
+ * tags + 16 m.  The per-nonce key is derived and expanded in the kernel, into LDS.  decrypt writes verdicts[m] (1 =
+ * authentic; verdicts may be NULL) and ORs 1 into *bad for a forgery, whose output is not written at all. */
+int uaesk_xaes_gcm_batch(void *stream, const uaesk_tables *tb, const uaesk_rk *master_ek, const uaesk_block *k1,
+                         int decrypt, const void *nonces, const void *aad, size_t aad_bytes, size_t nmsg,
+                         size_t msg_bytes, const void *lens, const void *in, void *out, void *tags, void *verdicts,
+                         int *bad);
+
 /* GHASH only: gh = GHASH_H(aad, ct) with H given (device), for tests.      */
 int uaesk_ghash(void *stream, const uaesk_tables *tb, const uint8_t *H_host,
                 const void *aad, size_t aad_len, const void *ct, size_t ct_len,

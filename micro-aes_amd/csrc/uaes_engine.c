@@ -1516,6 +1516,10 @@ const char *uaes_debug_plan_gcm_multikey_batch(int dir, size_t len, size_t nmsg,
 {
     return debug_plan_rows(uaesk_plan_gcm_multikey_batch, uaesk_gcm_multikey_arrangement_name, dir, len, nmsg, out);
 }
+const char *uaes_debug_plan_xaes256gcm_batch(int dir, size_t len, size_t nmsg, int out[3])
+{
+    return debug_plan_rows(uaesk_plan_xaes_gcm_batch, uaesk_xaes_gcm_arrangement_name, dir, len, nmsg, out);
+}
 const char *uaes_debug_plan_ocb_batch(int dir, size_t len, size_t nmsg, int out[3])
 {
     return debug_plan_rows(uaesk_plan_ocb_batch, uaesk_ocb_batch_arrangement_name, dir, len, nmsg, out);

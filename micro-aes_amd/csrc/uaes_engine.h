@@ -239,6 +239,7 @@ int tag_load(uint8_t tag[16], const void *src);
 int gcm_shard_sync(int keybits, const uint8_t *key, const uint8_t *nonce, int mode,
                    const void *aData, uint64_t aDataLen, const void *in, size_t len, uint64_t off,
                    uint64_t total, void *out, uint8_t share[16]);
+void xaes_k1(const keysched *mk, uint8_t k1[16]);
 
 /* ---- uaes_engine_mgpu.c ---- */
 void gather_teardown(void);

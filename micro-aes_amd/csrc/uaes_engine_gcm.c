@@ -209,48 +209,58 @@ static int gcm_args_ok(const uint8_t *nonce, size_t nonceLen, size_t tagLen, con
     return 0;
 }
 
-/* The lane's scratch made ready for a one-shot call under `key`: whether it holds the key's tables, and the call's J0. */
-static int gcm_lane_prepare(lane *L, keysched *ks, const uint8_t *key, int keybits, const uint8_t *nonce, size_t nonceLen,
-                            int *keyed, uint8_t j0[16])
+/* The lane's scratch made ready for a one-shot call under `key`: whether it holds the key's tables, and the call's J0.
+ * cache == 0: a key that no later call repeats (XAES-256-GCM: it belongs to the nonce), so the lane does not remember it. */
+static int gcm_lane_prepare(lane *L, keysched *ks, const uint8_t *key, int keybits, int cache, const uint8_t *nonce,
+                            size_t nonceLen, int *keyed, uint8_t j0[16])
 {
     int rc;
     if ((rc = gcm_scratch(L, SCRATCH_GCM_KEYED)) != 0) return rc;
     /* (before anything of this call writes the scratch under its key.  A one-shot setup builds only the tables its
      * message reaches and leaves the others undefined: with a nonce whose J0 is a GHASH of its own, which runs such
      * a setup, the call stays one-shot and the cache starts over) */
-    *keyed = nonceLen == 12 ? lane_gcm_keyed(L, ks, key, keybits) : 0;
+    *keyed = cache && nonceLen == 12 ? lane_gcm_keyed(L, ks, key, keybits) : 0;
     if (*keyed < 0) return *keyed;
-    if (nonceLen != 12) lane_scratch_clobbered(L);
+    if (!cache || nonceLen != 12) lane_scratch_clobbered(L);
     return gcm_j0(L, ks, nonce, nonceLen, j0);
 }
 
-int uaes_gcm_encrypt_ex(int keybits, const uint8_t *key, const uint8_t *nonce, size_t nonceLen, size_t tagLen,
-                        const void *aData, size_t aDataLen,
-                        const void *pntxt, size_t ptextLen, void *crtxt)
+/* One GCM encryption under the expanded `key`, whichever front door it came through: uaes_gcm_encrypt_ex, and
+ * uaes_xaes256gcm_encrypt with the key of its nonce (cache == 0, gcm_lane_prepare). */
+static int gcm_encrypt_call(keysched *ks, const uint8_t *key, int keybits, int cache, const uint8_t *nonce, size_t nonceLen,
+                            size_t tagLen, const void *aData, size_t aDataLen, const void *pntxt, size_t ptextLen, void *crtxt)
 {
     context *c;
     lane *L;
-    KEYSCHED(ks);
     uint8_t j0[16];
     int rc, keyed;
-    if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
     if ((rc = gcm_args_ok(nonce, nonceLen, tagLen, aData, aDataLen, crtxt, pntxt, ptextLen)) != 0) return rc;
     if (host_take_mode(pntxt, crtxt, ptextLen, 0, 1) && !is_device_ptr(aData)) {
-        const uaesh_key hk = host_key(&ks);
+        const uaesh_key hk = host_key(ks);
         return host_result(uaesh_gcm(&hk, 0, nonce, nonceLen, tagLen, (const uint8_t *)aData, aDataLen, (const uint8_t *)pntxt, ptextLen, (uint8_t *)crtxt));
     }
     if (nonceLen == 12 && tagLen == 16) {
         int devs[MAX_DEVICES];
         const int nd = auto_devices(pntxt, crtxt, ptextLen, devs);
         if (nd) return uaes_mgpu_gcm_encrypt(nd, devs, keybits, key, nonce, aData, aDataLen, pntxt, ptextLen, crtxt);
-        if (gcm_encrypt_pipelined(&ks, nonce, aData, aDataLen, pntxt, ptextLen, crtxt, &rc)) return rc;
+        if (gcm_encrypt_pipelined(ks, nonce, aData, aDataLen, pntxt, ptextLen, crtxt, &rc)) return rc;
     }
     if ((rc = enter(&c, &L)) != 0) return rc;
-    if ((rc = gcm_lane_prepare(L, &ks, key, keybits, nonce, nonceLen, &keyed, j0)) == 0) {
-        const gcm_how how = { &ks, keyed, L->scratch, scratch_done_word(L->scratch, L->scratch_cap) };
+    if ((rc = gcm_lane_prepare(L, ks, key, keybits, cache, nonce, nonceLen, &keyed, j0)) == 0) {
+        const gcm_how how = { ks, keyed, L->scratch, scratch_done_word(L->scratch, L->scratch_cap) };
         rc = gcm_encrypt_on_lane(c, L, &how, j0, tagLen, aData, aDataLen, pntxt, ptextLen, crtxt);
     }
     DONE(L, rc);
+}
+
+int uaes_gcm_encrypt_ex(int keybits, const uint8_t *key, const uint8_t *nonce, size_t nonceLen, size_t tagLen,
+                        const void *aData, size_t aDataLen,
+                        const void *pntxt, size_t ptextLen, void *crtxt)
+{
+    KEYSCHED(ks);
+    int rc;
+    if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
+    return gcm_encrypt_call(&ks, key, keybits, 1, nonce, nonceLen, tagLen, aData, aDataLen, pntxt, ptextLen, crtxt);
 }
 
 int uaes_gcm_encrypt_iv(int keybits, const uint8_t *key, const uint8_t *nonce, size_t nonceLen,
@@ -267,19 +277,17 @@ int uaes_gcm_encrypt(int keybits, const uint8_t *key, const uint8_t *nonce,
     return uaes_gcm_encrypt_iv(keybits, key, nonce, 12, aData, aDataLen, pntxt, ptextLen, crtxt);
 }
 
-int uaes_gcm_decrypt_ex(int keybits, const uint8_t *key, const uint8_t *nonce, size_t nonceLen, size_t tagLen,
-                        const void *aData, size_t aDataLen,
-                        const void *crtxt, size_t crtxtLen, void *pntxt)
+/* ... and one GCM decryption: uaes_gcm_decrypt_ex and uaes_xaes256gcm_decrypt */
+static int gcm_decrypt_call(keysched *ks, const uint8_t *key, int keybits, int cache, const uint8_t *nonce, size_t nonceLen,
+                            size_t tagLen, const void *aData, size_t aDataLen, const void *crtxt, size_t crtxtLen, void *pntxt)
 {
     context *c;
     lane *L;
-    KEYSCHED(ks);
     uint8_t j0[16];
     int rc, keyed;
-    if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
     if ((rc = gcm_args_ok(nonce, nonceLen, tagLen, aData, aDataLen, crtxt, pntxt, crtxtLen)) != 0) return rc;
     if (host_take_mode(crtxt, pntxt, crtxtLen, 0, 1) && !is_device_ptr(aData)) {
-        const uaesh_key hk = host_key(&ks);
+        const uaesh_key hk = host_key(ks);
         return host_result(uaesh_gcm(&hk, 1, nonce, nonceLen, tagLen, (const uint8_t *)aData, aDataLen, (const uint8_t *)crtxt, crtxtLen, (uint8_t *)pntxt));
     }
     if (nonceLen == 12 && tagLen == 16) {
@@ -288,11 +296,21 @@ int uaes_gcm_decrypt_ex(int keybits, const uint8_t *key, const uint8_t *nonce, s
         if (nd) return uaes_mgpu_gcm_decrypt(nd, devs, keybits, key, nonce, aData, aDataLen, crtxt, crtxtLen, pntxt);
     }
     if ((rc = enter(&c, &L)) != 0) return rc;
-    if ((rc = gcm_lane_prepare(L, &ks, key, keybits, nonce, nonceLen, &keyed, j0)) == 0) {
-        const gcm_how how = { &ks, keyed, L->scratch, scratch_done_word(L->scratch, L->scratch_cap) };
+    if ((rc = gcm_lane_prepare(L, ks, key, keybits, cache, nonce, nonceLen, &keyed, j0)) == 0) {
+        const gcm_how how = { ks, keyed, L->scratch, scratch_done_word(L->scratch, L->scratch_cap) };
         rc = gcm_decrypt_on_lane(c, L, &how, j0, tagLen, aData, aDataLen, crtxt, crtxtLen, pntxt);
     }
     DONE(L, rc);
+}
+
+int uaes_gcm_decrypt_ex(int keybits, const uint8_t *key, const uint8_t *nonce, size_t nonceLen, size_t tagLen,
+                        const void *aData, size_t aDataLen,
+                        const void *crtxt, size_t crtxtLen, void *pntxt)
+{
+    KEYSCHED(ks);
+    int rc;
+    if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
+    return gcm_decrypt_call(&ks, key, keybits, 1, nonce, nonceLen, tagLen, aData, aDataLen, crtxt, crtxtLen, pntxt);
 }
 
 int uaes_gcm_decrypt_iv(int keybits, const uint8_t *key, const uint8_t *nonce, size_t nonceLen,
@@ -307,6 +325,77 @@ int uaes_gcm_decrypt(int keybits, const uint8_t *key, const uint8_t *nonce,
                      const void *crtxt, size_t crtxtLen, void *pntxt)
 {
     return uaes_gcm_decrypt_iv(keybits, key, nonce, 12, aData, aDataLen, crtxt, crtxtLen, pntxt);
+}
+
+/* ------------------------------------------------------------------------ */
+/* XAES-256-GCM (C2SP): AES-256-GCM under a key made of half a 24-byte nonce   */
+/* ------------------------------------------------------------------------ */
+/* CMAC's first subkey under the master key: K1 = 2 AES_K(0^128) in GF(2^128), big-endian, x^128 = x^7 + x^2 + x + 1.
+ * Per call, and secret: the caller burns it (the batches hand it to their kernel, uaes_engine_modes.c). */
+void xaes_k1(const keysched *mk, uint8_t k1[16])
+{
+    static const uint8_t zero[16];
+    uint8_t l[16];
+    int i;
+    uaesh_encrypt(mk->ek.w, mk->nr, zero, l);
+    for (i = 0; i < 16; ++i) k1[i] = (uint8_t)((l[i] << 1) | (i < 15 ? l[i + 1] >> 7 : 0));
+    k1[15] ^= (uint8_t)(0x87 & -(l[0] >> 7));
+    burn(l, sizeof l);
+}
+
+/* Kx = CMAC_K(00 01 58 00 || N[0:12]) || CMAC_K(00 02 58 00 || N[0:12]): each message is one whole block, so each MAC
+ * is one block of the cipher over message ^ K1.  Three blocks of the host cipher in all; no device is touched. */
+static int xaes_derive(const uint8_t *key, const uint8_t *nonce, uint8_t kx[32])
+{
+    KEYSCHED(mk);
+    uint8_t k1[16], m[16];
+    int rc, i, half;
+    if (!key || !nonce) return fail(UAES_E_ARG, "NULL pointer");
+    if ((rc = expand_key(&mk, key, 256)) != 0) return rc;
+    xaes_k1(&mk, k1);
+    for (half = 0; half < 2; ++half) {
+        m[0] = 0; m[1] = (uint8_t)(half + 1); m[2] = 0x58; m[3] = 0;
+        memcpy(m + 4, nonce, 12);
+        for (i = 0; i < 16; ++i) m[i] ^= k1[i];
+        uaesh_encrypt(mk.ek.w, mk.nr, m, kx + 16 * half);
+    }
+    burn(k1, sizeof k1);
+    burn(m, sizeof m);
+    return 0;
+}
+
+int uaes_xaes256gcm_derive(const uint8_t key[32], const uint8_t nonce[24], uint8_t kx[32])
+{
+    if (!kx) return fail(UAES_E_ARG, "NULL pointer");
+    return xaes_derive(key, nonce, kx);
+}
+
+/* The one-message calls: Kx on the host, then the one-call GCM path under it with the second half of the nonce -- the
+ * fused kernels for a long text, the host data path for a short one where it is switched on, exactly as GCM.  The lane
+ * does not remember Kx (cache 0): no later call repeats it. */
+static int xaes_call(int decrypt, const uint8_t *key, const uint8_t *nonce, const void *aData, size_t aDataLen,
+                     const void *in, size_t len, void *out)
+{
+    KEYSCHED(ks);
+    uint8_t kx[32];
+    int rc;
+    if ((rc = xaes_derive(key, nonce, kx)) == 0 && (rc = expand_key(&ks, kx, 256)) == 0)
+        rc = decrypt ? gcm_decrypt_call(&ks, kx, 256, 0, nonce + 12, 12, 16, aData, aDataLen, in, len, out)
+                     : gcm_encrypt_call(&ks, kx, 256, 0, nonce + 12, 12, 16, aData, aDataLen, in, len, out);
+    burn(kx, sizeof kx);
+    return rc;
+}
+
+int uaes_xaes256gcm_encrypt(const uint8_t key[32], const uint8_t nonce[24], const void *aData, size_t aDataLen,
+                            const void *pntxt, size_t ptextLen, void *crtxt)
+{
+    return xaes_call(0, key, nonce, aData, aDataLen, pntxt, ptextLen, crtxt);
+}
+
+int uaes_xaes256gcm_decrypt(const uint8_t key[32], const uint8_t nonce[24], const void *aData, size_t aDataLen,
+                            const void *crtxt, size_t crtxtLen, void *pntxt)
+{
+    return xaes_call(1, key, nonce, aData, aDataLen, crtxt, crtxtLen, pntxt);
 }
 
 /* The *_dev calls: one uaesk_gcm under a 12-byte nonce on the caller's stream, nothing waited for.  slot >= 0: `how`'s

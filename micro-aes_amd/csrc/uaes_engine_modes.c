@@ -694,7 +694,7 @@ int uaes_siv_decrypt(int keybits, const uint8_t *keys, const uint8_t iv[16], con
     return siv_common(keybits, keys, 1, (uint8_t *)iv, aData, aDataLen, crtxt, crtxtLen, pntxt);
 }
 
-/* ---- AEAD record batches: EAX, SIV, CCM, GCM-SIV, multi-key GCM and OCB ----
+/* ---- AEAD record batches: EAX, SIV, CCM, GCM-SIV, multi-key GCM, XAES-256-GCM and OCB ----
  * nmsg records of msg_bytes each in one launch, sixteen lanes per record.  Every array may be host or device memory;
  * host arrays travel through the lane's staging buffers and scratch.  A mode checks its own limits, describes the call
  * in an aead_rows and hands it to aead_rows_run, which does everything the modes share, in this order: the sizes, the
@@ -950,6 +950,55 @@ int uaes_gcm_multikey_decrypt_batch(int keybits, const uint8_t *keys, size_t tag
 {
     return gcm_multikey_batch(1, keybits, keys, tagLen, nmsg, msg_bytes, lens, nonces, aData, aad_bytes, crtxt, pntxt,
                               (uint8_t *)tags, verdicts);
+}
+
+/* XAES-256-GCM batches (C2SP; k_xaes_gcm_batch, uaes_xaes.hip): as gcmsiv_batch with 24-byte nonces -- `key` is the
+ * MASTER key, always 256 bits: only its schedule and CMAC's subkey K1 under it are made here, every record derives and
+ * expands the key of its nonce in the kernel -- and decrypting as gcm_multikey_batch: the kernel writes an authentic
+ * record only, so the output's staging starts as the caller's buffer and uaes_set_wipe_on_auth_failure does not apply. */
+static int xaes_batch_launch(const aead_rows *b, context *c, lane *L, const keysched *const ks[2], const row_array *a, const row_text *t)
+{
+    uint8_t k1[16];
+    uaesk_block kb;
+    int k;
+    xaes_k1(ks[0], k1);
+    memcpy(kb.w, k1, sizeof k1);                  /* little-endian words of the byte stream, as a schedule's */
+    k = uaesk_xaes_gcm_batch(L->stream, &c->tb, &ks[0]->ek, &kb, b->decrypt, a[AB_NONCES].d, a[AB_AAD].d, b->side[AB_AAD].each,
+                             b->nmsg, b->msg_bytes, a[AB_LENS].d, t->d_in, t->d_out, a[AB_TAGS].d, a[AB_VERDICTS].d, L->d_status);
+    burn(k1, sizeof k1);
+    burn(&kb, sizeof kb);
+    return k;
+}
+
+static int xaes_batch(int decrypt, const uint8_t *key, size_t nmsg, size_t msg_bytes, const uint32_t *lens,
+                      const uint8_t *nonces, const void *aData, size_t aad_bytes, const void *in, void *outp,
+                      uint8_t *tags, uint8_t *verdicts)
+{
+    const aead_rows b = {
+        .name = "xaes-256-gcm batch", .launch = xaes_batch_launch, .nkeys = 1, .keybits = 256, .key = key, .decrypt = decrypt,
+        .prefill = decrypt, .nmsg = nmsg, .msg_bytes = msg_bytes, .in = in, .out = outp,
+        .side = { [AB_NONCES] = { nonces, 24 }, [AB_AAD] = { aData, aad_bytes },
+                  [AB_LENS] = { lens, lens ? sizeof *lens : 0 }, [AB_TAGS] = { tags, 16 },
+                  [AB_VERDICTS] = { verdicts, decrypt && verdicts } } };      /* (a caller may do without verdicts) */
+    if (msg_bytes > UAES_XAES_GCM_BATCH_MAX)
+        return fail(UAES_E_ARG, "an XAES-256-GCM batch record holds at most %zu bytes (got %zu)", (size_t)UAES_XAES_GCM_BATCH_MAX, msg_bytes);
+    if (aad_bytes > UAES_XAES_GCM_BATCH_MAX)
+        return fail(UAES_E_ARG, "an XAES-256-GCM batch record takes at most %zu bytes of AAD (got %zu)", (size_t)UAES_XAES_GCM_BATCH_MAX, aad_bytes);
+    return aead_rows_run(&b);
+}
+
+int uaes_xaes256gcm_encrypt_batch(const uint8_t key[32], size_t nmsg, size_t msg_bytes, const uint32_t *lens,
+                                  const uint8_t *nonces, const void *aData, size_t aad_bytes,
+                                  const void *pntxt, void *crtxt, uint8_t *tags)
+{
+    return xaes_batch(0, key, nmsg, msg_bytes, lens, nonces, aData, aad_bytes, pntxt, crtxt, tags, NULL);
+}
+
+int uaes_xaes256gcm_decrypt_batch(const uint8_t key[32], size_t nmsg, size_t msg_bytes, const uint32_t *lens,
+                                  const uint8_t *nonces, const void *aData, size_t aad_bytes,
+                                  const void *crtxt, const uint8_t *tags, void *pntxt, uint8_t *verdicts)
+{
+    return xaes_batch(1, key, nmsg, msg_bytes, lens, nonces, aData, aad_bytes, crtxt, pntxt, (uint8_t *)tags, verdicts);
 }
 
 /* ------------------------------------------------------------------------ */

@@ -9,7 +9,8 @@
  * right behind the tables at 128 KiB.  Per record the row
  *   1. loads the key's NK words into every lane (any byte offset: words when the key is 4-byte aligned, bytes
  *      otherwise) and expands them into the record's own LDS slot (gsb_expand, uaes_perkey.hip.h); row4_lane<NR>(slot)
- *      is then the record's RowLane;
+ *      is then the record's RowLane.  From here on the record is gcm_row_record (uaes_gcm_row.hip.h), which
+ *      k_xaes_gcm_batch (uaes_xaes.hip) runs too, behind a key derivation:
  *   2. encrypts the zero block and J0 = nonce || 00000001 together (one row_encrypt2 step): H and the tag's mask EJ0;
  *   3. hashes.  GHASH_H(X_1 ..) = rev(POLYVAL_K(rev(X_1) ..)) with K = mulX(rev(H)) (RFC 8452 appendix A; k_siv_prep
  *      uses the relation in the other direction), so the hash is uaes_perkey.hip.h's POLYVAL in registers, pv_lane over
@@ -47,24 +48,15 @@
 #include <string.h>
 #include "uaes_aes.hip.h"
 #include "uaes_perkey.hip.h"
+#include "uaes_gcm_row.hip.h"
 #include "uaes_device.h"
 #include "uaes_plan.h"
 
 #define GMK_KEYS_AT   131072u                             /* the slots: where the other row batches keep the call's round keys */
 #define GMK_LDS(wg)   (GMK_KEYS_AT + ((wg) / 16u) * GSB_SLOT)
-#define GMK_CH_ENC    4u                                  /* row_walk's chunk where a step is a block of the cipher and one of the hash */
-#define GMK_CH_HASH   8u                                  /* decrypt's walk 1: a block of the hash */
-#define GMK_CH_CTR    8u                                  /* decrypt's walk 2: a block of the cipher */
 
 static_assert(GMK_KEYS_AT % 16u == 0 && GMK_LDS(UAES_WG) <= 160u * 1024u, "64 schedules fit behind the row4 tables, 16-byte aligned");
 static_assert(UAES_GCM_MULTIKEY_BATCH_MAX <= 0x1fffffffu, "8 len fits the 32-bit word the length block is built from");
-
-/* the byte-reversed block: this lane's column word of it, from the column words the row holds (lane 15 - i is a lane
- * of column 3 - c) */
-__device__ __forceinline__ u32 gmk_rev(u32 w)
-{
-    return __builtin_amdgcn_perm(0u, row_dpp<0x140>(w), 0x00010203u);       /* row_mirror, then the four bytes swapped */
-}
 
 /* the NK little-endian words of the key at kp, in every lane */
 template <u32 NK>
@@ -78,12 +70,6 @@ __device__ __forceinline__ void gmk_load_key(u32 (&key)[NK], const unsigned char
         for (u32 i = 0; i < NK; ++i)
             key[i] = (u32)kp[4u * i] | ((u32)kp[4u * i + 1u] << 8) | ((u32)kp[4u * i + 2u] << 16) | ((u32)kp[4u * i + 3u] << 24);
     }
-}
-
-/* this lane's column of the counter block of text block i: J0 + 1 + i (nw = the nonce's word of columns 0..2) */
-__device__ __forceinline__ u32 gmk_ctr(u32 nw, u32 i, u32 c)
-{
-    return c == 3u ? __builtin_bswap32(i + 2u) : nw;
 }
 
 /* Record m: key at keys + 4 NK m, text at in / out + m msg_bytes (its first lens[m] <= msg_bytes bytes; lens == NULL:
@@ -121,57 +107,7 @@ __global__ __launch_bounds__(UAES_WG) void k_gcm_multikey(uaesk_tables tb, u32 t
             gsb_expand<NR>(key, slot, li, tlast, sel, lsel);
         }
         GSB_PHASE();
-        const RowLane<NR> R = row4_lane<NR>(slot);               /* the record's own key */
-        u32 nw = 0;                                              /* the nonce's word of this column; column 3 has none */
-#pragma unroll
-        for (u32 k = 0; k < 4; ++k)
-            if (c < 3u) nw |= (u32)np[4u * c + k] << (8u * k);
-        u32 ej0 = c == 3u ? 0x01000000u : nw;                    /* J0 = nonce || 00000001 */
-        PvLane V;
-        {
-            u32 h = 0, hr[4], hk[4];
-            row_encrypt2<NR>(h, ej0, R, R);
-#pragma unroll
-            for (u32 j = 0; j < 4; ++j) hr[j] = __builtin_bswap32(gsb_from_col(h, 3u - j));      /* rev(H), little-endian words */
-            pv_mulx(hr, hk);
-            pv_lane(V, hk, li);
-        }
-
-        const u32 full = len >> 4, rem = len & 15u;
-        u32 s = 0;
-        for (u32 i = 0; i < aad_bytes; i += 16) s = pv_step(s, gmk_rev(row_load(aad + m * aad_bytes + i, aad_bytes - i, c)), V, c);
-        const u32 lb = c == 0u ? len << 3 : c == 2u ? aad_bytes << 3 : 0u;      /* rev(BE64(8 aad) || BE64(8 len)) */
-        if (!DEC) {
-            row_walk<A4, GMK_CH_ENC>(src, full, c, [&](u64 i, u32 x) {
-                const u32 y = x ^ row_encrypt<NR>(gmk_ctr(nw, (u32)i, c), R);
-                row_store_full<A4>(dst + 16 * i, y, c);
-                s = pv_step(s, gmk_rev(y), V, c);
-            });
-            if (rem) {                                           /* the partial last block: cut, then zero padded into the hash */
-                const u32 x = row_load(src + 16 * (u64)full, rem, c);
-                const u32 y = (x ^ row_encrypt<NR>(gmk_ctr(nw, full, c), R)) & row_keep(rem, c);
-                row_put(dst + 16 * (u64)full, y, rem, c);
-                s = pv_step(s, gmk_rev(y), V, c);
-            }
-            s = pv_step(s, lb, V, c);
-            row_put(tags + m * tag_len, gmk_rev(s) ^ ej0, tag_len, c);
-        } else {
-            row_walk<A4, GMK_CH_HASH>(src, full, c, [&](u64, u32 x) { s = pv_step(s, gmk_rev(x), V, c); });
-            if (rem) s = pv_step(s, gmk_rev(row_load(src + 16 * (u64)full, rem, c)), V, c);
-            s = pv_step(s, lb, V, c);
-            const u32 t = gmk_rev(s) ^ ej0, rt = row_load(tags + m * tag_len, tag_len, c);
-            const bool forged = row_any(((t ^ rt) & row_keep(tag_len, c)) != 0u);
-            row_verdict(li == 0, verdicts, m, !forged, bad);
-            if (!forged) {
-                row_walk<A4, GMK_CH_CTR>(src, full, c, [&](u64 i, u32 x) {
-                    row_store_full<A4>(dst + 16 * i, x ^ row_encrypt<NR>(gmk_ctr(nw, (u32)i, c), R), c);
-                });
-                if (rem) {
-                    const u32 x = row_load(src + 16 * (u64)full, rem, c);
-                    row_put(dst + 16 * (u64)full, x ^ row_encrypt<NR>(gmk_ctr(nw, full, c), R), rem, c);
-                }
-            }
-        }
+        gcm_row_record<NR, DEC, A4>(slot, li, c, np, tag_len, aad, aad_bytes, m, len, src, dst, tags, verdicts, bad);
     }
 }
 

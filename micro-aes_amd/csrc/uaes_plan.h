@@ -27,6 +27,7 @@
  *         GCM_STRIPED           k_gcm_setup | k_gcm_ej0, k_gcm_fused, k_ghash_final (3)    encrypt / one-pass decrypt beyond (C4: 1 GiB)
  *         GCM_LEVELS            k_gcm_setup, k_ctr*, k_ghash_pass x0-2, k_ghash_final (3-5) whatever is left (tag-only; > 512 MiB tag-first)
  *         gcm.multikey          k_gcm_multikey (sixteen lanes per record, four per wave; a key per record) (1)  uaes_gcm_multikey_*_batch, records <= UAES_GCM_MULTIKEY_BATCH_MAX (65535 B)
+ *         xaes.gcm              k_xaes_gcm_batch (sixteen lanes per record, four per wave; a key per nonce) (1)  uaes_xaes256gcm_*_batch, records <= UAES_XAES_GCM_BATCH_MAX (65535 B)
  *   OCB   OCB_SMALL             k_ocb_small                                         (1)    <= OCB_SMALL_BLOCKS blocks and short AAD
  *         OCB_RUNS              k_ocb (last workgroup to arrive makes the tag)      (1)    otherwise
  *         ocb.batch             k_ocb_batch (sixteen lanes per record, four per wave) (1)  uaes_ocb_*_batch, records <= UAES_OCB_BATCH_MAX (65535 B)
@@ -85,8 +86,9 @@
  * and tests/test_gpu_ocb.py takes its sizes from walking it.  The OCB batches have uaesk_plan_ocb_batch (uaes_ocb.hip;
  * uaes_debug_plan_ocb_batch): one row, with an id outside enum uaes_arrangement.  So do the multi-key GCM batches:
  * uaesk_plan_gcm_multikey_batch (uaes_gcm_multikey.hip; uaes_debug_plan_gcm_multikey_batch), and the batches of the plain
- * cipher modes: uaesk_plan_cipher_batch (uaes_cipher_batch.hip; uaes_debug_plan_cipher_batch).
- * The rows that say "sixteen lanes per record / message" -- eax.batch, s2v.batch, ccm.batch, gcmsiv.batch, gcm.multikey, ocb.batch, batch.row,
+ * cipher modes: uaesk_plan_cipher_batch (uaes_cipher_batch.hip; uaes_debug_plan_cipher_batch), and the XAES-256-GCM
+ * batches: uaesk_plan_xaes_gcm_batch (uaes_xaes.hip; uaes_debug_plan_xaes256gcm_batch).
+ * The rows that say "sixteen lanes per record / message" -- eax.batch, s2v.batch, ccm.batch, gcmsiv.batch, gcm.multikey, xaes.gcm, ocb.batch, batch.row,
  * cipher.batch, kw.batch, kwp.batch, ff1.batch, ff3.batch -- are the row batches: grid and threads per workgroup are uaesk_row_shape's (uaes_launch.hip.h), the same
  * for the same number of records in every one of them.
  */
@@ -312,6 +314,19 @@ typedef char uaes_gcm_multikey_counter_stays_in_bytes_14_15[(UAES_GCM_MULTIKEY_B
 enum uaes_gcm_multikey_arrangement { UAES_GCM_MULTIKEY = 0 };
 int uaesk_plan_gcm_multikey_batch(int dir, size_t len, size_t nmsg, uaes_plan *p);
 const char *uaesk_gcm_multikey_arrangement_name(int id);
+
+/* The batches of XAES-256-GCM records (C2SP; k_xaes_gcm_batch, uaes_xaes.hip).  dir: 0 encrypt, 1 decrypt; len = bytes
+ * per record, nmsg = records; one arrangement, a row batch at any number of records.  A record is a key derivation and
+ * a key expansion in front of the multi-key batch's record (gcm_row_record, uaes_gcm_row.hip.h), so its cap is that
+ * batch's, for the same reason: at most 4096 counter blocks, J0 + 1 .. J0 + 4096 with J0 = N[12:24] || 00000001, and only
+ * bytes 14..15 of the counter block ever change (asserted below).  It is also the most AAD a record takes.  grid =
+ * workgroups, steps = threads per workgroup.  Returns a HIP error code for a dir other than 0 / 1 or a length above the
+ * limit. */
+#define UAES_XAES_GCM_BATCH_MAX ((size_t)65535)
+typedef char uaes_xaes_gcm_counter_stays_in_bytes_14_15[(UAES_XAES_GCM_BATCH_MAX + 15) / 16 + 1 <= 0xFFFF ? 1 : -1];
+enum uaes_xaes_gcm_arrangement { UAES_XAES_GCM = 0 };
+int uaesk_plan_xaes_gcm_batch(int dir, size_t len, size_t nmsg, uaes_plan *p);
+const char *uaesk_xaes_gcm_arrangement_name(int id);
 
 /* The batches of the plain cipher modes (k_cipher_batch, uaes_cipher_batch.hip).  mode = enum uaes_cipher_batch_mode;
  * len = bytes per record, nmsg = records; one arrangement, a row batch at any number of records and any record length

@@ -8,7 +8,10 @@
             uaes_gcm_key_encrypt_records / uaes_gcm_key_decrypt_records at the same shape -- those two under ONE key
 AES-128 and AES-256, 12 bytes of AAD per record, 16-byte tags, the keys in device memory.  Every figure: warm-up, then
 REPS repetitions; median, minimum and maximum.  The calls are synchronous, so every figure includes the host round trip.
-Usage: gcm_multikey_rate.py [--out FILE] [--quick]"""
+  --xaes    instead: 2^20 device-resident records of 16, 64 and 1024 bytes through uaes_xaes256gcm_encrypt_batch /
+            uaes_xaes256gcm_decrypt_batch (24-byte nonces, the key of every record derived in the kernel), and beside each
+            the multi-key batch at AES-256 on the same texts; to profiles/xaes_gcm_batch_rate.md unless --out names a file
+Usage: gcm_multikey_rate.py [--xaes] [--out FILE] [--quick]"""
 import ctypes as C
 import os
 import statistics
@@ -91,8 +94,70 @@ def shape(bits, key, n, ml, calls, emit):
     return med
 
 
+def xaes_main(quick, out_path):
+    rows = []
+    emit = rows.append
+    props = torch.cuda.get_device_properties(0)
+    emit("# XAES-256-GCM batches: measured rates\n")
+    emit("Output of `tools/gcm_multikey_rate.py --xaes` on %s (%d CUs).  Microseconds are median (minimum .. maximum) of %d "
+         "windows after a warm-up window; the calls are synchronous, so every figure includes the host round trip.  "
+         "Device-resident arrays; %d bytes of AAD per record, 16-byte tags; 24-byte nonces for XAES-256-GCM, 12-byte nonces "
+         "and a 32-byte key per record for the multi-key rows, which run in the same process on the same texts.\n"
+         % (props.name, props.multi_processor_count, REPS, AAD))
+    if quick:
+        emit("(Run with `--quick`: fewer calls per window.)\n")
+    emit("Row steps per record, from the code: k_xaes_gcm_batch does what k_gcm_multikey<14> does and one two-block step of "
+         "the cipher in front of it (the two halves of the nonce's key under the master key); it reads 24 bytes of nonce "
+         "where the multi-key kernel reads 32 bytes of key and 12 of nonce.\n")
+    emit("| record | records | call | plan | us per call | records per second | MiB/s of text | ns per record |\n"
+         "|---|---|---|---|---|---|---|---|")
+    key = (C.c_uint8 * 32).from_buffer_copy(bytes(range(32)))
+    n, calls = 1 << 20, 3 if quick else 10
+    ratios = []
+    for ml in (16, 64, 1024):
+        texts, xnonces, aads, keys = rand(n * ml), rand(n * 24), rand(n * AAD), rand(n * 32)
+        out, back = torch.zeros_like(texts), torch.zeros_like(texts)
+        mout = torch.zeros_like(texts)
+        tags, mtags = torch.zeros(n * 16, dtype=torch.uint8, device="cuda"), torch.zeros(n * 16, dtype=torch.uint8, device="cuda")
+        verdicts = torch.zeros(n, dtype=torch.uint8, device="cuda")
+        xenc = lambda: L.uaes_xaes256gcm_encrypt_batch(key, n, ml, None, p(xnonces), p(aads), AAD, p(texts), p(out), p(tags))
+        xdec = lambda: L.uaes_xaes256gcm_decrypt_batch(key, n, ml, None, p(xnonces), p(aads), AAD, p(out), p(tags), p(back), p(verdicts))
+        menc = lambda: L.uaes_gcm_multikey_encrypt_batch(256, p(keys), 16, n, ml, None, p(xnonces), p(aads), AAD, p(texts), p(mout), p(mtags))
+        mdec = lambda: L.uaes_gcm_multikey_decrypt_batch(256, p(keys), 16, n, ml, None, p(xnonces), p(aads), AAD, p(mout), p(mtags), p(back),
+                                                         p(verdicts))
+        assert xenc() == 0 and xdec() == 0 and torch.equal(back, texts) and not torch.equal(out, texts) and bool(verdicts.all())
+        assert menc() == 0 and mdec() == 0 and torch.equal(back, texts) and bool(verdicts.all())
+        xplan, mplan = uaes.xaes256gcm_batch_plan(ml, n), uaes.gcm_multikey_batch_plan(ml, n)
+        med = {}
+        for name, fn, pl in (("xaes-256-gcm encrypt", xenc, xplan), ("xaes-256-gcm decrypt", xdec, xplan),
+                             ("gcm multi-key encrypt, AES-256", menc, mplan), ("gcm multi-key decrypt, AES-256", mdec, mplan)):
+            assert fn() == 0, name
+            us = reps_of(fn, calls)
+            med[name] = statistics.median(us)
+            emit("| %d B | 2^20 | %s | %s %d x %d | %s | %.3g | %.0f | %.2f |" % (
+                ml, name, pl[0], pl[2], pl[3], cell(us), n / med[name] * 1e6, n * ml / med[name] * 1e6 / (1 << 20), med[name] * 1e3 / n))
+        ratios.append((ml, med["xaes-256-gcm encrypt"] / med["gcm multi-key encrypt, AES-256"],
+                       med["xaes-256-gcm decrypt"] / med["gcm multi-key decrypt, AES-256"]))
+        del texts, out, back, mout
+        torch.cuda.empty_cache()
+    emit("")
+    emit("Time of an XAES-256-GCM batch call as a multiple of the multi-key AES-256 call at the same shape:\n")
+    emit("| record | encrypt | decrypt |\n|---|---|---|")
+    for ml, e, d in ratios:
+        emit("| %d B | %.2f | %.2f |" % (ml, e, d))
+    emit("")
+    text_out = "\n".join(rows) + "\n"
+    print(text_out)
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        f.write(text_out)
+
+
 def main():
     quick = "--quick" in sys.argv
+    if "--xaes" in sys.argv:
+        return xaes_main(quick, sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv
+                         else os.path.join(ROOT, "profiles", "xaes_gcm_batch_rate.md"))
     out_path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(ROOT, "profiles", "gcm_multikey_batch_rate.md")
     rows = []
     emit = rows.append

@@ -87,6 +87,11 @@ print("Multi-key GCM batches: a record holds at most UAES_GCM_MULTIKEY_BATCH_MAX
 walk("Multi-key GCM batch, k records of 64 bytes (positions/thread: threads per workgroup)",
      lambda k: uaes.gcm_multikey_batch_plan(64, max(k, 1))[:2] + (0, uaes.gcm_multikey_batch_plan(64, max(k, 1))[3]), 1, 1 << 20, 1,
      lambda k: "%9d records (%9.3f MiB)" % (k, k * 64 / MIB))
+top = max(n for n in range(65000, 66000) if uaes.xaes256gcm_batch_plan(n, 2) is not None)
+print("XAES-256-GCM batches: a record holds at most UAES_XAES_GCM_BATCH_MAX = %d bytes of text" % top)
+walk("XAES-256-GCM batch, k records of 64 bytes (positions/thread: threads per workgroup)",
+     lambda k: uaes.xaes256gcm_batch_plan(64, max(k, 1))[:2] + (0, uaes.xaes256gcm_batch_plan(64, max(k, 1))[3]), 1, 1 << 20, 1,
+     lambda k: "%9d records (%9.3f MiB)" % (k, k * 64 / MIB))
 top = max(n for n in range(65000, 66000) if uaes.ocb_batch_plan(n, 2) is not None)
 print("OCB batches: a record holds at most UAES_OCB_BATCH_MAX = %d bytes of text" % top)
 walk("OCB batch, k records of 64 bytes (positions/thread: threads per workgroup)",
