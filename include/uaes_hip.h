@@ -175,6 +175,39 @@ int uaes_xts_decrypt(int keybits, const uint8_t *keys, const uint8_t *tweak,
 int uaes_xts_sectors(int keybits, const uint8_t *keys, uint64_t first_sector,
                      size_t sector_bytes, size_t nsectors,
                      const void *in, void *out, int encrypt);
+/* Batches: nmsg data units in slots of msg_bytes, a tweak each, one launch (k_xts_batch: sixteen GPU lanes per unit).
+ * The conventions are the cipher batches' (uaes_ctr_xcrypt_batch): unit m lies at m * msg_bytes in both texts, the calls
+ * always run on the GPU (no host policy), every array is host or device memory, in == out works (partial overlap is
+ * undefined); there are no *_dev and no uaes_mgpu_* forms.  keys = key1 || key2 in host memory.
+ * tweaks = nmsg * 16 raw bytes at any byte offset: unit m is bit for bit what uaes_xts_encrypt / uaes_xts_decrypt give
+ * for it with the tweak at tweaks + 16 m, ciphertext stealing included when its length is no multiple of 16.
+ * lens = NULL (every unit is msg_bytes long) or nmsg 32-bit lengths (device memory: 4-byte aligned, else UAES_E_ARG):
+ * unit m is the first lens[m] bytes of its slot, an entry above msg_bytes counts as msg_bytes, the rest of an output
+ * slot is not written (a host output is copied in first, so it stays the caller's).  An entry below 16, zero included,
+ * writes nothing for that unit; every other unit is finished and the call returns UAES_E_DATALENGTH, as
+ * uaes_kwp_wrap_batch has it.  Without lens no status word is armed or fetched.
+ * Refusals, in this order and before the device is touched: msg_bytes > UINT32_MAX or a size that overflows ->
+ * UAES_E_ARG; a NULL key pair or keybits other than 128 / 192 / 256 -> UAES_E_ARG; nmsg == 0 -> 0, nothing else looked
+ * at; msg_bytes < 16 -> UAES_E_DATALENGTH, output untouched; a NULL tweaks / text pointer -> UAES_E_ARG.
+ * uaes_xts_sector_list is the storage form: unit m's tweak is LE128(sectors[m]), eight bytes per unit instead of
+ * sixteen; the sectors come in any order and may repeat (a block layer's request list); every unit is sector_bytes long
+ * (520 steals per unit) and there is no lens.  A contiguous ascending list gives what uaes_xts_sectors gives -- and a
+ * contiguous run of equal sectors remains that call's job: it spreads a unit's blocks over many lanes, where a batch
+ * walks a unit on sixteen.
+ * Measured (profiles/xts_batch_rate.md; device-resident arrays, synchronous calls, AES-128, AES-256 in brackets): 2^10
+ * units of 16 bytes take 21.2 (21.6) us as ONE call, decrypting 22.4 (22.8), against 14.1 (16.2) us for EACH of 2^10
+ * one-unit uaes_xts_encrypt calls.  2^20 units of 16 / 64 / 512 / 1024 / 4096 bytes encrypt in 226 / 302 / 1148 / 2211 /
+ * 8935 us (248 / 349 / 1453 / 2817 / 11317), 4.6 G units/s at 16 bytes and 434 .. 452 GiB/s from 512 bytes on; decrypting
+ * takes 0 .. 4 % longer and the sector list as long as the batch.  Against uaes_ctr_xcrypt_batch at the same shape that
+ * is 1.25 / 1.19 / 1.08 / 1.06 / 1.05 x its time, where the row steps alone would give 2 / 1.5 / 1.06 / 1.03 / 1.01.
+ * For a CONTIGUOUS run of 2^20 equal sectors uaes_xts_sectors wins from 64 bytes per unit on (83 us against 302 at 64
+ * bytes, 443 against 1148 at 512, 3070 against 8935 at 4096); only at 16-byte units is the batch the faster call. */
+int uaes_xts_encrypt_batch(int keybits, const uint8_t *keys, const uint8_t *tweaks, size_t nmsg,
+                           size_t msg_bytes, const uint32_t *lens, const void *pntxt, void *crtxt);
+int uaes_xts_decrypt_batch(int keybits, const uint8_t *keys, const uint8_t *tweaks, size_t nmsg,
+                           size_t msg_bytes, const uint32_t *lens, const void *crtxt, void *pntxt);
+int uaes_xts_sector_list(int keybits, const uint8_t *keys, const uint64_t *sectors, size_t nsectors,
+                         size_t sector_bytes, const void *in, void *out, int encrypt);
 
 /* ---- GCM: replaces AES_GCM_encrypt / AES_GCM_decrypt --------------------
  * micro_aes.h:294-308, micro_aes.c:1164-1212.  12-byte nonce (GCM_NONCE_LEN),
@@ -1082,6 +1115,11 @@ const char *uaes_debug_plan_ocb_batch(int dir, size_t len, size_t nmsg, int out[
  * threads as "ccm.batch" for the same number of records), or NULL for another mode, a CBC record that is not a whole
  * number of blocks or a record of the other modes above UINT32_MAX bytes.  Works without a device (a 256-CU MI355X). */
 const char *uaes_debug_plan_cipher_batch(int mode, size_t len, size_t nmsg, int out[3]);
+/* The planner of the XTS batches and sector lists (csrc/uaes_plan.h): len = bytes per unit's slot, nmsg = units; out (may
+ * be NULL) receives { launches, workgroups, threads per workgroup, units per workgroup }.  Returns "xts.batch" (the one
+ * arrangement: sixteen lanes per unit, the same grid and threads as "ccm.batch" for the same number of records), or NULL
+ * for a unit below 16 or above UINT32_MAX bytes.  Works without a device (a 256-CU MI355X). */
+const char *uaes_debug_plan_xts_batch(size_t len, size_t nmsg, int out[4]);
 /* The plan of one piece of a streamed GCM message (csrc/uaes_plan.h, uaesk_plan_gcm_piece: the function
  * uaes_gcm_stream_update's kernel layer switches on): decrypt 0 / 1; len = bytes of the piece; done_bytes = text the
  * stream has taken before it (a multiple of 16), which decides where the piece's groups of 256 counters fall.  The

@@ -38,6 +38,7 @@ EXPORTS = [
     "uaes_set_wipe_on_auth_failure", "uaes_set_gcm_one_pass_decrypt", "uaes_clock_probe_dev",
     "uaes_ecb_encrypt", "uaes_ecb_encrypt_padded", "uaes_ecb_decrypt", "uaes_ctr_xcrypt", "uaes_ctr_xcrypt_iv", "uaes_ctr_xcrypt_at",
     "uaes_xts_encrypt", "uaes_xts_decrypt", "uaes_xts_sectors",
+    "uaes_xts_encrypt_batch", "uaes_xts_decrypt_batch", "uaes_xts_sector_list", "uaes_debug_plan_xts_batch",
     "uaes_gcm_encrypt", "uaes_gcm_decrypt", "uaes_gcm_encrypt_iv", "uaes_gcm_decrypt_iv", "uaes_ghash",
     "uaes_gcm_encrypt_ex", "uaes_gcm_decrypt_ex", "uaes_ccm_encrypt_ex", "uaes_ccm_decrypt_ex",
     "uaes_ccm_encrypt_batch", "uaes_ccm_decrypt_batch",
@@ -154,6 +155,11 @@ def engine():
     for n in ("uaes_xts_encrypt", "uaes_xts_decrypt"):
         getattr(L, n).argtypes = [i, vp, vp, vp, sz, vp]
     L.uaes_xts_sectors.argtypes = [i, vp, u64, sz, sz, vp, vp, i]
+    for n in ("uaes_xts_encrypt_batch", "uaes_xts_decrypt_batch"):
+        getattr(L, n).argtypes = [i, vp, vp, sz, sz, vp, vp, vp]
+    L.uaes_xts_sector_list.argtypes = [i, vp, vp, sz, sz, vp, vp, i]
+    L.uaes_debug_plan_xts_batch.argtypes = [sz, sz, C.POINTER(C.c_int)]
+    L.uaes_debug_plan_xts_batch.restype = C.c_char_p
     for n in ("uaes_gcm_encrypt", "uaes_gcm_decrypt"):
         getattr(L, n).argtypes = [i, vp, vp, vp, sz, vp, sz, vp]
     for n in ("uaes_gcm_encrypt_iv", "uaes_gcm_decrypt_iv"):
@@ -305,7 +311,7 @@ def engine():
                      "uaes_debug_plan_eax_siv", "uaes_debug_plan_chain", "uaes_debug_plan_kw", "uaes_debug_plan_kwp", "uaes_debug_plan_ff1",
                      "uaes_debug_plan_ff3", "uaes_ff3_maxlen", "uaes_debug_plan_gcmsiv_batch", "uaes_debug_plan_ocb", "uaes_debug_plan_xts",
                      "uaes_debug_gcm_stream_tables", "uaes_debug_plan_ocb_batch", "uaes_debug_plan_gcm_multikey_batch", "uaes_debug_plan_cipher_batch",
-                     "uaes_debug_plan_xaes256gcm_batch"):
+                     "uaes_debug_plan_xaes256gcm_batch", "uaes_debug_plan_xts_batch"):
             getattr(L, n).restype = i
     _lib = L
     return L
@@ -427,6 +433,50 @@ def xts_sectors(keys, first_sector, sector_bytes, data, encrypt=True):
                                           len(data) // sector_bytes, _in(data), o, 1 if encrypt else 0),
                 "uaes_xts_sectors")
     return rc, bytes(o)[: len(data)]
+
+
+def xts_batch(keys, tweaks, units, decrypt=False):
+    """XTS of many data units, a 16-byte tweak each, one launch: == [AES_XTS_encrypt(keys, tw, u)[1] for tw, u in ...]
+    (decrypt: AES_XTS_decrypt).  The units may differ in length: they travel in slots of the longest one, with their
+    lengths as the call's `lens`.  Returns (code, units); code 1 if a unit is below 16 bytes -- that unit comes back as
+    zeros of its length, every other one is done."""
+    n = len(units)
+    if len(tweaks) != n or any(len(t) != 16 for t in tweaks):
+        raise ValueError("one 16-byte tweak per unit")
+    if n == 0:
+        return 0, []
+    sizes = [len(u) for u in units]
+    size = max(sizes)
+    lens = (C.c_uint32 * n)(*sizes) if min(sizes) != size else None
+    packed = b"".join(bytes(u) + bytes(size - len(u)) for u in units)
+    o = _out(n * size)
+    name = "uaes_xts_decrypt_batch" if decrypt else "uaes_xts_encrypt_batch"
+    rc = _check(getattr(engine(), name)(_bits(keys, 2), _in(keys), _in(b"".join(bytes(t) for t in tweaks)), n, size, lens,
+                                        _in(packed), o), name)
+    raw = bytes(o)
+    return rc, [raw[m * size: m * size + sizes[m]] for m in range(n)]
+
+
+def xts_sector_list(keys, sectors, sector_bytes, data, encrypt=True):
+    """The storage form of xts_batch: unit m of `data` (sector_bytes each) has the tweak LE128(sectors[m]); the sectors
+    come in any order and may repeat.  Returns (code, output); code 1 if sector_bytes < 16 (output untouched)."""
+    n = len(sectors)
+    if sector_bytes <= 0 or len(data) != n * sector_bytes:
+        raise ValueError("data must hold one unit of sector_bytes per sector")
+    if n == 0:
+        return 0, b""
+    o = _out(len(data))
+    rc = _check(engine().uaes_xts_sector_list(_bits(keys, 2), _in(keys), (C.c_uint64 * n)(*sectors), n, sector_bytes,
+                                              _in(data), o, 1 if encrypt else 0), "uaes_xts_sector_list")
+    return rc, bytes(o)[: len(data)]
+
+
+def xts_batch_plan(nmsg, length=16):
+    """What an XTS batch or sector list of nmsg units of `length` bytes would run (uaes_debug_plan_xts_batch):
+    (arrangement, launches, workgroups, threads per workgroup), or None for a length XTS does not have."""
+    out = (C.c_int * 4)()
+    name = engine().uaes_debug_plan_xts_batch(length, nmsg, out)
+    return None if name is None else (name.decode(), out[0], out[1], out[2])
 
 
 def _taglen(tag_len, lo, hi, even, what):

@@ -241,6 +241,16 @@ int uaesk_chain_batch(void *stream, const uaesk_tables *tb, int nr, const uaesk_
 int uaesk_cipher_batch(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, const uaesk_rk *dk, int mode,
                        const void *ivs, size_t nmsg, size_t msg_bytes, const void *lens, const void *in, void *out);
 
+/* Batches of XTS data units, sixteen lanes per unit (k_xts_batch, uaes_xts_batch.hip); all device pointers at any byte
+ * offset (lens: 4-byte aligned).  Unit m: text at in / out + m msg_bytes (16 <= msg_bytes <= UINT32_MAX), its first
+ * lens[m] bytes (lens NULL: msg_bytes), tweak at tweaks + m tweak_bytes: 16 raw bytes, or 8, a sector number whose
+ * LE128 is the tweak.  k1: key 1's encryption schedule, decrypting its equivalent-inverse one; k2: key 2's encryption
+ * schedule.  A unit whose length is below 16 is left unwritten and sets bit 0 of *bad; bad is not touched without lens.
+ * in == out is fine.  The plan (uaesk_plan_xts_batch, uaes_plan.h) is one row, xts.batch. */
+int uaesk_xts_batch(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *k1, const uaesk_rk *k2, int decrypt,
+                    const void *tweaks, unsigned tweak_bytes, size_t nmsg, size_t msg_bytes, const void *lens,
+                    const void *in, void *out, int *bad);
+
 /* OCB (AES_OCB_encrypt/decrypt, micro_aes.c:1693-1811): nonce (host) of nonce_len = 1..15 bytes, tag_len
  * (1..16) bytes of tag at out+len (encrypt) / read at in+len (decrypt, *status = 0 / 0x1A; the text
  * is written either way, as in the reference).  dk = equivalent-inverse keys.  ONE launch; done_word = a device

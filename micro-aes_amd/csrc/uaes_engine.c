@@ -1528,6 +1528,15 @@ const char *uaes_debug_plan_cipher_batch(int mode, size_t len, size_t nmsg, int 
 {
     return debug_plan_rows(uaesk_plan_cipher_batch, uaesk_cipher_batch_arrangement_name, mode, len, nmsg, out);
 }
+/* out = { launches, workgroups, threads per workgroup, units per workgroup } */
+const char *uaes_debug_plan_xts_batch(size_t len, size_t nmsg, int out[4])
+{
+    uaes_plan p;
+    memset(&p, 0, sizeof p);
+    if (uaesk_plan_xts_batch(len, nmsg, &p)) return NULL;
+    if (out) { out[0] = p.launches; out[1] = (int)p.grid; out[2] = (int)p.steps; out[3] = (int)(p.steps / 16u); }
+    return uaesk_xts_batch_arrangement_name(p.arrangement);
+}
 const char *uaes_debug_plan_ocb(int dir, size_t len, size_t aad_len, int aad_aligned, int out[5])
 {
     uaes_plan p;

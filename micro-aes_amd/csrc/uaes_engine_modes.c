@@ -316,6 +316,65 @@ int uaes_xts_sectors_dev(int keybits, const uint8_t *keys, uint64_t first_sector
     return xts_run(c, stream, &k1, &k2, encrypt, NULL, first_sector, sector_bytes, nsectors, d_in, d_out, NULL);
 }
 
+/* Batches of data units, sixteen GPU lanes per unit (k_xts_batch, uaes_xts_batch.hip): nmsg units in slots of msg_bytes,
+ * one launch, always on the GPU.  tweaks = tweak_bytes per unit: 16 raw bytes, or 8, a sector number (the kernel
+ * widens it to LE128).  The conventions are the cipher batches' (cipher_rows): every array host or device memory at any
+ * byte offset, host arrays through the lane's scratch and staging buffers; with `lens` a host-memory output starts as a
+ * copy of the caller's buffer and the status word is armed, which a unit below 16 bytes sets.  The order: the sizes,
+ * the keys, nothing more for no units, a slot below 16 bytes, the pointers, and only then the device. */
+static int xts_rows(int encrypt, int keybits, const uint8_t *keys, const void *tweaks, unsigned tweak_bytes, size_t nmsg,
+                    size_t msg_bytes, const uint32_t *lens, const void *in, void *outp)
+{
+    const size_t total = nmsg * msg_bytes;
+    context *c;
+    lane *L;
+    KEYSCHED(k1);
+    KEYSCHED(k2);
+    int rc, k, bad;
+    if (msg_bytes > UINT32_MAX)
+        return fail(UAES_E_ARG, "a batch unit holds at most %u bytes (got %zu)", UINT32_MAX, msg_bytes);
+    if (nmsg > (size_t)-1 / 2 / (msg_bytes > 16 ? msg_bytes : 16))     /* / 2: the tweaks, the lengths and their padding */
+        return fail(UAES_E_ARG, "batch size overflows");
+    if ((rc = xts_keys(&k1, &k2, keys, keybits)) != 0) return rc;
+    if (nmsg == 0) return 0;
+    if (msg_bytes < 16) return UAES_E_DATALENGTH;                /* :1069, untouched */
+    if (!tweaks || !in || !outp) return fail(UAES_E_ARG, "NULL pointer");
+    if ((rc = enter(&c, &L)) != 0) return rc;
+    row_array a[2] = { { tweaks, nmsg * tweak_bytes, 0, NULL }, { lens, lens ? nmsg * sizeof *lens : 0, 0, NULL } };
+    row_text t = { in, outp, total, total, lens != NULL, NULL, NULL };
+    if (lens && is_device_ptr(lens) && ((uintptr_t)lens & 3u)) {
+        rc = fail(UAES_E_ARG, "a device array of lengths must be 4-byte aligned");
+        goto out;
+    }
+    if ((rc = row_stage(L, a, 2, lens != NULL)) != 0) goto out;
+    if ((rc = row_texts(L, &t)) != 0) goto out;
+    k = uaesk_xts_batch(L->stream, &c->tb, k1.nr, encrypt ? &k1.ek : &k1.dk, &k2.ek, !encrypt, a[0].d, tweak_bytes, nmsg,
+                        msg_bytes, a[1].d, t.d_in, t.d_out, L->d_status);
+    if ((rc = launched("xts batch", k)) != 0) goto out;
+    if ((rc = row_finish(L, &t, a, 2, lens != NULL, &bad)) != 0) goto out;
+    if (bad) rc = UAES_E_DATALENGTH;
+out:
+    DONE(L, rc);
+}
+
+int uaes_xts_encrypt_batch(int keybits, const uint8_t *keys, const uint8_t *tweaks, size_t nmsg,
+                           size_t msg_bytes, const uint32_t *lens, const void *pntxt, void *crtxt)
+{
+    return xts_rows(1, keybits, keys, tweaks, 16, nmsg, msg_bytes, lens, pntxt, crtxt);
+}
+
+int uaes_xts_decrypt_batch(int keybits, const uint8_t *keys, const uint8_t *tweaks, size_t nmsg,
+                           size_t msg_bytes, const uint32_t *lens, const void *crtxt, void *pntxt)
+{
+    return xts_rows(0, keybits, keys, tweaks, 16, nmsg, msg_bytes, lens, crtxt, pntxt);
+}
+
+int uaes_xts_sector_list(int keybits, const uint8_t *keys, const uint64_t *sectors, size_t nsectors,
+                         size_t sector_bytes, const void *in, void *out, int encrypt)
+{
+    return xts_rows(encrypt != 0, keybits, keys, sectors, 8, nsectors, sector_bytes, NULL, in, out);
+}
+
 /* ------------------------------------------------------------------------ */
 /* CMAC and CCM: serial CBC-MAC chains, one GPU lane */
 /* ------------------------------------------------------------------------ */

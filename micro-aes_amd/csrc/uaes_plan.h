@@ -20,7 +20,8 @@
  *   XTS   XTS_SMALL             k_xts_small [+ k_xts_cts]                           (1-2)  one unit <= 8 MiB, or <= 4 MiB of whole-block units
  *         XTS_PACKED            k_xts_tweaks + k_xts<PACKED>                        (2)    units shorter than a chunk, whole blocks
  *         XTS_BULK              k_xts_tweaks [+ k_xts_expand] + k_xts [+ k_xts_cts] (2-4)  everything else (C3: 2^20 sectors of 4 KiB)
- *   GCM   GCM_SMALL             k_gcm_small                                         (1)    <= 2046 GHASH positions (~32 KiB)
+ *         xts.batch             k_xts_batch (sixteen lanes per unit, four per wave; a tweak per unit) (1)  uaes_xts_*_batch, uaes_xts_sector_list: any number of units
+ *   GCM   GCM_SMALL             k_gcm_small                                      (1)    <= 2046 GHASH positions (~32 KiB)
  *         GCM_CHUNKS            k_gcm_chunks<FOLD> [+ gated k_ctr*]                 (1-2)  encrypt <= 16 MiB; tag-first decrypt <= 512 MiB
  *                               (k_gcm_chunks + k_gcm_combine without a counter word or for a one-pass decrypt)
  *         GCM_TWOPHASE          k_ctr_shared2, then hash-only k_gcm_chunks<FOLD>    (2)    encrypt / one-pass decrypt, 16 .. 128 MiB
@@ -87,9 +88,10 @@
  * uaes_debug_plan_ocb_batch): one row, with an id outside enum uaes_arrangement.  So do the multi-key GCM batches:
  * uaesk_plan_gcm_multikey_batch (uaes_gcm_multikey.hip; uaes_debug_plan_gcm_multikey_batch), and the batches of the plain
  * cipher modes: uaesk_plan_cipher_batch (uaes_cipher_batch.hip; uaes_debug_plan_cipher_batch), and the XAES-256-GCM
- * batches: uaesk_plan_xaes_gcm_batch (uaes_xaes.hip; uaes_debug_plan_xaes256gcm_batch).
- * The rows that say "sixteen lanes per record / message" -- eax.batch, s2v.batch, ccm.batch, gcmsiv.batch, gcm.multikey, xaes.gcm, ocb.batch, batch.row,
- * cipher.batch, kw.batch, kwp.batch, ff1.batch, ff3.batch -- are the row batches: grid and threads per workgroup are uaesk_row_shape's (uaes_launch.hip.h), the same
+ * batches: uaesk_plan_xaes_gcm_batch (uaes_xaes.hip; uaes_debug_plan_xaes256gcm_batch), and the XTS batches and sector
+ * lists: uaesk_plan_xts_batch (uaes_xts_batch.hip; uaes_debug_plan_xts_batch).
+ * The rows that say "sixteen lanes per record / message / unit" -- eax.batch, s2v.batch, ccm.batch, gcmsiv.batch, gcm.multikey, xaes.gcm, ocb.batch, batch.row,
+ * xts.batch, cipher.batch, kw.batch, kwp.batch, ff1.batch, ff3.batch -- are the row batches: grid and threads per workgroup are uaesk_row_shape's (uaes_launch.hip.h), the same
  * for the same number of records in every one of them.
  */
 #ifndef UAES_PLAN_H
@@ -339,6 +341,16 @@ enum uaes_cipher_batch_mode { UAES_CB_CBC_DEC = 0, UAES_CB_CBC_DEC_BLOCKS, UAES_
 enum uaes_cipher_batch_arrangement { UAES_CIPHER_BATCH = 0 };
 int uaesk_plan_cipher_batch(int mode, size_t len, size_t nmsg, uaes_plan *p);
 const char *uaesk_cipher_batch_arrangement_name(int id);
+
+/* The batches of XTS data units (k_xts_batch, uaes_xts_batch.hip): uaes_xts_encrypt_batch, uaes_xts_decrypt_batch and
+ * uaes_xts_sector_list.  len = bytes per unit's slot, nmsg = units; one arrangement, a row batch at any number of units,
+ * with an id outside enum uaes_arrangement (uaes_debug_plan_xts_batch names it).  A unit is walked by sixteen lanes, two
+ * blocks per step, so a contiguous run of equal sectors stays with the XTS rows above, which spread a unit over many
+ * lanes.  grid = workgroups, steps = threads per workgroup.  Returns a HIP error code for a unit below 16 bytes (XTS has
+ * none) or above UINT32_MAX (what a 32-bit length can say). */
+enum uaes_xts_batch_arrangement { UAES_XTS_BATCH = 0 };
+int uaesk_plan_xts_batch(size_t len, size_t nmsg, uaes_plan *p);
+const char *uaesk_xts_batch_arrangement_name(int id);
 
 #ifdef __cplusplus
 }

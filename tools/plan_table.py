@@ -100,6 +100,9 @@ walk("OCB batch, k records of 64 bytes (positions/thread: threads per workgroup)
 walk("Cipher batch (CBC decrypt / blocks, CFB, OFB, CTR), k records of 64 bytes (positions/thread: threads per workgroup)",
      lambda k: uaes.cipher_batch_plan(max(k, 1), "ctr", 64)[:2] + (0, uaes.cipher_batch_plan(max(k, 1), "ctr", 64)[3]), 1, 1 << 20, 1,
      lambda k: "%9d records (%9.3f MiB)" % (k, k * 64 / MIB))
+walk("XTS batch and sector list, k units of 512 bytes (positions/thread: threads per workgroup)",
+     lambda k: uaes.xts_batch_plan(max(k, 1), 512)[:2] + (0, uaes.xts_batch_plan(max(k, 1), 512)[3]), 1, 1 << 20, 1,
+     lambda k: "%9d units   (%9.3f MiB)" % (k, k * 512 / MIB))
 for dec in (False, True):
     walk("KW %s, one secret of n bytes" % ("unwrap" if dec else "wrap"),
          lambda n: uaes.kw_plan(max(n, 16), unwrap=dec)[:2] + (0, 0), 16, 64 * MIB, 8)
