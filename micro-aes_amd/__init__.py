@@ -55,6 +55,7 @@ EXPORTS = [
     "uaes_eax_encrypt", "uaes_eax_decrypt", "uaes_siv_encrypt", "uaes_siv_decrypt",
     "uaes_eax_encrypt_batch", "uaes_eax_decrypt_batch", "uaes_siv_encrypt_batch", "uaes_siv_decrypt_batch",
     "uaes_debug_plan_eax_siv", "uaes_debug_plan_chain",
+    "uaes_siv_encrypt_v", "uaes_siv_decrypt_v", "uaes_siv_encrypt_batch_v", "uaes_siv_decrypt_batch_v", "uaes_debug_plan_siv_v",
     "uaes_kw_wrap", "uaes_kw_unwrap", "uaes_kw_wrap_batch", "uaes_kw_unwrap_batch", "uaes_debug_plan_kw",
     "uaes_kwp_wrap", "uaes_kwp_unwrap", "uaes_kwp_wrap_batch", "uaes_kwp_unwrap_batch", "uaes_debug_plan_kwp",
     "uaes_ff1_encrypt", "uaes_ff1_decrypt", "uaes_ff1_encrypt_batch", "uaes_ff1_decrypt_batch", "uaes_debug_plan_ff1",
@@ -204,6 +205,12 @@ def engine():
     L.uaes_siv_decrypt_batch.argtypes = [i, vp, sz, sz, vp, sz, vp, vp, vp, vp]
     L.uaes_debug_plan_eax_siv.argtypes = [i, i, sz, sz, C.POINTER(C.c_int)]
     L.uaes_debug_plan_eax_siv.restype = C.c_char_p
+    L.uaes_siv_encrypt_v.argtypes = [i, vp, sz, vp, vp, vp, sz, vp, vp]
+    L.uaes_siv_decrypt_v.argtypes = [i, vp, vp, sz, vp, vp, vp, sz, vp]
+    L.uaes_siv_encrypt_batch_v.argtypes = [i, vp, sz, sz, vp, sz, vp, vp, vp, vp, vp]
+    L.uaes_siv_decrypt_batch_v.argtypes = [i, vp, sz, sz, vp, sz, vp, vp, vp, vp, vp, vp]
+    L.uaes_debug_plan_siv_v.argtypes = [i, sz, sz, sz, C.POINTER(C.c_int)]
+    L.uaes_debug_plan_siv_v.restype = C.c_char_p
     L.uaes_debug_plan_poly1305.restype = C.c_char_p
     L.uaes_debug_plan_chain.argtypes = [i, i, sz, sz, C.POINTER(C.c_int)]
     L.uaes_debug_plan_chain.restype = C.c_char_p
@@ -311,7 +318,7 @@ def engine():
                      "uaes_debug_plan_eax_siv", "uaes_debug_plan_chain", "uaes_debug_plan_kw", "uaes_debug_plan_kwp", "uaes_debug_plan_ff1",
                      "uaes_debug_plan_ff3", "uaes_ff3_maxlen", "uaes_debug_plan_gcmsiv_batch", "uaes_debug_plan_ocb", "uaes_debug_plan_xts",
                      "uaes_debug_gcm_stream_tables", "uaes_debug_plan_ocb_batch", "uaes_debug_plan_gcm_multikey_batch", "uaes_debug_plan_cipher_batch",
-                     "uaes_debug_plan_xaes256gcm_batch", "uaes_debug_plan_xts_batch"):
+                     "uaes_debug_plan_xaes256gcm_batch", "uaes_debug_plan_xts_batch", "uaes_debug_plan_siv_v"):
             getattr(L, n).restype = i
     _lib = L
     return L
@@ -731,6 +738,29 @@ def AES_SIV_decrypt(keys, iv, aData, crtxt, prefill=0):
     return rc, bytes(o)[: len(crtxt)]
 
 
+def _ad_vector(ads):
+    """a list of components as the _v calls take it: (nad, adLens or None, the components back to back)"""
+    ads = [bytes(a) for a in ads]
+    return len(ads), ((C.c_size_t * len(ads))(*[len(a) for a in ads]) if ads else None), _in(b"".join(ads))
+
+
+def AES_SIV_encrypt_v(keys, ads, pntxt):
+    """SIV with RFC 5297's vector of associated data (uaes_siv_encrypt_v): ads = a list of bytes, an empty one still a
+    component, the nonce of nonce-based SIV the last one.  Returns (iv, ciphertext)."""
+    iv, o = _out(16), _out(len(pntxt))
+    _check(engine().uaes_siv_encrypt_v(_bits(keys, 2), _in(keys), *_ad_vector(ads), _in(pntxt), len(pntxt), iv, o),
+           "AES_SIV_encrypt_v")
+    return bytes(iv), bytes(o)[: len(pntxt)]
+
+
+def AES_SIV_decrypt_v(keys, iv, ads, crtxt, prefill=0):
+    """uaes_siv_decrypt_v.  Returns (code, text); on 0x1A the text is the decryption (zeros under the wipe switch)."""
+    o = _out(len(crtxt), prefill)
+    rc = _check(engine().uaes_siv_decrypt_v(_bits(keys, 2), _in(keys), _fixed(iv, 16, "iv"), *_ad_vector(ads),
+                                            _in(crtxt), len(crtxt), o), "AES_SIV_decrypt_v")
+    return rc, bytes(o)[: len(crtxt)]
+
+
 def _records(items, what):
     n = len(items)
     size = len(items[0]) if n else 0
@@ -913,6 +943,46 @@ def siv_batch(keys, aads, texts, decrypt=False, ivs=None, prefill=0):
     def head(n, ml, lv):
         return _bits(keys, 2), _in(keys), n, ml
     return _aead_batch("siv", "AAD (and IV)", [], aads, texts, None, decrypt, ivs, 16, prefill, head, tags_first=True)
+
+
+def siv_batch_v(keys, ads, texts, decrypt=False, ivs=None, prefill=0, lens=None):
+    """SIV with a vector of associated data over many records under one key pair (uaes_siv_*_batch_v): ads[m] = the list
+    of record m's components, the same number and the same lengths in every record; equal-sized texts.  encrypt: returns
+    (ivs, ciphertexts); decrypt (ivs given): returns (code, plaintexts, verdicts).  lens (optional, one per record):
+    record m is the first lens[m] bytes of its text, and the rest of its output slot stays the prefill."""
+    shape = [len(a) for a in ads[0]] if len(ads) else []
+    if any([len(a) for a in rec] != shape for rec in ads):
+        raise ValueError("the same component lengths in every record")
+    adl = (C.c_size_t * len(shape))(*shape) if shape else None
+
+    def head(n, ml, lv):
+        return _bits(keys, 2), _in(keys), n, ml, lv, len(shape), adl
+    n = len(texts)
+    if len(ads) != n or (decrypt and (ivs is None or len(ivs) != n)) or (lens is not None and len(lens) != n):
+        raise ValueError("one component list (and IV and length) per record")
+    if n == 0:
+        return (0, [], []) if decrypt else ([], [])
+    ml, mb = _records(texts, "texts")
+    lv = (C.c_uint32 * n)(*lens) if lens is not None else None
+    name = "uaes_siv_%s_batch_v" % ("decrypt" if decrypt else "encrypt")
+    a = head(n, ml, lv) + (_in(b"".join(b"".join(bytes(x) for x in rec) for rec in ads)),)
+    o = _out(n * ml, prefill)
+    if not decrypt:
+        t = _out(n * 16)
+        _check(getattr(engine(), name)(*a, _in(mb), t, o), name)
+        return _split(bytes(t), 16, n), _split(bytes(o), ml, n)
+    v = _out(n)
+    rc = _check(getattr(engine(), name)(*a, _in(b"".join(ivs)), _in(mb), o, v), name)
+    return rc, _split(bytes(o), ml, n), list(bytes(v)[:n])
+
+
+def siv_v_plan(length, nad, nmsg=1, decrypt=False):
+    """What a SIV call with nad components of associated data would run (uaes_debug_plan_siv_v; nmsg >= 2: a batch):
+    (arrangement, launches, workgroups, rows the components are dealt over), or None for arguments that make no sense.
+    decrypt may also be an int: a direction other than 0 / 1 has no plan."""
+    out = (C.c_int * 3)()
+    name = engine().uaes_debug_plan_siv_v(int(decrypt), length, nad, nmsg, out)
+    return None if name is None else (name.decode(), out[0], out[1], out[2])
 
 
 def eax_siv_plan(siv, length, nmsg=1, decrypt=False):

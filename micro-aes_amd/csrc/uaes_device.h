@@ -336,6 +336,20 @@ int uaesk_eax_batch(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk
 int uaesk_s2v_batch(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek_s2v, const uaesk_rk *ek_ctr,
                     int decrypt, int wipe, const void *aad, size_t aad_bytes,
                     size_t nmsg, size_t msg_bytes, const void *in, void *out, void *ivs, void *verdicts, int *bad);
+/* S2V over nad components of associated data (RFC 5297 section 2.4).  uaesk_s2v_v: component i is aad[ends[i - 1] ..
+ * ends[i]) with ends = nad running totals of the lengths, uint64 each, device memory, 8-byte aligned (nad <=
+ * UAES_S2V_AD_MAX; an empty component is one); ctr != 0: a text of <= UAES_EAX_SIV_SMALL_MAX bytes and CTR in the same
+ * launch (uaesk_s2v_small's part), ctr == 0: the chains alone, over `in` (encrypt) or the plaintext in `out` (decrypt;
+ * uaesk_s2v_macs' part); res48: the status at +0 (decrypt), V at +16 (encrypt).
+ * uaesk_s2v_batch_v: uaesk_s2v_batch with every record's AAD slot cut into nad <= UAES_S2V_BATCH_AD_MAX components of
+ * ad_lens[i] bytes (host memory) and lens as uaesk_ccm_batch has it (NULL, or 4-byte aligned device memory). */
+int uaesk_s2v_v(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek_s2v, const uaesk_rk *ek_ctr,
+                int decrypt, int ctr, const uint8_t *iv16, const void *aad, const void *ends, unsigned nad,
+                const void *in, size_t len, void *out, void *res48);
+int uaesk_s2v_batch_v(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek_s2v, const uaesk_rk *ek_ctr,
+                      int decrypt, int wipe, const void *aad, unsigned nad, const size_t *ad_lens,
+                      size_t nmsg, size_t msg_bytes, const void *lens, const void *in, void *out, void *ivs,
+                      void *verdicts, int *bad);
 
 /* AES key wrap, RFC 3394 (pad 0; AES_KEY_wrap / AES_KEY_unwrap, micro_aes.c:1829-1894), and key wrap with padding,
  * RFC 5649 (pad 1; the reference has none): uaes_kw.hip; device pointers at any byte offset.  ek / dk: encryption /

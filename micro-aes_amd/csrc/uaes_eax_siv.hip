@@ -101,22 +101,22 @@ __device__ __forceinline__ void cmac_subkeys(const RowLane<NR> &L, u32 &k1c, u32
 
 /* ---- chains ----------------------------------------------------------------------------------------------------- */
 
-/* m <- Enc(m ^ X_i) over nblk whole blocks at p */
-template <int NR>
+/* m <- Enc(m ^ X_i) over nblk whole blocks at p (CH: row_walk's chunk; k_s2v_batch_v, short of registers, asks for 8) */
+template <int NR, u32 CH = ROW_CH>
 __device__ __forceinline__ u32 cbc_blocks(u32 m, const unsigned char *p, u64 nblk, const RowLane<NR> &L)
 {
-    if ((((uintptr_t)p) & 3u) == 0) row_walk<true>(p, nblk, L.c, [&](u64, u32 x) { m = row_encrypt<NR>(m ^ x, L); });
-    else row_walk<false>(p, nblk, L.c, [&](u64, u32 x) { m = row_encrypt<NR>(m ^ x, L); });
+    if ((((uintptr_t)p) & 3u) == 0) row_walk<true, CH>(p, nblk, L.c, [&](u64, u32 x) { m = row_encrypt<NR>(m ^ x, L); });
+    else row_walk<false, CH>(p, nblk, L.c, [&](u64, u32 x) { m = row_encrypt<NR>(m ^ x, L); });
     return m;
 }
 
 /* the CMAC chain continued over len >= 1 bytes at p: whole blocks, then the last one with K1, or 10* and K2 (cMac :576-590) */
-template <int NR>
+template <int NR, u32 CH = ROW_CH>
 __device__ __forceinline__ u32 cmac_more(u32 m, const unsigned char *p, u64 len, const RowLane<NR> &L, u32 k1c, u32 k2c)
 {
     const u32 s = (u32)((len - 1) % 16) + 1;
     const u64 full = (len - s) / 16;
-    m = cbc_blocks<NR>(m, p, full, L);
+    m = cbc_blocks<NR, CH>(m, p, full, L);
     u32 l = row_load(p + 16 * full, s, L.c);
     l ^= s < 16 ? pad_col(s, L.c) ^ k2c : k1c;
     return row_encrypt<NR>(m ^ l, L);
@@ -219,13 +219,13 @@ __device__ __forceinline__ void ctr_rows(const uaesk_ctr &ctr, const unsigned ch
 }
 
 /* the same in one row, block after block (batches: a row per record) */
-template <int NR, bool A4>
+template <int NR, bool A4, u32 CH = ROW_CH>
 __device__ __forceinline__ void ctr_row(const uaesk_ctr &ctr, const unsigned char *in, unsigned char *out, u64 len,
                                         const RowLane<NR> &L)
 {
     const u64 full = len / 16;
     const u32 rem = (u32)(len % 16);
-    row_walk<A4>(in, full, L.c, [&](u64 i, u32 x) {
+    row_walk<A4, CH>(in, full, L.c, [&](u64 i, u32 x) {
         row_store_full<A4>(out + 16 * i, x ^ row_encrypt<NR>(ctr_col(ctr, i, L.c), L), L.c);
     });
     if (rem) {
@@ -260,14 +260,14 @@ __device__ __forceinline__ u32 eax_text_enc(const uaesk_ctr &ctr, const unsigned
 
 /* SIV decryption of one record in one row: P_i = C_i ^ Enc_ctr(V' + i) written, and S2V's chain over P in the same
  * pass (Ls = K_s2v, Lc = K_ctr); returns the synthesized V */
-template <int NR, bool A4>
+template <int NR, bool A4, u32 CH = ROW_CH>
 __device__ __forceinline__ u32 s2v_text_dec(const uaesk_ctr &ctr, const unsigned char *in, unsigned char *out, u64 len,
                                             u32 y, const RowLane<NR> &Ls, const RowLane<NR> &Lc, u32 k1c, u32 k2c)
 {
     const u32 c = Ls.c;
     u32 m = 0, ks = len ? row_encrypt<NR>(ctr_col(ctr, 0, c), Lc) : 0u;
     const u64 lead = s2v_lead(len);
-    row_walk<A4>(in, lead, c, [&](u64 i, u32 x) {
+    row_walk<A4, CH>(in, lead, c, [&](u64 i, u32 x) {
         const u32 p = x ^ ks;
         row_store_full<A4>(out + 16 * i, p, c);
         m ^= p;
@@ -557,6 +557,159 @@ __global__ __launch_bounds__(UAES_WG) void k_s2v_batch(uaesk_rk rk, uaesk_rk rk2
     }
 }
 
+/* ---- S2V over a vector of associated data (RFC 5297 section 2.4) -------------------------------------------------- */
+/* Y_n = dbl^n(CMAC(0^128)) ^ XOR_i dbl^(n-i)(CMAC(S_i)), folded as Y_0 = CMAC(0^128), Y_i = dbl(Y_{i-1}) ^ CMAC(S_i).
+ * The component CMACs are independent chains; only the fold is serial, and it is doublings.  A component may be empty:
+ * it still is one, CMAC("") = Enc(10* ^ K2).  No component at all leaves Y_0, which is s2v_head without AAD; one
+ * non-empty component gives s2v_head's Y. */
+
+/* LDS behind k_s2v_small's: the CMAC of every component, sixteen bytes each */
+#define E4V_MACS  E4_LDS
+#define E4V_LDS   (E4_LDS + 16u * (u32)UAES_S2V_AD_MAX)
+/* the rows of the workgroup that the components are dealt over: all but wave 1's four, which walk the text */
+#define S2V_V_ROWS (SMALL_WG / 16u - 4u)
+
+/* CMAC of a whole string, the empty one included */
+template <int NR, u32 CH = ROW_CH>
+__device__ __forceinline__ u32 cmac_any(const unsigned char *p, u64 len, const RowLane<NR> &L, u32 k1c, u32 k2c)
+{
+    if (!len) return row_encrypt<NR>(pad_col(0u, L.c) ^ k2c, L);
+    return cmac_more<NR, CH>(0u, p, len, L, k1c, k2c);
+}
+
+/* SIV of one message with nad components (K_s2v = rk, K_ctr = rk2); component i is aad[ends[i - 1] .. ends[i]) (ends:
+ * nad running totals, 8-byte aligned).  Row r of the workgroup (wave 1's rows apart) takes components r, r + S2V_V_ROWS,
+ * ... and leaves their CMACs in LDS; wave 1 walks the text's leading blocks meanwhile, then folds the CMACs in order and
+ * finishes as k_s2v_small does.  CTR: the text is short and CTR runs here, before (decrypt) or after (encrypt) the
+ * chains, over all rows; without it this is the chains of a longer text (k_s2v_macs' part: CTR by the host, a decrypt's
+ * plaintext already in `out`).  V goes to iv_out (encrypt), *status = 0 / 0x1A (decrypt). */
+template <int NR, bool DEC, bool CTR>
+__global__ __launch_bounds__(SMALL_WG) void k_s2v_v(uaesk_rk rk, uaesk_rk rk2, uaesk_tables tb, uint4 iv4,
+                                                    const unsigned char *aad, const u64 *ends, u32 nad,
+                                                    const unsigned char *in, u64 len, unsigned char *out,
+                                                    unsigned char *iv_out, int *status)
+{
+    for (u32 i = threadIdx.x; i < 60u; i += blockDim.x) ((u32 *)(uaes_lds + E4_KEY2))[i] = rk2.w[i];
+    row4_fill_tables(tb.te0, rk);                            /* (its barrier covers the second schedule too) */
+    const RowLane<NR> L = row4_lane<NR>(), Lc = row4_lane<NR>(E4_KEY2);
+    u32 k1c, k2c;
+    cmac_subkeys<NR>(L, k1c, k2c);
+    u32 *xch = (u32 *)(uaes_lds + E4_XCH), *macs = (u32 *)(uaes_lds + E4V_MACS);
+    const u32 wave = threadIdx.x >> 6, row = threadIdx.x >> 4;
+    const bool put = (threadIdx.x & 63u) < 16u && (threadIdx.x & 3u) == 0;
+    if (DEC && CTR) {
+        u32 v[4] = { iv4.x, iv4.y, iv4.z & ~0x80u, iv4.w & ~0x80u };
+        ctr_rows<NR>(ctr_of(v), in, out, len, Lc);
+        __syncthreads();                                     /* the plaintext is in memory for the chains */
+    }
+    const unsigned char *p = DEC ? out : in;
+    u32 m = 0, y = 0;
+    if (wave == 1) {
+        m = cbc_blocks<NR>(0u, p, s2v_lead(len), L);
+        y = row_encrypt<NR>(k1c, L);                         /* Y_0 = CMAC of one zero block = Enc(K1) */
+    } else {
+        for (u32 i = row < 4u ? row : row - 4u; i < nad; i += S2V_V_ROWS) {
+            const u64 at = i ? ends[i - 1] : 0;
+            const u32 c = cmac_any<NR>(aad + at, ends[i] - at, L, k1c, k2c);
+            if ((threadIdx.x & 3u) == 0) macs[4u * i + L.c] = c;
+        }
+    }
+    __syncthreads();
+    if (wave == 1) {
+        u32 b[4];
+        row_gather(y, b);
+        for (u32 i = 0; i < nad; ++i) {
+            dbl_be(b);
+#pragma unroll
+            for (u32 k = 0; k < 4; ++k) b[k] ^= macs[4u * i + k];
+        }
+        const u32 v = s2v_text_end<NR>(m, p, len, row_pick(b, L.c), L, k1c, k2c);
+        if (put) xch[4 + L.c] = v;
+    }
+    __syncthreads();
+    u32 v[4];
+#pragma unroll
+    for (u32 k = 0; k < 4; ++k) v[k] = xch[4 + k];
+    if (DEC) {
+        if (threadIdx.x == 0)
+            *status = ((v[0] ^ iv4.x) | (v[1] ^ iv4.y) | (v[2] ^ iv4.z) | (v[3] ^ iv4.w)) ? 0x1A : 0;
+    } else {
+        if (threadIdx.x < 4) ((u32 *)iv_out)[threadIdx.x] = v[threadIdx.x];
+        if (CTR) {
+            v[2] &= ~0x80u;
+            v[3] &= ~0x80u;
+            ctr_rows<NR>(ctr_of(v), in, out, len, Lc);
+        }
+    }
+}
+
+/* the lengths of a batch record's components, by value */
+struct s2v_adl { u64 n[UAES_S2V_BATCH_AD_MAX]; };
+
+/* k_s2v_batch with every record's AAD slot cut into the same nad components and a length per record: record m is the
+ * first lens[m] bytes of its slot (lens NULL: msg_bytes; a longer entry counts as msg_bytes), the rest of its output
+ * slot is not written.  The record's row walks its components one after another. */
+template <int NR, bool DEC, bool A4>
+__global__ __launch_bounds__(UAES_WG) void k_s2v_batch_v(uaesk_rk rk, uaesk_rk rk2, uaesk_tables tb, int wipe,
+                                                         const unsigned char *aad, u64 aad_bytes, u32 nad, s2v_adl adl,
+                                                         u64 nmsg, u64 msg_bytes, const u32 *lens,
+                                                         const unsigned char *in, unsigned char *out,
+                                                         unsigned char *ivs, unsigned char *verdicts, int *bad)
+{
+    for (u32 i = threadIdx.x; i < 60u; i += blockDim.x) ((u32 *)(uaes_lds + E4_KEY2))[i] = rk2.w[i];
+    row4_fill_tables(tb.te0, rk);
+    const RowLane<NR> L = row4_lane<NR>(), Lc = row4_lane<NR>(E4_KEY2);
+    u32 k1c, k2c;
+    cmac_subkeys<NR>(L, k1c, k2c);
+    constexpr u32 BCH = 8;                                   /* row_walk's chunk: two key schedules leave no room for 2 x 16 blocks in flight */
+    u32 *y0 = (u32 *)(uaes_lds + E4_XCH);                    /* Y_0 = CMAC(0^128) = Enc(K1), the same for every record: kept */
+    y0[L.c] = row_encrypt<NR>(k1c, L);                       /* in LDS, not in a register (every lane of a column writes the same word) */
+    __syncthreads();
+    const u64 rows = blockDim.x >> 4;
+    for (u64 m = (u64)blockIdx.x * rows + (threadIdx.x >> 4); m < nmsg; m += (u64)gridDim.x * rows) {
+        u32 len = (u32)msg_bytes;                            /* (the host layer refuses slots above UINT32_MAX) */
+        if (lens) { len = lens[m]; if (len > msg_bytes) len = (u32)msg_bytes; }
+        const unsigned char *a = aad + m * aad_bytes;
+        u32 y = y0[L.c];
+        for (u32 i = 0; i < nad; ++i) {
+            u64 n = 0;
+#pragma unroll
+            for (u32 k = 0; k < UAES_S2V_BATCH_AD_MAX; ++k)
+                if (k == i) n = adl.n[k];
+            u32 b[4];
+            row_gather(y, b);
+            dbl_be(b);
+            y = row_pick(b, L.c) ^ cmac_any<NR, BCH>(a, n, L, k1c, k2c);
+            a += n;
+        }
+        const unsigned char *src = in + m * msg_bytes;
+        unsigned char *dst = out + m * msg_bytes;
+        unsigned char *ivp = ivs + 16 * m;
+        u32 vb[4];
+        if (!DEC) {
+            const u32 chain = cbc_blocks<NR, BCH>(0u, src, s2v_lead(len), L);
+            const u32 v = s2v_text_end<NR>(chain, src, len, y, L, k1c, k2c);
+            row_put(ivp, v, 16, L.c);
+            row_gather(v, vb);
+            vb[2] &= ~0x80u;
+            vb[3] &= ~0x80u;
+            ctr_row<NR, A4, BCH>(ctr_of(vb), src, dst, len, Lc);
+        } else {
+            const u32 iv = row_load(ivp, 16, L.c);
+            row_gather(iv, vb);
+            vb[2] &= ~0x80u;
+            vb[3] &= ~0x80u;
+            const u32 v = s2v_text_dec<NR, A4, BCH>(ctr_of(vb), src, dst, len, y, L, Lc, k1c, k2c);
+            u32 d[4];
+            row_gather(v ^ iv, d);
+            const bool ok = (d[0] | d[1] | d[2] | d[3]) == 0;
+            row_verdict((threadIdx.x & 15u) == 0, verdicts, m, ok, bad);
+            if (!ok && wipe)
+                for (u32 i = 0; i < len; i += 16) row_put(dst + i, 0u, len - i < 16 ? len - i : 16u, L.c);
+        }
+    }
+}
+
 /* ---- launchers ---------------------------------------------------------------------------------------------------- */
 static uint4 uint4_of(const uint8_t *b)
 {
@@ -683,6 +836,54 @@ extern "C" int uaesk_s2v_batch(void *stream, const uaesk_tables *tb, int nr, con
     return 0;
 }
 
+template <int NR>
+static int launch_s2v_v(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *ek, const uaesk_rk *ek2, int decrypt, int ctr,
+                        uint4 iv, const void *aad, const void *ends, unsigned nad, const void *in, size_t len, void *out,
+                        void *res)
+{
+    return with_bool(decrypt, [&](auto DEC) { return with_bool(ctr, [&](auto CTR) {
+        return uaesk_launch(k_s2v_v<NR, decltype(DEC)::value, decltype(CTR)::value>, 1, SMALL_WG, E4V_LDS, st, *ek, *ek2, *tb, iv,
+                            aad, ends, nad, in, len, out, (unsigned char *)res + 16, res); }); });
+}
+
+extern "C" int uaesk_s2v_v(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek_s2v, const uaesk_rk *ek_ctr,
+                           int decrypt, int ctr, const uint8_t *iv16, const void *aad, const void *ends, unsigned nad,
+                           const void *in, size_t len, void *out, void *res48)
+{
+    const uint4 iv = uint4_of(iv16);
+    if (nad > UAES_S2V_AD_MAX || (nad && (!ends || ((uintptr_t)ends & 7u))) || (ctr && len > UAES_EAX_SIV_SMALL_MAX))
+        return (int)hipErrorInvalidValue;
+    DISPATCH_NR(nr, return (launch_s2v_v<NR>(S(stream), tb, ek_s2v, ek_ctr, decrypt, ctr, iv, aad, ends, nad, in, len, out, res48)));
+    return 0;
+}
+
+template <int NR>
+static int launch_s2v_batch_v(hipStream_t st, const uaesk_tables *tb, const uaesk_rk *ek, const uaesk_rk *ek2, int decrypt,
+                              int wipe, const void *aad, size_t aad_bytes, unsigned nad, const s2v_adl &adl, size_t nmsg,
+                              size_t msg_bytes, const void *lens, const void *in, void *out, void *ivs, void *verdicts, int *bad)
+{
+    const RowShape s = uaesk_row_shape(nmsg);
+    return with_bool(decrypt, [&](auto DEC) { return with_bool(uaesk_rows_a4(in, out, msg_bytes), [&](auto A4) {
+        return uaesk_launch(k_s2v_batch_v<NR, decltype(DEC)::value, decltype(A4)::value>, s.grid, s.wg, E4_LDS, st, *ek, *ek2, *tb, wipe,
+                            aad, aad_bytes, nad, adl, nmsg, msg_bytes, lens, in, out, ivs, verdicts, bad); }); });
+}
+
+extern "C" int uaesk_s2v_batch_v(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek_s2v, const uaesk_rk *ek_ctr,
+                                 int decrypt, int wipe, const void *aad, unsigned nad, const size_t *ad_lens,
+                                 size_t nmsg, size_t msg_bytes, const void *lens, const void *in, void *out, void *ivs,
+                                 void *verdicts, int *bad)
+{
+    s2v_adl adl;
+    size_t aad_bytes = 0;
+    if (nad > UAES_S2V_BATCH_AD_MAX || (nad && !ad_lens) || ((uintptr_t)lens & 3u)) return (int)hipErrorInvalidValue;
+    memset(&adl, 0, sizeof adl);
+    for (unsigned i = 0; i < nad; ++i) { adl.n[i] = ad_lens[i]; aad_bytes += ad_lens[i]; }
+    if (nmsg == 0) return 0;
+    DISPATCH_NR(nr, return (launch_s2v_batch_v<NR>(S(stream), tb, ek_s2v, ek_ctr, decrypt, wipe, aad, aad_bytes, nad, adl, nmsg,
+                                                   msg_bytes, lens, in, out, ivs, verdicts, bad)));
+    return 0;
+}
+
 /* ---- the plan (uaes_plan.h) --------------------------------------------------------------------------------------- */
 extern "C" int uaesk_plan_eax_siv(int siv, int dir, size_t len, size_t nmsg, uaes_plan *p)
 {
@@ -705,8 +906,28 @@ extern "C" int uaesk_plan_eax_siv(int siv, int dir, size_t len, size_t nmsg, uae
     return 0;
 }
 
+/* the _v calls: steps = the rows a call's components are dealt over (a batch record's row walks its own) */
+extern "C" int uaesk_plan_siv_v(int dir, size_t len, size_t nad, size_t nmsg, uaes_plan *p)
+{
+    memset(p, 0, sizeof *p);
+    if ((dir != 0 && dir != 1) || nad > (nmsg > 1 ? UAES_S2V_BATCH_AD_MAX : UAES_S2V_AD_MAX)) return (int)hipErrorInvalidValue;
+    if (nmsg > 1) {
+        p->arrangement = UAES_S2V_BATCH_V;
+        p->launches = 1;
+        p->grid = uaesk_row_shape(nmsg).grid;
+        p->steps = 1;
+        return 0;
+    }
+    p->grid = 1;
+    p->steps = S2V_V_ROWS;
+    p->arrangement = len <= UAES_EAX_SIV_SMALL_MAX ? UAES_S2V_SMALL_V : UAES_S2V_LONG_V;
+    p->launches = len <= UAES_EAX_SIV_SMALL_MAX ? 1 : 2;
+    return 0;
+}
+
 extern "C" const char *uaesk_eax_siv_arrangement_name(int id)
 {
-    static const char *const names[] = { "eax.small", "eax.long", "eax.batch", "s2v.small", "s2v.long", "s2v.batch" };
-    return id >= 0 && id < 6 ? names[id] : "?";
+    static const char *const names[] = { "eax.small", "eax.long", "eax.batch", "s2v.small", "s2v.long", "s2v.batch",
+                                         "s2v.small.v", "s2v.long.v", "s2v.batch.v" };
+    return id >= 0 && id < 9 ? names[id] : "?";
 }

@@ -671,42 +671,71 @@ static int siv_keys(keysched *k1, keysched *k2, const uint8_t *keys, int keybits
     return expand_key(k2, keys + keybits / 8, keybits);
 }
 
-static int siv_common(int keybits, const uint8_t *keys, int decrypt, uint8_t *iv, const void *aData, size_t aDataLen,
-                      const void *in, size_t len, void *outp)
+typedef char uaes_siv_ad_limits_are_the_kernels[UAES_SIV_AD_MAX == UAES_S2V_AD_MAX && UAES_SIV_BATCH_AD_MAX == UAES_S2V_BATCH_AD_MAX ? 1 : -1];
+
+/* the components of SIV's associated data: at most `most` of them, their lengths, the bytes they add up to */
+static int siv_components(size_t nad, const size_t *adLens, size_t most, size_t *total)
+{
+    size_t i;
+    *total = 0;
+    if (nad > most) return fail(UAES_E_ARG, "S2V takes at most %zu components here (got %zu)", most, nad);
+    if (nad && !adLens) return fail(UAES_E_ARG, "NULL adLens with nad != 0");
+    for (i = 0; i < nad; ++i) {
+        if (adLens[i] > (size_t)-1 - 64 - *total) return fail(UAES_E_ARG, "the component lengths overflow");
+        *total += adLens[i];
+    }
+    return 0;
+}
+
+/* aData = nad components back to back.  vec: the _v calls, whose kernels (k_s2v_v) deal the components over the
+ * workgroup's rows and get the running totals of the lengths through the scratch, behind the components; else the
+ * one-aData calls and their kernels, nad = 0 or 1. */
+static int siv_common(int keybits, const uint8_t *keys, int decrypt, uint8_t *iv, int vec, size_t nad, const size_t *adLens,
+                      const void *aData, const void *in, size_t len, void *outp)
 {
     context *c;
     lane *L;
     KEYSCHED(k1);
     KEYSCHED(k2);
     io_plan io;
-    const void *d_aad;
-    size_t off = 0;
+    const void *d_aad, *d_ends = NULL;
+    size_t off = 0, total, i;
     int rc, k, status = 0;
     uint8_t v[16], res[32];
+    uint64_t ends[UAES_SIV_AD_MAX];
+    if ((rc = siv_components(nad, adLens, UAES_SIV_AD_MAX, &total)) != 0) return rc;
     if ((rc = siv_keys(&k1, &k2, keys, keybits)) != 0) return rc;
     if (!iv || (len && (!in || !outp))) return fail(UAES_E_ARG, "NULL pointer");
-    if (aDataLen && !aData) return fail(UAES_E_ARG, "NULL aData with aDataLen != 0");
+    if (total && !aData) return fail(UAES_E_ARG, "NULL aData with aDataLen != 0");
     if (decrypt && (rc = iv_read(v, iv)) != 0) return rc;
     if (host_take(in, outp, len, 1) && !is_device_ptr(aData) && !is_device_ptr(iv)) {
         const uaesh_key h1 = host_key(&k1), h2 = host_key(&k2);
-        rc = uaesh_siv(&h1, &h2, decrypt, v, (const uint8_t *)aData, aDataLen, (const uint8_t *)in, len, (uint8_t *)outp);
+        rc = uaesh_siv(&h1, &h2, decrypt, v, nad, adLens, (const uint8_t *)aData, (const uint8_t *)in, len, (uint8_t *)outp);
         if (!decrypt) memcpy(iv, v, 16);
         if (rc && len && wipe_on_auth_failure()) memset(outp, 0, len);       /* (the default leaves the text, as the reference does) */
         return host_result(rc);
     }
     if ((rc = enter(&c, &L)) != 0) return rc;
-    if ((rc = lane_scratch(L, SIDE(aDataLen), SCRATCH_OTHER)) != 0) goto out;
-    if ((rc = side_in(L, &off, aData, aDataLen, &d_aad)) != 0) goto out;
+    if ((rc = lane_scratch(L, SIDE(total) + (vec ? SIDE(nad * sizeof *ends) : 0), SCRATCH_OTHER)) != 0) goto out;
+    if ((rc = side_in(L, &off, aData, total, &d_aad)) != 0) goto out;
+    if (vec) {
+        for (i = 0; i < nad; ++i) ends[i] = (i ? ends[i - 1] : 0) + adLens[i];
+        if ((rc = side_in(L, &off, ends, nad * sizeof *ends, &d_ends)) != 0) goto out;
+    }
     if ((rc = plan_io(L, len ? in : NULL, len, len ? outp : NULL, len, &io)) != 0) goto out;
     if (len <= UAES_EAX_SIV_SMALL_MAX) {                  /* s2v.small: one launch */
-        k = uaesk_s2v_small(L->stream, &c->tb, k1.nr, &k1.ek, &k2.ek, decrypt, decrypt ? v : NULL, d_aad, aDataLen,
-                            io.din, len, io.dout, (char *)L->d_status + 16, decrypt ? L->d_status : NULL);
+        k = vec ? uaesk_s2v_v(L->stream, &c->tb, k1.nr, &k1.ek, &k2.ek, decrypt, 1, decrypt ? v : NULL, d_aad, d_ends, (unsigned)nad,
+                              io.din, len, io.dout, L->d_status)
+                : uaesk_s2v_small(L->stream, &c->tb, k1.nr, &k1.ek, &k2.ek, decrypt, decrypt ? v : NULL, d_aad, total,
+                                  io.din, len, io.dout, (char *)L->d_status + 16, decrypt ? L->d_status : NULL);
         if ((rc = launched("siv", k)) != 0) goto out;
         if ((rc = lane_fetch(L, res, L->d_status, sizeof res)) != 0) goto out;
         io.drained = 1;
     } else if (!decrypt) {                                /* s2v.long: the chains, one fetch, then CTR(V') */
         uaesk_ctr ctr;
-        k = uaesk_s2v_macs(L->stream, &c->tb, k1.nr, &k1.ek, 0, NULL, d_aad, aDataLen, io.din, len, L->d_status);
+        k = vec ? uaesk_s2v_v(L->stream, &c->tb, k1.nr, &k1.ek, &k2.ek, 0, 0, NULL, d_aad, d_ends, (unsigned)nad, io.din, len,
+                              io.dout, L->d_status)
+                : uaesk_s2v_macs(L->stream, &c->tb, k1.nr, &k1.ek, 0, NULL, d_aad, total, io.din, len, L->d_status);
         if ((rc = launched("siv", k)) != 0) goto out;
         if ((rc = lane_fetch(L, res, L->d_status, sizeof res)) != 0) goto out;
         memcpy(v, res + 16, 16);
@@ -724,7 +753,9 @@ static int siv_common(int keybits, const uint8_t *keys, int decrypt, uint8_t *iv
         make_ctr(&ctr, cv, 0);
         k = uaesk_ctr_xcrypt(L->stream, &c->tb, k2.nr, &k2.ek, &ctr, io.din, io.dout, len, NULL);
         if ((rc = launched("siv ctr", k)) != 0) goto out;
-        k = uaesk_s2v_macs(L->stream, &c->tb, k1.nr, &k1.ek, 1, v, d_aad, aDataLen, io.dout, len, L->d_status);
+        k = vec ? uaesk_s2v_v(L->stream, &c->tb, k1.nr, &k1.ek, &k2.ek, 1, 0, v, d_aad, d_ends, (unsigned)nad, io.din, len,
+                              io.dout, L->d_status)
+                : uaesk_s2v_macs(L->stream, &c->tb, k1.nr, &k1.ek, 1, v, d_aad, total, io.dout, len, L->d_status);
         if ((rc = launched("siv", k)) != 0) goto out;
         if ((rc = lane_fetch(L, res, L->d_status, sizeof res)) != 0) goto out;
         io.drained = 1;
@@ -741,16 +772,29 @@ out:
     DONE(L, rc);
 }
 
+/* the one-aData calls: an empty AAD is no header unit (micro_aes.c:1333-1344), so it is no component */
 int uaes_siv_encrypt(int keybits, const uint8_t *keys, const void *aData, size_t aDataLen,
                      const void *pntxt, size_t ptextLen, uint8_t iv[16], void *crtxt)
 {
-    return siv_common(keybits, keys, 0, iv, aData, aDataLen, pntxt, ptextLen, crtxt);
+    return siv_common(keybits, keys, 0, iv, 0, aDataLen ? 1 : 0, &aDataLen, aData, pntxt, ptextLen, crtxt);
 }
 
 int uaes_siv_decrypt(int keybits, const uint8_t *keys, const uint8_t iv[16], const void *aData, size_t aDataLen,
                      const void *crtxt, size_t crtxtLen, void *pntxt)
 {
-    return siv_common(keybits, keys, 1, (uint8_t *)iv, aData, aDataLen, crtxt, crtxtLen, pntxt);
+    return siv_common(keybits, keys, 1, (uint8_t *)iv, 0, aDataLen ? 1 : 0, &aDataLen, aData, crtxt, crtxtLen, pntxt);
+}
+
+int uaes_siv_encrypt_v(int keybits, const uint8_t *keys, size_t nad, const size_t *adLens, const void *aData,
+                       const void *pntxt, size_t ptextLen, uint8_t iv[16], void *crtxt)
+{
+    return siv_common(keybits, keys, 0, iv, 1, nad, adLens, aData, pntxt, ptextLen, crtxt);
+}
+
+int uaes_siv_decrypt_v(int keybits, const uint8_t *keys, const uint8_t iv[16], size_t nad, const size_t *adLens,
+                       const void *aData, const void *crtxt, size_t crtxtLen, void *pntxt)
+{
+    return siv_common(keybits, keys, 1, (uint8_t *)iv, 1, nad, adLens, aData, crtxt, crtxtLen, pntxt);
 }
 
 /* ---- AEAD record batches: EAX, SIV, CCM, GCM-SIV, multi-key GCM, XAES-256-GCM and OCB ----
@@ -773,6 +817,8 @@ struct aead_rows {
     void          *out;
     struct { const void *p; size_t each; } side[AB_NSIDE];   /* the caller's arrays and their bytes per record; 0: the
                                                               * call has no such array */
+    size_t         nad;                 /* SIV's _v batches: every record's AAD slot is these components */
+    const size_t  *ad_lens;
     int          (*launch)(const aead_rows *b, context *c, lane *L, const keysched *const ks[2], const row_array *a, const row_text *t);
 };
 
@@ -876,6 +922,50 @@ int uaes_siv_decrypt_batch(int keybits, const uint8_t *keys, size_t nmsg, size_t
 {
     return eax_siv_batch(1, 1, keybits, keys, nmsg, msg_bytes, NULL, 0, aData, aad_bytes, crtxt, pntxt, (uint8_t *)ivs,
                          verdicts);
+}
+
+/* SIV batches with the component vector and a length per record (k_s2v_batch_v): every record's AAD slot, sum(adLens)
+ * bytes, is cut into the same nad components.  What this call checks comes first: the components, the slot size, a
+ * device array of lengths; then aead_rows_run's order. */
+static int siv_batch_v_launch(const aead_rows *b, context *c, lane *L, const keysched *const ks[2], const row_array *a, const row_text *t)
+{
+    return uaesk_s2v_batch_v(L->stream, &c->tb, ks[0]->nr, &ks[0]->ek, &ks[1]->ek, b->decrypt, wipe_on_auth_failure(), a[AB_AAD].d,
+                             (unsigned)b->nad, b->ad_lens, b->nmsg, b->msg_bytes, a[AB_LENS].d, t->d_in, t->d_out, a[AB_TAGS].d,
+                             a[AB_VERDICTS].d, L->d_status);
+}
+
+static int siv_batch_v(int decrypt, int keybits, const uint8_t *keys, size_t nmsg, size_t msg_bytes, const uint32_t *lens,
+                       size_t nad, const size_t *adLens, const void *aData, const void *in, void *outp, uint8_t *ivs,
+                       uint8_t *verdicts)
+{
+    aead_rows b = {
+        .name = "siv batch", .launch = siv_batch_v_launch, .nkeys = 2, .keybits = keybits, .key = keys, .decrypt = decrypt,
+        .nmsg = nmsg, .msg_bytes = msg_bytes, .in = in, .out = outp, .nad = nad, .ad_lens = adLens,
+        .side = { [AB_LENS] = { lens, lens ? sizeof *lens : 0 }, [AB_TAGS] = { ivs, 16 }, [AB_VERDICTS] = { verdicts, decrypt } } };
+    size_t total;
+    int rc;
+    if ((rc = siv_components(nad, adLens, UAES_SIV_BATCH_AD_MAX, &total)) != 0) return rc;
+    if (msg_bytes > UINT32_MAX)
+        return fail(UAES_E_ARG, "a batch record holds at most %u bytes (got %zu)", UINT32_MAX, msg_bytes);
+    if (lens && ((uintptr_t)lens & 3u) && is_device_ptr(lens))
+        return fail(UAES_E_ARG, "a device array of lengths must be 4-byte aligned");
+    b.side[AB_AAD].p = aData;
+    b.side[AB_AAD].each = total;
+    return aead_rows_run(&b);
+}
+
+int uaes_siv_encrypt_batch_v(int keybits, const uint8_t *keys, size_t nmsg, size_t msg_bytes, const uint32_t *lens,
+                             size_t nad, const size_t *adLens, const void *aData,
+                             const void *pntxt, uint8_t *ivs, void *crtxt)
+{
+    return siv_batch_v(0, keybits, keys, nmsg, msg_bytes, lens, nad, adLens, aData, pntxt, crtxt, ivs, NULL);
+}
+
+int uaes_siv_decrypt_batch_v(int keybits, const uint8_t *keys, size_t nmsg, size_t msg_bytes, const uint32_t *lens,
+                             size_t nad, const size_t *adLens, const void *aData,
+                             const uint8_t *ivs, const void *crtxt, void *pntxt, uint8_t *verdicts)
+{
+    return siv_batch_v(1, keybits, keys, nmsg, msg_bytes, lens, nad, adLens, aData, crtxt, pntxt, (uint8_t *)ivs, verdicts);
 }
 
 /* CCM batches (k_ccm_batch, uaes_mac.hip): the nonce and tag lengths are arguments, the tags are packed, tagLen bytes

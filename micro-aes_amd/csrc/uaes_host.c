@@ -619,19 +619,28 @@ int uaesh_eax(const uaesh_key *k, int decrypt, const uint8_t *nonce, size_t nonc
     return rc;
 }
 
-/* V = S2V(aad, p): an empty AAD is no header unit at all; Y is XORed into the last 16 bytes of a text of 16 bytes or
- * more, a shorter one gets dbl(Y) ^ pad(p) */
-static void s2v(const uaesh_key *k, const uint8_t *aad, size_t aad_len, const uint8_t *p, size_t len, uint8_t v[16])
+/* V = S2V(S_1 .. S_nad, p), RFC 5297 section 2.4: the nad components lie back to back at aad, ad_lens[i] bytes each; an
+ * empty one is a component all the same (CMAC("") = Enc(10* ^ K2)), nad == 0 is no header unit at all.  Y is XORed
+ * into the last 16 bytes of a text of 16 bytes or more, a shorter one gets dbl(Y) ^ pad(p) */
+static void s2v(const uaesh_key *k, size_t nad, const size_t *ad_lens, const uint8_t *aad, const uint8_t *p, size_t len,
+                uint8_t v[16])
 {
     cmac_keys s;
     uint8_t y[16] = { 0 }, d[16], t[16];
-    size_t i;
+    size_t i, c;
     cmac_keys_of(k, &s);
     xor16(y, y, s.k1);
     uaesh_encrypt(k->ek, k->nr, y, y);                                  /* CMAC(0^128) */
-    if (aad_len) {
+    for (c = 0; c < nad; ++c) {
         memset(d, 0, 16);
-        cmac_continue(k, &s, d, aad, aad_len);
+        if (ad_lens[c]) {
+            cmac_continue(k, &s, d, aad, ad_lens[c]);
+            aad += ad_lens[c];
+        } else {
+            d[0] = 0x80;
+            xor16(d, d, s.k2);
+            uaesh_encrypt(k->ek, k->nr, d, d);
+        }
         cmac_double(y);
         xor16(y, y, d);
     }
@@ -670,19 +679,19 @@ static void s2v_ctr(const uaesh_key *k, const uint8_t v[16], const uint8_t *in, 
 }
 
 /* k = K_s2v, kc = K_ctr; decrypt: CTR first, then S2V over the plaintext, 0x1A on a mismatch (the text stays) */
-int uaesh_siv(const uaesh_key *k, const uaesh_key *kc, int decrypt, uint8_t iv[16], const uint8_t *aad, size_t aad_len,
-              const uint8_t *in, size_t len, uint8_t *out)
+int uaesh_siv(const uaesh_key *k, const uaesh_key *kc, int decrypt, uint8_t iv[16], size_t nad, const size_t *ad_lens,
+              const uint8_t *aad, const uint8_t *in, size_t len, uint8_t *out)
 {
     uint8_t v[16];
     if (!decrypt) {
-        s2v(k, aad, aad_len, in, len, v);
+        s2v(k, nad, ad_lens, aad, in, len, v);
         s2v_ctr(kc, v, in, len, out);
         memcpy(iv, v, 16);
         return 0;
     }
     memcpy(v, iv, 16);
     s2v_ctr(kc, v, in, len, out);
-    s2v(k, aad, aad_len, out, len, v);
+    s2v(k, nad, ad_lens, aad, out, len, v);
     return differ(v, iv, 16) ? 0x1A : 0;
 }
 

@@ -43,11 +43,12 @@ void uaesh_cmac(const uaesh_key *k, const uint8_t *data, size_t len, uint8_t mac
 int  uaesh_ccm(const uaesh_key *k, int decrypt, const uint8_t *nonce, size_t nonce_len, size_t tag_len,
                const uint8_t *aad, size_t aad_len, const uint8_t *in, size_t len, uint8_t *out);            /* :1226-1314 */
 /* EAX: any nonce length, tag_len 1..16 (decrypt: in = ct || tag, `out` untouched on 0x1A);
- * SIV: k = K_s2v, kc = K_ctr, iv = the synthesized IV (out) / the IV to check (in)                             */
+ * SIV: k = K_s2v, kc = K_ctr, iv = the synthesized IV (out) / the IV to check (in); aad = nad components of
+ * ad_lens[i] bytes back to back (RFC 5297's vector; the reference's one aData is nad = aDataLen ? 1 : 0)        */
 int  uaesh_eax(const uaesh_key *k, int decrypt, const uint8_t *nonce, size_t nonce_len, size_t tag_len,
                const uint8_t *aad, size_t aad_len, const uint8_t *in, size_t len, uint8_t *out);            /* :1560-1648 */
-int  uaesh_siv(const uaesh_key *k, const uaesh_key *kc, int decrypt, uint8_t iv[16], const uint8_t *aad, size_t aad_len,
-               const uint8_t *in, size_t len, uint8_t *out);                                                /* :1323-1411 */
+int  uaesh_siv(const uaesh_key *k, const uaesh_key *kc, int decrypt, uint8_t iv[16], size_t nad, const size_t *ad_lens,
+               const uint8_t *aad, const uint8_t *in, size_t len, uint8_t *out);                            /* :1323-1411 */
 
 /* r = the r half of the key pair (clamped here), AES_k(nonce) with k; len 0: mac = AES_k(nonce) */
 void uaesh_poly1305(const uaesh_key *k, const uint8_t r[16], const uint8_t nonce[16], const uint8_t *data, size_t len,

@@ -46,6 +46,9 @@
  *   S2V   s2v.small             k_s2v_small (Y || lead blocks, then CTR)            (1)    text <= UAES_EAX_SIV_SMALL_MAX
  *         s2v.long              k_s2v_macs and CTR (k_ctr*), in either order        (2)    beyond
  *         s2v.batch             k_s2v_batch (sixteen lanes per record)              (1)    uaes_siv_*_batch
+ *         s2v.small.v           k_s2v_v<CTR> (components over 60 rows || lead blocks, fold, CTR) (1)  uaes_siv_*_v, text <= UAES_EAX_SIV_SMALL_MAX
+ *         s2v.long.v            k_s2v_v and CTR (k_ctr*), in either order           (2)    uaes_siv_*_v beyond
+ *         s2v.batch.v           k_s2v_batch_v (sixteen lanes per record; lens)      (1)    uaes_siv_*_batch_v
  *   CBC   chain.serial          k_chain_serial (one wave walks the chain)           (1)    CBC encrypt, CFB encrypt, OFB: any length
  *   CFB   fbdec.single          k_fb_dec<U=1> (the CS3 pair / CFB tail: one lane)   (1)    CBC / CFB decrypt, < half the CUs' worth of
  *   OFB                                                                                    4-block tiles (<= 8 MiB on 256 CUs)
@@ -72,7 +75,8 @@
  *   FF3-1 ff3.batch             k_ff3 (sixteen lanes per record, four per wave)     (1)    uaes_ff3_*_batch; one text (<= 192 numerals) is a batch of one
  * The Poly1305 rows have a planner of their own (uaesk_plan_poly1305, uaes_poly1305.hip) and ids outside enum
  * uaes_arrangement (uaes_debug_plan_poly1305 names them); a larger message never goes back to a smaller row.
- * So do the EAX and SIV (RFC 5297) rows (uaesk_plan_eax_siv, uaes_eax_siv.hip; uaes_debug_plan_eax_siv), and the
+ * So do the EAX and SIV (RFC 5297) rows (uaesk_plan_eax_siv and, for the .v rows, uaesk_plan_siv_v, uaes_eax_siv.hip;
+ * uaes_debug_plan_eax_siv, uaes_debug_plan_siv_v), and the
  * CBC / CFB / OFB / CMAC / CCM / batch rows (uaesk_plan_chain, uaes_chain.hip, and uaesk_plan_mac / uaesk_plan_ccm_batch,
  * uaes_mac.hip; uaes_debug_plan_chain); tests/test_gpu_chains.py derives its sizes and message counts from them.  Key wrap has
  * uaesk_plan_kw (uaes_kw.hip; uaes_debug_plan_kw), and tests/test_gpu_kw.py finds its two boundaries by walking it; key
@@ -200,9 +204,18 @@ const char *uaesk_poly1305_arrangement_name(int id);
  * then runs the positioned CTR kernels.  siv: 0 = EAX, 1 = SIV; dir: 0 encrypt, 1 decrypt; nmsg >= 2 = a batch.
  * launches = kernels the call enqueues; grid = workgroups of the main kernel. */
 #define UAES_EAX_SIV_SMALL_MAX ((size_t)16384)
-enum uaes_eax_siv_arrangement { UAES_EAX_SMALL = 0, UAES_EAX_LONG, UAES_EAX_BATCH, UAES_S2V_SMALL, UAES_S2V_LONG, UAES_S2V_BATCH };
+enum uaes_eax_siv_arrangement { UAES_EAX_SMALL = 0, UAES_EAX_LONG, UAES_EAX_BATCH, UAES_S2V_SMALL, UAES_S2V_LONG, UAES_S2V_BATCH,
+                                UAES_S2V_SMALL_V, UAES_S2V_LONG_V, UAES_S2V_BATCH_V };
 int uaesk_plan_eax_siv(int siv, int dir, size_t len, size_t nmsg, uaes_plan *p);
 const char *uaesk_eax_siv_arrangement_name(int id);
+/* SIV with a vector of associated data (uaes_siv_*_v, uaes_siv_*_batch_v): the same boundary, with nad components of
+ * associated data, at most UAES_S2V_AD_MAX in a single call (RFC 5297: S2V takes 127 strings, the text included) and
+ * UAES_S2V_BATCH_AD_MAX in a batch record (their lengths travel by value).  steps = the rows of the workgroup the
+ * components are dealt over, round-robin (a batch record's one row walks its own: 1).  Returns a HIP error code for a
+ * dir other than 0 / 1 or more components than the call takes. */
+#define UAES_S2V_AD_MAX       126
+#define UAES_S2V_BATCH_AD_MAX 8
+int uaesk_plan_siv_v(int dir, size_t len, size_t nad, size_t nmsg, uaes_plan *p);
 
 /* The feedback modes, the CBC-MAC modes and the batches of chains.  what = enum uaes_chain_what; dir: 0 encrypt (or
  * the MAC), 1 decrypt; a = bytes of text (batches: bytes per message), b = messages of a batch (other rows ignore it).

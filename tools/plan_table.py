@@ -57,6 +57,12 @@ print("EAX / SIV (RFC 5297): one launch up to UAES_EAX_SIV_SMALL_MAX = %d bytes 
 walk("EAX encrypt", lambda n: uaes.eax_siv_plan(False, n)[:2] + (0, 0), 0, 64 * MIB)
 walk("EAX decrypt", lambda n: uaes.eax_siv_plan(False, n, decrypt=True)[:2] + (0, 0), 0, 64 * MIB)
 walk("SIV (RFC 5297)", lambda n: uaes.eax_siv_plan(True, n)[:2] + (0, 0), 0, 64 * MIB)
+print("SIV with a vector of associated data: the components of one call are dealt over %d rows of sixteen lanes" % uaes.siv_v_plan(0, 1)[3])
+for dec in (False, True):
+    walk("SIV %s, 3 components" % ("decrypt" if dec else "encrypt"), lambda n: uaes.siv_v_plan(n, 3, decrypt=dec)[:2] + (0, 0), 0, 64 * MIB, 1)
+walk("SIV batch with components, k records of 64 bytes (positions/thread: rows per record's components)",
+     lambda k: uaes.siv_v_plan(64, 2, max(k, 2))[:2] + (0, uaes.siv_v_plan(64, 2, max(k, 2))[3]), 2, 1 << 20, 1,
+     lambda k: "%9d records (%9.3f MiB)" % (k, k * 64 / MIB))
 for what in ("cbc", "cfb", "cbc_nocts"):
     walk("%s decrypt" % what.upper(), lambda n: uaes.chain_plan(what, max(n, 16), decrypt=True)[:2] + (0, 0), 16, 64 * MIB)
 walk("CBC / CFB encrypt, OFB, CMAC", lambda n: uaes.chain_plan("cbc", max(n, 16))[:2] + (0, 0), 16, 64 * MIB)
