@@ -9,7 +9,8 @@ import pytest
 import micro_aes_amd as uaes
 from tests import eax_siv_ref as ES
 from tests import kw_ref as KW
-from tests.test_gpu_ccm_batch import Mem, batch as ccm_batch
+from tests.guarded_mem import Mem, ptr
+from tests.test_gpu_ccm_batch import raw as ccm_raw
 from tests.test_gpu_eax_siv import batch as eax_siv_batch
 
 pytestmark = pytest.mark.gpu
@@ -20,16 +21,16 @@ _ref = {}
 
 
 def pointers(args):
-    return [a.ptr if isinstance(a, Mem) else a for a in args]
+    return [ptr(a) for a in args]
 
 
 def eax_siv_call(*args):
-    """tests/test_gpu_eax_siv.py's batch() with this file's Mem"""
     return eax_siv_batch(*pointers(args))
 
 
-def ccm_call(*args):
-    return ccm_batch(*pointers(args))
+def ccm_call(decrypt, key, *args):
+    """tests/test_gpu_ccm_batch.py's raw(): the arguments from nl on, without verdicts when encrypting"""
+    return ccm_raw(decrypt, len(key) * 8, key, *pointers(args), *[None] * (12 - len(args)))
 
 
 def flip_record(parts, bit):

@@ -1,261 +1,99 @@
-"""The CCM batches on the GPU (k_ccm_batch, uaes_mac.hip) against the CPU oracle's ccm_encrypt / ccm_decrypt: every short
-shape, record counts read from the plan, per-record lengths, placements, forgeries of every part of a record, the
-one-message calls, the published vectors and two threads.  Every failing case prints the tuple that reproduces it."""
-import ctypes as C
-import random
-import threading
-
+"""The CCM batches on the GPU (k_ccm_batch, uaes_mac.hip) against the CPU oracle's ccm_encrypt / ccm_decrypt, through the
+frame of tests/aead_batch_cases.py: every short shape, record counts read from the plan, per-record lengths, placements,
+forgeries of every part of a record, the one-message calls, two threads -- and, its own, the published vectors.  Every
+failing case prints the tuple that reproduces it."""
 import pytest
 
 import micro_aes_amd as uaes
+from tests import aead_batch_cases as F
 from tests import rsp
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 0xA5
-KEYS = {bits: bytes((bits // 8 + 7 * i) & 0xff for i in range(bits // 8)) for bits in (128, 192, 256)}
-
-
-class Mem:
-    """`data` (then `size - len(data)` guard bytes) in host or device memory, `off` bytes behind an aligned base, with
-    guard bytes in front of and behind it"""
-
-    def __init__(self, data=b"", device=False, off=0, size=None, room=64):
-        data = bytes(data)
-        self.size = max(len(data), size or 0)
-        self.off, self.device = off, device
-        raw = bytes([GUARD]) * off + data + bytes([GUARD]) * (self.size - len(data) + room)
-        if device:
-            import torch
-            self.t = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to("cuda")
-            self.ptr = C.c_void_p(self.t.data_ptr() + off)
-        else:
-            self.h = (C.c_uint8 * len(raw)).from_buffer_copy(raw)
-            self.ptr = C.c_void_p(C.addressof(self.h) + off)
-
-    def raw(self):
-        if self.device:
-            import torch
-            torch.cuda.synchronize()
-            return bytes(self.t.cpu().numpy())
-        return bytes(self.h)
-
-    def get(self, n=None):
-        return self.raw()[self.off:self.off + (self.size if n is None else n)]
-
-    def intact(self, n):
-        """nothing but the first n bytes was written"""
-        r = self.raw()
-        return set(r[:self.off]) | set(r[self.off + n:]) <= {GUARD}
-
-
-def ptr(x):
-    return x.ptr if isinstance(x, Mem) else x
-
-
-def batch(decrypt, key, nl, tl, nmsg, ml, lens, nonces, aads, al, src, dst, tags, verdicts=None):
-    """the two entry points; every array bytes, None or Mem"""
-    L = uaes.engine()
-    if decrypt:
-        return L.uaes_ccm_decrypt_batch(len(key) * 8, key, nl, tl, nmsg, ml, ptr(lens), ptr(nonces), ptr(aads), al, ptr(src),
-                                        ptr(tags), ptr(dst), ptr(verdicts))
-    return L.uaes_ccm_encrypt_batch(len(key) * 8, key, nl, tl, nmsg, ml, ptr(lens), ptr(nonces), ptr(aads), al, ptr(src),
-                                    ptr(dst), ptr(tags))
-
-
-def flip(b, i):
-    b = bytearray(b)
-    b[i % len(b)] ^= 1 << (i % 8)
-    return bytes(b)
-
-
-def records(rng, n, nl, al, ml):
-    return [rng.randbytes(nl) for _ in range(n)], [rng.randbytes(al) for _ in range(n)], [rng.randbytes(ml) for _ in range(n)]
-
-
-def expected(orc, key, nonces, aads, texts, tl):
-    """the oracle's (ciphertexts, tags), one call per record"""
-    cts, tags = [], []
-    for nonce, aad, pt in zip(nonces, aads, texts):
-        ct = orc.ccm_encrypt(key, nonce, aad, pt, tag_len=tl)
-        cts.append(ct[:len(pt)])
-        tags.append(ct[len(pt):])
-    return cts, tags
-
-
-def check_both(orc, key, nonces, aads, texts, tl, info):
-    """encrypt == the oracle per record; decrypt returns 0, all verdicts 1 and the plaintext"""
-    want = expected(orc, key, nonces, aads, texts, tl)
-    got = uaes.ccm_batch(key, nonces, aads, texts, tag_len=tl)
-    if got != want:
-        bad = [m for m in range(len(texts)) if (got[0][m], got[1][m]) != (want[0][m], want[1][m])]
-        raise AssertionError("encrypt %r: records %r differ" % (info, bad[:8]))
-    rc, pts, verdicts = uaes.ccm_batch(key, nonces, aads, got[0], tag_len=tl, decrypt=True, tags=got[1], prefill=0x77)
-    assert rc == 0 and verdicts == [1] * len(texts) and pts == texts, ("decrypt", info, rc, verdicts)
-
-
-# ---- 1. every short shape ---------------------------------------------------------------------------------------------
 AADS = (0, 1, 13, 14, 15, 30, 31)       # 14 exactly fills the header block, 15 spills one byte, 30 ends on a block
 
 
-@pytest.mark.parametrize("nl", [7, 11, 13])
+def raw(decrypt, bits, key, nl, tl, nmsg, ml, lens, nonces, aads, al, src, dst, tags, verdicts):
+    L = uaes.engine()
+    if decrypt:
+        return L.uaes_ccm_decrypt_batch(bits, key, nl, tl, nmsg, ml, lens, nonces, aads, al, src, tags, dst, verdicts)
+    return L.uaes_ccm_encrypt_batch(bits, key, nl, tl, nmsg, ml, lens, nonces, aads, al, src, dst, tags)
+
+
+def one(decrypt, key, nonce, aad, data, tl):
+    return (uaes.AES_CCM_decrypt if decrypt else uaes.AES_CCM_encrypt)(key, nonce, aad, data, tag_len=tl)
+
+
+MODE = F.Mode(
+    name="ccm",
+    plan=lambda length, nmsg, decrypt: uaes.chain_plan("ccm_batch", length, nmsg, decrypt),
+    arrangement="ccm.batch",
+    wrapper=uaes.ccm_batch,
+    raw=raw,
+    key_bits=(128, 192, 256),
+    fixed_keys={bits: bytes((bits // 8 + 7 * i) & 0xff for i in range(bits // 8)) for bits in (128, 192, 256)},
+    nonce_lens=tuple(range(7, 14)),
+    tag_lens=(4, 6, 8, 10, 12, 14, 16),
+    enc=lambda key, nonce, aad, pt, tl: F.oracle().ccm_encrypt(key, nonce, aad, pt, tag_len=tl),
+    dec=lambda key, nonce, aad, ct, tl: F.oracle().ccm_decrypt(key, nonce, aad, ct, tag_len=tl),
+    one=one,
+    forged=("released", "zeros"),
+    # 5 records per call: one of them lands in a second wave
+    short_shapes=lambda bits: [(5, tl, al, ml, None) for ml in (range(50) if bits == 128 else (0, 15, 16, 17, 49))
+                               for al in AADS for tl in (4, 8, 16)],
+    short_nls=(7, 11, 13),
+    short_seed=lambda bits, nl: 1000 * bits + nl,
+    count_shape=(13, 5, 16, 8),
+    count_sampled=False,
+    lengths_shape=(12, 8, 37),
+    placement_shape=(13, 10),
+    placement_offsets=(0, 1, 3),
+    forgery_shape=(9, 13, 8, None),
+    forgery_parts=("tag of 0", "text of 4", "AAD of 8", "nonce of 5"),
+)
+COUNTS = (1, 3, 4, 16, 17, 8192, 8193)
+
+
+@pytest.mark.parametrize("nl", MODE.short_nls)
 @pytest.mark.parametrize("bits", [128, 192, 256])
-def test_every_short_shape(orc, bits, nl):
-    """5 records per call: one of them lands in a second wave"""
-    rng = random.Random(1000 * bits + nl)
-    key = KEYS[bits]
-    for ml in (range(50) if bits == 128 else (0, 15, 16, 17, 49)):
-        for al in AADS:
-            for tl in (4, 8, 16):
-                nonces, aads, texts = records(rng, 5, nl, al, ml)
-                check_both(orc, key, nonces, aads, texts, tl, (bits, nl, tl, al, ml))
-
-
-# ---- 2. record counts from the plan -----------------------------------------------------------------------------------
-def second_pass():
-    """the first count at which the grid-stride loop of the largest launch runs a second time, + 3"""
-    name, launches, grid, threads = uaes.chain_plan("ccm_batch", 16, 1 << 20)
-    assert name == "ccm.batch" and launches == 1 and threads % 16 == 0
-    return grid * threads // 16 + 3
+def test_every_short_shape(bits, nl):
+    F.check_short_shapes(MODE, bits, nl)
 
 
 @pytest.mark.parametrize("which", range(8), ids=["1", "3", "4", "16", "17", "8192", "8193", "second-pass"])
-def test_record_counts_from_the_plan(orc, which):
-    nmsg = (1, 3, 4, 16, 17, 8192, 8193, second_pass())[which]
-    if which == 7:
-        name, _, grid, threads = uaes.chain_plan("ccm_batch", 16, nmsg)
-        assert name == "ccm.batch" and nmsg > grid * threads // 16               # it does run a second time
-    rng = random.Random(nmsg)
-    key = KEYS[128]
-    nonces, aads, texts = records(rng, nmsg, 13, 5, 16)
-    check_both(orc, key, nonces, aads, texts, 8, ("count", nmsg))               # every record is compared
+def test_record_counts_from_the_plan(which):
+    F.check_count(MODE, COUNTS[which] if which < 7 else F.second_pass(MODE), second=which == 7)
 
 
-# ---- 3. variable lengths ----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("lens_on_device", [False, True], ids=["host-lens", "device-lens"])
 @pytest.mark.parametrize("device", [False, True], ids=["host", "device"])
-def test_variable_lengths(orc, device, lens_on_device):
-    rng = random.Random(48)
-    key, n, ml, nl, al, tl = KEYS[128], 37, 48, 12, 9, 8
-    lens = [rng.randrange(49) for _ in range(n)]
-    lens[3], lens[20], lens[36] = 0, 48, 17
-    assert min(lens) == 0 and max(lens) == 48
-    nonces, aads, slots = records(rng, n, nl, al, ml)
-    want = expected(orc, key, nonces, aads, [s[:k] for s, k in zip(slots, lens)], tl)
-    lv = Mem(b"".join(k.to_bytes(4, "little") for k in lens), lens_on_device)
-    src, dst, tags = Mem(b"".join(slots), device), Mem(b"", device, size=n * ml), Mem(b"", device, size=n * tl)
-    mn, ma = Mem(b"".join(nonces), device), Mem(b"".join(aads), device)
-    assert batch(False, key, nl, tl, n, ml, lv, mn, ma, al, src, dst, tags) == 0
-    out, tg = dst.get(), tags.get()
-    for m in range(n):
-        info = (device, lens_on_device, m, lens[m])
-        assert out[m * ml:m * ml + lens[m]] == want[0][m] and tg[m * tl:(m + 1) * tl] == want[1][m], info
-        assert set(out[m * ml + lens[m]:(m + 1) * ml]) <= {GUARD}, info            # beyond lens[m]: not written
-    assert dst.intact(n * ml) and tags.intact(n * tl)
-    # decrypt, and an entry above msg_bytes is taken as msg_bytes
-    back, ver = Mem(b"", device, size=n * ml), Mem(b"", device, size=n)
-    assert batch(True, key, nl, tl, n, ml, lv, mn, ma, al, dst, back, tags, ver) == 0
-    got = back.get()
-    for m in range(n):
-        assert got[m * ml:m * ml + lens[m]] == slots[m][:lens[m]] and set(got[m * ml + lens[m]:(m + 1) * ml]) <= {GUARD}, m
-    assert ver.get() == b"\1" * n and back.intact(n * ml) and ver.intact(n)
-    clamp = Mem(b"".join((k if k < 48 else 1000 + k).to_bytes(4, "little") for k in lens), lens_on_device)
-    dst2, tags2 = Mem(b"", device, size=n * ml), Mem(b"", device, size=n * tl)
-    assert batch(False, key, nl, tl, n, ml, clamp, mn, ma, al, src, dst2, tags2) == 0
-    assert dst2.get() == out and tags2.get() == tg and dst2.intact(n * ml)
+def test_variable_lengths(device, lens_on_device):
+    F.check_lengths(MODE, F.lengths_case(MODE), device, lens_on_device)
 
 
-# ---- 4. placement -----------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("off", [0, 1, 3])
+@pytest.mark.parametrize("off", MODE.placement_offsets)
 @pytest.mark.parametrize("device", [False, True], ids=["host", "device"])
-def test_placement(orc, device, off):
-    """offsets 1 and 3 with 33-byte records: the byte-wise path; offset 0 with 32: the 4-byte-aligned one"""
-    rng = random.Random(33 + off)
-    key, n, nl, al, tl = KEYS[192], 21, 13, 17, 10
-    ml = 33 if off else 32
-    nonces, aads, texts = records(rng, n, nl, al, ml)
-    want = expected(orc, key, nonces, aads, texts, tl)
-    mn, ma = Mem(b"".join(nonces), device, off), Mem(b"".join(aads), device, off)
-    src, dst, tags = Mem(b"".join(texts), device, off), Mem(b"", device, off, size=n * ml), Mem(b"", device, off, size=n * tl)
-    info = (device, off)
-    assert batch(False, key, nl, tl, n, ml, None, mn, ma, al, src, dst, tags) == 0, info
-    assert dst.get() == b"".join(want[0]) and tags.get() == b"".join(want[1]), info
-    assert dst.intact(n * ml) and tags.intact(n * tl) and src.get() == b"".join(texts), info
-    back, ver = Mem(b"", device, off, size=n * ml), Mem(b"", device, off, size=n)
-    assert batch(True, key, nl, tl, n, ml, None, mn, ma, al, dst, back, tags, ver) == 0, info
-    assert back.get() == b"".join(texts) and ver.get() == b"\1" * n and back.intact(n * ml) and ver.intact(n), info
-    # crtxt == pntxt
-    io = Mem(b"".join(texts), device, off)
-    tags2 = Mem(b"", device, off, size=n * tl)
-    assert batch(False, key, nl, tl, n, ml, None, mn, ma, al, io, io, tags2) == 0, info
-    assert io.get() == b"".join(want[0]) and tags2.get() == b"".join(want[1]) and io.intact(n * ml) and tags2.intact(n * tl), info
-    ver2 = Mem(b"", device, off, size=n)
-    assert batch(True, key, nl, tl, n, ml, None, mn, ma, al, io, io, tags2, ver2) == 0, info
-    assert io.get() == b"".join(texts) and io.intact(n * ml) and ver2.get() == b"\1" * n, info
+def test_placement(device, off):
+    """all arrays together, on the host or in device memory"""
+    F.check_placement(MODE, F.placement_case(MODE, off), F.places(MODE)[1 if device else 0], off)
 
 
-def test_in_place_with_more_blocks_than_a_chunk(orc):
-    """row_walk requests sixteen blocks ahead: records of 21 blocks + 5 bytes in place, in device memory"""
-    rng = random.Random(341)
-    key, n, ml, nl, al, tl = KEYS[256], 6, 341, 7, 0, 16
-    nonces, aads, texts = records(rng, n, nl, al, ml)
-    want = expected(orc, key, nonces, aads, texts, tl)
-    for off in (0, 2):
-        io, tags, ver = Mem(b"".join(texts), True, off), Mem(b"", True, size=n * tl), Mem(b"", True, size=n)
-        mn = Mem(b"".join(nonces), True)
-        assert batch(False, key, nl, tl, n, ml, None, mn, None, 0, io, io, tags) == 0
-        assert io.get() == b"".join(want[0]) and tags.get() == b"".join(want[1]) and io.intact(n * ml), off
-        assert batch(True, key, nl, tl, n, ml, None, mn, None, 0, io, io, tags, ver) == 0
-        assert io.get() == b"".join(texts) and ver.get() == b"\1" * n and io.intact(n * ml), off
+def test_in_place_with_more_blocks_than_a_chunk():
+    """row_walk requests sixteen blocks ahead: records of 21 blocks + 5 bytes"""
+    F.check_in_place(MODE, 341, 341, 7)
 
 
-# ---- 5. forgeries -----------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("part", ["tag of 0", "text of 4", "AAD of 8", "nonce of 5"])
-def test_forgeries(orc, part):
-    rng = random.Random(9)
-    key, n, ml, nl, al, tl = KEYS[128], 9, 40, 13, 13, 8
-    nonces, aads, texts = records(rng, n, nl, al, ml)
-    cts, tags = expected(orc, key, nonces, aads, texts, tl)
-    m = int(part.split()[-1])
-    bit = rng.randrange(1 << 16)
-    if part.startswith("tag"):
-        tags[m] = flip(tags[m], bit)
-    elif part.startswith("text"):
-        cts[m] = flip(cts[m], bit)
-    elif part.startswith("AAD"):
-        aads[m] = flip(aads[m], bit)
-    else:
-        nonces[m] = flip(nonces[m], bit)
-    orc_rc, left = orc.ccm_decrypt(key, nonces[m], aads[m], cts[m] + tags[m], tag_len=tl)
-    assert orc_rc == 0x1A and len(left) == ml
-    eng = uaes.engine()
-    for wipe in (0, 1):
-        eng.uaes_set_wipe_on_auth_failure(wipe)
-        try:
-            rc, pts, verdicts = uaes.ccm_batch(key, nonces, aads, cts, tag_len=tl, decrypt=True, tags=tags, prefill=0x5A)
-        finally:
-            eng.uaes_set_wipe_on_auth_failure(0)
-        info = (part, bit, wipe)
-        assert rc == 0x1A and verdicts == [0 if k == m else 1 for k in range(n)], (info, rc, verdicts)
-        assert pts[m] == (bytes(ml) if wipe else left), info
-        assert [p for k, p in enumerate(pts) if k != m] == [t for k, t in enumerate(texts) if k != m], info
+@pytest.mark.parametrize("part", MODE.forgery_parts)
+def test_forgeries(part):
+    F.check_forgery(MODE, F.forgery(MODE, part))
 
 
-# ---- 6. one call at a time --------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("bits", [128, 192, 256])
 def test_equals_the_one_message_calls(bits):
-    rng = random.Random(bits)
-    key = KEYS[bits]
-    for nl, tl, al, ml in ((7, 4, 0, 0), (11, 16, 20, 100), (13, 8, 13, 64), (12, 10, 300, 1000), (8, 6, 14, 257)):
-        nonces, aads, texts = records(rng, 7, nl, al, ml)
-        cts, tags = uaes.ccm_batch(key, nonces, aads, texts, tag_len=tl)
-        for m in range(7):
-            one = uaes.AES_CCM_encrypt(key, nonces[m], aads[m], texts[m], tag_len=tl)
-            assert cts[m] + tags[m] == one, (bits, nl, tl, al, ml, m)
-            assert uaes.AES_CCM_decrypt(key, nonces[m], aads[m], cts[m] + tags[m], tag_len=tl) == (0, texts[m]), (bits, nl, tl, al, ml, m)
+    shapes = ((7, 4, 0, 0), (11, 16, 20, 100), (13, 8, 13, 64), (12, 10, 300, 1000), (8, 6, 14, 257))
+    F.check_one_message_calls(MODE, bits, bits, shapes, 7)
 
 
-# ---- 7. published vectors ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("bits", [128, 192, 256])
 def test_published_vectors(bits):
     """every [Nlen = n] section of VNT<bits>.rsp: one key, ten records, one batch"""
@@ -272,33 +110,5 @@ def test_published_vectors(bits):
     assert total == 70
 
 
-# ---- 8. threads -------------------------------------------------------------------------------------------------------
-def test_two_threads_with_different_keys(orc):
-    """the expected values are made first; the threads only call the engine"""
-    cases = {}
-    for seed in (10, 20):
-        rng = random.Random(seed)
-        key = rng.randbytes(16)
-        cases[seed] = []
-        for n, ml in ((1, 0), (5, 17), (70, 64), (300, 33), (9, 1000)):
-            nonces, aads, texts = records(rng, n, 13, ml % 31, ml)
-            cases[seed].append((key, nonces, aads, texts, expected(orc, key, nonces, aads, texts, 8)))
-    errors = []
-
-    def worker(seed):
-        try:
-            for _ in range(3):
-                for key, nonces, aads, texts, want in cases[seed]:
-                    got = uaes.ccm_batch(key, nonces, aads, texts, tag_len=8)
-                    assert got == want, (seed, len(texts), len(texts[0]))
-                    back = uaes.ccm_batch(key, nonces, aads, got[0], tag_len=8, decrypt=True, tags=got[1])
-                    assert back == (0, texts, [1] * len(texts)), (seed, len(texts), len(texts[0]))
-        except Exception as e:                                          # noqa: BLE001 -- reported below
-            errors.append(repr(e))
-
-    ts = [threading.Thread(target=worker, args=(s,)) for s in (10, 20)]
-    for t in ts:
-        t.start()
-    for t in ts:
-        t.join()
-    assert not errors, errors
+def test_two_threads_with_different_keys():
+    F.check_two_threads(MODE, F.keyed_thread_jobs(MODE, 13), repeats=3)

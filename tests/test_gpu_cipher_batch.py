@@ -9,9 +9,11 @@ import threading
 import pytest
 
 import micro_aes_amd as uaes
-from tests.test_gpu_ocb_batch import GUARD, KEYS, Mem, ptr
+from tests.guarded_mem import FILL, Mem, ptr
 
 pytestmark = pytest.mark.gpu
+
+KEYS = {bits: bytes((bits // 8 + 7 * i) & 0xff for i in range(bits // 8)) for bits in (128, 192, 256)}
 
 E_ARG = -2                                      # UAES_E_ARG (include/uaes_hip.h)
 ROW_CH = 16                                     # row_walk's look-ahead in blocks (csrc/uaes_aes.hip.h)
@@ -189,7 +191,7 @@ def test_variable_lengths(orc, mode, device, lens_on_device):
     for m in range(n):
         info = (mode, device, lens_on_device, m, lens[m])
         assert out[m * ml:m * ml + eff[m]] == want[m], info
-        assert set(out[m * ml + eff[m]:(m + 1) * ml]) <= {GUARD}, info                          # beyond lens[m]: not written
+        assert set(out[m * ml + eff[m]:(m + 1) * ml]) <= {FILL}, info                           # beyond lens[m]: not written
     assert dst.intact(n * ml) and src.get() == b"".join(slots) and lv.intact(4 * n)
     # in place: the rest of a slot stays the input's
     io = Mem(b"".join(slots), device)
@@ -300,7 +302,7 @@ def test_fuzz(orc, seed):
     assert batch(mode, key, mv, n, ml, lv, src, dst) == 0, info
     out = dst.get()
     for m in range(n):
-        rest = slots[m][eff[m]:] if in_place else bytes([GUARD]) * (ml - eff[m])
+        rest = slots[m][eff[m]:] if in_place else bytes([FILL]) * (ml - eff[m])
         assert out[m * ml:(m + 1) * ml] == want[m] + rest, (info, m)
     assert dst.intact(n * ml), info
 

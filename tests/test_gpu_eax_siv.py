@@ -15,6 +15,7 @@ import pytest
 
 import micro_aes_amd as uaes
 from tests import eax_siv_ref as R
+from tests.guarded_mem import Mem, ptr
 
 pytestmark = pytest.mark.gpu
 
@@ -23,46 +24,6 @@ def flip(b, i):
     b = bytearray(b)
     b[i % len(b)] ^= 1 << (i % 8)
     return bytes(b)
-
-
-GUARD = 0xA5
-
-
-class Mem:
-    """`data` (then `size - len(data)` guard bytes) in host or device memory, `off` bytes behind an aligned base, with
-    guard bytes in front of and behind it"""
-
-    def __init__(self, data=b"", device=False, off=0, size=None, room=64):
-        data = bytes(data)
-        self.size = max(len(data), size or 0)
-        self.off, self.device = off, device
-        raw = bytes([GUARD]) * off + data + bytes([GUARD]) * (self.size - len(data) + room)
-        if device:
-            import torch
-            self.t = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to("cuda")
-            self.ptr = C.c_void_p(self.t.data_ptr() + off)
-        else:
-            self.h = (C.c_uint8 * len(raw)).from_buffer_copy(raw)
-            self.ptr = C.c_void_p(C.addressof(self.h) + off)
-
-    def raw(self):
-        if self.device:
-            import torch
-            torch.cuda.synchronize()
-            return bytes(self.t.cpu().numpy())
-        return bytes(self.h)
-
-    def get(self, n=None):
-        return self.raw()[self.off:self.off + (self.size if n is None else n)]
-
-    def intact(self, n):
-        """nothing but the first n bytes was written"""
-        r = self.raw()
-        return set(r[:self.off]) | set(r[self.off + n:]) <= {GUARD}
-
-
-def ptr(x):
-    return x.ptr if isinstance(x, Mem) else x
 
 
 def eax(decrypt, bits, key, nonce, nl, tl, aad, al, src, n, dst):

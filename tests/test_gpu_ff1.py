@@ -12,45 +12,13 @@ import pytest
 
 import micro_aes_amd as uaes
 from tests import ff1_ref as R
+from tests.guarded_mem import Mem
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 0xA5
 E_DATALENGTH, E_DECRYPTION, E_ENCRYPTION = 1, 0x1D, 0x1E
 TWEAK_LENS = [0, 1, 15, 16, 17, 31, 32, 33, 100]
 RADICES = [2, 26, 36, 64, 95, 255, 256]
-
-
-class Mem:
-    """`size` bytes (starting with `data`, then `fill`) in host or device memory, `off` bytes behind an aligned base,
-    with guard bytes in front of and behind them"""
-
-    def __init__(self, data=b"", device=False, off=0, size=None, fill=0x5C, room=64):
-        data = bytes(data)
-        self.size = max(len(data), size or 0)
-        self.off, self.device = off, device
-        raw = bytes([GUARD]) * off + data + bytes([fill]) * (self.size - len(data)) + bytes([GUARD]) * room
-        if device:
-            import torch
-            self.t = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to("cuda")
-            self.ptr = C.c_void_p(self.t.data_ptr() + off)
-        else:
-            self.h = (C.c_uint8 * len(raw)).from_buffer_copy(raw)
-            self.ptr = C.c_void_p(C.addressof(self.h) + off)
-
-    def raw(self):
-        if self.device:
-            import torch
-            torch.cuda.synchronize()
-            return bytes(self.t.cpu().numpy())
-        return bytes(self.h)
-
-    def get(self):
-        return self.raw()[self.off:self.off + self.size]
-
-    def intact(self):
-        r = self.raw()
-        return set(r[:self.off]) | set(r[self.off + self.size:]) <= {GUARD}
 
 
 def kbuf(b):

@@ -16,12 +16,11 @@ import pytest
 
 import micro_aes_amd as uaes
 from tests import gcm_records_cases as GC
-from tests.test_gpu_ff1 import Mem
+from tests.guarded_mem import FILL, Mem
 
 pytestmark = pytest.mark.gpu
 
 E_AUTH, E_ARG = 0x1A, -2
-FILL = 0x5C                                                   # what a Mem holds where it was given no data
 ALL_BITS = (128, 192, 256)
 
 

@@ -18,6 +18,7 @@ import pytest
 
 import micro_aes_amd as uaes
 from tests import ocb_ref as R
+from tests.guarded_mem import Mem
 from tests.test_gpu_plan import boundaries
 
 pytestmark = pytest.mark.gpu
@@ -27,7 +28,6 @@ CHUNK = 256 * 16                        # bytes of a chunk: 256 blocks, one wave
 SLICE = 256 * MIB                       # what the torch reference works on at once: 65536 chunks, no multiple of
                                         # run x waves chunks at any grid that is not a power of two, and never aligned
                                         # with the chunks themselves (block i sits at byte 16 (i - 1))
-GUARD = 0xA5
 NONCE = bytes(range(50, 62))
 
 
@@ -381,39 +381,6 @@ def test_every_nonce_and_tag_length(orc):
 
 
 # ---- f. nothing outside the result is written ----------------------------------------------------------------------
-class Mem:
-    """`size` bytes (starting with `data`, then `fill`) in host or device memory, `off` bytes behind an aligned base,
-    with guard bytes in front of and behind them"""
-
-    def __init__(self, data=b"", device=False, off=0, size=None, fill=0x5C, room=64):
-        data = bytes(data)
-        self.size = max(len(data), size or 0)
-        self.off, self.device = off, device
-        raw = bytes([GUARD]) * off + data + bytes([fill]) * (self.size - len(data)) + bytes([GUARD]) * room
-        if device:
-            import torch
-            self.t = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to("cuda")
-            self.ptr = C.c_void_p(self.t.data_ptr() + off)
-        else:
-            self.h = (C.c_uint8 * len(raw)).from_buffer_copy(raw)
-            self.ptr = C.c_void_p(C.addressof(self.h) + off)
-
-    def raw(self):
-        if self.device:
-            import torch
-            torch.cuda.synchronize()
-            return bytes(self.t.cpu().numpy())
-        return bytes(self.h)
-
-    def get(self, n=None):
-        return self.raw()[self.off:self.off + (self.size if n is None else n)]
-
-    def intact(self):
-        """nothing outside the `size` bytes was written"""
-        r = self.raw()
-        return set(r[:self.off]) | set(r[self.off + self.size:]) <= {GUARD}
-
-
 @pytest.mark.parametrize("device", [False, True])
 def test_nothing_is_written_outside_the_result(orc, device):
     """guard bytes in front of the result and behind len + tag_len (encryption) / len (decryption)"""

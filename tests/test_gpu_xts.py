@@ -14,7 +14,7 @@ import pytest
 
 import micro_aes_amd as uaes
 from tests import xts_cases as XC
-from tests.test_gpu_ocb_batch import GUARD, Mem
+from tests.guarded_mem import GUARD, Mem
 
 pytestmark = pytest.mark.gpu
 

@@ -10,9 +10,11 @@ import pytest
 
 import micro_aes_amd as uaes
 from tests import rsp
-from tests.test_gpu_ocb_batch import GUARD, KEYS, Mem, ptr
+from tests.guarded_mem import FILL, Mem, ptr
 
 pytestmark = pytest.mark.gpu
+
+KEYS = {bits: bytes((bits // 8 + 7 * i) & 0xff for i in range(bits // 8)) for bits in (128, 192, 256)}
 
 E_ARG, E_DATALENGTH = -2, 1                     # include/uaes_hip.h
 ROW_CH = 16                                     # row_walk's look-ahead in blocks (csrc/uaes_aes.hip.h)
@@ -248,9 +250,9 @@ def test_bad_lengths(orc, decrypt, device, lens_on_device):
         info = (decrypt, device, lens_on_device, m, lens[m])
         if m in want:
             assert out[m * ml:m * ml + eff[m]] == want[m], info
-            assert set(out[m * ml + eff[m]:(m + 1) * ml]) <= {GUARD}, info                      # beyond lens[m]: not written
+            assert set(out[m * ml + eff[m]:(m + 1) * ml]) <= {FILL}, info                       # beyond lens[m]: not written
         else:
-            assert set(out[m * ml:(m + 1) * ml]) == {GUARD}, info                               # a short unit: its prefill
+            assert set(out[m * ml:(m + 1) * ml]) == {FILL}, info                                # a short unit: its prefill
     assert dst.intact(n * ml) and src.get() == b"".join(slots) and lv.intact(4 * n)
     assert uaes.engine().uaes_debug_live_key_schedules() == live
     # the same lengths without the short ones: the call succeeds
@@ -294,7 +296,7 @@ def test_placement(orc, place, decrypt):
         assert batch(decrypt, keys, tv, n, ml, lv, src, dst) == 0, info
         out = dst.get()
         for m in range(n):
-            assert out[m * ml:(m + 1) * ml] == cut[m] + bytes([GUARD]) * (ml - lens[m]), (info, "lens", m)
+            assert out[m * ml:(m + 1) * ml] == cut[m] + bytes([FILL]) * (ml - lens[m]), (info, "lens", m)
         assert dst.intact(n * ml) and tv.get() == b"".join(tweaks) and tv.intact(16 * n) and lv.intact(4 * n), info
 
 
@@ -320,7 +322,7 @@ def test_fuzz(orc, seed):
     assert batch(decrypt, keys, tv, n, ml, lv, src, dst) == 0, info
     out = dst.get()
     for m in range(n):
-        rest = slots[m][eff[m]:] if in_place else bytes([GUARD]) * (ml - eff[m])
+        rest = slots[m][eff[m]:] if in_place else bytes([FILL]) * (ml - eff[m])
         assert out[m * ml:(m + 1) * ml] == want[m] + rest, (info, m)
     assert dst.intact(n * ml), info
     # the other direction gives the input back
