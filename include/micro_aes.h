@@ -67,7 +67,9 @@
 #ifndef EAX                  /* micro_aes.h:43 -- EAX (uaes_eax_siv.hip); every library exports AES_EAX_*, a caller */
 #define EAX      0          /* built with -DEAX=1 sees the prototypes (below)                                       */
 #endif
-#define EAXP     0
+#ifndef EAXP                 /* micro_aes.h:70 -- EAX', IEEE 1703 (uaes_eax_siv.hip); every library exports AES_EAXP_*, a */
+#define EAXP     0          /* caller built with -DEAX=1 -DEAXP=1 gets AES_EAX_* with the EAX' parameter lists (below)  */
+#endif
 #ifndef SIV                  /* micro_aes.h:44 -- SIV, RFC 5297 (uaes_eax_siv.hip); every library exports AES_SIV_*, */
 #define SIV      0          /* a caller built with -DSIV=1 sees the prototypes (below)                              */
 #endif
@@ -117,7 +119,7 @@ enum constant_parameters_of_modes
 #endif
     SIVGCM_NONCE_LEN = 12,
     SIVGCM_TAG_LEN  = 16,
-#if EAX
+#if EAX && !EAXP           /* (micro_aes.h:119: EAX' takes the nonce length as an argument and its mac has four bytes) */
 #ifndef EAX_NONCE_LEN      /* micro_aes.h:120-121; -DEAX_NONCE_LEN=n (any, 0 too) / -DEAX_TAG_LEN=n (1..16) bind */
     EAX_NONCE_LEN   = 16,  /* AES_EAX_* to the general entry points below                                        */
 #endif
@@ -355,7 +357,20 @@ char GCM_SIV_decrypt(const uint8_t *key, const uint8_t *nonce,
 void AES_CMAC(const uint8_t *key,
               const void *data, const size_t dataSize, uint8_t mac[16]);
 
-#if EAX
+#if EAX && EAXP
+/* EAX' (micro_aes.c:1523-1648 with EAXP 1; micro_aes.h:359-383): the AEAD of ANSI C12.22 / IEEE Std 1703.  No associated
+ * data; the nonce (the datagram's cleartext header) has any length; mac = four bytes of N ^ C' appended at crtxt +
+ * ptextLen; decrypt checks them before it writes (a forgery returns M_AUTHENTICATION_ERROR and leaves pntxt as it was).
+ * AES_EAX_* are bound to the libraries' AES_EAXP_* symbols.  Minematsu, Lucks, Morita and Iwata (FSE 2013) forge EAX'
+ * when nonce and text are both at most 16 bytes: the standard's own messages never are, and the mode belongs nowhere
+ * else; such inputs are served all the same, as the reference serves them. */
+void AES_EAXP_encrypt(const uint8_t *key, const uint8_t *nonce, const size_t nonceLen,
+                      const void *pntxt, const size_t ptextLen, void *crtxt);
+char AES_EAXP_decrypt(const uint8_t *key, const uint8_t *nonce, const size_t nonceLen,
+                      const void *crtxt, const size_t crtxtLen, void *pntxt);
+#define AES_EAX_encrypt AES_EAXP_encrypt
+#define AES_EAX_decrypt AES_EAXP_decrypt
+#elif EAX
 /* EAX (micro_aes.c:1560-1648): tag = N ^ H ^ C, EAX_TAG_LEN bytes appended at crtxt + ptextLen; decrypt checks the tag
  * before it writes (a forgery returns M_AUTHENTICATION_ERROR and leaves pntxt as it was) */
 void AES_EAX_encrypt(const uint8_t *key, const uint8_t *nonce,

@@ -481,6 +481,46 @@ int uaes_siv_decrypt_batch_v(int keybits, const uint8_t *keys, size_t nmsg, size
                              size_t nad, const size_t *adLens, const void *aData,
                              const uint8_t *ivs, const void *crtxt, void *pntxt, uint8_t *verdicts);
 
+/* ---- EAX' (ANSI C12.22 / IEEE Std 1703): replace AES_EAX_* of a reference built with EAXP 1 ----
+ * micro_aes.c:1523-1648.  With L = Enc_K(0^128), D = dblLE(L), Q = dblLE(D) (little-endian doubling, doubleLblock) and
+ * CMAC'(start, X) = CMAC with subkeys D / Q whose chaining value starts at `start`:
+ *   N = CMAC'(D, nonce), N' = N with bit 7 of bytes 12 and 14 cleared, C = CTR(N', P) with the 56-bit counter,
+ *   C' = CMAC'(Q, C) (0^128 for an empty C), mac = N[12..15] ^ C'[12..15], four bytes appended at crtxt + ptextLen.
+ * There is no associated data: in C12.22 the cleartext header IS the nonce, of any length (0 and a NULL pointer
+ * included).  Host or device pointers, in == out works, the host policy applies to these two calls.  Decrypt reads the
+ * mac at crtxt + crtxtLen and checks it BEFORE it writes: on a mismatch it returns UAES_E_AUTHENTICATION and pntxt is
+ * untouched (the wipe switch does not apply).  UAES_E_ARG: NULL key, bad keybits, a needed pointer that is NULL.
+ * SECURITY: Minematsu, Lucks, Morita and Iwata ("Attacks and Security Proofs of EAX-Prime", FSE 2013) forge EAX' when
+ * nonce and text are BOTH at most one block (16 bytes).  The standard's own messages never are; do not use the mode
+ * outside it.  Such inputs are not refused, because the reference does not refuse them. */
+int uaes_eaxp_encrypt(int keybits, const uint8_t *key, const uint8_t *nonce, size_t nonceLen,
+                      const void *pntxt, size_t ptextLen, void *crtxt);    /* writes ptextLen + 4 */
+int uaes_eaxp_decrypt(int keybits, const uint8_t *key, const uint8_t *nonce, size_t nonceLen,
+                      const void *crtxt, size_t crtxtLen, void *pntxt);    /* crtxt holds crtxtLen + 4 */
+/* Batches under one key, always on the GPU, sixteen lanes per record, one launch: record m has its nonce in the slot at
+ * nonces + m * nonce_bytes and its text in the slot at m * msg_bytes, its mac at macs + 4 m.  nlens / lens (either may
+ * be NULL: every record fills its slot) = nmsg 32-bit lengths, nlens[m] <= nonce_bytes and lens[m] <= msg_bytes: in
+ * host memory an entry above its slot is UAES_E_ARG before the device is touched; in (4-byte aligned) device memory the
+ * kernel alone reads them and takes such an entry as the slot.  The bytes of an output slot beyond lens[m] are not
+ * written.  Every record is bit for bit what the single call gives.  Decrypt writes verdicts[m] = 1 (authentic) / 0
+ * (verdicts may be NULL), writes only authentic records (a host-memory output is copied in first; the wipe switch does
+ * not apply) and returns UAES_E_AUTHENTICATION if any record is forged.  UAES_E_ARG: a slot above UINT32_MAX bytes, a
+ * size product that overflows, NULL key, bad keybits, a needed pointer that is NULL.  nmsg == 0 returns 0.  key: host
+ * memory; every array host or device memory at any byte offset; crtxt == pntxt works.
+ * Measured on an MI355X (tools/eaxp_rate.py -> profiles/eaxp_batch_rate.md; AES-128, 2^20 device-resident records,
+ * 32-byte nonces; synchronous calls, the host round trip included), encrypt / decrypt:
+ *   records of 16 B     3.50 / 2.42 G records per second   (0.78 / 0.83x the time of uaes_eax_*_batch at the same shape)
+ *   records of 64 B     1.87 / 1.43 G records per second   (0.90 / 0.92x; 112 / 85 GiB/s of text)
+ *   records of 1024 B   0.264 / 0.216 G records per second (0.99 / 1.01x; 251 / 206 GiB/s of text) */
+int uaes_eaxp_encrypt_batch(int keybits, const uint8_t *key, size_t nmsg,
+                            size_t nonce_bytes, const uint32_t *nlens, const uint8_t *nonces,
+                            size_t msg_bytes, const uint32_t *lens,
+                            const void *pntxt, void *crtxt, uint8_t *macs);         /* macs: nmsg * 4 */
+int uaes_eaxp_decrypt_batch(int keybits, const uint8_t *key, size_t nmsg,
+                            size_t nonce_bytes, const uint32_t *nlens, const uint8_t *nonces,
+                            size_t msg_bytes, const uint32_t *lens,
+                            const void *crtxt, const uint8_t *macs, void *pntxt, uint8_t *verdicts);
+
 /* ---- CBC / CFB / OFB: replace AES_CBC_*, AES_CFB_*, AES_OFB_* -------------
  * micro_aes.c:697-782 (CBC with CS3 ciphertext stealing, CTS 1: the last two
  * blocks are always swapped, len < 16 -> UAES_E_DATALENGTH), :799-845 (CFB),
@@ -1095,6 +1135,9 @@ const char *uaes_debug_plan_eax_siv(int siv, int dir, size_t len, size_t nmsg, i
  * NULL) = launches, workgroups of the main kernel, the rows of sixteen lanes the components are dealt over (a batch
  * record's one row walks its own: 1).  NULL for a dir other than 0 / 1 or more components than the call takes. */
 const char *uaes_debug_plan_siv_v(int dir, size_t len, size_t nad, size_t nmsg, int out[3]);
+/* The planner of EAX' (csrc/uaes_plan.h): "eaxp.small" / "eaxp.long" / "eaxp.batch", out as uaes_debug_plan_eax_siv; NULL for a
+ * dir other than 0 / 1.  Works without a device. */
+const char *uaes_debug_plan_eaxp(int dir, size_t len, size_t nmsg, int out[3]);
 /* The planners of the feedback modes, the CBC-MAC modes and the batches of chains (csrc/uaes_plan.h, their own rows):
  *   what   0 CBC with CS3 stealing, 1 CFB, 2 OFB, 3 CMAC, 4 CCM, 5 uaes_cbc_encrypt_batch, 6 uaes_cmac_batch,
  *          7 CBC without stealing (uaes_cbc_encrypt_padded / uaes_cbc_decrypt_blocks), 9 uaes_ccm_*_batch

@@ -55,6 +55,7 @@ EXPORTS = [
     "uaes_eax_encrypt", "uaes_eax_decrypt", "uaes_siv_encrypt", "uaes_siv_decrypt",
     "uaes_eax_encrypt_batch", "uaes_eax_decrypt_batch", "uaes_siv_encrypt_batch", "uaes_siv_decrypt_batch",
     "uaes_debug_plan_eax_siv", "uaes_debug_plan_chain",
+    "uaes_eaxp_encrypt", "uaes_eaxp_decrypt", "uaes_eaxp_encrypt_batch", "uaes_eaxp_decrypt_batch", "uaes_debug_plan_eaxp",
     "uaes_siv_encrypt_v", "uaes_siv_decrypt_v", "uaes_siv_encrypt_batch_v", "uaes_siv_decrypt_batch_v", "uaes_debug_plan_siv_v",
     "uaes_kw_wrap", "uaes_kw_unwrap", "uaes_kw_wrap_batch", "uaes_kw_unwrap_batch", "uaes_debug_plan_kw",
     "uaes_kwp_wrap", "uaes_kwp_unwrap", "uaes_kwp_wrap_batch", "uaes_kwp_unwrap_batch", "uaes_debug_plan_kwp",
@@ -89,7 +90,8 @@ COMPAT_EXPORTS = [
     "AES_OCB_encrypt", "AES_OCB_decrypt", "AES_Poly1305", "AES_KEY_wrap", "AES_KEY_unwrap",
     "AES_FPE_encrypt", "AES_FPE_decrypt", "AES_FPE_encrypt_alpha", "AES_FPE_decrypt_alpha",
     "AES_FF3_encrypt", "AES_FF3_decrypt", "AES_FF3_encrypt_alpha", "AES_FF3_decrypt_alpha",
-    "AES_EAX_encrypt", "AES_EAX_decrypt", "AES_EAX_encrypt_lens", "AES_EAX_decrypt_lens", "AES_SIV_encrypt", "AES_SIV_decrypt",
+    "AES_EAX_encrypt", "AES_EAX_decrypt", "AES_EAX_encrypt_lens", "AES_EAX_decrypt_lens", "AES_EAXP_encrypt", "AES_EAXP_decrypt",
+    "AES_SIV_encrypt", "AES_SIV_decrypt",
     "AES_CBC_encrypt", "AES_CBC_decrypt", "AES_CFB_encrypt", "AES_CFB_decrypt", "AES_OFB_encrypt", "AES_OFB_decrypt",
 ]
 
@@ -205,6 +207,12 @@ def engine():
     L.uaes_siv_decrypt_batch.argtypes = [i, vp, sz, sz, vp, sz, vp, vp, vp, vp]
     L.uaes_debug_plan_eax_siv.argtypes = [i, i, sz, sz, C.POINTER(C.c_int)]
     L.uaes_debug_plan_eax_siv.restype = C.c_char_p
+    L.uaes_eaxp_encrypt.argtypes = [i, vp, vp, sz, vp, sz, vp]
+    L.uaes_eaxp_decrypt.argtypes = [i, vp, vp, sz, vp, sz, vp]
+    L.uaes_eaxp_encrypt_batch.argtypes = [i, vp, sz, sz, vp, vp, sz, vp, vp, vp, vp]
+    L.uaes_eaxp_decrypt_batch.argtypes = [i, vp, sz, sz, vp, vp, sz, vp, vp, vp, vp, vp]
+    L.uaes_debug_plan_eaxp.argtypes = [i, sz, sz, C.POINTER(C.c_int)]
+    L.uaes_debug_plan_eaxp.restype = C.c_char_p
     L.uaes_siv_encrypt_v.argtypes = [i, vp, sz, vp, vp, vp, sz, vp, vp]
     L.uaes_siv_decrypt_v.argtypes = [i, vp, vp, sz, vp, vp, vp, sz, vp]
     L.uaes_siv_encrypt_batch_v.argtypes = [i, vp, sz, sz, vp, sz, vp, vp, vp, vp, vp]
@@ -318,7 +326,7 @@ def engine():
                      "uaes_debug_plan_eax_siv", "uaes_debug_plan_chain", "uaes_debug_plan_kw", "uaes_debug_plan_kwp", "uaes_debug_plan_ff1",
                      "uaes_debug_plan_ff3", "uaes_ff3_maxlen", "uaes_debug_plan_gcmsiv_batch", "uaes_debug_plan_ocb", "uaes_debug_plan_xts",
                      "uaes_debug_gcm_stream_tables", "uaes_debug_plan_ocb_batch", "uaes_debug_plan_gcm_multikey_batch", "uaes_debug_plan_cipher_batch",
-                     "uaes_debug_plan_xaes256gcm_batch", "uaes_debug_plan_xts_batch", "uaes_debug_plan_siv_v"):
+                     "uaes_debug_plan_xaes256gcm_batch", "uaes_debug_plan_xts_batch", "uaes_debug_plan_siv_v", "uaes_debug_plan_eaxp"):
             getattr(L, n).restype = i
     _lib = L
     return L
@@ -826,6 +834,60 @@ def eax_batch(key, nonces, aads, texts, decrypt=False, tags=None, prefill=0):
     return _aead_batch("eax", "nonce, AAD (and tag)", [nonces], aads, texts, None, decrypt, tags, 16, prefill, head)
 
 
+def eaxp_encrypt(key, nonce, pntxt):
+    """EAX' (ANSI C12.22 / IEEE 1703; micro_aes.c:1563 built with EAXP 1).  Any nonce length, no associated data;
+    returns ciphertext || 4-byte mac."""
+    o = _out(len(pntxt) + 4)
+    _check(engine().uaes_eaxp_encrypt(_bits(key), _in(key), _in(nonce), len(nonce), _in(pntxt), len(pntxt), o), "eaxp_encrypt")
+    return bytes(o)[: len(pntxt) + 4]
+
+
+def eaxp_decrypt(key, nonce, crtxt_and_mac, prefill=0):
+    """micro_aes.c:1611 built with EAXP 1.  Returns (code, text); the mac is checked first, so on 0x1A the text is the
+    untouched prefill."""
+    n = len(crtxt_and_mac) - 4
+    if n < 0:
+        raise ValueError("shorter than the mac")
+    o = _out(n, prefill)
+    rc = _check(engine().uaes_eaxp_decrypt(_bits(key), _in(key), _in(nonce), len(nonce), _in(crtxt_and_mac), n, o), "eaxp_decrypt")
+    return rc, bytes(o)[:n]
+
+
+def _eaxp_batch(key, nonces, texts, decrypt, macs, prefill, nlens, lens):
+    n = len(texts)
+    if len(nonces) != n or (decrypt and (macs is None or len(macs) != n)) or \
+            any(x is not None and len(x) != n for x in (nlens, lens)):
+        raise ValueError("one nonce (mac and lengths) per record")
+    if n == 0:
+        return (0, [], []) if decrypt else ([], [])
+    nl, nb = _records(nonces, "nonce slots")
+    ml, mb = _records(texts, "text slots")
+    nv, lv = ((C.c_uint32 * n)(*x) if x is not None else None for x in (nlens, lens))
+    a = (_bits(key), _in(key), n, nl, nv, _in(nb), ml, lv)
+    o = _out(n * ml, prefill)
+    if not decrypt:
+        t = _out(n * 4)
+        _check(engine().uaes_eaxp_encrypt_batch(*a, _in(mb), o, t), "uaes_eaxp_encrypt_batch")
+        return _split(bytes(o), ml, n), _split(bytes(t), 4, n)
+    if any(len(x) != 4 for x in macs):
+        raise ValueError("4-byte macs")
+    v = _out(n)
+    rc = _check(engine().uaes_eaxp_decrypt_batch(*a, _in(mb), _in(b"".join(macs)), o, v), "uaes_eaxp_decrypt_batch")
+    return rc, _split(bytes(o), ml, n), list(bytes(v)[:n])
+
+
+def eaxp_encrypt_batch(key, nonces, texts, nlens=None, lens=None, prefill=0):
+    """EAX' of many records under one key (uaes_eaxp_encrypt_batch): equal-sized nonce slots and text slots; nlens / lens
+    (optional, one per record): record m is the first lens[m] bytes of its text under the first nlens[m] bytes of its
+    nonce, and the rest of its output slot stays the prefill.  Returns (ciphertexts, 4-byte macs)."""
+    return _eaxp_batch(key, nonces, texts, False, None, prefill, nlens, lens)
+
+
+def eaxp_decrypt_batch(key, nonces, texts, macs, nlens=None, lens=None, prefill=0):
+    """uaes_eaxp_decrypt_batch.  Returns (code, plaintexts, verdicts); a forged record's plaintext stays the prefill."""
+    return _eaxp_batch(key, nonces, texts, True, macs, prefill, nlens, lens)
+
+
 def ccm_batch(key, nonces, aads, texts, tag_len=16, decrypt=False, tags=None, prefill=0, lens=None):
     """CCM of many records under one key (uaes_ccm_*_batch): equal-sized nonces (7..13 bytes), AADs (or None) and
     texts.  encrypt: returns (ciphertexts, tag_len-byte tags); decrypt (tags given): returns (code, plaintexts,
@@ -990,6 +1052,13 @@ def eax_siv_plan(siv, length, nmsg=1, decrypt=False):
     longest text of the small arrangement)."""
     out = (C.c_int * 3)()
     name = engine().uaes_debug_plan_eax_siv(int(bool(siv)), int(bool(decrypt)), length, nmsg, out)
+    return name.decode(), out[0], out[1], out[2]
+
+
+def eaxp_plan(length, nmsg=1, decrypt=False):
+    """What an EAX' call would run (uaes_debug_plan_eaxp): as eax_siv_plan."""
+    out = (C.c_int * 3)()
+    name = engine().uaes_debug_plan_eaxp(int(bool(decrypt)), length, nmsg, out)
     return name.decode(), out[0], out[1], out[2]
 
 

@@ -433,6 +433,25 @@ char AES_EAX_decrypt_lens(const size_t nonceLen, const size_t tagLen, const uint
                 M_DECRYPTION_ERROR);
 }
 
+/* EAX' (the reference built with EAXP 1): what include/micro_aes.h binds AES_EAX_* to under -DEAX=1 -DEAXP=1; declared
+ * here because this file sees the header with EAXP 0 */
+void AES_EAXP_encrypt(const uint8_t *key, const uint8_t *nonce, const size_t nonceLen,
+                      const void *pntxt, const size_t ptextLen, void *crtxt);
+char AES_EAXP_decrypt(const uint8_t *key, const uint8_t *nonce, const size_t nonceLen,
+                      const void *crtxt, const size_t crtxtLen, void *pntxt);
+
+void AES_EAXP_encrypt(const uint8_t *key, const uint8_t *nonce, const size_t nonceLen,
+                      const void *pntxt, const size_t ptextLen, void *crtxt)
+{
+    must("AES_EAX_encrypt", uaes_eaxp_encrypt(KB, key, nonce, nonceLen, pntxt, ptextLen, crtxt));
+}
+
+char AES_EAXP_decrypt(const uint8_t *key, const uint8_t *nonce, const size_t nonceLen,
+                      const void *crtxt, const size_t crtxtLen, void *pntxt)
+{
+    return soft("AES_EAX_decrypt", uaes_eaxp_decrypt(KB, key, nonce, nonceLen, crtxt, crtxtLen, pntxt), M_DECRYPTION_ERROR);
+}
+
 void AES_EAX_encrypt(const uint8_t *key, const uint8_t *nonce,
                      const void *aData, const size_t aDataLen,
                      const void *pntxt, const size_t ptextLen, void *crtxt)

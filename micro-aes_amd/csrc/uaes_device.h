@@ -336,6 +336,20 @@ int uaesk_eax_batch(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk
 int uaesk_s2v_batch(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek_s2v, const uaesk_rk *ek_ctr,
                     int decrypt, int wipe, const void *aad, size_t aad_bytes,
                     size_t nmsg, size_t msg_bytes, const void *in, void *out, void *ivs, void *verdicts, int *bad);
+/* EAX' (the reference built with EAXP 1; uaes_eax_siv.hip), the same three forms without associated data and with a
+ * 4-byte mac at any byte offset.  uaesk_eaxp_small: as uaesk_eax_small (len <= UAES_EAX_SIV_SMALL_MAX).
+ * uaesk_eaxp_macs: mode 0 = N into res48 (the counter block N' at +16, N's last four bytes at +32); 1 = N || C', the mac
+ * compared with mac_io (status at +0, N' at +16); 2 = C' only over ct, the mac (with +32 of res48) to mac_io.
+ * uaesk_eaxp_batch: record m's nonce is the first nlens[m] bytes at nonces + m nonce_bytes, its text the first lens[m]
+ * bytes at in / out + m msg_bytes (NULL: the whole slot; else 4-byte aligned device memory, a longer entry counts as the
+ * slot), its mac at macs + 4 m; verdicts may be NULL; a forged record's output is not written. */
+int uaesk_eaxp_small(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, int decrypt,
+                     const void *nonce, size_t nonce_len, const void *in, size_t len, void *out, void *mac_io, int *status);
+int uaesk_eaxp_macs(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, int mode,
+                    const void *nonce, size_t nonce_len, const void *ct, size_t len, void *mac_io, void *res48);
+int uaesk_eaxp_batch(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, int decrypt,
+                     const void *nonces, size_t nonce_bytes, const void *nlens, size_t nmsg, size_t msg_bytes,
+                     const void *lens, const void *in, void *out, void *macs, void *verdicts, int *bad);
 /* S2V over nad components of associated data (RFC 5297 section 2.4).  uaesk_s2v_v: component i is aad[ends[i - 1] ..
  * ends[i]) with ends = nad running totals of the lengths, uint64 each, device memory, 8-byte aligned (nad <=
  * UAES_S2V_AD_MAX; an empty component is one); ctr != 0: a text of <= UAES_EAX_SIV_SMALL_MAX bytes and CTR in the same

@@ -21,6 +21,9 @@
  *   k_eax_macs / k_s2v_macs     the chains of a longer message in one launch; the counter block and the verdict go
  *                               back to the host, which runs the existing positioned CTR kernels (uaesk_ctr_xcrypt)
  *   k_eax_batch / k_s2v_batch   nmsg records under one key, sixteen lanes per record (as k_chain_batch_row)
+ *
+ * EAX' (the reference built with EAXP 1, :1523-1648) has kernels of its own on the same frame, k_eaxp_small /
+ * k_eaxp_macs / k_eaxp_batch: see its section below.
  */
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -710,6 +713,199 @@ __global__ __launch_bounds__(UAES_WG) void k_s2v_batch_v(uaesk_rk rk, uaesk_rk r
     }
 }
 
+/* ---- EAX' (ANSI C12.22 / IEEE 1703; the reference built with EAXP 1, :1523-1648) ---------------------------------- */
+/* L = Enc(0), D = dblLE(L), Q = dblLE(D).  CMAC'(start, X) is CMAC with D / Q as its subkeys and a chaining value that
+ * starts at `start`; N = CMAC'(D, nonce), N' = N with the top bits of bytes 12 and 14 cleared, C = CTR(N', P) with the
+ * 56-bit counter, C' = CMAC'(Q, C) (0^128 for an empty C, oMac :1535-1539), mac = N[12..15] ^ C'[12..15]: column 3.  No
+ * associated data, so a call has one chain fewer than EAX.  Minematsu, Lucks, Morita and Iwata (2013) forge EAX' when
+ * nonce and text are both at most one block; such inputs are taken all the same, as the reference takes them. */
+
+/* little-endian doubling (doubleLblock :449-458): the block as a little-endian 128-bit integer, 0x87 into byte 0 */
+__device__ __forceinline__ void dbl_le(u32 (&b)[4])
+{
+    const u32 carry = b[3] >> 31;
+    b[3] = (b[3] << 1) | (b[2] >> 31);
+    b[2] = (b[2] << 1) | (b[1] >> 31);
+    b[1] = (b[1] << 1) | (b[0] >> 31);
+    b[0] = (b[0] << 1) ^ (carry ? 0x87u : 0u);
+}
+
+/* D and Q: this lane's columns */
+template <int NR>
+__device__ __forceinline__ void cmac_subkeys_le(const RowLane<NR> &L, u32 &dc, u32 &qc)
+{
+    u32 b[4];
+    row_gather(row_encrypt<NR>(0u, L), b);
+    dbl_le(b);
+    dc = row_pick(b, L.c);
+    dbl_le(b);
+    qc = row_pick(b, L.c);
+}
+
+/* CMAC'(start, p[0 .. len)); the empty string is one padded empty block (cMac :579-589 with dataSize 0) */
+template <int NR>
+__device__ __forceinline__ u32 cmac_prime(u32 start, const unsigned char *p, u64 len, const RowLane<NR> &L, u32 dc, u32 qc)
+{
+    if (!len) return row_encrypt<NR>(start ^ pad_col(0u, L.c) ^ qc, L);
+    return cmac_more<NR>(start, p, len, L, dc, qc);
+}
+
+/* C' of a ciphertext in memory */
+template <int NR>
+__device__ __forceinline__ u32 eaxp_cmac_text(const unsigned char *p, u64 len, const RowLane<NR> &L, u32 dc, u32 qc)
+{
+    return len ? cmac_prime<NR>(qc, p, len, L, dc, qc) : 0u;
+}
+
+/* N -> the counter of CTR(N'): mac[12] &= 0x7F, mac[14] &= 0x7F (:1581-1582), bits 7 and 23 of the little-endian column 3 */
+__device__ __forceinline__ uaesk_ctr eaxp_ctr(const u32 (&n)[4])
+{
+    const u32 v[4] = { n[0], n[1], n[2], n[3] & ~0x00800080u };
+    return ctr_of(v);
+}
+
+/* the four bytes of a mac at any byte offset */
+__device__ __forceinline__ u32 mac_get(const unsigned char *p)
+{
+    if ((((uintptr_t)p) & 3u) == 0) return *(const u32 *)p;
+    return (u32)p[0] | ((u32)p[1] << 8) | ((u32)p[2] << 16) | ((u32)p[3] << 24);
+}
+
+__device__ __forceinline__ void mac_put(unsigned char *p, u32 w)
+{
+    if ((((uintptr_t)p) & 3u) == 0) { *(u32 *)p = w; return; }
+    p[0] = (unsigned char)w; p[1] = (unsigned char)(w >> 8); p[2] = (unsigned char)(w >> 16); p[3] = (unsigned char)(w >> 24);
+}
+
+/* EAX' of a short message.  Encrypt: wave 0 makes N, all rows run CTR(N'), then wave 0 makes C' of the ciphertext and
+ * writes the mac to mac_io.  Decrypt: N and C' in waves 0 and 1, the mac compared with mac_io (*status = 0 / 0x1A), and
+ * CTR writes only an authentic text (:1631-1644). */
+template <int NR, bool DEC>
+__global__ __launch_bounds__(SMALL_WG) void k_eaxp_small(uaesk_rk rk, uaesk_tables tb, const unsigned char *nonce, u64 nonce_len,
+                                                         const unsigned char *in, u64 len, unsigned char *out,
+                                                         unsigned char *mac_io, int *status)
+{
+    row4_fill_tables(tb.te0, rk);
+    const RowLane<NR> L = row4_lane<NR>();
+    u32 dc, qc;
+    cmac_subkeys_le<NR>(L, dc, qc);
+    u32 *xch = (u32 *)(uaes_lds + E4_XCH);
+    const u32 wave = threadIdx.x >> 6;
+    const bool put = (threadIdx.x & 63u) < 16u && (threadIdx.x & 3u) == 0;      /* row 0 of a wave, one lane per column */
+    if (wave == 0) {
+        const u32 v = cmac_prime<NR>(dc, nonce, nonce_len, L, dc, qc);
+        if (put) xch[L.c] = v;
+    } else if (DEC && wave == 1) {
+        const u32 v = eaxp_cmac_text<NR>(in, len, L, dc, qc);
+        if (put) xch[4 + L.c] = v;
+    }
+    __syncthreads();
+    u32 n[4];
+#pragma unroll
+    for (u32 k = 0; k < 4; ++k) n[k] = xch[k];
+    const uaesk_ctr ctr = eaxp_ctr(n);
+    if (DEC) {
+        const u32 diff = n[3] ^ xch[7] ^ mac_get(mac_io);
+        if (threadIdx.x == 0) *status = diff ? 0x1A : 0;
+        if (diff) return;                                    /* the same verdict in every thread */
+        ctr_rows<NR>(ctr, in, out, len, L);
+    } else {
+        ctr_rows<NR>(ctr, in, out, len, L);
+        __syncthreads();                                     /* the ciphertext is in memory for wave 0 */
+        if (wave == 0) {
+            const u32 c = eaxp_cmac_text<NR>(out, len, L, dc, qc);
+            if (threadIdx.x == 12) mac_put(mac_io, c ^ n[3]);                   /* column 3 of row 0 */
+        }
+    }
+}
+
+/* The chains of a longer message, one wave per chain; res (device, 48 bytes) as k_eax_macs has it.  mode 0: N (encrypt:
+ * res gets the counter block N' at 16 and N's column 3 at 32); 1: N || C' (decrypt: the mac compared with mac_io, res
+ * gets the status and N'); 2: C' only (encrypt, after CTR: the mac to mac_io). */
+template <int NR>
+__global__ __launch_bounds__(128) void k_eaxp_macs(uaesk_rk rk, uaesk_tables tb, int mode, const unsigned char *nonce, u64 nonce_len,
+                                                   const unsigned char *ct, u64 len, unsigned char *mac_io, unsigned char *res)
+{
+    row_fill_tables(tb.te0, rk);
+    const RowLane<NR> L = row_lane<NR>();
+    u32 dc, qc;
+    cmac_subkeys_le<NR>(L, dc, qc);
+    u32 *xch = (u32 *)(uaes_lds + ER_XCH);
+    const u32 slot = mode == 2 ? 1u : threadIdx.x >> 6;      /* 0 = N, 1 = C' */
+    const u32 v = slot == 0 ? cmac_prime<NR>(dc, nonce, nonce_len, L, dc, qc) : eaxp_cmac_text<NR>(ct, len, L, dc, qc);
+    if ((threadIdx.x & 63u) < 16u && (threadIdx.x & 3u) == 0) xch[4 * slot + L.c] = v;
+    __syncthreads();
+    u32 *r32 = (u32 *)res;
+    if (mode == 2) {
+        if (threadIdx.x == 0) mac_put(mac_io, xch[7] ^ r32[8]);
+        return;
+    }
+    if (threadIdx.x < 4) r32[4 + threadIdx.x] = threadIdx.x == 3 ? xch[3] & ~0x00800080u : xch[threadIdx.x];
+    if (threadIdx.x == 0) {
+        if (mode == 0) r32[8] = xch[3];
+        else r32[0] = (xch[3] ^ xch[7] ^ mac_get(mac_io)) ? 0x1Au : 0u;
+    }
+}
+
+/* EAX' encryption of one record in one row: C_i = P_i ^ Enc(N' + i) and C' in the same pass, as eax_text_enc */
+template <int NR, bool A4>
+__device__ __forceinline__ u32 eaxp_text_enc(const uaesk_ctr &ctr, const unsigned char *in, unsigned char *out, u64 len,
+                                             const RowLane<NR> &L, u32 dc, u32 qc)
+{
+    if (!len) return 0u;
+    const u32 s = (u32)((len - 1) % 16) + 1;
+    const u64 full = (len - s) / 16;
+    u32 m = qc, ks = row_encrypt<NR>(ctr_col(ctr, 0, L.c), L);
+    row_walk<A4>(in, full, L.c, [&](u64 i, u32 x) {
+        const u32 y = x ^ ks;
+        row_store_full<A4>(out + 16 * i, y, L.c);
+        m ^= y;
+        ks = ctr_col(ctr, i + 1, L.c);
+        row_encrypt2<NR>(m, ks, L, L);
+    });
+    const u32 y = (row_load(in + 16 * full, s, L.c) ^ ks) & row_keep(s, L.c);
+    row_put(out + 16 * full, y, s, L.c);
+    return row_encrypt<NR>(m ^ y ^ (s < 16 ? pad_col(s, L.c) ^ qc : dc), L);
+}
+
+/* Batches: record m is the first lens[m] bytes of its text slot (in / out + m msg_bytes) under the first nlens[m] bytes
+ * of its nonce slot (nonces + m nonce_bytes); NULL lens / nlens: the whole slot, a longer entry counts as the slot.  Its
+ * mac is the four bytes at macs + 4 m.  Decrypt: verdicts (may be NULL) and bad as k_eax_batch, a forged record's output
+ * untouched; the rest of an output slot is not written. */
+template <int NR, bool DEC, bool A4>
+__global__ __launch_bounds__(UAES_WG) void k_eaxp_batch(uaesk_rk rk, uaesk_tables tb, const unsigned char *nonces, u32 nonce_bytes,
+                                                        const u32 *nlens, u64 nmsg, u32 msg_bytes, const u32 *lens,
+                                                        const unsigned char *in, unsigned char *out,
+                                                        unsigned char *macs, unsigned char *verdicts, int *bad)
+{
+    row4_fill_tables(tb.te0, rk);
+    const RowLane<NR> L = row4_lane<NR>();
+    u32 dc, qc;
+    cmac_subkeys_le<NR>(L, dc, qc);
+    const u64 rows = blockDim.x >> 4;
+    for (u64 m = (u64)blockIdx.x * rows + (threadIdx.x >> 4); m < nmsg; m += (u64)gridDim.x * rows) {
+        u32 len = msg_bytes, nl = nonce_bytes;
+        if (lens) { len = lens[m]; if (len > msg_bytes) len = msg_bytes; }
+        if (nlens) { nl = nlens[m]; if (nl > nonce_bytes) nl = nonce_bytes; }
+        const u32 n = cmac_prime<NR>(dc, nonces + m * nonce_bytes, nl, L, dc, qc);
+        u32 nb[4], d[4];
+        row_gather(n, nb);
+        const uaesk_ctr ctr = eaxp_ctr(nb);
+        const unsigned char *src = in + m * msg_bytes;
+        unsigned char *dst = out + m * msg_bytes;
+        unsigned char *mac = macs + 4 * m;
+        if (!DEC) {
+            row_gather(eaxp_text_enc<NR, A4>(ctr, src, dst, len, L, dc, qc), d);
+            if ((threadIdx.x & 15u) == 0) mac_put(mac, nb[3] ^ d[3]);
+        } else {
+            row_gather(eaxp_cmac_text<NR>(src, len, L, dc, qc), d);
+            const bool ok = (nb[3] ^ d[3]) == mac_get(mac);
+            row_verdict<true>((threadIdx.x & 15u) == 0, verdicts, m, ok, bad);
+            if (ok) ctr_row<NR, A4>(ctr, src, dst, len, L);
+        }
+    }
+}
+
 /* ---- launchers ---------------------------------------------------------------------------------------------------- */
 static uint4 uint4_of(const uint8_t *b)
 {
@@ -884,6 +1080,38 @@ extern "C" int uaesk_s2v_batch_v(void *stream, const uaesk_tables *tb, int nr, c
     return 0;
 }
 
+extern "C" int uaesk_eaxp_small(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, int decrypt,
+                                const void *nonce, size_t nonce_len, const void *in, size_t len, void *out, void *mac_io, int *status)
+{
+    if (len > UAES_EAX_SIV_SMALL_MAX) return (int)hipErrorInvalidValue;
+    DISPATCH_NR(nr, return with_bool(decrypt, [&](auto DEC) {
+        return uaesk_launch(k_eaxp_small<NR, decltype(DEC)::value>, 1, SMALL_WG, E4_LDS, S(stream), *ek, *tb, nonce, nonce_len,
+                            in, len, out, mac_io, status); }));
+    return 0;
+}
+
+extern "C" int uaesk_eaxp_macs(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, int mode,
+                               const void *nonce, size_t nonce_len, const void *ct, size_t len, void *mac_io, void *res48)
+{
+    if (mode < 0 || mode > 2) return (int)hipErrorInvalidValue;
+    DISPATCH_NR(nr, return uaesk_launch(k_eaxp_macs<NR>, 1, mode == 1 ? 128 : 64, ER_LDS, S(stream), *ek, *tb, mode, nonce, nonce_len,
+                                        ct, len, mac_io, res48));
+    return 0;
+}
+
+extern "C" int uaesk_eaxp_batch(void *stream, const uaesk_tables *tb, int nr, const uaesk_rk *ek, int decrypt,
+                                const void *nonces, size_t nonce_bytes, const void *nlens, size_t nmsg, size_t msg_bytes,
+                                const void *lens, const void *in, void *out, void *macs, void *verdicts, int *bad)
+{
+    if (nonce_bytes > UINT32_MAX || msg_bytes > UINT32_MAX || (((uintptr_t)lens | (uintptr_t)nlens) & 3u)) return (int)hipErrorInvalidValue;
+    if (nmsg == 0) return 0;
+    const RowShape s = uaesk_row_shape(nmsg);
+    DISPATCH_NR(nr, return with_bool(decrypt, [&](auto DEC) { return with_bool(uaesk_rows_a4(in, out, msg_bytes), [&](auto A4) {
+        return uaesk_launch(k_eaxp_batch<NR, decltype(DEC)::value, decltype(A4)::value>, s.grid, s.wg, E4_LDS, S(stream), *ek, *tb,
+                            nonces, nonce_bytes, nlens, nmsg, msg_bytes, lens, in, out, macs, verdicts, bad); }); }));
+    return 0;
+}
+
 /* ---- the plan (uaes_plan.h) --------------------------------------------------------------------------------------- */
 extern "C" int uaesk_plan_eax_siv(int siv, int dir, size_t len, size_t nmsg, uaes_plan *p)
 {
@@ -925,9 +1153,26 @@ extern "C" int uaesk_plan_siv_v(int dir, size_t len, size_t nad, size_t nmsg, ua
     return 0;
 }
 
+/* EAX': the same boundary; a longer encryption is N, CTR, C', a longer decryption N || C' and CTR for an authentic text */
+extern "C" int uaesk_plan_eaxp(int dir, size_t len, size_t nmsg, uaes_plan *p)
+{
+    memset(p, 0, sizeof *p);
+    if (dir != 0 && dir != 1) return (int)hipErrorInvalidValue;
+    if (nmsg > 1) {
+        p->arrangement = UAES_EAXP_BATCH;
+        p->launches = 1;
+        p->grid = uaesk_row_shape(nmsg).grid;
+        return 0;
+    }
+    p->grid = 1;
+    p->arrangement = len <= UAES_EAX_SIV_SMALL_MAX ? UAES_EAXP_SMALL : UAES_EAXP_LONG;
+    p->launches = len <= UAES_EAX_SIV_SMALL_MAX ? 1 : dir ? 2 : 3;
+    return 0;
+}
+
 extern "C" const char *uaesk_eax_siv_arrangement_name(int id)
 {
     static const char *const names[] = { "eax.small", "eax.long", "eax.batch", "s2v.small", "s2v.long", "s2v.batch",
-                                         "s2v.small.v", "s2v.long.v", "s2v.batch.v" };
-    return id >= 0 && id < 9 ? names[id] : "?";
+                                         "s2v.small.v", "s2v.long.v", "s2v.batch.v", "eaxp.small", "eaxp.long", "eaxp.batch" };
+    return id >= 0 && id < 12 ? names[id] : "?";
 }

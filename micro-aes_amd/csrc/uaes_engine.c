@@ -1463,6 +1463,14 @@ const char *uaes_debug_plan_eax_siv(int siv, int dir, size_t len, size_t nmsg, i
     if (out) { out[0] = p.launches; out[1] = (int)p.grid; out[2] = (int)UAES_EAX_SIV_SMALL_MAX; }
     return uaesk_eax_siv_arrangement_name(p.arrangement);
 }
+const char *uaes_debug_plan_eaxp(int dir, size_t len, size_t nmsg, int out[3])
+{
+    uaes_plan p;
+    memset(&p, 0, sizeof p);
+    if (uaesk_plan_eaxp(dir, len, nmsg, &p)) return NULL;
+    if (out) { out[0] = p.launches; out[1] = (int)p.grid; out[2] = (int)UAES_EAX_SIV_SMALL_MAX; }
+    return uaesk_eax_siv_arrangement_name(p.arrangement);
+}
 const char *uaes_debug_plan_siv_v(int dir, size_t len, size_t nad, size_t nmsg, int out[3])
 {
     uaes_plan p;

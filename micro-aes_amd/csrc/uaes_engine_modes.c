@@ -1,5 +1,5 @@
 /*
- * uaes_engine_modes.c -- entry points of the modes other than GCM: ECB, CTR, XTS, CMAC, Poly1305, CCM, EAX, SIV,
+ * uaes_engine_modes.c -- entry points of the modes other than GCM: ECB, CTR, XTS, CMAC, Poly1305, CCM, EAX, EAX', SIV,
  * CBC / CFB / OFB, the chain batches, OCB, key wrap (KW and KWP), FF1 and FF3-1.  They mirror the reference's mode
  * drivers (AES_ECB_*, AES_CTR_*, AES_XTS_* ...; micro_aes.c:636-680, :962-990, :1066-1093): argument checking, the
  * reference's error behaviour and buffer plumbing on top of the core (uaes_engine.c, through uaes_engine.h).
@@ -663,6 +663,84 @@ int uaes_eax_decrypt(int keybits, const uint8_t *key, const uint8_t *nonce, size
     return eax_common(keybits, key, 1, nonce, nonceLen, tagLen, aData, aDataLen, crtxt, crtxtLen, pntxt);
 }
 
+/* EAX' (the reference built with EAXP 1, :1523-1648): eax_common's shape without associated data and with the 4-byte mac
+ * behind the text; the kernels hand back N' as the counter block (k_eaxp_small / k_eaxp_macs, uaes_eax_siv.hip) */
+static int eaxp_common(int keybits, const uint8_t *key, int decrypt, const uint8_t *nonce, size_t nonceLen,
+                       const void *in, size_t len, void *outp)
+{
+    context *c;
+    lane *L;
+    KEYSCHED(ks);
+    io_plan io;
+    const void *d_nonce;
+    size_t off = 0;
+    int rc, k, status = 0;
+    uint8_t res[32];
+    if ((rc = expand_key(&ks, key, keybits)) != 0) return rc;
+    if (!in || (len && !outp) || (nonceLen && !nonce)) return fail(UAES_E_ARG, "NULL pointer");
+    if (!decrypt && !outp) return fail(UAES_E_ARG, "NULL pointer");
+    if (len > (size_t)-1 - 64) return fail(UAES_E_ARG, "the text length overflows");
+    if (host_take(in, outp, len, 1) && !is_device_ptr(nonce)) {
+        const uaesh_key hk = host_key(&ks);
+        return host_result(uaesh_eaxp(&hk, decrypt, nonce, nonceLen, (const uint8_t *)in, len, (uint8_t *)outp));
+    }
+    if ((rc = enter(&c, &L)) != 0) return rc;
+    if ((rc = lane_scratch(L, SIDE(nonceLen), SCRATCH_OTHER)) != 0) goto out;
+    if ((rc = side_in(L, &off, nonce, nonceLen, &d_nonce)) != 0) goto out;
+    if (decrypt) rc = plan_io(L, in, len + 4, outp, len, &io);
+    else rc = plan_io(L, in, len, outp, len + 4, &io);
+    if (rc) goto out;
+    {
+        unsigned char *mac = decrypt ? (unsigned char *)io.din + len : (unsigned char *)io.dout + len;
+        if (len <= UAES_EAX_SIV_SMALL_MAX) {             /* eaxp.small: one launch */
+            k = uaesk_eaxp_small(L->stream, &c->tb, ks.nr, &ks.ek, decrypt, d_nonce, nonceLen, io.din, len, io.dout, mac,
+                                 decrypt ? L->d_status : NULL);
+            if ((rc = launched("eax'", k)) != 0) goto out;
+            if (decrypt) {
+                if ((rc = lane_fetch(L, &status, L->d_status, sizeof status)) != 0) goto out;
+                io.drained = 1;
+            }
+        } else {                                          /* eaxp.long: the chains, one fetch, then CTR */
+            uaesk_ctr ctr;
+            k = uaesk_eaxp_macs(L->stream, &c->tb, ks.nr, &ks.ek, decrypt ? 1 : 0, d_nonce, nonceLen, decrypt ? io.din : NULL,
+                                decrypt ? len : 0, mac, L->d_status);
+            if ((rc = launched("eax'", k)) != 0) goto out;
+            if ((rc = lane_fetch(L, res, L->d_status, sizeof res)) != 0) goto out;
+            memcpy(&status, res, sizeof status);
+            if (decrypt && status) {
+                io.drained = 1;
+            } else {
+                make_ctr(&ctr, res + 16, 0);
+                k = uaesk_ctr_xcrypt(L->stream, &c->tb, ks.nr, &ks.ek, &ctr, io.din, io.dout, len, NULL);
+                if ((rc = launched("eax' ctr", k)) != 0) goto out;
+                if (!decrypt) {
+                    k = uaesk_eaxp_macs(L->stream, &c->tb, ks.nr, &ks.ek, 2, NULL, 0, io.dout, len, mac, L->d_status);
+                    if ((rc = launched("eax'", k)) != 0) goto out;
+                }
+            }
+        }
+    }
+    /* the mac is checked before anything is written (:1631-1643): a forgery leaves pntxt as it was */
+    if (decrypt && status) rc = UAES_E_AUTHENTICATION;
+    else rc = finish_io(&io, decrypt ? len : len + 4);
+out:
+    memset(res, 0, sizeof res);
+    DONE(L, rc);
+}
+
+int uaes_eaxp_encrypt(int keybits, const uint8_t *key, const uint8_t *nonce, size_t nonceLen,
+                      const void *pntxt, size_t ptextLen, void *crtxt)
+{
+    if (!pntxt && !ptextLen) pntxt = crtxt;                       /* (nothing is read) */
+    return eaxp_common(keybits, key, 0, nonce, nonceLen, pntxt, ptextLen, crtxt);
+}
+
+int uaes_eaxp_decrypt(int keybits, const uint8_t *key, const uint8_t *nonce, size_t nonceLen,
+                      const void *crtxt, size_t crtxtLen, void *pntxt)
+{
+    return eaxp_common(keybits, key, 1, nonce, nonceLen, crtxt, crtxtLen, pntxt);
+}
+
 static int siv_keys(keysched *k1, keysched *k2, const uint8_t *keys, int keybits)
 {
     int rc;
@@ -797,12 +875,12 @@ int uaes_siv_decrypt_v(int keybits, const uint8_t *keys, const uint8_t iv[16], s
     return siv_common(keybits, keys, 1, (uint8_t *)iv, 1, nad, adLens, aData, crtxt, crtxtLen, pntxt);
 }
 
-/* ---- AEAD record batches: EAX, SIV, CCM, GCM-SIV, multi-key GCM, XAES-256-GCM and OCB ----
+/* ---- AEAD record batches: EAX, EAX', SIV, CCM, GCM-SIV, multi-key GCM, XAES-256-GCM and OCB ----
  * nmsg records of msg_bytes each in one launch, sixteen lanes per record.  Every array may be host or device memory;
  * host arrays travel through the lane's staging buffers and scratch.  A mode checks its own limits, describes the call
  * in an aead_rows and hands it to aead_rows_run, which does everything the modes share, in this order: the sizes, the
  * key, nothing more for no records, the pointers, and only then the device.  What a mode adds is its launch.       */
-enum { AB_KEYS, AB_NONCES, AB_AAD, AB_LENS, AB_TAGS, AB_VERDICTS, AB_NSIDE };      /* the side arrays, in scratch order */
+enum { AB_KEYS, AB_NONCES, AB_NLENS, AB_AAD, AB_LENS, AB_TAGS, AB_VERDICTS, AB_NSIDE };      /* the side arrays, in scratch order (AB_NLENS: EAX' alone) */
 
 typedef struct aead_rows aead_rows;
 struct aead_rows {
@@ -922,6 +1000,63 @@ int uaes_siv_decrypt_batch(int keybits, const uint8_t *keys, size_t nmsg, size_t
 {
     return eax_siv_batch(1, 1, keybits, keys, nmsg, msg_bytes, NULL, 0, aData, aad_bytes, crtxt, pntxt, (uint8_t *)ivs,
                          verdicts);
+}
+
+/* EAX' batches (k_eaxp_batch, uaes_eax_siv.hip): no associated data, 4-byte macs, and a length per nonce (nlens) as well
+ * as per text (lens).  A decryption writes only authentic records, so its output starts as the caller's buffer.  What
+ * this call checks comes first: the slot sizes, the lengths; then aead_rows_run's order.  An array of lengths in host
+ * memory is read here and an entry above its slot refused; one in device memory is read by the kernel alone, which takes
+ * such an entry as the slot. */
+static int eaxp_batch_launch(const aead_rows *b, context *c, lane *L, const keysched *const ks[2], const row_array *a, const row_text *t)
+{
+    return uaesk_eaxp_batch(L->stream, &c->tb, ks[0]->nr, &ks[0]->ek, b->decrypt, a[AB_NONCES].d, b->side[AB_NONCES].each,
+                            a[AB_NLENS].d, b->nmsg, b->msg_bytes, a[AB_LENS].d, t->d_in, t->d_out, a[AB_TAGS].d, a[AB_VERDICTS].d,
+                            L->d_status);
+}
+
+static int eaxp_lens_ok(const char *what, const uint32_t *lens, size_t nmsg, size_t slot)
+{
+    size_t m;
+    if (!lens) return 0;
+    if (is_device_ptr(lens))
+        return ((uintptr_t)lens & 3u) ? fail(UAES_E_ARG, "a device array of lengths must be 4-byte aligned") : 0;
+    for (m = 0; m < nmsg; ++m)
+        if (lens[m] > slot) return fail(UAES_E_ARG, "%s length %zu is %u, above its slot of %zu bytes", what, m, lens[m], slot);
+    return 0;
+}
+
+static int eaxp_batch(int decrypt, int keybits, const uint8_t *key, size_t nmsg, size_t nonce_bytes, const uint32_t *nlens,
+                      const uint8_t *nonces, size_t msg_bytes, const uint32_t *lens, const void *in, void *outp,
+                      uint8_t *macs, uint8_t *verdicts)
+{
+    const aead_rows b = {
+        .name = "eax' batch", .launch = eaxp_batch_launch, .nkeys = 1, .keybits = keybits, .key = key, .decrypt = decrypt,
+        .prefill = decrypt, .nmsg = nmsg, .msg_bytes = msg_bytes, .in = in, .out = outp,
+        .side = { [AB_NONCES] = { nonces, nonce_bytes }, [AB_NLENS] = { nlens, nlens ? sizeof *nlens : 0 },
+                  [AB_LENS] = { lens, lens ? sizeof *lens : 0 }, [AB_TAGS] = { macs, 4 },
+                  [AB_VERDICTS] = { verdicts, decrypt && verdicts } } };      /* (a caller may do without verdicts) */
+    int rc;
+    if (msg_bytes > UINT32_MAX || nonce_bytes > UINT32_MAX)
+        return fail(UAES_E_ARG, "a batch slot holds at most %u bytes (got %zu of text, %zu of nonce)", UINT32_MAX, msg_bytes, nonce_bytes);
+    if (nmsg > (size_t)-1 / 8 / (msg_bytes > nonce_bytes ? msg_bytes | 4 : nonce_bytes | 4))     /* (before lens is walked) */
+        return fail(UAES_E_ARG, "batch size overflows");
+    if (nmsg && (rc = eaxp_lens_ok("nonce", nlens, nmsg, nonce_bytes)) != 0) return rc;
+    if (nmsg && (rc = eaxp_lens_ok("text", lens, nmsg, msg_bytes)) != 0) return rc;
+    return aead_rows_run(&b);
+}
+
+int uaes_eaxp_encrypt_batch(int keybits, const uint8_t *key, size_t nmsg, size_t nonce_bytes, const uint32_t *nlens,
+                            const uint8_t *nonces, size_t msg_bytes, const uint32_t *lens,
+                            const void *pntxt, void *crtxt, uint8_t *macs)
+{
+    return eaxp_batch(0, keybits, key, nmsg, nonce_bytes, nlens, nonces, msg_bytes, lens, pntxt, crtxt, macs, NULL);
+}
+
+int uaes_eaxp_decrypt_batch(int keybits, const uint8_t *key, size_t nmsg, size_t nonce_bytes, const uint32_t *nlens,
+                            const uint8_t *nonces, size_t msg_bytes, const uint32_t *lens,
+                            const void *crtxt, const uint8_t *macs, void *pntxt, uint8_t *verdicts)
+{
+    return eaxp_batch(1, keybits, key, nmsg, nonce_bytes, nlens, nonces, msg_bytes, lens, crtxt, pntxt, (uint8_t *)macs, verdicts);
 }
 
 /* SIV batches with the component vector and a length per record (k_s2v_batch_v): every record's AAD slot, sum(adLens)

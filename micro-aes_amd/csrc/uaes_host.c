@@ -619,6 +619,50 @@ int uaesh_eax(const uaesh_key *k, int decrypt, const uint8_t *nonce, size_t nonc
     return rc;
 }
 
+/* EAX' (the reference built with EAXP 1, :1523-1648): D = dblLE(Enc(0)) and Q = dblLE(D) (xts_double is doubleLblock)
+ * are CMAC's subkeys, the chain of N = CMAC'(nonce) starts at D and the one of C' = CMAC'(ciphertext) at Q; an empty
+ * string is one padded empty block (cMac :579-589), but an empty ciphertext gives C' = 0 (oMac :1535-1539) */
+static void eaxp_cmac(const uaesh_key *k, const cmac_keys *s, int text, const uint8_t *x, size_t len, uint8_t out[16])
+{
+    memset(out, 0, 16);
+    if (text && !len) return;
+    memcpy(out, text ? s->k2 : s->k1, 16);
+    if (len) { cmac_continue(k, s, out, x, len); return; }
+    out[0] ^= 0x80;
+    xor16(out, out, s->k2);
+    uaesh_encrypt(k->ek, k->nr, out, out);
+}
+
+/* decrypt: in = ct || 4-byte mac; the mac is checked first and `out` stays untouched on 0x1A */
+int uaesh_eaxp(const uaesh_key *k, int decrypt, const uint8_t *nonce, size_t nonce_len, const uint8_t *in, size_t len, uint8_t *out)
+{
+    cmac_keys s;
+    uint8_t n[16], c[16], mac[4];
+    int i, rc = 0;
+    memset(s.k1, 0, 16);
+    uaesh_encrypt(k->ek, k->nr, s.k1, s.k1);
+    xts_double(s.k1);
+    memcpy(s.k2, s.k1, 16);
+    xts_double(s.k2);
+    eaxp_cmac(k, &s, 0, nonce, nonce_len, n);
+    memcpy(mac, n + 12, 4);
+    n[12] &= 0x7F;                                                      /* N' (:1581-1582) */
+    n[14] &= 0x7F;
+    if (decrypt) {
+        eaxp_cmac(k, &s, 1, in, len, c);
+        for (i = 0; i < 4; ++i) mac[i] ^= c[12 + i];
+        if (differ(mac, in + len, 4)) rc = 0x1A;
+        else uaesh_ctr(k, n, 0, in, len, out);
+    } else {
+        uaesh_ctr(k, n, 0, in, len, out);
+        eaxp_cmac(k, &s, 1, out, len, c);
+        for (i = 0; i < 4; ++i) out[len + i] = mac[i] ^ c[12 + i];
+    }
+    memset(&s, 0, sizeof s);
+    memset(n, 0, sizeof n);
+    return rc;
+}
+
 /* V = S2V(S_1 .. S_nad, p), RFC 5297 section 2.4: the nad components lie back to back at aad, ad_lens[i] bytes each; an
  * empty one is a component all the same (CMAC("") = Enc(10* ^ K2)), nad == 0 is no header unit at all.  Y is XORed
  * into the last 16 bytes of a text of 16 bytes or more, a shorter one gets dbl(Y) ^ pad(p) */

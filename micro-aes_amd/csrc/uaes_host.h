@@ -47,6 +47,9 @@ int  uaesh_ccm(const uaesh_key *k, int decrypt, const uint8_t *nonce, size_t non
  * ad_lens[i] bytes back to back (RFC 5297's vector; the reference's one aData is nad = aDataLen ? 1 : 0)        */
 int  uaesh_eax(const uaesh_key *k, int decrypt, const uint8_t *nonce, size_t nonce_len, size_t tag_len,
                const uint8_t *aad, size_t aad_len, const uint8_t *in, size_t len, uint8_t *out);            /* :1560-1648 */
+/* EAX' (the reference built with EAXP 1): any nonce length, a 4-byte mac (decrypt: in = ct || mac, `out` untouched on 0x1A) */
+int  uaesh_eaxp(const uaesh_key *k, int decrypt, const uint8_t *nonce, size_t nonce_len,
+                const uint8_t *in, size_t len, uint8_t *out);                                               /* :1523-1648 */
 int  uaesh_siv(const uaesh_key *k, const uaesh_key *kc, int decrypt, uint8_t iv[16], size_t nad, const size_t *ad_lens,
                const uint8_t *aad, const uint8_t *in, size_t len, uint8_t *out);                            /* :1323-1411 */
 

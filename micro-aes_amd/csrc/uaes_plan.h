@@ -43,6 +43,9 @@
  *         eax.long              k_eax_macs, CTR (k_ctr*) [, k_eax_macs C]           (3)    beyond (the counter block and the
  *                                                                                          verdict come back to the host)
  *         eax.batch             k_eax_batch (sixteen lanes per record)              (1)    uaes_eax_*_batch
+ *   EAX'  eaxp.small            k_eaxp_small (N, CTR, C'; decrypt: N || C', CTR)    (1)    text <= UAES_EAX_SIV_SMALL_MAX
+ *         eaxp.long             k_eaxp_macs, CTR (k_ctr*) [, k_eaxp_macs C']        (2-3)  beyond (as eax.long)
+ *         eaxp.batch            k_eaxp_batch (sixteen lanes per record; nlens, lens) (1)   uaes_eaxp_*_batch
  *   S2V   s2v.small             k_s2v_small (Y || lead blocks, then CTR)            (1)    text <= UAES_EAX_SIV_SMALL_MAX
  *         s2v.long              k_s2v_macs and CTR (k_ctr*), in either order        (2)    beyond
  *         s2v.batch             k_s2v_batch (sixteen lanes per record)              (1)    uaes_siv_*_batch
@@ -76,7 +79,7 @@
  * The Poly1305 rows have a planner of their own (uaesk_plan_poly1305, uaes_poly1305.hip) and ids outside enum
  * uaes_arrangement (uaes_debug_plan_poly1305 names them); a larger message never goes back to a smaller row.
  * So do the EAX and SIV (RFC 5297) rows (uaesk_plan_eax_siv and, for the .v rows, uaesk_plan_siv_v, uaes_eax_siv.hip;
- * uaes_debug_plan_eax_siv, uaes_debug_plan_siv_v), and the
+ * uaes_debug_plan_eax_siv, uaes_debug_plan_siv_v; the EAX' rows: uaesk_plan_eaxp, uaes_debug_plan_eaxp), and the
  * CBC / CFB / OFB / CMAC / CCM / batch rows (uaesk_plan_chain, uaes_chain.hip, and uaesk_plan_mac / uaesk_plan_ccm_batch,
  * uaes_mac.hip; uaes_debug_plan_chain); tests/test_gpu_chains.py derives its sizes and message counts from them.  Key wrap has
  * uaesk_plan_kw (uaes_kw.hip; uaes_debug_plan_kw), and tests/test_gpu_kw.py finds its two boundaries by walking it; key
@@ -94,7 +97,7 @@
  * cipher modes: uaesk_plan_cipher_batch (uaes_cipher_batch.hip; uaes_debug_plan_cipher_batch), and the XAES-256-GCM
  * batches: uaesk_plan_xaes_gcm_batch (uaes_xaes.hip; uaes_debug_plan_xaes256gcm_batch), and the XTS batches and sector
  * lists: uaesk_plan_xts_batch (uaes_xts_batch.hip; uaes_debug_plan_xts_batch).
- * The rows that say "sixteen lanes per record / message / unit" -- eax.batch, s2v.batch, ccm.batch, gcmsiv.batch, gcm.multikey, xaes.gcm, ocb.batch, batch.row,
+ * The rows that say "sixteen lanes per record / message / unit" -- eax.batch, eaxp.batch, s2v.batch, ccm.batch, gcmsiv.batch, gcm.multikey, xaes.gcm, ocb.batch, batch.row,
  * xts.batch, cipher.batch, kw.batch, kwp.batch, ff1.batch, ff3.batch -- are the row batches: grid and threads per workgroup are uaesk_row_shape's (uaes_launch.hip.h), the same
  * for the same number of records in every one of them.
  */
@@ -205,9 +208,12 @@ const char *uaesk_poly1305_arrangement_name(int id);
  * launches = kernels the call enqueues; grid = workgroups of the main kernel. */
 #define UAES_EAX_SIV_SMALL_MAX ((size_t)16384)
 enum uaes_eax_siv_arrangement { UAES_EAX_SMALL = 0, UAES_EAX_LONG, UAES_EAX_BATCH, UAES_S2V_SMALL, UAES_S2V_LONG, UAES_S2V_BATCH,
-                                UAES_S2V_SMALL_V, UAES_S2V_LONG_V, UAES_S2V_BATCH_V };
+                                UAES_S2V_SMALL_V, UAES_S2V_LONG_V, UAES_S2V_BATCH_V, UAES_EAXP_SMALL, UAES_EAXP_LONG, UAES_EAXP_BATCH };
 int uaesk_plan_eax_siv(int siv, int dir, size_t len, size_t nmsg, uaes_plan *p);
 const char *uaesk_eax_siv_arrangement_name(int id);
+/* EAX' (uaes_eaxp_*): the same boundary and the same three forms; it has no associated data, so a longer decryption is
+ * two launches and a longer encryption three.  Returns a HIP error code for a dir other than 0 / 1. */
+int uaesk_plan_eaxp(int dir, size_t len, size_t nmsg, uaes_plan *p);
 /* SIV with a vector of associated data (uaes_siv_*_v, uaes_siv_*_batch_v): the same boundary, with nad components of
  * associated data, at most UAES_S2V_AD_MAX in a single call (RFC 5297: S2V takes 127 strings, the text included) and
  * UAES_S2V_BATCH_AD_MAX in a batch record (their lengths travel by value).  steps = the rows of the workgroup the

@@ -56,6 +56,10 @@ walk("Poly1305-AES, batches of k messages of 1 KiB", lambda k: uaes.poly1305_pla
 print("EAX / SIV (RFC 5297): one launch up to UAES_EAX_SIV_SMALL_MAX = %d bytes of text" % uaes.eax_siv_plan(False, 0)[3])
 walk("EAX encrypt", lambda n: uaes.eax_siv_plan(False, n)[:2] + (0, 0), 0, 64 * MIB)
 walk("EAX decrypt", lambda n: uaes.eax_siv_plan(False, n, decrypt=True)[:2] + (0, 0), 0, 64 * MIB)
+walk("EAX' encrypt", lambda n: uaes.eaxp_plan(n)[:2] + (0, 0), 0, 64 * MIB)
+walk("EAX' decrypt", lambda n: uaes.eaxp_plan(n, decrypt=True)[:2] + (0, 0), 0, 64 * MIB)
+walk("EAX' batch, k records of 64 bytes", lambda k: uaes.eaxp_plan(64, max(k, 2))[:2] + (0, 0), 2, 1 << 20, 1,
+     lambda k: "%9d records (%9.3f MiB)" % (k, k * 64 / MIB))
 walk("SIV (RFC 5297)", lambda n: uaes.eax_siv_plan(True, n)[:2] + (0, 0), 0, 64 * MIB)
 print("SIV with a vector of associated data: the components of one call are dealt over %d rows of sixteen lanes" % uaes.siv_v_plan(0, 1)[3])
 for dec in (False, True):
